@@ -14,8 +14,15 @@ round 3's figure) - INCLUDING the hand-over of the results: the decoded transpor
 memory (N = 1) or gathered to rank 0 with ONE collective per batch (N > 1: RCCL gather over xGMI; the
 reference's sf_worker pool handing TBs to the one MAC, srsenb/src/phy/phy.cc:113-148) and copied to rank 0's host memory.
 The decode itself shards by UE with no collective: rank r decodes UE r (RNTI 0x1234+r, cell id 1+r), so scaling is weak.
-The timed region of the contract (K steps between barriers) is a few milliseconds, so it is REPEATED until >= 0.5 s have
-been timed; `value` / `ms_per_step` are the median repeat, the spread is in `config.repeat_*`. Rank 0 prints ONE JSON line.
+The timed region of the contract is K steps between two barriers, run once after the warm-up: `--steps` is the number of timed
+steps. By default every figure on the line - `value` / `ms_per_step`, `steady_state` (the difference of one 4 K-step region and one
+K-step region), `config.same_input_value`, `config.full_iter`, and --grants-mix's `value` - is therefore ONE sample of a region of a few milliseconds.
+`--min-timed-s S` repeats each region until S seconds (S / 2 for the others) have been timed; the figures are then median repeats
+and the spread of the headline region is in `config.repeat_*`. Rank 0 prints ONE JSON line.
+`--dump-outputs DIR` writes what step K - 1 of the first timed region (the last timed step, unless --min-timed-s repeats the region)
+delivered to rank 0's host memory - every rank's decoded transport blocks and CRC flags - as DIR/transport_blocks.npy and
+DIR/crc_ok.npy (float32). Its input batch does not depend on the timing and the inputs are seeded, so two runs or two builds with
+the same arguments can be compared output for output.
 
 Extra objects on that line:
   roofline      dominant kernel (turbo decoder). It is a serial-trellis integer kernel: bound by VALU issue, not by HBM
@@ -117,6 +124,25 @@ def fftw_probe(n_fft=1536, per_sf=14, seconds=0.5):
         return None
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, rec, ok_off, tb_stride, batch):
+    """--dump-outputs: rank 0's host record of one step ([ranks][record bytes]) as DIR/transport_blocks.npy ([ranks][batch][TBS/8] bytes)
+    and DIR/crc_ok.npy ([ranks][batch]), in float32. Past DUMP_MAX_BYTES the transport blocks are a fixed sample of subframes, listed in
+    DIR/transport_blocks_subframes.npy."""
+    os.makedirs(path, exist_ok=True)
+    tb = rec[:, :ok_off].reshape(rec.shape[0], batch, tb_stride)[:, :, :TBS // 8]
+    ok = rec[:, ok_off:ok_off + batch]
+    keep = max(1, (DUMP_MAX_BYTES - 4 * ok.size) // (4 * tb.shape[0] * tb.shape[2]))
+    if keep < batch:
+        sel = np.sort(np.random.default_rng(0).choice(batch, keep, replace=False))
+        tb = tb[:, sel]
+        np.save(os.path.join(path, "transport_blocks_subframes.npy"), sel.astype(np.float32))
+    np.save(os.path.join(path, "transport_blocks.npy"), tb.astype(np.float32))
+    np.save(os.path.join(path, "crc_ok.npy"), ok.astype(np.float32))
+
+
 def cpu_model():
     try:
         with open("/proc/cpuinfo") as f:
@@ -194,7 +220,8 @@ def main():
     ap.add_argument("--snr", type=float, default=18.0, help="AWGN SNR in dB (18 dB ~ 20 %% BLER for MCS 28)")
     ap.add_argument("--snr-full", type=float, default=14.0, help="SNR of the companion run in which every code block needs all 6 passes")
     ap.add_argument("--batch", type=int, default=BATCH)
-    ap.add_argument("--min-timed-s", type=float, default=0.5, help="repeat the K-step timed region until this much has been timed")
+    ap.add_argument("--min-timed-s", type=float, default=0.0, help="repeat the K-step timed region until this much has been timed (0: once)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the transport blocks and CRC flags of the first timed region's last step to DIR/*.npy")
     ap.add_argument("--cpu-seconds", type=float, default=6.0, help="CPU-baseline time budget per leg (one core; all cores)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-full", action="store_true", help="skip the all-6-passes companion run")
@@ -232,6 +259,8 @@ def main():
     if args.grants_mix:
         if args.gpus != 1:
             raise SystemExit("--grants-mix is a one-GPU side workload")
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs covers the flagship workload, not --grants-mix")
         sys.path.insert(0, os.path.join(ROOT, "scripts"))
         return importlib.import_module("bench_grants_mix").main(args)
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -409,9 +438,10 @@ def main():
 
     issue_s = []
 
-    def timed_repeats(src, min_s, with_events, nsteps=None):
+    def timed_repeats(src, min_s, with_events, nsteps=None, after_first=None):
         """Repeats of the contract's timed region: K steps between barriers. Returns (per-repeat max-over-ranks seconds, mean tdec ms).
-        nsteps: a region of another length (the steady-state figure)."""
+        nsteps: a region of another length (the steady-state figure). after_first: called between the first repeat and the next, outside
+        the timed intervals."""
         nsteps = nsteps or args.steps
         evs = [(L.srslte_hip_event_create(), L.srslte_hip_event_create()) for _ in range(nsteps)] if (with_events and grant_arr is None) else None
         times, tdec = [], []
@@ -435,6 +465,8 @@ def main():
                 done = sum(times) >= min_s
             if evs:
                 tdec.append(float(np.mean([L.srslte_hip_event_elapsed_ms(a, b) for a, b in evs])))
+            if after_first is not None and len(times) == 1:
+                after_first()
             if done or len(times) >= 2000:
                 break
         return times, (float(np.mean(tdec)) if tdec else None)
@@ -445,7 +477,10 @@ def main():
     # timed region ran at half speed), so whole untimed repeats follow until 0.15 s have passed
     timed_repeats(d_inputs, 0.15, False)
     del issue_s[:]
-    times, tdec_ms = timed_repeats(d_inputs, args.min_timed_s, pool is None)  # pool mode: one call per batch, no per-stage events
+    # --dump-outputs: the record of step K - 1 of the FIRST region (input batch (K - 1) mod --inputs), taken before the next repeat reuses it:
+    # the same step whatever number of repeats --min-timed-s needs, and the last timed step when the region runs once
+    dump = (lambda: dump_outputs(args.dump_outputs, h_out[(args.steps - 1) % nstreams].numpy(), ok_off, tb_stride, B)) if (args.dump_outputs and rank == 0) else None
+    times, tdec_ms = timed_repeats(d_inputs, args.min_timed_s, pool is None, after_first=dump)  # pool mode: one call per batch, no per-stage events
     t_med = float(np.median(times))
     host_issue_ms = float(np.median(issue_s)) * 1e3
     # What the K-step region costs beyond K steps of a pipeline that never drains: the same loop over 4 K steps per region; the slope between the

@@ -10,6 +10,7 @@ ctypes mirrors of the reference structs used by the parity harness follow the re
 (lib/include/srslte/phy/common/phy_common.h:195-212, ch_estimation/chest_dl.h:49-130).
 """
 import ctypes as C
+import json
 import os
 import subprocess
 
@@ -216,17 +217,13 @@ def ref_ul_sf_cfg(tti):
     return buf
 
 
-_ref_layout_cache = {}
+REF_INC = "/root/reference/lib/include"
+REF_ABI = os.path.join(ROOT, "tests", "golden", "ref_abi.json")
 
 
-def ref_layout(structs, includes):
-    """{"struct": [fields]} -> {"struct": sizeof, "struct.field": offsetof} from the REFERENCE headers (compiled on the fly with gcc;
-    only where /root/reference exists). For driving reference functions that take configuration structs by pointer."""
-    import subprocess
+def struct_layout(structs, includes, incdirs):
+    """{"struct": [fields]} -> {"struct": sizeof, "struct.field": offsetof} of the given headers, compiled on the fly with gcc."""
     import tempfile
-    key = repr((sorted((k, tuple(v)) for k, v in structs.items()), tuple(includes)))
-    if key in _ref_layout_cache:
-        return _ref_layout_cache[key]
     body = "".join('  printf("%s %%zu\\n", sizeof(%s));\n' % (st, st) + "".join('  printf("%s.%s %%zu\\n", offsetof(%s, %s));\n' % (st, f, st, f) for f in fs)
                    for st, fs in structs.items())
     src = "#include <stdio.h>\n#include <stddef.h>\n" + "".join('#include "%s"\n' % i for i in includes) + "int main(void) {\n" + body + "  return 0;\n}\n"
@@ -234,7 +231,20 @@ def ref_layout(structs, includes):
         c, exe = os.path.join(d, "l.c"), os.path.join(d, "l")
         with open(c, "w") as f:
             f.write(src)
-        subprocess.check_call(["gcc", "-std=c99", "-D_GNU_SOURCE", "-w", "-I/root/reference/lib/include", c, "-o", exe])
-        out = {a: int(b) for a, b in (line.split() for line in subprocess.check_output([exe]).decode().splitlines())}
-    _ref_layout_cache[key] = out
-    return out
+        subprocess.check_call(["gcc", "-std=c99", "-D_GNU_SOURCE", "-w"] + ["-I" + i for i in incdirs] + [c, "-o", exe])
+        return {a: int(b) for a, b in (line.split() for line in subprocess.check_output([exe]).decode().splitlines())}
+
+
+def ref_layout(structs, includes):
+    """{"struct": [fields]} -> {"struct": sizeof, "struct.field": offsetof} of the REFERENCE headers, as stored in tests/golden/ref_abi.json
+    (written by tests/gen_golden.py --abi-only where the reference tree exists; `includes` name the headers it was taken from). For driving
+    reference functions that take configuration structs by pointer."""
+    if "abi" not in _cache:
+        with open(REF_ABI) as f:
+            _cache["abi"] = json.load(f)
+    stored = _cache["abi"]["layouts"]
+    names = [st for st in structs] + ["%s.%s" % (st, f) for st, fs in structs.items() for f in fs]
+    missing = [n for n in names if n not in stored]
+    if missing:
+        raise KeyError("%s: not in tests/golden/ref_abi.json (%s); regenerate it with tests/gen_golden.py --abi-only" % (missing, ", ".join(includes)))
+    return {n: stored[n] for n in names}

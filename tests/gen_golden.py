@@ -5,11 +5,16 @@ sources under /root/reference) and from the known-answer data the reference's ow
 
     make -C oracle ref && python tests/gen_golden.py
 
+`--abi-only` writes tests/golden/ref_abi.json alone, from the reference headers and nothing built: sizeof / offsetof of the reference
+structs that tests/test_abi_layout.py compares and that tests/lte_sim.py and tests/test_oracle_vs_ref.py fill (tests/lte_sim.py:
+REF_LAYOUTS), and the names of the boundary headers' SRSLTE_API prototypes.
+
 A fixture is inputs + expected outputs; no reference source text is stored. The seeded inputs are regenerated here, the
 expected outputs come from reference code. tests/test_oracle_golden.py pins the oracle to them on any machine and
 tests/test_gpu_golden.py checks the HIP path against the same files.
 """
 import ctypes as C
+import json
 import os
 import re
 import sys
@@ -405,7 +410,22 @@ def ul_extcp():
     print("ul_extcp.npz", os.path.getsize(os.path.join(OUT, "ul_extcp.npz")), "bytes")
 
 
+def ref_abi():
+    import test_abi_layout as T
+    from _libs import REF_ABI, REF_INC, struct_layout
+    from lte_sim import REF_LAYOUTS
+    layouts = struct_layout(T.STRUCTS, T.REF_HEADERS, [REF_INC])
+    for structs, includes in REF_LAYOUTS:
+        layouts.update(struct_layout(structs, includes, [REF_INC]))
+    with open(REF_ABI, "w") as f:
+        json.dump({"layouts": dict(sorted(layouts.items())), "boundary_prototypes": T.boundary_prototypes_from_headers()}, f, indent=0)
+        f.write("\n")
+
+
 if __name__ == "__main__":
+    if "--abi-only" in sys.argv:
+        ref_abi()
+        sys.exit(0)
     if "--round4-only" in sys.argv:
         pmch()
         ul_extcp()

@@ -382,6 +382,38 @@ def oracle_rx(cfg, iq, tti, keep=False, grid_in=None, harq=None, rv=0, new_data=
     return out
 
 
+# the reference structs the Ref* drivers below fill by offset: (structs and fields, headers they come from); the offsets are stored in
+# tests/golden/ref_abi.json (tests/gen_golden.py --abi-only), so the drivers need the reference's compiled code, not its headers
+REF_LAYOUT_PDSCH_RX = ({"srslte_pdsch_t": ["llr_is_8bit", "d", "e", "csi", "dl_sch"], "srslte_sch_t": ["llr_is_8bit"],
+                       "srslte_pdsch_cfg_t": ["rnti", "max_nof_iterations", "decoder_type", "csi_enable", "softbuffers", "p_a", "p_b", "power_scale"],
+                       "srslte_pdsch_grant_t": ["tx_scheme", "pmi", "prb_idx", "nof_prb", "nof_re", "nof_symb_slot", "tb", "nof_tb", "nof_layers"],
+                       "srslte_ra_tb_t": ["mod", "tbs", "rv", "nof_bits", "cw_idx", "enabled"],
+                       "srslte_softbuffer_rx_t": [], "srslte_pdsch_res_t": ["payload", "crc"]}, ["srslte/phy/phch/pdsch.h"])
+REF_LAYOUT_PMCH_RX = ({"srslte_pmch_t": ["d", "e"], "srslte_pmch_cfg_t": ["pdsch_cfg", "area_id"],
+                      "srslte_pdsch_cfg_t": ["max_nof_iterations", "softbuffers"],
+                      "srslte_pdsch_grant_t": ["prb_idx", "nof_prb", "nof_re", "tb", "nof_tb", "nof_layers"],
+                      "srslte_ra_tb_t": ["mod", "tbs", "rv", "nof_bits", "cw_idx", "enabled"],
+                      "srslte_softbuffer_rx_t": [], "srslte_softbuffer_tx_t": [], "srslte_pdsch_res_t": ["payload", "crc"]},
+                      ["srslte/phy/phch/pmch.h"])
+REF_LAYOUT_PDSCH_TX = ({"srslte_pdsch_t": [], "srslte_pdsch_cfg_t": ["rnti", "softbuffers"],
+                       "srslte_pdsch_grant_t": ["tx_scheme", "pmi", "prb_idx", "nof_prb", "nof_re", "nof_symb_slot", "tb", "nof_tb", "nof_layers"],
+                       "srslte_ra_tb_t": ["mod", "tbs", "rv", "nof_bits", "cw_idx", "enabled"], "srslte_softbuffer_tx_t": []},
+                       ["srslte/phy/phch/pdsch.h"])
+REF_LAYOUT_ULSCH = ({"srslte_sch_t": [], "srslte_pusch_cfg_t": ["grant", "max_nof_iterations", "softbuffers", "uci_cfg", "uci_offset"],
+                    "srslte_uci_cfg_t": ["ack", "cqi"], "srslte_uci_cfg_ack_t": ["nof_acks"], "srslte_cqi_cfg_t": ["ri_len", "data_enable", "N", "type"],
+                    "srslte_uci_offset_cfg_t": ["I_offset_ack", "I_offset_ri", "I_offset_cqi"],
+                    "srslte_uci_value_t": ["ack", "ri", "cqi"], "srslte_uci_value_ack_t": ["ack_value"],
+                    "srslte_cqi_value_t": ["data_crc", "wideband.wideband_cqi", "subband_hl.wideband_cqi_cw0", "subband_hl.subband_diff_cqi_cw0"],
+                    "srslte_pusch_grant_t": ["L_prb", "nof_re", "nof_symb", "tb"],
+                    "srslte_ra_tb_t": ["mod", "tbs", "rv", "nof_bits", "enabled"],
+                    "srslte_softbuffer_rx_t": [], "srslte_softbuffer_tx_t": []}, ["srslte/phy/ch_estimation/chest_ul.h", "srslte/phy/phch/pusch.h"])
+# ... and single offsets tests/test_oracle_vs_ref.py reads
+REF_LAYOUT_REFSIGNAL = ({"srslte_refsignal_t": ["pilots"]}, ["srslte/phy/ch_estimation/refsignal_dl.h"])
+REF_LAYOUT_SCH = ({"srslte_sch_t": ["llr_is_8bit"]}, ["srslte/phy/phch/sch.h"])
+REF_LAYOUT_PUSCH_CFG = ({"srslte_pusch_cfg_t": ["K_segm", "grant.L_prb", "grant.nof_symb", "grant.tb.mod"]}, ["srslte/phy/phch/pusch_cfg.h"])
+REF_LAYOUTS = (REF_LAYOUT_PDSCH_RX, REF_LAYOUT_PMCH_RX, REF_LAYOUT_PDSCH_TX, REF_LAYOUT_ULSCH, REF_LAYOUT_REFSIGNAL, REF_LAYOUT_SCH, REF_LAYOUT_PUSCH_CFG)
+
+
 class RefRx:
     """UE receive chain on the REFERENCE's own compiled code (oracle/_ref/libsrslte_ref.so) for every stage it holds:
     srslte_chest_dl_estimate_cfg, srslte_predecoding_single, srslte_demod_soft_demodulate_s, srslte_rm_turbo_rx_lut,
@@ -482,11 +514,7 @@ class RefPdsch:
         from _libs import RefCell, RefChestCfg, RefChestRes, RefDlSfCfg, aligned, opaque, ref, ref_layout
         R = self.R = lib if lib is not None else ref()
         self.cfg, self.aligned = cfg, aligned
-        L = self.L = ref_layout({"srslte_pdsch_t": ["llr_is_8bit", "d", "e", "csi", "dl_sch"], "srslte_sch_t": ["llr_is_8bit"],
-                                 "srslte_pdsch_cfg_t": ["rnti", "max_nof_iterations", "decoder_type", "csi_enable", "softbuffers", "p_a", "p_b", "power_scale"],
-                                 "srslte_pdsch_grant_t": ["tx_scheme", "pmi", "prb_idx", "nof_prb", "nof_re", "nof_symb_slot", "tb", "nof_tb", "nof_layers"],
-                                 "srslte_ra_tb_t": ["mod", "tbs", "rv", "nof_bits", "cw_idx", "enabled"],
-                                 "srslte_softbuffer_rx_t": [], "srslte_pdsch_res_t": ["payload", "crc"]}, ["srslte/phy/phch/pdsch.h"])
+        L = self.L = ref_layout(*REF_LAYOUT_PDSCH_RX)
         cell = RefCell(cfg.nof_prb, cfg.nof_ports, cfg.cell_id, 1 if cfg.cp_ext else 0, 0, 0, 1 if cfg.tdd else 0)  # srslte_cp_t NORM 0 / EXT 1; frame type FDD 0 / TDD 1
         self.chest = opaque(1 << 20)
         assert R.srslte_chest_dl_init(self.chest, cfg.nof_prb, cfg.nof_rx) == 0 and R.srslte_chest_dl_set_cell(self.chest, cell) == 0
@@ -752,12 +780,7 @@ class RefPmch:
         from _libs import RefCell, RefChestCfg, RefChestRes, RefDlSfCfg, aligned, opaque, ref, ref_layout
         R = self.R = ref()
         self.cfg, self.aligned = cfg, aligned
-        L = self.L = ref_layout({"srslte_pmch_t": ["d", "e"], "srslte_pmch_cfg_t": ["pdsch_cfg", "area_id"],
-                                 "srslte_pdsch_cfg_t": ["max_nof_iterations", "softbuffers"],
-                                 "srslte_pdsch_grant_t": ["prb_idx", "nof_prb", "nof_re", "tb", "nof_tb", "nof_layers"],
-                                 "srslte_ra_tb_t": ["mod", "tbs", "rv", "nof_bits", "cw_idx", "enabled"],
-                                 "srslte_softbuffer_rx_t": [], "srslte_softbuffer_tx_t": [], "srslte_pdsch_res_t": ["payload", "crc"]},
-                                ["srslte/phy/phch/pmch.h"])
+        L = self.L = ref_layout(*REF_LAYOUT_PMCH_RX)
         cell = RefCell(cfg.nof_prb, 1, cfg.cell_id, 1 if cfg.cp_ext else 0, 0, 0, 0)
         self.chest = opaque(1 << 20)
         assert R.srslte_chest_dl_init(self.chest, cfg.nof_prb, cfg.nof_rx) == 0 and R.srslte_chest_dl_set_cell(self.chest, cell) == 0
@@ -853,10 +876,7 @@ class RefPdschTx:
         from _libs import RefCell, RefDlSfCfg, aligned, opaque, ref, ref_layout
         R = self.R = ref()
         self.cfg, self.aligned = cfg, aligned
-        L = self.L = ref_layout({"srslte_pdsch_t": [], "srslte_pdsch_cfg_t": ["rnti", "softbuffers"],
-                                 "srslte_pdsch_grant_t": ["tx_scheme", "pmi", "prb_idx", "nof_prb", "nof_re", "nof_symb_slot", "tb", "nof_tb", "nof_layers"],
-                                 "srslte_ra_tb_t": ["mod", "tbs", "rv", "nof_bits", "cw_idx", "enabled"], "srslte_softbuffer_tx_t": []},
-                                ["srslte/phy/phch/pdsch.h"])
+        L = self.L = ref_layout(*REF_LAYOUT_PDSCH_TX)
         cell = RefCell(cfg.nof_prb, cfg.nof_ports, cfg.cell_id, 1 if cfg.cp_ext else 0, 0, 0, 0)
         self.q = opaque(L["srslte_pdsch_t"] + 64)
         assert R.srslte_pdsch_init_enb(self.q, cfg.nof_prb) == 0 and R.srslte_pdsch_set_cell(self.q, cell) == 0
@@ -1253,14 +1273,7 @@ class RefUlsch:
         from _libs import opaque, ref, ref_layout
         R = self.R = ref()
         self.cfg = cfg
-        L = self.L = ref_layout({"srslte_sch_t": [], "srslte_pusch_cfg_t": ["grant", "max_nof_iterations", "softbuffers", "uci_cfg", "uci_offset"],
-                                 "srslte_uci_cfg_t": ["ack", "cqi"], "srslte_uci_cfg_ack_t": ["nof_acks"], "srslte_cqi_cfg_t": ["ri_len", "data_enable", "N", "type"],
-                                 "srslte_uci_offset_cfg_t": ["I_offset_ack", "I_offset_ri", "I_offset_cqi"],
-                                 "srslte_uci_value_t": ["ack", "ri", "cqi"], "srslte_uci_value_ack_t": ["ack_value"],
-                                 "srslte_cqi_value_t": ["data_crc", "wideband.wideband_cqi", "subband_hl.wideband_cqi_cw0", "subband_hl.subband_diff_cqi_cw0"],
-                                 "srslte_pusch_grant_t": ["L_prb", "nof_re", "nof_symb", "tb"],
-                                 "srslte_ra_tb_t": ["mod", "tbs", "rv", "nof_bits", "enabled"],
-                                 "srslte_softbuffer_rx_t": [], "srslte_softbuffer_tx_t": []}, ["srslte/phy/ch_estimation/chest_ul.h", "srslte/phy/phch/pusch.h"])
+        L = self.L = ref_layout(*REF_LAYOUT_ULSCH)
         self.q = opaque(L["srslte_sch_t"] + 64)
         assert R.srslte_sch_init(self.q) == 0
         R.srslte_sch_set_max_noi.argtypes = [C.c_void_p, C.c_uint32]

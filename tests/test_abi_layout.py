@@ -1,16 +1,11 @@
 """sizeof/offsetof of every public struct in include/srslte_hip/srslte_compat.h against the reference headers.
 Callers embed these structs by value and poke their fields, so the layouts must be identical.
-Needs the reference headers: skipped where /root/reference is absent (the GPU box)."""
+The reference's side is stored in tests/golden/ref_abi.json (tests/gen_golden.py --abi-only); where the reference headers are present the
+stored data is checked against them too."""
+import json
 import os
-import subprocess
-import tempfile
 
-import pytest
-
-from _libs import ROOT
-
-REF_INC = "/root/reference/lib/include"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_INC), reason="reference headers not available")
+from _libs import REF_ABI, REF_INC, ROOT, struct_layout
 
 STRUCTS = {
     "srslte_cell_t": ["nof_prb", "nof_ports", "id", "cp", "phich_length", "phich_resources", "frame_type"],
@@ -50,22 +45,34 @@ STRUCTS = {
 }
 
 
-def layout(includes, incdirs):
-    body = "\n".join('  printf("%s %%zu\\n", sizeof(%s));\n' % (s, s) + "".join('  printf("%s.%s %%zu\\n", offsetof(%s, %s));\n' % (s, f, s, f) for f in fs)
-                     for s, fs in STRUCTS.items())
-    src = "#include <stdio.h>\n#include <stddef.h>\n" + "".join('#include "%s"\n' % i for i in includes) + "int main(void) {\n" + body + "  return 0;\n}\n"
-    with tempfile.TemporaryDirectory() as d:
-        c, exe = os.path.join(d, "l.c"), os.path.join(d, "l")
-        open(c, "w").write(src)
-        subprocess.check_call(["gcc", "-std=c99", "-D_GNU_SOURCE", "-w"] + ["-I" + i for i in incdirs] + [c, "-o", exe])
-        return dict(line.split() for line in subprocess.check_output([exe]).decode().splitlines())
+REF_HEADERS = ["srslte/phy/dft/ofdm.h", "srslte/phy/dft/dft_precoding.h", "srslte/phy/fec/cbsegm.h", "srslte/phy/fec/tc_interl.h",
+               "srslte/phy/fec/turbocoder.h", "srslte/phy/fec/turbodecoder.h", "srslte/phy/ch_estimation/chest_dl.h", "srslte/phy/phch/sch.h"]
+# the eleven headers the boundary names
+BOUNDARY_HEADERS = ["dft/dft", "dft/ofdm", "dft/dft_precoding", "fec/turbocoder", "fec/turbodecoder", "fec/tc_interl", "fec/cbsegm",
+                    "ch_estimation/chest_dl", "ch_estimation/chest_common", "ch_estimation/refsignal_dl", "modem/demod_soft"]
+
+
+def boundary_prototypes_from_headers():
+    import re
+    names = set()
+    for h in BOUNDARY_HEADERS:
+        src = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(REF_INC, "srslte/phy", h + ".h")).read(), flags=re.S)
+        names.update(re.findall(r"SRSLTE_API\s+[^;{(]*?\b(srslte_[A-Za-z0-9_]+)\s*\(", src))
+    return sorted(names)
+
+
+def stored_abi():
+    with open(REF_ABI) as f:
+        return json.load(f)
 
 
 def test_struct_layouts_match_reference():
-    ref = layout(["srslte/phy/dft/ofdm.h", "srslte/phy/dft/dft_precoding.h", "srslte/phy/fec/cbsegm.h", "srslte/phy/fec/tc_interl.h",
-                  "srslte/phy/fec/turbocoder.h", "srslte/phy/fec/turbodecoder.h", "srslte/phy/ch_estimation/chest_dl.h", "srslte/phy/phch/sch.h"],
-                 [REF_INC])
-    ours = layout(["srslte_hip/srslte_compat.h"], [os.path.join(ROOT, "include")])
+    stored = stored_abi()["layouts"]
+    names = list(STRUCTS) + ["%s.%s" % (st, f) for st, fs in STRUCTS.items() for f in fs]
+    ref = {k: stored[k] for k in names}
+    if os.path.isdir(REF_INC):
+        assert struct_layout(STRUCTS, REF_HEADERS, [REF_INC]) == ref, "tests/golden/ref_abi.json is stale: tests/gen_golden.py --abi-only"
+    ours = struct_layout(STRUCTS, ["srslte_hip/srslte_compat.h"], [os.path.join(ROOT, "include")])
     diff = {k: (ref[k], ours.get(k)) for k in ref if ref[k] != ours.get(k)}
     assert not diff, "layout differences (reference, ours): %s" % diff
 
@@ -74,14 +81,10 @@ def test_every_prototype_of_the_boundary_headers_is_exported():
     """'every SRSLTE_API prototype' of the eleven headers the boundary names - all of them, by name, in the product library
     (plus srslte_tc_interl_UMTS_gen, which row a6 cites and no header declares)."""
     import ctypes
-    import re
     from _libs import HIP_SO
-    heads = ["dft/dft", "dft/ofdm", "dft/dft_precoding", "fec/turbocoder", "fec/turbodecoder", "fec/tc_interl", "fec/cbsegm",
-             "ch_estimation/chest_dl", "ch_estimation/chest_common", "ch_estimation/refsignal_dl", "modem/demod_soft"]
-    names = set()
-    for h in heads:
-        src = re.sub(r"/\*.*?\*/|//[^\n]*", "", open(os.path.join(REF_INC, "srslte/phy", h + ".h")).read(), flags=re.S)
-        names.update(re.findall(r"SRSLTE_API\s+[^;{(]*?\b(srslte_[A-Za-z0-9_]+)\s*\(", src))
+    names = set(stored_abi()["boundary_prototypes"])
+    if os.path.isdir(REF_INC):
+        assert sorted(names) == boundary_prototypes_from_headers(), "tests/golden/ref_abi.json is stale: tests/gen_golden.py --abi-only"
     assert len(names) >= 100, len(names)
     lib = ctypes.CDLL(HIP_SO)
     missing = sorted(n for n in names | {"srslte_tc_interl_UMTS_gen"} if not hasattr(lib, n))

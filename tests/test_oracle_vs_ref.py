@@ -6,7 +6,8 @@ import numpy as np
 import pytest
 
 from _libs import (OrcCell, OrcChestCfg, OrcChestRes, RefCell, RefChestCfg, RefChestRes, RefDlSfCfg, acopy, aligned, opaque, oracle, p, ref)
-from lte_sim import DlConfig, RefRx, RefUlRx, UlConfig, make_subframe, make_ul_subframe, oracle_rx, oracle_ul_rx
+from lte_sim import (REF_LAYOUT_PUSCH_CFG, REF_LAYOUT_REFSIGNAL, REF_LAYOUT_SCH, DlConfig, RefRx, RefUlRx, UlConfig, make_subframe, make_ul_subframe,
+                     oracle_rx, oracle_ul_rx)
 
 pytestmark = pytest.mark.skipif(ref() is None, reason="oracle/_ref/libsrslte_ref.so not built")
 orc = oracle()
@@ -539,7 +540,7 @@ def test_chest_dl_mbsfn_vs_ref(prb, cid, area, port):
         rs = opaque(4096)
         assert R.srslte_refsignal_mbsfn_init(rs, prb) == 0 and R.srslte_refsignal_mbsfn_set_cell(rs, RefCell(prb, nports, cid, 0, 0, 0, 0), area) == 0
         from _libs import ref_layout
-        off = ref_layout({"srslte_refsignal_t": ["pilots"]}, ["srslte/phy/ch_estimation/refsignal_dl.h"])["srslte_refsignal_t.pilots"]
+        off = ref_layout(*REF_LAYOUT_REFSIGNAL)["srslte_refsignal_t.pilots"]
         pil_ptr = C.cast(C.byref(rs, off), C.POINTER(C.c_void_p))
         ref_mb = np.frombuffer(C.string_at(pil_ptr[(port // 2) * 10 + sf_idx], 8 * 18 * prb), np.complex64)
         assert np.array_equal(ref_mb.view(np.float32), mb.view(np.float32)), "MBSFN pilot sequence"
@@ -1580,7 +1581,7 @@ def test_reference_8bit_pusch_receive_cannot_decode_a_clean_transmission():
     from _libs import ref_layout
     from lte_sim import RefUlsch, UlConfig
     cfg = UlConfig(50, 3, 2, 4008, 40, 0)
-    flag = ref_layout({"srslte_sch_t": ["llr_is_8bit"]}, ["srslte/phy/phch/sch.h"])["srslte_sch_t.llr_is_8bit"]
+    flag = ref_layout(*REF_LAYOUT_SCH)["srslte_sch_t.llr_is_8bit"]
     data = np.random.default_rng(8).integers(0, 256, cfg.tbs // 8, dtype=np.uint8)
     res = {}
     for llr8 in (False, True):
@@ -1925,7 +1926,7 @@ def test_pdsch_arbitrary_allocation_vs_reference(case):
 # ---------------------------------------------------------------- CQI / PMI report on the PUSCH (uci.c:264-494)
 def _ref_pusch_cfg(L_prb, nof_symb, mod, K_segm):
     from _libs import ref_layout
-    lay = ref_layout({"srslte_pusch_cfg_t": ["K_segm", "grant.L_prb", "grant.nof_symb", "grant.tb.mod"]}, ["srslte/phy/phch/pusch_cfg.h"])
+    lay = ref_layout(*REF_LAYOUT_PUSCH_CFG)
     buf = (C.c_uint8 * lay["srslte_pusch_cfg_t"])()
     u32 = C.cast(buf, C.POINTER(C.c_uint32))
     u32[lay["srslte_pusch_cfg_t.K_segm"] // 4], u32[lay["srslte_pusch_cfg_t.grant.L_prb"] // 4] = K_segm, L_prb
