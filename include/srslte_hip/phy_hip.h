@@ -294,8 +294,11 @@ int srslte_hip_dl_rx_grid_batch(srslte_hip_dl_rx_t* q, const void* d_grid, uint3
  * (pdsch.c:81-206). tbs = 0: no transport block in that subframe (tb_ok = 0). rv / new_data as srslte_hip_dl_rx_batch_harq, per subframe.
  * cfg.tbs of the object bounds every grant's tbs; cfg.mod / cfg.rnti / cfg.cfi are not used. Single antenna port or transmit diversity (cfg.nof_ports); cfg.llr_8bit, cfg.csi_enable
  * (csi_correction with every subframe's own allocation and modulation) and cfg.nof_rx_antennas apply.
+ * Every grant's tbs is at most 105528 bits (36.213 Table 7.1.7.2.1-1 at 110 PRB), a multiple of 8, and segments without filler bits and
+ * into code blocks of one size (srslte_cbsegm: F = 0, C2 = 0); other grants are refused with SRSLTE_ERROR_INVALID_INPUTS.
  * With 16-bit LLRs the transport blocks are assembled and judged by the decoder launch itself (no assembly kernel behind it; blocks kept from an
- * earlier transmission contribute their stored bytes). Environment SRSLTE_HIP_GRANTS_TB_DIRECT=0, read when an object serves its first grants
+ * earlier transmission contribute their stored bytes) when every transport block of the call has at most 16 code blocks; a call with a larger
+ * one has the separate assembly kernel do it for all of its transport blocks. Environment SRSLTE_HIP_GRANTS_TB_DIRECT=0, read when an object serves its first grants
  * call, keeps the separate assembly kernel (A/B, tests). Results are the same either way. */
 typedef struct {
   uint32_t prb_mask[2][4];

@@ -39,7 +39,9 @@ struct srslte_hip_dl_rx {
   int                    harq_combine;
   uint32_t*              d_tbcrc;
   cf32 *                 d_grid, *d_ce, *d_d;
-  const uint8_t*         direct_tb; // where the last decoder run (stage 4) assembled the transport blocks itself, or null: stage 5 has nothing to do then
+  const uint8_t*         direct_tb; // where the last decoder run (stage 4) assembled the transport blocks itself, or null: stage 5 has nothing to do then,
+  const uint8_t*         direct_ok; // if it is called with the same rows, verdicts, stride and subframe count as that run
+  uint32_t               direct_stride, direct_nof_sf;
   cf32*                  d_ce_full; // debug view of a compact d_ce (pg.ce_nre != 0) expanded to whole grids, made on request
   ChestResDev*           d_res;
   int16_t *              d_e, *d_w;
@@ -438,7 +440,7 @@ extern "C" int srslte_hip_dl_rx_stage(srslte_hip_dl_rx_t* q, int stage, const vo
       q->direct_tb = nullptr;
       if (dl_rx_tb_direct(q, d_tb, tb_stride, d_tb_ok)) {
         if (int r = tdec_set_tb_direct(q->tdec, d_tb, tb_stride, q->tg.rlen / 8, d_tb_ok)) return r;
-        q->direct_tb = d_tb;
+        q->direct_tb = d_tb; q->direct_ok = d_tb_ok; q->direct_stride = tb_stride; q->direct_nof_sf = nof_sf;
       }
       return tdec_run_batch_w(q->tdec, q->d_w, q->cfg.llr_8bit ? 1 : 0, q->in_stride, q->W != 0, K, -1, nof_sf * C, q->cfg.max_iterations,
                               C > 1 ? 0x1800063u : 0x1864CFBu, C > 1 ? K : q->cfg.tbs + 24, q->d_cb_bytes, K / 8, q->d_cb_iters, q->d_cb_ok, st);
@@ -447,7 +449,9 @@ extern "C" int srslte_hip_dl_rx_stage(srslte_hip_dl_rx_t* q, int stage, const vo
       if (q->cw1) { // rows nof_sf .. 2 nof_sf - 1 of d_tb / d_tb_ok: the second transport block of every subframe
         if (int r = srslte_hip_dl_rx_stage(q->cw1, 5, nullptr, tti0, nof_sf, d_tb + (size_t)nof_sf * tb_stride, tb_stride, d_tb_ok + nof_sf, stream)) return r;
       }
-      if (q->direct_tb && q->direct_tb == d_tb) return SRSLTE_SUCCESS; // stage 4 assembled these transport blocks and gave the verdicts
+      // stage 4 assembled these transport blocks and gave these verdicts; other outputs: the assembly kernel, from the blocks' bytes and CRC
+      // syndromes, which the decoders store in that mode as well
+      if (q->direct_tb && q->direct_tb == d_tb && q->direct_ok == d_tb_ok && q->direct_stride == tb_stride && q->direct_nof_sf == nof_sf) return SRSLTE_SUCCESS;
       TbGeom g    = q->tg;
       g.tb_stride = (int)tb_stride;
       g.iters     = q->d_cb_iters;

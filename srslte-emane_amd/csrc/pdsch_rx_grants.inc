@@ -473,10 +473,15 @@ static int grants_run(srslte_hip_dl_rx_t* q, const void* d_iq, uint32_t tti0, ui
     }
   }
   bd.fill_map(h_map);
-  // 16-bit LLRs: the decoders assemble the transport blocks themselves (a byte per slot: its block count)
-  const bool direct = !l8 && g->tb_direct;
-  uint8_t*   h_cof = g->h_pin[hs] + g->desc_bytes - ((V + 15) & ~15u);
-  for (uint32_t v = 0; v < V; v++) h_cof[v] = (uint8_t)h_sf[v].C;
+  // 16-bit LLRs: the decoders assemble the transport blocks themselves (a byte per slot: its block count), when none of the call's has more
+  // blocks than their CRC factor table covers (TDEC_TB_MAX_C_DIRECT)
+  uint8_t* h_cof = g->h_pin[hs] + g->desc_bytes - ((V + 15) & ~15u);
+  uint32_t max_C = 0;
+  for (uint32_t v = 0; v < V; v++) {
+    h_cof[v] = (uint8_t)h_sf[v].C;
+    if (v % B < nof_sf) max_C = std::max(max_C, (uint32_t)h_sf[v].C); // the other slots keep an earlier call's descriptors
+  }
+  const bool direct = !l8 && g->tb_direct && max_C <= TDEC_TB_MAX_C_DIRECT;
   const uint8_t* d_cof = direct ? g->d_desc + g->desc_bytes - ((V + 15) & ~15u) : nullptr;
   // stages 0, 1: OFDM demodulation and channel estimation do not depend on the grants
   int r = q->grid_in ? SRSLTE_SUCCESS : srslte_hip_dl_rx_stage(q, 0, d_iq, tti0, nof_sf, d_tb, tb_stride, d_tb_ok, stream); // grids from the caller: no OFDM stage

@@ -59,6 +59,9 @@ int tdec_set_tb_direct(srslte_hip_tdec_t* q, uint8_t* d_tb, uint32_t tb_stride, 
 // row v (v < B) or rows0 + v - B of d_tb / d_tb_ok
 int tdec_set_tb_ragged(srslte_hip_tdec_t* q, uint8_t* d_tb, uint32_t tb_stride, uint8_t* d_tb_ok, const uint8_t* d_Cof, uint32_t width, uint32_t B,
                        uint32_t rows0);
+// The largest block count of a transport block that tdec_set_tb_ragged may be given: block r of C multiplies its CRC24A share by factor C-1-r of
+// tdec_tbA_table (tdec.hip), which holds 16 factors. A grants call with a larger transport block has tb_crc_bytes_kernel assemble and judge them.
+constexpr uint32_t TDEC_TB_MAX_C_DIRECT = 16;
 // tdec.hip: blocks with d_skip[cb] != 0 are left alone by the following runs: bytes, CRC flag, TB-CRC share stay (nullptr: off)
 void tdec_set_skip(srslte_hip_tdec_t* q, const uint8_t* d_skip);
 // tdec.hip: the following runs work on the block slots d_map[0 .. nof_cb) instead of 0 .. nof_cb-1 (input, output, iteration count, CRC flag,

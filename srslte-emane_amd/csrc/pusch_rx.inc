@@ -814,14 +814,17 @@ extern "C" int srslte_hip_ul_rx_batch_grants(srslte_hip_ul_rx_t* q, const void* 
     if (int r = bd.add_tb(p, p, gr.mod, gr.tbs, gr.rv, gr.new_data, nof_re - (uint32_t)Qp_ri - (uint32_t)Qp_cqi, 1, (uint32_t)pd.cqi_Q)) return r;
   }
   bd.fill_map(h_map);
-  // the decoders assemble the transport blocks and give the verdicts (grants_back_end)
-  const bool direct = g->tb_direct;
-  bool       no_tb = false;
-  uint8_t*   h_cof = g->h_pin[hs] + g->desc_bytes - ((V + 15) & ~15u);
+  // the decoders assemble the transport blocks and give the verdicts (grants_back_end), when none of the call's has more blocks than their CRC
+  // factor table covers (TDEC_TB_MAX_C_DIRECT)
+  bool     no_tb = false;
+  uint32_t max_C = 0;
+  uint8_t* h_cof = g->h_pin[hs] + g->desc_bytes - ((V + 15) & ~15u);
   for (uint32_t p = 0; p < nof_grants; p++) {
     h_cof[p] = (uint8_t)h_sf[p].C;
     no_tb    = no_tb || grants[p].tbs == 0;
+    max_C    = std::max(max_C, (uint32_t)h_sf[p].C);
   }
+  const bool direct = g->tb_direct && max_C <= TDEC_TB_MAX_C_DIRECT;
   const uint8_t* d_cof = direct ? g->d_desc + g->desc_bytes - ((V + 15) & ~15u) : nullptr;
   if (direct && no_tb) HIP_TRY(hipMemsetAsync(d_tb_ok, 0, nof_grants, st)); // rows without a transport block get no verdict from a decoder
   int r = srslte_hip_ofdm_rx_sf_batch(q->ofdm, d_iq, q->d_grid, (int)nof_sf, stream);

@@ -93,7 +93,10 @@ class Side:
 
 @pytest.mark.skipif(ref() is None, reason="oracle/_ref/libsrslte_ref.so not built")
 @pytest.mark.parametrize("prb,tbs,mod,nre,Nl,llr8,snr", [(25, 4008, 2, 3000, 1, False, -5.0), (100, 75376, 3, 14580, 1, False, 3.5), (100, 30576, 2, 14580, 2, False, -1.5),
-                                                         (6, 328, 1, 600, 1, False, -5.5), (50, 21384, 3, 6600, 1, True, 1.5), (100, 75376, 3, 14580, 1, True, 4.0)])
+                                                         (6, 328, 1, 600, 1, False, -5.5), (50, 21384, 3, 6600, 1, True, 1.5), (100, 75376, 3, 14580, 1, True, 4.0),
+                                                         # 16 blocks of K = 6144 at 256QAM: the most the reference's soft buffer holds (softbuffer.c:47-49 at
+                                                         # 110 PRB: 97896 / 6120 + 1), so the most its srslte_dlsch_decode2 decodes
+                                                         (110, 97896, 4, 14230, 1, False, 3.5), (110, 97896, 4, 14230, 1, True, 3.0)])
 def test_dlsch_decode2_vs_reference_with_harq(prb, tbs, mod, nre, Nl, llr8, snr):
     from lte_sim import OrcSchCfg
     orc, rng = oracle(), np.random.default_rng(tbs + nre)
