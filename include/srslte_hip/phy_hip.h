@@ -548,6 +548,91 @@ void              srslte_hip_sch_destroy(srslte_hip_sch_t* q);
 int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, uint32_t nof_e_bits, uint32_t tbs, int mod, uint32_t Nl, uint32_t rv,
                           uint32_t max_iterations, int16_t** buffer_f, uint8_t* cb_crc, uint8_t* cb_bytes, uint32_t* sum_passes);
 
+/* ------------------------------------------------------------------ DL control region receive (UE side): the part of srslte_ue_dl_find_dl_dci
+ * that precedes the DCI unpacking, for a batch of subframes (ue/ue_dl.c:334-367 estimate_pdcch_pcfich, :422-478 dci_blind_search, :534-646
+ * find_dl_dci_type_siprarnti / _crnti): PCFICH -> CFI -> PDCCH LLRs -> blind search -> one DL DCI message per subframe, all on the device and
+ * in one sequence of launches on the caller's stream (no host synchronisation; the CFI decided on the device selects the REG list and the
+ * candidates there). Inputs are what srslte_hip_ofdm_rx_sf_batch and srslte_hip_chest_dl_estimate_batch[_multi] produce.
+ *   PCFICH (pcfich.c:160-227): srslte_predecoding_single_multi with the noise estimate as it is, or srslte_predecoding_diversity_multi +
+ *     srslte_layerdemap_diversity (2 / 4 ports), QPSK soft demapping, the subframe's sequence (sequences.c:36-38), then
+ *     srslte_pcfich_cfi_decode (pcfich.c:124-142): max_corr starts at 0 with index 0, so all-negative correlations give CFI 1, correlation 0.
+ *   PDCCH LLRs (srslte_pdcch_extract_llr, pdcch.c:424-488): 36 NOF_CCE(cfi) REs of the REG list of the CFI (regs.c, built on the host once per
+ *     object), srslte_predecoding_single_multi with noise / 2, QPSK demapping, srslte_scrambling_f_offset with srslte_sequence_pdcch of slot
+ *     2 sf_idx sized 8 srslte_regs_pdcch_nregs(3) (pdcch.c:199-201, sequences.c:51-53). As on an AVX host the equaliser of a single-port cell
+ *     combines at most antennas 0 and 1 over the first 16 (n / 16) symbols (antenna 0 alone with 3 or 4; precoding.c:149-236), the 2-port
+ *     diversity equaliser antennas 0 and 1 (antenna 0 alone with 3 or 4; srslte_predecoding_diversity2_sse precoding.c:433-540); 4 ports: all.
+ *   Candidates: srslte_pdcch_ue_locations_ncce (the Y_k hash, pdcch.c:228-275) and srslte_pdcch_common_locations_ncce (:291-314) with
+ *     NOF_CCE of the CFI in use. A candidate whose mean |LLR| (summed in double) is not above 0.3 is skipped (pdcch.c:382-389). Otherwise
+ *     srslte_pdcch_dci_decode (pdcch.c:327-363): srslte_rm_conv_rx to 3 (nof_bits + 16) with the repetitions added in the reference's order
+ *     (rm_conv.c), srslte_viterbi_decode_f's quantisation and tail-biting decoder, CRC-16 and the XOR with the received parity; formats 0 / 1A
+ *     told apart by the flag bit (pdcch.c:393-396). DCI sizes: srslte_dci_format_sizeof with a zero srslte_dci_cfg_t (dci.c:114-360).
+ *   Search (cif disabled): SI / P / RA-RNTI: common space, 1A then 1C; C-RNTI: UE-specific space with ue_dci_formats[tm] (1A + 1 / 1 / 2A / 2
+ *     for TM1-4, ue_dl.c:31-39), then 1A in the common space. The first candidate whose CRC remainder equals the RNTI and whose format is the
+ *     one searched ends the search; a format-0 hit while searching 1A is not a DL DCI (ue_dl.c:452-470).
+ * FDD cells, normal / extended CP, 6-110 PRB, 1 / 2 / 4 ports, 1-4 receive antennas, every PHICH configuration (phich_resources
+ * srslte_phich_r_t 0-3 = 1/6, 1/2, 1, 2; phich_ext = SRSLTE_PHICH_EXT; the PHICH REGs of regs.c:245-367 with mi = 1). Refused: TDD cells
+ * (srslte_hip_dl_ctrl_create returns NULL) and MBSFN subframes (SRSLTE_ERROR_INVALID_INPUTS).
+ * Not here: PDCCH / PCFICH encoding in srslte_hip_dl_tx_*, PHICH decoding, UL DCIs (srslte_ue_dl_find_ul_dci), carrier indicator / carrier
+ * aggregation, the DCI -> grant unpacking (srslte_dci_msg_unpack_pdsch + srslte_ra_dl_dci_to_grant stay with the caller), and
+ * the single-subframe drop-in's pcfich.c / pdcch.c, which remain the reference's. */
+typedef struct srslte_hip_dl_ctrl srslte_hip_dl_ctrl_t;
+typedef struct {
+  uint32_t nof_prb, nof_ports, cell_id;
+  int      cp_ext;          /* srslte_cell_t.cp == SRSLTE_CP_EXT */
+  int      phich_resources; /* srslte_phich_r_t */
+  int      phich_ext;       /* srslte_cell_t.phich_length == SRSLTE_PHICH_EXT */
+  int      tdd;             /* srslte_cell_t.frame_type == SRSLTE_TDD: refused */
+  uint32_t nof_rx_antennas; /* 1-4 */
+  uint32_t max_batch;       /* subframes per call */
+} srslte_hip_dl_ctrl_cfg_t;
+typedef struct {            /* per subframe (host array) */
+  uint16_t rnti;            /* SI / P / RA-RNTI: common space; anything else: C-RNTI. 0: nothing is searched (ue_dl.c:474-476) */
+  uint32_t tm;              /* srslte_tm_t: 0-3 = TM1-TM4 */
+  uint32_t cfi;             /* 0: from the PCFICH; 1-3: given (the sf->cfi a caller sets, refdrv_dl_estimate's cfi_in) */
+  int      mbsfn;           /* MBSFN subframe: refused */
+} srslte_hip_dl_ctrl_req_t;
+typedef struct {            /* per subframe */
+  uint32_t cfi;             /* the CFI used */
+  float    cfi_corr;        /* srslte_pcfich_decode's correlation (computed also when the CFI is given) */
+  uint32_t nof_dci;         /* DL DCIs found: 0 or 1 */
+} srslte_hip_dl_ctrl_res_t;
+typedef struct {            /* same members, order and sizes as srslte_dci_msg_t (dci.h:65-71) */
+  uint8_t  payload[128];    /* nof_bits + 16 decoded bits (message, then the received CRC), zero behind */
+  uint32_t nof_bits;
+  uint32_t L, ncce;         /* srslte_dci_location_t */
+  int      format;          /* srslte_dci_format_t */
+  uint16_t rnti;
+} srslte_hip_dci_msg_t;
+typedef struct {            /* one searched candidate (srslte_hip_dl_ctrl_debug_buffer 1) */
+  uint32_t L, ncce, format, nof_bits; /* location, format searched, srslte_dci_format_sizeof */
+  uint32_t skipped;         /* mean |LLR| <= 0.3: not decoded */
+  uint32_t crc_rem;         /* CRC-16 XOR received parity (msg->rnti of srslte_pdcch_decode_msg) */
+  uint32_t format_decoded;  /* after the 0 / 1A differentiation */
+  uint8_t  payload[128];    /* as srslte_hip_dci_msg_t.payload */
+} srslte_hip_dl_ctrl_cand_t;
+#define SRSLTE_HIP_DL_CTRL_MAX_CAND 38 /* 16 UE-specific x 2 formats + 6 common */
+srslte_hip_dl_ctrl_t* srslte_hip_dl_ctrl_create(const srslte_hip_dl_ctrl_cfg_t* cfg);
+void                  srslte_hip_dl_ctrl_destroy(srslte_hip_dl_ctrl_t* q);
+/* d_grid [nof_sf][nof_rx][nsym][12 nof_prb] (nsym 14 / 12), d_ce [nof_sf][nof_ports][nof_rx][nsym][12 nof_prb], d_res [nof_sf]
+ * srslte_hip_chest_dl_res_t; subframe b is TTI tti0 + b and is searched with reqs[b]. d_out [nof_sf] and d_msg [nof_sf] (subframes without
+ * a DCI: nof_bits 0) may be device-visible pinned host memory. */
+int srslte_hip_dl_ctrl_batch(srslte_hip_dl_ctrl_t* q, const void* d_grid, const void* d_ce, const void* d_res, uint32_t tti0, uint32_t nof_sf,
+                             const srslte_hip_dl_ctrl_req_t* reqs, srslte_hip_dl_ctrl_res_t* d_out, srslte_hip_dci_msg_t* d_msg, void* stream);
+/* device buffers of the last call: 0 LLR rows [max_batch][srslte_hip_dl_ctrl_llr_stride] float (72 NOF_CCE(cfi) LLRs, zeros behind, as
+ * q->llr of pdcch.c), 1 candidates [max_batch][SRSLTE_HIP_DL_CTRL_MAX_CAND] srslte_hip_dl_ctrl_cand_t in search order, 2 their numbers
+ * [max_batch] uint32 */
+const void* srslte_hip_dl_ctrl_debug_buffer(const srslte_hip_dl_ctrl_t* q, int which);
+uint32_t    srslte_hip_dl_ctrl_llr_stride(const srslte_hip_dl_ctrl_t* q);
+/* host helpers (no device needed): RE indices into one antenna's [nsym][12 nof_prb] grid, in the order srslte_regs_pcfich_get (16) and
+ * srslte_regs_pdcch_get (36 NOF_CCE(cfi)) read them; return the count, or < 0 for an invalid cell / cfi / too small max */
+int      srslte_hip_dl_ctrl_pcfich_re(const srslte_hip_dl_ctrl_cfg_t* cfg, uint32_t* re, uint32_t max);
+int      srslte_hip_dl_ctrl_pdcch_re(const srslte_hip_dl_ctrl_cfg_t* cfg, uint32_t cfi, uint32_t* re, uint32_t max);
+/* srslte_pdcch_ue_locations_ncce / srslte_pdcch_common_locations_ncce: loc[2 k] = L (0-3), loc[2 k + 1] = ncce; returns k */
+uint32_t srslte_hip_pdcch_ue_locations_ncce(uint32_t nof_cce, uint32_t* loc, uint32_t max_candidates, uint32_t sf_idx, uint16_t rnti);
+uint32_t srslte_hip_pdcch_common_locations_ncce(uint32_t nof_cce, uint32_t* loc, uint32_t max_candidates);
+/* srslte_dci_format_sizeof of an FDD cell with a zero srslte_dci_cfg_t, format srslte_dci_format_t 0-8 (0 1 1A 1C 1B 1D 2 2A 2B); 0 otherwise */
+uint32_t srslte_hip_dci_format_sizeof(uint32_t nof_prb, uint32_t nof_ports, int format);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,7 @@ def lib():
         L.srslte_hip_dl_rx_debug_buffer.restype = vp
         L.srslte_hip_dl_rx_debug_buffer.argtypes = [vp, C.c_int]
         L.srslte_hip_dl_rx_keep_symbols.argtypes = [vp, C.c_int]
+        _bind_dl_ctrl(L)
         _lib = L
     return _lib
 
@@ -934,4 +935,158 @@ class DlTx:
     def free(self):
         if self.h:
             lib().srslte_hip_dl_tx_destroy(self.h)
+            self.h = None
+
+
+# ---------------------------------------------------------------- DL control region receive (phy_hip.h "DL control region receive")
+DCI_FORMAT0, DCI_FORMAT1, DCI_FORMAT1A, DCI_FORMAT1C, DCI_FORMAT1B, DCI_FORMAT1D, DCI_FORMAT2, DCI_FORMAT2A, DCI_FORMAT2B = range(9)  # srslte_dci_format_t
+DL_CTRL_MAX_CAND = 38
+
+
+class DlCtrlCfg(C.Structure):
+    """srslte_hip_dl_ctrl_cfg_t: the cell (srslte_cell_t) and the object's batch size."""
+    _fields_ = [("nof_prb", C.c_uint32), ("nof_ports", C.c_uint32), ("cell_id", C.c_uint32), ("cp_ext", C.c_int), ("phich_resources", C.c_int),
+                ("phich_ext", C.c_int), ("tdd", C.c_int), ("nof_rx_antennas", C.c_uint32), ("max_batch", C.c_uint32)]
+
+
+class DlCtrlReq(C.Structure):
+    """srslte_hip_dl_ctrl_req_t: RNTI, srslte_tm_t (0-3), CFI (0 = from the PCFICH) and the MBSFN flag of one subframe."""
+    _fields_ = [("rnti", C.c_uint16), ("tm", C.c_uint32), ("cfi", C.c_uint32), ("mbsfn", C.c_int)]
+
+
+class DlCtrlRes(C.Structure):
+    """srslte_hip_dl_ctrl_res_t."""
+    _fields_ = [("cfi", C.c_uint32), ("cfi_corr", C.c_float), ("nof_dci", C.c_uint32)]
+
+
+class DciMsg(C.Structure):
+    """srslte_hip_dci_msg_t = srslte_dci_msg_t (dci.h:65-71)."""
+    _fields_ = [("payload", C.c_uint8 * 128), ("nof_bits", C.c_uint32), ("L", C.c_uint32), ("ncce", C.c_uint32), ("format", C.c_int), ("rnti", C.c_uint16)]
+
+
+class DlCtrlCand(C.Structure):
+    """srslte_hip_dl_ctrl_cand_t: one searched candidate."""
+    _fields_ = [("L", C.c_uint32), ("ncce", C.c_uint32), ("format", C.c_uint32), ("nof_bits", C.c_uint32), ("skipped", C.c_uint32), ("crc_rem", C.c_uint32),
+                ("format_decoded", C.c_uint32), ("payload", C.c_uint8 * 128)]
+
+
+def _bind_dl_ctrl(L):
+    vp = C.c_void_p
+    L.srslte_hip_dl_ctrl_create.restype = vp
+    L.srslte_hip_dl_ctrl_create.argtypes = [C.POINTER(DlCtrlCfg)]
+    L.srslte_hip_dl_ctrl_destroy.argtypes = [vp]
+    L.srslte_hip_dl_ctrl_batch.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+    L.srslte_hip_dl_ctrl_debug_buffer.restype = vp
+    L.srslte_hip_dl_ctrl_debug_buffer.argtypes = [vp, C.c_int]
+    L.srslte_hip_dl_ctrl_llr_stride.restype = C.c_uint32
+    L.srslte_hip_dl_ctrl_llr_stride.argtypes = [vp]
+    L.srslte_hip_dl_ctrl_pcfich_re.argtypes = [C.POINTER(DlCtrlCfg), vp, C.c_uint32]
+    L.srslte_hip_dl_ctrl_pdcch_re.argtypes = [C.POINTER(DlCtrlCfg), C.c_uint32, vp, C.c_uint32]
+    L.srslte_hip_pdcch_ue_locations_ncce.restype = C.c_uint32
+    L.srslte_hip_pdcch_ue_locations_ncce.argtypes = [C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint16]
+    L.srslte_hip_pdcch_common_locations_ncce.restype = C.c_uint32
+    L.srslte_hip_pdcch_common_locations_ncce.argtypes = [C.c_uint32, vp, C.c_uint32]
+    L.srslte_hip_dci_format_sizeof.restype = C.c_uint32
+    L.srslte_hip_dci_format_sizeof.argtypes = [C.c_uint32, C.c_uint32, C.c_int]
+    return L
+
+
+def _ctrl_cfg(nof_prb, nof_ports, cell_id, cp_ext=False, phich_resources=0, phich_ext=False, nof_rx=1, max_batch=1, tdd=False):
+    return DlCtrlCfg(nof_prb, nof_ports, cell_id, 1 if cp_ext else 0, phich_resources, 1 if phich_ext else 0, 1 if tdd else 0, nof_rx, max_batch)
+
+
+def pcfich_re(nof_prb, nof_ports, cell_id, cp_ext=False, phich_resources=0, phich_ext=False):
+    """The 16 PCFICH REs as indices into one antenna's [nsym][12 nof_prb] grid, in srslte_regs_pcfich_get's order (host; no GPU)."""
+    L = _bind_dl_ctrl(lib())
+    out = np.zeros(16, np.uint32)
+    n = L.srslte_hip_dl_ctrl_pcfich_re(C.byref(_ctrl_cfg(nof_prb, nof_ports, cell_id, cp_ext, phich_resources, phich_ext)), out.ctypes.data, 16)
+    if n < 0:
+        raise ValueError("srslte_hip_dl_ctrl_pcfich_re: %d" % n)
+    return out[:n]
+
+
+def pdcch_re(nof_prb, nof_ports, cell_id, cfi, cp_ext=False, phich_resources=0, phich_ext=False):
+    """The 36 NOF_CCE(cfi) PDCCH REs in srslte_regs_pdcch_get's order (host; no GPU)."""
+    L = _bind_dl_ctrl(lib())
+    out = np.zeros(14 * 12 * 110, np.uint32)
+    n = L.srslte_hip_dl_ctrl_pdcch_re(C.byref(_ctrl_cfg(nof_prb, nof_ports, cell_id, cp_ext, phich_resources, phich_ext)), cfi, out.ctypes.data, out.size)
+    if n < 0:
+        raise ValueError("srslte_hip_dl_ctrl_pdcch_re: %d" % n)
+    return out[:n]
+
+
+def pdcch_ue_locations(nof_cce, sf_idx, rnti, max_candidates=16):
+    """srslte_pdcch_ue_locations_ncce -> [(L, ncce), ...] (host)."""
+    loc = np.zeros(2 * max_candidates, np.uint32)
+    k = _bind_dl_ctrl(lib()).srslte_hip_pdcch_ue_locations_ncce(nof_cce, loc.ctypes.data, max_candidates, sf_idx, rnti)
+    return [(int(loc[2 * i]), int(loc[2 * i + 1])) for i in range(k)]
+
+
+def pdcch_common_locations(nof_cce, max_candidates=6):
+    """srslte_pdcch_common_locations_ncce -> [(L, ncce), ...] (host)."""
+    loc = np.zeros(2 * max_candidates, np.uint32)
+    k = _bind_dl_ctrl(lib()).srslte_hip_pdcch_common_locations_ncce(nof_cce, loc.ctypes.data, max_candidates)
+    return [(int(loc[2 * i]), int(loc[2 * i + 1])) for i in range(k)]
+
+
+def dci_format_sizeof(nof_prb, nof_ports, fmt):
+    """srslte_dci_format_sizeof for an FDD cell with a zero srslte_dci_cfg_t (host)."""
+    return _bind_dl_ctrl(lib()).srslte_hip_dci_format_sizeof(nof_prb, nof_ports, fmt)
+
+
+class DlCtrl:
+    """Batched control-region receive: srslte_pcfich_decode + srslte_pdcch_extract_llr + the DL DCI blind search of srslte_ue_dl_find_dl_dci."""
+
+    def __init__(self, nof_prb, nof_ports, cell_id, cp_ext=False, phich_resources=0, phich_ext=False, nof_rx=1, max_batch=1, tdd=False):
+        L = _bind_dl_ctrl(lib())
+        self.cfg = _ctrl_cfg(nof_prb, nof_ports, cell_id, cp_ext, phich_resources, phich_ext, nof_rx, max_batch, tdd)
+        self.h = L.srslte_hip_dl_ctrl_create(C.byref(self.cfg))
+        if not self.h:
+            raise RuntimeError("srslte_hip_dl_ctrl_create failed")
+        self.grid_len = (12 if cp_ext else 14) * 12 * nof_prb
+        self.nof_ports, self.nof_rx, self.max_batch = nof_ports, nof_rx, max_batch
+        self.llr_stride = L.srslte_hip_dl_ctrl_llr_stride(self.h)
+
+    def run_device(self, d_grid, d_ce, d_res, tti0, reqs, d_out, d_msg, stream=None):
+        """Device pointers in and out; reqs: list of DlCtrlReq. Returns the status code."""
+        arr = (DlCtrlReq * max(1, len(reqs)))(*reqs)
+        return lib().srslte_hip_dl_ctrl_batch(self.h, d_grid, d_ce, d_res, tti0, len(reqs), arr, d_out, d_msg, stream)
+
+    def batch(self, grid, ce, res, tti0, reqs):
+        """grid [nof_sf][nof_rx][grid_len], ce [nof_sf][nof_ports][nof_rx][grid_len] (complex64), res [nof_sf][10] float32 (srslte_hip_chest_dl_res_t)
+        -> (rc, [DlCtrlRes], [DciMsg])."""
+        n = len(reqs)
+        g = np.ascontiguousarray(grid, np.complex64).reshape(n, self.nof_rx, self.grid_len)
+        h = np.ascontiguousarray(ce, np.complex64).reshape(n, self.nof_ports, self.nof_rx, self.grid_len)
+        r = np.ascontiguousarray(res, np.float32).reshape(n, 10)
+        dg, dh, dr = DevBuf.from_host(g), DevBuf.from_host(h), DevBuf.from_host(r)
+        dout, dmsg = DevBuf(C.sizeof(DlCtrlRes) * n), DevBuf(C.sizeof(DciMsg) * n)
+        rc = self.run_device(dg.ptr, dh.ptr, dr.ptr, tti0, reqs, dout.ptr, dmsg.ptr)
+        if rc != SRSLTE_SUCCESS:
+            return rc, None, None
+        sync()
+        out, msg = (DlCtrlRes * n)(), (DciMsg * n)()
+        _check(lib().srslte_hip_memcpy_d2h(C.addressof(out), dout.ptr, C.sizeof(out)), "memcpy_d2h")
+        _check(lib().srslte_hip_memcpy_d2h(C.addressof(msg), dmsg.ptr, C.sizeof(msg)), "memcpy_d2h")
+        return rc, list(out), list(msg)
+
+    def llr(self, nof_sf):
+        """Debug buffer 0: the LLR rows of the last call, [nof_sf][llr_stride] float32."""
+        ptr = lib().srslte_hip_dl_ctrl_debug_buffer(self.h, 0)
+        out = np.empty(nof_sf * self.llr_stride, np.float32)
+        _check(lib().srslte_hip_memcpy_d2h(out.ctypes.data, ptr, out.nbytes), "memcpy_d2h")
+        return out.reshape(nof_sf, self.llr_stride)
+
+    def candidates(self, nof_sf):
+        """Debug buffers 1 and 2: for each subframe of the last call the list of DlCtrlCand in search order."""
+        L = lib()
+        cand = (DlCtrlCand * (nof_sf * DL_CTRL_MAX_CAND))()
+        cnt = np.empty(nof_sf, np.uint32)
+        _check(L.srslte_hip_memcpy_d2h(C.addressof(cand), L.srslte_hip_dl_ctrl_debug_buffer(self.h, 1), C.sizeof(cand)), "memcpy_d2h")
+        _check(L.srslte_hip_memcpy_d2h(cnt.ctypes.data, L.srslte_hip_dl_ctrl_debug_buffer(self.h, 2), cnt.nbytes), "memcpy_d2h")
+        return [list(cand[b * DL_CTRL_MAX_CAND:b * DL_CTRL_MAX_CAND + int(cnt[b])]) for b in range(nof_sf)]
+
+    def free(self):
+        if self.h:
+            lib().srslte_hip_dl_ctrl_destroy(self.h)
             self.h = None

@@ -1,0 +1,676 @@
+// DL control region receive for gfx950 (include/srslte_hip/phy_hip.h, "DL control region receive"): PCFICH -> CFI -> PDCCH LLRs ->
+// blind search -> DL DCI messages for a batch of subframes, three launches on the caller's stream:
+//   dl_ctrl_llr_kernel     one workgroup per subframe: srslte_pcfich_decode (pcfich.c:160-227), srslte_pdcch_extract_llr for the CFI it
+//                          decided or was given (pdcch.c:424-488) into an LLR row, and the subframe's candidate list in search order
+//                          (ue_dl.c:534-618 with srslte_pdcch_ue_locations_ncce / srslte_pdcch_common_locations_ncce, pdcch.c:228-314)
+//   dl_ctrl_dci_kernel     one wavefront per (subframe, candidate): the skip rule and srslte_pdcch_dci_decode (pdcch.c:327-396) - rate
+//                          de-matching with the reference's combining order, the Viterbi decoder of viterbi_dev.hpp, CRC-16
+//   dl_ctrl_select_kernel  one lane per subframe: dci_blind_search's first hit (ue_dl.c:422-478)
+// The REG lists (regs.c), the DCI sizes (dci.c:93-360) and the scrambling sequences are built on the host when the object is made.
+#include "common.hpp"
+#include "demod_dev.hpp"
+#include "phy_hip_internal.hpp"
+#include "viterbi_dev.hpp"
+#include <math.h>
+#include <string.h>
+#include <vector>
+
+namespace {
+
+constexpr int      MAX_CAND = SRSLTE_HIP_DL_CTRL_MAX_CAND;
+constexpr int      REQ_CHUNK = 128;        // subframes per launch of dl_ctrl_llr_kernel (their requests travel as a kernel argument)
+constexpr int      DCI_CHUNK = 32768;      // subframes per launch of dl_ctrl_dci_kernel (gridDim.y)
+constexpr int      MAX_F     = 128;        // nof_bits + 16 of the largest DCI decoded (rm_conv.c's limit is 32 rows; DCIs here stay below 80)
+constexpr float    RX_NULL   = 10000.0f;   // SRSLTE_RX_NULL (rm_conv.c)
+constexpr uint16_t SIRNTI = 0xFFFF, PRNTI = 0xFFFE, RARNTI_START = 0x0001, RARNTI_END = 0x000A; // phy_common.h:71-80
+enum { F0 = 0, F1, F1A, F1C, F1B, F1D, F2, F2A, F2B, NOF_FORMATS };      // srslte_dci_format_t (phy_common.h:249-265)
+
+__constant__ uint8_t RM_PERM[32]     = {1, 17, 9, 25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31, 0, 16, 8, 24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30};
+__constant__ uint8_t RM_PERM_INV[32] = {16, 0, 24, 8, 20, 4, 28, 12, 18, 2, 26, 10, 22, 6, 30, 14, 17, 1, 25, 9, 21, 5, 29, 13, 19, 3, 27, 11, 23, 7, 31, 15};
+__constant__ uint8_t UE_FORMATS[4][2] = {{F1A, F1}, {F1A, F1}, {F1A, F2A}, {F1A, F2}}; // ue_dci_formats, ue_dl.c:31-39
+
+// srslte_pdcch_ue_locations_ncce (pdcch.c:228-275): Y_k of the subframe, aggregation levels 8 .. 1, candidates of 36.213 Table 9.1.1-1
+__host__ __device__ inline uint32_t ue_locations(uint32_t nof_cce, uint32_t* loc, uint32_t max_candidates, uint32_t sf_idx, uint16_t rnti)
+{
+  const uint32_t nof_candidates[4] = {6, 6, 2, 2};
+  uint32_t       Yk = rnti, k = 0;
+  for (uint32_t m = 0; m < sf_idx + 1; m++) Yk = (39827 * Yk) % 65537;
+  for (int l = 3; l >= 0; l--) {
+    const uint32_t L = 1u << l;
+    for (uint32_t i = 0; i < nof_candidates[l]; i++) {
+      if (nof_cce >= L) {
+        const uint32_t ncce = L * ((Yk + i) % (nof_cce / L));
+        if (k < max_candidates && ncce + L <= nof_cce) {
+          loc[2 * k] = l, loc[2 * k + 1] = ncce;
+          k++;
+        }
+      }
+    }
+  }
+  return k;
+}
+
+// srslte_pdcch_common_locations_ncce (pdcch.c:291-314)
+__host__ __device__ inline uint32_t common_locations(uint32_t nof_cce, uint32_t* loc, uint32_t max_candidates)
+{
+  uint32_t k = 0;
+  for (uint32_t l = 3; l > 1; l--) {
+    const uint32_t L = 1u << l;
+    for (uint32_t i = 0; i < (nof_cce < 16 ? nof_cce : 16) / L; i++) {
+      const uint32_t ncce = L * i;
+      if (k < max_candidates && ncce + L <= nof_cce) {
+        loc[2 * k] = l, loc[2 * k + 1] = ncce;
+        k++;
+      }
+    }
+  }
+  return k;
+}
+
+struct CtrlGeom {
+  const uint32_t* re;        // [16 PCFICH][n[0]][n[1]][n[2]] RE indices into one [nsym][12 prb] grid
+  const uint32_t* scr_pcfich; // [10] words: the 32 bits of srslte_sequence_pcfich of each subframe, bit i = bit i
+  const uint32_t* scr_pdcch;  // [10][scr_words]
+  int             scr_words;
+  int             off[3], n[3]; // PDCCH REs of CFI 1-3 (36 NOF_CCE)
+  int             nof_ports, nof_rx, grid_len;
+  int             llr_stride;
+  uint32_t        dci_bits[NOF_FORMATS];
+};
+struct CtrlReqs { uint32_t w[REQ_CHUNK]; }; // rnti | tm << 16 | cfi << 20
+
+// srslte_predecoding_single_gen (precoding.c:238-249): all antennas, x = r / ((hh + noise) scaling), scaling 1
+__device__ __forceinline__ cf32 eq_single_gen(const cf32* y, const cf32* h, int nof_rx, int glen, uint32_t k, float noise)
+{
+  float re = 0.f, im = 0.f, hh = 0.f;
+  for (int a = 0; a < nof_rx; a++) {
+    const cf32 yy = y[(size_t)a * glen + k], hv = h[(size_t)a * glen + k];
+    re += yy.x * hv.x + yy.y * hv.y;
+    im += yy.y * hv.x - yy.x * hv.y;
+    hh += hv.x * hv.x + hv.y * hv.y;
+  }
+  const float den = hh + noise;
+  return make_float2(re / den, im / den);
+}
+
+// srslte_predecoding_single_avx's body (precoding.c:149-226): antenna 0, plus antenna 1 when there are exactly two; noise added when > 0
+__device__ __forceinline__ cf32 eq_single_avx(const cf32* y, const cf32* h, int nof_rx, int glen, uint32_t k, float noise)
+{
+  const int na = nof_rx == 2 ? 2 : 1;
+  float     re = 0.f, im = 0.f, hh = 0.f;
+  for (int a = 0; a < na; a++) {
+    const cf32 yy = y[(size_t)a * glen + k], hv = h[(size_t)a * glen + k];
+    re += yy.x * hv.x + yy.y * hv.y;
+    im += yy.y * hv.x - yy.x * hv.y;
+    hh += hv.x * hv.x + hv.y * hv.y;
+  }
+  if (noise > 0.f) hh += noise;
+  return make_float2(re / hh * 1.0f, im / hh * 1.0f);
+}
+
+// one SFBC pair of srslte_predecoding_diversity_gen_ (gen = 1: precoding.c:351-384, every antenna, the 1e-4 guard, sqrt(2) in double) or of
+// srslte_predecoding_diversity2_sse (gen = 0: :433-540, antennas 0 and 1 only when there are exactly two, sqrtf(2) in float)
+__device__ __forceinline__ void eq_div2(const cf32* y, const cf32* h0, const cf32* h1, int nof_rx, int glen, uint32_t k0, uint32_t k1, bool gen, cf32* x)
+{
+  const int na = gen ? nof_rx : (nof_rx == 2 ? 2 : 1);
+  float     hh = 0.f, x0r = 0.f, x0i = 0.f, x1r = 0.f, x1i = 0.f;
+  for (int a = 0; a < na; a++) {
+    const size_t o   = (size_t)a * glen;
+    const cf32   h00 = h0[o + k0], h01 = h0[o + k1], h10 = h1[o + k0], h11 = h1[o + k1], r0 = y[o + k0], r1 = y[o + k1];
+    hh += h00.x * h00.x + h00.y * h00.y + h11.x * h11.x + h11.y * h11.y;
+    if (gen && hh == 0.f) hh = 1e-4f;
+    x0r += h00.x * r0.x + h00.y * r0.y + h11.x * r1.x + h11.y * r1.y;
+    x0i += h00.x * r0.y - h00.y * r0.x + h11.y * r1.x - h11.x * r1.y;
+    x1r += h01.x * r1.x + h01.y * r1.y - (h10.x * r0.x + h10.y * r0.y);
+    x1i += h01.x * r1.y - h01.y * r1.x - (h10.y * r0.x - h10.x * r0.y);
+  }
+  if (gen) {
+    x[0] = make_float2((float)((double)(x0r / hh) * 1.4142135623730951), (float)((double)(x0i / hh) * 1.4142135623730951));
+    x[1] = make_float2((float)((double)(x1r / hh) * 1.4142135623730951), (float)((double)(x1i / hh) * 1.4142135623730951));
+  } else {
+    const float s2 = sqrtf(2.0f);
+    x[0] = make_float2(x0r / hh * s2, x0i / hh * s2);
+    x[1] = make_float2(x1r / hh * s2, x1i / hh * s2);
+  }
+}
+
+// one group of four of srslte_predecoding_diversity_gen_ for 4 ports (precoding.c:385-420) + srslte_layerdemap_diversity: d[4i + l] = x[l]
+__device__ __forceinline__ void eq_div4(const cf32* y, const cf32* const* h, int nof_rx, int glen, const uint32_t* k, cf32* x)
+{
+  float hh02 = 0.f, hh13 = 0.f, xr[4] = {0.f, 0.f, 0.f, 0.f}, xi[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int a = 0; a < nof_rx; a++) {
+    const size_t o  = (size_t)a * glen;
+    const cf32   g0 = h[0][o + k[0]], g1 = h[1][o + k[2]], g2 = h[2][o + k[0]], g3 = h[3][o + k[2]];
+    const cf32   r0 = y[o + k[0]], r1 = y[o + k[1]], r2 = y[o + k[2]], r3 = y[o + k[3]];
+    hh02 += g0.x * g0.x + g0.y * g0.y + g2.x * g2.x + g2.y * g2.y;
+    hh13 += g1.x * g1.x + g1.y * g1.y + g3.x * g3.x + g3.y * g3.y;
+    // x0 = conj(g0) r0 + g2 conj(r1); x1 = -g2 conj(r0) + conj(g0) r1; x2, x3 the same with g1, g3 on r2, r3
+    xr[0] += g0.x * r0.x + g0.y * r0.y + g2.x * r1.x + g2.y * r1.y;
+    xi[0] += g0.x * r0.y - g0.y * r0.x + g2.y * r1.x - g2.x * r1.y;
+    xr[1] += -(g2.x * r0.x + g2.y * r0.y) + g0.x * r1.x + g0.y * r1.y;
+    xi[1] += -(g2.y * r0.x - g2.x * r0.y) + g0.x * r1.y - g0.y * r1.x;
+    xr[2] += g1.x * r2.x + g1.y * r2.y + g3.x * r3.x + g3.y * r3.y;
+    xi[2] += g1.x * r2.y - g1.y * r2.x + g3.y * r3.x - g3.x * r3.y;
+    xr[3] += -(g3.x * r2.x + g3.y * r2.y) + g1.x * r3.x + g1.y * r3.y;
+    xi[3] += -(g3.y * r2.x - g3.x * r2.y) + g1.x * r3.y - g1.y * r3.x;
+  }
+#pragma unroll
+  for (int l = 0; l < 4; l++) {
+    const float hh = l < 2 ? hh02 : hh13;
+    x[l]           = make_float2((float)((double)(xr[l] / hh) * 1.4142135623730951), (float)((double)(xi[l] / hh) * 1.4142135623730951));
+  }
+}
+
+__device__ __forceinline__ int scr_bit(const uint32_t* s, int i) { return (s[i >> 5] >> (i & 31)) & 1; }
+
+// grid = (chunk, 1), 256 threads
+__global__ __launch_bounds__(256) void dl_ctrl_llr_kernel(const cf32* __restrict__ grid, const cf32* __restrict__ ce, const float* __restrict__ res,
+                                                          uint32_t tti0, int sf0, CtrlReqs reqs, CtrlGeom g, float* __restrict__ llr,
+                                                          srslte_hip_dl_ctrl_cand_t* __restrict__ cand, uint32_t* __restrict__ ncand,
+                                                          srslte_hip_dl_ctrl_res_t* __restrict__ out)
+{
+  __shared__ int      cfi_s;
+  __shared__ float    d[32];      // the PCFICH's 32 LLRs
+  __shared__ uint32_t loc[2 * 16]; // candidate locations
+  const int      b = sf0 + blockIdx.x, tid = threadIdx.x, sf_idx = (tti0 + b) % 10;
+  const uint32_t rq = reqs.w[blockIdx.x];
+  const int      P = g.nof_ports, R = g.nof_rx, glen = g.grid_len;
+  const cf32*    y = grid + (size_t)b * R * glen;
+  const cf32*    h[4];
+  for (int p = 0; p < 4; p++) h[p] = ce + ((size_t)b * P + (p < P ? p : 0)) * R * glen;
+  const float noise = res[(size_t)b * 10]; // srslte_hip_chest_dl_res_t.noise_estimate
+  if (tid == 0) {
+    // PCFICH: 16 REs, srslte_predecoding_single_multi / diversity_multi take their generic paths at 16 symbols (precoding.c:325-348,:665-683)
+    for (int i = 0; i < 16; i += P) {
+      cf32 x[4];
+      if (P == 1) {
+        x[0] = eq_single_gen(y, h[0], R, glen, g.re[i], noise);
+      } else if (P == 2) {
+        eq_div2(y, h[0], h[1], R, glen, g.re[i], g.re[i + 1], true, x);
+      } else {
+        eq_div4(y, h, R, glen, g.re + i, x);
+      }
+#pragma unroll
+      for (int l = 0; l < 4; l++) {
+        if (l < P) {
+          float o[8];
+          demod_dev::demod_f(demod_dev::MOD_QPSK, x[l], o);
+          d[2 * (i + l)]     = scr_bit(g.scr_pcfich + sf_idx, 2 * (i + l)) ? -o[0] : o[0];
+          d[2 * (i + l) + 1] = scr_bit(g.scr_pcfich + sf_idx, 2 * (i + l) + 1) ? -o[1] : o[1];
+        }
+      }
+    }
+    // srslte_pcfich_cfi_decode (pcfich.c:124-142): CFI c's code word is the pattern "011" / "101" / "110" repeated (36.212 Table 5.3.4-1)
+    int   index = 0;
+    float max_corr = 0.f;
+    for (int c = 0; c < 3; c++) {
+      float corr = 0.f;
+      for (int j = 0; j < 32; j++) corr += (j % 3) == c ? -d[j] : d[j];
+      if (corr > max_corr) max_corr = corr, index = c;
+    }
+    const int cfi_req = (rq >> 20) & 3;
+    cfi_s = cfi_req ? cfi_req : index + 1;
+    out[b].cfi = cfi_s;
+    out[b].cfi_corr = max_corr;
+  }
+  __syncthreads();
+  const int       cfi = cfi_s, n = g.n[cfi - 1], e_bits = 2 * n, ncce = n / 36;
+  const uint32_t* re  = g.re + g.off[cfi - 1];
+  const uint32_t* cs  = g.scr_pdcch + (size_t)sf_idx * g.scr_words;
+  float*          row = llr + (size_t)b * g.llr_stride;
+  const int       G = P, n16 = 16 * (n / 16);
+  for (int q = tid; q < n / G; q += 256) {
+    cf32 x[4];
+    if (P == 1) {
+      const int i = q;
+      x[0] = i < n16 ? eq_single_avx(y, h[0], R, glen, re[i], noise / 2) : eq_single_gen(y, h[0], R, glen, re[i], noise / 2);
+    } else if (P == 2) {
+      eq_div2(y, h[0], h[1], R, glen, re[2 * q], re[2 * q + 1], false, x); // 36 NOF_CCE > 32 symbols: the SSE path, no tail
+    } else {
+      eq_div4(y, h, R, glen, re + 4 * q, x);
+    }
+#pragma unroll
+    for (int l = 0; l < 4; l++) {
+      if (l < G) {
+        const int i = G * q + l;
+        float     o[8];
+        demod_dev::demod_f(demod_dev::MOD_QPSK, x[l], o);
+        row[2 * i]     = scr_bit(cs, 2 * i) ? -o[0] : o[0];
+        row[2 * i + 1] = scr_bit(cs, 2 * i + 1) ? -o[1] : o[1];
+      }
+    }
+  }
+  for (int i = e_bits + tid; i < g.llr_stride; i += 256) row[i] = 0.f; // bzero(q->llr) (pdcch.c:441)
+  if (tid == 0) {
+    // the candidates in the order the searches of ue_dl.c:534-618 try them
+    const uint16_t rnti = (uint16_t)(rq & 0xffff);
+    const int      tm = (rq >> 16) & 3;
+    srslte_hip_dl_ctrl_cand_t* c = cand + (size_t)b * MAX_CAND;
+    uint32_t k = 0;
+    if (rnti == SIRNTI || rnti == PRNTI || (rnti >= RARNTI_START && rnti <= RARNTI_END)) {
+      const uint32_t nc = common_locations(ncce, loc, 6);
+      for (int f = 0; f < 2; f++)
+        for (uint32_t i = 0; i < nc; i++, k++) c[k].L = loc[2 * i], c[k].ncce = loc[2 * i + 1], c[k].format = f ? F1C : F1A;
+    } else if (rnti) {
+      const uint32_t nu = ue_locations(ncce, loc, 16, sf_idx, rnti);
+      for (int f = 0; f < 2; f++)
+        for (uint32_t i = 0; i < nu; i++, k++) c[k].L = loc[2 * i], c[k].ncce = loc[2 * i + 1], c[k].format = UE_FORMATS[tm][f];
+      const uint32_t nc = common_locations(ncce, loc, 6);
+      for (uint32_t i = 0; i < nc; i++, k++) c[k].L = loc[2 * i], c[k].ncce = loc[2 * i + 1], c[k].format = F1A;
+    }
+    for (uint32_t i = 0; i < k; i++) c[i].nof_bits = g.dci_bits[c[i].format];
+    ncand[b] = k;
+  }
+}
+
+// CRC-16 of 36.212 5.1.1 (srslte_crc_checksum with SRSLTE_LTE_CRC16 0x11021 on unpacked bits, crc.c)
+__device__ __forceinline__ uint32_t crc16(const uint8_t* bits, int n)
+{
+  uint32_t r = 0;
+  for (int i = 0; i < n + 16; i++) {
+    r = (r << 1) | (i < n ? (bits[i] & 1u) : 0u);
+    if (r & 0x10000u) r ^= 0x11021u;
+  }
+  return r & 0xffffu;
+}
+
+// grid = (MAX_CAND, nof_sf), one wavefront per candidate
+__global__ __launch_bounds__(64) void dl_ctrl_dci_kernel(const float* __restrict__ llr, int llr_stride, srslte_hip_dl_ctrl_cand_t* __restrict__ cand,
+                                                         const uint32_t* __restrict__ ncand, int sf0)
+{
+  __shared__ float              tmp[3 * MAX_F], rmf[3 * MAX_F];
+  __shared__ uint16_t           us[3 * MAX_F];
+  __shared__ unsigned long long dec[3 * MAX_F + 6];
+  __shared__ uint8_t            bits[3 * MAX_F];
+  const int b = sf0 + blockIdx.y, lane = threadIdx.x;
+  if ((uint32_t)blockIdx.x >= ncand[b]) return;
+  srslte_hip_dl_ctrl_cand_t* cd = cand + (size_t)b * MAX_CAND + blockIdx.x;
+  const int    L = cd->L, nb = cd->nof_bits, E = 72 << L;
+  const float* e = llr + (size_t)b * llr_stride + cd->ncce * 72;
+  // skip rule (pdcch.c:382-389): mean |LLR| accumulated in double
+  double s = 0.0;
+  for (int i = lane; i < E; i += 64) s += (double)fabsf(e[i]);
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if (!(s / E > 0.3)) {
+    if (lane == 0) cd->skipped = 1, cd->crc_rem = 0, cd->format_decoded = cd->format;
+    for (int i = lane; i < 128; i += 64) cd->payload[i] = 0;
+    return;
+  }
+  // srslte_rm_conv_rx (rm_conv.c): the walk over the 3 K_p positions of the circular buffer skips the dummy ones and wraps; valid position j
+  // of rank r receives input r, r + 3F, r + 6F, ... in that order (the first replaces the RX_NULL fill, later ones are added unless RX_NULL)
+  const int F = nb + 16, nrows = (F - 1) / 32 + 1, Kp = nrows * 32, nd = Kp - F, W = 3 * Kp;
+  int       base = 0;
+  for (int j0 = 0; j0 < W; j0 += 64) {
+    const int  j = j0 + lane, r = j % Kp, di = r / nrows, dj = r % nrows;
+    const bool valid = j < W && dj * 32 + RM_PERM[di] >= nd;
+    const unsigned long long m = __ballot(valid);
+    const int  rank = base + __popcll(m & ((1ull << lane) - 1ull));
+    if (j < W) {
+      float acc = RX_NULL;
+      if (valid) {
+        for (int k = rank; k < E; k += 3 * F) {
+          const float v = e[k];
+          if (acc == RX_NULL) {
+            acc = v;
+          } else if (v != RX_NULL) {
+            acc += v;
+          }
+        }
+      }
+      tmp[j] = acc;
+    }
+    base += __popcll(m);
+  }
+  __syncthreads();
+  for (int i = lane; i < 3 * F; i += 64) {
+    const int   ii = i / 3, sidx = i - 3 * ii, di = (ii + nd) / 32, dj = (ii + nd) % 32;
+    const float o = tmp[Kp * sidx + RM_PERM_INV[dj] * nrows + di];
+    rmf[i]        = o != RX_NULL ? o : 0.f;
+  }
+  for (int i = 3 * F + lane; i < 3 * F + 6; i += 64) dec[i] = 0ull;
+  __syncthreads();
+  viterbi_dev::quant_fus(rmf, us, 3 * F, lane);
+  viterbi_dev::decode37_tb(us, dec, bits, F, lane);
+  __syncthreads();
+  const uint8_t* msg = bits + F; // the middle repetition
+  for (int i = lane; i < 128; i += 64) cd->payload[i] = i < F ? msg[i] : 0;
+  if (lane == 0) {
+    uint32_t p = 0;
+    for (int i = 0; i < 16; i++) p = (p << 1) | msg[nb + i];
+    cd->skipped        = 0;
+    cd->crc_rem        = p ^ crc16(msg, nb);
+    cd->format_decoded = (cd->format == F0 || cd->format == F1A) ? (msg[0] == 0 ? F0 : F1A) : cd->format;
+  }
+}
+
+// grid = ceil(nof_sf / 64), one lane per subframe
+__global__ __launch_bounds__(64) void dl_ctrl_select_kernel(const srslte_hip_dl_ctrl_cand_t* __restrict__ cand, const uint32_t* __restrict__ ncand,
+                                                            int sf0, CtrlReqs reqs, int nof_sf, srslte_hip_dl_ctrl_res_t* __restrict__ out,
+                                                            srslte_hip_dci_msg_t* __restrict__ msg)
+{
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= nof_sf) return;
+  const int                        b    = sf0 + i;
+  const uint32_t                   rnti = reqs.w[i] & 0xffff;
+  const srslte_hip_dl_ctrl_cand_t* c    = cand + (size_t)b * MAX_CAND;
+  int                              hit  = -1;
+  for (uint32_t k = 0; k < ncand[b] && hit < 0; k++) {
+    if (!c[k].skipped && c[k].crc_rem == rnti && c[k].format_decoded == c[k].format) hit = (int)k;
+  }
+  srslte_hip_dci_msg_t* m = msg + b;
+  out[b].nof_dci          = hit >= 0 ? 1 : 0;
+  for (int j = 0; j < 128; j += 4) *reinterpret_cast<uint32_t*>(m->payload + j) = hit >= 0 ? *reinterpret_cast<const uint32_t*>(c[hit].payload + j) : 0u;
+  m->nof_bits = hit >= 0 ? c[hit].nof_bits : 0;
+  m->L        = hit >= 0 ? c[hit].L : 0;
+  m->ncce     = hit >= 0 ? c[hit].ncce : 0;
+  m->format   = hit >= 0 ? (int)c[hit].format : 0;
+  m->rnti     = hit >= 0 ? (uint16_t)rnti : 0;
+}
+
+// ---------------------------------------------------------------- host: REGs (regs.c), DCI sizes (dci.c)
+struct Reg {
+  uint32_t l, k0, k[4];
+  bool     assigned;
+};
+
+static bool cell_ok(const srslte_hip_dl_ctrl_cfg_t* c)
+{
+  return c && c->nof_prb >= 6 && c->nof_prb <= 110 && (c->nof_ports == 1 || c->nof_ports == 2 || c->nof_ports == 4) && c->cell_id < 504 &&
+         c->phich_resources >= 0 && c->phich_resources <= 3;
+}
+
+// srslte_regs_init_opts with mi = 1 outside MBSFN / TDD special subframes (regs.c:698-786, REGs :633-675, PCFICH :491-523, PHICH :245-367,
+// PDCCH :77-154): pcfich = the 16 REs, pdcch[c] = the 36 NOF_CCE REs of CFI c + 1, as RE indices of the [nsym][12 prb] grid
+static int build_regs(const srslte_hip_dl_ctrl_cfg_t* c, std::vector<uint32_t>& pcfich, std::vector<uint32_t> pdcch[3])
+{
+  if (!cell_ok(c)) return SRSLTE_ERROR_INVALID_INPUTS;
+  const uint32_t prb = c->nof_prb, id = c->cell_id, max_ctrl = prb <= 10 ? 4 : 3, vo = id % 3;
+  uint32_t       n[4];
+  for (uint32_t i = 0; i < max_ctrl; i++) n[i] = i == 0 ? 2 : i == 1 ? (c->nof_ports == 4 ? 2 : 3) : i == 2 ? 3 : (c->cp_ext ? 2 : 3);
+  uint32_t nof_regs = 0;
+  for (uint32_t i = 0; i < max_ctrl; i++) nof_regs += prb * n[i];
+  std::vector<Reg> regs(nof_regs);
+  uint32_t         j[4] = {0, 0, 0, 0}, k = 0, i = 0, p = 0, jmax = 0;
+  while (k < nof_regs) { // lowest symbol first, then frequency, PRB by PRB
+    if (n[i] == 3 || (n[i] == 2 && jmax != 1)) {
+      Reg& r = regs[k];
+      r.l = i, r.assigned = false;
+      const uint32_t b0 = p * 12;
+      if (n[i] == 2) { // two REGs around the reference signals at vo, vo + 3
+        r.k0 = b0 + j[i] * 6;
+        uint32_t t = 0;
+        for (uint32_t z = 0; z < 6; z++)
+          if (z != vo && z != vo + 3) r.k[t++] = r.k0 + z;
+      } else {
+        r.k0 = b0 + j[i] * 4;
+        for (uint32_t z = 0; z < 4; z++) r.k[z] = r.k0 + z;
+      }
+      j[i]++, k++;
+    }
+    if (++i == max_ctrl) i = 0, jmax++;
+    if (jmax == 3) p++, j[0] = j[1] = j[2] = j[3] = 0, jmax = 0;
+  }
+  auto re_of = [prb](const Reg& r, uint32_t t) { return r.k[t] + r.l * prb * 12; };
+  // PCFICH
+  pcfich.clear();
+  const uint32_t k_hat = 6 * (id % (2 * prb));
+  for (uint32_t q = 0; q < 4; q++) {
+    const uint32_t kk = (k_hat + (q * prb / 2) * 6) % (prb * 12);
+    Reg*           f  = nullptr;
+    for (auto& r : regs)
+      if (r.l == 0 && r.k0 == kk) {
+        f = &r;
+        break;
+      }
+    if (!f || f->assigned) return SRSLTE_ERROR;
+    f->assigned = true;
+    for (uint32_t t = 0; t < 4; t++) pcfich.push_back(re_of(*f, t));
+  }
+  // PHICH
+  const float    ng[4]   = {(float)1 / 6, (float)1 / 2, 1.0f, 2.0f};
+  const uint32_t ngroups = (uint32_t)(int)ceilf(ng[c->phich_resources] * ((float)prb / 8));
+  std::vector<Reg*> ph[3];
+  for (auto& r : regs)
+    if (r.l < 3 && !r.assigned) ph[r.l].push_back(&r);
+  for (uint32_t mi = 0; mi < ngroups; mi++) {
+    for (uint32_t q = 0; q < 3; q++) {
+      const uint32_t li = c->phich_ext ? q : 0, nl = (uint32_t)ph[li].size();
+      const uint32_t ni = ((id * nl / (uint32_t)ph[0].size()) + mi + q * nl / 3) % nl;
+      ph[li][ni]->assigned = true;
+    }
+  }
+  // PDCCH: quadruplet sub-block interleaver (32 columns, PDCCH_PERM) and the cyclic shift by the cell id
+  static const uint8_t PERM[32] = {1, 17, 9, 25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31, 0, 16, 8, 24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30};
+  for (uint32_t cfi = 0; cfi < 3; cfi++) {
+    const uint32_t    nsym = prb <= 10 ? cfi + 2 : cfi + 1;
+    std::vector<Reg*> tmp;
+    for (auto& r : regs)
+      if (r.l < nsym && !r.assigned) tmp.push_back(&r);
+    const uint32_t    m = (uint32_t)tmp.size(), nrows = (m - 1) / 32 + 1;
+    const int         ndummy = (int)(32 * nrows) - (int)m;
+    std::vector<Reg*> out(m);
+    uint32_t          kk = 0;
+    for (uint32_t jj = 0; jj < 32; jj++) {
+      for (uint32_t ii = 0; ii < nrows; ii++) {
+        if ((int)(ii * 32 + PERM[jj]) >= ndummy) {
+          const uint32_t mm = ii * 32 + PERM[jj] - ndummy;
+          const uint32_t kp = kk < id ? (m + kk - (id % m)) % m : (kk - id) % m;
+          out[mm]           = tmp[kp];
+          kk++;
+        }
+      }
+    }
+    pdcch[cfi].clear();
+    for (uint32_t r = 0; r < (m / 9) * 9; r++)
+      for (uint32_t t = 0; t < 4; t++) pdcch[cfi].push_back(re_of(*out[r], t));
+  }
+  return SRSLTE_SUCCESS;
+}
+
+static uint32_t riv_nbits(uint32_t n) { return (uint32_t)ceilf(log2f((float)n * ((float)n + 1) / 2)); }
+static bool     ambiguous(uint32_t n)
+{
+  static const uint32_t a[10] = {12, 14, 16, 20, 24, 26, 32, 40, 44, 56};
+  for (uint32_t v : a)
+    if (n == v) return true;
+  return false;
+}
+static uint32_t type0_P(uint32_t prb) { return prb <= 10 ? 1 : prb <= 26 ? 2 : prb <= 63 ? 3 : 4; } // ra.c:62-72
+
+// srslte_dci_format_sizeof (dci.c:114-360) for FDD, cif / multiple CSI request / SRS request / resource allocation type bit off
+static uint32_t dci_sizeof(uint32_t prb, uint32_t ports, int f)
+{
+  const uint32_t f0_ = 1 + 1 + riv_nbits(prb) + 5 + 1 + 2 + 3 + 1;
+  uint32_t       f1a = 1 + 1 + riv_nbits(prb) + 5 + 3 + 1 + 2 + 2;
+  while (f1a < f0_) f1a++;
+  if (ambiguous(f1a)) f1a++;
+  uint32_t f0 = f0_;
+  while (f0 < f1a) f0++;
+  const uint32_t rbg = (uint32_t)ceilf((float)prb / type0_P(prb)) + (prb > 10 ? 1 : 0);
+  switch (f) {
+    case F0: return f0;
+    case F1A: return f1a;
+    case F1: {
+      uint32_t n = rbg + 5 + 3 + 1 + 2 + 2;
+      while (n == f0 || n == f1a || ambiguous(n)) n++;
+      return n;
+    }
+    case F1C: { // ra.c:81-120: N_gap,1, n_vrb_dl = 2 min(N_gap, N_rb - N_gap), step 2 / 4
+      const uint32_t ngap = prb <= 10 ? prb / 2 : prb == 11 ? 4 : prb <= 19 ? 8 : prb <= 26 ? 12 : prb <= 44 ? 18 : prb <= 49 ? 27 : prb <= 63 ? 27
+                          : prb <= 79 ? 32 : 48;
+      const uint32_t nvrb = 2 * (ngap < prb - ngap ? ngap : prb - ngap), step = prb < 50 ? 2 : 4;
+      return riv_nbits(nvrb / step) + 5 + (prb >= 50 ? 1 : 0);
+    }
+    case F1B:
+    case F1D: {
+      uint32_t n = f1a - 1 + (ports <= 2 ? 2 : 4) + 1;
+      while (ambiguous(n)) n++;
+      return n;
+    }
+    case F2:
+    case F2A:
+    case F2B: {
+      const uint32_t pre = f == F2 ? (ports <= 2 ? 3 : 6) : f == F2A ? (ports <= 2 ? 0 : 2) : 0;
+      uint32_t       n   = rbg + 2 + 3 + 1 + 2 * (5 + 1 + 2) + pre;
+      while (ambiguous(n)) n++;
+      return n;
+    }
+    default: return 0;
+  }
+}
+
+} // namespace
+
+struct srslte_hip_dl_ctrl {
+  srslte_hip_dl_ctrl_cfg_t cfg;
+  CtrlGeom                 g;
+  uint32_t*                d_re = nullptr;
+  uint32_t*                d_scr = nullptr;
+  float*                   d_llr = nullptr;
+  srslte_hip_dl_ctrl_cand_t* d_cand = nullptr;
+  uint32_t*                d_ncand = nullptr;
+};
+
+extern "C" {
+
+int srslte_hip_dl_ctrl_pcfich_re(const srslte_hip_dl_ctrl_cfg_t* cfg, uint32_t* re, uint32_t max)
+{
+  std::vector<uint32_t> pc, pd[3];
+  const int             rc = build_regs(cfg, pc, pd);
+  if (rc != SRSLTE_SUCCESS) return rc;
+  if (!re || max < pc.size()) return SRSLTE_ERROR_INVALID_INPUTS;
+  memcpy(re, pc.data(), pc.size() * 4);
+  return (int)pc.size();
+}
+
+int srslte_hip_dl_ctrl_pdcch_re(const srslte_hip_dl_ctrl_cfg_t* cfg, uint32_t cfi, uint32_t* re, uint32_t max)
+{
+  if (cfi < 1 || cfi > 3) return SRSLTE_ERROR_INVALID_INPUTS;
+  std::vector<uint32_t> pc, pd[3];
+  const int             rc = build_regs(cfg, pc, pd);
+  if (rc != SRSLTE_SUCCESS) return rc;
+  const std::vector<uint32_t>& v = pd[cfi - 1];
+  if (!re || max < v.size()) return SRSLTE_ERROR_INVALID_INPUTS;
+  memcpy(re, v.data(), v.size() * 4);
+  return (int)v.size();
+}
+
+uint32_t srslte_hip_pdcch_ue_locations_ncce(uint32_t nof_cce, uint32_t* loc, uint32_t max_candidates, uint32_t sf_idx, uint16_t rnti)
+{
+  return loc ? ue_locations(nof_cce, loc, max_candidates, sf_idx, rnti) : 0;
+}
+
+uint32_t srslte_hip_pdcch_common_locations_ncce(uint32_t nof_cce, uint32_t* loc, uint32_t max_candidates)
+{
+  return loc ? common_locations(nof_cce, loc, max_candidates) : 0;
+}
+
+uint32_t srslte_hip_dci_format_sizeof(uint32_t nof_prb, uint32_t nof_ports, int format)
+{
+  if (nof_prb < 6 || nof_prb > 110) return 0;
+  return dci_sizeof(nof_prb, nof_ports, format);
+}
+
+void srslte_hip_dl_ctrl_destroy(srslte_hip_dl_ctrl_t* q)
+{
+  if (!q) return;
+  (void)hipFree(q->d_re);
+  (void)hipFree(q->d_scr);
+  (void)hipFree(q->d_llr);
+  (void)hipFree(q->d_cand);
+  (void)hipFree(q->d_ncand);
+  delete q;
+}
+
+srslte_hip_dl_ctrl_t* srslte_hip_dl_ctrl_create(const srslte_hip_dl_ctrl_cfg_t* cfg)
+{
+  if (!cell_ok(cfg) || cfg->tdd || cfg->nof_rx_antennas < 1 || cfg->nof_rx_antennas > 4 || cfg->max_batch < 1) return nullptr;
+  std::vector<uint32_t> pc, pd[3];
+  if (build_regs(cfg, pc, pd) != SRSLTE_SUCCESS) return nullptr;
+  srslte_hip_dl_ctrl_t* q = new srslte_hip_dl_ctrl_t();
+  q->cfg                  = *cfg;
+  CtrlGeom& g             = q->g;
+  std::vector<uint32_t> re(pc);
+  for (int c = 0; c < 3; c++) {
+    g.off[c] = (int)re.size(), g.n[c] = (int)pd[c].size();
+    re.insert(re.end(), pd[c].begin(), pd[c].end());
+  }
+  g.nof_ports  = (int)cfg->nof_ports;
+  g.nof_rx     = (int)cfg->nof_rx_antennas;
+  g.grid_len   = (cfg->cp_ext ? 12 : 14) * 12 * (int)cfg->nof_prb;
+  g.llr_stride = (2 * g.n[2] + 3) & ~3; // 72 NOF_CCE(3)
+  for (int f = 0; f < NOF_FORMATS; f++) g.dci_bits[f] = dci_sizeof(cfg->nof_prb, cfg->nof_ports, f);
+  if (g.dci_bits[F2] + 16 > MAX_F || g.n[0] < 36) { // every cell of the range fits; a CFI-1 region without a CCE does not happen either
+    delete q;
+    return nullptr;
+  }
+  // scrambling: srslte_sequence_pcfich (32 bits) and srslte_sequence_pdcch sized 8 srslte_regs_pdcch_nregs(3) = 2 n[2] bits, slot 2 sf_idx
+  g.scr_words = (2 * g.n[2] + 31) / 32;
+  std::vector<uint32_t> scr(10 + 10 * (size_t)g.scr_words, 0u);
+  std::vector<uint8_t>  c;
+  for (uint32_t s = 0; s < 10; s++) {
+    lte_gold_sequence((s + 1) * (2 * cfg->cell_id + 1) * 512 + cfg->cell_id, 32, c);
+    for (int i = 0; i < 32; i++) scr[s] |= (uint32_t)(c[i] & 1) << i;
+    lte_gold_sequence(s * 512 + cfg->cell_id, 2 * g.n[2], c);
+    for (int i = 0; i < 2 * g.n[2]; i++) scr[10 + s * g.scr_words + (i >> 5)] |= (uint32_t)(c[i] & 1) << (i & 31);
+  }
+  const size_t B = cfg->max_batch;
+  if (hipMalloc(&q->d_re, re.size() * 4) != hipSuccess || hipMalloc(&q->d_scr, scr.size() * 4) != hipSuccess ||
+      hipMalloc(&q->d_llr, B * g.llr_stride * 4) != hipSuccess || hipMalloc(&q->d_cand, B * MAX_CAND * sizeof(srslte_hip_dl_ctrl_cand_t)) != hipSuccess ||
+      hipMalloc(&q->d_ncand, B * 4) != hipSuccess || hipMemcpy(q->d_re, re.data(), re.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(q->d_scr, scr.data(), scr.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    hip_log("[srslte_hip] srslte_hip_dl_ctrl_create: device allocation failed\n");
+    srslte_hip_dl_ctrl_destroy(q);
+    return nullptr;
+  }
+  g.re = q->d_re, g.scr_pcfich = q->d_scr, g.scr_pdcch = q->d_scr + 10;
+  return q;
+}
+
+int srslte_hip_dl_ctrl_batch(srslte_hip_dl_ctrl_t* q, const void* d_grid, const void* d_ce, const void* d_res, uint32_t tti0, uint32_t nof_sf,
+                             const srslte_hip_dl_ctrl_req_t* reqs, srslte_hip_dl_ctrl_res_t* d_out, srslte_hip_dci_msg_t* d_msg, void* stream)
+{
+  if (!q || !d_grid || !d_ce || !d_res || !reqs || !d_out || !d_msg || nof_sf < 1 || nof_sf > q->cfg.max_batch) return SRSLTE_ERROR_INVALID_INPUTS;
+  for (uint32_t b = 0; b < nof_sf; b++) {
+    if (reqs[b].mbsfn || reqs[b].tm > 3 || reqs[b].cfi > 3) return SRSLTE_ERROR_INVALID_INPUTS;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  for (uint32_t s0 = 0; s0 < nof_sf; s0 += REQ_CHUNK) {
+    const uint32_t n = nof_sf - s0 < (uint32_t)REQ_CHUNK ? nof_sf - s0 : (uint32_t)REQ_CHUNK;
+    CtrlReqs       r;
+    memset(&r, 0, sizeof(r));
+    for (uint32_t i = 0; i < n; i++) r.w[i] = reqs[s0 + i].rnti | reqs[s0 + i].tm << 16 | reqs[s0 + i].cfi << 20;
+    hipLaunchKernelGGL(dl_ctrl_llr_kernel, dim3(n), dim3(256), 0, st, (const cf32*)d_grid, (const cf32*)d_ce, (const float*)d_res, tti0, (int)s0, r, q->g,
+                       q->d_llr, q->d_cand, q->d_ncand, d_out);
+    LAUNCH_CHECK();
+  }
+  for (uint32_t s0 = 0; s0 < nof_sf; s0 += DCI_CHUNK) { // gridDim.y stays below 65536 whatever max_batch is
+    const uint32_t n = nof_sf - s0 < (uint32_t)DCI_CHUNK ? nof_sf - s0 : (uint32_t)DCI_CHUNK;
+    hipLaunchKernelGGL(dl_ctrl_dci_kernel, dim3(MAX_CAND, n), dim3(64), 0, st, q->d_llr, q->g.llr_stride, q->d_cand, q->d_ncand, (int)s0);
+    LAUNCH_CHECK();
+  }
+  for (uint32_t s0 = 0; s0 < nof_sf; s0 += REQ_CHUNK) {
+    const uint32_t n = nof_sf - s0 < (uint32_t)REQ_CHUNK ? nof_sf - s0 : (uint32_t)REQ_CHUNK;
+    CtrlReqs       r;
+    memset(&r, 0, sizeof(r));
+    for (uint32_t i = 0; i < n; i++) r.w[i] = reqs[s0 + i].rnti;
+    hipLaunchKernelGGL(dl_ctrl_select_kernel, dim3(ceil_div((int)n, 64)), dim3(64), 0, st, q->d_cand, q->d_ncand, (int)s0, r, (int)n, d_out, d_msg);
+    LAUNCH_CHECK();
+  }
+  return SRSLTE_SUCCESS;
+}
+
+const void* srslte_hip_dl_ctrl_debug_buffer(const srslte_hip_dl_ctrl_t* q, int which)
+{
+  if (!q) return nullptr;
+  switch (which) {
+    case 0: return q->d_llr;
+    case 1: return q->d_cand;
+    case 2: return q->d_ncand;
+    default: return nullptr;
+  }
+}
+
+uint32_t srslte_hip_dl_ctrl_llr_stride(const srslte_hip_dl_ctrl_t* q) { return q ? (uint32_t)q->g.llr_stride : 0; }
+
+} // extern "C"

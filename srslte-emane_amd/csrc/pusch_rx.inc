@@ -312,41 +312,9 @@ __global__ __launch_bounds__(256) void pusch_cqi_decode_kernel(const int16_t* __
   }
   __syncthreads();
   if (tid >= 64) return;
-  // srslte_viterbi_decode_f's quantisation (viterbi.c:532-540, srslte_vec_quant_fus): gain 1000 / max |.|, offset 32767.5, clip to 16 bits
-  float mx = -9e9f;
-  for (int i = tid; i < 3 * F; i += 64) mx = fmaxf(mx, fabsf((float)dem[i]));
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-  const float gain = 1000.0f / mx;
-  for (int i = tid; i < 3 * F; i += 64) {
-    const long t = (long)fmaf(gain, (float)dem[i], 32767.5f);
-    us[i]        = (uint16_t)(t < 0 ? 0 : (t > 65535 ? 65535 : t));
-  }
-  __builtin_amdgcn_s_waitcnt(0xc07f); // lgkmcnt(0): one wavefront from here on, LDS in order
-  const int      n = tid, b = n >> 1;
-  const uint32_t bt0 = (__builtin_popcount((2 * b) & 0x6D) & 1) ? 65535u : 0u, bt1 = (__builtin_popcount((2 * b) & 0x4F) & 1) ? 65535u : 0u,
-                 bt2 = (__builtin_popcount((2 * b) & 0x57) & 1) ? 65535u : 0u;
-  uint32_t old = 63;
-  for (int t = 0; t < 3 * F; t++) {
-    const int      f  = t % F;
-    const uint32_t a = bt0 ^ us[3 * f], bb = bt1 ^ us[3 * f + 1], c = bt2 ^ us[3 * f + 2];
-    const uint32_t m01 = (a + bb + 1) >> 1, met = ((c + m01 + 1) >> 1) >> 3, mm = 8191u - met;
-    const uint32_t oi = (uint32_t)__shfl((int)old, b, 64), oj = (uint32_t)__shfl((int)old, b + 32, 64);
-    const uint16_t x  = (uint16_t)(oi + ((n & 1) ? mm : met)), y = (uint16_t)(oj + ((n & 1) ? met : mm)); // (m0, m1) or (m2, m3)
-    const bool     d  = (int16_t)(uint16_t)(x - y) > 0;
-    old               = d ? y : x;
-    const unsigned long long bal = __ballot(d);
-    if (tid == 0) dec[t] = bal;
-  }
-  uint32_t mn = old;
-  for (int o = 32; o > 0; o >>= 1) mn = min(mn, (uint32_t)__shfl_xor((int)mn, o, 64));
-  const unsigned long long at_min = __ballot(old == mn);
+  viterbi_dev::quant_fus(dem, us, 3 * F, tid);
+  viterbi_dev::decode37_tb(us, dec, bits, F, tid);
   if (tid == 0) {
-    uint32_t endstate = (uint32_t)(63 - __builtin_clzll(at_min)) << 2; // the LAST state with the smallest metric
-    for (int i = 3 * F - 1; i >= F; i--) {
-      const uint32_t k = (uint32_t)(dec[6 + i] >> (endstate >> 2)) & 1u;
-      endstate         = (endstate >> 1) | (k << 7);
-      bits[i]          = (uint8_t)k;
-    }
     const uint8_t* msg = bits + F; // the middle repetition
     uint32_t       rx  = 0;
     for (int i = 0; i < 8; i++) rx = (rx << 1) | msg[O + i];
