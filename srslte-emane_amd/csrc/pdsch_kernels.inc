@@ -920,7 +920,6 @@ __global__ __launch_bounds__(RELIST_THREADS) void grants_prep_kernel(const Grant
                                                                      const uint4* __restrict__ desc_src, uint4* __restrict__ desc_dst, int desc_n16,
                                                                      int copy_first)
 {
-#if SRSLTE_HIP_GRANTS_DESC_BY_KERNEL
   // Third role (workgroups from copy_first on): the call's descriptors from the pinned host buffer to the device - what a hipMemcpyAsync in front of
   // this launch did (an engine hand-over or a 17-56 us blit kernel on the call's stream). gr / gr1 then point into the HOST buffer: the two roles
   // above read their 64-byte grant from there (wave-uniform loads), every later kernel reads the device copy.
@@ -929,7 +928,6 @@ __global__ __launch_bounds__(RELIST_THREADS) void grants_prep_kernel(const Grant
     if (i < desc_n16) desc_dst[i] = desc_src[i];
     return;
   }
-#endif
   if ((int)blockIdx.x < nof_sf) {
     // the call's verdict rows start at "no transport block" (rows behind the first nof_sf: second codewords): the decoders' own assembly only
     // writes the rows that have one
@@ -998,7 +996,20 @@ int rm_lds_bytes(const RmGeom& g, int llr_bytes)
   mx     = mx > g.nof_re[2] ? mx : g.nof_re[2];
   return ((g.Qm * (mx / g.C) + 2 * g.Qm) * llr_bytes + 32 + 15) & ~15; // + the bytes below the 16-byte boundary and the rounded-up last load
 }
-bool rm_fits_lds(const RmGeom& g, int llr_bytes = 2) { return rm_lds_bytes(g, llr_bytes) <= 64 * 1024; }
+
+// rate de-matching of nblk code blocks: rm_rx_lds_kernel with `lds` bytes of LDS when they fit 64 KB, else rm_rx_kernel (1024 / sizeof(T)
+// slots of w_stride per workgroup)
+template <typename T>
+int rm_rx_launch(int lds, uint32_t nblk, const void* e, void* w, const uint32_t* tbl, const RmGeom& g, hipStream_t st)
+{
+  if (lds <= 64 * 1024) {
+    hipLaunchKernelGGL(rm_rx_lds_kernel<T>, dim3(nblk), dim3(256), lds, st, (const T*)e, (T*)w, tbl, g);
+  } else {
+    hipLaunchKernelGGL(rm_rx_kernel<T>, dim3(ceil_div(g.w_stride, 1024 / (int)sizeof(T)), nblk), dim3(256), 0, st, (const T*)e, (T*)w, tbl, g);
+  }
+  LAUNCH_CHECK();
+  return SRSLTE_SUCCESS;
+}
 
 // slot -> circular-buffer position: 32-bit entries [w_stride] for the generic kernels, then the same as 16-bit entries for the LDS kernel
 std::vector<uint32_t> rm_slot_table(const std::vector<uint32_t>& t, uint32_t w_stride)
@@ -1057,5 +1068,108 @@ int upload(T** d, const std::vector<T>& h)
   HIP_TRY(hipMemcpy(*d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
   return SRSLTE_SUCCESS;
 }
+
+// rate de-matching table of (K, rv) (rm_turbo.c:160-260) in the turbo decoder's input layout, as rm_slot_table's slot table of w_stride; W != 0:
+// the windowed decoders' layout (stream s at s (K + 32), bit i at (i % (K / W)) W + i / (K / W), the tails behind the three streams)
+int rm_rx_table_upload(uint32_t K, uint32_t rv, uint32_t W, uint32_t w_stride, uint32_t** d_tbl)
+{
+  std::vector<uint32_t> t;
+  lte_rm_rx_table(K, rv, t);
+  if (W) {
+    for (auto& v : t) v = v < 3 * K ? (v % 3) * (K + 32) + ((v / 3) % (K / W)) * W + (v / 3) / (K / W) : (v - 3 * K) + 3 * (K + 32);
+  }
+  return upload(d_tbl, rm_slot_table(t, w_stride));
+}
+
+// rate matching table of (K, rv) (rm_turbo.c:100-158): the coded bit of each circular-buffer position from k0(rv) on, addressed in the encoder's
+// byte streams (systematic byte p, tail bit (1 << 30) | p - K, parity bytes (2 << 30) | p of stream 1, K + 4 + p of stream 2)
+int rm_tx_table_upload(uint32_t K, uint32_t rv, uint32_t** d_tbl)
+{
+  std::vector<uint32_t> t;
+  lte_rm_rx_table(K, rv, t);
+  for (auto& v : t) {
+    const uint32_t p = v / 3, s = v % 3;
+    v = s == 0 ? (p < K ? p : (1u << 30) | (p - K)) : (2u << 30) | (s == 1 ? p : K + 4 + p);
+  }
+  return upload(d_tbl, t);
+}
+
+// the levels of one axis of modulation mod (1 QPSK .. 4 256QAM) for each of its 2^mod bit patterns (36.211 7.1.2-7.1.5, lte_tables.c:57-262)
+void constellation_levels(int mod, float* lvl)
+{
+  for (uint32_t idx = 0; idx < (1u << mod); idx++) {
+    double v = 1.0;
+    for (int i = mod - 1; i >= 1; i--) v = (double)(1 << (mod - i)) - (1 - 2 * (int)((idx >> (mod - 1 - i)) & 1)) * v;
+    const double norm = mod == 1 ? sqrt(2.0) : (mod == 2 ? sqrt(10.0) : (mod == 3 ? sqrt(42.0) : sqrt(170.0)));
+    lvl[idx]          = (float)((1 - 2 * (int)((idx >> (mod - 1)) & 1)) * v / norm);
+  }
+}
+
+// srslte_rm_conv_tx (rm_conv.c:44-89) for a CQI report of cqi_len bits (+ 8 CRC bits): the coded bits 3 i + stream in the order the sub-block
+// interleaved streams are read, dummies skipped - one turn of the circular buffer
+std::vector<uint16_t> cqi_rm_conv_order(uint32_t cqi_len)
+{
+  static const uint8_t perm[32] = {1, 17, 9, 25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31, 0, 16, 8, 24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30};
+  const int             F = (int)cqi_len + 8, nrows = (F - 1) / 32 + 1, ndummy = nrows * 32 - F;
+  std::vector<uint16_t> w;
+  for (int s = 0; s < 3; s++) {
+    for (int j = 0; j < 32; j++) {
+      for (int i = 0; i < nrows; i++) {
+        const int pos = i * 32 + perm[j];
+        if (pos >= ndummy) w.push_back((uint16_t)((pos - ndummy) * 3 + s));
+      }
+    }
+  }
+  return w;
+}
+
+// srslte_refsignal_cs_put_sf (refsignal_dl.c:253-272) as a grid initialiser: the CRS of `port` in its first nsym CRS symbols (ports 0 / 1:
+// 0, nsl - 3, nsl, 2 nsl - 3; ports 2 / 3: 1, nsl + 1) -> -(pilot index + 2) in src, a subframe of 12 P sub-carriers per symbol
+void crs_src_put(int32_t* src, uint32_t port, int nsym, uint32_t nsl, uint32_t P, uint32_t cell_id)
+{
+  for (int l = 0; l < nsym; l++) {
+    const uint32_t sym = port >= 2 ? 1 + nsl * l : ((l & 1) ? (l / 2 + 1) * nsl - 3 : (l / 2) * nsl), fidx = ((((l + port) & 1) ? 3 : 0) + cell_id % 6) % 6;
+    for (uint32_t i = 0; i < 2 * P; i++) src[sym * 12 * P + fidx + 6 * i] = -(int32_t)(l * 2 * P + i) - 2;
+  }
+}
+
+// A call's descriptors are built in one of four pinned host buffers and copied asynchronously: the host does not wait for the stream, only,
+// four calls later, for the copy that last read the buffer it takes
+struct PinnedRing {
+  uint8_t*   pin[4]  = {};
+  hipEvent_t ev[4]   = {};
+  bool       used[4] = {};
+  uint32_t   next = 0, cur = 0;
+  int init(size_t bytes)
+  {
+    for (int i = 0; i < 4; i++) {
+      HIP_TRY(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+      HIP_TRY(hipHostMalloc((void**)&pin[i], bytes));
+    }
+    return SRSLTE_SUCCESS;
+  }
+  // the next buffer, once the copy that last read it has completed
+  int acquire(uint8_t** h)
+  {
+    cur = next++ & 3u;
+    if (used[cur]) HIP_TRY(hipEventSynchronize(ev[cur]));
+    *h = pin[cur];
+    return SRSLTE_SUCCESS;
+  }
+  // the acquired buffer is free again when what st holds so far (the copy that reads it among it) has run
+  int release(hipStream_t st)
+  {
+    HIP_TRY(hipEventRecord(ev[cur], st));
+    used[cur] = true;
+    return SRSLTE_SUCCESS;
+  }
+  void destroy()
+  {
+    for (int i = 0; i < 4; i++) {
+      if (pin[i]) (void)hipHostFree(pin[i]);
+      if (ev[i]) (void)hipEventDestroy(ev[i]); // also when the allocation right after its creation failed
+    }
+  }
+};
 
 } // namespace

@@ -11,12 +11,8 @@ struct GrantsState {
   float*             d_csi;     // [B][max_re], cfg.csi_enable
   uint32_t*          d_csi_max; // [B]
   size_t             desc_bytes;
-  // descriptors of a call are built in one of four pinned host buffers and copied asynchronously: the host does not wait for the stream
-  uint8_t*   h_pin[4];
-  hipEvent_t h_ev[4];
-  bool       h_used[4];
-  uint32_t   h_slot;
-  bool       tb_direct; // 16-bit calls: the decoders assemble the transport blocks (environment SRSLTE_HIP_GRANTS_TB_DIRECT=0: the assembly kernel, for A/B and tests)
+  PinnedRing         ring; // the host copies of the descriptor block, desc_bytes + 16 each
+  bool               tb_direct; // 16-bit calls: the decoders assemble the transport blocks (environment SRSLTE_HIP_GRANTS_TB_DIRECT=0: the assembly kernel, for A/B and tests)
   std::map<std::pair<uint32_t, uint32_t>, uint32_t*>   rm_tbl; // (K, rv) -> slot table in the layout of that K's decoder
   std::map<uint32_t, uint32_t*>                        crc_fac; // tbs -> tb_crc_bytes_kernel's 256 chunk weights
 };
@@ -72,20 +68,6 @@ extern "C" void srslte_hip_dl_rx_destroy(srslte_hip_dl_rx_t* q)
   }
   grants_free(q->gs);
   delete q;
-}
-
-// rate de-matching table of redundancy version rv in the decoder's input layout (rm_turbo.c:160-260)
-static int dl_rx_rm_table(srslte_hip_dl_rx_t* q, uint32_t rv, uint32_t** d_tbl)
-{
-  const uint32_t        K = q->seg.K1;
-  std::vector<uint32_t> t;
-  lte_rm_rx_table(K, rv, t);
-  if (q->W) {
-    for (auto& v : t) {
-      v = v < 3 * K ? (v % 3) * (K + 32) + ((v / 3) % (K / q->W)) * q->W + (v / 3) / (K / q->W) : (v - 3 * K) + 3 * (K + 32);
-    }
-  }
-  return upload(d_tbl, rm_slot_table(t, q->in_stride)); // in_stride is a multiple of 32
 }
 
 // cw: 0 = a whole pipeline; 1 = the back end of the second codeword of a two-layer mode (cfg->mod / tbs already those of that codeword):
@@ -177,7 +159,7 @@ static srslte_hip_dl_rx_t* dl_rx_create_impl(const srslte_hip_dl_rx_cfg_t* cfg, 
   q->W         = cfg->llr_8bit ? srslte_hip_tdec_autoimp_get_subblocks_8bit(K) : srslte_hip_tdec_autoimp_get_subblocks(K);
   q->in_stride = (srslte_hip_tdec_input_len(K, q->W != 0) + 31) & ~31u;
   if (ok) {
-    ok                = dl_rx_rm_table(q, 0, &q->d_rm_tbl) == SRSLTE_SUCCESS;
+    ok                = rm_rx_table_upload(K, 0, q->W, q->in_stride, &q->d_rm_tbl) == SRSLTE_SUCCESS;
     q->d_rm_tbl_rv[0] = q->d_rm_tbl;
   }
   // TB CRC24A remainders x^(tbs+24-1-j) mod g
@@ -412,24 +394,8 @@ extern "C" int srslte_hip_dl_rx_stage(srslte_hip_dl_rx_t* q, int stage, const vo
       g.combine = q->harq_combine;
       g.skip    = q->harq_combine ? q->d_cb_ok : nullptr;
       const uint32_t* tbl = q->d_rm_tbl_rv[q->harq_rv];
-      if (q->cfg.llr_8bit) {
-        if (rm_fits_lds(g, 1)) {
-          hipLaunchKernelGGL(rm_rx_lds_kernel<int8_t>, dim3(nof_sf * C), dim3(256), rm_lds_bytes(g, 1), st, (const int8_t*)q->d_e, (int8_t*)q->d_w,
-                             tbl, g);
-        } else {
-          hipLaunchKernelGGL(rm_rx_kernel<int8_t>, dim3(ceil_div(g.w_stride, 1024), nof_sf * C), dim3(256), 0, st, (const int8_t*)q->d_e,
-                             (int8_t*)q->d_w, tbl, g);
-        }
-      } else {
-        if (rm_fits_lds(g)) {
-          hipLaunchKernelGGL(rm_rx_lds_kernel<int16_t>, dim3(nof_sf * C), dim3(256), rm_lds_bytes(g, 2), st, (const int16_t*)q->d_e, q->d_w, tbl, g);
-        } else {
-          hipLaunchKernelGGL(rm_rx_kernel<int16_t>, dim3(ceil_div(g.w_stride, 512), nof_sf * C), dim3(256), 0, st, (const int16_t*)q->d_e,
-                             q->d_w, tbl, g);
-        }
-      }
-      LAUNCH_CHECK();
-      return SRSLTE_SUCCESS;
+      if (q->cfg.llr_8bit) return rm_rx_launch<int8_t>(rm_lds_bytes(g, 1), nof_sf * C, q->d_e, q->d_w, tbl, g, st);
+      return rm_rx_launch<int16_t>(rm_lds_bytes(g, 2), nof_sf * C, q->d_e, q->d_w, tbl, g, st);
     }
     case 4:
       if (q->cw1) {
@@ -505,7 +471,7 @@ extern "C" int srslte_hip_dl_rx_batch_harq2(srslte_hip_dl_rx_t* q, const void* d
     srslte_hip_dl_rx_t* o = objs[c];
     if (!o) continue;
     if (!o->d_rm_tbl_rv[rv[c]]) {
-      if (int r = dl_rx_rm_table(o, rv[c], &o->d_rm_tbl_rv[rv[c]])) return r;
+      if (int r = rm_rx_table_upload(o->seg.K1, rv[c], o->W, o->in_stride, &o->d_rm_tbl_rv[rv[c]])) return r;
     }
     o->harq_rv      = rv[c];
     o->harq_combine = new_data[c] ? 0 : 1;

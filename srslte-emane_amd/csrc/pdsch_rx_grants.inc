@@ -45,28 +45,14 @@ static int grants_alloc(GrantsState* g, uint32_t max_re, uint32_t V, uint32_t Cm
   g->V        = V;
   {
     const char* e = getenv("SRSLTE_HIP_GRANTS_TB_DIRECT");
-    g->tb_direct  = SRSLTE_HIP_GRANTS_TB_DIRECT != 0 && !(e && e[0] == '0');
+    g->tb_direct  = !(e && e[0] == '0');
   }
   g->tdec     = srslte_hip_tdec_create(6144, g->V * g->Cmax);
-  g->d_relist = g->d_scr = g->d_basis = g->d_cb_iters = nullptr;
-  g->d_e = g->d_w = nullptr;
-  g->d_cb_bytes = g->d_cb_ok = g->d_desc = nullptr;
-  g->d_csi = nullptr; g->d_csi_max = nullptr;
-  g->h_slot = 0;
-  for (int i = 0; i < 4; i++) {
-    g->h_pin[i]  = nullptr;
-    g->h_ev[i]   = nullptr;
-    g->h_used[i] = false;
-  }
   if (!g->tdec) return SRSLTE_ERROR;
   if (gold_basis_upload(g->words, &g->d_basis)) return SRSLTE_ERROR;
   const size_t nblk = (size_t)g->V * g->Cmax;
-  // ... and, at the very end, one byte per slot: its transport block's code-block count (the decoders' own transport-block assembly, tdec_set_tb_ragged)
   g->desc_bytes     = sizeof(GrantDev) * g->V + sizeof(SfDesc) * g->V + sizeof(CbDesc) * nblk + sizeof(uint32_t) * nblk + extra_desc_bytes + ((g->V + 15) & ~15u);
-  for (int i = 0; i < 4; i++) {
-    HIP_TRY(hipEventCreateWithFlags(&g->h_ev[i], hipEventDisableTiming));
-    HIP_TRY(hipHostMalloc((void**)&g->h_pin[i], g->desc_bytes + 16)); // + 16: copied in 16-byte words (grants_prep_kernel)
-  }
+  if (g->ring.init(g->desc_bytes + 16)) return SRSLTE_ERROR; // + 16: copied in 16-byte words (grants_prep_kernel, desc_copy_kernel)
   if (relist_rows) HIP_TRY(hipMalloc((void**)&g->d_relist, sizeof(uint32_t) * (size_t)g->max_re * relist_rows));
   HIP_TRY(hipMalloc((void**)&g->d_scr, sizeof(uint32_t) * (size_t)g->words * g->V));
   HIP_TRY(hipMalloc((void**)&g->d_e, sizeof(int16_t) * ((size_t)g->max_bits * g->V + 16)));
@@ -97,11 +83,43 @@ static void grants_free(GrantsState* g)
   }
   for (auto& kv : g->rm_tbl) (void)hipFree(kv.second);
   for (auto& kv : g->crc_fac) (void)hipFree(kv.second);
-  for (int i = 0; i < 4; i++) {
-    if (g->h_pin[i]) (void)hipHostFree(g->h_pin[i]);
-    if (g->h_ev[i]) (void)hipEventDestroy(g->h_ev[i]); // also when the allocation right after its creation failed
-  }
+  g->ring.destroy();
   delete g;
+}
+
+// The sections of a descriptor block of a grants mode, host or device copy: GrantDev[V] | SfDesc[V] | CbDesc[V Cmax] | block map[V Cmax] |
+// the caller's extra_desc_bytes | cof[(V + 15) & ~15], one byte per slot: its transport block's code-block count (the decoders' own
+// transport-block assembly, tdec_set_tb_ragged)
+struct GrantsDesc {
+  GrantDev* gr;
+  SfDesc*   sf;
+  CbDesc*   cb;
+  uint32_t* map;
+  uint8_t * extra, *cof;
+  GrantsDesc(const GrantsState* g, uint8_t* base)
+  {
+    const size_t nblk = (size_t)g->V * g->Cmax;
+    gr    = reinterpret_cast<GrantDev*>(base);
+    sf    = reinterpret_cast<SfDesc*>(gr + g->V);
+    cb    = reinterpret_cast<CbDesc*>(sf + g->V);
+    map   = reinterpret_cast<uint32_t*>(cb + nblk);
+    extra = reinterpret_cast<uint8_t*>(map + nblk);
+    cof   = base + g->desc_bytes - ((g->V + 15) & ~15u);
+  }
+};
+
+// Direct assembly: the decoders assemble the transport blocks themselves (16-bit LLRs, unless SRSLTE_HIP_GRANTS_TB_DIRECT=0), when none of the
+// call's has more blocks than their CRC factor table covers (TDEC_TB_MAX_C_DIRECT). Writes the block counts of slots 0 .. n-1 to h.cof;
+// counts(v): slot v holds a transport block of this call. Returns d.cof, or null: tb_crc_bytes_kernel assembles
+template <typename Counts>
+static const uint8_t* grants_direct_cof(const GrantsState* g, const GrantsDesc& h, const GrantsDesc& d, uint32_t n, bool l8, Counts counts)
+{
+  uint32_t max_C = 0;
+  for (uint32_t v = 0; v < n; v++) {
+    h.cof[v] = (uint8_t)h.sf[v].C;
+    if (counts(v)) max_C = std::max(max_C, (uint32_t)h.sf[v].C);
+  }
+  return !l8 && g->tb_direct && max_C <= TDEC_TB_MAX_C_DIRECT ? d.cof : nullptr;
 }
 
 static int grants_init(srslte_hip_dl_rx_t* q)
@@ -117,13 +135,8 @@ static int grants_rm_table(GrantsState* g, uint32_t K, uint32_t rv, uint32_t W, 
 {
   auto it = g->rm_tbl.find({K, rv});
   if (it == g->rm_tbl.end()) {
-    std::vector<uint32_t> t;
-    lte_rm_rx_table(K, rv, t);
-    if (W) {
-      for (auto& v : t) v = v < 3 * K ? (v % 3) * (K + 32) + ((v / 3) % (K / W)) * W + (v / 3) / (K / W) : (v - 3 * K) + 3 * (K + 32);
-    }
     uint32_t* d = nullptr;
-    if (upload(&d, rm_slot_table(t, w_len))) return SRSLTE_ERROR;
+    if (rm_rx_table_upload(K, rv, W, w_len, &d)) return SRSLTE_ERROR;
     it = g->rm_tbl.emplace(std::make_pair(K, rv), d).first;
   }
   *d_tbl = it->second;
@@ -310,19 +323,8 @@ static int grants_back_end(GrantsState* g, const GrantsBuild& bd, const SfDesc* 
     rg.cbd = d_cb; rg.cb_ok_rst = g->d_cb_ok; rg.C = (int)g->Cmax; rg.tti0 = (int)tti0; rg.max_bits = (int)g->max_bits; rg.w_stride = (int)g->stride;
     rg.Nl = 1; rg.skip = g->d_cb_ok; rg.max_re = (int)g->max_re; rg.csi = g->d_csi; rg.csi_max = g->d_csi_max;
     const int lds = (int)((bd.max_seg + 15) & ~15u);
-    const uint32_t ncb = bd.ncb;
-    if (l8 && lds <= 64 * 1024) {
-      hipLaunchKernelGGL(rm_rx_lds_kernel<int8_t>, dim3(ncb), dim3(256), lds, st, (const int8_t*)g->d_e, (int8_t*)g->d_w, (const uint32_t*)nullptr, rg);
-    } else if (l8) {
-      hipLaunchKernelGGL(rm_rx_kernel<int8_t>, dim3(ceil_div((int)g->stride, 1024), ncb), dim3(256), 0, st, (const int8_t*)g->d_e, (int8_t*)g->d_w,
-                         (const uint32_t*)nullptr, rg);
-    } else if (lds <= 64 * 1024) {
-      hipLaunchKernelGGL(rm_rx_lds_kernel<int16_t>, dim3(ncb), dim3(256), lds, st, (const int16_t*)g->d_e, g->d_w, (const uint32_t*)nullptr, rg);
-    } else {
-      hipLaunchKernelGGL(rm_rx_kernel<int16_t>, dim3(ceil_div((int)g->stride, 512), ncb), dim3(256), 0, st, (const int16_t*)g->d_e, g->d_w,
-                         (const uint32_t*)nullptr, rg);
-    }
-    LAUNCH_CHECK();
+    if (int r = l8 ? rm_rx_launch<int8_t>(lds, bd.ncb, g->d_e, g->d_w, nullptr, rg, st) : rm_rx_launch<int16_t>(lds, bd.ncb, g->d_e, g->d_w, nullptr, rg, st))
+      return r;
     tdec_set_tb_syndrome(g->tdec, nullptr, 1, nullptr);
     tdec_set_skip(g->tdec, g->d_cb_ok);
     // every block length of the batch in one call: one launch per decoder kernel, not one per length (tdec_run_groups)
@@ -411,21 +413,15 @@ static int grants_run(srslte_hip_dl_rx_t* q, const void* d_iq, uint32_t tti0, ui
   hipStream_t    st = (hipStream_t)stream;
   const uint32_t P = q->cfg.nof_prb, cell_id = q->cfg.cell_id, B = q->cfg.max_batch, V = g->V;
   const int      npt = q->pg.nof_ports;
-  const size_t   nblk = (size_t)V * g->Cmax;
-  const uint32_t hs = g->h_slot++ & 3u;
-  if (g->h_used[hs]) HIP_TRY(hipEventSynchronize(g->h_ev[hs])); // the copy that last read this buffer (four calls ago) has completed
-  auto*          h_gr = reinterpret_cast<GrantDev*>(g->h_pin[hs]);
-  auto*          h_sf = reinterpret_cast<SfDesc*>(h_gr + V);
-  auto*          h_cb = reinterpret_cast<CbDesc*>(h_sf + V);
-  auto*          h_map = reinterpret_cast<uint32_t*>(h_cb + nblk);
-  auto*          d_gr = reinterpret_cast<GrantDev*>(g->d_desc);
-  auto*          d_sf = reinterpret_cast<SfDesc*>(d_gr + V);
-  auto*          d_cb = reinterpret_cast<CbDesc*>(d_sf + V);
-  auto*          d_map = reinterpret_cast<uint32_t*>(d_cb + nblk);
+  uint8_t*       h_pin = nullptr;
+  if (int r = g->ring.acquire(&h_pin)) return r;
+  const GrantsDesc h(g, h_pin), d(g, g->d_desc);
+  GrantDev*        h_gr = h.gr;
+  SfDesc*          h_sf = h.sf;
   const bool         l8 = q->cfg.llr_8bit != 0; // the 8-bit LLR path the applications select (pdsch.c:760-779, sch.c:336-356): same buffers, as bytes
   bool               any_mimo = false;
   GrantsBuild        bd;
-  bd.g = g; bd.h_sf = h_sf; bd.h_cb = h_cb; bd.l8 = l8; bd.max_tbs = q->cfg.tbs; bd.npt = npt; bd.max_mod = 4; bd.who = "dl_rx";
+  bd.g = g; bd.h_sf = h_sf; bd.h_cb = h.cb; bd.l8 = l8; bd.max_tbs = q->cfg.tbs; bd.npt = npt; bd.max_mod = 4; bd.who = "dl_rx";
   auto add_tb = [&](uint32_t b, uint32_t v, int mod, uint32_t tbs, uint32_t rv, int new_data, uint32_t nre, uint32_t Nl) -> int {
     return bd.add_tb(b, v, mod, tbs, rv, new_data, nre, Nl);
   };
@@ -472,40 +468,29 @@ static int grants_run(srslte_hip_dl_rx_t* q, const void* d_iq, uint32_t tti0, ui
       sd1.scheme = g2.tx_scheme; sd1.nof_tb = 2; sd1.codebook = sd.codebook;
     }
   }
-  bd.fill_map(h_map);
-  // 16-bit LLRs: the decoders assemble the transport blocks themselves (a byte per slot: its block count), when none of the call's has more
-  // blocks than their CRC factor table covers (TDEC_TB_MAX_C_DIRECT)
-  uint8_t* h_cof = g->h_pin[hs] + g->desc_bytes - ((V + 15) & ~15u);
-  uint32_t max_C = 0;
-  for (uint32_t v = 0; v < V; v++) {
-    h_cof[v] = (uint8_t)h_sf[v].C;
-    if (v % B < nof_sf) max_C = std::max(max_C, (uint32_t)h_sf[v].C); // the other slots keep an earlier call's descriptors
-  }
-  const bool direct = !l8 && g->tb_direct && max_C <= TDEC_TB_MAX_C_DIRECT;
-  const uint8_t* d_cof = direct ? g->d_desc + g->desc_bytes - ((V + 15) & ~15u) : nullptr;
+  bd.fill_map(h.map);
+  // slots of subframes nof_sf .. B - 1 keep an earlier call's descriptors
+  const uint8_t* d_cof = grants_direct_cof(g, h, d, V, l8, [&](uint32_t v) { return v % B < nof_sf; });
   // stages 0, 1: OFDM demodulation and channel estimation do not depend on the grants
   int r = q->grid_in ? SRSLTE_SUCCESS : srslte_hip_dl_rx_stage(q, 0, d_iq, tti0, nof_sf, d_tb, tb_stride, d_tb_ok, stream); // grids from the caller: no OFDM stage
   if (!r) r = srslte_hip_dl_rx_stage(q, 1, d_iq, tti0, nof_sf, d_tb, tb_stride, d_tb_ok, stream);
   if (r) return r;
-  // the descriptors: copied by the preparation launch itself (its last workgroups; the grants it needs are read from the pinned buffer)
-  const bool by_kernel = SRSLTE_HIP_GRANTS_DESC_BY_KERNEL != 0;
-  if (!by_kernel) HIP_TRY(hipMemcpyAsync(g->d_desc, g->h_pin[hs], g->desc_bytes, hipMemcpyHostToDevice, st));
   const uint32_t nrows = (second_rows && V > B) ? 2 * nof_sf : nof_sf; // transport-block rows of the call
-  { // RE lists and scrambling sequences (with the second codewords' when a two-layer grant is among them): one launch
+  { // RE lists and scrambling sequences (with the second codewords' when a two-layer grant is among them) and the descriptors: one launch,
+    // whose last workgroups copy the descriptors (the grants the first ones need are read from the pinned buffer)
     const int       per = ceil_div((int)g->words, RELIST_THREADS), work = (int)(nof_sf + (any_mimo ? 2 : 1) * nof_sf * per);
-    const int       n16 = (int)((g->desc_bytes + 15) / 16), copy_wgs = by_kernel ? ceil_div(n16, RELIST_THREADS) : 0;
-    const GrantDev* src = by_kernel ? (const GrantDev*)h_gr : (const GrantDev*)d_gr;
-    hipLaunchKernelGGL(grants_prep_kernel, dim3(work + copy_wgs), dim3(RELIST_THREADS), 0, st, src, g->d_relist, (int)P,
+    const int       n16 = (int)((g->desc_bytes + 15) / 16);
+    const GrantDev* src = h_gr;
+    hipLaunchKernelGGL(grants_prep_kernel, dim3(work + ceil_div(n16, RELIST_THREADS)), dim3(RELIST_THREADS), 0, st, src, g->d_relist, (int)P,
                        (int)cell_id, (int)g->max_re, q->pg.nof_ports, q->cfg.cp_ext ? 6 : 7, (int)nof_sf, (const uint32_t*)g->d_basis, g->d_scr,
-                       any_mimo ? src + B : (const GrantDev*)nullptr, g->d_scr + (size_t)B * g->words, (int)g->words, d_tb_ok,
-                       (int)nrows, (const uint4*)g->h_pin[hs], (uint4*)g->d_desc, n16, work);
+                       any_mimo ? src + B : nullptr, g->d_scr + (size_t)B * g->words, (int)g->words, d_tb_ok,
+                       (int)nrows, (const uint4*)h_pin, (uint4*)g->d_desc, n16, work);
   }
   LAUNCH_CHECK();
-  HIP_TRY(hipEventRecord(g->h_ev[hs], st)); // the pinned buffer is free again when this launch (resp. the copy) has run
-  g->h_used[hs] = true;
+  if (int r = g->ring.release(st)) return r; // the pinned buffer is free again when this launch has run
   {
     PdschGeom pg = q->pg;
-    pg.desc = d_sf; pg.tti0 = (int)tti0; pg.max_re = (int)g->max_re; pg.max_bits = (int)g->max_bits; pg.csi = g->d_csi; pg.csi_max = g->d_csi_max;
+    pg.desc = d.sf; pg.tti0 = (int)tti0; pg.max_re = (int)g->max_re; pg.max_bits = (int)g->max_bits; pg.csi = g->d_csi; pg.csi_max = g->d_csi_max;
     if (g->d_csi_max) HIP_TRY(hipMemsetAsync(g->d_csi_max, 0, sizeof(uint32_t) * V, st));
     const cf32* grid = q->grid_in ? q->grid_in : q->d_grid;
     if (pg.nof_ports == 4) {
@@ -547,7 +532,7 @@ static int grants_run(srslte_hip_dl_rx_t* q, const void* d_iq, uint32_t tti0, ui
     }
     LAUNCH_CHECK();
   }
-  return grants_back_end(g, bd, d_sf, d_cb, d_map, tti0, q->cfg.max_iterations, nrows, nof_sf, B, d_tb, tb_stride, d_tb_ok, st, d_cof);
+  return grants_back_end(g, bd, d.sf, d.cb, d.map, tti0, q->cfg.max_iterations, nrows, nof_sf, B, d_tb, tb_stride, d_tb_ok, st, d_cof);
 }
 
 // ---- srslte_hip_dl_rx_pool_*: `depth` pipelines behind one submission call (phy_hip.h)

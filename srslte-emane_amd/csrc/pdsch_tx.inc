@@ -199,10 +199,7 @@ struct TxGrantsState {
   int32_t*  d_crs_src[4]; // per port: grid RE -> -1 (zero) or the CRS pilot -(v + 2), for pdsch_tx_map_kernel as the grid initialiser
   int32_t*  d_crs_src_sp[4]; // the same for a TDD special subframe: the CRS symbols its DwPTS holds (refsignal_dl.c:162-225), or null
   size_t    desc_bytes;
-  uint8_t*   h_pin[4];
-  hipEvent_t h_ev[4];
-  bool       h_used[4];
-  uint32_t   h_slot;
+  PinnedRing ring; // the host copies of the descriptor block
   TxLevels   lv;
   std::map<std::pair<uint32_t, uint32_t>, uint32_t*> rm_tbl; // (K, rv) -> rate-matching table over the encoder's byte streams
 };
@@ -216,12 +213,7 @@ static void tx_grants_free(TxGrantsState* g)
     if (b) (void)hipFree(b);
   }
   for (auto& kv : g->rm_tbl) (void)hipFree(kv.second);
-  for (int i = 0; i < 4; i++) {
-    if (g->h_pin[i]) {
-      (void)hipHostFree(g->h_pin[i]);
-      (void)hipEventDestroy(g->h_ev[i]);
-    }
-  }
+  g->ring.destroy();
   delete g;
 }
 
@@ -242,18 +234,6 @@ extern "C" void srslte_hip_dl_tx_destroy(srslte_hip_dl_tx_t* q)
   }
   tx_grants_free(q->gs);
   delete q;
-}
-
-static int dl_tx_rm_table(srslte_hip_dl_tx_t* q, uint32_t rv)
-{ // rate matching (rm_turbo.c:100-158): coded bit of each circular-buffer position read from k0(rv), addressed in the encoder's byte streams
-  const uint32_t        K = q->seg.K1;
-  std::vector<uint32_t> t;
-  lte_rm_rx_table(K, rv, t);
-  for (auto& v : t) {
-    const uint32_t p = v / 3, s = v % 3;
-    v = s == 0 ? (p < K ? p : (1u << 30) | (p - K)) : (2u << 30) | (s == 1 ? p : K + 4 + p);
-  }
-  return upload(&q->d_rm[rv], t);
 }
 
 extern "C" srslte_hip_dl_tx_t* srslte_hip_dl_tx_create(const srslte_hip_dl_tx_cfg_t* cfg)
@@ -305,10 +285,8 @@ extern "C" srslte_hip_dl_tx_t* srslte_hip_dl_tx_create(const srslte_hip_dl_tx_cf
         for (uint32_t l = 0; l < 3; l++) {
           for (uint32_t i = 0; i < 6 * P; i++) src[(2 + 4 * l) * nre + (l == 1 ? 1 : 0) + 2 * i] = -(int32_t)(l * 6 * P + i) - 2 - MBSFN_REF;
         }
-      }
-      for (int l = 0; l < (cfg->mbsfn ? 0 : (port < 2 ? 4 : 2)); l++) { // srslte_refsignal_cs_put_sf (refsignal_dl.c:253-272): ports 0/1 symbols 0, 4, 7, 11; ports 2/3 symbols 1, 8
-        const uint32_t sym = port >= 2 ? 1 + nsl * l : ((l & 1) ? (l / 2 + 1) * nsl - 3 : (l / 2) * nsl), fidx = ((((l + port) & 1) ? 3 : 0) + cfg->cell_id % 6) % 6;
-        for (uint32_t i = 0; i < 2 * P; i++) src[sym * nre + fidx + 6 * i] = -(int32_t)(l * 2 * P + i) - 2;
+      } else {
+        crs_src_put(src.data(), port, port < 2 ? 4 : 2, nsl, P, cfg->cell_id);
       }
       ok             = upload(&q->d_src[c][port], src) == SRSLTE_SUCCESS;
       g.src[c][port] = q->d_src[c][port];
@@ -325,7 +303,7 @@ extern "C" srslte_hip_dl_tx_t* srslte_hip_dl_tx_create(const srslte_hip_dl_tx_cf
     }
     ok = upload(&q->d_scr, scr) == SRSLTE_SUCCESS;
   }
-  ok = ok && dl_tx_rm_table(q, 0) == SRSLTE_SUCCESS;
+  ok = ok && rm_tx_table_upload(K, 0, &q->d_rm[0]) == SRSLTE_SUCCESS;
   PuschTxGeom& cg = q->cg;
   cg.C = (int)C; cg.K = (int)K; cg.tbs = (int)cfg->tbs; cg.rlenB = (int)((C == 1 ? K : K - 24) / 8); cg.cb_stride = (int)((K / 8 + 15) & ~15u);
   cg.par_stride = (int)((K / 4 + 1 + 15) & ~15u);
@@ -334,13 +312,7 @@ extern "C" srslte_hip_dl_tx_t* srslte_hip_dl_tx_create(const srslte_hip_dl_tx_cf
   g.tdd_s6 = -1; // the fixed-grant calls are FDD (srslte_hip_dl_tx_batch refuses a TDD cell); the grants mode sets its own
   g.grid_len = (int)glen; g.max_re = (int)max_re; g.Qm = (int)Qm; g.Nl = npt > 1 ? 2 : 1; g.nof_ports = (int)npt; g.scr_words = (int)scr_words;
   g.C = (int)C; g.K = (int)K; g.cb_stride = cg.cb_stride; g.par_stride = cg.par_stride; g.rm_len = (int)(3 * K + 12);
-  for (uint32_t idx = 0; idx < (1u << cfg->mod); idx++) { // 36.211 7.1.2-7.1.5, one axis (lte_tables.c:57-262)
-    const int    nb = cfg->mod;
-    double       v  = 1.0;
-    for (int i = nb - 1; i >= 1; i--) v = (double)(1 << (nb - i)) - (1 - 2 * (int)((idx >> (nb - 1 - i)) & 1)) * v;
-    const double norm = nb == 1 ? sqrt(2.0) : (nb == 2 ? sqrt(10.0) : (nb == 3 ? sqrt(42.0) : sqrt(170.0)));
-    g.lvl[idx]        = (float)((1 - 2 * (int)((idx >> (nb - 1)) & 1)) * v / norm);
-  }
+  constellation_levels(cfg->mod, g.lvl);
   const float rho_a = powf(10.0f, cfg->p_a / 20.0f) * (npt == 1 ? 1.0f : sqrtf(2.0f)); // pdsch.c:525
   g.gain            = npt == 1 ? rho_a : rho_a / sqrtf(2.0f);                          // precoding.c:1859-1860
   ok = ok && hipMalloc((void**)&q->d_tbcrc, sizeof(uint32_t) * B) == hipSuccess &&
@@ -379,7 +351,7 @@ extern "C" int srslte_hip_dl_tx_batch(srslte_hip_dl_tx_t* q, const uint8_t* d_tb
     return SRSLTE_ERROR;
   }
   if (!q->d_rm[rv]) {
-    if (int r = dl_tx_rm_table(q, rv)) return r;
+    if (int r = rm_tx_table_upload(q->seg.K1, rv, &q->d_rm[rv])) return r;
   }
   hipStream_t st = (hipStream_t)stream;
   PuschTxGeom cg = q->cg;
@@ -419,10 +391,7 @@ static int dl_tx_grants_init(srslte_hip_dl_tx_t* q, uint32_t V)
   g->par_stride = (6144 / 4 + 1 + 15) & ~15u;
   const size_t nblk = (size_t)V * g->Cmax;
   g->desc_bytes     = (sizeof(GrantDev) + sizeof(TxDesc)) * V;
-  for (int i = 0; i < 4; i++) {
-    HIP_TRY(hipEventCreateWithFlags(&g->h_ev[i], hipEventDisableTiming));
-    HIP_TRY(hipHostMalloc((void**)&g->h_pin[i], g->desc_bytes));
-  }
+  if (g->ring.init(g->desc_bytes)) return SRSLTE_ERROR;
   if (gold_basis_upload(g->words, &g->d_basis)) return SRSLTE_ERROR;
   HIP_TRY(hipMalloc((void**)&g->d_relist, sizeof(uint32_t) * (size_t)g->max_re * V));
   HIP_TRY(hipMalloc((void**)&g->d_scr, sizeof(uint32_t) * (size_t)g->words * V));
@@ -432,34 +401,21 @@ static int dl_tx_grants_init(srslte_hip_dl_tx_t* q, uint32_t V)
   HIP_TRY(hipMalloc((void**)&g->d_sys_tail, nblk));
   HIP_TRY(hipMalloc((void**)&g->d_desc, g->desc_bytes));
   HIP_TRY(hipMalloc((void**)&g->d_y, sizeof(cf32) * (size_t)g->max_re * V * npt));
-  for (int port = 0; port < npt; port++) { // srslte_refsignal_cs_put_sf (refsignal_dl.c:253-272), as srslte_hip_dl_tx_create maps it
+  for (int port = 0; port < npt; port++) { // the CRS as srslte_hip_dl_tx_create maps them
     const uint32_t       nsl = q->cfg.cp_ext ? 6 : 7;
     std::vector<int32_t> src((size_t)14 * 12 * P, -1);
-    for (int l = 0; l < (port < 2 ? 4 : 2); l++) {
-      const uint32_t sym = port >= 2 ? 1 + nsl * l : ((l & 1) ? (l / 2 + 1) * nsl - 3 : (l / 2) * nsl), fidx = ((((l + port) & 1) ? 3 : 0) + cell_id % 6) % 6;
-      for (uint32_t i = 0; i < 2 * P; i++) src[sym * 12 * P + fidx + 6 * i] = -(int32_t)(l * 2 * P + i) - 2;
-    }
+    crs_src_put(src.data(), port, port < 2 ? 4 : 2, nsl, P, cell_id);
     if (upload(&g->d_crs_src[port], src)) return SRSLTE_ERROR;
     if (q->cfg.tdd) { // srslte_refsignal_cs_nof_symbols for a special subframe: by the DwPTS length (phy_common.c:128-135)
       static const int dwt[10] = {3, 9, 10, 11, 12, 3, 9, 10, 11, 6};
       const int dw = dwt[q->cfg.tdd_ss_config % 10], t3 = nsl == 7 ? 12 : 10, t2 = nsl == 7 ? 9 : 8, t1 = nsl == 7 ? 5 : 4;
       const int nsym = dw >= t3 ? (port < 2 ? 4 : 2) : (dw >= t2 ? (port < 2 ? 3 : 2) : (dw >= t1 ? (port < 2 ? 2 : 1) : 1));
       std::vector<int32_t> sp((size_t)14 * 12 * P, -1);
-      for (int l = 0; l < nsym; l++) {
-        const uint32_t sym = port >= 2 ? 1 + nsl * l : ((l & 1) ? (l / 2 + 1) * nsl - 3 : (l / 2) * nsl), fidx = ((((l + port) & 1) ? 3 : 0) + cell_id % 6) % 6;
-        for (uint32_t i = 0; i < 2 * P; i++) sp[sym * 12 * P + fidx + 6 * i] = -(int32_t)(l * 2 * P + i) - 2;
-      }
+      crs_src_put(sp.data(), port, nsym, nsl, P, cell_id);
       if (upload(&g->d_crs_src_sp[port], sp)) return SRSLTE_ERROR;
     }
   }
-  for (int mod = 1; mod <= 4; mod++) { // 36.211 7.1.2-7.1.5, one axis (lte_tables.c:57-262)
-    for (uint32_t idx = 0; idx < (1u << mod); idx++) {
-      double v = 1.0;
-      for (int i = mod - 1; i >= 1; i--) v = (double)(1 << (mod - i)) - (1 - 2 * (int)((idx >> (mod - 1 - i)) & 1)) * v;
-      const double norm = mod == 1 ? sqrt(2.0) : (mod == 2 ? sqrt(10.0) : (mod == 3 ? sqrt(42.0) : sqrt(170.0)));
-      g->lv.v[mod][idx] = (float)((1 - 2 * (int)((idx >> (mod - 1)) & 1)) * v / norm);
-    }
-  }
+  for (int mod = 1; mod <= 4; mod++) constellation_levels(mod, g->lv.v[mod]);
   return SRSLTE_SUCCESS;
 }
 
@@ -489,10 +445,10 @@ extern "C" int srslte_hip_dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_
     q->gs = nullptr;
     return SRSLTE_ERROR;
   }
-  TxGrantsState* g  = q->gs;
-  const uint32_t hs = g->h_slot++ & 3u;
-  if (g->h_used[hs]) HIP_TRY(hipEventSynchronize(g->h_ev[hs]));
-  auto* h_gr = reinterpret_cast<GrantDev*>(g->h_pin[hs]);
+  TxGrantsState* g     = q->gs;
+  uint8_t*       h_pin = nullptr;
+  if (int r = g->ring.acquire(&h_pin)) return r;
+  auto* h_gr = reinterpret_cast<GrantDev*>(h_pin);
   auto* h_td = reinterpret_cast<TxDesc*>(h_gr + V);
   auto* d_gr = reinterpret_cast<GrantDev*>(g->d_desc);
   auto* d_td = reinterpret_cast<TxDesc*>(d_gr + V);
@@ -527,15 +483,9 @@ extern "C" int srslte_hip_dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_
     max_nre = nre > max_nre ? nre : max_nre;
     const uint32_t K  = segs[p].K1;
     auto           it = g->rm_tbl.find({K, gr.rv});
-    if (it == g->rm_tbl.end()) { // rate matching (rm_turbo.c:100-158) addressed in the encoder's byte streams, as dl_tx_rm_table
-      std::vector<uint32_t> t;
-      lte_rm_rx_table(K, gr.rv, t);
-      for (auto& v : t) {
-        const uint32_t pos = v / 3, sidx = v % 3;
-        v = sidx == 0 ? (pos < K ? pos : (1u << 30) | (pos - K)) : (2u << 30) | (sidx == 1 ? pos : K + 4 + pos);
-      }
+    if (it == g->rm_tbl.end()) {
       uint32_t* d = nullptr;
-      if (upload(&d, t)) return SRSLTE_ERROR;
+      if (rm_tx_table_upload(K, gr.rv, &d)) return SRSLTE_ERROR;
       it = g->rm_tbl.emplace(std::make_pair(K, gr.rv), d).first;
     }
     TxDesc& td = h_td[p];
@@ -543,9 +493,8 @@ extern "C" int srslte_hip_dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_
     td.cb0 = (int)cb0; td.nre = (int)nre; td.mod = gr.mod; td.Qm = 2 * gr.mod; td.rm = it->second;
     cb0 += segs[p].C;
   }
-  HIP_TRY(hipMemcpyAsync(g->d_desc, g->h_pin[hs], g->desc_bytes, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipEventRecord(g->h_ev[hs], st));
-  g->h_used[hs] = true;
+  HIP_TRY(hipMemcpyAsync(g->d_desc, h_pin, g->desc_bytes, hipMemcpyHostToDevice, st));
+  if (int r = g->ring.release(st)) return r;
   PdschTxGeom tg = q->g; // ports, N_L, gain; the grid initialiser's maps
   tg.max_re = (int)g->max_re;
   tg.cb_stride = (int)g->cb_stride; tg.par_stride = (int)g->par_stride; // the slots of this mode are spaced for the largest block length

@@ -468,16 +468,7 @@ extern "C" srslte_hip_ul_rx_t* srslte_hip_ul_rx_create(const srslte_hip_ul_rx_cf
   }
   q->W         = C ? srslte_hip_tdec_autoimp_get_subblocks(K) : 0;
   q->in_stride = C ? (srslte_hip_tdec_input_len(K, q->W != 0) + 31) & ~31u : 0;
-  if (ok && C) { // rate-dematching table in the decoder's input layout (rm_turbo.c:160-260), as for the PDSCH
-    std::vector<uint32_t> t;
-    lte_rm_rx_table(K, 0, t);
-    if (q->W) {
-      for (auto& v : t) {
-        v = v < 3 * K ? (v % 3) * (K + 32) + ((v / 3) % (K / q->W)) * q->W + (v / 3) / (K / q->W) : (v - 3 * K) + 3 * (K + 32);
-      }
-    }
-    ok = upload(&q->d_rm_tbl, rm_slot_table(t, q->in_stride)) == SRSLTE_SUCCESS;
-  }
+  if (ok && C) ok = rm_rx_table_upload(K, 0, q->W, q->in_stride, &q->d_rm_tbl) == SRSLTE_SUCCESS; // as for the PDSCH
   if (ok && C) {
     std::vector<uint32_t> rem(cfg->tbs + 24);
     uint32_t              v = 1;
@@ -582,14 +573,7 @@ extern "C" int srslte_hip_ul_rx_batch_harq(srslte_hip_ul_rx_t* q, const void* d_
   const uint32_t* d_rm_tbl = q->d_rm_tbl;
   if (rv && C) {
     if (!q->d_rm_tbl_rv[rv]) {
-      std::vector<uint32_t> t;
-      lte_rm_rx_table(K, rv, t);
-      if (q->W) {
-        for (auto& v : t) {
-          v = v < 3 * K ? (v % 3) * (K + 32) + ((v / 3) % (K / q->W)) * q->W + (v / 3) / (K / q->W) : (v - 3 * K) + 3 * (K + 32);
-        }
-      }
-      if (int rc = upload(&q->d_rm_tbl_rv[rv], rm_slot_table(t, q->in_stride))) return rc;
+      if (int rc = rm_rx_table_upload(K, rv, q->W, q->in_stride, &q->d_rm_tbl_rv[rv])) return rc;
     }
     d_rm_tbl = q->d_rm_tbl_rv[rv];
   }
@@ -634,13 +618,7 @@ extern "C" int srslte_hip_ul_rx_batch_harq(srslte_hip_ul_rx_t* q, const void* d_
   rg.tti0   = (int)tti0;
   rg.combine = combine;
   rg.skip    = combine ? q->d_cb_ok : nullptr;
-  if (rm_fits_lds(rg)) {
-    hipLaunchKernelGGL(rm_rx_lds_kernel<int16_t>, dim3(nof_sf * C), dim3(256), rm_lds_bytes(rg, 2), st, (const int16_t*)q->d_g, q->d_w, d_rm_tbl, rg);
-  } else {
-    hipLaunchKernelGGL(rm_rx_kernel<int16_t>, dim3(ceil_div(rg.w_stride, 512), nof_sf * C), dim3(256), 0, st, (const int16_t*)q->d_g, q->d_w,
-                       d_rm_tbl, rg);
-  }
-  LAUNCH_CHECK();
+  if (int rc = rm_rx_launch<int16_t>(rm_lds_bytes(rg, 2), nof_sf * C, q->d_g, q->d_w, d_rm_tbl, rg, st)) return rc;
   tdec_set_tb_syndrome(q->tdec, q->d_tb_rem, C, q->d_cb_syn);
   tdec_set_skip(q->tdec, combine ? q->d_cb_ok : nullptr);
   r = tdec_run_batch_w(q->tdec, q->d_w, 0, q->in_stride, q->W != 0, K, -1, nof_sf * C, q->cfg.max_iterations, C > 1 ? 0x1800063u : 0x1864CFBu,
@@ -703,24 +681,18 @@ extern "C" int srslte_hip_ul_rx_batch_grants(srslte_hip_ul_rx_t* q, const void* 
     }
     return SRSLTE_ERROR;
   }
-  GrantsState*   g    = q->gs;
-  const size_t   nblk = (size_t)V * g->Cmax;
-  const uint32_t hs   = g->h_slot++ & 3u;
-  if (g->h_used[hs]) HIP_TRY(hipEventSynchronize(g->h_ev[hs])); // the copy that last read this buffer (four calls ago) has completed
-  auto* h_gr = reinterpret_cast<GrantDev*>(g->h_pin[hs]);
-  auto* h_sf = reinterpret_cast<SfDesc*>(h_gr + V);
-  auto* h_cb = reinterpret_cast<CbDesc*>(h_sf + V);
-  auto* h_map = reinterpret_cast<uint32_t*>(h_cb + nblk);
-  auto* h_pd = reinterpret_cast<PuschDesc*>(h_map + nblk);
-  auto* h_it = reinterpret_cast<ChestUlItem*>(h_pd + V);
-  auto* d_gr = reinterpret_cast<GrantDev*>(g->d_desc);
-  auto* d_sf = reinterpret_cast<SfDesc*>(d_gr + V);
-  auto* d_cb = reinterpret_cast<CbDesc*>(d_sf + V);
-  auto* d_map = reinterpret_cast<uint32_t*>(d_cb + nblk);
-  auto* d_pd = reinterpret_cast<PuschDesc*>(d_map + nblk);
-  auto* d_it = reinterpret_cast<ChestUlItem*>(d_pd + V);
+  GrantsState* g     = q->gs;
+  uint8_t*     h_pin = nullptr;
+  if (int r = g->ring.acquire(&h_pin)) return r;
+  const GrantsDesc h(g, h_pin), d(g, g->d_desc);
+  GrantDev*        h_gr = h.gr;
+  SfDesc*          h_sf = h.sf;
+  auto*            h_pd = reinterpret_cast<PuschDesc*>(h.extra); // extra_desc_bytes: PuschDesc[V] | ChestUlItem[V]
+  auto*            h_it = reinterpret_cast<ChestUlItem*>(h_pd + V);
+  auto*            d_pd = reinterpret_cast<PuschDesc*>(d.extra);
+  auto*            d_it = reinterpret_cast<ChestUlItem*>(d_pd + V);
   GrantsBuild bd;
-  bd.g = g; bd.h_sf = h_sf; bd.h_cb = h_cb; bd.l8 = false; bd.max_tbs = q->cfg.tbs; bd.npt = 1; bd.max_mod = 3; bd.who = "ul_rx";
+  bd.g = g; bd.h_sf = h_sf; bd.h_cb = h.cb; bd.l8 = false; bd.max_tbs = q->cfg.tbs; bd.npt = 1; bd.max_mod = 3; bd.who = "ul_rx";
   // PUSCHs in the order (L_prb, n_dmrs): one estimator launch per (L_prb, n_dmrs), one de-precoding launch per L_prb
   std::vector<uint32_t> order(nof_grants);
   for (uint32_t p = 0; p < nof_grants; p++) order[p] = p;
@@ -781,31 +753,17 @@ extern "C" int srslte_hip_ul_rx_batch_grants(srslte_hip_ul_rx_t* q, const void* 
     if (gr.tbs == 0) continue; // no code blocks: row p of d_tb_ok becomes 0
     if (int r = bd.add_tb(p, p, gr.mod, gr.tbs, gr.rv, gr.new_data, nof_re - (uint32_t)Qp_ri - (uint32_t)Qp_cqi, 1, (uint32_t)pd.cqi_Q)) return r;
   }
-  bd.fill_map(h_map);
-  // the decoders assemble the transport blocks and give the verdicts (grants_back_end), when none of the call's has more blocks than their CRC
-  // factor table covers (TDEC_TB_MAX_C_DIRECT)
-  bool     no_tb = false;
-  uint32_t max_C = 0;
-  uint8_t* h_cof = g->h_pin[hs] + g->desc_bytes - ((V + 15) & ~15u);
-  for (uint32_t p = 0; p < nof_grants; p++) {
-    h_cof[p] = (uint8_t)h_sf[p].C;
-    no_tb    = no_tb || grants[p].tbs == 0;
-    max_C    = std::max(max_C, (uint32_t)h_sf[p].C);
-  }
-  const bool direct = g->tb_direct && max_C <= TDEC_TB_MAX_C_DIRECT;
-  const uint8_t* d_cof = direct ? g->d_desc + g->desc_bytes - ((V + 15) & ~15u) : nullptr;
-  if (direct && no_tb) HIP_TRY(hipMemsetAsync(d_tb_ok, 0, nof_grants, st)); // rows without a transport block get no verdict from a decoder
+  bd.fill_map(h.map);
+  const uint8_t* d_cof = grants_direct_cof(g, h, d, nof_grants, false, [](uint32_t) { return true; });
+  bool           no_tb = false;
+  for (uint32_t p = 0; p < nof_grants; p++) no_tb = no_tb || grants[p].tbs == 0;
+  if (d_cof && no_tb) HIP_TRY(hipMemsetAsync(d_tb_ok, 0, nof_grants, st)); // rows without a transport block get no verdict from a decoder
   int r = srslte_hip_ofdm_rx_sf_batch(q->ofdm, d_iq, q->d_grid, (int)nof_sf, stream);
   if (r) return r;
-  if (SRSLTE_HIP_GRANTS_DESC_BY_KERNEL) {
-    const int n16 = (int)((g->desc_bytes + 15) / 16);
-    hipLaunchKernelGGL(desc_copy_kernel, dim3(ceil_div(n16, 256)), dim3(256), 0, st, (const uint4*)g->h_pin[hs], (uint4*)g->d_desc, n16);
-    LAUNCH_CHECK();
-  } else {
-    HIP_TRY(hipMemcpyAsync(g->d_desc, g->h_pin[hs], g->desc_bytes, hipMemcpyHostToDevice, st));
-  }
-  HIP_TRY(hipEventRecord(g->h_ev[hs], st));
-  g->h_used[hs] = true;
+  const int n16 = (int)((g->desc_bytes + 15) / 16);
+  hipLaunchKernelGGL(desc_copy_kernel, dim3(ceil_div(n16, 256)), dim3(256), 0, st, (const uint4*)h_pin, (uint4*)g->d_desc, n16);
+  LAUNCH_CHECK();
+  if (int rc = g->ring.release(st)) return rc;
   for (uint32_t i = 0; i < nof_grants;) { // estimator: runs of equal (L_prb, n_dmrs)
     uint32_t j = i + 1;
     while (j < nof_grants && grants[order[j]].L_prb == grants[order[i]].L_prb && grants[order[j]].n_dmrs == grants[order[i]].n_dmrs) j++;
@@ -813,7 +771,7 @@ extern "C" int srslte_hip_ul_rx_batch_grants(srslte_hip_ul_rx_t* q, const void* 
     if (r) return r;
     i = j;
   }
-  hipLaunchKernelGGL(scr_gen_kernel, dim3(ceil_div((int)g->words, 256), nof_grants), dim3(256), 0, st, (const GrantDev*)d_gr, (const uint32_t*)g->d_basis, g->d_scr,
+  hipLaunchKernelGGL(scr_gen_kernel, dim3(ceil_div((int)g->words, 256), nof_grants), dim3(256), 0, st, (const GrantDev*)d.gr, (const uint32_t*)g->d_basis, g->d_scr,
                      (int)g->words, (int)q->cfg.cell_id);
   hipLaunchKernelGGL(pusch_eq_grants_kernel, dim3(ceil_div((int)max_M, 256), nsymb, nof_grants), dim3(256), 0, st, (const cf32*)q->d_grid, (const cf32*)q->d_ce,
                      (const float*)q->g_res, q->g_z, (const PuschDesc*)d_pd, 12 * (int)P, (int)nsymb, q->cfg.mmse, q->pg.nsl);
@@ -840,5 +798,5 @@ extern "C" int srslte_hip_ul_rx_batch_grants(srslte_hip_ul_rx_t* q, const void* 
                        (const PuschDesc*)d_pd);
   }
   LAUNCH_CHECK();
-  return grants_back_end(g, bd, d_sf, d_cb, d_map, tti0, q->cfg.max_iterations, nof_grants, nof_grants, V, d_tb, tb_stride, d_tb_ok, st, d_cof);
+  return grants_back_end(g, bd, d.sf, d.cb, d.map, tti0, q->cfg.max_iterations, nof_grants, nof_grants, V, d_tb, tb_stride, d_tb_ok, st, d_cof);
 }

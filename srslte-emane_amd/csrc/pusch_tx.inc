@@ -264,13 +264,7 @@ extern "C" srslte_hip_ul_tx_t* srslte_hip_ul_tx_create(const srslte_hip_ul_tx_cf
   g.cqi_stride = (g.Qp_cqi * (int)Qm + 15) & ~15;
   const uint32_t g_re = nof_re - g.ri.Qprime - g.Qp_cqi; // UL-SCH symbols: what the RI and the CQI report leave (sch.c:1157-1160)
   g.syms_lo = C ? (int)(g_re / C) : 0; g.C_lo = C ? (int)(C - g_re % C) : 0; // G' = the UL-SCH symbols, gamma = G' mod C (sch.c:205-207)
-  for (uint32_t idx = 0; idx < (1u << cfg->mod); idx++) { // 36.211 7.1.2-7.1.4, one axis: bits b0 b2 b4 of the symbol (lte_tables.c:57-182)
-    const int    nb = cfg->mod;
-    double       v  = 1.0;
-    for (int i = nb - 1; i >= 1; i--) v = (double)(1 << (nb - i)) - (1 - 2 * (int)((idx >> (nb - 1 - i)) & 1)) * v;
-    const double norm = nb == 1 ? sqrt(2.0) : (nb == 2 ? sqrt(10.0) : sqrt(42.0));
-    g.lvl[idx]        = (float)((1 - 2 * (int)((idx >> (nb - 1)) & 1)) * v / norm);
-  }
+  constellation_levels(cfg->mod, g.lvl); // one axis: bits b0 b2 b4 of the symbol
   q->ofdm = srslte_hip_ofdm_create((int)P, cfg->cp_ext ? 0 : 1, 0);
   q->dmrs = srslte_hip_chest_ul_create(cfg->cell_id, P, cfg->cp_ext ? 0 : 1, &cfg->dmrs_cfg);
   bool ok = q->ofdm && q->dmrs && srslte_hip_ofdm_set_normalize(q->ofdm, 1) == SRSLTE_SUCCESS &&
@@ -284,29 +278,12 @@ extern "C" srslte_hip_ul_tx_t* srslte_hip_ul_tx_create(const srslte_hip_ul_tx_cf
     }
     ok = upload(&q->d_scr, scr) == SRSLTE_SUCCESS;
   }
-  if (ok && C) { // rate matching, rv 0 (rm_turbo.c:100-158): coded bit of each circular-buffer position, addressed in the encoder's byte streams
-    std::vector<uint32_t> t;
-    lte_rm_rx_table(K, 0, t);
-    for (auto& v : t) {
-      const uint32_t p = v / 3, s = v % 3;
-      v = s == 0 ? (p < K ? p : (1u << 30) | (p - K)) : (2u << 30) | (s == 1 ? p : K + 4 + p);
-    }
-    ok = upload(&q->d_rm, t) == SRSLTE_SUCCESS;
-  }
-  if (ok && cfg->cqi_len > 11) { // srslte_rm_conv_tx (rm_conv.c:44-89): the sub-block interleaved streams read circularly, dummies skipped
-    static const uint8_t perm[32] = {1, 17, 9, 25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31, 0, 16, 8, 24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30};
-    const int            F = (int)cfg->cqi_len + 8, nrows = (F - 1) / 32 + 1, K_p = nrows * 32, ndummy = K_p - F, Q = g.Qp_cqi * (int)Qm;
-    std::vector<int>      w;
-    for (int st = 0; st < 3; st++) {
-      for (int j = 0; j < 32; j++) {
-        for (int i = 0; i < nrows; i++) {
-          const int pos = i * 32 + perm[j];
-          if (pos >= ndummy) w.push_back((pos - ndummy) * 3 + st);
-        }
-      }
-    }
-    std::vector<uint16_t> t((size_t)(Q > 0 ? Q : 1));
-    for (int i = 0; i < Q; i++) t[i] = (uint16_t)w[(size_t)i % w.size()];
+  if (ok && C) ok = rm_tx_table_upload(K, 0, &q->d_rm) == SRSLTE_SUCCESS; // rate matching, rv 0
+  if (ok && cfg->cqi_len > 11) { // the CQI report's rate matching: cqi_rm_conv_order read circularly up to Q
+    const std::vector<uint16_t> w = cqi_rm_conv_order(cfg->cqi_len);
+    const int                   Q = g.Qp_cqi * (int)Qm;
+    std::vector<uint16_t>       t((size_t)(Q > 0 ? Q : 1));
+    for (int i = 0; i < Q; i++) t[i] = w[(size_t)i % w.size()];
     ok = upload(&q->d_cqi_rm, t) == SRSLTE_SUCCESS;
   }
   if (ok && cfg->cqi_len) ok = hipMalloc((void**)&q->d_qcqi, (size_t)g.cqi_stride * B + 16) == hipSuccess;
@@ -380,14 +357,7 @@ extern "C" int srslte_hip_ul_tx_batch_rv(srslte_hip_ul_tx_t* q, const uint8_t* d
   const uint32_t* d_rm = q->d_rm;
   if (rv && q->seg.C) {
     if (!q->d_rm_rv[rv]) {
-      const uint32_t        K = q->seg.K1;
-      std::vector<uint32_t> t;
-      lte_rm_rx_table(K, rv, t);
-      for (auto& v : t) {
-        const uint32_t p = v / 3, s = v % 3;
-        v = s == 0 ? (p < K ? p : (1u << 30) | (p - K)) : (2u << 30) | (s == 1 ? p : K + 4 + p);
-      }
-      if (int r = upload(&q->d_rm_rv[rv], t)) return r;
+      if (int r = rm_tx_table_upload(q->seg.K1, rv, &q->d_rm_rv[rv])) return r;
     }
     d_rm = q->d_rm_rv[rv];
   }

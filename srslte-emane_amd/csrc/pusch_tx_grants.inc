@@ -96,10 +96,7 @@ struct UlTxGrantsState {
   uint8_t * d_cb, *d_parity, *d_sys_tail, *d_desc, *d_qcqi;
   cf32 *    d_d, *d_z;
   size_t    desc_bytes;
-  uint8_t*   h_pin[4];
-  hipEvent_t h_ev[4];
-  bool       h_used[4];
-  uint32_t   h_slot;
+  PinnedRing ring; // the host copies of the descriptor block
   TxLevels   lv;
   std::map<std::pair<uint32_t, uint32_t>, uint32_t*> rm_tbl; // (K, rv)
   std::map<uint32_t, std::pair<uint16_t*, uint32_t>> cqi_w;  // report size O > 11 -> (device table, length)
@@ -114,12 +111,7 @@ static void ul_tx_grants_free(UlTxGrantsState* g)
   }
   for (auto& kv : g->rm_tbl) (void)hipFree(kv.second);
   for (auto& kv : g->cqi_w) (void)hipFree(kv.second.first);
-  for (int i = 0; i < 4; i++) {
-    if (g->h_pin[i]) {
-      (void)hipHostFree(g->h_pin[i]);
-      (void)hipEventDestroy(g->h_ev[i]);
-    }
-  }
+  g->ring.destroy();
   delete g;
 }
 
@@ -137,10 +129,7 @@ static int ul_tx_grants_init(srslte_hip_ul_tx_t* q, uint32_t V)
   g->cqi_stride = (g->max_sym * 6 + 15) & ~15u; // a report may take the whole allocation (min(.., M_sc N_symb - Q'_ri), uci.c:264-281)
   const size_t nblk = (size_t)V * g->Cmax;
   g->desc_bytes     = (sizeof(GrantDev) + sizeof(TxDesc) + sizeof(PuschTxDesc)) * V;
-  for (int i = 0; i < 4; i++) {
-    HIP_TRY(hipEventCreateWithFlags(&g->h_ev[i], hipEventDisableTiming));
-    HIP_TRY(hipHostMalloc((void**)&g->h_pin[i], g->desc_bytes));
-  }
+  if (g->ring.init(g->desc_bytes)) return SRSLTE_ERROR;
   if (gold_basis_upload(g->words, &g->d_basis)) return SRSLTE_ERROR;
   HIP_TRY(hipMalloc((void**)&g->d_scr, sizeof(uint32_t) * (size_t)g->words * V));
   HIP_TRY(hipMalloc((void**)&g->d_tbcrc, sizeof(uint32_t) * V));
@@ -151,14 +140,7 @@ static int ul_tx_grants_init(srslte_hip_ul_tx_t* q, uint32_t V)
   HIP_TRY(hipMalloc((void**)&g->d_qcqi, (size_t)g->cqi_stride * V));
   HIP_TRY(hipMalloc((void**)&g->d_d, sizeof(cf32) * (size_t)g->max_sym * V));
   HIP_TRY(hipMalloc((void**)&g->d_z, sizeof(cf32) * (size_t)g->max_sym * V));
-  for (int mod = 1; mod <= 4; mod++) { // 36.211 7.1.2-7.1.5, one axis (lte_tables.c:57-262)
-    for (uint32_t idx = 0; idx < (1u << mod); idx++) {
-      double v = 1.0;
-      for (int i = mod - 1; i >= 1; i--) v = (double)(1 << (mod - i)) - (1 - 2 * (int)((idx >> (mod - 1 - i)) & 1)) * v;
-      const double norm = mod == 1 ? sqrt(2.0) : (mod == 2 ? sqrt(10.0) : (mod == 3 ? sqrt(42.0) : sqrt(170.0)));
-      g->lv.v[mod][idx] = (float)((1 - 2 * (int)((idx >> (mod - 1)) & 1)) * v / norm);
-    }
-  }
+  for (int mod = 1; mod <= 4; mod++) constellation_levels(mod, g->lv.v[mod]);
   return SRSLTE_SUCCESS;
 }
 
@@ -179,10 +161,10 @@ extern "C" int srslte_hip_ul_tx_batch_grants(srslte_hip_ul_tx_t* q, const uint8_
     q->gs = nullptr;
     return SRSLTE_ERROR;
   }
-  UlTxGrantsState* g  = q->gs;
-  const uint32_t   hs = g->h_slot++ & 3u;
-  if (g->h_used[hs]) HIP_TRY(hipEventSynchronize(g->h_ev[hs]));
-  auto* h_gr = reinterpret_cast<GrantDev*>(g->h_pin[hs]);
+  UlTxGrantsState* g     = q->gs;
+  uint8_t*         h_pin = nullptr;
+  if (int r = g->ring.acquire(&h_pin)) return r;
+  auto* h_gr = reinterpret_cast<GrantDev*>(h_pin);
   auto* h_td = reinterpret_cast<TxDesc*>(h_gr + V);
   auto* h_pd = reinterpret_cast<PuschTxDesc*>(h_td + V);
   auto* d_gr = reinterpret_cast<GrantDev*>(g->d_desc);
@@ -232,14 +214,8 @@ extern "C" int srslte_hip_ul_tx_batch_grants(srslte_hip_ul_tx_t* q, const uint8_
     }
     auto it = g->rm_tbl.find({K, gr.rv});
     if (it == g->rm_tbl.end() && C) {
-      std::vector<uint32_t> t;
-      lte_rm_rx_table(K, gr.rv, t);
-      for (auto& v : t) {
-        const uint32_t pos = v / 3, sidx = v % 3;
-        v = sidx == 0 ? (pos < K ? pos : (1u << 30) | (pos - K)) : (2u << 30) | (sidx == 1 ? pos : K + 4 + pos);
-      }
       uint32_t* d = nullptr;
-      if (upload(&d, t)) return SRSLTE_ERROR;
+      if (rm_tx_table_upload(K, gr.rv, &d)) return SRSLTE_ERROR;
       it = g->rm_tbl.emplace(std::make_pair(K, gr.rv), d).first;
     }
     TxDesc& td = h_td[p];
@@ -250,21 +226,11 @@ extern "C" int srslte_hip_ul_tx_batch_grants(srslte_hip_ul_tx_t* q, const uint8_
     pd.M_sc = 12 * (int)gr.L_prb; pd.n_prb = (int)gr.n_prb; pd.n_prb1 = (int)gr.n_prb_slot1; pd.syms_lo = C ? (int)(g_re / C) : 0; pd.C_lo = C ? (int)(C - g_re % C) : 0;
     pd.Qp_cqi = Qp_cqi; pd.cqi_O = (int)gr.cqi_len; pd.cqi_w = nullptr; pd.cqi_wlen = 1; pd.sf_idx = gd.sf_idx;
     pd.ack.O = (int)gr.ack_len; pd.ack.Qprime = Qp_ack; pd.ri.O = (int)gr.ri_len; pd.ri.Qprime = Qp_ri;
-    if (gr.cqi_len > 11) { // srslte_rm_conv_tx (rm_conv.c:44-89): the sub-block interleaved streams without their dummies, read circularly
+    if (gr.cqi_len > 11) { // the CQI report's rate matching (cqi_rm_conv_order), read circularly by the kernel
       auto cw = g->cqi_w.find(gr.cqi_len);
       if (cw == g->cqi_w.end()) {
-        static const uint8_t perm[32] = {1, 17, 9, 25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31, 0, 16, 8, 24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30};
-        const int             F = (int)gr.cqi_len + 8, nrows = (F - 1) / 32 + 1, ndummy = nrows * 32 - F;
-        std::vector<uint16_t> w;
-        for (int s3 = 0; s3 < 3; s3++) {
-          for (int j = 0; j < 32; j++) {
-            for (int i = 0; i < nrows; i++) {
-              const int pos = i * 32 + perm[j];
-              if (pos >= ndummy) w.push_back((uint16_t)((pos - ndummy) * 3 + s3));
-            }
-          }
-        }
-        uint16_t* d = nullptr;
+        const std::vector<uint16_t> w = cqi_rm_conv_order(gr.cqi_len);
+        uint16_t*                   d = nullptr;
         if (upload(&d, w)) return SRSLTE_ERROR;
         cw = g->cqi_w.emplace(gr.cqi_len, std::make_pair(d, (uint32_t)w.size())).first;
       }
@@ -274,9 +240,8 @@ extern "C" int srslte_hip_ul_tx_batch_grants(srslte_hip_ul_tx_t* q, const uint8_
     if (int r = chest_ul_dmrs_table_cached(q->dmrs, gr.L_prb, gr.n_dmrs, &d_r)) return r;
     pd.dmrs = (const cf32*)d_r;
   }
-  HIP_TRY(hipMemcpyAsync(g->d_desc, g->h_pin[hs], g->desc_bytes, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipEventRecord(g->h_ev[hs], st));
-  g->h_used[hs] = true;
+  HIP_TRY(hipMemcpyAsync(g->d_desc, h_pin, g->desc_bytes, hipMemcpyHostToDevice, st));
+  if (int r = g->ring.release(st)) return r;
   HIP_TRY(hipMemsetAsync(q->d_grid, 0, sizeof(cf32) * (size_t)2 * q->g.nsl * 12 * P * nof_sf, st)); // ue_ul.c:320: the grid is cleared, then pusch_put
   if (nof_grants) {
     hipLaunchKernelGGL(scr_gen_kernel, dim3(ceil_div((int)g->words, 256), nof_grants), dim3(256), 0, st, (const GrantDev*)d_gr, (const uint32_t*)g->d_basis,

@@ -63,17 +63,12 @@ extern "C" int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, ui
     return SRSLTE_ERROR_INVALID_INPUTS;
   GrantsState*   g    = q->gs;
   const size_t   esz  = q->l8 ? 1 : 2;
-  const uint32_t hs   = g->h_slot++ & 3u;
-  if (g->h_used[hs]) HIP_TRY(hipEventSynchronize(g->h_ev[hs]));
-  auto* h_gr  = reinterpret_cast<GrantDev*>(g->h_pin[hs]);
-  auto* h_sf  = reinterpret_cast<SfDesc*>(h_gr + 1);
-  auto* h_cb  = reinterpret_cast<CbDesc*>(h_sf + 1);
-  auto* h_map = reinterpret_cast<uint32_t*>(h_cb + q->Cmax);
-  auto* d_gr  = reinterpret_cast<GrantDev*>(g->d_desc);
-  auto* d_sf  = reinterpret_cast<SfDesc*>(d_gr + 1);
-  auto* d_cb  = reinterpret_cast<CbDesc*>(d_sf + 1);
-  auto* d_map = reinterpret_cast<uint32_t*>(d_cb + q->Cmax);
-  memset(h_gr, 0, sizeof(GrantDev));
+  uint8_t*       h_pin = nullptr;
+  if (int r = g->ring.acquire(&h_pin)) return r;
+  const GrantsDesc h(g, h_pin), d(g, g->d_desc);
+  SfDesc*          h_sf = h.sf;
+  CbDesc*          h_cb = h.cb;
+  memset(h.gr, 0, sizeof(GrantDev));
   memset(h_sf, 0, sizeof(SfDesc));
   GrantsBuild bd;
   bd.g = g; bd.h_sf = h_sf; bd.h_cb = h_cb; bd.l8 = q->l8; bd.max_tbs = q->max_tbs; bd.npt = 1; bd.max_mod = 4; bd.who = "sch";
@@ -107,15 +102,14 @@ extern "C" int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, ui
   }
   if (sum_passes) *sum_passes = 0;
   if (todo == 0) return SRSLTE_SUCCESS;
-  bd.fill_map(h_map);
+  bd.fill_map(h.map);
   memcpy(q->h_pin, e_bits, (size_t)nof_e_bits * esz);
   HIP_TRY(hipMemcpyAsync(g->d_e, q->h_pin, (size_t)nof_e_bits * esz, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(g->d_cb_ok, h_ok, C, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(g->d_desc, g->h_pin[hs], g->desc_bytes, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipEventRecord(g->h_ev[hs], st));
-  g->h_used[hs] = true;
+  HIP_TRY(hipMemcpyAsync(g->d_desc, h_pin, g->desc_bytes, hipMemcpyHostToDevice, st));
+  if (int r = g->ring.release(st)) return r;
   // no transport-block assembly on the device: the caller (sch.c's decode_tb, compat) assembles from the blocks' bytes as upstream does
-  if (int r = grants_back_end(g, bd, d_sf, d_cb, d_map, 0, max_iterations, 1, 1, 0, nullptr, 0, nullptr, st)) return r;
+  if (int r = grants_back_end(g, bd, d.sf, d.cb, d.map, 0, max_iterations, 1, 1, 0, nullptr, 0, nullptr, st)) return r;
   // ---- results down: bytes, flags, pass counts; the soft buffers of blocks that failed (the next transmission combines into them)
   uint8_t*  h_bytes = q->h_pin + q->o_bytes;
   uint8_t*  h_ok2   = q->h_pin + q->o_ok;
