@@ -524,7 +524,8 @@ int srslte_hip_dl_tx_batch(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t 
 /* Per-PDSCH grants (srslte_enb_dl_put_base once per TTI, srslte_enb_dl_put_pdsch once per scheduled UE, srslte_enb_dl_gen_signal; enb_dl.c:330-419):
  * grants[p] = the subframe of the batch and a grant as the receive side takes it (PRB masks of both slots, modulation, transport block <= cfg.tbs,
  * redundancy version, RNTI, CFI; new_data unused); row p of d_tb is its transport block. Several PDSCHs may share a subframe; its grids carry the
- * CRS of every port and nothing else besides the PDSCHs (no control region, PSS / SSS / PBCH). d_iq as srslte_hip_dl_tx_batch. */
+ * CRS of every port and nothing else besides the PDSCHs (no control region, PSS / SSS / PBCH). d_iq as srslte_hip_dl_tx_batch.
+ * srslte_hip_dl_tx_batch_grants_ctrl ("DL control region transmit" below) is the same call with the PCFICH, PHICH and PDCCH added. */
 typedef struct {
   uint32_t              sf; /* 0 .. nof_sf-1 */
   srslte_hip_dl_grant_t grant;
@@ -572,7 +573,7 @@ int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, uint32_t nof_
  * FDD cells, normal / extended CP, 6-110 PRB, 1 / 2 / 4 ports, 1-4 receive antennas, every PHICH configuration (phich_resources
  * srslte_phich_r_t 0-3 = 1/6, 1/2, 1, 2; phich_ext = SRSLTE_PHICH_EXT; the PHICH REGs of regs.c:245-367 with mi = 1). Refused: TDD cells
  * (srslte_hip_dl_ctrl_create returns NULL) and MBSFN subframes (SRSLTE_ERROR_INVALID_INPUTS).
- * Not here: PDCCH / PCFICH encoding in srslte_hip_dl_tx_*, PHICH decoding, UL DCIs (srslte_ue_dl_find_ul_dci), carrier indicator / carrier
+ * Not here: PHICH decoding, UL DCIs (srslte_ue_dl_find_ul_dci), carrier indicator / carrier
  * aggregation, the DCI -> grant unpacking (srslte_dci_msg_unpack_pdsch + srslte_ra_dl_dci_to_grant stay with the caller), and
  * the single-subframe drop-in's pcfich.c / pdcch.c, which remain the reference's. */
 typedef struct srslte_hip_dl_ctrl srslte_hip_dl_ctrl_t;
@@ -632,6 +633,69 @@ uint32_t srslte_hip_pdcch_ue_locations_ncce(uint32_t nof_cce, uint32_t* loc, uin
 uint32_t srslte_hip_pdcch_common_locations_ncce(uint32_t nof_cce, uint32_t* loc, uint32_t max_candidates);
 /* srslte_dci_format_sizeof of an FDD cell with a zero srslte_dci_cfg_t, format srslte_dci_format_t 0-8 (0 1 1A 1C 1B 1D 2 2A 2B); 0 otherwise */
 uint32_t srslte_hip_dci_format_sizeof(uint32_t nof_prb, uint32_t nof_ports, int format);
+
+/* ------------------------------------------------------------------ DL control region transmit (eNB side): what srslte_enb_dl_put_base does
+ * for the PCFICH (enb_dl.c:342-351), srslte_enb_dl_put_phich (:353-358) and srslte_enb_dl_put_pdcch_dl / _ul (:360-390) for a batch of
+ * subframes, in one call on the caller's stream with no host synchronisation (the descriptors travel through pinned buffers, as the grants
+ * paths' do). Per subframe b (TTI tti0 + b) of d_grid [nof_sf][nof_ports][nsym][12 nof_prb] cf32 it writes, and touches nothing else:
+ *   PCFICH (srslte_pcfich_encode, pcfich.c:231-275): the 32-bit code word of in->cfi[b] (pcfich.c:39-47), srslte_sequence_pcfich of sf_idx,
+ *     QPSK, srslte_layermap_diversity + srslte_precoding_diversity(..., 1.0f) for 2 / 4 ports, put on the 16 REs of every port.
+ *   PHICH (srslte_regs_phich_reset + srslte_phich_encode + srslte_regs_phich_add; phich.c:318-430, regs.c:413-449): every PHICH REG of the
+ *     cell is set to zero, then each of the subframe's PHICHs is added in entry order: three BPSK symbols of the ack, spread by the orthogonal
+ *     sequence nseq of 36.211 Table 6.9.1-2 (phich.c:36-41), srslte_sequence_phich (the first 12 bits of the PCFICH's), on an extended-CP cell
+ *     groups 2m and 2m + 1 share the REGs of mapping unit m and the odd group sits in the second half of each REG (phich.c:392-407), the
+ *     precoding above on 12 symbols. Four ports follow the reference's precoding, not the rule of 36.211 6.9.2 (its FIXME, phich.c:421).
+ *   PDCCH (srslte_pdcch_encode, pdcch.c:503-629): per DCI the CRC-16 with the RNTI mask, the tail-biting rate-1/3 convolutional code (K = 7,
+ *     0x6D / 0x4F / 0x57), srslte_rm_conv_tx to E = 72 2^L bits, srslte_sequence_pdcch from bit 72 ncce, QPSK, the precoding above, put on
+ *     entries [36 ncce, 36 (ncce + 2^L)) of the CFI's PDCCH RE list of every port. REGs of unused CCEs keep what they hold.
+ * The result is bit-identical to the reference's grids. The REG lists and sequences are built on the host when the object is made.
+ * Refused with SRSLTE_ERROR_INVALID_INPUTS before anything is queued: a cfi outside 1-3, an entry's sf >= nof_sf, nof_sf > max_batch, L > 3,
+ * ncce + 2^L > NOF_CCE(cfi), nof_bits 0 or >= SRSLTE_DCI_MAX_BITS - 16 (pdcch.c:572-573), two DCIs of one subframe on a common CCE (the
+ * reference would silently overwrite: a deliberate difference), a PHICH group >= srslte_regs_phich_ngroups, ack > 1, more than max_dci DCIs or
+ * max_phich PHICHs. TDD cells are refused by create (NULL).
+ * Not here: PSS / SSS / PBCH, PHICH decoding, control in the fixed-grant srslte_hip_dl_tx_batch, TDD (the PHICH mi factor, special
+ * subframes) and MBSFN subframes, DCI packing (srslte_dci_msg_pack_pdsch / _pusch stay with the caller), carrier indicator, and the
+ * single-subframe drop-in's pcfich.c / pdcch.c / phich.c, which remain the reference's. */
+typedef struct srslte_hip_dl_ctrl_tx srslte_hip_dl_ctrl_tx_t;
+typedef struct {
+  uint32_t nof_prb, nof_ports, cell_id;
+  int      cp_ext, phich_resources, phich_ext, tdd; /* as srslte_hip_dl_ctrl_cfg_t; tdd: refused */
+  uint32_t max_batch;       /* subframes per call */
+  uint32_t max_dci;         /* DCIs per call */
+  uint32_t max_phich;       /* PHICHs per call */
+} srslte_hip_dl_ctrl_tx_cfg_t;
+typedef struct {            /* one DCI (host array) */
+  uint32_t             sf;  /* its subframe within the batch */
+  srslte_hip_dci_msg_t msg; /* payload (one bit per byte, the first nof_bits read), nof_bits, L, ncce, rnti; format is not used */
+} srslte_hip_dl_ctrl_tx_dci_t;
+typedef struct {            /* one PHICH (host array): the srslte_phich_grant_t of srslte_enb_dl_put_phich, resource by srslte_phich_calc */
+  uint32_t sf, n_prb_lowest, n_dmrs, I_phich;
+  uint8_t  ack;             /* 0 / 1 */
+} srslte_hip_phich_tx_t;
+typedef struct {
+  const uint32_t*                    cfi; /* [nof_sf], 1-3 */
+  const srslte_hip_dl_ctrl_tx_dci_t* dci;
+  uint32_t                           nof_dci;
+  const srslte_hip_phich_tx_t*       phich; /* added in this order, per subframe */
+  uint32_t                           nof_phich;
+} srslte_hip_dl_ctrl_tx_in_t;
+srslte_hip_dl_ctrl_tx_t* srslte_hip_dl_ctrl_tx_create(const srslte_hip_dl_ctrl_tx_cfg_t* cfg);
+void                     srslte_hip_dl_ctrl_tx_destroy(srslte_hip_dl_ctrl_tx_t* q);
+int srslte_hip_dl_ctrl_tx_put(srslte_hip_dl_ctrl_tx_t* q, uint32_t tti0, uint32_t nof_sf, const srslte_hip_dl_ctrl_tx_in_t* in, void* d_grid, void* stream);
+/* srslte_hip_dl_tx_batch_grants with srslte_hip_dl_ctrl_tx_put on its grids between the PDSCH mapping and the OFDM modulation: one complete
+ * subframe per TTI apart from PSS / SSS / PBCH. Refused (SRSLTE_ERROR_INVALID_INPUTS) besides what either call refuses: a ctrl object of
+ * another cell (nof_prb, ports - a pipeline's nof_ports 0 is 1 -, cell_id, cp_ext), a TDD or MBSFN pipeline, a grant whose cfi differs from
+ * in->cfi[grant.sf]. */
+int srslte_hip_dl_tx_batch_grants_ctrl(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
+                                       const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
+                                       const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream);
+/* host helpers (no device needed), for a cell given as srslte_hip_dl_ctrl_tx_cfg_t (limits not looked at): srslte_regs_phich_ngroups (x 2 on
+ * an extended-CP cell); srslte_phich_calc (36.213 9.1.2, phich.c:132-143): ngroup, nseq; the 12 REs of a group in srslte_regs_phich_add
+ * order. Return < 0 for an invalid cell / group / too small max. */
+int srslte_hip_dl_ctrl_phich_ngroups(const srslte_hip_dl_ctrl_tx_cfg_t* cfg);
+int srslte_hip_phich_calc(const srslte_hip_dl_ctrl_tx_cfg_t* cfg, uint32_t n_prb_lowest, uint32_t n_dmrs, uint32_t I_phich, uint32_t* ngroup,
+                          uint32_t* nseq);
+int srslte_hip_dl_ctrl_phich_re(const srslte_hip_dl_ctrl_tx_cfg_t* cfg, uint32_t ngroup, uint32_t* re, uint32_t max);
 
 #ifdef __cplusplus
 }

@@ -926,6 +926,27 @@ class DlTx:
         sync()
         return self.d_iq.to_host(np.complex64).reshape(self.max_batch, self.nof_ports, self.sf_len)[:x.shape[0]]
 
+    def encode_grants_ctrl(self, tbs_bytes, tti0, nof_sf, grants, ctrl, cfi, dcis=(), phichs=()):
+        """srslte_hip_dl_tx_batch_grants_ctrl: encode_grants with the control region of ctrl (a DlCtrlTx of the same cell) - cfi [nof_sf], dcis and
+        phichs as DlCtrlTx.put takes them - on the grids before the OFDM modulation -> (rc, iq [nof_sf][nof_ports][sf_len] or None)."""
+        class TxGrant(C.Structure):
+            _fields_ = [("sf", C.c_uint32), ("grant", DlGrant)]
+        stride = (self.tbs // 8 + 15) & ~15
+        x = np.zeros((max(1, len(grants)), stride), np.uint8)
+        for p_, b in enumerate(tbs_bytes):
+            x[p_, :len(b)] = b
+        din = DevBuf.from_host(x)
+        arr = (TxGrant * max(1, len(grants)))(*[TxGrant(sf, g) for sf, g in grants])
+        inp, keep = _ctrl_tx_in(cfi, dcis, phichs)
+        L = _bind_dl_ctrl_tx(lib())
+        L.srslte_hip_dl_tx_batch_grants_ctrl.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                         C.POINTER(DlCtrlTxIn), C.c_void_p, C.c_void_p]
+        rc = L.srslte_hip_dl_tx_batch_grants_ctrl(self.h, din.ptr, stride, tti0, nof_sf, arr, len(grants), ctrl.h, C.byref(inp), self.d_iq.ptr, None)
+        if rc != SRSLTE_SUCCESS:
+            return rc, None
+        sync()
+        return rc, self.d_iq.to_host(np.complex64).reshape(self.max_batch, self.nof_ports, self.sf_len)[:nof_sf]
+
     def debug(self, which, dtype, count):
         ptr = lib().srslte_hip_dl_tx_debug_buffer(self.h, which)
         out = np.empty(count, dtype)
@@ -1089,4 +1110,111 @@ class DlCtrl:
     def free(self):
         if self.h:
             lib().srslte_hip_dl_ctrl_destroy(self.h)
+            self.h = None
+
+
+# ---------------------------------------------------------------- DL control region transmit (phy_hip.h "DL control region transmit")
+class DlCtrlTxCfg(C.Structure):
+    """srslte_hip_dl_ctrl_tx_cfg_t: the cell and the per-call limits."""
+    _fields_ = [("nof_prb", C.c_uint32), ("nof_ports", C.c_uint32), ("cell_id", C.c_uint32), ("cp_ext", C.c_int), ("phich_resources", C.c_int),
+                ("phich_ext", C.c_int), ("tdd", C.c_int), ("max_batch", C.c_uint32), ("max_dci", C.c_uint32), ("max_phich", C.c_uint32)]
+
+
+class DlCtrlTxDci(C.Structure):
+    """srslte_hip_dl_ctrl_tx_dci_t: a DCI message and its subframe within the batch."""
+    _fields_ = [("sf", C.c_uint32), ("msg", DciMsg)]
+
+
+class PhichTx(C.Structure):
+    """srslte_hip_phich_tx_t: srslte_phich_grant_t and the ack of one PHICH, with its subframe within the batch."""
+    _fields_ = [("sf", C.c_uint32), ("n_prb_lowest", C.c_uint32), ("n_dmrs", C.c_uint32), ("I_phich", C.c_uint32), ("ack", C.c_uint8)]
+
+
+class DlCtrlTxIn(C.Structure):
+    """srslte_hip_dl_ctrl_tx_in_t."""
+    _fields_ = [("cfi", C.c_void_p), ("dci", C.POINTER(DlCtrlTxDci)), ("nof_dci", C.c_uint32), ("phich", C.POINTER(PhichTx)), ("nof_phich", C.c_uint32)]
+
+
+def _bind_dl_ctrl_tx(L):
+    vp = C.c_void_p
+    L.srslte_hip_dl_ctrl_tx_create.restype = vp
+    L.srslte_hip_dl_ctrl_tx_create.argtypes = [C.POINTER(DlCtrlTxCfg)]
+    L.srslte_hip_dl_ctrl_tx_destroy.argtypes = [vp]
+    L.srslte_hip_dl_ctrl_tx_put.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(DlCtrlTxIn), vp, vp]
+    L.srslte_hip_dl_ctrl_phich_ngroups.argtypes = [C.POINTER(DlCtrlTxCfg)]
+    L.srslte_hip_phich_calc.argtypes = [C.POINTER(DlCtrlTxCfg), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.srslte_hip_dl_ctrl_phich_re.argtypes = [C.POINTER(DlCtrlTxCfg), C.c_uint32, vp, C.c_uint32]
+    return L
+
+
+def _ctrl_tx_cfg(nof_prb, nof_ports, cell_id, cp_ext=False, phich_resources=0, phich_ext=False, max_batch=1, max_dci=0, max_phich=0, tdd=False):
+    return DlCtrlTxCfg(nof_prb, nof_ports, cell_id, 1 if cp_ext else 0, phich_resources, 1 if phich_ext else 0, 1 if tdd else 0, max_batch, max_dci,
+                       max_phich)
+
+
+def _ctrl_tx_in(cfi, dcis, phichs):
+    """(DlCtrlTxIn, the ctypes arrays it points at). dcis: (sf, msg) with msg anything of the srslte_dci_msg_t layout; phichs: PhichTx or
+    (sf, n_prb_lowest, n_dmrs, I_phich, ack)."""
+    c = np.ascontiguousarray(cfi, np.uint32)
+    d = (DlCtrlTxDci * max(1, len(dcis)))(*[DlCtrlTxDci(sf, DciMsg.from_buffer_copy(bytes(m)[:C.sizeof(DciMsg)])) for sf, m in dcis])
+    p = (PhichTx * max(1, len(phichs)))(*[x if isinstance(x, PhichTx) else PhichTx(*x) for x in phichs])
+    return DlCtrlTxIn(c.ctypes.data if c.size else None, d, len(dcis), p, len(phichs)), (c, d, p)
+
+
+def phich_ngroups(nof_prb, nof_ports, cell_id, cp_ext=False, phich_resources=0, phich_ext=False):
+    """srslte_regs_phich_ngroups (PHICH groups; x 2 on an extended-CP cell) (host; no GPU)."""
+    n = _bind_dl_ctrl_tx(lib()).srslte_hip_dl_ctrl_phich_ngroups(C.byref(_ctrl_tx_cfg(nof_prb, nof_ports, cell_id, cp_ext, phich_resources, phich_ext)))
+    if n < 0:
+        raise ValueError("srslte_hip_dl_ctrl_phich_ngroups: %d" % n)
+    return n
+
+
+def phich_calc(nof_prb, nof_ports, cell_id, n_prb_lowest, n_dmrs, I_phich, cp_ext=False, phich_resources=0, phich_ext=False):
+    """srslte_phich_calc -> (ngroup, nseq) (host)."""
+    g, q = C.c_uint32(0), C.c_uint32(0)
+    rc = _bind_dl_ctrl_tx(lib()).srslte_hip_phich_calc(C.byref(_ctrl_tx_cfg(nof_prb, nof_ports, cell_id, cp_ext, phich_resources, phich_ext)),
+                                                        n_prb_lowest, n_dmrs, I_phich, C.byref(g), C.byref(q))
+    if rc != SRSLTE_SUCCESS:
+        raise ValueError("srslte_hip_phich_calc: %d" % rc)
+    return g.value, q.value
+
+
+def phich_re(nof_prb, nof_ports, cell_id, ngroup, cp_ext=False, phich_resources=0, phich_ext=False):
+    """The 12 REs of PHICH group ngroup in srslte_regs_phich_add's order (host)."""
+    out = np.zeros(12, np.uint32)
+    n = _bind_dl_ctrl_tx(lib()).srslte_hip_dl_ctrl_phich_re(C.byref(_ctrl_tx_cfg(nof_prb, nof_ports, cell_id, cp_ext, phich_resources, phich_ext)),
+                                                            ngroup, out.ctypes.data, 12)
+    if n < 0:
+        raise ValueError("srslte_hip_dl_ctrl_phich_re: %d" % n)
+    return out[:n]
+
+
+class DlCtrlTx:
+    """Batched control-region transmit: the PCFICH of srslte_enb_dl_put_base, srslte_enb_dl_put_phich and srslte_enb_dl_put_pdcch_dl / _ul."""
+
+    def __init__(self, nof_prb, nof_ports, cell_id, cp_ext=False, phich_resources=0, phich_ext=False, max_batch=1, max_dci=16, max_phich=16, tdd=False):
+        L = _bind_dl_ctrl_tx(lib())
+        self.cfg = _ctrl_tx_cfg(nof_prb, nof_ports, cell_id, cp_ext, phich_resources, phich_ext, max_batch, max_dci, max_phich, tdd)
+        self.h = L.srslte_hip_dl_ctrl_tx_create(C.byref(self.cfg))
+        if not self.h:
+            raise RuntimeError("srslte_hip_dl_ctrl_tx_create failed")
+        self.grid_len = (12 if cp_ext else 14) * 12 * nof_prb
+        self.nof_ports, self.max_batch = nof_ports, max_batch
+
+    def put_device(self, d_grid, tti0, nof_sf, cfi, dcis=(), phichs=(), stream=None):
+        """srslte_hip_dl_ctrl_tx_put on a device grid [nof_sf][nof_ports][grid_len] -> the status code."""
+        inp, keep = _ctrl_tx_in(cfi, dcis, phichs)
+        return lib().srslte_hip_dl_ctrl_tx_put(self.h, tti0, nof_sf, C.byref(inp), d_grid, stream)
+
+    def put(self, grid, tti0, cfi, dcis=(), phichs=()):
+        """grid [nof_sf][nof_ports][grid_len] complex64 (host), cfi [nof_sf] -> (rc, the grids after the call)."""
+        g = np.ascontiguousarray(grid, np.complex64).reshape(len(cfi), self.nof_ports, self.grid_len)
+        d = DevBuf.from_host(g)
+        rc = self.put_device(d.ptr, tti0, len(cfi), cfi, dcis, phichs)
+        sync()
+        return rc, d.to_host(np.complex64).reshape(g.shape)
+
+    def free(self):
+        if self.h:
+            lib().srslte_hip_dl_ctrl_tx_destroy(self.h)
             self.h = None

@@ -1,0 +1,24 @@
+// Host tables of the DL control region, shared by the receiver (pdcch.hip) and the encoder (pdcch_tx.hip): the REG lists of regs.c and the
+// scrambling sequences of the PCFICH, PHICH and PDCCH (sequences.c), for one cell.
+#pragma once
+#include "srslte_hip/phy_hip.h"
+#include <stdint.h>
+#include <vector>
+
+struct CtrlRegs {
+  std::vector<uint32_t> pcfich;   // the 16 PCFICH REs in srslte_regs_pcfich_put order
+  std::vector<uint32_t> pdcch[3]; // the 36 NOF_CCE(cfi) PDCCH REs of CFI 1-3 in srslte_regs_pdcch_put order
+  std::vector<uint32_t> phich;    // [ngroups_m1][12]: the REs of each PHICH mapping unit in srslte_regs_phich_add order
+  uint32_t              ngroups_m1 = 0; // mapping units (srslte_regs_phich_ngroups_m1); PHICH groups: that, x 2 on an extended-CP cell
+};
+
+// the cell description of srslte_hip_dl_ctrl_cfg_t is one srslte_regs_init accepts (TDD and nof_rx_antennas are not looked at)
+bool ctrl_cell_ok(const srslte_hip_dl_ctrl_cfg_t* c);
+
+// srslte_regs_init_opts with mi = 1 outside MBSFN / TDD special subframes (regs.c:698-786, REGs :633-675, PCFICH :491-523, PHICH :245-367,
+// PDCCH :77-154), as RE indices of one port's [nsym][12 prb] grid
+int ctrl_build_regs(const srslte_hip_dl_ctrl_cfg_t* c, CtrlRegs& r);
+
+// srslte_sequence_pcfich (32 bits; its first 12 are srslte_sequence_phich, the same c_init: sequences.c:36-46) and srslte_sequence_pdcch of
+// pdcch_bits bits (sequences.c:51-53) of subframes 0-9, packed bit i -> word i / 32, bit i % 32: scr = [10 PCFICH words][10][scr_words]
+void ctrl_scrambling(uint32_t cell_id, uint32_t pdcch_bits, std::vector<uint32_t>& scr, int* scr_words);

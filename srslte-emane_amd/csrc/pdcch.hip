@@ -8,6 +8,7 @@
 //   dl_ctrl_select_kernel  one lane per subframe: dci_blind_search's first hit (ue_dl.c:422-478)
 // The REG lists (regs.c), the DCI sizes (dci.c:93-360) and the scrambling sequences are built on the host when the object is made.
 #include "common.hpp"
+#include "ctrl_host.hpp"
 #include "demod_dev.hpp"
 #include "phy_hip_internal.hpp"
 #include "viterbi_dev.hpp"
@@ -367,106 +368,7 @@ __global__ __launch_bounds__(64) void dl_ctrl_select_kernel(const srslte_hip_dl_
   m->rnti     = hit >= 0 ? (uint16_t)rnti : 0;
 }
 
-// ---------------------------------------------------------------- host: REGs (regs.c), DCI sizes (dci.c)
-struct Reg {
-  uint32_t l, k0, k[4];
-  bool     assigned;
-};
-
-static bool cell_ok(const srslte_hip_dl_ctrl_cfg_t* c)
-{
-  return c && c->nof_prb >= 6 && c->nof_prb <= 110 && (c->nof_ports == 1 || c->nof_ports == 2 || c->nof_ports == 4) && c->cell_id < 504 &&
-         c->phich_resources >= 0 && c->phich_resources <= 3;
-}
-
-// srslte_regs_init_opts with mi = 1 outside MBSFN / TDD special subframes (regs.c:698-786, REGs :633-675, PCFICH :491-523, PHICH :245-367,
-// PDCCH :77-154): pcfich = the 16 REs, pdcch[c] = the 36 NOF_CCE REs of CFI c + 1, as RE indices of the [nsym][12 prb] grid
-static int build_regs(const srslte_hip_dl_ctrl_cfg_t* c, std::vector<uint32_t>& pcfich, std::vector<uint32_t> pdcch[3])
-{
-  if (!cell_ok(c)) return SRSLTE_ERROR_INVALID_INPUTS;
-  const uint32_t prb = c->nof_prb, id = c->cell_id, max_ctrl = prb <= 10 ? 4 : 3, vo = id % 3;
-  uint32_t       n[4];
-  for (uint32_t i = 0; i < max_ctrl; i++) n[i] = i == 0 ? 2 : i == 1 ? (c->nof_ports == 4 ? 2 : 3) : i == 2 ? 3 : (c->cp_ext ? 2 : 3);
-  uint32_t nof_regs = 0;
-  for (uint32_t i = 0; i < max_ctrl; i++) nof_regs += prb * n[i];
-  std::vector<Reg> regs(nof_regs);
-  uint32_t         j[4] = {0, 0, 0, 0}, k = 0, i = 0, p = 0, jmax = 0;
-  while (k < nof_regs) { // lowest symbol first, then frequency, PRB by PRB
-    if (n[i] == 3 || (n[i] == 2 && jmax != 1)) {
-      Reg& r = regs[k];
-      r.l = i, r.assigned = false;
-      const uint32_t b0 = p * 12;
-      if (n[i] == 2) { // two REGs around the reference signals at vo, vo + 3
-        r.k0 = b0 + j[i] * 6;
-        uint32_t t = 0;
-        for (uint32_t z = 0; z < 6; z++)
-          if (z != vo && z != vo + 3) r.k[t++] = r.k0 + z;
-      } else {
-        r.k0 = b0 + j[i] * 4;
-        for (uint32_t z = 0; z < 4; z++) r.k[z] = r.k0 + z;
-      }
-      j[i]++, k++;
-    }
-    if (++i == max_ctrl) i = 0, jmax++;
-    if (jmax == 3) p++, j[0] = j[1] = j[2] = j[3] = 0, jmax = 0;
-  }
-  auto re_of = [prb](const Reg& r, uint32_t t) { return r.k[t] + r.l * prb * 12; };
-  // PCFICH
-  pcfich.clear();
-  const uint32_t k_hat = 6 * (id % (2 * prb));
-  for (uint32_t q = 0; q < 4; q++) {
-    const uint32_t kk = (k_hat + (q * prb / 2) * 6) % (prb * 12);
-    Reg*           f  = nullptr;
-    for (auto& r : regs)
-      if (r.l == 0 && r.k0 == kk) {
-        f = &r;
-        break;
-      }
-    if (!f || f->assigned) return SRSLTE_ERROR;
-    f->assigned = true;
-    for (uint32_t t = 0; t < 4; t++) pcfich.push_back(re_of(*f, t));
-  }
-  // PHICH
-  const float    ng[4]   = {(float)1 / 6, (float)1 / 2, 1.0f, 2.0f};
-  const uint32_t ngroups = (uint32_t)(int)ceilf(ng[c->phich_resources] * ((float)prb / 8));
-  std::vector<Reg*> ph[3];
-  for (auto& r : regs)
-    if (r.l < 3 && !r.assigned) ph[r.l].push_back(&r);
-  for (uint32_t mi = 0; mi < ngroups; mi++) {
-    for (uint32_t q = 0; q < 3; q++) {
-      const uint32_t li = c->phich_ext ? q : 0, nl = (uint32_t)ph[li].size();
-      const uint32_t ni = ((id * nl / (uint32_t)ph[0].size()) + mi + q * nl / 3) % nl;
-      ph[li][ni]->assigned = true;
-    }
-  }
-  // PDCCH: quadruplet sub-block interleaver (32 columns, PDCCH_PERM) and the cyclic shift by the cell id
-  static const uint8_t PERM[32] = {1, 17, 9, 25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31, 0, 16, 8, 24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30};
-  for (uint32_t cfi = 0; cfi < 3; cfi++) {
-    const uint32_t    nsym = prb <= 10 ? cfi + 2 : cfi + 1;
-    std::vector<Reg*> tmp;
-    for (auto& r : regs)
-      if (r.l < nsym && !r.assigned) tmp.push_back(&r);
-    const uint32_t    m = (uint32_t)tmp.size(), nrows = (m - 1) / 32 + 1;
-    const int         ndummy = (int)(32 * nrows) - (int)m;
-    std::vector<Reg*> out(m);
-    uint32_t          kk = 0;
-    for (uint32_t jj = 0; jj < 32; jj++) {
-      for (uint32_t ii = 0; ii < nrows; ii++) {
-        if ((int)(ii * 32 + PERM[jj]) >= ndummy) {
-          const uint32_t mm = ii * 32 + PERM[jj] - ndummy;
-          const uint32_t kp = kk < id ? (m + kk - (id % m)) % m : (kk - id) % m;
-          out[mm]           = tmp[kp];
-          kk++;
-        }
-      }
-    }
-    pdcch[cfi].clear();
-    for (uint32_t r = 0; r < (m / 9) * 9; r++)
-      for (uint32_t t = 0; t < 4; t++) pdcch[cfi].push_back(re_of(*out[r], t));
-  }
-  return SRSLTE_SUCCESS;
-}
-
+// ---------------------------------------------------------------- host: DCI sizes (dci.c); the REG lists and sequences are in ctrl_host.cpp
 static uint32_t riv_nbits(uint32_t n) { return (uint32_t)ceilf(log2f((float)n * ((float)n + 1) / 2)); }
 static bool     ambiguous(uint32_t n)
 {
@@ -535,21 +437,21 @@ extern "C" {
 
 int srslte_hip_dl_ctrl_pcfich_re(const srslte_hip_dl_ctrl_cfg_t* cfg, uint32_t* re, uint32_t max)
 {
-  std::vector<uint32_t> pc, pd[3];
-  const int             rc = build_regs(cfg, pc, pd);
+  CtrlRegs  r;
+  const int rc = ctrl_build_regs(cfg, r);
   if (rc != SRSLTE_SUCCESS) return rc;
-  if (!re || max < pc.size()) return SRSLTE_ERROR_INVALID_INPUTS;
-  memcpy(re, pc.data(), pc.size() * 4);
-  return (int)pc.size();
+  if (!re || max < r.pcfich.size()) return SRSLTE_ERROR_INVALID_INPUTS;
+  memcpy(re, r.pcfich.data(), r.pcfich.size() * 4);
+  return (int)r.pcfich.size();
 }
 
 int srslte_hip_dl_ctrl_pdcch_re(const srslte_hip_dl_ctrl_cfg_t* cfg, uint32_t cfi, uint32_t* re, uint32_t max)
 {
   if (cfi < 1 || cfi > 3) return SRSLTE_ERROR_INVALID_INPUTS;
-  std::vector<uint32_t> pc, pd[3];
-  const int             rc = build_regs(cfg, pc, pd);
+  CtrlRegs  r;
+  const int rc = ctrl_build_regs(cfg, r);
   if (rc != SRSLTE_SUCCESS) return rc;
-  const std::vector<uint32_t>& v = pd[cfi - 1];
+  const std::vector<uint32_t>& v = r.pdcch[cfi - 1];
   if (!re || max < v.size()) return SRSLTE_ERROR_INVALID_INPUTS;
   memcpy(re, v.data(), v.size() * 4);
   return (int)v.size();
@@ -584,9 +486,10 @@ void srslte_hip_dl_ctrl_destroy(srslte_hip_dl_ctrl_t* q)
 
 srslte_hip_dl_ctrl_t* srslte_hip_dl_ctrl_create(const srslte_hip_dl_ctrl_cfg_t* cfg)
 {
-  if (!cell_ok(cfg) || cfg->tdd || cfg->nof_rx_antennas < 1 || cfg->nof_rx_antennas > 4 || cfg->max_batch < 1) return nullptr;
-  std::vector<uint32_t> pc, pd[3];
-  if (build_regs(cfg, pc, pd) != SRSLTE_SUCCESS) return nullptr;
+  if (!ctrl_cell_ok(cfg) || cfg->tdd || cfg->nof_rx_antennas < 1 || cfg->nof_rx_antennas > 4 || cfg->max_batch < 1) return nullptr;
+  CtrlRegs regs;
+  if (ctrl_build_regs(cfg, regs) != SRSLTE_SUCCESS) return nullptr;
+  const std::vector<uint32_t>&pc = regs.pcfich, *pd = regs.pdcch;
   srslte_hip_dl_ctrl_t* q = new srslte_hip_dl_ctrl_t();
   q->cfg                  = *cfg;
   CtrlGeom& g             = q->g;
@@ -605,15 +508,8 @@ srslte_hip_dl_ctrl_t* srslte_hip_dl_ctrl_create(const srslte_hip_dl_ctrl_cfg_t* 
     return nullptr;
   }
   // scrambling: srslte_sequence_pcfich (32 bits) and srslte_sequence_pdcch sized 8 srslte_regs_pdcch_nregs(3) = 2 n[2] bits, slot 2 sf_idx
-  g.scr_words = (2 * g.n[2] + 31) / 32;
-  std::vector<uint32_t> scr(10 + 10 * (size_t)g.scr_words, 0u);
-  std::vector<uint8_t>  c;
-  for (uint32_t s = 0; s < 10; s++) {
-    lte_gold_sequence((s + 1) * (2 * cfg->cell_id + 1) * 512 + cfg->cell_id, 32, c);
-    for (int i = 0; i < 32; i++) scr[s] |= (uint32_t)(c[i] & 1) << i;
-    lte_gold_sequence(s * 512 + cfg->cell_id, 2 * g.n[2], c);
-    for (int i = 0; i < 2 * g.n[2]; i++) scr[10 + s * g.scr_words + (i >> 5)] |= (uint32_t)(c[i] & 1) << (i & 31);
-  }
+  std::vector<uint32_t> scr;
+  ctrl_scrambling(cfg->cell_id, 2 * g.n[2], scr, &g.scr_words);
   const size_t B = cfg->max_batch;
   if (hipMalloc(&q->d_re, re.size() * 4) != hipSuccess || hipMalloc(&q->d_scr, scr.size() * 4) != hipSuccess ||
       hipMalloc(&q->d_llr, B * g.llr_stride * 4) != hipSuccess || hipMalloc(&q->d_cand, B * MAX_CAND * sizeof(srslte_hip_dl_ctrl_cand_t)) != hipSuccess ||

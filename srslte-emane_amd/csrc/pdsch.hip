@@ -21,6 +21,7 @@
 #include "common.hpp"
 #include "demod_dev.hpp"
 #include "phy_hip_internal.hpp"
+#include "pinned_ring.hpp"
 #include "viterbi_dev.hpp"
 #include <algorithm>
 #include <map>

@@ -427,8 +427,10 @@ static int dl_tx_grants_init(srslte_hip_dl_tx_t* q, uint32_t V)
 // true, including upstream's stale-offset rule); allocations that overlap within a subframe are the caller's error (which PDSCH wins an RE is
 // not defined here; upstream the later put would). The object's
 // cell, antenna ports (TM1 / transmit diversity), p_a apply; cfg.tbs bounds every grant's tbs, cfg.max_grants the number of PDSCHs per call.
-extern "C" int srslte_hip_dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
-                                             const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants, void* d_iq, void* stream)
+// ctrl / in: srslte_hip_dl_tx_batch_grants_ctrl's control region, put on the grids after the PDSCHs (nullptr: none)
+static int dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
+                              const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
+                              const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream)
 {
   if (!q || !d_tb || !d_iq || !grants || nof_sf > q->cfg.max_batch) return SRSLTE_ERROR_INVALID_INPUTS;
   const uint32_t V = q->cfg.max_grants ? q->cfg.max_grants : q->cfg.max_batch, P = q->cfg.nof_prb, cell_id = q->cfg.cell_id;
@@ -531,5 +533,32 @@ extern "C" int srslte_hip_dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_
                        (const uint32_t*)g->d_relist, q->d_grid, (const TxDesc*)d_td, (int)g->max_re, tg.grid_len, npt);
     LAUNCH_CHECK();
   }
+  if (ctrl) {
+    if (int r = srslte_hip_dl_ctrl_tx_put(ctrl, tti0, nof_sf, in, q->d_grid, stream)) return r;
+  }
   return srslte_hip_ofdm_tx_sf_batch(q->ofdm, q->d_grid, d_iq, (int)nof_sf * npt, stream);
+}
+
+extern "C" int srslte_hip_dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
+                                             const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants, void* d_iq, void* stream)
+{
+  return dl_tx_batch_grants(q, d_tb, tb_stride, tti0, nof_sf, grants, nof_grants, nullptr, nullptr, d_iq, stream);
+}
+
+// srslte_enb_dl_put_base's PCFICH, srslte_enb_dl_put_phich, srslte_enb_dl_put_pdcch_dl / _ul and srslte_enb_dl_put_pdsch of a run of TTIs
+// (sf_worker.cc:428-753) in one call: the grants path above with srslte_hip_dl_ctrl_tx_put on its grids before the OFDM modulation. Everything
+// the control region refuses is refused before anything is queued.
+extern "C" int srslte_hip_dl_tx_batch_grants_ctrl(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
+                                                  const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
+                                                  const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream)
+{
+  const srslte_hip_dl_ctrl_tx_cfg_t* cc = dl_ctrl_tx_cfg(ctrl);
+  if (!q || !cc || !in || !grants || q->cfg.tdd || q->cfg.mbsfn || cc->nof_prb != q->cfg.nof_prb || cc->nof_ports != (uint32_t)q->g.nof_ports ||
+      cc->cell_id != q->cfg.cell_id || (cc->cp_ext != 0) != (q->cfg.cp_ext != 0))
+    return SRSLTE_ERROR_INVALID_INPUTS;
+  if (int r = dl_ctrl_tx_check(ctrl, nof_sf, in)) return r;
+  for (uint32_t p = 0; p < nof_grants; p++) {
+    if (grants[p].sf < nof_sf && grants[p].grant.cfi != in->cfi[grants[p].sf]) return SRSLTE_ERROR_INVALID_INPUTS;
+  }
+  return dl_tx_batch_grants(q, d_tb, tb_stride, tti0, nof_sf, grants, nof_grants, ctrl, in, d_iq, stream);
 }

@@ -82,3 +82,6 @@ int tdec_run_groups(srslte_hip_tdec_t* q, const void* d_input, int llr8, uint32_
 int tdec_run_batch_w(srslte_hip_tdec_t* q, const void* d_input, int llr8, uint32_t in_stride, int sb_layout, uint32_t K, int force_w,
                      uint32_t nof_cb, uint32_t nof_iterations, uint32_t crc_poly, uint32_t crc_nbits, uint8_t* d_output,
                      uint32_t out_stride, uint32_t* d_iters, uint8_t* d_crc_ok, hipStream_t st);
+// pdcch_tx.hip: the checks of srslte_hip_dl_ctrl_tx_put alone (nothing is queued), and the cell an object was made for
+int                                dl_ctrl_tx_check(srslte_hip_dl_ctrl_tx_t* q, uint32_t nof_sf, const srslte_hip_dl_ctrl_tx_in_t* in);
+const srslte_hip_dl_ctrl_tx_cfg_t* dl_ctrl_tx_cfg(const srslte_hip_dl_ctrl_tx_t* q);
