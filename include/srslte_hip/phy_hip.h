@@ -573,6 +573,7 @@ int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, uint32_t nof_
  * FDD cells, normal / extended CP, 6-110 PRB, 1 / 2 / 4 ports, 1-4 receive antennas, every PHICH configuration (phich_resources
  * srslte_phich_r_t 0-3 = 1/6, 1/2, 1, 2; phich_ext = SRSLTE_PHICH_EXT; the PHICH REGs of regs.c:245-367 with mi = 1). Refused: TDD cells
  * (srslte_hip_dl_ctrl_create returns NULL) and MBSFN subframes (SRSLTE_ERROR_INVALID_INPUTS).
+ * The MIB: srslte_hip_dl_ctrl_mib_batch ("DL broadcast" below).
  * Not here: PHICH decoding, UL DCIs (srslte_ue_dl_find_ul_dci), carrier indicator / carrier
  * aggregation, the DCI -> grant unpacking (srslte_dci_msg_unpack_pdsch + srslte_ra_dl_dci_to_grant stay with the caller), and
  * the single-subframe drop-in's pcfich.c / pdcch.c, which remain the reference's. */
@@ -653,7 +654,7 @@ uint32_t srslte_hip_dci_format_sizeof(uint32_t nof_prb, uint32_t nof_ports, int 
  * ncce + 2^L > NOF_CCE(cfi), nof_bits 0 or >= SRSLTE_DCI_MAX_BITS - 16 (pdcch.c:572-573), two DCIs of one subframe on a common CCE (the
  * reference would silently overwrite: a deliberate difference), a PHICH group >= srslte_regs_phich_ngroups, ack > 1, more than max_dci DCIs or
  * max_phich PHICHs. TDD cells are refused by create (NULL).
- * Not here: PSS / SSS / PBCH, PHICH decoding, control in the fixed-grant srslte_hip_dl_tx_batch, TDD (the PHICH mi factor, special
+ * Not here: PHICH decoding, control in the fixed-grant srslte_hip_dl_tx_batch, TDD (the PHICH mi factor, special
  * subframes) and MBSFN subframes, DCI packing (srslte_dci_msg_pack_pdsch / _pusch stay with the caller), carrier indicator, and the
  * single-subframe drop-in's pcfich.c / pdcch.c / phich.c, which remain the reference's. */
 typedef struct srslte_hip_dl_ctrl_tx srslte_hip_dl_ctrl_tx_t;
@@ -683,7 +684,7 @@ srslte_hip_dl_ctrl_tx_t* srslte_hip_dl_ctrl_tx_create(const srslte_hip_dl_ctrl_t
 void                     srslte_hip_dl_ctrl_tx_destroy(srslte_hip_dl_ctrl_tx_t* q);
 int srslte_hip_dl_ctrl_tx_put(srslte_hip_dl_ctrl_tx_t* q, uint32_t tti0, uint32_t nof_sf, const srslte_hip_dl_ctrl_tx_in_t* in, void* d_grid, void* stream);
 /* srslte_hip_dl_tx_batch_grants with srslte_hip_dl_ctrl_tx_put on its grids between the PDSCH mapping and the OFDM modulation: one complete
- * subframe per TTI apart from PSS / SSS / PBCH. Refused (SRSLTE_ERROR_INVALID_INPUTS) besides what either call refuses: a ctrl object of
+ * subframe per TTI apart from PSS / SSS / PBCH (srslte_hip_dl_tx_batch_grants_full below adds them). Refused (SRSLTE_ERROR_INVALID_INPUTS) besides what either call refuses: a ctrl object of
  * another cell (nof_prb, ports - a pipeline's nof_ports 0 is 1 -, cell_id, cp_ext), a TDD or MBSFN pipeline, a grant whose cfi differs from
  * in->cfi[grant.sf]. */
 int srslte_hip_dl_tx_batch_grants_ctrl(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
@@ -696,6 +697,63 @@ int srslte_hip_dl_ctrl_phich_ngroups(const srslte_hip_dl_ctrl_tx_cfg_t* cfg);
 int srslte_hip_phich_calc(const srslte_hip_dl_ctrl_tx_cfg_t* cfg, uint32_t n_prb_lowest, uint32_t n_dmrs, uint32_t I_phich, uint32_t* ngroup,
                           uint32_t* nseq);
 int srslte_hip_dl_ctrl_phich_re(const srslte_hip_dl_ctrl_tx_cfg_t* cfg, uint32_t ngroup, uint32_t* re, uint32_t max);
+
+/* ------------------------------------------------------------------ DL broadcast: PSS, SSS and PBCH of a batch of subframes (eNB side) and
+ * the MIB of every subframe 0 of a batch (UE side), on the control objects above, one launch each on the caller's stream, no host
+ * synchronisation and no per-call descriptors (the MIB depends only on the cell and the TTI). FDD only: TDD cells are refused when the
+ * objects are made.
+ * srslte_hip_dl_ctrl_tx_put_bcast writes what put_sync and put_mib of srslte_enb_dl_put_base write (enb_dl.c:297-307, :324-335), on every port
+ * of d_grid [nof_sf][nof_ports][nsym][12 nof_prb] cf32, subframe b being TTI t = tti0 + b, and touches nothing else:
+ *   t % 10 in {0, 5}: the PSS (srslte_pss_generate of cell_id % 3, built on the host with the reference's expression) in the last symbol of
+ *     slot 0 and the SSS (srslte_sss_generate's signal0 / signal5, imaginary part 0) in the one before, each with five zeros on either side
+ *     (pss.c:380-386, sss.c:106-119);
+ *   t % 10 == 0: srslte_pbch_encode (pbch.c:554-607) of srslte_pbch_mib_pack(nof_prb, phich_ext, phich_resources, sfn = t / 10): CRC-16 and
+ *     the port mask of srslte_crc_set_mask, the K = 7 tail-biting code, srslte_rm_conv_tx to 4 nof_bits (480 normal CP, 432 extended), and
+ *     the quarter sfn % 4 alone scrambled with srslte_sequence_pbch at offset (sfn % 4) nof_bits, QPSK, layer mapping + precoding (1.0f),
+ *     put in slot 1 on the REs of srslte_pbch_cp (pbch.c:54-101: the CRS positions of four ports are always skipped).
+ * The result is bit-identical to the reference's. Refused with SRSLTE_ERROR_INVALID_INPUTS: a null object or grid, nof_sf > max_batch.
+ * srslte_hip_dl_ctrl_mib_batch is srslte_pbch_decode called right after srslte_pbch_decode_reset (pbch.c:441-550, as srslte_ue_mib_decode's
+ * first frame) on every subframe whose TTI % 10 == 0; the others get found = 0. d_grid, d_ce, d_res as srslte_hip_dl_ctrl_batch; only
+ * receive antenna 0 is read (sf_symbols[0], ce[p][0]). For nant = 1, 2, 4 up to the object's nof_ports (search_all_ports), or nof_ports
+ * alone: srslte_predecoding_single with noise_estimate (the AVX body, the generic tail) or srslte_predecoding_diversity (the SSE path for 2
+ * ports) + srslte_layerdemap_diversity, QPSK demapping, then for dst = 0-3 decode_frame(0, dst, 1): descrambling at dst nof_bits, the other
+ * quarters SRSLTE_RX_NULL, srslte_rm_conv_rx to 120 in its combining order, times 1 / 2, srslte_viterbi_decode_f, and the CRC check with the
+ * nant mask, which rejects an all-zero payload (pbch.c:373-391). The first hit in (nant, dst) order wins. Stateless: each subframe 0 of a
+ * batch is decoded on its own. d_mib [nof_sf] may be device-visible pinned host memory. Buffers are allocated by srslte_hip_dl_ctrl_create.
+ * Refused with SRSLTE_ERROR_INVALID_INPUTS: null pointers, nof_sf > max_batch.
+ * Not here: soft combining across calls (the reference's frame_idx window and memmove), cell search (PSS / SSS detection), TDD positions of
+ * PSS / SSS, broadcast in the fixed-grant srslte_hip_dl_tx_batch, and the single-subframe drop-in's pbch.c / pss.c / sss.c, which remain
+ * the reference's. */
+int srslte_hip_dl_ctrl_tx_put_bcast(srslte_hip_dl_ctrl_tx_t* q, uint32_t tti0, uint32_t nof_sf, void* d_grid, void* stream);
+/* srslte_hip_dl_tx_batch_grants_ctrl with srslte_hip_dl_ctrl_tx_put_bcast on its grids after the CRS and before the PDSCHs, as the reference
+ * writes sync and MIB before srslte_enb_dl_put_pdsch (a PDSCH RE wins where the two meet): srslte_enb_dl_put_base + _put_phich +
+ * _put_pdcch_dl / _ul + _put_pdsch + srslte_enb_dl_gen_signal, a complete FDD subframe per TTI. Refused as srslte_hip_dl_tx_batch_grants_ctrl. */
+int srslte_hip_dl_tx_batch_grants_full(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
+                                       const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
+                                       const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream);
+typedef struct {            /* per subframe */
+  uint32_t found;           /* 1: a MIB was decoded; 0 otherwise and in every subframe whose TTI % 10 != 0 */
+  uint32_t nof_tx_ports;    /* nant that decoded */
+  int32_t  sfn_offset;      /* as srslte_pbch_decode returns it (dst) */
+  uint32_t nof_prb, phich_ext, phich_resources, sfn; /* srslte_pbch_mib_unpack; sfn = (unpacked + sfn_offset) % 1024 as srsue's sync does */
+  uint8_t  payload[24];     /* the MIB bits */
+} srslte_hip_mib_res_t;
+typedef struct {            /* one decode_frame of the last call (srslte_hip_dl_ctrl_mib_debug_buffer 1) */
+  uint32_t nant, dst;       /* nant 0: not tried */
+  uint32_t hit;             /* srslte_pbch_crc_check passed */
+  uint8_t  data[40];        /* srslte_viterbi_decode_f's output: payload, received CRC (before the mask) */
+} srslte_hip_mib_cand_t;
+int srslte_hip_dl_ctrl_mib_batch(srslte_hip_dl_ctrl_t* q, const void* d_grid, const void* d_ce, const void* d_res, uint32_t tti0, uint32_t nof_sf,
+                                 int search_all_ports, srslte_hip_mib_res_t* d_mib, void* stream);
+/* device buffers of the last srslte_hip_dl_ctrl_mib_batch: 0 LLR rows [max_batch][3][480] float (nant 1, 2, 4; nof_bits LLRs before
+ * descrambling, as q->llr; zeros behind and in rows not tried), 1 candidates [max_batch][3][4] srslte_hip_mib_cand_t (nant, dst) */
+const void* srslte_hip_dl_ctrl_mib_debug_buffer(const srslte_hip_dl_ctrl_t* q, int which);
+/* host helpers (no device needed), for a cell given as srslte_hip_dl_ctrl_cfg_t (limits and receive antennas not looked at): the PBCH REs of
+ * one port's subframe grid in srslte_pbch_put order (240 / 216); the 72 PSS REs then the 72 SSS REs of subframe sf_idx (0 or 5) with their
+ * values val [144][2] (re, im), guards included; srslte_pbch_mib_pack into payload [24]. Return the count, or < 0 for invalid input. */
+int srslte_hip_pbch_re(const srslte_hip_dl_ctrl_cfg_t* cfg, uint32_t* re, uint32_t max);
+int srslte_hip_sync_re(const srslte_hip_dl_ctrl_cfg_t* cfg, uint32_t sf_idx, uint32_t* re, float* val, uint32_t max);
+int srslte_hip_pbch_mib_pack(uint32_t nof_prb, int phich_ext, int phich_resources, uint32_t sfn, uint8_t* payload);
 
 #ifdef __cplusplus
 }

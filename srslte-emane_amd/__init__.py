@@ -929,6 +929,14 @@ class DlTx:
     def encode_grants_ctrl(self, tbs_bytes, tti0, nof_sf, grants, ctrl, cfi, dcis=(), phichs=()):
         """srslte_hip_dl_tx_batch_grants_ctrl: encode_grants with the control region of ctrl (a DlCtrlTx of the same cell) - cfi [nof_sf], dcis and
         phichs as DlCtrlTx.put takes them - on the grids before the OFDM modulation -> (rc, iq [nof_sf][nof_ports][sf_len] or None)."""
+        return self._encode_grants_with(lib().srslte_hip_dl_tx_batch_grants_ctrl, tbs_bytes, tti0, nof_sf, grants, ctrl, cfi, dcis, phichs)
+
+    def encode_grants_full(self, tbs_bytes, tti0, nof_sf, grants, ctrl, cfi, dcis=(), phichs=()):
+        """srslte_hip_dl_tx_batch_grants_full: encode_grants_ctrl with ctrl's PSS / SSS / PBCH put before the PDSCHs, a complete FDD subframe per
+        TTI -> (rc, iq [nof_sf][nof_ports][sf_len] or None)."""
+        return self._encode_grants_with(lib().srslte_hip_dl_tx_batch_grants_full, tbs_bytes, tti0, nof_sf, grants, ctrl, cfi, dcis, phichs)
+
+    def _encode_grants_with(self, fn, tbs_bytes, tti0, nof_sf, grants, ctrl, cfi, dcis, phichs):
         class TxGrant(C.Structure):
             _fields_ = [("sf", C.c_uint32), ("grant", DlGrant)]
         stride = (self.tbs // 8 + 15) & ~15
@@ -938,10 +946,10 @@ class DlTx:
         din = DevBuf.from_host(x)
         arr = (TxGrant * max(1, len(grants)))(*[TxGrant(sf, g) for sf, g in grants])
         inp, keep = _ctrl_tx_in(cfi, dcis, phichs)
-        L = _bind_dl_ctrl_tx(lib())
-        L.srslte_hip_dl_tx_batch_grants_ctrl.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
-                                                         C.POINTER(DlCtrlTxIn), C.c_void_p, C.c_void_p]
-        rc = L.srslte_hip_dl_tx_batch_grants_ctrl(self.h, din.ptr, stride, tti0, nof_sf, arr, len(grants), ctrl.h, C.byref(inp), self.d_iq.ptr, None)
+        _bind_dl_ctrl_tx(lib())
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(DlCtrlTxIn), C.c_void_p,
+                       C.c_void_p]
+        rc = fn(self.h, din.ptr, stride, tti0, nof_sf, arr, len(grants), ctrl.h, C.byref(inp), self.d_iq.ptr, None)
         if rc != SRSLTE_SUCCESS:
             return rc, None
         sync()
@@ -1009,6 +1017,12 @@ def _bind_dl_ctrl(L):
     L.srslte_hip_pdcch_common_locations_ncce.argtypes = [C.c_uint32, vp, C.c_uint32]
     L.srslte_hip_dci_format_sizeof.restype = C.c_uint32
     L.srslte_hip_dci_format_sizeof.argtypes = [C.c_uint32, C.c_uint32, C.c_int]
+    L.srslte_hip_dl_ctrl_mib_batch.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, C.c_int, vp, vp]
+    L.srslte_hip_dl_ctrl_mib_debug_buffer.restype = vp
+    L.srslte_hip_dl_ctrl_mib_debug_buffer.argtypes = [vp, C.c_int]
+    L.srslte_hip_pbch_re.argtypes = [C.POINTER(DlCtrlCfg), vp, C.c_uint32]
+    L.srslte_hip_sync_re.argtypes = [C.POINTER(DlCtrlCfg), C.c_uint32, vp, vp, C.c_uint32]
+    L.srslte_hip_pbch_mib_pack.argtypes = [C.c_uint32, C.c_int, C.c_int, C.c_uint32, vp]
     return L
 
 
@@ -1053,6 +1067,44 @@ def pdcch_common_locations(nof_cce, max_candidates=6):
 def dci_format_sizeof(nof_prb, nof_ports, fmt):
     """srslte_dci_format_sizeof for an FDD cell with a zero srslte_dci_cfg_t (host)."""
     return _bind_dl_ctrl(lib()).srslte_hip_dci_format_sizeof(nof_prb, nof_ports, fmt)
+
+
+class MibRes(C.Structure):
+    """srslte_hip_mib_res_t: the MIB of one subframe."""
+    _fields_ = [("found", C.c_uint32), ("nof_tx_ports", C.c_uint32), ("sfn_offset", C.c_int32), ("nof_prb", C.c_uint32), ("phich_ext", C.c_uint32),
+                ("phich_resources", C.c_uint32), ("sfn", C.c_uint32), ("payload", C.c_uint8 * 24)]
+
+
+class MibCand(C.Structure):
+    """srslte_hip_mib_cand_t: one decode_frame of the MIB decoder."""
+    _fields_ = [("nant", C.c_uint32), ("dst", C.c_uint32), ("hit", C.c_uint32), ("data", C.c_uint8 * 40)]
+
+
+def pbch_re(nof_prb, nof_ports, cell_id, cp_ext=False):
+    """The PBCH REs of one port's subframe grid in srslte_pbch_put's order (host; no GPU)."""
+    out = np.zeros(240, np.uint32)
+    n = _bind_dl_ctrl(lib()).srslte_hip_pbch_re(C.byref(_ctrl_cfg(nof_prb, nof_ports, cell_id, cp_ext)), out.ctypes.data, out.size)
+    if n < 0:
+        raise ValueError("srslte_hip_pbch_re: %d" % n)
+    return out[:n]
+
+
+def sync_re(nof_prb, cell_id, sf_idx, cp_ext=False):
+    """The 72 PSS then 72 SSS REs of subframe sf_idx (0 / 5) with the zero guards -> (re [144] uint32, values [144] complex64) (host)."""
+    re, val = np.zeros(144, np.uint32), np.zeros(144, np.complex64)
+    n = _bind_dl_ctrl(lib()).srslte_hip_sync_re(C.byref(_ctrl_cfg(nof_prb, 1, cell_id, cp_ext)), sf_idx, re.ctypes.data, val.ctypes.data, 144)
+    if n < 0:
+        raise ValueError("srslte_hip_sync_re: %d" % n)
+    return re, val
+
+
+def mib_pack(nof_prb, phich_ext, phich_resources, sfn):
+    """srslte_pbch_mib_pack -> 24 bits (uint8) (host)."""
+    out = np.zeros(24, np.uint8)
+    n = _bind_dl_ctrl(lib()).srslte_hip_pbch_mib_pack(nof_prb, 1 if phich_ext else 0, phich_resources, sfn, out.ctypes.data)
+    if n < 0:
+        raise ValueError("srslte_hip_pbch_mib_pack: %d" % n)
+    return out
 
 
 class DlCtrl:
@@ -1107,6 +1159,37 @@ class DlCtrl:
         _check(L.srslte_hip_memcpy_d2h(cnt.ctypes.data, L.srslte_hip_dl_ctrl_debug_buffer(self.h, 2), cnt.nbytes), "memcpy_d2h")
         return [list(cand[b * DL_CTRL_MAX_CAND:b * DL_CTRL_MAX_CAND + int(cnt[b])]) for b in range(nof_sf)]
 
+    def decode_mib_device(self, d_grid, d_ce, d_res, tti0, nof_sf, search_all_ports, d_mib, stream=None):
+        """srslte_hip_dl_ctrl_mib_batch on device pointers -> the status code."""
+        return lib().srslte_hip_dl_ctrl_mib_batch(self.h, d_grid, d_ce, d_res, tti0, nof_sf, 1 if search_all_ports else 0, d_mib, stream)
+
+    def decode_mib(self, grid, ce, res, tti0, search_all_ports=True):
+        """srslte_hip_dl_ctrl_mib_batch: grid, ce, res as batch takes them -> (rc, [MibRes] or None)."""
+        n = len(res)
+        g = np.ascontiguousarray(grid, np.complex64).reshape(n, self.nof_rx, self.grid_len)
+        h = np.ascontiguousarray(ce, np.complex64).reshape(n, self.nof_ports, self.nof_rx, self.grid_len)
+        r = np.ascontiguousarray(res, np.float32).reshape(n, 10)
+        dg, dh, dr, dm = DevBuf.from_host(g), DevBuf.from_host(h), DevBuf.from_host(r), DevBuf(C.sizeof(MibRes) * n)
+        rc = self.decode_mib_device(dg.ptr, dh.ptr, dr.ptr, tti0, n, search_all_ports, dm.ptr)
+        if rc != SRSLTE_SUCCESS:
+            return rc, None
+        sync()
+        out = (MibRes * n)()
+        _check(lib().srslte_hip_memcpy_d2h(C.addressof(out), dm.ptr, C.sizeof(out)), "memcpy_d2h")
+        return rc, list(out)
+
+    def mib_llr(self, nof_sf):
+        """MIB debug buffer 0: [nof_sf][3][480] float32, rows of nant 1, 2, 4."""
+        out = np.empty(nof_sf * 3 * 480, np.float32)
+        _check(lib().srslte_hip_memcpy_d2h(out.ctypes.data, lib().srslte_hip_dl_ctrl_mib_debug_buffer(self.h, 0), out.nbytes), "memcpy_d2h")
+        return out.reshape(nof_sf, 3, 480)
+
+    def mib_candidates(self, nof_sf):
+        """MIB debug buffer 1: [nof_sf][3][4] MibCand (nant 1, 2, 4; dst 0-3)."""
+        cand = (MibCand * (nof_sf * 12))()
+        _check(lib().srslte_hip_memcpy_d2h(C.addressof(cand), lib().srslte_hip_dl_ctrl_mib_debug_buffer(self.h, 1), C.sizeof(cand)), "memcpy_d2h")
+        return [[list(cand[(b * 3 + s) * 4:(b * 3 + s) * 4 + 4]) for s in range(3)] for b in range(nof_sf)]
+
     def free(self):
         if self.h:
             lib().srslte_hip_dl_ctrl_destroy(self.h)
@@ -1141,6 +1224,7 @@ def _bind_dl_ctrl_tx(L):
     L.srslte_hip_dl_ctrl_tx_create.argtypes = [C.POINTER(DlCtrlTxCfg)]
     L.srslte_hip_dl_ctrl_tx_destroy.argtypes = [vp]
     L.srslte_hip_dl_ctrl_tx_put.argtypes = [vp, C.c_uint32, C.c_uint32, C.POINTER(DlCtrlTxIn), vp, vp]
+    L.srslte_hip_dl_ctrl_tx_put_bcast.argtypes = [vp, C.c_uint32, C.c_uint32, vp, vp]
     L.srslte_hip_dl_ctrl_phich_ngroups.argtypes = [C.POINTER(DlCtrlTxCfg)]
     L.srslte_hip_phich_calc.argtypes = [C.POINTER(DlCtrlTxCfg), C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.srslte_hip_dl_ctrl_phich_re.argtypes = [C.POINTER(DlCtrlTxCfg), C.c_uint32, vp, C.c_uint32]
@@ -1211,6 +1295,18 @@ class DlCtrlTx:
         g = np.ascontiguousarray(grid, np.complex64).reshape(len(cfi), self.nof_ports, self.grid_len)
         d = DevBuf.from_host(g)
         rc = self.put_device(d.ptr, tti0, len(cfi), cfi, dcis, phichs)
+        sync()
+        return rc, d.to_host(np.complex64).reshape(g.shape)
+
+    def put_bcast_device(self, d_grid, tti0, nof_sf, stream=None):
+        """srslte_hip_dl_ctrl_tx_put_bcast on a device grid [nof_sf][nof_ports][grid_len] -> the status code."""
+        return lib().srslte_hip_dl_ctrl_tx_put_bcast(self.h, tti0, nof_sf, d_grid, stream)
+
+    def put_bcast(self, grid, tti0):
+        """PSS / SSS / PBCH of TTIs tti0 .. tti0 + nof_sf - 1 on grid [nof_sf][nof_ports][grid_len] complex64 (host) -> (rc, the grids after)."""
+        g = np.ascontiguousarray(grid, np.complex64).reshape(-1, self.nof_ports, self.grid_len)
+        d = DevBuf.from_host(g)
+        rc = self.put_bcast_device(d.ptr, tti0, g.shape[0])
         sync()
         return rc, d.to_host(np.complex64).reshape(g.shape)
 

@@ -1,8 +1,10 @@
-// Host tables of the DL control region (ctrl_host.hpp): REG lists and scrambling sequences, shared by pdcch.hip and pdcch_tx.hip.
+// Host tables of the DL control region (ctrl_host.hpp): REG lists and scrambling sequences, shared by pdcch.hip and pdcch_tx.hip, and the
+// PSS / SSS / PBCH tables of pbch.hip.
 #include "ctrl_host.hpp"
 #include "common.hpp"
 #include "phy_hip_internal.hpp"
 #include <math.h>
+#include <string.h>
 
 namespace {
 struct Reg {
@@ -118,4 +120,90 @@ void ctrl_scrambling(uint32_t cell_id, uint32_t pdcch_bits, std::vector<uint32_t
     for (uint32_t i = 0; i < pdcch_bits; i++) scr[10 + s * w + (i >> 5)] |= (uint32_t)(c[i] & 1) << (i & 31);
   }
   *scr_words = w;
+}
+
+void bcast_build(uint32_t nof_prb, uint32_t cell_id, int cp_ext, BcastHost& b)
+{
+  const uint32_t w = 12 * nof_prb, nsym = cp_ext ? 6 : 7, v = cell_id % 3;
+  // srslte_pbch_cp with put = true: the output walks slot 1 from the first RE of the six central PRBs. A symbol with reference signals takes
+  // v REs, then 23 times (skip one, take two), then (skip one, take 2 - v) when 2 - v > 0: the CRS positions of four ports are never used.
+  // After each of the first two symbols the walk moves on by w - 72, plus one when v == 2 (the last skip did not happen). Symbols 2 and 3
+  // are taken whole on a normal-CP cell; on an extended-CP cell symbol 2 is, and symbol 3 (which carries CRS) is walked like symbol 0
+  b.pbch_re.clear();
+  uint32_t out = nsym * w + w / 2 - 36;
+  auto     ref_sym = [&](bool advance) {
+    for (uint32_t i = 0; i < v; i++) b.pbch_re.push_back(out++);
+    for (int i = 0; i < 23; i++) {
+      out++;
+      b.pbch_re.push_back(out++), b.pbch_re.push_back(out++);
+    }
+    if (2 > v) {
+      out++;
+      for (uint32_t i = 0; i < 2 - v; i++) b.pbch_re.push_back(out++);
+    }
+    if (advance) out += w - 72 + (v == 2 ? 1 : 0);
+  };
+  auto full_sym = [&]() {
+    for (int i = 0; i < 72; i++) b.pbch_re.push_back(out++);
+    out += w - 72;
+  };
+  ref_sym(true);
+  ref_sym(true);
+  full_sym();
+  if (cp_ext) {
+    ref_sym(false);
+  } else {
+    full_sym();
+  }
+  b.nof_bits = cp_ext ? 432 : 480;
+  // PSS in the last, SSS in the second-to-last symbol of slot 0, 62 values around DC with five zeros on each side
+  b.pss_k0 = (nsym - 1) * w + w / 2 - 31 - 5;
+  b.sss_k0 = (nsym - 2) * w + w / 2 - 31 - 5;
+  memset(b.pss, 0, sizeof(b.pss));
+  memset(b.sss, 0, sizeof(b.sss));
+  // srslte_pss_generate (36.211 6.11.1.1): Zadoff-Chu of root 25 / 29 / 34; the phase is formed in double as the reference's expression
+  // promotes it, rounded to float, then cosf / sinf
+  const float root = v == 0 ? 25.0f : v == 1 ? 29.0f : 34.0f;
+  for (int i = 0; i < 62; i++) {
+    const float fi  = (float)i;
+    float       arg = (float)((float)-1 * M_PI * root * (i < 31 ? fi * (fi + 1.0) : (fi + 2.0) * (fi + 1.0)) / 63.0);
+    if (arg == 0.f) arg = 0.f; // i = 0: the reference's build (-Ofast, no signed zeros) has sinf(+0), not sinf(-0)
+    b.pss[5 + i][0] = cosf(arg);
+    b.pss[5 + i][1] = sinf(arg);
+  }
+  // srslte_sss_generate (36.211 6.11.2.1): the m-sequences s~, c~, z~ of x^5 + x^2 + 1, x^5 + x^3 + 1, x^5 + x^4 + x^2 + x + 1; as in gen_sss.c,
+  // c0 is c~ shifted by N_id_2 and c1 by N_id_2 + 3
+  int st[31], ct[31], zt[31], x[31];
+  const int taps[3][4] = {{2, 0, -1, -1}, {3, 0, -1, -1}, {4, 2, 1, 0}};
+  int*      dst[3]     = {st, ct, zt};
+  for (int s = 0; s < 3; s++) {
+    memset(x, 0, sizeof(x));
+    x[4] = 1;
+    for (int i = 0; i < 26; i++) {
+      int t = 0;
+      for (int j = 0; j < 4; j++)
+        if (taps[s][j] >= 0) t += x[i + taps[s][j]];
+      x[i + 5] = t % 2;
+    }
+    for (int i = 0; i < 31; i++) dst[s][i] = 1 - 2 * x[i];
+  }
+  const uint32_t id1 = cell_id / 3, qp = id1 / 30, q = (id1 + qp * (qp + 1) / 2) / 30, mp = id1 + q * (q + 1) / 2;
+  const uint32_t m0 = mp % 31, m1 = (m0 + mp / 31 + 1) % 31;
+  for (int i = 0; i < 31; i++) {
+    const int s0 = st[(i + m0) % 31], s1 = st[(i + m1) % 31], c0 = ct[(i + v) % 31], c1 = ct[(i + v + 3) % 31];
+    const int z0 = zt[(i + m0 % 8) % 31], z1 = zt[(i + m1 % 8) % 31];
+    b.sss[0][5 + 2 * i] = (float)(s0 * c0), b.sss[0][5 + 2 * i + 1] = (float)(s1 * c1 * z0);
+    b.sss[1][5 + 2 * i] = (float)(s1 * c0), b.sss[1][5 + 2 * i + 1] = (float)(s0 * c1 * z1);
+  }
+  // srslte_sequence_pbch: c_init = cell_id, 1920 / 1728 bits
+  std::vector<uint8_t> c;
+  lte_gold_sequence(cell_id, 4 * b.nof_bits, c);
+  b.scr.assign((4 * b.nof_bits + 31) / 32, 0u);
+  for (uint32_t i = 0; i < 4 * b.nof_bits; i++) b.scr[i >> 5] |= (uint32_t)(c[i] & 1) << (i & 31);
+}
+
+uint32_t mib_head(uint32_t nof_prb, int phich_ext, int phich_resources)
+{
+  const uint32_t bw = nof_prb <= 6 ? 0 : nof_prb <= 15 ? 1 : 1 + nof_prb / 25;
+  return (bw & 7) << 3 | (phich_ext ? 1u : 0u) << 2 | ((uint32_t)phich_resources & 3);
 }

@@ -22,3 +22,19 @@ int ctrl_build_regs(const srslte_hip_dl_ctrl_cfg_t* c, CtrlRegs& r);
 // srslte_sequence_pcfich (32 bits; its first 12 are srslte_sequence_phich, the same c_init: sequences.c:36-46) and srslte_sequence_pdcch of
 // pdcch_bits bits (sequences.c:51-53) of subframes 0-9, packed bit i -> word i / 32, bit i % 32: scr = [10 PCFICH words][10][scr_words]
 void ctrl_scrambling(uint32_t cell_id, uint32_t pdcch_bits, std::vector<uint32_t>& scr, int* scr_words);
+
+// Broadcast channels of one cell (pbch.hip): the RE list of srslte_pbch_cp (pbch.c:54-101) as indices into one port's [nsym][12 prb] grid
+// of the subframe (slot 1), the 72 REs of the PSS and of the SSS with their zero guards (pss.c:380-386, sss.c:106-119) and their values,
+// srslte_sequence_pbch (4 nof_bits bits) packed bit i -> word i / 32, bit i % 32
+struct BcastHost {
+  std::vector<uint32_t> pbch_re;      // 240 (normal CP) / 216 (extended) in srslte_pbch_put order
+  uint32_t              pss_k0, sss_k0; // first RE of the 72 (5 guards, 62 values, 5 guards) of each signal in slot 0
+  float                 pss[72][2];   // srslte_pss_generate(cell_id % 3) with the guards
+  float                 sss[2][72];   // srslte_sss_generate's signal0 / signal5 with the guards (real parts; the imaginary parts are 0)
+  std::vector<uint32_t> scr;          // srslte_sequence_pbch
+  uint32_t              nof_bits;     // 480 / 432
+};
+void bcast_build(uint32_t nof_prb, uint32_t cell_id, int cp_ext, BcastHost& b);
+
+// srslte_pbch_mib_pack (pbch.c:318-354) without the SFN: the first 6 bits (bandwidth, PHICH length, PHICH resources) as an integer, MSB first
+uint32_t mib_head(uint32_t nof_prb, int phich_ext, int phich_resources);

@@ -10,6 +10,7 @@
 // through a PinnedRing.
 #include "common.hpp"
 #include "ctrl_host.hpp"
+#include "ctrl_tx_dev.hpp"
 #include "phy_hip_internal.hpp"
 #include "pinned_ring.hpp"
 #include <math.h>
@@ -19,8 +20,6 @@
 namespace {
 
 constexpr int MAX_F = 128; // nof_bits + 16 < SRSLTE_DCI_MAX_BITS (pdcch.c:572-573)
-
-__constant__ uint8_t RM_PERM_TX[32] = {1, 17, 9, 25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31, 0, 16, 8, 24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30};
 
 struct CtrlTxGeom {
   const uint32_t* re;         // [16 PCFICH][n[0]][n[1]][n[2]][units x 12 PHICH] RE indices into one port's [nsym][12 prb] grid
@@ -37,40 +36,6 @@ struct DciTxDesc {
   uint32_t sf, cfi, L, ncce, nof_bits, rnti;
   uint32_t pay[4]; // payload bit i -> word i / 32, bit i % 32
 };
-
-// srslte_mod_modulate's QPSK (lte_tables.c:46-58) / BPSK (:32-41) level, QPSK_LEVEL = BPSK_LEVEL = 1/sqrt(2) as float
-constexpr float LVL = 0.70710677f;
-
-__device__ __forceinline__ cf32 qpsk(uint32_t b0, uint32_t b1) { return make_float2(b0 ? -LVL : LVL, b1 ? -LVL : LVL); }
-
-// one Alamouti pair of srslte_precoding_diversity: position 0 gives xa, -conj(xb), position 1 xb, conj(xa), on the pair's two ports, times s
-__device__ __forceinline__ void sfbc(cf32 xa, cf32 xb, int odd, float s, cf32& first, cf32& second)
-{
-  if (!odd) {
-    first  = make_float2(xa.x * s, xa.y * s);
-    second = make_float2(-xb.x * s, xb.y * s);
-  } else {
-    first  = make_float2(xb.x * s, xb.y * s);
-    second = make_float2(xa.x * s, -xa.y * s);
-  }
-}
-
-// srslte_layermap_diversity + srslte_precoding_diversity (layermap.c:36-44, precoding.c:1848-1893) at position k of a group of P symbols whose
-// layer symbols are x[0 .. P): y[p] for every port. 2 ports: one pair; 4 ports: layers 0, 1 on ports 0 / 2 at positions 0, 1, layers 2, 3 on
-// ports 1 / 3 at positions 2, 3, zero on the other two ports. 1 port: the symbol itself, no scaling.
-__device__ __forceinline__ void precode(int P, int k, const cf32* x, float s, cf32* y)
-{
-  y[0] = y[1] = y[2] = y[3] = make_float2(0.f, 0.f);
-  if (P == 1) {
-    y[0] = x[0];
-  } else if (P == 2) {
-    sfbc(x[0], x[1], k & 1, s, y[0], y[1]);
-  } else if (k < 2) {
-    sfbc(x[0], x[1], k & 1, s, y[0], y[2]);
-  } else {
-    sfbc(x[2], x[3], k & 1, s, y[1], y[3]);
-  }
-}
 
 // symbol m (0-11) of a PHICH entry before precoding, d0 of srslte_phich_encode: BPSK of the ack, times the orthogonal sequence nseq (36.211
 // Table 6.9.1-2, w_normal / w_ext of phich.c:36-41), times c(m) of srslte_sequence_phich; on an extended-CP cell the six symbols of group
@@ -236,6 +201,7 @@ struct srslte_hip_dl_ctrl_tx {
   std::vector<uint32_t>       words;   // the descriptor block of a call, as it is built
   std::vector<uint8_t>        used;    // CCEs taken, per subframe
   std::vector<uint32_t>       ph_unit; // per PHICH of the call: its mapping unit
+  BcastTables*                bc = nullptr; // PSS / SSS / PBCH (pbch.hip)
 };
 
 namespace {
@@ -302,6 +268,8 @@ int dl_ctrl_tx_check(srslte_hip_dl_ctrl_tx_t* q, uint32_t nof_sf, const srslte_h
 
 const srslte_hip_dl_ctrl_tx_cfg_t* dl_ctrl_tx_cfg(const srslte_hip_dl_ctrl_tx_t* q) { return q ? &q->cfg : nullptr; }
 
+const BcastTables* dl_ctrl_tx_bcast(const srslte_hip_dl_ctrl_tx_t* q) { return q ? q->bc : nullptr; }
+
 extern "C" {
 
 void srslte_hip_dl_ctrl_tx_destroy(srslte_hip_dl_ctrl_tx_t* q)
@@ -311,6 +279,7 @@ void srslte_hip_dl_ctrl_tx_destroy(srslte_hip_dl_ctrl_tx_t* q)
   (void)hipFree(q->d_scr);
   (void)hipFree(q->d_desc);
   q->ring.destroy();
+  bcast_tables_destroy(q->bc);
   delete q;
 }
 
@@ -339,7 +308,8 @@ srslte_hip_dl_ctrl_tx_t* srslte_hip_dl_ctrl_tx_create(const srslte_hip_dl_ctrl_t
   q->desc_bytes = 4 * ((size_t)cfg->max_batch + (size_t)cfg->max_dci * (sizeof(DciTxDesc) / 4) + (size_t)cfg->max_batch * g.units + 1 + cfg->max_phich);
   if (hipMalloc(&q->d_re, re.size() * 4) != hipSuccess || hipMalloc(&q->d_scr, scr.size() * 4) != hipSuccess ||
       hipMalloc(&q->d_desc, q->desc_bytes) != hipSuccess || hipMemcpy(q->d_re, re.data(), re.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(q->d_scr, scr.data(), scr.size() * 4, hipMemcpyHostToDevice) != hipSuccess || q->ring.init(q->desc_bytes) != SRSLTE_SUCCESS) {
+      hipMemcpy(q->d_scr, scr.data(), scr.size() * 4, hipMemcpyHostToDevice) != hipSuccess || q->ring.init(q->desc_bytes) != SRSLTE_SUCCESS ||
+      !(q->bc = bcast_tables_create(&rc, cfg->phich_ext, cfg->phich_resources, false))) {
     hip_log("[srslte_hip] srslte_hip_dl_ctrl_tx_create: device allocation failed\n");
     srslte_hip_dl_ctrl_tx_destroy(q);
     return nullptr;

@@ -427,10 +427,11 @@ static int dl_tx_grants_init(srslte_hip_dl_tx_t* q, uint32_t V)
 // true, including upstream's stale-offset rule); allocations that overlap within a subframe are the caller's error (which PDSCH wins an RE is
 // not defined here; upstream the later put would). The object's
 // cell, antenna ports (TM1 / transmit diversity), p_a apply; cfg.tbs bounds every grant's tbs, cfg.max_grants the number of PDSCHs per call.
-// ctrl / in: srslte_hip_dl_tx_batch_grants_ctrl's control region, put on the grids after the PDSCHs (nullptr: none)
+// ctrl / in: srslte_hip_dl_tx_batch_grants_ctrl's control region, put on the grids after the PDSCHs (nullptr: none); bcast: ctrl's PSS / SSS /
+// PBCH put between the grid initialisation and the PDSCHs (srslte_hip_dl_tx_batch_grants_full)
 static int dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
                               const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
-                              const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream)
+                              const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream, bool bcast = false)
 {
   if (!q || !d_tb || !d_iq || !grants || nof_sf > q->cfg.max_batch) return SRSLTE_ERROR_INVALID_INPUTS;
   const uint32_t V = q->cfg.max_grants ? q->cfg.max_grants : q->cfg.max_batch, P = q->cfg.nof_prb, cell_id = q->cfg.cell_id;
@@ -509,6 +510,9 @@ static int dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32
   hipLaunchKernelGGL(pdsch_tx_map_kernel, dim3(ceil_div(tg.grid_len, 256), nof_sf * npt), dim3(256), 0, st, (const cf32*)g->d_y,
                      (const cf32*)srslte_hip_chest_dl_pilots(q->crs), q->d_grid, 8 * (int)P, tg);
   LAUNCH_CHECK();
+  if (bcast) {
+    if (int r = bcast_tx_launch(dl_ctrl_tx_bcast(ctrl), tti0, nof_sf, q->d_grid, st)) return r;
+  }
   if (nof_grants) {
     hipLaunchKernelGGL(pdsch_relist_kernel, dim3(nof_grants), dim3(RELIST_THREADS), 0, st, (const GrantDev*)d_gr, g->d_relist, (int)P, (int)cell_id,
                        (int)g->max_re, npt, q->cfg.cp_ext ? 6 : 7);
@@ -545,12 +549,10 @@ extern "C" int srslte_hip_dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_
   return dl_tx_batch_grants(q, d_tb, tb_stride, tti0, nof_sf, grants, nof_grants, nullptr, nullptr, d_iq, stream);
 }
 
-// srslte_enb_dl_put_base's PCFICH, srslte_enb_dl_put_phich, srslte_enb_dl_put_pdcch_dl / _ul and srslte_enb_dl_put_pdsch of a run of TTIs
-// (sf_worker.cc:428-753) in one call: the grants path above with srslte_hip_dl_ctrl_tx_put on its grids before the OFDM modulation. Everything
-// the control region refuses is refused before anything is queued.
-extern "C" int srslte_hip_dl_tx_batch_grants_ctrl(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
-                                                  const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
-                                                  const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream)
+// the checks srslte_hip_dl_tx_batch_grants_ctrl / _full add: the control object's cell is the pipeline's, and everything the control region
+// refuses is refused before anything is queued
+static int dl_tx_ctrl_check(srslte_hip_dl_tx_t* q, uint32_t nof_sf, const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants,
+                            srslte_hip_dl_ctrl_tx_t* ctrl, const srslte_hip_dl_ctrl_tx_in_t* in)
 {
   const srslte_hip_dl_ctrl_tx_cfg_t* cc = dl_ctrl_tx_cfg(ctrl);
   if (!q || !cc || !in || !grants || q->cfg.tdd || q->cfg.mbsfn || cc->nof_prb != q->cfg.nof_prb || cc->nof_ports != (uint32_t)q->g.nof_ports ||
@@ -560,5 +562,26 @@ extern "C" int srslte_hip_dl_tx_batch_grants_ctrl(srslte_hip_dl_tx_t* q, const u
   for (uint32_t p = 0; p < nof_grants; p++) {
     if (grants[p].sf < nof_sf && grants[p].grant.cfi != in->cfi[grants[p].sf]) return SRSLTE_ERROR_INVALID_INPUTS;
   }
+  return SRSLTE_SUCCESS;
+}
+
+// srslte_enb_dl_put_base's PCFICH, srslte_enb_dl_put_phich, srslte_enb_dl_put_pdcch_dl / _ul and srslte_enb_dl_put_pdsch of a run of TTIs
+// (sf_worker.cc:428-753) in one call: the grants path above with srslte_hip_dl_ctrl_tx_put on its grids before the OFDM modulation. Everything
+// the control region refuses is refused before anything is queued.
+extern "C" int srslte_hip_dl_tx_batch_grants_ctrl(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
+                                                  const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
+                                                  const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream)
+{
+  if (int r = dl_tx_ctrl_check(q, nof_sf, grants, nof_grants, ctrl, in)) return r;
   return dl_tx_batch_grants(q, d_tb, tb_stride, tti0, nof_sf, grants, nof_grants, ctrl, in, d_iq, stream);
+}
+
+// the same with PSS / SSS / PBCH (srslte_hip_dl_ctrl_tx_put_bcast) put after the CRS and before the PDSCHs: the whole of
+// srslte_enb_dl_put_base, a complete FDD subframe per TTI
+extern "C" int srslte_hip_dl_tx_batch_grants_full(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
+                                                  const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
+                                                  const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream)
+{
+  if (int r = dl_tx_ctrl_check(q, nof_sf, grants, nof_grants, ctrl, in)) return r;
+  return dl_tx_batch_grants(q, d_tb, tb_stride, tti0, nof_sf, grants, nof_grants, ctrl, in, d_iq, stream, true);
 }

@@ -85,3 +85,12 @@ int tdec_run_batch_w(srslte_hip_tdec_t* q, const void* d_input, int llr8, uint32
 // pdcch_tx.hip: the checks of srslte_hip_dl_ctrl_tx_put alone (nothing is queued), and the cell an object was made for
 int                                dl_ctrl_tx_check(srslte_hip_dl_ctrl_tx_t* q, uint32_t nof_sf, const srslte_hip_dl_ctrl_tx_in_t* in);
 const srslte_hip_dl_ctrl_tx_cfg_t* dl_ctrl_tx_cfg(const srslte_hip_dl_ctrl_tx_t* q);
+// pbch.hip: the broadcast tables of a cell on the device (PBCH REs, PSS / SSS, srslte_sequence_pbch; rx: the MIB decoder's buffers for
+// c->max_batch subframes), owned by a srslte_hip_dl_ctrl_tx_t / srslte_hip_dl_ctrl_t; the broadcast put of a batch on the stream
+struct BcastTables;
+BcastTables* bcast_tables_create(const srslte_hip_dl_ctrl_cfg_t* c, int phich_ext, int phich_resources, bool rx);
+void         bcast_tables_destroy(BcastTables* t);
+int          bcast_tx_launch(const BcastTables* t, uint32_t tti0, uint32_t nof_sf, void* d_grid, hipStream_t st);
+// pdcch_tx.hip / pdcch.hip: an object's broadcast tables
+const BcastTables* dl_ctrl_tx_bcast(const srslte_hip_dl_ctrl_tx_t* q);
+const BcastTables* dl_ctrl_bcast(const srslte_hip_dl_ctrl_t* q);
