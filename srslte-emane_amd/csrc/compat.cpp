@@ -692,7 +692,11 @@ void srslte_ofdm_tx_slot_mbsfn(srslte_ofdm_t* q, cf_t* input, cf_t* output)
 }
 
 // ====================================================================================================== transform precoding
-bool srslte_dft_precoding_valid_prb(uint32_t nof_prb) { return srslte_hip_dft_precoding_valid_prb(nof_prb) != 0; }
+bool srslte_dft_precoding_valid_prb(uint32_t nof_prb)
+{ // dft_precoding.c:87-98: upstream's table ends at 100 PRB and accepts 0 (srsenb's scheduler_metric.cc:222 counts down until this is true);
+  // the device path's own rule (srslte_hip_dft_precoding_valid_prb) is 36.211's 2^a 3^b 5^c up to 110
+  return nof_prb == 0 || (nof_prb <= 100 && srslte_hip_dft_precoding_valid_prb(nof_prb) != 0);
+}
 
 int srslte_dft_precoding_init(srslte_dft_precoding_t* q, uint32_t max_prb, bool is_tx)
 { // dft_precoding.c:39-69: one normalised plan per valid nof_prb
@@ -722,7 +726,7 @@ void srslte_dft_precoding_free(srslte_dft_precoding_t* q)
 
 int srslte_dft_precoding(srslte_dft_precoding_t* q, cf_t* input, cf_t* output, uint32_t nof_prb, uint32_t nof_symbols)
 { // dft_precoding.c:100-113
-  if (!srslte_dft_precoding_valid_prb(nof_prb) || nof_prb > q->max_prb) {
+  if (nof_prb == 0 || !srslte_dft_precoding_valid_prb(nof_prb) || nof_prb > q->max_prb) {
     ERROR("Error invalid number of PRB (%u)", nof_prb);
     return SRSLTE_ERROR;
   }
@@ -1090,7 +1094,8 @@ void srslte_chest_dl_free(srslte_chest_dl_t* q)
 
 int srslte_chest_dl_set_cell(srslte_chest_dl_t* q, srslte_cell_t cell)
 { // chest_dl.c:244-300
-  if (!q || !q->tmp_noise || cell.nof_prb < 6 || cell.nof_prb > SRSLTE_MAX_PRB || cell.id > 503) return SRSLTE_ERROR_INVALID_INPUTS;
+  // srslte_cell_isvalid (phy_common.c:38-60): a cell of more than 100 PRB is refused before anything changes, as upstream
+  if (!q || !q->tmp_noise || cell.nof_prb < 6 || cell.nof_prb > 100 || cell.id > 503 || cell.nof_ports > SRSLTE_MAX_PORTS) return SRSLTE_ERROR_INVALID_INPUTS;
   if (q->cell.id == cell.id && q->cell.nof_prb == cell.nof_prb && ((ChestState*)q->tmp_noise)->h) return SRSLTE_SUCCESS;
   chest_drop_cell(q);
   auto* st = (ChestState*)q->tmp_noise;

@@ -190,3 +190,51 @@ def test_symbol_size_families_without_gpu():
     for prb, n in ((100, 1024), (25, 300), (50, 1000), (0, 128), (111, 2048), (6, 64)):  # carriers do not fit / not a size of either family / no such cell
         assert not lib.srslte_hip_ofdm_create_sz(prb, n, 1, 1), (prb, n)
     assert lib.srslte_hip_chest_dl_set_symbol_sz(None, 2048) == -2  # SRSLTE_ERROR_INVALID_INPUTS
+
+
+def test_tc_interl_object_without_gpu():
+    """srslte_tc_interl_init / _LTE_gen / _LTE_gen_interl / _free (tc_interl_lte.c:40-114) on the caller's srslte_tc_interl_t: the tables the
+    oracle's QPP gives, and a block longer than max_long_cb refused."""
+    lib = C.CDLL(HIP_SO)
+
+    class Interl(C.Structure):
+        _fields_ = [("forward", C.POINTER(C.c_uint16)), ("reverse", C.POINTER(C.c_uint16)), ("max_long_cb", C.c_uint32)]
+    h = Interl()
+    assert lib.srslte_tc_interl_init(C.byref(h), 6144) == 0 and h.max_long_cb == 6144
+    for K, W in ((40, 1), (1008, 1), (6144, 1), (504, 8), (6144, 16)):
+        rc = lib.srslte_tc_interl_LTE_gen(C.byref(h), K) if W == 1 else lib.srslte_tc_interl_LTE_gen_interl(C.byref(h), K, W)
+        rf, rr = np.zeros(K, np.uint16), np.zeros(K, np.uint16)
+        assert rc == 0 and oracle().orc_qpp(K, W, p(rf), p(rr)) == 0
+        assert np.array_equal(np.ctypeslib.as_array(h.forward, (K,)), rf) and np.array_equal(np.ctypeslib.as_array(h.reverse, (K,)), rr), (K, W)
+    lib.srslte_tc_interl_free(C.byref(h))
+    small = Interl()
+    assert lib.srslte_tc_interl_init(C.byref(small), 512) == 0 and lib.srslte_tc_interl_LTE_gen(C.byref(small), 1008) == -1
+    lib.srslte_tc_interl_free(C.byref(small))
+
+
+# Entry points of include/srslte_hip/srslte_compat.h that no test in tests/ and no oracle/dropin_*.c driver names, each with the reason
+COMPAT_NOT_NAMED = {
+    "srslte_dft_load": "FFTW wisdom import, a no-op here (nothing to persist); upstream it only prints a warning without FFTW_WISDOM_FILE "
+                       "(dft_fftw.c:44-50). Reached by the drop-in program pusch_test, which calls it at start (pusch_test.c:198)",
+    "srslte_dft_exit": "FFTW wisdom export and fftwf_cleanup, a no-op here (dft_fftw.c:52-57). Reached by the drop-in programs pusch_test, "
+                       "pdsch_test, pmch_test, ofdm_test and phy_dl_test at exit",
+    "srslte_dft_plan_set_db": "sets a flag; no caller in the reference's lib/, srsue/ or srsenb/ sets it",
+}
+
+
+def test_every_compat_entry_point_is_named_by_a_test():
+    """Each function srslte_compat.h declares is named in tests/*.py, in an oracle/dropin_*.c driver, or in COMPAT_NOT_NAMED with a reason:
+    an entry point of the single-call API that nothing exercises cannot be wrong without the suite noticing."""
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "srslte_hip", "srslte_compat.h")).read(), flags=re.S)
+    hdr = re.sub(r"//[^\n]*", "", hdr)  # names in comments of either kind are not entry points
+    names = sorted(set(re.findall(r"\b(srslte_[a-zA-Z0-9_]+)\s*\(", hdr)))
+    assert len(names) > 100
+    files = [os.path.join(ROOT, "tests", f) for f in os.listdir(os.path.join(ROOT, "tests")) if f.endswith(".py")]
+    files += [os.path.join(ROOT, "oracle", f) for f in os.listdir(os.path.join(ROOT, "oracle")) if f.startswith("dropin_") and f.endswith(".c")]
+    text = "".join(open(f).read() for f in files if os.path.basename(f) != "test_abi_and_host.py")
+    text += re.sub(r"COMPAT_NOT_NAMED = \{.*?\n\}", "", open(__file__).read(), flags=re.S)
+    unnamed = [n for n in names if not re.search(r"\b%s\b" % n, text)]
+    assert sorted(set(unnamed) - set(COMPAT_NOT_NAMED)) == [], "no test names these entry points: give them a test or a reason"
+    assert sorted(set(COMPAT_NOT_NAMED) - set(names)) == [], "allow-listed names that the header no longer declares"
+    stale = sorted(set(COMPAT_NOT_NAMED) - set(unnamed))
+    assert stale == [], "allow-listed names that a test now names: drop them from COMPAT_NOT_NAMED"

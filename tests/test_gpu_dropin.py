@@ -174,3 +174,15 @@ def test_registered_log_handler_receives_diagnostics():
     diagnostics go to the registered callback like the reference's ERROR() does (debug.h:75-89). oracle/dropin_log_test.c."""
     rc, out = run("dropin_log_test", [])
     assert rc == 0, out
+
+
+@need_bin
+def test_objects_built_at_max_prb_follow_the_cell():
+    """srsue builds its objects once for the widest cell and resizes them when it learns the real one (cc_worker.cc:74,79): oracle/
+    dropin_resize_test.c builds srslte_enb_dl / _ue_dl / _ue_ul / _enb_ul at SRSLTE_MAX_PRB and moves them through eight cells (6 to 100 PRB,
+    1 and 2 ports, extended CP) with their set_cell calls, which resize this library's OFDM objects and estimator. On every cell each DCI is
+    found and every PDSCH and PUSCH transport block arrives byte for byte."""
+    rc, out = run("dropin_resize_test", [], timeout=300)
+    cells = re.findall(r"^cell id=\d+ prb=(\d+) ports=(\d) cp=(\w+): (\w+)", out, re.M)
+    assert rc == 0 and len(cells) == 8 and all(c[3] == "ok" for c in cells), out
+    assert {c[0] for c in cells} >= {"6", "15", "25", "50", "75", "100"} and {c[1] for c in cells} == {"1", "2"} and "ext" in {c[2] for c in cells}
