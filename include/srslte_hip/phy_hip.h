@@ -755,6 +755,111 @@ int srslte_hip_pbch_re(const srslte_hip_dl_ctrl_cfg_t* cfg, uint32_t* re, uint32
 int srslte_hip_sync_re(const srslte_hip_dl_ctrl_cfg_t* cfg, uint32_t sf_idx, uint32_t* re, float* val, uint32_t max);
 int srslte_hip_pbch_mib_pack(uint32_t nof_prb, int phich_ext, int phich_resources, uint32_t sfn, uint8_t* payload);
 
+/* ------------------------------------------------------------------ UL control: PUCCH formats 1, 1a, 1b, 2, 2a, 2b (eNB receive, UE transmit)
+ * srslte_hip_ul_ctrl_pucch_batch does what srslte_enb_ul_get_pucch does (enb_ul.c:175-228) for a list of (subframe, UE) requests, in one
+ * launch on the caller's stream with no host synchronisation (descriptors through pinned buffers, as the DL control calls):
+ *   resource selection  srslte_ue_ul_pucch_resource_selection with a zero srslte_uci_value_t (ue_ul.c:482-531 get_format, :823-900 get_npucch):
+ *                       the CQI is dropped when HARQ-ACK collides and simul_cqi_ack is off; an SR TTI uses n_pucch_sr; formats 1/1a/1b
+ *                       use ncce + N_pucch_1, formats 2/2a/2b n_pucch_2. Done on the host when the call is made.
+ *   estimate            srslte_chest_ul_estimate_pucch (chest_ul.c:329-412): LS estimates at the DMRS of srslte_refsignal_dmrs_pucch_gen
+ *                       (refsignal_ul.c:558-639), each slot's mean over its DMRS symbols, the 3-tap filter {0.3333, 1 - 2 0.3333, 0.3333}
+ *                       with srslte_conv_same_cf's end extrapolation. 2a / 2b: every DMRS hypothesis, the last maximum of |sum| (>=) wins
+ *                       and gives the HARQ-ACK bits.
+ *   decode              srslte_pucch_decode (pucch.c:767-828, decode_signal :612-708): srslte_predecoding_single with req.noise_estimate
+ *                       (the AVX body over 16 (n / 16) symbols, the generic tail). 1/1a/1b: srslte_vec_corr_ccc against every hypothesis,
+ *                       the first maximum (>) wins; format 1 is detected with corr >= threshold_format1, 1a / 1b with >. 2/2a/2b: the
+ *                       product with the conjugate reference, the 12-RE means, int16 QPSK LLRs, srslte_sequence_pucch (sequences.c:72-74,
+ *                       made on the device), srslte_uci_decode_cqi_pucch (uci.c:169-200): the int32 correlation with every RM(20, A)
+ *                       word in steps of 1 << (13 - len), the first maximum wins, returned as int16 and divided by 2000.
+ *   SR retry            an SR TTI with HARQ-ACK that is not detected is decoded again on the HARQ-ACK resource (enb_ul.c:217-224).
+ *   validity            ack_valid: corr > threshold_data_valid_format1a (1a / 1b) or > threshold_data_valid_format2 (2 / 2a / 2b), which
+ *                       also gives cqi_crc; 0 otherwise.
+ * srslte_hip_ul_ctrl_tx_put_pucch writes what srslte_ue_ul's pucch_encode writes: srslte_pucch_encode (pucch.c:741-765, encode_signal_format12
+ * :429-492, pucch_cp :380-417) plus srslte_refsignal_dmrs_pucch_gen / _put (refsignal_ul.c:558-680), the selection made with the UCI values
+ * (a positive SR selects n_pucch_sr). Only the PUCCH's REs are written. The per-(slot, symbol) tables (n_cs_cell pucch.c:954-972, the group's
+ * srslte_refsignal_r_uv_arg_1prb, the orthogonal sequences) are made on the host once per object; the cyclic shifts (pucch.c:974-1059) on the
+ * device. The time-domain signal comes from srslte_hip_ofdm_tx_sf_batch with the UL half-carrier shift. Requests of one call that write the same
+ * RE (two UEs on one PRB of one grid) leave either value there: a subframe's grid is one UE's, as srslte_ue_ul's.
+ * Grids are [nof_sf][nsym][12 nof_prb] (nsym 14 / 12), one antenna, as srslte_hip_ofdm_rx_sf_batch makes them; subframe b is TTI tti0 + b.
+ * FDD, normal / extended CP, 6-110 PRB, one receive antenna (srslte_enb_ul_t), shortened subframes (SRS).
+ * Refused with SRSLTE_ERROR_INVALID_INPUTS before anything is queued: ack_len > 2 (format 3, channel selection), cqi_len > 12 (a 13-bit
+ * report: srslte_uci_decode_cqi_pucch tests cqi_len < 13 and fails it), cqi_len and ri_len together, ri_len > 1, a request that selects no
+ * format (no HARQ-ACK, no SR TTI, no report), an n_pucch whose PRB lies outside the band in either slot, sf >= nof_sf, nof > max_pucch,
+ * and a format 2 / 2a / 2b for an RNTI outside [SRSLTE_CRNTI_START, SRSLTE_CRNTI_END) (0x000B-0xFFF2), for which get_user_sequence
+ * (pucch.c:214-236) has no scrambling sequence and the reference decodes nothing.
+ * srslte_hip_ul_ctrl_create returns NULL for a configuration srslte_pucch_cfg_isvalid rejects (pucch.c:901-909), an invalid cell or TDD.
+ * Not here: format 3, CA channel selection, TDD (n_pucch_i_tdd), several receive antennas, PRACH, PUCCH inside srslte_hip_ul_tx_*, and the
+ * single-subframe drop-in's pucch.c, which remains the reference's. */
+typedef struct srslte_hip_ul_ctrl    srslte_hip_ul_ctrl_t;
+typedef struct srslte_hip_ul_ctrl_tx srslte_hip_ul_ctrl_tx_t;
+typedef struct {
+  uint32_t nof_prb, cell_id;
+  int      cp_ext;                  /* srslte_cell_t.cp == SRSLTE_CP_EXT */
+  uint32_t delta_pucch_shift, n_rb_2, N_cs, N_pucch_1; /* srslte_pucch_cfg_t common configuration (pucch_cfg.h:45-90) */
+  int      group_hopping_en;
+  float    threshold_format1, threshold_data_valid_format1a, threshold_data_valid_format2;
+  uint32_t max_pucch;               /* requests per call */
+  int      tdd;                     /* refused */
+} srslte_hip_ul_ctrl_cfg_t;
+typedef struct {                    /* one (subframe, UE): what srslte_enb_ul_get_pucch is given */
+  uint32_t sf;                      /* 0 .. nof_sf-1 */
+  uint16_t rnti;
+  uint32_t ack_len;                 /* 0-2 HARQ-ACK bits (srslte_uci_cfg_total_ack) */
+  uint32_t ncce;                    /* n_pucch = ncce + N_pucch_1 for formats 1a / 1b */
+  int      sr_tti;                  /* srslte_uci_cfg_t.is_scheduling_request_tti */
+  uint32_t n_pucch_sr;
+  uint32_t cqi_len;                 /* 0, 1-12: periodic CQI report (srslte_cqi_size) */
+  uint32_t ri_len;                  /* 0, 1: rank indication instead of a report */
+  uint32_t n_pucch_2;
+  int      simul_cqi_ack;
+  int      shortened;               /* srslte_ul_sf_cfg_t.shortened */
+  float    noise_estimate;          /* the equaliser's noise (receive; srslte_chest_ul_estimate_pucch leaves chest_res.noise_estimate alone) */
+} srslte_hip_pucch_req_t;
+typedef struct {                    /* per request */
+  uint32_t detected;
+  float    correlation;
+  uint32_t format;                  /* srslte_pucch_format_t used last (0-5) */
+  uint32_t n_pucch;                 /* the resource used last */
+  uint8_t  sr;                      /* SR TTI: detected on n_pucch_sr; 0 otherwise */
+  uint8_t  ack[2];                  /* 1a / 1b: the hypothesis; 2a / 2b (and a report with ACK): the DMRS hypothesis */
+  uint8_t  ack_valid;
+  uint8_t  cqi[13];                 /* formats 2 / 2a / 2b: the 13 bits of the decoded word, the report in the first cqi_len */
+  uint8_t  cqi_crc;
+  uint8_t  ri;
+  uint8_t  reserved;
+} srslte_hip_pucch_res_t;
+typedef struct {                    /* transmit: the request and the UCI values (srslte_uci_value_t) */
+  srslte_hip_pucch_req_t req;       /* noise_estimate unused */
+  uint8_t                ack[2], sr, ri;
+  uint8_t                cqi[12];   /* the report's bits, cqi_len of them */
+} srslte_hip_pucch_tx_t;
+srslte_hip_ul_ctrl_t* srslte_hip_ul_ctrl_create(const srslte_hip_ul_ctrl_cfg_t* cfg);
+void                  srslte_hip_ul_ctrl_destroy(srslte_hip_ul_ctrl_t* q);
+/* d_grid [nof_sf][nsym][12 nof_prb]; d_res [nof] may be device-visible pinned host memory */
+int srslte_hip_ul_ctrl_pucch_batch(srslte_hip_ul_ctrl_t* q, const void* d_grid, uint32_t tti0, uint32_t nof_sf, const srslte_hip_pucch_req_t* reqs,
+                                   uint32_t nof, srslte_hip_pucch_res_t* d_res, void* stream);
+/* device buffers of the last call: 0 equalised symbols [max_pucch][120] cf32 of the attempt used last (q->z of pucch.c, nof_re of them),
+ * 1 descrambled LLRs [max_pucch][20] int16 (formats 2 / 2a / 2b) */
+const void* srslte_hip_ul_ctrl_debug_buffer(const srslte_hip_ul_ctrl_t* q, int which);
+/* srslte_hip_ul_rx_batch_grants plus the PUCCHs of reqs, decoded from the pipeline's own grid (one SC-FDMA demodulation for both, as
+ * srslte_enb_ul_fft + get_pusch + get_pucch). ctrl must be made for the receiver's cell; nof_grants may be 0. PUSCH outputs are those of
+ * srslte_hip_ul_rx_batch_grants. */
+int srslte_hip_ul_rx_batch_grants_pucch(srslte_hip_ul_rx_t* q, const void* d_iq, uint32_t tti0, uint32_t nof_sf, const srslte_hip_ul_grant_t* grants,
+                                        uint32_t nof_grants, uint8_t* d_tb, uint32_t tb_stride, uint8_t* d_tb_ok, srslte_hip_ul_ctrl_t* ctrl,
+                                        const srslte_hip_pucch_req_t* reqs, uint32_t nof_pucch, srslte_hip_pucch_res_t* d_res, void* stream);
+srslte_hip_ul_ctrl_tx_t* srslte_hip_ul_ctrl_tx_create(const srslte_hip_ul_ctrl_cfg_t* cfg);
+void                     srslte_hip_ul_ctrl_tx_destroy(srslte_hip_ul_ctrl_tx_t* q);
+/* writes the PUCCHs and their DMRS of tx[0 .. nof) into d_grid [nof_sf][nsym][12 nof_prb] */
+int srslte_hip_ul_ctrl_tx_put_pucch(srslte_hip_ul_ctrl_tx_t* q, uint32_t tti0, uint32_t nof_sf, const srslte_hip_pucch_tx_t* tx, uint32_t nof, void* d_grid,
+                                    void* stream);
+/* host helpers (no device needed), for a configuration given as srslte_hip_ul_ctrl_cfg_t (max_pucch not looked at):
+ * srslte_pucch_n_cs_cell into n_cs_cell [20][7]; the resource selection of a request (uci: NULL = the receiver's zero value, else the
+ * transmitter's values) into res = {format, n_pucch, n_prb slot 0, n_prb slot 1}; the DMRS of srslte_refsignal_dmrs_pucch_gen for (format,
+ * n_pucch, TTI, 2a / 2b bits) into r [2][N_rs][12] cf32, returning 12 N_rs per slot. < 0: invalid input. */
+int srslte_hip_pucch_n_cs_cell(const srslte_hip_ul_ctrl_cfg_t* cfg, uint32_t* n_cs_cell);
+int srslte_hip_pucch_resource(const srslte_hip_ul_ctrl_cfg_t* cfg, const srslte_hip_pucch_tx_t* uci, const srslte_hip_pucch_req_t* req, uint32_t* res);
+int srslte_hip_pucch_dmrs(const srslte_hip_ul_ctrl_cfg_t* cfg, uint32_t format, uint32_t n_pucch, uint32_t tti, const uint8_t* drs_bits, void* r);
+
 #ifdef __cplusplus
 }
 #endif

@@ -137,6 +137,7 @@ def lib():
         L.srslte_hip_dl_rx_debug_buffer.argtypes = [vp, C.c_int]
         L.srslte_hip_dl_rx_keep_symbols.argtypes = [vp, C.c_int]
         _bind_dl_ctrl(L)
+        _bind_ul_ctrl(L)
         _lib = L
     return _lib
 
@@ -1314,3 +1315,190 @@ class DlCtrlTx:
         if self.h:
             lib().srslte_hip_dl_ctrl_tx_destroy(self.h)
             self.h = None
+
+
+# ---------------------------------------------------------------- UL control: PUCCH (phy_hip.h "UL control")
+PUCCH_FORMAT_1, PUCCH_FORMAT_1A, PUCCH_FORMAT_1B, PUCCH_FORMAT_2, PUCCH_FORMAT_2A, PUCCH_FORMAT_2B = range(6)
+
+
+class UlCtrlCfg(C.Structure):
+    """srslte_hip_ul_ctrl_cfg_t: the cell, the common PUCCH configuration of srslte_pucch_cfg_t and the requests per call."""
+    _fields_ = [("nof_prb", C.c_uint32), ("cell_id", C.c_uint32), ("cp_ext", C.c_int), ("delta_pucch_shift", C.c_uint32), ("n_rb_2", C.c_uint32),
+                ("N_cs", C.c_uint32), ("N_pucch_1", C.c_uint32), ("group_hopping_en", C.c_int), ("threshold_format1", C.c_float),
+                ("threshold_data_valid_format1a", C.c_float), ("threshold_data_valid_format2", C.c_float), ("max_pucch", C.c_uint32), ("tdd", C.c_int)]
+
+
+class PucchReq(C.Structure):
+    """srslte_hip_pucch_req_t: one (subframe, UE) as srslte_enb_ul_get_pucch is given it."""
+    _fields_ = [("sf", C.c_uint32), ("rnti", C.c_uint16), ("ack_len", C.c_uint32), ("ncce", C.c_uint32), ("sr_tti", C.c_int), ("n_pucch_sr", C.c_uint32),
+                ("cqi_len", C.c_uint32), ("ri_len", C.c_uint32), ("n_pucch_2", C.c_uint32), ("simul_cqi_ack", C.c_int), ("shortened", C.c_int),
+                ("noise_estimate", C.c_float)]
+
+    @classmethod
+    def make(cls, sf, rnti, ack_len=0, ncce=0, sr_tti=False, n_pucch_sr=0, cqi_len=0, ri_len=0, n_pucch_2=0, simul_cqi_ack=False, shortened=False,
+             noise_estimate=0.0):
+        return cls(sf, rnti, ack_len, ncce, 1 if sr_tti else 0, n_pucch_sr, cqi_len, ri_len, n_pucch_2, 1 if simul_cqi_ack else 0, 1 if shortened else 0,
+                   noise_estimate)
+
+
+class PucchRes(C.Structure):
+    """srslte_hip_pucch_res_t."""
+    _fields_ = [("detected", C.c_uint32), ("correlation", C.c_float), ("format", C.c_uint32), ("n_pucch", C.c_uint32), ("sr", C.c_uint8),
+                ("ack", C.c_uint8 * 2), ("ack_valid", C.c_uint8), ("cqi", C.c_uint8 * 13), ("cqi_crc", C.c_uint8), ("ri", C.c_uint8), ("reserved", C.c_uint8)]
+
+
+class PucchTx(C.Structure):
+    """srslte_hip_pucch_tx_t: a request and its UCI values."""
+    _fields_ = [("req", PucchReq), ("ack", C.c_uint8 * 2), ("sr", C.c_uint8), ("ri", C.c_uint8), ("cqi", C.c_uint8 * 12)]
+
+    @classmethod
+    def make(cls, req, ack=(0, 0), sr=0, ri=0, cqi=()):
+        t = cls()
+        t.req = req
+        t.ack[0], t.ack[1], t.sr, t.ri = ack[0], ack[1], sr, ri
+        for i, b in enumerate(cqi):
+            t.cqi[i] = b
+        return t
+
+
+def _bind_ul_ctrl(L):
+    vp = C.c_void_p
+    L.srslte_hip_ul_ctrl_create.restype = vp
+    L.srslte_hip_ul_ctrl_create.argtypes = [C.POINTER(UlCtrlCfg)]
+    L.srslte_hip_ul_ctrl_destroy.argtypes = [vp]
+    L.srslte_hip_ul_ctrl_pucch_batch.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp]
+    L.srslte_hip_ul_ctrl_debug_buffer.restype = vp
+    L.srslte_hip_ul_ctrl_debug_buffer.argtypes = [vp, C.c_int]
+    L.srslte_hip_ul_ctrl_tx_create.restype = vp
+    L.srslte_hip_ul_ctrl_tx_create.argtypes = [C.POINTER(UlCtrlCfg)]
+    L.srslte_hip_ul_ctrl_tx_destroy.argtypes = [vp]
+    L.srslte_hip_ul_ctrl_tx_put_pucch.argtypes = [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp]
+    L.srslte_hip_ul_rx_batch_grants_pucch.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, C.c_uint32, vp, vp]
+    L.srslte_hip_pucch_n_cs_cell.argtypes = [C.POINTER(UlCtrlCfg), vp]
+    L.srslte_hip_pucch_resource.argtypes = [C.POINTER(UlCtrlCfg), vp, C.POINTER(PucchReq), vp]
+    L.srslte_hip_pucch_dmrs.argtypes = [C.POINTER(UlCtrlCfg), C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
+    return L
+
+
+def ul_ctrl_cfg(nof_prb, cell_id, cp_ext=False, delta_pucch_shift=1, n_rb_2=2, N_cs=0, N_pucch_1=0, group_hopping_en=False, threshold_format1=0.5,
+                threshold_data_valid_format1a=0.5, threshold_data_valid_format2=0.5, max_pucch=1, tdd=False):
+    return UlCtrlCfg(nof_prb, cell_id, 1 if cp_ext else 0, delta_pucch_shift, n_rb_2, N_cs, N_pucch_1, 1 if group_hopping_en else 0, threshold_format1,
+                     threshold_data_valid_format1a, threshold_data_valid_format2, max_pucch, 1 if tdd else 0)
+
+
+def pucch_n_cs_cell(cfg):
+    """srslte_pucch_n_cs_cell -> [20][7] uint32 (host; no GPU)."""
+    out = np.zeros((20, 7), np.uint32)
+    _check(_bind_ul_ctrl(lib()).srslte_hip_pucch_n_cs_cell(C.byref(cfg), out.ctypes.data), "pucch_n_cs_cell")
+    return out
+
+
+def pucch_resource(cfg, req, uci=None):
+    """srslte_ue_ul_pucch_resource_selection -> (format, n_pucch, n_prb slot 0, n_prb slot 1), or None where no format fits (host).
+    uci: None for the receiver's zero value, else a PucchTx whose UCI values count."""
+    out = np.zeros(4, np.uint32)
+    rc = _bind_ul_ctrl(lib()).srslte_hip_pucch_resource(C.byref(cfg), C.byref(uci) if uci is not None else None, C.byref(req), out.ctypes.data)
+    return None if rc != SRSLTE_SUCCESS else tuple(int(x) for x in out)
+
+
+def pucch_dmrs(cfg, fmt, n_pucch, tti, drs_bits=(0, 0)):
+    """srslte_refsignal_dmrs_pucch_gen of one configuration -> [2][N_rs][12] complex64 (host)."""
+    r = np.zeros(2 * 3 * 12, np.complex64)
+    b = np.array(drs_bits, np.uint8)
+    n = _bind_ul_ctrl(lib()).srslte_hip_pucch_dmrs(C.byref(cfg), fmt, n_pucch, tti, b.ctypes.data, r.ctypes.data)
+    if n < 0:
+        raise ValueError("srslte_hip_pucch_dmrs: %d" % n)
+    return r[:2 * n].reshape(2, n // 12, 12)
+
+
+class UlCtrl:
+    """Batched PUCCH receive: srslte_enb_ul_get_pucch for a list of (subframe, UE) requests."""
+
+    def __init__(self, nof_prb, cell_id, max_pucch=1, **kw):
+        L = _bind_ul_ctrl(lib())
+        self.cfg = ul_ctrl_cfg(nof_prb, cell_id, max_pucch=max_pucch, **kw)
+        self.h = L.srslte_hip_ul_ctrl_create(C.byref(self.cfg))
+        if not self.h:
+            raise RuntimeError("srslte_hip_ul_ctrl_create failed")
+        self.grid_len = (12 if self.cfg.cp_ext else 14) * 12 * nof_prb
+        self.max_pucch = max_pucch
+
+    def run_device(self, d_grid, tti0, nof_sf, reqs, d_res, stream=None):
+        arr = (PucchReq * max(1, len(reqs)))(*reqs)
+        return lib().srslte_hip_ul_ctrl_pucch_batch(self.h, d_grid, tti0, nof_sf, arr, len(reqs), d_res, stream)
+
+    def batch(self, grid, tti0, reqs):
+        """grid [nof_sf][grid_len] complex64 -> (rc, [PucchRes] or None)."""
+        g = np.ascontiguousarray(grid, np.complex64).reshape(-1, self.grid_len)
+        dg, dr = DevBuf.from_host(g), DevBuf(C.sizeof(PucchRes) * max(1, len(reqs)))
+        rc = self.run_device(dg.ptr, tti0, g.shape[0], reqs, dr.ptr)
+        if rc != SRSLTE_SUCCESS:
+            return rc, None
+        sync()
+        out = (PucchRes * max(1, len(reqs)))()
+        _check(lib().srslte_hip_memcpy_d2h(C.addressof(out), dr.ptr, C.sizeof(out)), "memcpy_d2h")
+        return rc, list(out)[:len(reqs)]
+
+    def debug(self, which, nof):
+        """0: equalised symbols [nof][120] complex64; 1: descrambled LLRs [nof][20] int16 (last call)."""
+        dt, n = (np.complex64, 120) if which == 0 else (np.int16, 20)
+        out = np.empty(nof * n, dt)
+        _check(lib().srslte_hip_memcpy_d2h(out.ctypes.data, lib().srslte_hip_ul_ctrl_debug_buffer(self.h, which), out.nbytes), "memcpy_d2h")
+        return out.reshape(nof, n)
+
+    def free(self):
+        if self.h:
+            lib().srslte_hip_ul_ctrl_destroy(self.h)
+            self.h = None
+
+
+class UlCtrlTx:
+    """Batched PUCCH transmit: srslte_pucch_encode + the PUCCH DMRS into UE grids."""
+
+    def __init__(self, nof_prb, cell_id, max_pucch=1, **kw):
+        L = _bind_ul_ctrl(lib())
+        self.cfg = ul_ctrl_cfg(nof_prb, cell_id, max_pucch=max_pucch, **kw)
+        self.h = L.srslte_hip_ul_ctrl_tx_create(C.byref(self.cfg))
+        if not self.h:
+            raise RuntimeError("srslte_hip_ul_ctrl_tx_create failed")
+        self.grid_len = (12 if self.cfg.cp_ext else 14) * 12 * nof_prb
+
+    def put_device(self, d_grid, tti0, nof_sf, txs, stream=None):
+        arr = (PucchTx * max(1, len(txs)))(*txs)
+        return lib().srslte_hip_ul_ctrl_tx_put_pucch(self.h, tti0, nof_sf, arr, len(txs), d_grid, stream)
+
+    def put(self, grid, tti0, txs):
+        """grid [nof_sf][grid_len] complex64 (host) -> (rc, the grids after the call)."""
+        g = np.ascontiguousarray(grid, np.complex64).reshape(-1, self.grid_len)
+        d = DevBuf.from_host(g)
+        rc = self.put_device(d.ptr, tti0, g.shape[0], txs)
+        sync()
+        return rc, d.to_host(np.complex64).reshape(g.shape)
+
+    def free(self):
+        if self.h:
+            lib().srslte_hip_ul_ctrl_tx_destroy(self.h)
+            self.h = None
+
+
+def _ul_rx_decode_grants_pucch(self, iq, tti0, grants, ctrl, reqs):
+    """srslte_hip_ul_rx_batch_grants_pucch: (rc, tb, tb_ok, [PucchRes]); grants may be empty."""
+    x = np.ascontiguousarray(iq, np.complex64).reshape(-1, self.sf_len)
+    din = DevBuf.from_host(x)
+    garr = (UlGrant * max(1, len(grants)))(*grants)
+    rarr = (PucchReq * max(1, len(reqs)))(*reqs)
+    dres = DevBuf(C.sizeof(PucchRes) * max(1, len(reqs)))
+    L = _bind_ul_ctrl(lib())
+    rc = L.srslte_hip_ul_rx_batch_grants_pucch(self.h, din.ptr, tti0, x.shape[0], garr, len(grants), self.d_tb.ptr, self.tb_stride, self.d_ok.ptr, ctrl.h,
+                                               rarr, len(reqs), dres.ptr, None)
+    if rc != SRSLTE_SUCCESS:
+        return rc, None, None, None
+    sync()
+    self.last_nof_grants = len(grants)
+    out = (PucchRes * max(1, len(reqs)))()
+    _check(lib().srslte_hip_memcpy_d2h(C.addressof(out), dres.ptr, C.sizeof(out)), "memcpy_d2h")
+    tb = self.d_tb.to_host(np.uint8).reshape(self.rows, self.tb_stride)[:len(grants)]
+    return rc, tb, self.d_ok.to_host(np.uint8)[:len(grants)], list(out)[:len(reqs)]
+
+
+UlRx.decode_grants_pucch = _ul_rx_decode_grants_pucch

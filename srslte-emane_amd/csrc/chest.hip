@@ -1097,6 +1097,12 @@ __global__ __launch_bounds__(CH_THREADS) void chest_ul_kernel(const cf32* __rest
 
 } // namespace
 
+// srslte_refsignal_r_uv_arg_1prb (refsignal_ul.c:143-147) for the PUCCH (pucch.hip): arg[i] = phi(i) pi / 4 of group u, in double, kept as float
+void ul_r_uv_arg_1prb(uint32_t u, float* arg)
+{
+  for (int i = 0; i < 12; i++) arg[i] = (float)((2 * (PHI_12[u][i] - '0') - 3) * M_PI / 4);
+}
+
 struct srslte_hip_chest_ul {
   uint32_t cell_id, nof_prb, nsl; // nsl: symbols per slot (7, or 6 with the extended CP)
   srslte_hip_dmrs_pusch_cfg_t cfg;

@@ -94,3 +94,6 @@ int          bcast_tx_launch(const BcastTables* t, uint32_t tti0, uint32_t nof_s
 // pdcch_tx.hip / pdcch.hip: an object's broadcast tables
 const BcastTables* dl_ctrl_tx_bcast(const srslte_hip_dl_ctrl_tx_t* q);
 const BcastTables* dl_ctrl_bcast(const srslte_hip_dl_ctrl_t* q);
+// pucch.hip: the checks of srslte_hip_ul_ctrl_pucch_batch alone (nothing is queued), and whether an object was made for a receiver's cell
+int  ul_ctrl_check(const srslte_hip_ul_ctrl_t* q, uint32_t nof_sf, const srslte_hip_pucch_req_t* reqs, uint32_t nof);
+bool ul_ctrl_same_cell(const srslte_hip_ul_ctrl_t* q, uint32_t nof_prb, uint32_t cell_id, int cp_ext);

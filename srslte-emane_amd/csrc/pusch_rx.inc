@@ -662,8 +662,16 @@ static int ul_rx_grants_init(srslte_hip_ul_rx_t* q, uint32_t V, uint32_t max_re)
 // their geometry from per-PUSCH descriptors, the transform de-precoding runs once per distinct L_prb (PUSCHs of one size sit next to each other
 // in the symbol buffers), and from the LLRs on it is the downlink's grants machinery with one slot per PUSCH: slot p = grants[p] keeps soft
 // buffers, CRC flags and bytes between calls (HARQ as srslte_hip_ul_rx_batch_harq). HARQ-ACK, rank indication and CQI report per PUSCH.
-extern "C" int srslte_hip_ul_rx_batch_grants(srslte_hip_ul_rx_t* q, const void* d_iq, uint32_t tti0, uint32_t nof_sf, const srslte_hip_ul_grant_t* grants,
-                                             uint32_t nof_grants, uint8_t* d_tb, uint32_t tb_stride, uint8_t* d_tb_ok, void* stream)
+// pucch: the PUCCHs of srslte_hip_ul_rx_batch_grants_pucch, decoded from the grid right after the OFDM demodulation (nullptr: none)
+struct UlPucchCall {
+  srslte_hip_ul_ctrl_t*         ctrl;
+  const srslte_hip_pucch_req_t* reqs;
+  uint32_t                      nof;
+  srslte_hip_pucch_res_t*       d_res;
+};
+
+static int ul_rx_grants(srslte_hip_ul_rx_t* q, const void* d_iq, uint32_t tti0, uint32_t nof_sf, const srslte_hip_ul_grant_t* grants, uint32_t nof_grants,
+                        uint8_t* d_tb, uint32_t tb_stride, uint8_t* d_tb_ok, const UlPucchCall* pucch, void* stream)
 {
   if (!q || !d_iq || !grants || !d_tb || !d_tb_ok || nof_sf > q->cfg.max_batch || tb_stride < q->cfg.tbs / 8 + 6) return SRSLTE_ERROR_INVALID_INPUTS;
   const uint32_t V = q->cfg.max_grants ? q->cfg.max_grants : q->cfg.max_batch, P = q->cfg.nof_prb;
@@ -760,6 +768,7 @@ extern "C" int srslte_hip_ul_rx_batch_grants(srslte_hip_ul_rx_t* q, const void* 
   if (d_cof && no_tb) HIP_TRY(hipMemsetAsync(d_tb_ok, 0, nof_grants, st)); // rows without a transport block get no verdict from a decoder
   int r = srslte_hip_ofdm_rx_sf_batch(q->ofdm, d_iq, q->d_grid, (int)nof_sf, stream);
   if (r) return r;
+  if (pucch && (r = srslte_hip_ul_ctrl_pucch_batch(pucch->ctrl, q->d_grid, tti0, nof_sf, pucch->reqs, pucch->nof, pucch->d_res, stream))) return r;
   const int n16 = (int)((g->desc_bytes + 15) / 16);
   hipLaunchKernelGGL(desc_copy_kernel, dim3(ceil_div(n16, 256)), dim3(256), 0, st, (const uint4*)h_pin, (uint4*)g->d_desc, n16);
   LAUNCH_CHECK();
@@ -799,4 +808,28 @@ extern "C" int srslte_hip_ul_rx_batch_grants(srslte_hip_ul_rx_t* q, const void* 
   }
   LAUNCH_CHECK();
   return grants_back_end(g, bd, d.sf, d.cb, d.map, tti0, q->cfg.max_iterations, nof_grants, nof_grants, V, d_tb, tb_stride, d_tb_ok, st, d_cof);
+}
+
+extern "C" int srslte_hip_ul_rx_batch_grants(srslte_hip_ul_rx_t* q, const void* d_iq, uint32_t tti0, uint32_t nof_sf, const srslte_hip_ul_grant_t* grants,
+                                             uint32_t nof_grants, uint8_t* d_tb, uint32_t tb_stride, uint8_t* d_tb_ok, void* stream)
+{
+  return ul_rx_grants(q, d_iq, tti0, nof_sf, grants, nof_grants, d_tb, tb_stride, d_tb_ok, nullptr, stream);
+}
+
+// srslte_enb_ul_fft + get_pusch per grant + get_pucch per request: the PUCCH requests are checked before anything is queued; without grants
+// the call is the OFDM demodulation and the PUCCH batch alone
+extern "C" int srslte_hip_ul_rx_batch_grants_pucch(srslte_hip_ul_rx_t* q, const void* d_iq, uint32_t tti0, uint32_t nof_sf, const srslte_hip_ul_grant_t* grants,
+                                                   uint32_t nof_grants, uint8_t* d_tb, uint32_t tb_stride, uint8_t* d_tb_ok, srslte_hip_ul_ctrl_t* ctrl,
+                                                   const srslte_hip_pucch_req_t* reqs, uint32_t nof_pucch, srslte_hip_pucch_res_t* d_res, void* stream)
+{
+  if (!q || !d_iq || nof_sf > q->cfg.max_batch || !ul_ctrl_same_cell(ctrl, q->cfg.nof_prb, q->cfg.cell_id, q->cfg.cp_ext) || (nof_pucch && !d_res))
+    return SRSLTE_ERROR_INVALID_INPUTS;
+  if (int r = ul_ctrl_check(ctrl, nof_sf, reqs, nof_pucch)) return r;
+  if (nof_grants == 0) {
+    if (nof_sf == 0 || nof_pucch == 0) return SRSLTE_SUCCESS;
+    if (int r = srslte_hip_ofdm_rx_sf_batch(q->ofdm, d_iq, q->d_grid, (int)nof_sf, stream)) return r;
+    return srslte_hip_ul_ctrl_pucch_batch(ctrl, q->d_grid, tti0, nof_sf, reqs, nof_pucch, d_res, stream);
+  }
+  const UlPucchCall pc = {ctrl, reqs, nof_pucch, d_res};
+  return ul_rx_grants(q, d_iq, tti0, nof_sf, grants, nof_grants, d_tb, tb_stride, d_tb_ok, nof_pucch ? &pc : nullptr, stream);
 }
