@@ -788,7 +788,7 @@ int srslte_hip_pbch_mib_pack(uint32_t nof_prb, int phich_ext, int phich_resource
  * and a format 2 / 2a / 2b for an RNTI outside [SRSLTE_CRNTI_START, SRSLTE_CRNTI_END) (0x000B-0xFFF2), for which get_user_sequence
  * (pucch.c:214-236) has no scrambling sequence and the reference decodes nothing.
  * srslte_hip_ul_ctrl_create returns NULL for a configuration srslte_pucch_cfg_isvalid rejects (pucch.c:901-909), an invalid cell or TDD.
- * Not here: format 3, CA channel selection, TDD (n_pucch_i_tdd), several receive antennas, PRACH, PUCCH inside srslte_hip_ul_tx_*, and the
+ * Not here: format 3, CA channel selection, TDD (n_pucch_i_tdd), several receive antennas, PUCCH inside srslte_hip_ul_tx_*, and the
  * single-subframe drop-in's pucch.c, which remains the reference's. */
 typedef struct srslte_hip_ul_ctrl    srslte_hip_ul_ctrl_t;
 typedef struct srslte_hip_ul_ctrl_tx srslte_hip_ul_ctrl_tx_t;
@@ -859,6 +859,74 @@ int srslte_hip_ul_ctrl_tx_put_pucch(srslte_hip_ul_ctrl_tx_t* q, uint32_t tti0, u
 int srslte_hip_pucch_n_cs_cell(const srslte_hip_ul_ctrl_cfg_t* cfg, uint32_t* n_cs_cell);
 int srslte_hip_pucch_resource(const srslte_hip_ul_ctrl_cfg_t* cfg, const srslte_hip_pucch_tx_t* uci, const srslte_hip_pucch_req_t* req, uint32_t* res);
 int srslte_hip_pucch_dmrs(const srslte_hip_ul_ctrl_cfg_t* cfg, uint32_t format, uint32_t n_pucch, uint32_t tti, const uint8_t* drs_bits, void* r);
+
+/* ------------------------------------------------------------------ UL control: PRACH preamble formats 0-3, FDD (UE generate, eNB detect)
+ * The object holds what srslte_prach_set_cell_ / srslte_prach_gen_seqs build (lib/src/phy/phch/prach.c:224-322, :394-508), made on the host
+ * once: the 64 sequences of the unrestricted set, shifted by v N_cs from roots u taken in the order of 36.211 Table 5.7.2-4 starting at
+ * root_seq_idx, N_zc = 839, N_cs (Table 5.7.2-2), N_cp / N_seq (Table 5.7.1-1 scaled by N_ifft_ul / 2048), N_ifft_prach = 12 N_ifft_ul
+ * (N_ifft_ul = srslte_symbol_sz(nof_prb)) and the DFT of every sequence as srslte_dft makes it (forward, 1/sqrt(839), not mirrored).
+ * srslte_hip_prach_gen_batch writes what srslte_prach_gen writes (prach.c:510-549) for each entry: the sequence's DFT in the bins
+ * [begin, begin + 839) of an N_ifft_prach-point inverse DFT, begin = 7 + 12 k_0 + 6, k_0 = 12 freq_offset - 6 N_rb_ul + N_ifft_ul / 2 with
+ * N_rb_ul = srslte_nof_prb(N_ifft_ul); the transform mirrored (bin m is frequency m - N_ifft_prach / 2) and scaled by 1/sqrt(N_ifft_prach);
+ * then the last N_cp samples and N_seq samples taken modulo N_ifft_prach (formats 2 and 3 repeat the sequence).
+ * srslte_hip_prach_detect_batch is srslte_prach_detect_offset (prach.c:564-666) for each occasion: the bins [begin, begin + 839) of the
+ * mirrored, unnormalised forward DFT of N_ifft_prach samples from occ.sample on; for each root the product with conj(DFT of the root
+ * sequence), the unnormalised inverse DFT of 839 points, |.|^2 and its mean; window j of n_wins = 839 / N_cs (1 for N_cs = 0) starts at
+ * (839 - j N_cs) % 839 and spans N_cs samples (839 for N_cs = 0), its first maximum (>) is the peak; a peak > detect_factor mean is reported
+ * with index root n_wins + j, t_offset = c peak_offset / (1250 839) (c = 1.8, 1.9 above 30, 1.91 above 250; float) and peak / mean, in the
+ * order (root, window). Rows of max_det = nof_roots n_wins per occasion; d_nof_det[o] tells how many of row o are written, the rest of the
+ * row is left as it was. max_det may exceed 64 and indices >= 64 are reported as the reference reports them (zero_corr_zone 2: 2 roots x 55).
+ * The long transforms are split as N_ifft_prach = 12 N_ifft_ul and only the 839 bins of the PRACH band are computed; the 839-point
+ * correlations are direct sums with the twiddles in LDS. Both calls queue their work on the caller's stream with no host synchronisation
+ * (descriptors through pinned buffers): gen_batch one launch, detect_batch three. Calls on one object run one after another on one stream.
+ * Refused with SRSLTE_ERROR_INVALID_INPUTS before anything is queued: n greater than max_preambles / max_occasions, seq_index >= 64,
+ * 6 + freq_offset > nof_prb, an occasion whose N_ifft_prach samples run past sig_len.
+ * srslte_hip_prach_create returns NULL for a high-speed (restricted) set - the reference generates restricted-set sequences but numbers its
+ * detections as windows of an unrestricted set, so there is nothing consistent to match -, TDD, and what srslte_prach_set_cell_ refuses
+ * (config_idx >= 64, root_seq_idx >= 838, zero_corr_zone >= 16) or a cell outside 6-110 PRB.
+ * Not here: high-speed sets, TDD and preamble format 4 (config_idx / 16 is 0-3 for FDD), several receive antennas (srsenb detects on antenna
+ * 0), the deadzone (0 in the reference), and the single-call drop-in's prach.c, which remains the reference's over srslte_dft_*. */
+typedef struct srslte_hip_prach srslte_hip_prach_t;
+typedef struct {
+  uint32_t nof_prb, config_idx, root_seq_idx, zero_corr_zone;
+  int      hs_flag;                 /* refused */
+  int      tdd;                     /* refused */
+  float    detect_factor;           /* 0: the reference's PRACH_DETECT_FACTOR 18 (srsenb sets 60, srslte_prach_set_detect_factor) */
+  uint32_t max_occasions;           /* srslte_hip_prach_detect_batch: occasions per call */
+  uint32_t max_preambles;           /* srslte_hip_prach_gen_batch: preambles per call */
+} srslte_hip_prach_cfg_t;
+typedef struct {
+  uint32_t N_zc, N_cs, N_cp, N_seq, N_ifft_prach, N_ifft_ul;
+  uint32_t format;                  /* config_idx / 16 */
+  uint32_t nof_roots, n_wins, max_det;
+  uint32_t nof_sf;                  /* ceil(T_tot 1000): subframes a preamble spans (what srsenb buffers) */
+  uint32_t root_seqs_idx[64];       /* first sequence of each root */
+} srslte_hip_prach_info_t;
+typedef struct {
+  uint32_t seq_index, freq_offset;
+} srslte_hip_prach_tx_t;
+typedef struct {
+  uint64_t sample;                  /* index into d_signal of the first sample after the CP (prach_worker.cc passes &samples[N_cp]) */
+  uint32_t freq_offset;
+  uint32_t reserved;
+} srslte_hip_prach_occasion_t;
+srslte_hip_prach_t* srslte_hip_prach_create(const srslte_hip_prach_cfg_t* cfg);
+void                srslte_hip_prach_destroy(srslte_hip_prach_t* q);
+int                 srslte_hip_prach_info(const srslte_hip_prach_t* q, srslte_hip_prach_info_t* info);
+/* d_out [n][N_cp + N_seq] cf32 */
+int srslte_hip_prach_gen_batch(srslte_hip_prach_t* q, const srslte_hip_prach_tx_t* list, uint32_t n, void* d_out, void* stream);
+/* d_signal cf32 [sig_len] (e.g. the [nof_sf][15 N] buffer given to srslte_hip_ul_rx_batch_grants); d_nof_det [n]; d_indices, d_t_offsets,
+ * d_peak_to_avg [n][max_det] (the last two may be NULL) */
+int srslte_hip_prach_detect_batch(srslte_hip_prach_t* q, const void* d_signal, size_t sig_len, const srslte_hip_prach_occasion_t* occ, uint32_t n,
+                                  uint32_t* d_nof_det, uint32_t* d_indices, float* d_t_offsets, float* d_peak_to_avg, void* stream);
+/* host helpers (no device needed): the info of a configuration (< 0: create would refuse it); the checks of gen_batch / detect_batch for an
+ * object of that configuration alone (nothing is queued); srslte_prach_tti_opportunity_config_fdd (prach.c:82-104); the preamble format
+ * of config_idx (srslte_prach_get_preamble_format, < 0 for config_idx >= 64) */
+int srslte_hip_prach_cfg_info(const srslte_hip_prach_cfg_t* cfg, srslte_hip_prach_info_t* info);
+int srslte_hip_prach_gen_check(const srslte_hip_prach_cfg_t* cfg, const srslte_hip_prach_tx_t* list, uint32_t n);
+int srslte_hip_prach_detect_check(const srslte_hip_prach_cfg_t* cfg, size_t sig_len, const srslte_hip_prach_occasion_t* occ, uint32_t n);
+int srslte_hip_prach_tti_opportunity_fdd(uint32_t config_idx, uint32_t tti, int allowed_subframe);
+int srslte_hip_prach_preamble_format(uint32_t config_idx);
 
 #ifdef __cplusplus
 }

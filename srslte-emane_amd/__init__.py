@@ -138,6 +138,7 @@ def lib():
         L.srslte_hip_dl_rx_keep_symbols.argtypes = [vp, C.c_int]
         _bind_dl_ctrl(L)
         _bind_ul_ctrl(L)
+        _bind_prach(L)
         _lib = L
     return _lib
 
@@ -1502,3 +1503,120 @@ def _ul_rx_decode_grants_pucch(self, iq, tti0, grants, ctrl, reqs):
 
 
 UlRx.decode_grants_pucch = _ul_rx_decode_grants_pucch
+
+
+# ---------------------------------------------------------------- UL control: PRACH (phy_hip.h "UL control: PRACH")
+class PrachCfg(C.Structure):
+    """srslte_hip_prach_cfg_t: the cell's PRACH configuration (SIB2), the detection factor and the entries per call."""
+    _fields_ = [("nof_prb", C.c_uint32), ("config_idx", C.c_uint32), ("root_seq_idx", C.c_uint32), ("zero_corr_zone", C.c_uint32), ("hs_flag", C.c_int),
+                ("tdd", C.c_int), ("detect_factor", C.c_float), ("max_occasions", C.c_uint32), ("max_preambles", C.c_uint32)]
+
+
+class PrachInfo(C.Structure):
+    """srslte_hip_prach_info_t."""
+    _fields_ = [("N_zc", C.c_uint32), ("N_cs", C.c_uint32), ("N_cp", C.c_uint32), ("N_seq", C.c_uint32), ("N_ifft_prach", C.c_uint32),
+                ("N_ifft_ul", C.c_uint32), ("format", C.c_uint32), ("nof_roots", C.c_uint32), ("n_wins", C.c_uint32), ("max_det", C.c_uint32),
+                ("nof_sf", C.c_uint32), ("root_seqs_idx", C.c_uint32 * 64)]
+
+
+class PrachTx(C.Structure):
+    """srslte_hip_prach_tx_t: one preamble to generate."""
+    _fields_ = [("seq_index", C.c_uint32), ("freq_offset", C.c_uint32)]
+
+
+class PrachOccasion(C.Structure):
+    """srslte_hip_prach_occasion_t: the first sample after the CP in the signal, and the PRACH's PRB offset."""
+    _fields_ = [("sample", C.c_uint64), ("freq_offset", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def _bind_prach(L):
+    vp = C.c_void_p
+    L.srslte_hip_prach_create.restype = vp
+    L.srslte_hip_prach_create.argtypes = [C.POINTER(PrachCfg)]
+    L.srslte_hip_prach_destroy.argtypes = [vp]
+    L.srslte_hip_prach_info.argtypes = [vp, C.POINTER(PrachInfo)]
+    L.srslte_hip_prach_gen_batch.argtypes = [vp, vp, C.c_uint32, vp, vp]
+    L.srslte_hip_prach_detect_batch.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp, vp, vp, vp, vp]
+    L.srslte_hip_prach_cfg_info.argtypes = [C.POINTER(PrachCfg), C.POINTER(PrachInfo)]
+    L.srslte_hip_prach_gen_check.argtypes = [C.POINTER(PrachCfg), vp, C.c_uint32]
+    L.srslte_hip_prach_detect_check.argtypes = [C.POINTER(PrachCfg), C.c_size_t, vp, C.c_uint32]
+    L.srslte_hip_prach_tti_opportunity_fdd.argtypes = [C.c_uint32, C.c_uint32, C.c_int]
+    L.srslte_hip_prach_preamble_format.argtypes = [C.c_uint32]
+    return L
+
+
+def prach_cfg(nof_prb, config_idx, root_seq_idx=0, zero_corr_zone=1, hs_flag=False, tdd=False, detect_factor=0.0, max_occasions=1, max_preambles=1):
+    return PrachCfg(nof_prb, config_idx, root_seq_idx, zero_corr_zone, 1 if hs_flag else 0, 1 if tdd else 0, detect_factor, max_occasions, max_preambles)
+
+
+def prach_cfg_info(cfg):
+    """srslte_hip_prach_cfg_info -> PrachInfo, or None where create would refuse the configuration (host; no GPU)."""
+    info = PrachInfo()
+    return info if lib().srslte_hip_prach_cfg_info(C.byref(cfg), C.byref(info)) == SRSLTE_SUCCESS else None
+
+
+def prach_tti_opportunity_fdd(config_idx, tti, allowed_subframe=-1):
+    """srslte_prach_tti_opportunity_config_fdd (host)."""
+    return bool(lib().srslte_hip_prach_tti_opportunity_fdd(config_idx, tti, allowed_subframe))
+
+
+def prach_preamble_format(config_idx):
+    return lib().srslte_hip_prach_preamble_format(config_idx)
+
+
+class Prach:
+    """Batched PRACH: srslte_prach_gen for a list of preambles, srslte_prach_detect_offset for a list of occasions in one signal."""
+
+    def __init__(self, nof_prb, config_idx, max_occasions=1, max_preambles=1, **kw):
+        self.cfg = prach_cfg(nof_prb, config_idx, max_occasions=max_occasions, max_preambles=max_preambles, **kw)
+        self.h = lib().srslte_hip_prach_create(C.byref(self.cfg))
+        if not self.h:
+            raise RuntimeError("srslte_hip_prach_create failed")
+        self.info = PrachInfo()
+        _check(lib().srslte_hip_prach_info(self.h, C.byref(self.info)), "prach_info")
+        self.len = self.info.N_cp + self.info.N_seq
+
+    def gen_device(self, txs, d_out, stream=None):
+        arr = (PrachTx * max(1, len(txs)))(*txs)
+        return lib().srslte_hip_prach_gen_batch(self.h, arr, len(txs), d_out, stream)
+
+    def gen(self, txs):
+        """[(seq_index, freq_offset)] -> (rc, [n][N_cp + N_seq] complex64 or None)."""
+        txs = [PrachTx(*t) for t in txs]
+        d = DevBuf(8 * self.len * max(1, len(txs)))
+        rc = self.gen_device(txs, d.ptr)
+        if rc != SRSLTE_SUCCESS:
+            return rc, None
+        sync()
+        return rc, d.to_host(np.complex64).reshape(-1, self.len)[:len(txs)]
+
+    def detect_device(self, d_signal, sig_len, occs, d_nof, d_idx, d_toff, d_p2a, stream=None):
+        arr = (PrachOccasion * max(1, len(occs)))(*occs)
+        return lib().srslte_hip_prach_detect_batch(self.h, d_signal, sig_len, arr, len(occs), d_nof, d_idx, d_toff, d_p2a, stream)
+
+    def detect(self, signal, occs, d_signal=None, sig_len=None):
+        """signal complex64 (host; or None with its device copy d_signal of sig_len samples), occs [(sample, freq_offset)] ->
+        (rc, [(indices uint32, t_offsets float32, peak_to_avg float32)] per occasion, or None)."""
+        occs = [PrachOccasion(s, f, 0) for s, f in occs]
+        n, md = len(occs), self.info.max_det
+        keep = None
+        if d_signal is None:
+            keep = DevBuf.from_host(np.ascontiguousarray(signal, np.complex64))
+            d_signal = keep.ptr
+        if sig_len is None:
+            sig_len = int(np.asarray(signal).size)
+        dn, di, dt, dp = DevBuf(4 * max(1, n)), DevBuf(4 * md * max(1, n)), DevBuf(4 * md * max(1, n)), DevBuf(4 * md * max(1, n))
+        rc = self.detect_device(d_signal, sig_len, occs, dn.ptr, di.ptr, dt.ptr, dp.ptr)
+        if rc != SRSLTE_SUCCESS:
+            return rc, None
+        sync()
+        nof = dn.to_host(np.uint32)[:n]
+        idx = di.to_host(np.uint32).reshape(-1, md)
+        tof = dt.to_host(np.float32).reshape(-1, md)
+        p2a = dp.to_host(np.float32).reshape(-1, md)
+        return rc, [(idx[o, :nof[o]].copy(), tof[o, :nof[o]].copy(), p2a[o, :nof[o]].copy()) for o in range(n)]
+
+    def free(self):
+        if self.h:
+            lib().srslte_hip_prach_destroy(self.h)
+            self.h = None
