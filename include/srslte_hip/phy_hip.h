@@ -574,7 +574,8 @@ int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, uint32_t nof_
  * srslte_phich_r_t 0-3 = 1/6, 1/2, 1, 2; phich_ext = SRSLTE_PHICH_EXT; the PHICH REGs of regs.c:245-367 with mi = 1). Refused: TDD cells
  * (srslte_hip_dl_ctrl_create returns NULL) and MBSFN subframes (SRSLTE_ERROR_INVALID_INPUTS).
  * The MIB: srslte_hip_dl_ctrl_mib_batch ("DL broadcast" below).
- * Not here: PHICH decoding, UL DCIs (srslte_ue_dl_find_ul_dci), carrier indicator / carrier
+ * UL DCIs and the PHICH: srslte_hip_dl_ctrl_batch_ul / srslte_hip_dl_ctrl_phich_batch below.
+ * Not here: carrier indicator / carrier
  * aggregation, the DCI -> grant unpacking (srslte_dci_msg_unpack_pdsch + srslte_ra_dl_dci_to_grant stay with the caller), and
  * the single-subframe drop-in's pcfich.c / pdcch.c, which remain the reference's. */
 typedef struct srslte_hip_dl_ctrl srslte_hip_dl_ctrl_t;
@@ -635,6 +636,72 @@ uint32_t srslte_hip_pdcch_common_locations_ncce(uint32_t nof_cce, uint32_t* loc,
 /* srslte_dci_format_sizeof of an FDD cell with a zero srslte_dci_cfg_t, format srslte_dci_format_t 0-8 (0 1 1A 1C 1B 1D 2 2A 2B); 0 otherwise */
 uint32_t srslte_hip_dci_format_sizeof(uint32_t nof_prb, uint32_t nof_ports, int format);
 
+/* ------------------------------------------------------------------ DL control region receive: UL DCIs and PHICH (UE side). What
+ * srslte_ue_dl_find_ul_dci (ue_dl.c:480-531, with the pending-UL-DCI rule of dci_blind_search :448-470) and srslte_ue_dl_decode_phich
+ * (:673-703 -> srslte_phich_calc + srslte_phich_decode, phich.c:132-143, :181-313) do per TTI, for a batch of subframes on a
+ * srslte_hip_dl_ctrl_t: a UE's find_dl_dci -> find_ul_dci -> decode_phich becomes one call, queued on the caller's stream with no host
+ * synchronisation, one launch behind the three of srslte_hip_dl_ctrl_batch.
+ *   UL DCIs (stateless per subframe, cif disabled), for a C-RNTI request:
+ *     1. The DL search is walked as srslte_hip_dl_ctrl_batch walks it. While the format searched is 1A (UE-specific space, and the common
+ *        space last), every candidate decoded before the DL hit whose CRC remainder equals the RNTI and whose flag bit says format 0 joins
+ *        the subframe's pending list, unless SRSLTE_HIP_DL_CTRL_MAX_UL_DCI are held or one with the same nof_bits and payload is (find_dci,
+ *        ue_dl.c:406-420). The walk ends at the first DL hit; candidates behind it are not looked at in this step.
+ *     2. A pending list that is not empty is the UL result, in the order of discovery (pending = 1). Otherwise the UE-specific locations are
+ *        walked again for format 0 and the first candidate with a matching CRC and the format-0 flag is the one UL result (pending = 0).
+ *     3. Formats 0 and 1A have one size and srslte_pdcch_decode_msg is a pure function of the LLR row, so step 2 runs no decoder: it reads
+ *        the candidates the 1A search decoded.
+ *     A deliberate narrowing: for an SI-, P- or RA-RNTI request and for RNTI 0 the UL result is empty (srsue searches no UL DCI with those).
+ *   PHICH: ngroup, nseq by srslte_phich_calc; the 12 REs of the group's mapping unit (the REG lists of the transmit side; mi = 1; on an
+ *     extended-CP cell groups 2m and 2m + 1 share a unit and the odd one takes symbols 2, 3 of each REG, phich.c:263-277) on every receive
+ *     antenna; srslte_predecoding_single_multi with the noise estimate as it is, or srslte_predecoding_diversity_multi +
+ *     srslte_layerdemap_diversity (2 / 4 ports) - 12 symbols are below every SIMD threshold of precoding.c, so the generic bodies with all
+ *     antennas; srslte_scrambling_c with srslte_sequence_phich; de-spreading by the conjugate orthogonal sequence with the 1 / N_SF factor
+ *     inside the sum (N_SF 4 / 2); BPSK soft demapping; srslte_phich_ack_decode: ack_value 1 only if the +1 correlation is strictly greater,
+ *     distance the winning correlation.
+ * Capacity for PHICH requests is not part of srslte_hip_dl_ctrl_cfg_t (its layout is kept): srslte_hip_dl_ctrl_set_max_phich allocates it
+ * (0 after create; calling it again replaces the buffers and waits for the device, so not with work of this object in flight). The requests
+ * and soft values of a call lie in one device buffer per object, as the candidates of srslte_hip_dl_ctrl_batch do: calls on one object belong
+ * on one stream at a time; use one object per stream.
+ * Refused with SRSLTE_ERROR_INVALID_INPUTS before anything is queued: what srslte_hip_dl_ctrl_batch refuses (null pointers, nof_sf 0 or
+ * beyond max_batch, MBSFN, tm > 3, cfi > 3), nof_phich beyond the capacity, a request's sf >= nof_sf, I_phich > 1, a resulting ngroup >=
+ * srslte_regs_phich_ngroups (I_phich 1 names a group only on an extended-CP cell; phich.c:215-218. nseq is within the CP's sequence count by
+ * srslte_phich_calc's own modulo, so the check of phich.c:204-214 has nothing to refuse).
+ * Not here: TDD (mi factors, I_phich by UL / DL configuration), MBSFN subframes, carrier indicator / cross-carrier UL DCIs, TPC formats
+ * 3 / 3A, the DCI -> grant unpacking (srslte_dci_msg_unpack_pusch + srslte_ra_ul_dci_to_grant stay with the caller), several UEs searching
+ * one subframe's LLR row in one call, PHICH / UL DCIs in the fixed-grant srslte_hip_dl_rx_batch, and the single-subframe drop-in's phich.c,
+ * which remains the reference's. */
+#define SRSLTE_HIP_DL_CTRL_MAX_UL_DCI 5 /* SRSLTE_MAX_DCI_MSG */
+typedef struct {            /* per subframe */
+  uint32_t nof_ul_dci;      /* format-0 messages found: 0 .. SRSLTE_HIP_DL_CTRL_MAX_UL_DCI */
+  uint32_t pending;         /* 1: they are the pending list of the DL search; 0: found by the format-0 search (or none) */
+} srslte_hip_dl_ctrl_ul_res_t;
+typedef struct {            /* one PHICH to read (host array): the srslte_phich_grant_t of the PUSCH it acknowledges */
+  uint32_t sf;              /* subframe within the batch; several requests per subframe are allowed */
+  uint32_t n_prb_lowest, n_dmrs, I_phich;
+} srslte_hip_phich_req_t;
+typedef struct {            /* per request */
+  uint32_t ack_value;       /* srslte_phich_res_t.ack_value */
+  float    distance;        /* srslte_phich_res_t.distance */
+  uint32_t ngroup, nseq;    /* srslte_phich_resource_t */
+} srslte_hip_phich_res_t;
+typedef struct {            /* per request (srslte_hip_dl_ctrl_phich_debug_buffer) */
+  float z[3][2];            /* q->z of phich.c after de-spreading (re, im) */
+  float bits[3];            /* q->data_rx: the BPSK soft bits */
+} srslte_hip_phich_soft_t;
+int srslte_hip_dl_ctrl_set_max_phich(srslte_hip_dl_ctrl_t* q, uint32_t max_phich);
+/* Everything srslte_hip_dl_ctrl_batch takes and returns (d_out and d_msg get what that call writes), plus d_ul_out [nof_sf], d_ul_msg
+ * [nof_sf][SRSLTE_HIP_DL_CTRL_MAX_UL_DCI] (format 0; unused entries: nof_bits 0), and phich [nof_phich] (host; may be NULL with
+ * nof_phich 0) -> d_phich_res [nof_phich] in request order. Result buffers may be device-visible pinned host memory. */
+int srslte_hip_dl_ctrl_batch_ul(srslte_hip_dl_ctrl_t* q, const void* d_grid, const void* d_ce, const void* d_res, uint32_t tti0, uint32_t nof_sf,
+                                const srslte_hip_dl_ctrl_req_t* reqs, srslte_hip_dl_ctrl_res_t* d_out, srslte_hip_dci_msg_t* d_msg,
+                                srslte_hip_dl_ctrl_ul_res_t* d_ul_out, srslte_hip_dci_msg_t* d_ul_msg, const srslte_hip_phich_req_t* phich,
+                                uint32_t nof_phich, srslte_hip_phich_res_t* d_phich_res, void* stream);
+/* the PHICH part alone, for callers that know the grants already; nof_phich 0 queues nothing */
+int srslte_hip_dl_ctrl_phich_batch(srslte_hip_dl_ctrl_t* q, const void* d_grid, const void* d_ce, const void* d_res, uint32_t tti0, uint32_t nof_sf,
+                                   const srslte_hip_phich_req_t* phich, uint32_t nof_phich, srslte_hip_phich_res_t* d_phich_res, void* stream);
+/* device buffer of the last call with PHICH requests: [nof_phich] srslte_hip_phich_soft_t; NULL before srslte_hip_dl_ctrl_set_max_phich */
+const void* srslte_hip_dl_ctrl_phich_debug_buffer(const srslte_hip_dl_ctrl_t* q);
+
 /* ------------------------------------------------------------------ DL control region transmit (eNB side): what srslte_enb_dl_put_base does
  * for the PCFICH (enb_dl.c:342-351), srslte_enb_dl_put_phich (:353-358) and srslte_enb_dl_put_pdcch_dl / _ul (:360-390) for a batch of
  * subframes, in one call on the caller's stream with no host synchronisation (the descriptors travel through pinned buffers, as the grants
@@ -654,7 +721,7 @@ uint32_t srslte_hip_dci_format_sizeof(uint32_t nof_prb, uint32_t nof_ports, int 
  * ncce + 2^L > NOF_CCE(cfi), nof_bits 0 or >= SRSLTE_DCI_MAX_BITS - 16 (pdcch.c:572-573), two DCIs of one subframe on a common CCE (the
  * reference would silently overwrite: a deliberate difference), a PHICH group >= srslte_regs_phich_ngroups, ack > 1, more than max_dci DCIs or
  * max_phich PHICHs. TDD cells are refused by create (NULL).
- * Not here: PHICH decoding, control in the fixed-grant srslte_hip_dl_tx_batch, TDD (the PHICH mi factor, special
+ * Not here: control in the fixed-grant srslte_hip_dl_tx_batch, TDD (the PHICH mi factor, special
  * subframes) and MBSFN subframes, DCI packing (srslte_dci_msg_pack_pdsch / _pusch stay with the caller), carrier indicator, and the
  * single-subframe drop-in's pcfich.c / pdcch.c / phich.c, which remain the reference's. */
 typedef struct srslte_hip_dl_ctrl_tx srslte_hip_dl_ctrl_tx_t;

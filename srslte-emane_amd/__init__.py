@@ -1001,8 +1001,36 @@ class DlCtrlCand(C.Structure):
                 ("format_decoded", C.c_uint32), ("payload", C.c_uint8 * 128)]
 
 
+DL_CTRL_MAX_UL_DCI = 5
+
+
+class DlCtrlUlRes(C.Structure):
+    """srslte_hip_dl_ctrl_ul_res_t: the UL DCIs of one subframe; pending = 1 if they are the DL search's pending list."""
+    _fields_ = [("nof_ul_dci", C.c_uint32), ("pending", C.c_uint32)]
+
+
+class PhichReq(C.Structure):
+    """srslte_hip_phich_req_t: the srslte_phich_grant_t of the PUSCH a PHICH acknowledges, with its subframe within the batch."""
+    _fields_ = [("sf", C.c_uint32), ("n_prb_lowest", C.c_uint32), ("n_dmrs", C.c_uint32), ("I_phich", C.c_uint32)]
+
+
+class PhichRes(C.Structure):
+    """srslte_hip_phich_res_t: srslte_phich_res_t and the srslte_phich_resource_t it was read from."""
+    _fields_ = [("ack_value", C.c_uint32), ("distance", C.c_float), ("ngroup", C.c_uint32), ("nseq", C.c_uint32)]
+
+
+class PhichSoft(C.Structure):
+    """srslte_hip_phich_soft_t: z after de-spreading (re, im) and the three BPSK soft bits of one PHICH."""
+    _fields_ = [("z", (C.c_float * 2) * 3), ("bits", C.c_float * 3)]
+
+
 def _bind_dl_ctrl(L):
     vp = C.c_void_p
+    L.srslte_hip_dl_ctrl_set_max_phich.argtypes = [vp, C.c_uint32]
+    L.srslte_hip_dl_ctrl_batch_ul.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp]
+    L.srslte_hip_dl_ctrl_phich_batch.argtypes = [vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp, vp]
+    L.srslte_hip_dl_ctrl_phich_debug_buffer.restype = vp
+    L.srslte_hip_dl_ctrl_phich_debug_buffer.argtypes = [vp]
     L.srslte_hip_dl_ctrl_create.restype = vp
     L.srslte_hip_dl_ctrl_create.argtypes = [C.POINTER(DlCtrlCfg)]
     L.srslte_hip_dl_ctrl_destroy.argtypes = [vp]
@@ -1109,10 +1137,16 @@ def mib_pack(nof_prb, phich_ext, phich_resources, sfn):
     return out
 
 
-class DlCtrl:
-    """Batched control-region receive: srslte_pcfich_decode + srslte_pdcch_extract_llr + the DL DCI blind search of srslte_ue_dl_find_dl_dci."""
+def _phich_reqs(phichs):
+    """PhichReq or (sf, n_prb_lowest, n_dmrs, I_phich) -> a ctypes array (one dummy entry when empty)."""
+    return (PhichReq * max(1, len(phichs)))(*[x if isinstance(x, PhichReq) else PhichReq(*x) for x in phichs])
 
-    def __init__(self, nof_prb, nof_ports, cell_id, cp_ext=False, phich_resources=0, phich_ext=False, nof_rx=1, max_batch=1, tdd=False):
+
+class DlCtrl:
+    """Batched control-region receive: srslte_pcfich_decode + srslte_pdcch_extract_llr + the DL DCI blind search of srslte_ue_dl_find_dl_dci;
+    with batch_ul / phich also srslte_ue_dl_find_ul_dci and srslte_ue_dl_decode_phich (max_phich: PHICH requests per call)."""
+
+    def __init__(self, nof_prb, nof_ports, cell_id, cp_ext=False, phich_resources=0, phich_ext=False, nof_rx=1, max_batch=1, tdd=False, max_phich=0):
         L = _bind_dl_ctrl(lib())
         self.cfg = _ctrl_cfg(nof_prb, nof_ports, cell_id, cp_ext, phich_resources, phich_ext, nof_rx, max_batch, tdd)
         self.h = L.srslte_hip_dl_ctrl_create(C.byref(self.cfg))
@@ -1121,6 +1155,67 @@ class DlCtrl:
         self.grid_len = (12 if cp_ext else 14) * 12 * nof_prb
         self.nof_ports, self.nof_rx, self.max_batch = nof_ports, nof_rx, max_batch
         self.llr_stride = L.srslte_hip_dl_ctrl_llr_stride(self.h)
+        if max_phich:
+            self.set_max_phich(max_phich)
+
+    def set_max_phich(self, max_phich):
+        """srslte_hip_dl_ctrl_set_max_phich: room for max_phich PHICH requests per call (waits for the device)."""
+        _check(lib().srslte_hip_dl_ctrl_set_max_phich(self.h, max_phich), "srslte_hip_dl_ctrl_set_max_phich")
+
+    def batch_ul_device(self, d_grid, d_ce, d_res, tti0, reqs, d_out, d_msg, d_ul_out, d_ul_msg, phichs=(), d_phich_res=None, stream=None):
+        """srslte_hip_dl_ctrl_batch_ul on device pointers; reqs: list of DlCtrlReq, phichs: PhichReq or tuples. Returns the status code."""
+        arr = (DlCtrlReq * max(1, len(reqs)))(*reqs)
+        return lib().srslte_hip_dl_ctrl_batch_ul(self.h, d_grid, d_ce, d_res, tti0, len(reqs), arr, d_out, d_msg, d_ul_out, d_ul_msg,
+                                                 _phich_reqs(phichs) if len(phichs) else None, len(phichs), d_phich_res, stream)
+
+    def phich_device(self, d_grid, d_ce, d_res, tti0, nof_sf, phichs, d_phich_res, stream=None):
+        """srslte_hip_dl_ctrl_phich_batch on device pointers -> the status code."""
+        return lib().srslte_hip_dl_ctrl_phich_batch(self.h, d_grid, d_ce, d_res, tti0, nof_sf, _phich_reqs(phichs) if len(phichs) else None,
+                                                    len(phichs), d_phich_res, stream)
+
+    def _upload(self, n, grid, ce, res):
+        g = np.ascontiguousarray(grid, np.complex64).reshape(n, self.nof_rx, self.grid_len)
+        h = np.ascontiguousarray(ce, np.complex64).reshape(n, self.nof_ports, self.nof_rx, self.grid_len)
+        r = np.ascontiguousarray(res, np.float32).reshape(n, 10)
+        return DevBuf.from_host(g), DevBuf.from_host(h), DevBuf.from_host(r)
+
+    def batch_ul(self, grid, ce, res, tti0, reqs, phichs=()):
+        """grid, ce, res as batch takes them -> (rc, [DlCtrlRes], [DciMsg], [DlCtrlUlRes], [[DciMsg] per subframe, nof_ul_dci long], [PhichRes])."""
+        n, m = len(reqs), len(phichs)
+        dg, dh, dr = self._upload(n, grid, ce, res)
+        dout, dmsg = DevBuf(C.sizeof(DlCtrlRes) * n), DevBuf(C.sizeof(DciMsg) * n)
+        dul, dulm = DevBuf(C.sizeof(DlCtrlUlRes) * n), DevBuf(C.sizeof(DciMsg) * n * DL_CTRL_MAX_UL_DCI)
+        dph = DevBuf(C.sizeof(PhichRes) * max(1, m))
+        rc = self.batch_ul_device(dg.ptr, dh.ptr, dr.ptr, tti0, reqs, dout.ptr, dmsg.ptr, dul.ptr, dulm.ptr, phichs, dph.ptr)
+        if rc != SRSLTE_SUCCESS:
+            return rc, None, None, None, None, None
+        sync()
+        out, msg, ul, ulm, ph = (DlCtrlRes * n)(), (DciMsg * n)(), (DlCtrlUlRes * n)(), (DciMsg * (n * DL_CTRL_MAX_UL_DCI))(), (PhichRes * max(1, m))()
+        for dst, src in ((out, dout), (msg, dmsg), (ul, dul), (ulm, dulm), (ph, dph)):
+            _check(lib().srslte_hip_memcpy_d2h(C.addressof(dst), src.ptr, C.sizeof(dst)), "memcpy_d2h")
+        ul_msgs = [list(ulm[b * DL_CTRL_MAX_UL_DCI:b * DL_CTRL_MAX_UL_DCI + ul[b].nof_ul_dci]) for b in range(n)]
+        return rc, list(out), list(msg), list(ul), ul_msgs, list(ph)[:m]
+
+    def phich(self, grid, ce, res, tti0, phichs):
+        """srslte_hip_dl_ctrl_phich_batch: grid, ce, res as batch takes them -> (rc, [PhichRes] or None)."""
+        n, m = len(res), len(phichs)
+        dg, dh, dr = self._upload(n, grid, ce, res)
+        dph = DevBuf(C.sizeof(PhichRes) * max(1, m))
+        rc = self.phich_device(dg.ptr, dh.ptr, dr.ptr, tti0, n, phichs, dph.ptr)
+        if rc != SRSLTE_SUCCESS:
+            return rc, None
+        sync()
+        ph = (PhichRes * max(1, m))()
+        _check(lib().srslte_hip_memcpy_d2h(C.addressof(ph), dph.ptr, C.sizeof(ph)), "memcpy_d2h")
+        return rc, list(ph)[:m]
+
+    def phich_soft(self, nof_phich):
+        """The PHICH debug buffer of the last call: [PhichSoft] (z after de-spreading and the soft bits of each request)."""
+        out = (PhichSoft * max(1, nof_phich))()
+        ptr = lib().srslte_hip_dl_ctrl_phich_debug_buffer(self.h)
+        if nof_phich:
+            _check(lib().srslte_hip_memcpy_d2h(C.addressof(out), ptr, C.sizeof(PhichSoft) * nof_phich), "memcpy_d2h")
+        return list(out)[:nof_phich]
 
     def run_device(self, d_grid, d_ce, d_res, tti0, reqs, d_out, d_msg, stream=None):
         """Device pointers in and out; reqs: list of DlCtrlReq. Returns the status code."""

@@ -23,6 +23,14 @@ int ctrl_build_regs(const srslte_hip_dl_ctrl_cfg_t* c, CtrlRegs& r);
 // pdcch_bits bits (sequences.c:51-53) of subframes 0-9, packed bit i -> word i / 32, bit i % 32: scr = [10 PCFICH words][10][scr_words]
 void ctrl_scrambling(uint32_t cell_id, uint32_t pdcch_bits, std::vector<uint32_t>& scr, int* scr_words);
 
+// srslte_phich_calc (phich.c:132-143) for the transmit (pdcch_tx.hip) and the receive side (phich.hip): Ngroups is
+// srslte_regs_phich_ngroups_m1, nsf 4 (normal CP) or 2 (extended)
+inline void phich_calc(uint32_t ng_m1, int cp_ext, uint32_t n_prb_lowest, uint32_t n_dmrs, uint32_t I_phich, uint32_t* ngroup, uint32_t* nseq)
+{
+  *ngroup = (n_prb_lowest + n_dmrs) % ng_m1 + I_phich * ng_m1;
+  *nseq   = ((n_prb_lowest / ng_m1) + n_dmrs) % (2 * (cp_ext ? 2u : 4u));
+}
+
 // Broadcast channels of one cell (pbch.hip): the RE list of srslte_pbch_cp (pbch.c:54-101) as indices into one port's [nsym][12 prb] grid
 // of the subframe (slot 1), the 72 REs of the PSS and of the SSS with their zero guards (pss.c:380-386, sss.c:106-119) and their values,
 // srslte_sequence_pbch (4 nof_bits bits) packed bit i -> word i / 32, bit i % 32

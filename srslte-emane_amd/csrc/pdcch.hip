@@ -335,9 +335,23 @@ struct srslte_hip_dl_ctrl {
   srslte_hip_dl_ctrl_cand_t* d_cand = nullptr;
   uint32_t*                d_ncand = nullptr;
   BcastTables*             bc = nullptr; // the MIB decoder (pbch.hip)
+  PhichRx*                 ph = nullptr; // the PHICH receiver (phich.hip), once srslte_hip_dl_ctrl_set_max_phich has made it
 };
 
 const BcastTables* dl_ctrl_bcast(const srslte_hip_dl_ctrl_t* q) { return q ? q->bc : nullptr; }
+
+DlCtrlView dl_ctrl_view(srslte_hip_dl_ctrl_t* q) { return DlCtrlView{&q->cfg, q->g.scr_pcfich, q->d_cand, q->d_ncand}; }
+PhichRx*   dl_ctrl_phich(const srslte_hip_dl_ctrl_t* q) { return q->ph; }
+void       dl_ctrl_set_phich(srslte_hip_dl_ctrl_t* q, PhichRx* t) { q->ph = t; }
+
+int dl_ctrl_check(const srslte_hip_dl_ctrl_t* q, uint32_t nof_sf, const srslte_hip_dl_ctrl_req_t* reqs)
+{
+  if (!q || !reqs || nof_sf < 1 || nof_sf > q->cfg.max_batch) return SRSLTE_ERROR_INVALID_INPUTS;
+  for (uint32_t b = 0; b < nof_sf; b++) {
+    if (reqs[b].mbsfn || reqs[b].tm > 3 || reqs[b].cfi > 3) return SRSLTE_ERROR_INVALID_INPUTS;
+  }
+  return SRSLTE_SUCCESS;
+}
 
 extern "C" {
 
@@ -388,6 +402,7 @@ void srslte_hip_dl_ctrl_destroy(srslte_hip_dl_ctrl_t* q)
   (void)hipFree(q->d_cand);
   (void)hipFree(q->d_ncand);
   bcast_tables_destroy(q->bc);
+  phich_rx_destroy(q->ph);
   delete q;
 }
 
@@ -434,10 +449,8 @@ srslte_hip_dl_ctrl_t* srslte_hip_dl_ctrl_create(const srslte_hip_dl_ctrl_cfg_t* 
 int srslte_hip_dl_ctrl_batch(srslte_hip_dl_ctrl_t* q, const void* d_grid, const void* d_ce, const void* d_res, uint32_t tti0, uint32_t nof_sf,
                              const srslte_hip_dl_ctrl_req_t* reqs, srslte_hip_dl_ctrl_res_t* d_out, srslte_hip_dci_msg_t* d_msg, void* stream)
 {
-  if (!q || !d_grid || !d_ce || !d_res || !reqs || !d_out || !d_msg || nof_sf < 1 || nof_sf > q->cfg.max_batch) return SRSLTE_ERROR_INVALID_INPUTS;
-  for (uint32_t b = 0; b < nof_sf; b++) {
-    if (reqs[b].mbsfn || reqs[b].tm > 3 || reqs[b].cfi > 3) return SRSLTE_ERROR_INVALID_INPUTS;
-  }
+  if (!d_grid || !d_ce || !d_res || !d_out || !d_msg) return SRSLTE_ERROR_INVALID_INPUTS;
+  if (int r = dl_ctrl_check(q, nof_sf, reqs)) return r;
   hipStream_t st = (hipStream_t)stream;
   for (uint32_t s0 = 0; s0 < nof_sf; s0 += REQ_CHUNK) {
     const uint32_t n = nof_sf - s0 < (uint32_t)REQ_CHUNK ? nof_sf - s0 : (uint32_t)REQ_CHUNK;

@@ -182,13 +182,6 @@ srslte_hip_dl_ctrl_cfg_t rx_cfg(const srslte_hip_dl_ctrl_tx_cfg_t* c)
   return r;
 }
 
-// srslte_phich_calc (phich.c:132-143): Ngroups is srslte_regs_phich_ngroups_m1, nsf 4 (normal CP) or 2 (extended)
-void phich_calc(uint32_t ng_m1, int cp_ext, uint32_t n_prb_lowest, uint32_t n_dmrs, uint32_t I_phich, uint32_t* ngroup, uint32_t* nseq)
-{
-  *ngroup = (n_prb_lowest + n_dmrs) % ng_m1 + I_phich * ng_m1;
-  *nseq   = ((n_prb_lowest / ng_m1) + n_dmrs) % (2 * (cp_ext ? 2u : 4u));
-}
-
 } // namespace
 
 struct srslte_hip_dl_ctrl_tx {

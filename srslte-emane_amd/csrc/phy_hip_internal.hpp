@@ -94,6 +94,22 @@ int          bcast_tx_launch(const BcastTables* t, uint32_t tti0, uint32_t nof_s
 // pdcch_tx.hip / pdcch.hip: an object's broadcast tables
 const BcastTables* dl_ctrl_tx_bcast(const srslte_hip_dl_ctrl_tx_t* q);
 const BcastTables* dl_ctrl_bcast(const srslte_hip_dl_ctrl_t* q);
+// pdcch.hip: the checks of srslte_hip_dl_ctrl_batch on the object, the batch size and the requests alone (nothing is queued), and what
+// phich.hip reads of a srslte_hip_dl_ctrl_t: its cell, the PCFICH / PHICH sequences and the searched candidates on the device; and the PHICH
+// receiver the object owns (phich.hip makes it in srslte_hip_dl_ctrl_set_max_phich and hands it over with dl_ctrl_set_phich, which does not free
+// the one held before; srslte_hip_dl_ctrl_destroy frees it with phich_rx_destroy)
+struct PhichRx;
+struct DlCtrlView {
+  const srslte_hip_dl_ctrl_cfg_t*  cfg;
+  const uint32_t*                  d_scr_pcfich; // [10] words
+  const srslte_hip_dl_ctrl_cand_t* d_cand;       // [max_batch][SRSLTE_HIP_DL_CTRL_MAX_CAND]
+  const uint32_t*                  d_ncand;      // [max_batch]
+};
+int        dl_ctrl_check(const srslte_hip_dl_ctrl_t* q, uint32_t nof_sf, const srslte_hip_dl_ctrl_req_t* reqs);
+DlCtrlView dl_ctrl_view(srslte_hip_dl_ctrl_t* q);
+PhichRx*   dl_ctrl_phich(const srslte_hip_dl_ctrl_t* q);
+void       dl_ctrl_set_phich(srslte_hip_dl_ctrl_t* q, PhichRx* t);
+void       phich_rx_destroy(PhichRx* t);
 // pucch.hip: the checks of srslte_hip_ul_ctrl_pucch_batch alone (nothing is queued), and whether an object was made for a receiver's cell
 int  ul_ctrl_check(const srslte_hip_ul_ctrl_t* q, uint32_t nof_sf, const srslte_hip_pucch_req_t* reqs, uint32_t nof);
 bool ul_ctrl_same_cell(const srslte_hip_ul_ctrl_t* q, uint32_t nof_prb, uint32_t cell_id, int cp_ext);
