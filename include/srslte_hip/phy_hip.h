@@ -995,6 +995,101 @@ int srslte_hip_prach_detect_check(const srslte_hip_prach_cfg_t* cfg, size_t sig_
 int srslte_hip_prach_tti_opportunity_fdd(uint32_t config_idx, uint32_t tti, int allowed_subframe);
 int srslte_hip_prach_preamble_format(uint32_t config_idx);
 
+/* ------------------------------------------------------------------ UE CSI feedback: PMI, RI and CQI from the DL estimates. What
+ * select_pmi / select_ri_pmi / srslte_ue_dl_select_ri (ue_dl.c:705-800) measure per TTI - srslte_precoding_pmi_select for one and two
+ * layers, srslte_precoding_cn (precoding.c:2151-2929) and srslte_cqi_from_snr - for a batch of subframes in ONE launch, one workgroup per
+ * subframe, on the estimates where srslte_hip_chest_dl_estimate_batch_multi left them: d_ce [nof_sf][nof_ports][nof_rx][nsym][12 nof_prb]
+ * (the reference's h[i][j] is port i, antenna j), d_res [nof_sf] srslte_hip_chest_dl_res_t, whose noise_estimate and snr_db are read on the
+ * device; d_out [nof_sf] may be device-visible pinned host memory.
+ * Sampling is that of the reference's AVX build: with N = nsym 12 nof_prb the PMI selection reads RE 24 k for k < 4 floor(N / 96) (the vector
+ * loops drop the tail group), the condition number k < ceil(N / 24) (srslte_precoding_2x2_cn_gen). Per sample the arithmetic is the _gen
+ * text with exact divisions; the sums are reduced in a fixed order. The AVX two-layer variant's _mm256_rcp_ps is not imitated.
+ * 2-port cells with 2 receive antennas are what the reference computes. nof_ports = 1: every field 0 (select_pmi does nothing).
+ * nof_rx = 1 on a 2-port cell: one-layer selection with the missing antenna's row zero, ri = 0, and no condition number (srslte_precoding_cn
+ * refuses all but 2x2): sinr_2l, pmi_2l, cn_db and ri_cn are 0. srslte_hip_csi_create returns NULL for 4 ports, more than 2 antennas or a cell
+ * outside 6-110 PRB; srslte_hip_csi_batch refuses null pointers with SRSLTE_ERROR_INVALID_INPUTS before anything is queued.
+ * A noise_estimate of 0 (the estimator on a noise-free signal) is not clamped, as the reference does not clamp it: the one-layer SINRs are
+ * +inf (none exceeds another: pmi_1l 0, sinr_db +inf, cqi_sinr 15), the two-layer ones 0 / 0 = NaN (pmi_2l 0, never chosen), cn_db is
+ * unaffected. A caller that wants a floor applies it to d_res before the call. */
+typedef struct srslte_hip_csi srslte_hip_csi_t;
+typedef struct {
+  float    sinr_1l[4], sinr_2l[2]; /* linear, sinr_list of srslte_precoding_pmi_select for 1 / 2 layers */
+  uint32_t pmi_1l, pmi_2l;         /* the selected codebook entries */
+  float    cn_db;                  /* srslte_precoding_cn */
+  uint32_t ri_cn;                  /* cn_db < 17.0f ? 1 : 0 (srslte_ue_dl_select_ri) */
+  uint32_t ri, pmi;                /* select_ri_pmi: this_sinr_db > best + 0.1 || this_sinr_db > 20.0 over ri < min(nof_rx, nof_ports) */
+  float    sinr_db;
+  uint32_t cqi_sinr;               /* srslte_cqi_from_snr(sinr_db + snr_to_cqi_offset) */
+  uint32_t cqi_wideband;           /* srslte_cqi_from_snr(snr_db + snr_to_cqi_offset) */
+  uint32_t reserved;               /* 0; the record is 64 bytes */
+} srslte_hip_csi_res_t;
+srslte_hip_csi_t* srslte_hip_csi_create(uint32_t nof_prb, uint32_t nof_ports, uint32_t nof_rx, int cp_is_norm);
+void              srslte_hip_csi_destroy(srslte_hip_csi_t* q);
+int               srslte_hip_csi_set_snr_to_cqi_offset(srslte_hip_csi_t* q, float offset); /* srslte_ue_dl_cfg_t.snr_to_cqi_offset; default 0 */
+int               srslte_hip_csi_nof_samples(const srslte_hip_csi_t* q, uint32_t* n_pmi, uint32_t* n_cn); /* the two sample counts above */
+int srslte_hip_csi_batch(srslte_hip_csi_t* q, const void* d_ce, const void* d_res, uint32_t nof_sf, srslte_hip_csi_res_t* d_out, void* stream);
+/* The same measurement on the estimates and noise figures the last batch call of a receive pipeline left in its buffers (the ones stage 2 of
+ * srslte_hip_dl_rx_stage reads): one launch behind the existing ones. Refused with SRSLTE_ERROR_INVALID_INPUTS before anything is queued: no batch
+ * has run on the object, nof_sf greater than that batch, null pointers, a 4-port cell or more than 2 receive antennas. A single-port pipeline
+ * writes zeros. srslte_hip_dl_rx_set_snr_to_cqi_offset: the offset of these calls (default 0). */
+int srslte_hip_dl_rx_csi_batch(srslte_hip_dl_rx_t* q, uint32_t nof_sf, srslte_hip_csi_res_t* d_out, void* stream);
+int srslte_hip_dl_rx_set_snr_to_cqi_offset(srslte_hip_dl_rx_t* q, float offset);
+/* TEST AND DIAGNOSTIC ENTRIES, not needed to use the feature (srslte_hip_csi_nof_samples above is one too): they let the sampling rule and the
+ * decision rules be checked exactly without a device.
+ * host (no device needed): the decisions of one subframe from its seven sums - sums[0..3] the one-layer entries, [4..5] the two-layer ones,
+ * [6] the condition numbers, over n_pmi / n_cn samples - by the function the kernel's deciding lane runs; and srslte_cqi_from_snr */
+int      srslte_hip_csi_decide(const float sums[7], uint32_t n_pmi, uint32_t n_cn, float noise_estimate, float snr_db, float snr_to_cqi_offset,
+                               uint32_t nof_rx, srslte_hip_csi_res_t* out);
+uint32_t srslte_hip_cqi_from_snr(float snr);
+/* Host report generation (cqi.c, ue_dl.c:802-928; no device needed). srslte_hip_cqi_cfg_t / _value_t: srslte_cqi_cfg_t and the members of the four
+ * report structs of srslte_cqi_value_t side by side - WIDEBAND (PUCCH format 2): wideband_cqi, spatial_diff_cqi, pmi; SUBBAND: subband_cqi,
+ * subband_label; SUBBAND_UE: wideband_cqi, subband_diff_cqi; SUBBAND_HL: wideband_cqi / subband_diff_cqi (codeword 0), wideband_cqi_cw1 /
+ * subband_diff_cqi_cw1, pmi. srslte_hip_cqi_size and srslte_hip_cqi_value_pack return what srslte_cqi_size / srslte_cqi_value_pack return, the
+ * reference's quirks included (a SUBBAND report counts 2 bits; a SUBBAND_UE report repeats the differential in the position field); the packed
+ * row holds one bit per byte, the form srslte_hip_ul_tx_batch_uci_cqi (d_cqi rows) and srslte_hip_pucch_tx_t.cqi take. A report of
+ * more than 64 bits (SUBBAND_HL above 104 PRB with two codewords, SUBBAND_UE with L > 58) does not fit the row and is refused.
+ * srslte_hip_cqi_periodic_send / _ri_send: cqi_send / ri_send of cqi.c:457-528 (36.213 Tables 7.2.2-1A / -1B, FDD and TDD). */
+#define SRSLTE_HIP_CQI_MAX_BITS 64
+typedef struct {
+  int      type;                 /* srslte_cqi_type_t: 0 WIDEBAND, 1 SUBBAND, 2 SUBBAND_UE, 3 SUBBAND_HL */
+  int      data_enable, pmi_present, four_antenna_ports, rank_is_not_one, subband_label_2_bits;
+  uint32_t L, N;
+} srslte_hip_cqi_cfg_t;
+typedef struct {
+  uint32_t wideband_cqi, spatial_diff_cqi, pmi, subband_cqi, subband_label, subband_diff_cqi, wideband_cqi_cw1, subband_diff_cqi_cw1;
+} srslte_hip_cqi_value_t;
+int srslte_hip_cqi_size(const srslte_hip_cqi_cfg_t* cfg);
+int srslte_hip_cqi_value_pack(const srslte_hip_cqi_cfg_t* cfg, const srslte_hip_cqi_value_t* value, uint8_t buff[SRSLTE_HIP_CQI_MAX_BITS]);
+int srslte_hip_cqi_periodic_send(uint32_t I_cqi_pmi, uint32_t tti, int tdd);
+int srslte_hip_cqi_periodic_ri_send(uint32_t I_cqi_pmi, uint32_t I_ri, uint32_t tti, int tdd);
+int srslte_hip_cqi_hl_get_no_subbands(int nof_prb);
+/* srslte_ue_dl_gen_cqi_periodic / _aperiodic on a host copy of a measurement record, branch for branch. cfg: the UE's reporting configuration
+ * and last_ri, which is carried in and out as srslte_ue_dl_cfg_t.last_ri is (rank_is_not_one of a periodic report comes from it, not from
+ * the record). wideband_value: the caller's wideband CQI (srsue passes srslte_cqi_from_snr(snr_db + offset): the record's cqi_wideband).
+ * Subband differentials are zero and N = srslte_cqi_hl_get_no_subbands (0 up to 7 PRB), as in the reference. out: the report's configuration
+ * and value, ri_len / ri, cqi_len = srslte_cqi_size and the packed row. A TTI without a periodic report leaves everything 0. */
+typedef struct {
+  int      tm;                   /* 1-4 (srslte_tm_t + 1) */
+  uint32_t nof_prb, nof_ports, nof_rx_antennas;
+  int      tdd;                  /* frame type of the report schedule */
+  int      periodic_configured, ri_idx_present;
+  uint32_t I_cqi_pmi, I_ri;      /* cqi-pmi-ConfigIndex, ri-ConfigIndex */
+  int      format_is_subband;
+  int      aperiodic_mode;       /* 30 or 31 */
+  float    snr_to_cqi_offset;
+  uint32_t last_ri;              /* in / out */
+} srslte_hip_csi_report_cfg_t;
+typedef struct {
+  srslte_hip_cqi_cfg_t   cqi;
+  srslte_hip_cqi_value_t value;
+  uint32_t               ri_len, ri, cqi_len;
+  uint8_t                cqi_bits[SRSLTE_HIP_CQI_MAX_BITS];
+} srslte_hip_csi_report_t;
+int srslte_hip_csi_gen_cqi_periodic(const srslte_hip_csi_res_t* csi, srslte_hip_csi_report_cfg_t* cfg, uint32_t wideband_value, uint32_t tti,
+                                    srslte_hip_csi_report_t* out);
+int srslte_hip_csi_gen_cqi_aperiodic(const srslte_hip_csi_res_t* csi, srslte_hip_csi_report_cfg_t* cfg, uint32_t wideband_value,
+                                     srslte_hip_csi_report_t* out);
+
 #ifdef __cplusplus
 }
 #endif

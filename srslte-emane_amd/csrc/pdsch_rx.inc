@@ -49,6 +49,9 @@ struct srslte_hip_dl_rx {
   const cf32*            grid_in; // resource grids supplied by the caller (srslte_hip_dl_rx_grid_batch) instead of d_grid
   struct GrantsState*    gs;      // srslte_hip_dl_rx_batch_grants: created on first use
   struct srslte_hip_dl_rx* cw1;   // two-layer modes: the second codeword's back end (rate de-matching, decoder, TB assembly and their buffers)
+  srslte_hip_csi_t*      csi;        // srslte_hip_dl_rx_csi_batch: made on first use
+  uint32_t               est_nof_sf; // subframes the last estimator run (stage 1) left in d_ce / d_res; 0: none yet
+  float                  csi_offset; // snr_to_cqi_offset of srslte_hip_dl_rx_csi_batch
 };
 
 static void grants_free(GrantsState* g);
@@ -60,6 +63,7 @@ extern "C" void srslte_hip_dl_rx_destroy(srslte_hip_dl_rx_t* q)
   srslte_hip_ofdm_destroy(q->ofdm);
   srslte_hip_chest_dl_destroy(q->chest);
   srslte_hip_tdec_destroy(q->tdec);
+  srslte_hip_csi_destroy(q->csi);
   void* bufs[] = {q->d_idx[0], q->d_idx[1], q->d_idx[2], q->d_scr, q->d_rm_tbl, q->d_tbcrc, q->d_grid, q->d_ce, q->d_ce_full, q->d_d,
                   q->d_res,    q->d_e,      q->d_w,      q->d_cb_bytes, q->d_cb_ok, q->d_cb_iters, q->d_tb_rem, q->d_cb_syn,
                   q->d_csi,    q->d_csi_max, q->d_rm_tbl_rv[1], q->d_rm_tbl_rv[2], q->d_rm_tbl_rv[3]};
@@ -337,13 +341,19 @@ extern "C" int srslte_hip_dl_rx_stage(srslte_hip_dl_rx_t* q, int stage, const vo
   }
   switch (stage) {
     case 0: return srslte_hip_ofdm_rx_sf_batch(q->ofdm, d_iq, q->d_grid, (int)nof_sf * q->pg.nof_rx, stream); // [sf][rx] = nof_sf * nof_rx subframes
-    case 1:
+    case 1: {
+      q->est_nof_sf = 0; // srslte_hip_dl_rx_csi_batch measures what a successful estimator run left, nothing after a failed one
+      int r;
       if (q->cfg.mbsfn) { // estimate_port_mbsfn; the result's noise figure is the mean of the antennas' REFS estimates (get_noise, chest_dl.c:747-758)
         srslte_hip_chest_dl_cfg_t mc = q->cfg.chest_cfg;
         mc.mbsfn_area_id             = (uint16_t)q->cfg.mbsfn_area_id;
-        return chest_dl_estimate_mbsfn_rows(q->chest, &mc, tti0, grid, q->d_ce, (int)nof_sf, q->pg.nof_rx, 6, q->d_res, stream);
+        r = chest_dl_estimate_mbsfn_rows(q->chest, &mc, tti0, grid, q->d_ce, (int)nof_sf, q->pg.nof_rx, 6, q->d_res, stream);
+      } else {
+        r = chest_dl_estimate_batch_rows(q->chest, &q->cfg.chest_cfg, tti0, grid, q->d_ce, q->d_res, (int)nof_sf, q->pg.nof_rx, q->pg.ce_nre != 0, stream);
       }
-      return chest_dl_estimate_batch_rows(q->chest, &q->cfg.chest_cfg, tti0, grid, q->d_ce, q->d_res, (int)nof_sf, q->pg.nof_rx, q->pg.ce_nre != 0, stream);
+      if (r == SRSLTE_SUCCESS) q->est_nof_sf = nof_sf;
+      return r;
+    }
     case 2: {
       PdschGeom g = q->pg;
       g.tti0      = (int)tti0;
@@ -485,6 +495,25 @@ extern "C" int srslte_hip_dl_rx_batch_harq2(srslte_hip_dl_rx_t* q, const void* d
     }
   }
   return r;
+}
+
+// UE CSI feedback (csi.hip) on the estimates and noise figures of the last batch: one launch behind that batch's on the caller's stream
+extern "C" int srslte_hip_dl_rx_csi_batch(srslte_hip_dl_rx_t* q, uint32_t nof_sf, srslte_hip_csi_res_t* d_out, void* stream)
+{
+  if (!q || !d_out || nof_sf == 0 || q->est_nof_sf == 0 || nof_sf > q->est_nof_sf) return SRSLTE_ERROR_INVALID_INPUTS;
+  if (!q->csi) {
+    q->csi = srslte_hip_csi_create(q->cfg.nof_prb, (uint32_t)q->pg.nof_ports, (uint32_t)q->pg.nof_rx, (q->cfg.cp_ext || q->cfg.mbsfn) ? 0 : 1);
+    if (!q->csi) return SRSLTE_ERROR_INVALID_INPUTS;
+  }
+  if (int r = srslte_hip_csi_set_snr_to_cqi_offset(q->csi, q->csi_offset)) return r;
+  return srslte_hip_csi_batch(q->csi, q->d_ce, q->d_res, nof_sf, d_out, stream);
+}
+
+extern "C" int srslte_hip_dl_rx_set_snr_to_cqi_offset(srslte_hip_dl_rx_t* q, float offset)
+{
+  if (!q || !(offset == offset)) return SRSLTE_ERROR_INVALID_INPUTS;
+  q->csi_offset = offset;
+  return SRSLTE_SUCCESS;
 }
 
 // Same chain from resource grids already in the frequency domain (what follows srslte_ofdm_rx_sf in ue_dl.c:375-397): stages 1..5
