@@ -494,7 +494,8 @@ const void* srslte_hip_ul_tx_debug_buffer(const srslte_hip_ul_tx_t* q, int which
 /* ------------------------------------------------------------------ PDSCH transmit pipeline (eNB side): srslte_pdsch_encode
  * (pdsch.c:1059-1185: DL-SCH coding, scrambling, modulation, layer mapping + SFBC precoding, RE mapping) + CRS
  * (srslte_refsignal_cs_put_sf refsignal_dl.c:253-272) + srslte_ofdm_tx_sf with 1/sqrt(N) (enb_dl.c:56-62). One codeword, TM1 or 2-port
- * TM2, full-band grant; no control region, PSS/SSS or PBCH content (their REs stay zero). */
+ * TM2, full-band grant; no control region, PSS/SSS or PBCH content (their REs stay zero). Two codewords, TM3 (large-delay CDD) and TM4
+ * (codebook precoding) on a 2-port cell: srslte_hip_dl_tx_batch_grants2 below. */
 typedef struct srslte_hip_dl_tx srslte_hip_dl_tx_t;
 typedef struct {
   uint32_t cell_id, nof_prb, cfi;
@@ -532,6 +533,31 @@ typedef struct {
 } srslte_hip_dl_tx_grant_t;
 int srslte_hip_dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
                                   const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants, void* d_iq, void* stream);
+/* The same with the transmission scheme of each PDSCH and a second transport block: grants[p].grant is the srslte_hip_dl_grant2_t the receive
+ * side takes (srslte_hip_dl_rx_batch_grants2; new_data / new_data2 unused), so a grant unpacked once from DCI 2 / 2A serves both directions.
+ * srslte_pdsch_encode with nof_layers == nof_tb (pdsch.c:1100-1173): every enabled block is CRC-attached, segmented, turbo-coded and
+ * rate-matched on its own with the split unit Qm * N_L, N_L = 1 (sch.c:552-556), scrambled with its own codeword's sequence and modulated;
+ * srslte_precoding_type then applies rho_a: large-delay CDD (precoding.c:1897-1956) or the codebook of 36.211 Table 6.3.4.2.3-1 with
+ * codebook_idx = pmi for one block, pmi + 1 for two (pdsch.c:1152). On a 2-port object a call may mix, per entry, transmit diversity (tx_scheme
+ * 0 / 1, tbs2 = 0), CDD (SRSLTE_TXSCHEME_CDD 3: two blocks) and multiplexing (SRSLTE_TXSCHEME_SPATIALMUX 2: two blocks with pmi 0-1, or one
+ * with pmi 0-3) - what srslte_hip_dl_rx_batch_grants2 accepts; on other objects every entry is tx_scheme 0 / 1 with one block.
+ * d_tb has 2 * nof_grants rows: row p = transport block 0 of entry p, row nof_grants + p = its block 1 (not read where tbs2 = 0).
+ * cfg.tbs bounds both blocks, cfg.max_grants the PDSCHs of a call (so up to twice that many codewords). The buffers of the second
+ * codewords are made by the first of these calls on an object (it replaces the per-codeword buffers of srslte_hip_dl_tx_batch_grants by ones
+ * of twice the size, which both calls then use); an object that never makes one allocates nothing for them.
+ * Refused with SRSLTE_ERROR_INVALID_INPUTS and a log line, before anything is queued: tx_scheme 2 / 3 on an object whose cell is not 2-port;
+ * CDD without a second block; pmi out of range for its block count; a diversity entry with tbs2 != 0; mod2 / tbs2 / rv2 out of range; a block
+ * that needs filler bits or two block lengths; fewer REs than code blocks; and everything srslte_hip_dl_tx_batch_grants refuses.
+ * Out of scope, and refused the same way: objects created with cp_ext, tdd or mbsfn (they take srslte_hip_dl_tx_batch_grants only).
+ * Not here: 4-port cells and more than two layers (the reference's precoders are 2x2), the TB-swap flag, a disabled block 0 with block 1
+ * enabled, the fixed-grant srslte_hip_dl_tx_batch. srslte_hip_dl_tx_batch_grants2_ctrl / _full ("DL control region transmit" below): with
+ * the control region / the whole subframe, as srslte_hip_dl_tx_batch_grants_ctrl / _full. */
+typedef struct {
+  uint32_t               sf; /* 0 .. nof_sf-1 */
+  srslte_hip_dl_grant2_t grant;
+} srslte_hip_dl_tx_grant2_t;
+int srslte_hip_dl_tx_batch_grants2(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
+                                   const srslte_hip_dl_tx_grant2_t* grants, uint32_t nof_grants, void* d_iq, void* stream);
 /* intermediate device buffers of the last call: 0 code blocks, 1 parity streams, 2 per-port symbol streams [nof_sf][nof_ports][max nof_re],
  * 3 grids [nof_sf][nof_ports][14][12*nof_prb] */
 const void* srslte_hip_dl_tx_debug_buffer(const srslte_hip_dl_tx_t* q, int which);
@@ -798,6 +824,14 @@ int srslte_hip_dl_ctrl_tx_put_bcast(srslte_hip_dl_ctrl_tx_t* q, uint32_t tti0, u
 int srslte_hip_dl_tx_batch_grants_full(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
                                        const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
                                        const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream);
+/* srslte_hip_dl_tx_batch_grants_ctrl / _full with two-codeword grants (srslte_hip_dl_tx_batch_grants2: TM3 / TM4 PDSCHs beside the DCI
+ * formats 2A / 2 that announce them). Refused as those calls and as srslte_hip_dl_tx_batch_grants2. */
+int srslte_hip_dl_tx_batch_grants2_ctrl(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
+                                        const srslte_hip_dl_tx_grant2_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
+                                        const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream);
+int srslte_hip_dl_tx_batch_grants2_full(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
+                                        const srslte_hip_dl_tx_grant2_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
+                                        const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream);
 typedef struct {            /* per subframe */
   uint32_t found;           /* 1: a MIB was decoded; 0 otherwise and in every subframe whose TTI % 10 != 0 */
   uint32_t nof_tx_ports;    /* nant that decoded */

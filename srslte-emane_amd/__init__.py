@@ -885,6 +885,11 @@ class DlTxCfg(C.Structure):
                 ("mbsfn", C.c_int), ("mbsfn_area_id", C.c_uint32), ("non_mbsfn_region", C.c_uint32)]
 
 
+class DlTxGrant2(C.Structure):
+    """srslte_hip_dl_tx_grant2_t: the subframe of the batch and the grant as the receive side takes it (DlGrant2)."""
+    _fields_ = [("sf", C.c_uint32), ("grant", DlGrant2)]
+
+
 class DlTx:
     """Batched PDSCH transmit chain (srslte_pdsch_encode pdsch.c:1059-1185 + CRS + srslte_ofdm_tx_sf, enb_dl.c)."""
 
@@ -953,6 +958,51 @@ class DlTx:
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(DlCtrlTxIn), C.c_void_p,
                        C.c_void_p]
         rc = fn(self.h, din.ptr, stride, tti0, nof_sf, arr, len(grants), ctrl.h, C.byref(inp), self.d_iq.ptr, None)
+        if rc != SRSLTE_SUCCESS:
+            return rc, None
+        sync()
+        return rc, self.d_iq.to_host(np.complex64).reshape(self.max_batch, self.nof_ports, self.sf_len)[:nof_sf]
+
+    def _tb_rows2(self, tbs_bytes, n):
+        """[2 n][stride] device rows: row p = the first payload of entry p, row n + p its second (entries: lists of one or two payloads)."""
+        stride = (self.tbs // 8 + 15) & ~15
+        x = np.zeros((max(1, 2 * n), stride), np.uint8)
+        for p_, tbs_ in enumerate(tbs_bytes):
+            for cw, b in enumerate(tbs_):
+                x[cw * n + p_, :len(b)] = b
+        return DevBuf.from_host(x), stride
+
+    def encode_grants2(self, tbs_bytes, tti0, nof_sf, grants):
+        """srslte_hip_dl_tx_batch_grants2: grants = list of (sf, DlGrant2); tbs_bytes[p] = [payload of block 0] or [block 0, block 1] of grants[p]
+        -> (rc, iq [nof_sf][nof_ports][sf_len] or None)."""
+        n = len(grants)
+        din, stride = self._tb_rows2(tbs_bytes, n)
+        arr = (DlTxGrant2 * max(1, n))(*[DlTxGrant2(sf, g) for sf, g in grants])
+        fn = lib().srslte_hip_dl_tx_batch_grants2
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        rc = fn(self.h, din.ptr, stride, tti0, nof_sf, arr, n, self.d_iq.ptr, None)
+        if rc != SRSLTE_SUCCESS:
+            return rc, None
+        sync()
+        return rc, self.d_iq.to_host(np.complex64).reshape(self.max_batch, self.nof_ports, self.sf_len)[:nof_sf]
+
+    def encode_grants2_ctrl(self, tbs_bytes, tti0, nof_sf, grants, ctrl, cfi, dcis=(), phichs=()):
+        """srslte_hip_dl_tx_batch_grants2_ctrl: encode_grants2 with the control region of ctrl, as encode_grants_ctrl."""
+        return self._encode_grants2_with(lib().srslte_hip_dl_tx_batch_grants2_ctrl, tbs_bytes, tti0, nof_sf, grants, ctrl, cfi, dcis, phichs)
+
+    def encode_grants2_full(self, tbs_bytes, tti0, nof_sf, grants, ctrl, cfi, dcis=(), phichs=()):
+        """srslte_hip_dl_tx_batch_grants2_full: encode_grants2_ctrl with ctrl's PSS / SSS / PBCH, as encode_grants_full."""
+        return self._encode_grants2_with(lib().srslte_hip_dl_tx_batch_grants2_full, tbs_bytes, tti0, nof_sf, grants, ctrl, cfi, dcis, phichs)
+
+    def _encode_grants2_with(self, fn, tbs_bytes, tti0, nof_sf, grants, ctrl, cfi, dcis, phichs):
+        n = len(grants)
+        din, stride = self._tb_rows2(tbs_bytes, n)
+        arr = (DlTxGrant2 * max(1, n))(*[DlTxGrant2(sf, g) for sf, g in grants])
+        inp, keep = _ctrl_tx_in(cfi, dcis, phichs)
+        _bind_dl_ctrl_tx(lib())
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(DlCtrlTxIn), C.c_void_p,
+                       C.c_void_p]
+        rc = fn(self.h, din.ptr, stride, tti0, nof_sf, arr, n, ctrl.h, C.byref(inp), self.d_iq.ptr, None)
         if rc != SRSLTE_SUCCESS:
             return rc, None
         sync()

@@ -2,7 +2,8 @@
 // ====================================================================================================================
 // PDSCH transmit pipeline (eNB side; SURVEY §3.2): srslte_pdsch_encode (pdsch.c:1059-1185: DL-SCH coding sch.c:183-297 with the
 // Qm * N_L block split :549-575, scrambling, modulation, layer mapping + SFBC precoding, RE mapping) + CRS (srslte_refsignal_cs_put_sf,
-// refsignal_dl.c:253-272) + srslte_ofdm_tx_sf with 1/sqrt(N) (enb_dl.c:56-62). One codeword, TM1 or 2-port TM2, full-band grant.
+// refsignal_dl.c:253-272) + srslte_ofdm_tx_sf with 1/sqrt(N) (enb_dl.c:56-62). One codeword, TM1 or 2-port TM2, full-band grant;
+// the per-PDSCH grants mode also with two codewords, large-delay CDD and codebook precoding on a 2-port cell (TM3 / TM4).
 // Re-uses the PUSCH transmit kernels for CRC attachment / segmentation and the byte-stream turbo encoder.
 // ====================================================================================================================
 namespace {
@@ -21,43 +22,55 @@ struct PdschTxGeom {
 };
 constexpr int MBSFN_REF = 1 << 24;
 
+// Symbol i of a transport block on nre REs -> the indices of its two levels: its Qm coded bits - bit e of a code block = coded bit
+// rm[e mod (3K+12)] in the encoder's byte streams, as in pusch_tx_mod_kernel; the block split in units of Qm * Nl bits - scrambled with cs. Shared by every
+// modulation kernel of the transmit side.
+__device__ __forceinline__ void pdsch_tx_sym_bits(const uint8_t* __restrict__ cb, const uint8_t* __restrict__ parity, const uint8_t* __restrict__ sys_tail,
+                                                  const uint32_t* __restrict__ rm, const uint32_t* __restrict__ cs, int cb_stride, int par_stride, int i, int Nl,
+                                                  int nre, int cb0, int C, int Qm, int rm_len, int& re, int& im)
+{
+  const int Gp = nre / Nl; // Gp = G' of 36.212 5.1.4.1.2
+  const int QmL = Qm * Nl, gamma = Gp % C, lo = Gp / C, C_lo = C - gamma; // blocks 0..C_lo-1 carry lo units, the rest lo + 1 (sch.c:232-236)
+  const int u = i / Nl; // split unit
+  int       r, e0;
+  if (u < C_lo * lo) {
+    r  = u / lo;
+    e0 = (u - r * lo) * QmL;
+  } else {
+    const int v = u - C_lo * lo;
+    r           = C_lo + v / (lo + 1);
+    e0          = (v % (lo + 1)) * QmL;
+  }
+  e0 += (i % Nl) * Qm;
+  const size_t   cbi = (size_t)cb0 + r;
+  const uint8_t *xb = cb + cbi * cb_stride, *pb = parity + cbi * par_stride;
+  const int      q0 = i * Qm;
+  re = 0;
+  im = 0;
+  for (int b = 0; b < Qm; b++) {
+    const uint32_t src = rm[(e0 + b) % rm_len], pos = src & 0x3fffffffu;
+    const uint8_t  byte = (src >> 30) == 0 ? xb[pos >> 3] : ((src >> 30) == 1 ? sys_tail[cbi] : pb[pos >> 3]);
+    int            bit  = (byte >> (7 - (pos & 7))) & 1;
+    bit ^= (cs[(q0 + b) >> 5] >> ((q0 + b) & 31)) & 1;
+    if (b & 1) im = (im << 1) | bit;
+    else re = (re << 1) | bit;
+  }
+}
+
 // grid = (ceil(max_re / (256 * G)), nof_sf), G = nof_ports: one thread per precoding group (one symbol for TM1, the SFBC pair 2i, 2i+1 for
-// 2 ports, four symbols for 4 ports). Bit e of a code block = coded bit rm[e mod (3K+12)] in the encoder's byte streams, as in
-// pusch_tx_mod_kernel; the block split counts in units of Qm * N_L bits (N_L = 2 with transmit diversity). y: [nof_sf][nof_ports][max_re].
+// 2 ports, four symbols for 4 ports). The block split counts in units of Qm * N_L bits (N_L = 2 with transmit diversity). y: [nof_sf][nof_ports][max_re].
 // One transport block: nre symbols in precoding groups of G = nof_ports; cs: its scrambling bits; cb0: its first code-block slot; C / Qm / rm_len /
 // lvl: of ITS segmentation and modulation; y0: its [nof_ports][max_re] symbol streams.
 __device__ __forceinline__ void pdsch_tx_mod_body(const uint8_t* __restrict__ cb, const uint8_t* __restrict__ parity, const uint8_t* __restrict__ sys_tail,
                                                   const uint32_t* __restrict__ rm, const uint32_t* __restrict__ cs, cf32* __restrict__ y0, const PdschTxGeom& g,
                                                   int grp, int nre, int cb0, int C, int Qm, int rm_len, const float* __restrict__ lvl)
 {
-  const int G = g.nof_ports, Gp = nre / g.Nl; // Gp = G' of 36.212 5.1.4.1.2
+  const int G = g.nof_ports;
   if (grp * G >= nre) return;
-  const int QmL = Qm * g.Nl, gamma = Gp % C, lo = Gp / C, C_lo = C - gamma; // blocks 0..C_lo-1 carry lo units, the rest lo + 1 (sch.c:232-236)
   cf32            d[4];
   for (int t = 0; t < G; t++) {
-    const int i = grp * G + t, u = i / g.Nl; // symbol, split unit
-    int       r, e0;
-    if (u < C_lo * lo) {
-      r  = u / lo;
-      e0 = (u - r * lo) * QmL;
-    } else {
-      const int v = u - C_lo * lo;
-      r           = C_lo + v / (lo + 1);
-      e0          = (v % (lo + 1)) * QmL;
-    }
-    e0 += (i % g.Nl) * Qm;
-    const size_t   cbi = (size_t)cb0 + r;
-    const uint8_t *xb = cb + cbi * g.cb_stride, *pb = parity + cbi * g.par_stride;
-    const int      q0 = i * Qm;
-    int            re = 0, im = 0;
-    for (int b = 0; b < Qm; b++) {
-      const uint32_t src = rm[(e0 + b) % rm_len], pos = src & 0x3fffffffu;
-      const uint8_t  byte = (src >> 30) == 0 ? xb[pos >> 3] : ((src >> 30) == 1 ? sys_tail[cbi] : pb[pos >> 3]);
-      int            bit  = (byte >> (7 - (pos & 7))) & 1;
-      bit ^= (cs[(q0 + b) >> 5] >> ((q0 + b) & 31)) & 1;
-      if (b & 1) im = (im << 1) | bit;
-      else re = (re << 1) | bit;
-    }
+    int re, im;
+    pdsch_tx_sym_bits(cb, parity, sys_tail, rm, cs, g.cb_stride, g.par_stride, grp * G + t, g.Nl, nre, cb0, C, Qm, rm_len, re, im);
     d[t] = make_float2(lvl[re] * g.gain, lvl[im] * g.gain);
   }
   const cf32 z  = make_float2(0.f, 0.f);
@@ -98,6 +111,9 @@ struct TxDesc {
   int             cb0;                 // its first code-block slot (slots have the strides of the largest block size)
   int             nre, mod, Qm;
   const uint32_t* rm;                  // rate-matching table of (K, rv)
+  // descriptor of a PDSCH's codeword 0 (srslte_hip_dl_tx_batch_grants2): srslte_tx_scheme_t, the precoder's codebook index (pdsch.c:1152), and
+  // the descriptor of its codeword 1 (-1: one transport block)
+  int             scheme, codebook, cw1;
 };
 struct TxLevels { float v[5][16]; };   // constellation levels of one axis per srslte_mod_t
 
@@ -147,6 +163,48 @@ __global__ __launch_bounds__(256) void pdsch_tx_mod_grants_kernel(const uint8_t*
                     d.C, d.Qm, 3 * d.K + 12, lv.v[d.mod]);
 }
 
+// The two-layer modes of a 2-port cell (srslte_pdsch_encode with nof_layers == nof_tb, pdsch.c:1100-1173): grid = (ceil(max_re / 256), nof_pdsch2),
+// PDSCH v0 + blockIdx.y, one thread per symbol i of the PDSCH. Symbol i of codeword 0 and - where the PDSCH has one - of codeword 1 (descriptor
+// cw1: its own code blocks, rate-matching table, modulation and scrambling row), each split in units of Qm (N_L = 1, sch.c:552-556) and modulated
+// to the table's levels as srslte_mod_modulate leaves them; then the precoder, which applies the gain, operation by operation as the reference:
+//   large-delay CDD (srslte_precoding_cdd_2x2, precoding.c:1897-1956), s2 = 0.5 scaling: y0 = (x0 + x1) s2; y1 = (x0 - x1) s2 for even i,
+//     (-x0 + x1) s2 for odd i - i counts the symbols of the PDSCH
+//   multiplexing, one layer (srslte_precoding_multiplex, :1988-2010), s1 = scaling / sqrt(2): y0 = x s1; y1 = x s1, -x s1, j x s1, -j x s1 for
+//     codebook index 0-3
+//   multiplexing, two layers (:2015-2090): index 1: y0 = (x0 + x1) s2, y1 = (x0 - x1) s2; index 2: y1 = j (x0 - x1) s2
+// y: [nof_pdsch][2][max_re], as pdsch_tx_scatter_kernel reads it.
+__global__ __launch_bounds__(256) void pdsch_tx_mod2_grants_kernel(const uint8_t* __restrict__ cb, const uint8_t* __restrict__ parity,
+                                                                   const uint8_t* __restrict__ sys_tail, const uint32_t* __restrict__ scr, int scr_words,
+                                                                   cf32* __restrict__ y, const TxDesc* __restrict__ desc, int v0, TxLevels lv, float s1,
+                                                                   float s2, int max_re, int cb_stride, int par_stride)
+{
+  const int     v = v0 + (int)blockIdx.y, i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  const TxDesc& d = desc[v];
+  const int     nre = d.nre, scheme = d.scheme, codebook = d.codebook, cw1 = d.cw1;
+  if (i >= nre) return;
+  int re, im;
+  pdsch_tx_sym_bits(cb, parity, sys_tail, d.rm, scr + (size_t)v * scr_words, cb_stride, par_stride, i, 1, nre, d.cb0, d.C, d.Qm, 3 * d.K + 12, re, im);
+  const cf32 x0 = make_float2(lv.v[d.mod][re], lv.v[d.mod][im]);
+  cf32*      y0 = y + (size_t)v * 2 * max_re;
+  cf32*      y1 = y0 + max_re;
+  if (cw1 < 0) { // one layer: srslte_vec_sc_prod_cfc / _ccc with the codebook's second entry
+    const float a = x0.x * s1, b = x0.y * s1;
+    y0[i] = make_float2(a, b);
+    y1[i] = codebook == 0 ? make_float2(a, b) : (codebook == 1 ? make_float2(-a, -b) : (codebook == 2 ? make_float2(-b, a) : make_float2(b, -a)));
+    return;
+  }
+  const TxDesc& e = desc[cw1];
+  pdsch_tx_sym_bits(cb, parity, sys_tail, e.rm, scr + (size_t)cw1 * scr_words, cb_stride, par_stride, i, 1, nre, e.cb0, e.C, e.Qm, 3 * e.K + 12, re, im);
+  const cf32 x1 = make_float2(lv.v[e.mod][re], lv.v[e.mod][im]);
+  y0[i] = make_float2((x0.x + x1.x) * s2, (x0.y + x1.y) * s2);
+  float dr = x0.x - x1.x, di = x0.y - x1.y;
+  if (scheme == 3 && (i & 1)) { // -x0 + x1
+    dr = -x0.x + x1.x;
+    di = -x0.y + x1.y;
+  }
+  y1[i] = (scheme == 2 && codebook == 2) ? make_float2(-di * s2, dr * s2) : make_float2(dr * s2, di * s2);
+}
+
 // grid = (ceil(max_re / 256), nof_pdsch * nof_ports): the symbols of PDSCH p, port by port, onto the REs of its list in its subframe's grids
 __global__ __launch_bounds__(256) void pdsch_tx_scatter_kernel(const cf32* __restrict__ y, const uint32_t* __restrict__ relist, cf32* __restrict__ grid,
                                                                const TxDesc* __restrict__ desc, int max_re, int grid_len, int nof_ports)
@@ -187,12 +245,13 @@ struct srslte_hip_dl_tx {
   int32_t*               d_src[3][4];
   uint8_t *              d_cb, *d_parity, *d_sys_tail;
   cf32 *                 d_y, *d_grid;
-  struct TxGrantsState*  gs; // srslte_hip_dl_tx_batch_grants: created on first use
+  struct TxGrantsState*  gs; // srslte_hip_dl_tx_batch_grants / _grants2: created on first use
+  float                  rho_a; // pdsch.c:525: the precoders' `scaling`
 };
 
 // Device / host resources of the per-PDSCH grants mode of the transmit pipeline
 struct TxGrantsState {
-  uint32_t  V, Cmax, max_re, words, cb_stride, par_stride;
+  uint32_t  V, W, Cmax, max_re, words, cb_stride, par_stride; // V PDSCHs of W codewords: W = V, or 2 V from the first srslte_hip_dl_tx_batch_grants2 call on
   uint32_t *d_relist, *d_scr, *d_basis, *d_tbcrc;
   uint8_t * d_cb, *d_parity, *d_sys_tail, *d_desc;
   cf32*     d_y;
@@ -315,6 +374,7 @@ extern "C" srslte_hip_dl_tx_t* srslte_hip_dl_tx_create(const srslte_hip_dl_tx_cf
   constellation_levels(cfg->mod, g.lvl);
   const float rho_a = powf(10.0f, cfg->p_a / 20.0f) * (npt == 1 ? 1.0f : sqrtf(2.0f)); // pdsch.c:525
   g.gain            = npt == 1 ? rho_a : rho_a / sqrtf(2.0f);                          // precoding.c:1859-1860
+  q->rho_a          = rho_a;
   ok = ok && hipMalloc((void**)&q->d_tbcrc, sizeof(uint32_t) * B) == hipSuccess &&
        hipMalloc((void**)&q->d_cb, (size_t)cg.cb_stride * B * C) == hipSuccess &&
        hipMalloc((void**)&q->d_parity, (size_t)cg.par_stride * B * C) == hipSuccess &&
@@ -377,25 +437,27 @@ extern "C" int srslte_hip_dl_tx_batch(srslte_hip_dl_tx_t* q, const uint8_t* d_tb
   return srslte_hip_ofdm_tx_sf_batch(q->ofdm, q->d_grid, d_iq, (int)nof_sf * g.nof_ports, stream);
 }
 
-static int dl_tx_grants_init(srslte_hip_dl_tx_t* q, uint32_t V)
+// W: the codewords the state holds (code-block slots, parity, scrambling rows, CRC words, descriptors): V, or 2 V for the two-layer modes
+static int dl_tx_grants_init(srslte_hip_dl_tx_t* q, uint32_t V, uint32_t W)
 {
   const uint32_t P = q->cfg.nof_prb, cell_id = q->cfg.cell_id;
   const int      npt = q->g.nof_ports;
   auto*          g = new TxGrantsState(); // value-initialised: every pointer and flag starts null / false
   q->gs         = g;
   g->V          = V;
+  g->W          = W;
   g->Cmax       = q->seg.C;
   g->max_re     = 14 * 12 * P;
   g->words      = (g->max_re * 8 + 31) / 32 + 2;
   g->cb_stride  = (6144 / 8 + 15) & ~15u;
   g->par_stride = (6144 / 4 + 1 + 15) & ~15u;
-  const size_t nblk = (size_t)V * g->Cmax;
-  g->desc_bytes     = (sizeof(GrantDev) + sizeof(TxDesc)) * V;
+  const size_t nblk = (size_t)W * g->Cmax;
+  g->desc_bytes     = (sizeof(GrantDev) + sizeof(TxDesc)) * W;
   if (g->ring.init(g->desc_bytes)) return SRSLTE_ERROR;
   if (gold_basis_upload(g->words, &g->d_basis)) return SRSLTE_ERROR;
   HIP_TRY(hipMalloc((void**)&g->d_relist, sizeof(uint32_t) * (size_t)g->max_re * V));
-  HIP_TRY(hipMalloc((void**)&g->d_scr, sizeof(uint32_t) * (size_t)g->words * V));
-  HIP_TRY(hipMalloc((void**)&g->d_tbcrc, sizeof(uint32_t) * V));
+  HIP_TRY(hipMalloc((void**)&g->d_scr, sizeof(uint32_t) * (size_t)g->words * W));
+  HIP_TRY(hipMalloc((void**)&g->d_tbcrc, sizeof(uint32_t) * W));
   HIP_TRY(hipMalloc((void**)&g->d_cb, (size_t)g->cb_stride * nblk));
   HIP_TRY(hipMalloc((void**)&g->d_parity, (size_t)g->par_stride * nblk));
   HIP_TRY(hipMalloc((void**)&g->d_sys_tail, nblk));
@@ -421,20 +483,24 @@ static int dl_tx_grants_init(srslte_hip_dl_tx_t* q, uint32_t V)
 
 // Per-PDSCH grants on the transmit side: what an eNB sends in a run of TTIs - srslte_enb_dl_put_base once per TTI, then srslte_enb_dl_put_pdsch
 // once per scheduled UE (enb_dl.c:330-398 -> srslte_pdsch_encode, pdsch.c:1059-1185), each with its own srslte_pdsch_grant_t, then
-// srslte_enb_dl_gen_signal. grants[p]: the subframe of the batch, and a srslte_hip_dl_grant_t as the receive side takes it (PRB masks of both
-// slots, modulation, transport block, redundancy version, RNTI, CFI; new_data is not used). Row p of d_tb is its transport block. The grids are
+// srslte_enb_dl_gen_signal. grants[p]: the subframe of the batch, and a srslte_hip_dl_grant2_t as the receive side takes it (PRB masks of both
+// slots, modulation, transport block, redundancy version, RNTI, CFI, and - two_cw - the transmission scheme, pmi and second transport block;
+// new_data is not used). Row p of d_tb is its transport block 0, row nof_grants + p its block 1. The grids are
 // initialised with the CRS of every port, each PDSCH's symbols go onto the REs pdsch_relist_kernel lists for its masks (srslte_pdsch_cp, put =
 // true, including upstream's stale-offset rule); allocations that overlap within a subframe are the caller's error (which PDSCH wins an RE is
 // not defined here; upstream the later put would). The object's
-// cell, antenna ports (TM1 / transmit diversity), p_a apply; cfg.tbs bounds every grant's tbs, cfg.max_grants the number of PDSCHs per call.
+// cell, antenna ports, p_a apply; cfg.tbs bounds every transport block, cfg.max_grants the number of PDSCHs per call.
+// Every codeword is one TxDesc / GrantDev: descriptors 0 .. n - 1 are the PDSCHs (codeword 0, the RE list, the symbol streams; the transmit-
+// diversity ones first, so that each modulation kernel runs over a range), the ones behind them the second codewords.
+// two_cw = false (srslte_hip_dl_tx_batch_grants): every entry is TM1 / transmit diversity with one block, and d_tb has nof_grants rows.
 // ctrl / in: srslte_hip_dl_tx_batch_grants_ctrl's control region, put on the grids after the PDSCHs (nullptr: none); bcast: ctrl's PSS / SSS /
 // PBCH put between the grid initialisation and the PDSCHs (srslte_hip_dl_tx_batch_grants_full)
 static int dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
-                              const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
+                              const srslte_hip_dl_tx_grant2_t* grants, uint32_t nof_grants, bool two_cw, srslte_hip_dl_ctrl_tx_t* ctrl,
                               const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream, bool bcast = false)
 {
   if (!q || !d_tb || !d_iq || !grants || nof_sf > q->cfg.max_batch) return SRSLTE_ERROR_INVALID_INPUTS;
-  const uint32_t V = q->cfg.max_grants ? q->cfg.max_grants : q->cfg.max_batch, P = q->cfg.nof_prb, cell_id = q->cfg.cell_id;
+  const uint32_t V = q->cfg.max_grants ? q->cfg.max_grants : q->cfg.max_batch, P = q->cfg.nof_prb, cell_id = q->cfg.cell_id, Cmax = q->seg.C;
   const int      npt = q->g.nof_ports;
   if (nof_grants > V) return SRSLTE_ERROR_INVALID_INPUTS;
   if (q->cfg.mbsfn) {
@@ -443,7 +509,54 @@ static int dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32
   }
   if (nof_sf == 0) return SRSLTE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
-  if (!q->gs && dl_tx_grants_init(q, V)) { // a failed start leaves no half-made state behind
+  // every refusal before anything is allocated or queued
+  struct Cw { uint32_t p, row, tbs, rv; int mod, cw; srslte_hip_cbsegm_t seg; };
+  auto tb_ok = [&](int mod, uint32_t tbs, uint32_t rv, srslte_hip_cbsegm_t* seg) {
+    return mod >= 1 && mod <= 4 && rv <= 3 && tbs != 0 && tbs <= q->cfg.tbs && (tbs % 8) == 0 && tb_stride >= tbs / 8 && srslte_hip_cbsegm(seg, tbs) == 0 &&
+           seg->F == 0 && seg->C2 == 0 && seg->C <= Cmax;
+  };
+  std::vector<GrantDev>            gds(nof_grants);
+  std::vector<uint32_t>            nres(nof_grants);
+  std::vector<srslte_hip_cbsegm_t> seg0(nof_grants), seg1(nof_grants);
+  uint32_t                         nd = 0, n2 = 0; // transmit-diversity PDSCHs, second codewords
+  for (uint32_t p = 0; p < nof_grants; p++) {
+    const srslte_hip_dl_grant2_t& g2 = grants[p].grant;
+    const srslte_hip_dl_grant_t&  gr = g2.tb0;
+    if (grants[p].sf >= nof_sf || gr.cfi < 1 || gr.cfi > 3 || !tb_ok(gr.mod, gr.tbs, gr.rv, &seg0[p])) {
+      hip_log("[srslte_hip] dl_tx grants: entry %u: unsupported grant (subframe %u of %u, mod %d, tbs %u, rv %u, cfi %u)\n", p, grants[p].sf, nof_sf, gr.mod,
+              gr.tbs, gr.rv, gr.cfi);
+      return SRSLTE_ERROR_INVALID_INPUTS;
+    }
+    const bool two_layer = g2.tx_scheme >= 2;
+    if (g2.tx_scheme < 0 || g2.tx_scheme > 3 || (two_layer && (npt != 2 || (g2.tx_scheme == 3 && g2.tbs2 == 0) || (g2.tbs2 ? g2.pmi > 1 : g2.pmi > 3))) ||
+        (!two_layer && g2.tbs2)) {
+      hip_log("[srslte_hip] dl_tx grants: entry %u: unsupported grant (%d ports, tx_scheme %d, pmi %u, second transport block %u bits)\n", p, npt, g2.tx_scheme,
+              g2.pmi, g2.tbs2);
+      return SRSLTE_ERROR_INVALID_INPUTS;
+    }
+    if (g2.tbs2 && !tb_ok(g2.mod2, g2.tbs2, g2.rv2, &seg1[p])) {
+      hip_log("[srslte_hip] dl_tx grants: entry %u: unsupported second transport block (mod %d, tbs %u, rv %u)\n", p, g2.mod2, g2.tbs2, g2.rv2);
+      return SRSLTE_ERROR_INVALID_INPUTS;
+    }
+    GrantDev& gd = gds[p];
+    memset(&gd, 0, sizeof(gd));
+    gd.sf_idx = (int)((tti0 + grants[p].sf) % 10); gd.lstart = (int)(gr.cfi + (P < 10 ? 1 : 0)); gd.rnti = gr.rnti;
+    tdd_grant_symbols(q->cfg.tdd, q->cfg.tdd_sf_config, q->cfg.tdd_ss_config, q->cfg.cp_ext ? 6 : 7, (uint32_t)gd.sf_idx, gd);
+    const uint32_t nre = nres[p] = pdsch_grant_dev(gr, P, cell_id, npt, gd, q->cfg.cp_ext ? 6 : 7);
+    // the block split: Qm * N_L bits a unit, N_L = 2 with transmit diversity, 1 where nof_layers == nof_tb (sch.c:552-556)
+    if (two_layer ? (nre == 0 || nre < seg0[p].C || (g2.tbs2 && nre < seg1[p].C)) : (nre == 0 || (nre % (uint32_t)npt) || nre < seg0[p].C * (uint32_t)q->g.Nl)) {
+      hip_log("[srslte_hip] dl_tx grants: entry %u: %u REs do not carry %u code blocks on %d ports\n", p, nre, two_layer && g2.tbs2 ? seg1[p].C : seg0[p].C, npt);
+      return SRSLTE_ERROR_INVALID_INPUTS;
+    }
+    nd += two_layer ? 0 : 1;
+    n2 += g2.tbs2 ? 1 : 0;
+  }
+  const uint32_t W = two_cw ? 2 * V : V;
+  if (q->gs && q->gs->W < W) { // the first two-codeword call of an object that served single-codeword calls: the state is made anew for 2 V codewords
+    tx_grants_free(q->gs);     // (hipFree waits for what the device still runs on the old buffers)
+    q->gs = nullptr;
+  }
+  if (!q->gs && dl_tx_grants_init(q, V, W)) { // a failed start leaves no half-made state behind
     tx_grants_free(q->gs);
     q->gs = nullptr;
     return SRSLTE_ERROR;
@@ -452,49 +565,51 @@ static int dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32
   uint8_t*       h_pin = nullptr;
   if (int r = g->ring.acquire(&h_pin)) return r;
   auto* h_gr = reinterpret_cast<GrantDev*>(h_pin);
-  auto* h_td = reinterpret_cast<TxDesc*>(h_gr + V);
+  auto* h_td = reinterpret_cast<TxDesc*>(h_gr + g->W);
   auto* d_gr = reinterpret_cast<GrantDev*>(g->d_desc);
-  auto* d_td = reinterpret_cast<TxDesc*>(d_gr + V);
-  // code-block slots in the order of the block length, so that the encoder runs once per length over neighbouring slots
-  std::vector<uint32_t>            order(nof_grants);
-  std::vector<srslte_hip_cbsegm_t> segs(nof_grants);
-  uint32_t                         max_nre = 0;
-  for (uint32_t p = 0; p < nof_grants; p++) {
-    const srslte_hip_dl_grant_t& gr = grants[p].grant;
-    order[p] = p;
-    if (grants[p].sf >= nof_sf || gr.mod < 1 || gr.mod > 4 || gr.rv > 3 || gr.cfi < 1 || gr.cfi > 3 || gr.tbs == 0 || gr.tbs > q->cfg.tbs || (gr.tbs % 8) ||
-        tb_stride < gr.tbs / 8 || srslte_hip_cbsegm(&segs[p], gr.tbs) || segs[p].F || segs[p].C2 || segs[p].C > g->Cmax) {
-      hip_log("[srslte_hip] dl_tx grants: entry %u: unsupported grant (subframe %u of %u, mod %d, tbs %u, rv %u, cfi %u)\n", p, grants[p].sf, nof_sf, gr.mod,
-              gr.tbs, gr.rv, gr.cfi);
-      return SRSLTE_ERROR_INVALID_INPUTS;
+  auto* d_td = reinterpret_cast<TxDesc*>(d_gr + g->W);
+  // the codewords: descriptor v < nof_grants = codeword 0 of a PDSCH, transmit diversity in front; then the codewords 1
+  const uint32_t  ncw = nof_grants + n2;
+  std::vector<Cw> cws(ncw);
+  uint32_t        max_nre = 0, max_nre2 = 0;
+  {
+    uint32_t vd = 0, v2 = nd, c1 = nof_grants;
+    for (uint32_t p = 0; p < nof_grants; p++) {
+      const srslte_hip_dl_grant2_t& g2 = grants[p].grant;
+      const bool                    two_layer = g2.tx_scheme >= 2;
+      const uint32_t                v = two_layer ? v2++ : vd++;
+      cws[v] = {p, p, g2.tb0.tbs, g2.tb0.rv, g2.tb0.mod, -1, seg0[p]};
+      if (two_layer) max_nre2 = std::max(max_nre2, nres[p]);
+      else max_nre = std::max(max_nre, nres[p]);
+      if (g2.tbs2) {
+        cws[v].cw = (int)c1;
+        cws[c1++] = {p, nof_grants + p, g2.tbs2, g2.rv2, g2.mod2, -1, seg1[p]};
+      }
     }
   }
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return segs[a].K1 < segs[b].K1; });
+  // code-block slots in the order of the block length, so that the encoder runs once per length over neighbouring slots
+  std::vector<uint32_t> order(ncw);
+  for (uint32_t c = 0; c < ncw; c++) order[c] = c;
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cws[a].seg.K1 < cws[b].seg.K1; });
   uint32_t cb0 = 0;
-  for (uint32_t i = 0; i < nof_grants; i++) {
-    const uint32_t               p  = order[i];
-    const srslte_hip_dl_grant_t& gr = grants[p].grant;
-    GrantDev&                    gd = h_gr[p];
-    memset(&gd, 0, sizeof(gd));
-    gd.sf_idx = (int)((tti0 + grants[p].sf) % 10); gd.lstart = (int)(gr.cfi + (P < 10 ? 1 : 0)); gd.rnti = gr.rnti;
-    tdd_grant_symbols(q->cfg.tdd, q->cfg.tdd_sf_config, q->cfg.tdd_ss_config, q->cfg.cp_ext ? 6 : 7, (uint32_t)gd.sf_idx, gd);
-    const uint32_t nre = pdsch_grant_dev(gr, P, cell_id, npt, gd, q->cfg.cp_ext ? 6 : 7);
-    if (nre == 0 || (nre % (uint32_t)npt) || nre < segs[p].C * (uint32_t)q->g.Nl) {
-      hip_log("[srslte_hip] dl_tx grants: entry %u: %u REs do not carry %u code blocks on %d ports\n", p, nre, segs[p].C, npt);
-      return SRSLTE_ERROR_INVALID_INPUTS;
-    }
-    max_nre = nre > max_nre ? nre : max_nre;
-    const uint32_t K  = segs[p].K1;
-    auto           it = g->rm_tbl.find({K, gr.rv});
+  for (uint32_t i = 0; i < ncw; i++) {
+    const uint32_t                c  = order[i];
+    const Cw&                     w  = cws[c];
+    const srslte_hip_dl_grant2_t& g2 = grants[w.p].grant;
+    h_gr[c]    = gds[w.p];
+    h_gr[c].cw = c < nof_grants ? 0 : 1; // the codeword's own scrambling sequence (36.211 6.3.1)
+    const uint32_t K  = w.seg.K1;
+    auto           it = g->rm_tbl.find({K, w.rv});
     if (it == g->rm_tbl.end()) {
       uint32_t* d = nullptr;
-      if (rm_tx_table_upload(K, gr.rv, &d)) return SRSLTE_ERROR;
-      it = g->rm_tbl.emplace(std::make_pair(K, gr.rv), d).first;
+      if (rm_tx_table_upload(K, w.rv, &d)) return SRSLTE_ERROR;
+      it = g->rm_tbl.emplace(std::make_pair(K, w.rv), d).first;
     }
-    TxDesc& td = h_td[p];
-    td.row = (int)p; td.sf = (int)grants[p].sf; td.tbs = (int)gr.tbs; td.C = (int)segs[p].C; td.K = (int)K; td.rlenB = (int)((segs[p].C == 1 ? K : K - 24) / 8);
-    td.cb0 = (int)cb0; td.nre = (int)nre; td.mod = gr.mod; td.Qm = 2 * gr.mod; td.rm = it->second;
-    cb0 += segs[p].C;
+    TxDesc& td = h_td[c];
+    td.row = (int)w.row; td.sf = (int)grants[w.p].sf; td.tbs = (int)w.tbs; td.C = (int)w.seg.C; td.K = (int)K; td.rlenB = (int)((w.seg.C == 1 ? K : K - 24) / 8);
+    td.cb0 = (int)cb0; td.nre = (int)nres[w.p]; td.mod = w.mod; td.Qm = 2 * w.mod; td.rm = it->second;
+    td.scheme = g2.tx_scheme; td.codebook = (int)(g2.tbs2 ? g2.pmi + 1 : g2.pmi); td.cw1 = w.cw; // pdsch.c:1152
+    cb0 += w.seg.C;
   }
   HIP_TRY(hipMemcpyAsync(g->d_desc, h_pin, g->desc_bytes, hipMemcpyHostToDevice, st));
   if (int r = g->ring.release(st)) return r;
@@ -516,24 +631,31 @@ static int dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32
   if (nof_grants) {
     hipLaunchKernelGGL(pdsch_relist_kernel, dim3(nof_grants), dim3(RELIST_THREADS), 0, st, (const GrantDev*)d_gr, g->d_relist, (int)P, (int)cell_id,
                        (int)g->max_re, npt, q->cfg.cp_ext ? 6 : 7);
-    hipLaunchKernelGGL(scr_gen_kernel, dim3(ceil_div((int)g->words, 256), nof_grants), dim3(256), 0, st, (const GrantDev*)d_gr, (const uint32_t*)g->d_basis,
+    hipLaunchKernelGGL(scr_gen_kernel, dim3(ceil_div((int)g->words, 256), ncw), dim3(256), 0, st, (const GrantDev*)d_gr, (const uint32_t*)g->d_basis,
                        g->d_scr, (int)g->words, (int)cell_id);
-    hipLaunchKernelGGL(tx_tbcrc_grants_kernel, dim3(nof_grants), dim3(256), 0, st, d_tb, (int)tb_stride, (const TxDesc*)d_td, g->d_tbcrc);
-    hipLaunchKernelGGL(tx_seg_grants_kernel, dim3(g->Cmax, nof_grants), dim3(256), 0, st, d_tb, (int)tb_stride, (const uint32_t*)g->d_tbcrc, (const TxDesc*)d_td,
+    hipLaunchKernelGGL(tx_tbcrc_grants_kernel, dim3(ncw), dim3(256), 0, st, d_tb, (int)tb_stride, (const TxDesc*)d_td, g->d_tbcrc);
+    hipLaunchKernelGGL(tx_seg_grants_kernel, dim3(g->Cmax, ncw), dim3(256), 0, st, d_tb, (int)tb_stride, (const uint32_t*)g->d_tbcrc, (const TxDesc*)d_td,
                        g->d_cb, (int)g->cb_stride);
     LAUNCH_CHECK();
-    for (uint32_t i = 0; i < nof_grants;) { // the encoder: runs of equal block length
+    for (uint32_t i = 0; i < ncw;) { // the encoder: runs of equal block length
       uint32_t j = i, n = 0;
-      while (j < nof_grants && segs[order[j]].K1 == segs[order[i]].K1) n += segs[order[j++]].C;
+      while (j < ncw && cws[order[j]].seg.K1 == cws[order[i]].seg.K1) n += cws[order[j++]].seg.C;
       const size_t s0 = (size_t)h_td[order[i]].cb0;
       if (int r = srslte_hip_tcod_encode_bytes_batch(g->d_cb + s0 * g->cb_stride, g->cb_stride, g->d_parity + s0 * g->par_stride, g->par_stride,
-                                                     g->d_sys_tail + s0, segs[order[i]].K1, n, stream))
+                                                     g->d_sys_tail + s0, cws[order[i]].seg.K1, n, stream))
         return r;
       i = j;
     }
-    hipLaunchKernelGGL(pdsch_tx_mod_grants_kernel, dim3(ceil_div((int)max_nre / npt, 256), nof_grants), dim3(256), 0, st, (const uint8_t*)g->d_cb,
-                       (const uint8_t*)g->d_parity, (const uint8_t*)g->d_sys_tail, (const uint32_t*)g->d_scr, (int)g->words, g->d_y, (const TxDesc*)d_td, g->lv, tg);
-    hipLaunchKernelGGL(pdsch_tx_scatter_kernel, dim3(ceil_div((int)max_nre, 256), nof_grants * npt), dim3(256), 0, st, (const cf32*)g->d_y,
+    if (nd) {
+      hipLaunchKernelGGL(pdsch_tx_mod_grants_kernel, dim3(ceil_div((int)max_nre / npt, 256), nd), dim3(256), 0, st, (const uint8_t*)g->d_cb,
+                         (const uint8_t*)g->d_parity, (const uint8_t*)g->d_sys_tail, (const uint32_t*)g->d_scr, (int)g->words, g->d_y, (const TxDesc*)d_td, g->lv, tg);
+    }
+    if (nof_grants > nd) { // scaling / sqrt(2) and scaling / 2 as the reference's precoders form them
+      hipLaunchKernelGGL(pdsch_tx_mod2_grants_kernel, dim3(ceil_div((int)max_nre2, 256), nof_grants - nd), dim3(256), 0, st, (const uint8_t*)g->d_cb,
+                         (const uint8_t*)g->d_parity, (const uint8_t*)g->d_sys_tail, (const uint32_t*)g->d_scr, (int)g->words, g->d_y, (const TxDesc*)d_td, (int)nd,
+                         g->lv, q->rho_a / sqrtf(2.0f), q->rho_a / 2.0f, (int)g->max_re, (int)g->cb_stride, (int)g->par_stride);
+    }
+    hipLaunchKernelGGL(pdsch_tx_scatter_kernel, dim3(ceil_div((int)std::max(max_nre, max_nre2), 256), nof_grants * npt), dim3(256), 0, st, (const cf32*)g->d_y,
                        (const uint32_t*)g->d_relist, q->d_grid, (const TxDesc*)d_td, (int)g->max_re, tg.grid_len, npt);
     LAUNCH_CHECK();
   }
@@ -541,6 +663,28 @@ static int dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32
     if (int r = srslte_hip_dl_ctrl_tx_put(ctrl, tti0, nof_sf, in, q->d_grid, stream)) return r;
   }
   return srslte_hip_ofdm_tx_sf_batch(q->ofdm, q->d_grid, d_iq, (int)nof_sf * npt, stream);
+}
+
+// a single-codeword grant as the entry the pipeline takes: the object's scheme (TM1 / transmit diversity), no second transport block
+static std::vector<srslte_hip_dl_tx_grant2_t> dl_tx_grants_as2(const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants)
+{
+  std::vector<srslte_hip_dl_tx_grant2_t> g2(grants ? nof_grants : 0);
+  for (size_t p = 0; p < g2.size(); p++) {
+    memset(&g2[p], 0, sizeof(g2[p]));
+    g2[p].sf        = grants[p].sf;
+    g2[p].grant.tb0 = grants[p].grant;
+  }
+  return g2;
+}
+
+static int dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
+                              const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
+                              const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream, bool bcast = false)
+{
+  if (!grants) return SRSLTE_ERROR_INVALID_INPUTS;
+  const std::vector<srslte_hip_dl_tx_grant2_t> g2 = dl_tx_grants_as2(grants, nof_grants);
+  srslte_hip_dl_tx_grant2_t                    none = {};
+  return dl_tx_batch_grants(q, d_tb, tb_stride, tti0, nof_sf, g2.empty() ? &none : g2.data(), nof_grants, false, ctrl, in, d_iq, stream, bcast);
 }
 
 extern "C" int srslte_hip_dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
@@ -551,8 +695,11 @@ extern "C" int srslte_hip_dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_
 
 // the checks srslte_hip_dl_tx_batch_grants_ctrl / _full add: the control object's cell is the pipeline's, and everything the control region
 // refuses is refused before anything is queued
-static int dl_tx_ctrl_check(srslte_hip_dl_tx_t* q, uint32_t nof_sf, const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants,
-                            srslte_hip_dl_ctrl_tx_t* ctrl, const srslte_hip_dl_ctrl_tx_in_t* in)
+static uint32_t dl_tx_grant_cfi(const srslte_hip_dl_tx_grant_t& g) { return g.grant.cfi; }
+static uint32_t dl_tx_grant_cfi(const srslte_hip_dl_tx_grant2_t& g) { return g.grant.tb0.cfi; }
+template <typename Grant>
+static int dl_tx_ctrl_check(srslte_hip_dl_tx_t* q, uint32_t nof_sf, const Grant* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
+                            const srslte_hip_dl_ctrl_tx_in_t* in)
 {
   const srslte_hip_dl_ctrl_tx_cfg_t* cc = dl_ctrl_tx_cfg(ctrl);
   if (!q || !cc || !in || !grants || q->cfg.tdd || q->cfg.mbsfn || cc->nof_prb != q->cfg.nof_prb || cc->nof_ports != (uint32_t)q->g.nof_ports ||
@@ -560,7 +707,7 @@ static int dl_tx_ctrl_check(srslte_hip_dl_tx_t* q, uint32_t nof_sf, const srslte
     return SRSLTE_ERROR_INVALID_INPUTS;
   if (int r = dl_ctrl_tx_check(ctrl, nof_sf, in)) return r;
   for (uint32_t p = 0; p < nof_grants; p++) {
-    if (grants[p].sf < nof_sf && grants[p].grant.cfi != in->cfi[grants[p].sf]) return SRSLTE_ERROR_INVALID_INPUTS;
+    if (grants[p].sf < nof_sf && dl_tx_grant_cfi(grants[p]) != in->cfi[grants[p].sf]) return SRSLTE_ERROR_INVALID_INPUTS;
   }
   return SRSLTE_SUCCESS;
 }
@@ -584,4 +731,60 @@ extern "C" int srslte_hip_dl_tx_batch_grants_full(srslte_hip_dl_tx_t* q, const u
 {
   if (int r = dl_tx_ctrl_check(q, nof_sf, grants, nof_grants, ctrl, in)) return r;
   return dl_tx_batch_grants(q, d_tb, tb_stride, tti0, nof_sf, grants, nof_grants, ctrl, in, d_iq, stream, true);
+}
+
+// The two-layer modes of a 2-port cell on the transmit side (srslte_pdsch_encode with tx_scheme CDD / SPATIALMUX, pdsch.c:1100-1173): the grants
+// path above with the receive side's srslte_hip_dl_grant2_t per PDSCH; d_tb has 2 * nof_grants rows. Extended-CP, TDD and MBSFN objects are
+// not served by these calls.
+static int dl_tx_grants2_check(const srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t nof_sf, const srslte_hip_dl_tx_grant2_t* grants, uint32_t nof_grants,
+                               const void* d_iq)
+{
+  if (!q || !d_tb || !d_iq || !grants) {
+    hip_log("[srslte_hip] dl_tx grants2: null argument\n");
+    return SRSLTE_ERROR_INVALID_INPUTS;
+  }
+  if (q->cfg.cp_ext || q->cfg.tdd || q->cfg.mbsfn) {
+    hip_log("[srslte_hip] dl_tx grants2: extended-CP, TDD and MBSFN objects take single-codeword grants only (srslte_hip_dl_tx_batch_grants)\n");
+    return SRSLTE_ERROR_INVALID_INPUTS;
+  }
+  const uint32_t V = q->cfg.max_grants ? q->cfg.max_grants : q->cfg.max_batch;
+  if (nof_sf > q->cfg.max_batch || nof_grants > V) {
+    hip_log("[srslte_hip] dl_tx grants2: %u subframes / %u PDSCHs on an object made for %u / %u\n", nof_sf, nof_grants, q->cfg.max_batch, V);
+    return SRSLTE_ERROR_INVALID_INPUTS;
+  }
+  return SRSLTE_SUCCESS;
+}
+
+// dl_tx_ctrl_check with the log line the two-codeword calls promise for every refusal
+static int dl_tx_grants2_ctrl_check(srslte_hip_dl_tx_t* q, uint32_t nof_sf, const srslte_hip_dl_tx_grant2_t* grants, uint32_t nof_grants,
+                                    srslte_hip_dl_ctrl_tx_t* ctrl, const srslte_hip_dl_ctrl_tx_in_t* in)
+{
+  const int r = dl_tx_ctrl_check(q, nof_sf, grants, nof_grants, ctrl, in);
+  if (r) hip_log("[srslte_hip] dl_tx grants2: the control region is refused (another cell, a grant's cfi that is not its subframe's, or its own inputs)\n");
+  return r;
+}
+
+extern "C" int srslte_hip_dl_tx_batch_grants2(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
+                                              const srslte_hip_dl_tx_grant2_t* grants, uint32_t nof_grants, void* d_iq, void* stream)
+{
+  if (int r = dl_tx_grants2_check(q, d_tb, nof_sf, grants, nof_grants, d_iq)) return r;
+  return dl_tx_batch_grants(q, d_tb, tb_stride, tti0, nof_sf, grants, nof_grants, true, nullptr, nullptr, d_iq, stream);
+}
+
+extern "C" int srslte_hip_dl_tx_batch_grants2_ctrl(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
+                                                   const srslte_hip_dl_tx_grant2_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
+                                                   const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream)
+{
+  if (int r = dl_tx_grants2_check(q, d_tb, nof_sf, grants, nof_grants, d_iq)) return r;
+  if (int r = dl_tx_grants2_ctrl_check(q, nof_sf, grants, nof_grants, ctrl, in)) return r;
+  return dl_tx_batch_grants(q, d_tb, tb_stride, tti0, nof_sf, grants, nof_grants, true, ctrl, in, d_iq, stream);
+}
+
+extern "C" int srslte_hip_dl_tx_batch_grants2_full(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
+                                                   const srslte_hip_dl_tx_grant2_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
+                                                   const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream)
+{
+  if (int r = dl_tx_grants2_check(q, d_tb, nof_sf, grants, nof_grants, d_iq)) return r;
+  if (int r = dl_tx_grants2_ctrl_check(q, nof_sf, grants, nof_grants, ctrl, in)) return r;
+  return dl_tx_batch_grants(q, d_tb, tb_stride, tti0, nof_sf, grants, nof_grants, true, ctrl, in, d_iq, stream, true);
 }
