@@ -1124,6 +1124,67 @@ int srslte_hip_csi_gen_cqi_periodic(const srslte_hip_csi_res_t* csi, srslte_hip_
 int srslte_hip_csi_gen_cqi_aperiodic(const srslte_hip_csi_res_t* csi, srslte_hip_csi_report_cfg_t* cfg, uint32_t wideband_value,
                                      srslte_hip_csi_report_t* out);
 
+/* ------------------------------------------------------------------ channel emulator (replaces srslte::channel::run, lib/src/phy/channel/channel.cc:124-186,
+ * over fading.c, delay.c, hst.c and rlf.c; the noise stage is this library's own). One object emulates nof_channels independent channels (a channel
+ * is a UE x port: channel.cc keeps one fading and one delay object per port) at one sample rate. One call processes nof_calls consecutive blocks of
+ * len samples per channel and equals nof_calls successive channel::run(in, out, len, t_i) calls, t_i = srslte_timestamp_add(t0, 0, i * len / srate);
+ * the fading filter's overlap, the delay line and the noise counter are carried on the device from block to block and from call to call.
+ *   fading: 36.104 B.2 EPA / EVA / ETU as fading.c:85-145,:249-275 computes them (N-point overlap-add filter, N = srslte_hip_channel_fft_size, a new
+ *           frequency response every N/4 samples, segments restarting at every block); channel c draws its coefficients from seed0 + c * seed_stride
+ *           (channel.cc: 0x1234 * port). The filter delays the signal by N/4 samples (srslte_hip_channel_path_delay): a receiver shifts its window by it.
+ *   delay:  delay.c:26-126, one delay per block, computed on the host as upstream does; a pure copy. A block must be at least as long as its delay.
+ *   hst:    hst.c:48-80, one Doppler shift per block, out[i] = in[i] exp(j 2 pi (-fs / srate) i), the phase restarting at 0 in every block as upstream.
+ *   rlf:    rlf.c:31-44, the block times 1.0f or 0.0f.
+ *   awgn:   complex noise of variance n0 per sample (n0 / 2 per component) from Philox-4x32-10 keyed by (awgn_seed, channel) with the sample's index
+ *           since creation or reset as counter, and Box-Muller: the noise does not depend on how a run is split into calls.
+ * Disabled stages cost nothing. Samples: d_in[c * in_ch_stride + i * in_call_stride + n], d_out likewise (strides in samples; d_out must not overlap
+ * d_in). Results are bit-reproducible from run to run (the overlap-add is a gather in a fixed order, no atomics). */
+typedef struct srslte_hip_channel srslte_hip_channel_t;
+enum { SRSLTE_HIP_CHANNEL_FADING_NONE = 0, SRSLTE_HIP_CHANNEL_FADING_EPA, SRSLTE_HIP_CHANNEL_FADING_EVA, SRSLTE_HIP_CHANNEL_FADING_ETU };
+#define SRSLTE_HIP_CHANNEL_MAXTAPS 9
+typedef struct {
+  double   srate_hz;
+  uint32_t nof_channels, max_calls, max_len; /* the largest nof_calls and len of a call */
+  int      fading_enable, fading_model;      /* SRSLTE_HIP_CHANNEL_FADING_*; the model string "etu300" is model ETU with doppler_hz 300 */
+  float    doppler_hz;
+  uint32_t seed0, seed_stride;
+  int      delay_enable;
+  float    delay_min_us, delay_max_us, delay_period_s, delay_init_time_s;
+  int      hst_enable;
+  float    hst_fd_hz, hst_period_s, hst_init_time_s;
+  int      rlf_enable;
+  uint32_t rlf_t_on_ms, rlf_t_off_ms;
+  int      awgn_enable;
+  float    awgn_n0;
+  uint32_t awgn_seed;
+} srslte_hip_channel_cfg_t;
+/* Refused with SRSLTE_ERROR_INVALID_INPUTS and a message: null pointers, no channels, a rate or a model out of range, fading enabled with model NONE
+ * (upstream leaves its N undefined), a delay or RLF period of zero, a negative n0; at run time nof_calls > max_calls, len > max_len or a block
+ * shorter than its delay. */
+int  srslte_hip_channel_create(srslte_hip_channel_t** q, const srslte_hip_channel_cfg_t* cfg);
+void srslte_hip_channel_destroy(srslte_hip_channel_t* q);
+int  srslte_hip_channel_reset(srslte_hip_channel_t* q); /* the state of a new object: no overlap, an empty delay line, noise counter 0 */
+int  srslte_hip_channel_run_batch(srslte_hip_channel_t* q, const void* d_in, uint64_t in_ch_stride, uint64_t in_call_stride, void* d_out,
+                                  uint64_t out_ch_stride, uint64_t out_call_stride, uint32_t nof_calls, uint32_t len, int64_t t_full_secs,
+                                  double t_frac_secs, void* stream);
+int  srslte_hip_channel_fft_size(const srslte_hip_channel_t* q);   /* N; 0 without fading */
+int  srslte_hip_channel_path_delay(const srslte_hip_channel_t* q); /* N / 4; 0 without fading */
+/* TEST AND DIAGNOSTIC ENTRIES (no device needed but for _coeffs' object): the drawn coefficients of a channel (returns the number of taps), the draw
+ * itself, N for a model and rate, and the per-block figures the host computes for block i of a call starting at (t_full_secs, t_frac_secs) */
+int srslte_hip_channel_coeffs(const srslte_hip_channel_t* q, uint32_t channel, double a[SRSLTE_HIP_CHANNEL_MAXTAPS], double w[SRSLTE_HIP_CHANNEL_MAXTAPS],
+                              double p[SRSLTE_HIP_CHANNEL_MAXTAPS]);
+int srslte_hip_channel_draw_coeffs(int fading_model, float doppler_hz, uint32_t seed, double a[SRSLTE_HIP_CHANNEL_MAXTAPS],
+                                   double w[SRSLTE_HIP_CHANNEL_MAXTAPS], double p[SRSLTE_HIP_CHANNEL_MAXTAPS]);
+int srslte_hip_channel_fft_size_for(int fading_model, double srate_hz);
+typedef struct {
+  double   t;             /* full + frac seconds of the block's timestamp: the fading filter's time */
+  uint32_t delay_samples; /* delay.c:26-47 */
+  float    hst_fs_hz;     /* hst.c:52-75 */
+  int      rlf_on;        /* rlf.c:34-39 */
+} srslte_hip_channel_block_t;
+int srslte_hip_channel_block_params(const srslte_hip_channel_cfg_t* cfg, uint32_t len, uint32_t i, int64_t t_full_secs, double t_frac_secs,
+                                    srslte_hip_channel_block_t* out);
+
 #ifdef __cplusplus
 }
 #endif
