@@ -1138,7 +1138,7 @@ int srslte_hip_csi_gen_cqi_aperiodic(const srslte_hip_csi_res_t* csi, srslte_hip
  *   awgn:   complex noise of variance n0 per sample (n0 / 2 per component) from Philox-4x32-10 keyed by (awgn_seed, channel) with the sample's index
  *           since creation or reset as counter, and Box-Muller: the noise does not depend on how a run is split into calls.
  * Disabled stages cost nothing. Samples: d_in[c * in_ch_stride + i * in_call_stride + n], d_out likewise (strides in samples; d_out must not overlap
- * d_in). Results are bit-reproducible from run to run (the overlap-add is a gather in a fixed order, no atomics). */
+ * d_in; a call stride is at least len; in_ch_stride may be 0: one transmitted signal through every channel). Results are bit-reproducible from run to run (the overlap-add is a gather in a fixed order, no atomics). */
 typedef struct srslte_hip_channel srslte_hip_channel_t;
 enum { SRSLTE_HIP_CHANNEL_FADING_NONE = 0, SRSLTE_HIP_CHANNEL_FADING_EPA, SRSLTE_HIP_CHANNEL_FADING_EVA, SRSLTE_HIP_CHANNEL_FADING_ETU };
 #define SRSLTE_HIP_CHANNEL_MAXTAPS 9
@@ -1158,8 +1158,8 @@ typedef struct {
   float    awgn_n0;
   uint32_t awgn_seed;
 } srslte_hip_channel_cfg_t;
-/* Refused with SRSLTE_ERROR_INVALID_INPUTS and a message: null pointers, no channels, a rate or a model out of range, fading enabled with model NONE
- * (upstream leaves its N undefined), a delay or RLF period of zero, a negative n0; at run time nof_calls > max_calls, len > max_len or a block
+/* Refused with SRSLTE_ERROR_INVALID_INPUTS and a message: null pointers, no channels, a rate or a model out of range (a rate at which the model's filter would
+ * be longer than 1024 points included: ETU at 61.44 MHz), fading enabled with model NONE (upstream leaves its N undefined), a delay or RLF period of zero, a negative n0; at run time nof_calls > max_calls, len > max_len or a block
  * shorter than its delay. */
 int  srslte_hip_channel_create(srslte_hip_channel_t** q, const srslte_hip_channel_cfg_t* cfg);
 void srslte_hip_channel_destroy(srslte_hip_channel_t* q);

@@ -33,13 +33,21 @@ CASES = {
     "rlf": dict(srate=1.92e6, channels=1, len=64, rlf=(50, 30), calls=[(0, 0.04995, 3), (0, 0.0799, 2)]),
     "chain": dict(srate=1.92e6, channels=1, len=480, fading="epa5", delay=(10.0, 100.0, 1.0, 0.0), hst=(750.0, 7.2, 0.0), rlf=(50, 30),
                   calls=[(0, 0.0495, 3), (1, 0.7995, 2)]),
+    # N = 128 (three radix-4 passes and a closing radix-2 pass), the 50-PRB rate; 700 is no multiple of 32: a short last segment in every block,
+    # and the second call starts where the first ends, so the overlap crosses a call boundary
+    "fading_eva5_n128": dict(srate=7.68e6, channels=2, len=700, fading="eva5", calls=[(3, 0.5, 3), (3, 0.5 + 3 * 700 / 7.68e6, 2)]),
+    # N = 256 (four radix-4 passes) with the nine taps of ETU; blocks shorter than a segment of 64: the overlap accumulates over more than five blocks
+    "fading_etu70_n256": dict(srate=7.68e6, channels=2, len=50, fading="etu70", calls=[(1, 0.75, 14)]),
 }
+# A case's input seed is 1000 + its position here: the first seven in the sorted order they were recorded with, later cases appended (never
+# inserted), so that adding a case leaves the recorded inputs and outputs of the others as they are
+SEED_ORDER = ("chain", "delay", "fading_epa5_n64", "fading_etu300_n1024", "fading_eva70_n512", "hst", "rlf", "fading_eva5_n128", "fading_etu70_n256")
 
 
 def case_input(name):
     """[call] -> [channels][blocks][len] complex64, unit power, from the case's own seed."""
     c = CASES[name]
-    rng = np.random.default_rng(sorted(CASES).index(name) + 1000)
+    rng = np.random.default_rng(SEED_ORDER.index(name) + 1000)
     return [((rng.standard_normal((c["channels"], nb, c["len"])) + 1j * rng.standard_normal((c["channels"], nb, c["len"]))) / np.sqrt(2)).astype(np.complex64)
             for (_, _, nb) in c["calls"]]
 

@@ -2,9 +2,9 @@
 reference's own sources (tests/golden/channel.npz), the coefficient draw against libsrslte_ref.so, and the library's host functions
 (filter size, draw, per-block delay / Doppler shift / gate) against both.
 
-Measured distance restatement <-> recorded reference, |a - b| / max(|b|, rms(b)): epa5 N=64 3.9e-6, eva70 N=512 3.2e-5, etu300 N=1024 7.3e-5
-(upstream builds the frequency response with a recursive oscillator over N steps), HST over 960 samples 2.9e-6, the full chain 5.5e-6; delay
-and RLF 0. All inside the project's 1e-4 rule, which is asserted here."""
+Measured distance restatement <-> recorded reference, |a - b| / max(|b|, rms(b)): epa5 N=64 3.9e-6, eva5 N=128 9.0e-6, etu70 N=256 2.5e-5,
+eva70 N=512 3.2e-5, etu300 N=1024 7.3e-5 (upstream builds the frequency response with a recursive oscillator over N steps), HST over 960
+samples 2.9e-6, the full chain 5.5e-6; delay and RLF 0. All inside the project's 1e-4 rule, which is asserted here."""
 import ctypes as C
 import importlib
 import struct
@@ -15,7 +15,7 @@ import pytest
 import channel_ref as R
 from _libs import ref
 from gen_golden_channel import CASES, GOLDEN, case_input
-from test_gpu_channel import LOOPBACK_NSF, LOOPBACK_TBS, LOOPBACK_TTI0
+from test_gpu_channel import LOOPBACK_NSF, LOOPBACK_TBS, LOOPBACK_TTI0, UL_LOOPBACK, ul_loopback_payload
 
 TOL = 1e-4
 
@@ -104,6 +104,16 @@ def test_fft_size_table(hp):
     assert hp.channel_fft_size_for(0, 1.92e6) == hp.SRSLTE_ERROR_INVALID_INPUTS and hp.channel_fft_size_for(9, 1.92e6) == hp.SRSLTE_ERROR_INVALID_INPUTS
 
 
+def test_fft_sizes_of_the_25_and_50_prb_cells_and_beyond_the_largest_filter(hp):
+    """The rates at which the 128- and 256-point filters run, and one whose size no filter covers: create refuses it before it touches a device."""
+    for model, srate, n in ((2, 5.76e6, 128), (2, 7.68e6, 128), (3, 3.84e6, 128), (1, 30.72e6, 128), (3, 5.76e6, 256), (3, 7.68e6, 256),
+                            (2, 15.36e6, 256), (3, 61.44e6, 2048)):
+        assert R.fft_size(model, srate) == n and hp.channel_fft_size_for(model, srate) == n
+    h = C.c_void_p()
+    cfg = hp.channel_cfg(61.44e6, 1, 1, 1920, fading="etu70")
+    assert hp.lib().srslte_hip_channel_create(C.byref(h), C.byref(cfg)) == hp.SRSLTE_ERROR_INVALID_INPUTS and not h.value
+
+
 def test_delay_bookkeeping_over_a_full_period(hp, golden):
     """The per-block delay of the library's host code equals the restatement's over a whole period (the recorded delays pin the restatement);
     and the FIFO against the closed form the device uses: the history is the last d samples, zeros go behind it, the oldest are dropped."""
@@ -154,3 +164,23 @@ def test_loopback_precondition():
     for b in range(LOOPBACK_NSF):
         r = oracle_rx(cfg, y[ch.path_delay + b * cfg.sf_len:][:cfg.sf_len], LOOPBACK_TTI0 + b)
         assert r["ok"] and np.array_equal(r["tb"][:LOOPBACK_TBS // 8], data[b])
+
+
+def test_ul_loopback_precondition():
+    """What tests/test_gpu_channel.py::test_loopback_ul_tx_channel_ul_rx_n128 relies on: a 10-PRB QPSK PUSCH of a 25-PRB cell through the
+    restatement's EVA5 channel at the cell's own rate (N = 128), read at offset path_delay, decodes in the oracle's uplink receiver for every
+    subframe of that test."""
+    from lte_sim import UlConfig, make_ul_subframe, oracle_ul_rx
+    u = UL_LOOPBACK
+    cfg = UlConfig(u["prb"], u["cell_id"], u["mod"], u["tbs"], u["L_prb"], u["n_prb"])
+    payload = ul_loopback_payload()
+    rng = np.random.default_rng(0)  # not drawn from: the payload is given and no noise is added
+    x = np.zeros((1, u["nsf"] + 1, cfg.sf_len), np.complex64)
+    for b in range(u["nsf"]):
+        x[0, b] = make_ul_subframe(cfg, u["tti0"] + b, rng, data=payload[b])[0]
+    ch = R.ChannelRef(u["srate"], 1, fading=u["fading"])
+    assert cfg.sf_len * 1000 == u["srate"] and ch.N == 128 and ch.path_delay == 32
+    y = ch.run(x, 0, 0.0).reshape(-1).astype(np.complex64)
+    for b in range(u["nsf"]):
+        r = oracle_ul_rx(cfg, y[ch.path_delay + b * cfg.sf_len:][:cfg.sf_len], u["tti0"] + b)
+        assert r["ok"] and np.array_equal(r["tb"][:u["tbs"] // 8], payload[b])
