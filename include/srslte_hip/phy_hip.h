@@ -1185,6 +1185,90 @@ typedef struct {
 int srslte_hip_channel_block_params(const srslte_hip_channel_cfg_t* cfg, uint32_t len, uint32_t i, int64_t t_full_secs, double t_frac_secs,
                                     srslte_hip_channel_block_t* out);
 
+/* ------------------------------------------------------------------ UL sounding reference signal, FDD (UE transmit, eNB sounding and timing)
+ * srslte_hip_srs_tx_put writes what srslte_refsignal_srs_gen + srslte_refsignal_srs_put write (refsignal_ul.c:987-1026) for a list of
+ * (subframe, UE) entries in one launch: r[i] into grid[sf][nsym-1][k0 + 2 i], i < M_sc, with M_sc = 6 m_srs_b[B][bw_cfg] (Tables
+ * 5.5.3.2-1..4 of 36.211), k0 of srs_k0_ue (:919-941, frequency hopping for b > b_hop with n_srs = tti / T_srs, srs_Fb :896-916) and
+ * r = exp(j (arg r_uv(i) + alpha i)), alpha = 2 pi n_srs / 8, u taken with delta_ss = 0, v = v_pusch[ns][delta_ss] when M_sc / 12 >= 6 and
+ * sequence hopping is on. Only the SRS REs are written. The call always writes: whether TTI tti0 + sf is an SRS occasion is the caller's
+ * decision, made with srslte_hip_srs_send_cs / _send_ue (the division of srs_tx_enabled and the put in ue_ul.c:283-291).
+ * Three things are the reference's and are kept: (1) the symbol, which lies in the subframe's second slot, carries the sequence of the
+ * FIRST slot (r_srs[i], not r_srs[M_sc + i]); with group hopping on that is not 36.211's sequence; (2) srslte_hip_srs_send_ue computes
+ * (tti - T_offset) % T_srs in uint32_t, so for tti < T_offset the answer is that of 2^32 + tti - T_offset; (3) the comparisons of
+ * srslte_hip_srs_pusch_shortened are those of :769-814 as written (an allocation whose last PRB lies just below the cell's sounding
+ * band counts as overlapping it: n_prb + L_prb >= start is tested, not >).
+ * srslte_hip_srs_rx_batch is this library's own (the reference has no SRS receiver): one launch, one workgroup per request, no scratch memory.
+ * With y[i] = grid[sf][nsym-1][k0 + 2 i], z[i] = y[i] conj(r[i]) and J = M_sc / 8 blocks (M_sc is a multiple of 24; J <= 72):
+ *   Z_j[k] = 1/8 sum_{i<8} z[8 j + i] exp(-j 2 pi k i / 8), k = 0..7: bin k holds the UE whose cyclic shift is (n_srs + k) % 8
+ *   h_j = Z_j[0] -> d_ce[req][j] (rows of SRSLTE_HIP_SRS_MAX_CE, entries from J on are left alone); nof_ce = J
+ *   free bins F = {k != 0 : bit (n_srs + k) % 8 of cs_used clear}; noise_estimate = 8 mean_{j, k in F} |Z_j[k]|^2, 0 when F is empty
+ *   rsrp = mean_j |h_j|^2; snr = rsrp / noise_estimate, NaN when noise_estimate is 0; snr_db = 10 log10(snr); noise_estimate_dbm =
+ *   10 log10(noise_estimate) + 30 (the conventions of chest_ul.c:317-321)
+ *   ta_us = -arg(sum_{j<J-1} h_{j+1} conj(h_j)) / (2 pi 16 15e3) 1e6: blocks are 16 subcarriers apart, unambiguous within +-2.08 us
+ * Both calls queue their work on the caller's stream with no host synchronisation (descriptors through pinned buffers); the sequence tables
+ * of each (M_sc, n_srs) are made on the host on first use and kept on the device. Grids are [nof_sf][nsym][12 nof_prb] (nsym 14 / 12), one
+ * antenna; subframe b is TTI tti0 + b. d_res and d_ce may be device-visible pinned host memory.
+ * srslte_hip_srs_create returns NULL for a cell outside 6-110 PRB, TDD, subframe_config >= 15, bw_cfg >= 8 and a bw_cfg whose
+ * m_srs_b[0][bw_cfg] exceeds nof_prb (6 PRB with bw_cfg < 7: the reference then computes a negative k0 in unsigned arithmetic and writes
+ * outside the grid). A call returns SRSLTE_ERROR_INVALID_INPUTS before anything is queued for B > 3, b_hop > 3, n_srs > 7, k_tc > 1,
+ * I_srs >= 637, n_rrc > 23, sf >= nof_sf, nof > max_srs.
+ * Not here: TDD and UpPTS, aperiodic (DCI-triggered) SRS, antenna selection, several receive antennas, and the single-call drop-in, whose
+ * refsignal_ul.c remains the reference's. */
+#define SRSLTE_HIP_SRS_MAX_CE 72    /* M_sc / 8 at 96 PRB */
+typedef struct srslte_hip_srs srslte_hip_srs_t;
+typedef struct {
+  uint32_t nof_prb, cell_id;
+  int      cp_ext;                  /* srslte_cell_t.cp == SRSLTE_CP_EXT */
+  uint32_t subframe_config;         /* 0-14: srs-SubframeConfig (Table 5.5.3.3-1) */
+  uint32_t bw_cfg;                  /* 0-7: srs-BandwidthConfig C_SRS */
+  int      group_hopping_en, sequence_hopping_en; /* srslte_refsignal_dmrs_pusch_cfg_t, which the SRS sequence shares */
+  uint32_t delta_ss;                /* 0-29; selects v only (u is taken with delta_ss = 0) */
+  uint32_t max_srs;                 /* entries per call */
+  int      tdd;                     /* refused */
+} srslte_hip_srs_cfg_t;
+typedef struct {                    /* one (subframe, UE): srslte_refsignal_srs_cfg_t's UE-specific part */
+  uint32_t sf;                      /* 0 .. nof_sf-1 */
+  uint32_t B, b_hop;                /* 0-3: srs-Bandwidth, srs-HoppingBandwidth */
+  uint32_t n_srs;                   /* 0-7: cyclic shift */
+  uint32_t I_srs;                   /* 0-636: srs-ConfigIndex (36.213 Table 8.2-1) */
+  uint32_t k_tc;                    /* 0, 1: transmission comb */
+  uint32_t n_rrc;                   /* 0-23: freqDomainPosition */
+  uint32_t cs_used;                 /* receive only: bit c set = some UE uses cyclic shift c on these REs in that subframe (own bit implied) */
+} srslte_hip_srs_ue_t;
+typedef struct {                    /* per request */
+  float    rsrp, noise_estimate, noise_estimate_dbm, snr, snr_db, ta_us;
+  uint32_t nof_ce;                  /* J: entries of the request's d_ce row that were written */
+} srslte_hip_srs_res_t;
+srslte_hip_srs_t* srslte_hip_srs_create(const srslte_hip_srs_cfg_t* cfg);
+void              srslte_hip_srs_destroy(srslte_hip_srs_t* q);
+/* d_grid [nof_sf][nsym][12 nof_prb] */
+int srslte_hip_srs_tx_put(srslte_hip_srs_t* q, uint32_t tti0, uint32_t nof_sf, const srslte_hip_srs_ue_t* list, uint32_t nof, void* d_grid, void* stream);
+/* d_res [nof]; d_ce [nof][SRSLTE_HIP_SRS_MAX_CE] cf32 */
+int srslte_hip_srs_rx_batch(srslte_hip_srs_t* q, const void* d_grid, uint32_t tti0, uint32_t nof_sf, const srslte_hip_srs_ue_t* list, uint32_t nof,
+                            srslte_hip_srs_res_t* d_res, void* d_ce, void* stream);
+/* srslte_hip_ul_rx_batch_grants_pucch plus the SRS requests of srs_list, read from the pipeline's own grid right after its SC-FDMA
+ * demodulation. ctrl and srs may each be NULL (then their lists are not looked at); objects given must be made for the receiver's cell. */
+int srslte_hip_ul_rx_batch_grants_pucch_srs(srslte_hip_ul_rx_t* q, const void* d_iq, uint32_t tti0, uint32_t nof_sf, const srslte_hip_ul_grant_t* grants,
+                                            uint32_t nof_grants, uint8_t* d_tb, uint32_t tb_stride, uint8_t* d_tb_ok, srslte_hip_ul_ctrl_t* ctrl,
+                                            const srslte_hip_pucch_req_t* reqs, uint32_t nof_pucch, srslte_hip_pucch_res_t* d_res, srslte_hip_srs_t* srs,
+                                            const srslte_hip_srs_ue_t* srs_list, uint32_t nof_srs, srslte_hip_srs_res_t* d_srs_res, void* d_srs_ce,
+                                            void* stream);
+/* host helpers (no device needed). srslte_refsignal_srs_send_cs / _send_ue (1, 0, or < 0 for invalid input); _rb_start_cs / _rb_L_cs
+ * (:881-894); M_sc and k0 of a UE at a TTI (0 where srs_k0_ue gives 0); the two shortened decisions (:750-814; ue NULL / ue_configured 0:
+ * srs_cfg->configured false; format: srslte_pucch_format_t, 0-2 are formats 1 / 1a / 1b); srslte_refsignal_srs_gen into r [2][M_sc] cf32;
+ * srslte_hip_srs_check: what create (list NULL, nof 0) and a call with this list would refuse, SRSLTE_SUCCESS otherwise. */
+int      srslte_hip_srs_send_cs(uint32_t subframe_config, uint32_t sf_idx);
+int      srslte_hip_srs_send_ue(uint32_t I_srs, uint32_t tti);
+uint32_t srslte_hip_srs_rb_start_cs(uint32_t bw_cfg, uint32_t nof_prb);
+uint32_t srslte_hip_srs_rb_L_cs(uint32_t bw_cfg, uint32_t nof_prb);
+uint32_t srslte_hip_srs_M_sc(const srslte_hip_srs_cfg_t* cfg, const srslte_hip_srs_ue_t* ue);
+uint32_t srslte_hip_srs_k0(const srslte_hip_srs_cfg_t* cfg, const srslte_hip_srs_ue_t* ue, uint32_t tti);
+int      srslte_hip_srs_pusch_shortened(const srslte_hip_srs_cfg_t* cfg, const srslte_hip_srs_ue_t* ue, uint32_t tti, const uint32_t n_prb_tilde[2],
+                                        uint32_t L_prb);
+int      srslte_hip_srs_pucch_shortened(const srslte_hip_srs_cfg_t* cfg, int ue_configured, int simul_ack, uint32_t format, uint32_t tti);
+int      srslte_hip_srs_gen(const srslte_hip_srs_cfg_t* cfg, const srslte_hip_srs_ue_t* ue, uint32_t sf_idx, void* r);
+int      srslte_hip_srs_check(const srslte_hip_srs_cfg_t* cfg, uint32_t tti0, uint32_t nof_sf, const srslte_hip_srs_ue_t* list, uint32_t nof);
+
 #ifdef __cplusplus
 }
 #endif

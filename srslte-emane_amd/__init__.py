@@ -141,6 +141,7 @@ def lib():
         _bind_prach(L)
         _bind_csi(L)
         _bind_channel(L)
+        _bind_srs(L)
         _lib = L
     return _lib
 
@@ -2064,3 +2065,181 @@ class Channel:
         if self.h:
             lib().srslte_hip_channel_destroy(self.h)
             self.h = None
+
+
+# ---------------------------------------------------------------- UL sounding reference signal (phy_hip.h "UL sounding reference signal")
+SRS_MAX_CE = 72
+
+
+class SrsCfg(C.Structure):
+    """srslte_hip_srs_cfg_t: the cell, its SRS subframe and bandwidth configuration, the sequence hopping switches and the entries per call."""
+    _fields_ = [("nof_prb", C.c_uint32), ("cell_id", C.c_uint32), ("cp_ext", C.c_int), ("subframe_config", C.c_uint32), ("bw_cfg", C.c_uint32),
+                ("group_hopping_en", C.c_int), ("sequence_hopping_en", C.c_int), ("delta_ss", C.c_uint32), ("max_srs", C.c_uint32), ("tdd", C.c_int)]
+
+
+class SrsUe(C.Structure):
+    """srslte_hip_srs_ue_t: one (subframe, UE)."""
+    _fields_ = [("sf", C.c_uint32), ("B", C.c_uint32), ("b_hop", C.c_uint32), ("n_srs", C.c_uint32), ("I_srs", C.c_uint32), ("k_tc", C.c_uint32),
+                ("n_rrc", C.c_uint32), ("cs_used", C.c_uint32)]
+
+    @classmethod
+    def make(cls, sf, B=0, b_hop=3, n_srs=0, I_srs=0, k_tc=0, n_rrc=0, cs_used=0):
+        return cls(sf, B, b_hop, n_srs, I_srs, k_tc, n_rrc, cs_used)
+
+
+class SrsRes(C.Structure):
+    """srslte_hip_srs_res_t."""
+    _fields_ = [("rsrp", C.c_float), ("noise_estimate", C.c_float), ("noise_estimate_dbm", C.c_float), ("snr", C.c_float), ("snr_db", C.c_float),
+                ("ta_us", C.c_float), ("nof_ce", C.c_uint32)]
+
+
+def _bind_srs(L):
+    vp, u32, cp, up = C.c_void_p, C.c_uint32, C.POINTER(SrsCfg), C.POINTER(SrsUe)
+    L.srslte_hip_srs_create.restype = vp
+    L.srslte_hip_srs_create.argtypes = [cp]
+    L.srslte_hip_srs_destroy.argtypes = [vp]
+    L.srslte_hip_srs_tx_put.argtypes = [vp, u32, u32, vp, u32, vp, vp]
+    L.srslte_hip_srs_rx_batch.argtypes = [vp, vp, u32, u32, vp, u32, vp, vp, vp]
+    L.srslte_hip_ul_rx_batch_grants_pucch_srs.argtypes = [vp, vp, u32, u32, vp, u32, vp, u32, vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp]
+    L.srslte_hip_srs_send_cs.argtypes = [u32, u32]
+    L.srslte_hip_srs_send_ue.argtypes = [u32, u32]
+    for fn in (L.srslte_hip_srs_rb_start_cs, L.srslte_hip_srs_rb_L_cs):
+        fn.restype, fn.argtypes = u32, [u32, u32]
+    L.srslte_hip_srs_M_sc.restype, L.srslte_hip_srs_M_sc.argtypes = u32, [cp, up]
+    L.srslte_hip_srs_k0.restype, L.srslte_hip_srs_k0.argtypes = u32, [cp, up, u32]
+    L.srslte_hip_srs_pusch_shortened.argtypes = [cp, up, u32, C.POINTER(u32 * 2), u32]
+    L.srslte_hip_srs_pucch_shortened.argtypes = [cp, C.c_int, C.c_int, u32, u32]
+    L.srslte_hip_srs_gen.argtypes = [cp, up, u32, vp]
+    L.srslte_hip_srs_check.argtypes = [cp, u32, u32, vp, u32]
+    return L
+
+
+def srs_cfg(nof_prb, cell_id, bw_cfg, subframe_config=0, cp_ext=False, group_hopping_en=False, sequence_hopping_en=False, delta_ss=0, max_srs=1,
+            tdd=False):
+    return SrsCfg(nof_prb, cell_id, 1 if cp_ext else 0, subframe_config, bw_cfg, 1 if group_hopping_en else 0, 1 if sequence_hopping_en else 0, delta_ss,
+                  max_srs, 1 if tdd else 0)
+
+
+def srs_send_cs(subframe_config, sf_idx):
+    return _bind_srs(lib()).srslte_hip_srs_send_cs(subframe_config, sf_idx)
+
+
+def srs_send_ue(I_srs, tti):
+    return _bind_srs(lib()).srslte_hip_srs_send_ue(I_srs, tti)
+
+
+def srs_rb_start_cs(bw_cfg, nof_prb):
+    return _bind_srs(lib()).srslte_hip_srs_rb_start_cs(bw_cfg, nof_prb)
+
+
+def srs_rb_L_cs(bw_cfg, nof_prb):
+    return _bind_srs(lib()).srslte_hip_srs_rb_L_cs(bw_cfg, nof_prb)
+
+
+def srs_M_sc(cfg, ue):
+    return _bind_srs(lib()).srslte_hip_srs_M_sc(C.byref(cfg), C.byref(ue))
+
+
+def srs_k0(cfg, ue, tti):
+    return _bind_srs(lib()).srslte_hip_srs_k0(C.byref(cfg), C.byref(ue), tti)
+
+
+def srs_pusch_shortened(cfg, ue, tti, n_prb_tilde, L_prb):
+    """srslte_refsignal_srs_pusch_shortened (host); ue None: no UE-specific SRS configured."""
+    n = (C.c_uint32 * 2)(*n_prb_tilde)
+    return _bind_srs(lib()).srslte_hip_srs_pusch_shortened(C.byref(cfg), C.byref(ue) if ue is not None else None, tti, C.byref(n), L_prb)
+
+
+def srs_pucch_shortened(cfg, ue_configured, simul_ack, fmt, tti):
+    return _bind_srs(lib()).srslte_hip_srs_pucch_shortened(C.byref(cfg), 1 if ue_configured else 0, 1 if simul_ack else 0, fmt, tti)
+
+
+def srs_gen(cfg, ue, sf_idx):
+    """srslte_refsignal_srs_gen -> [2][M_sc] complex64 (host; no GPU)."""
+    M = srs_M_sc(cfg, ue)
+    r = np.zeros(2 * max(M, 1), np.complex64)
+    _check(lib().srslte_hip_srs_gen(C.byref(cfg), C.byref(ue), sf_idx, r.ctypes.data), "srs_gen")
+    return r.reshape(2, -1)
+
+
+def srs_check(cfg, tti0, nof_sf, ues):
+    """What srslte_hip_srs_create and a call with this list would answer, without a device."""
+    arr = (SrsUe * max(1, len(ues)))(*ues)
+    return _bind_srs(lib()).srslte_hip_srs_check(C.byref(cfg), tti0, nof_sf, arr, len(ues))
+
+
+class Srs:
+    """Batched SRS: srslte_refsignal_srs_put on UE grids and the eNB's sounding receiver."""
+
+    def __init__(self, nof_prb, cell_id, bw_cfg, max_srs=1, **kw):
+        L = _bind_srs(lib())
+        self.cfg = srs_cfg(nof_prb, cell_id, bw_cfg, max_srs=max_srs, **kw)
+        self.h = L.srslte_hip_srs_create(C.byref(self.cfg))
+        if not self.h:
+            raise RuntimeError("srslte_hip_srs_create failed")
+        self.grid_len = (12 if self.cfg.cp_ext else 14) * 12 * nof_prb
+
+    def put_device(self, d_grid, tti0, nof_sf, ues, stream=None):
+        arr = (SrsUe * max(1, len(ues)))(*ues)
+        return lib().srslte_hip_srs_tx_put(self.h, tti0, nof_sf, arr, len(ues), d_grid, stream)
+
+    def put(self, grid, tti0, ues):
+        """grid [nof_sf][grid_len] complex64 (host) -> (rc, the grids after the call)."""
+        g = np.ascontiguousarray(grid, np.complex64).reshape(-1, self.grid_len)
+        d = DevBuf.from_host(g)
+        rc = self.put_device(d.ptr, tti0, g.shape[0], ues)
+        sync()
+        return rc, d.to_host(np.complex64).reshape(g.shape)
+
+    def rx_device(self, d_grid, tti0, nof_sf, ues, d_res, d_ce, stream=None):
+        arr = (SrsUe * max(1, len(ues)))(*ues)
+        return lib().srslte_hip_srs_rx_batch(self.h, d_grid, tti0, nof_sf, arr, len(ues), d_res, d_ce, stream)
+
+    @staticmethod
+    def read(d_res, d_ce, nof):
+        """-> ([SrsRes], ce [nof][SRS_MAX_CE] complex64; entries from nof_ce on are whatever the buffer held)."""
+        out = (SrsRes * max(1, nof))()
+        _check(lib().srslte_hip_memcpy_d2h(C.addressof(out), d_res.ptr, C.sizeof(out)), "memcpy_d2h")
+        return list(out)[:nof], d_ce.to_host(np.complex64).reshape(-1, SRS_MAX_CE)[:nof]
+
+    def rx(self, grid, tti0, ues):
+        """grid [nof_sf][grid_len] complex64 -> (rc, [SrsRes] or None, ce or None)."""
+        g = np.ascontiguousarray(grid, np.complex64).reshape(-1, self.grid_len)
+        n = max(1, len(ues))
+        dg, dr, dc = DevBuf.from_host(g), DevBuf(C.sizeof(SrsRes) * n), DevBuf(8 * SRS_MAX_CE * n)
+        rc = self.rx_device(dg.ptr, tti0, g.shape[0], ues, dr.ptr, dc.ptr)
+        if rc != SRSLTE_SUCCESS:
+            return rc, None, None
+        sync()
+        return (rc,) + self.read(dr, dc, len(ues))
+
+    def free(self):
+        if self.h:
+            lib().srslte_hip_srs_destroy(self.h)
+            self.h = None
+
+
+def _ul_rx_decode_grants_pucch_srs(self, iq, tti0, grants, ctrl, reqs, srs, ues):
+    """srslte_hip_ul_rx_batch_grants_pucch_srs: (rc, tb, tb_ok, [PucchRes], [SrsRes], ce); ctrl and srs may each be None."""
+    x = np.ascontiguousarray(iq, np.complex64).reshape(-1, self.sf_len)
+    din = DevBuf.from_host(x)
+    garr = (UlGrant * max(1, len(grants)))(*grants)
+    rarr = (PucchReq * max(1, len(reqs)))(*reqs)
+    uarr = (SrsUe * max(1, len(ues)))(*ues)
+    dres = DevBuf(C.sizeof(PucchRes) * max(1, len(reqs)))
+    dsr, dsc = DevBuf(C.sizeof(SrsRes) * max(1, len(ues))), DevBuf(8 * SRS_MAX_CE * max(1, len(ues)))
+    rc = _bind_srs(lib()).srslte_hip_ul_rx_batch_grants_pucch_srs(self.h, din.ptr, tti0, x.shape[0], garr, len(grants), self.d_tb.ptr, self.tb_stride,
+                                                                   self.d_ok.ptr, ctrl.h if ctrl is not None else None, rarr, len(reqs), dres.ptr,
+                                                                   srs.h if srs is not None else None, uarr, len(ues), dsr.ptr, dsc.ptr, None)
+    if rc != SRSLTE_SUCCESS:
+        return rc, None, None, None, None, None
+    sync()
+    self.last_nof_grants = len(grants)
+    out = (PucchRes * max(1, len(reqs)))()
+    _check(lib().srslte_hip_memcpy_d2h(C.addressof(out), dres.ptr, C.sizeof(out)), "memcpy_d2h")
+    tb = self.d_tb.to_host(np.uint8).reshape(self.rows, self.tb_stride)[:len(grants)]
+    sres, sce = Srs.read(dsr, dsc, len(ues))
+    return rc, tb, self.d_ok.to_host(np.uint8)[:len(grants)], list(out)[:len(reqs)], sres, sce
+
+
+UlRx.decode_grants_pucch_srs = _ul_rx_decode_grants_pucch_srs

@@ -1103,6 +1103,30 @@ void ul_r_uv_arg_1prb(uint32_t u, float* arg)
   for (int i = 0; i < 12; i++) arg[i] = (float)((2 * (PHI_12[u][i] - '0') - 3) * M_PI / 4);
 }
 
+// compute_r_uv_arg (refsignal_ul.c:285-293) for the SRS generator (srs_host.cpp): the argument of the base sequence r_uv of nof_prb PRB, the two
+// QPSK tables below 3 PRB (:143-147, :251-255), get_q and arg_r_uv_mprb from there on (:257-283), with the reference's float / double mix
+void ul_r_uv_arg(uint32_t nof_prb, uint32_t u, uint32_t v, float* arg)
+{
+  const uint32_t M_sc = 12 * nof_prb;
+  if (nof_prb < 3) {
+    for (uint32_t i = 0; i < M_sc; i++) arg[i] = (float)((2 * ((nof_prb == 1 ? PHI_12 : PHI_24)[u][i] - '0') - 3) * M_PI / 4);
+    return;
+  }
+  const uint32_t N_sz = largest_prime_below(M_sc);
+  const float    n_sz = (float)N_sz, q_hat = n_sz * (u + 1) / 31;
+  float          qf;
+  if ((((uint32_t)(2 * q_hat)) % 2) == 0) {
+    qf = (float)(q_hat + 0.5 + v);
+  } else {
+    qf = (float)(q_hat + 0.5 - v);
+  }
+  const float qq = (float)(uint32_t)qf;
+  for (uint32_t i = 0; i < M_sc; i++) {
+    const float m = (float)(i % N_sz);
+    arg[i]        = (float)(-M_PI * qq * m * (m + 1) / n_sz);
+  }
+}
+
 struct srslte_hip_chest_ul {
   uint32_t cell_id, nof_prb, nsl; // nsl: symbols per slot (7, or 6 with the extended CP)
   srslte_hip_dmrs_pusch_cfg_t cfg;

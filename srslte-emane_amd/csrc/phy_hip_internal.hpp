@@ -113,3 +113,13 @@ void       phich_rx_destroy(PhichRx* t);
 // pucch.hip: the checks of srslte_hip_ul_ctrl_pucch_batch alone (nothing is queued), and whether an object was made for a receiver's cell
 int  ul_ctrl_check(const srslte_hip_ul_ctrl_t* q, uint32_t nof_sf, const srslte_hip_pucch_req_t* reqs, uint32_t nof);
 bool ul_ctrl_same_cell(const srslte_hip_ul_ctrl_t* q, uint32_t nof_prb, uint32_t cell_id, int cp_ext);
+// chest.hip: compute_r_uv_arg (refsignal_ul.c:285-293): the argument of the uplink base sequence r_uv of nof_prb PRB into arg [12 nof_prb] (host)
+void ul_r_uv_arg(uint32_t nof_prb, uint32_t u, uint32_t v, float* arg);
+// srs_host.cpp: the checks of srslte_hip_srs_tx_put / _rx_batch on the configuration and the list alone (nothing is queued); the first slot's
+// sequence of every subframe of a frame, [10][M_sc], as srslte_refsignal_srs_put reads it from srslte_refsignal_srs_gen's output
+bool srs_cfg_valid(const srslte_hip_srs_cfg_t* c);
+int  srs_list_check(const srslte_hip_srs_cfg_t* c, uint32_t tti0, uint32_t nof_sf, const srslte_hip_srs_ue_t* list, uint32_t nof);
+void srs_first_slot_table(const srslte_hip_srs_cfg_t* c, uint32_t M_sc, uint32_t n_srs, std::vector<cf32>& r);
+// srs.hip: whether an object was made for a receiver's cell, and the configuration it was made with
+bool                        srs_same_cell(const srslte_hip_srs_t* q, uint32_t nof_prb, uint32_t cell_id, int cp_ext);
+const srslte_hip_srs_cfg_t* srs_cfg(const srslte_hip_srs_t* q);

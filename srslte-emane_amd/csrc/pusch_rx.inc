@@ -669,9 +669,17 @@ struct UlPucchCall {
   uint32_t                      nof;
   srslte_hip_pucch_res_t*       d_res;
 };
+// srs: the sounding requests of srslte_hip_ul_rx_batch_grants_pucch_srs, read from the same grid (nullptr: none)
+struct UlSrsCall {
+  srslte_hip_srs_t*          srs;
+  const srslte_hip_srs_ue_t* list;
+  uint32_t                   nof;
+  srslte_hip_srs_res_t*      d_res;
+  void*                      d_ce;
+};
 
 static int ul_rx_grants(srslte_hip_ul_rx_t* q, const void* d_iq, uint32_t tti0, uint32_t nof_sf, const srslte_hip_ul_grant_t* grants, uint32_t nof_grants,
-                        uint8_t* d_tb, uint32_t tb_stride, uint8_t* d_tb_ok, const UlPucchCall* pucch, void* stream)
+                        uint8_t* d_tb, uint32_t tb_stride, uint8_t* d_tb_ok, const UlPucchCall* pucch, const UlSrsCall* srs, void* stream)
 {
   if (!q || !d_iq || !grants || !d_tb || !d_tb_ok || nof_sf > q->cfg.max_batch || tb_stride < q->cfg.tbs / 8 + 6) return SRSLTE_ERROR_INVALID_INPUTS;
   const uint32_t V = q->cfg.max_grants ? q->cfg.max_grants : q->cfg.max_batch, P = q->cfg.nof_prb;
@@ -769,6 +777,7 @@ static int ul_rx_grants(srslte_hip_ul_rx_t* q, const void* d_iq, uint32_t tti0, 
   int r = srslte_hip_ofdm_rx_sf_batch(q->ofdm, d_iq, q->d_grid, (int)nof_sf, stream);
   if (r) return r;
   if (pucch && (r = srslte_hip_ul_ctrl_pucch_batch(pucch->ctrl, q->d_grid, tti0, nof_sf, pucch->reqs, pucch->nof, pucch->d_res, stream))) return r;
+  if (srs && (r = srslte_hip_srs_rx_batch(srs->srs, q->d_grid, tti0, nof_sf, srs->list, srs->nof, srs->d_res, srs->d_ce, stream))) return r;
   const int n16 = (int)((g->desc_bytes + 15) / 16);
   hipLaunchKernelGGL(desc_copy_kernel, dim3(ceil_div(n16, 256)), dim3(256), 0, st, (const uint4*)h_pin, (uint4*)g->d_desc, n16);
   LAUNCH_CHECK();
@@ -813,7 +822,7 @@ static int ul_rx_grants(srslte_hip_ul_rx_t* q, const void* d_iq, uint32_t tti0, 
 extern "C" int srslte_hip_ul_rx_batch_grants(srslte_hip_ul_rx_t* q, const void* d_iq, uint32_t tti0, uint32_t nof_sf, const srslte_hip_ul_grant_t* grants,
                                              uint32_t nof_grants, uint8_t* d_tb, uint32_t tb_stride, uint8_t* d_tb_ok, void* stream)
 {
-  return ul_rx_grants(q, d_iq, tti0, nof_sf, grants, nof_grants, d_tb, tb_stride, d_tb_ok, nullptr, stream);
+  return ul_rx_grants(q, d_iq, tti0, nof_sf, grants, nof_grants, d_tb, tb_stride, d_tb_ok, nullptr, nullptr, stream);
 }
 
 // srslte_enb_ul_fft + get_pusch per grant + get_pucch per request: the PUCCH requests are checked before anything is queued; without grants
@@ -831,5 +840,34 @@ extern "C" int srslte_hip_ul_rx_batch_grants_pucch(srslte_hip_ul_rx_t* q, const 
     return srslte_hip_ul_ctrl_pucch_batch(ctrl, q->d_grid, tti0, nof_sf, reqs, nof_pucch, d_res, stream);
   }
   const UlPucchCall pc = {ctrl, reqs, nof_pucch, d_res};
-  return ul_rx_grants(q, d_iq, tti0, nof_sf, grants, nof_grants, d_tb, tb_stride, d_tb_ok, nof_pucch ? &pc : nullptr, stream);
+  return ul_rx_grants(q, d_iq, tti0, nof_sf, grants, nof_grants, d_tb, tb_stride, d_tb_ok, nof_pucch ? &pc : nullptr, nullptr, stream);
+}
+
+// ... + the sounding requests of srs_list on the same grid. ctrl and srs may each be NULL; both lists are checked before anything is queued;
+// without grants the call is the OFDM demodulation and the two batches alone
+extern "C" int srslte_hip_ul_rx_batch_grants_pucch_srs(srslte_hip_ul_rx_t* q, const void* d_iq, uint32_t tti0, uint32_t nof_sf, const srslte_hip_ul_grant_t* grants,
+                                                       uint32_t nof_grants, uint8_t* d_tb, uint32_t tb_stride, uint8_t* d_tb_ok, srslte_hip_ul_ctrl_t* ctrl,
+                                                       const srslte_hip_pucch_req_t* reqs, uint32_t nof_pucch, srslte_hip_pucch_res_t* d_res,
+                                                       srslte_hip_srs_t* srs, const srslte_hip_srs_ue_t* srs_list, uint32_t nof_srs,
+                                                       srslte_hip_srs_res_t* d_srs_res, void* d_srs_ce, void* stream)
+{
+  if (!q || !d_iq || nof_sf > q->cfg.max_batch) return SRSLTE_ERROR_INVALID_INPUTS;
+  if (!ctrl) nof_pucch = 0;
+  if (!srs) nof_srs = 0;
+  if (ctrl && (!ul_ctrl_same_cell(ctrl, q->cfg.nof_prb, q->cfg.cell_id, q->cfg.cp_ext) || (nof_pucch && !d_res))) return SRSLTE_ERROR_INVALID_INPUTS;
+  if (srs && (!srs_same_cell(srs, q->cfg.nof_prb, q->cfg.cell_id, q->cfg.cp_ext) || (nof_srs && (!d_srs_res || !d_srs_ce)))) return SRSLTE_ERROR_INVALID_INPUTS;
+  if (ctrl)
+    if (int r = ul_ctrl_check(ctrl, nof_sf, reqs, nof_pucch)) return r;
+  if (srs)
+    if (int r = srs_list_check(srs_cfg(srs), tti0, nof_sf, srs_list, nof_srs)) return r;
+  if (nof_grants == 0) {
+    if (nof_sf == 0 || (nof_pucch == 0 && nof_srs == 0)) return SRSLTE_SUCCESS;
+    if (int r = srslte_hip_ofdm_rx_sf_batch(q->ofdm, d_iq, q->d_grid, (int)nof_sf, stream)) return r;
+    if (nof_pucch)
+      if (int r = srslte_hip_ul_ctrl_pucch_batch(ctrl, q->d_grid, tti0, nof_sf, reqs, nof_pucch, d_res, stream)) return r;
+    return nof_srs ? srslte_hip_srs_rx_batch(srs, q->d_grid, tti0, nof_sf, srs_list, nof_srs, d_srs_res, d_srs_ce, stream) : SRSLTE_SUCCESS;
+  }
+  const UlPucchCall pc = {ctrl, reqs, nof_pucch, d_res};
+  const UlSrsCall   sc = {srs, srs_list, nof_srs, d_srs_res, d_srs_ce};
+  return ul_rx_grants(q, d_iq, tti0, nof_sf, grants, nof_grants, d_tb, tb_stride, d_tb_ok, nof_pucch ? &pc : nullptr, nof_srs ? &sc : nullptr, stream);
 }
