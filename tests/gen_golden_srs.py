@@ -8,7 +8,9 @@ reference or compiled from it enters the tree: the fixture holds recorded output
 CASES is also what tests/test_srs_host.py and tests/test_gpu_srs.py run. Recorded: srslte_refsignal_srs_gen and srslte_refsignal_srs_put (on a zeroed
 grid: the non-zero indices and their values) for every TTI of every case, M_sc, srslte_refsignal_srs_send_cs over the 15 x 10 pairs,
 srslte_refsignal_srs_send_ue over I_srs 0-636 x SEND_UE_TTIS, srslte_refsignal_srs_rb_start_cs / _rb_L_cs over BW_PRBS x 8, and the two
-shortened decisions over the drawn inputs of shortened_inputs()."""
+shortened decisions over the drawn inputs of shortened_inputs(). The 32 row_* cases - one per (band, bw_cfg) row of 36.211 Tables 5.5.3.2-1..4 - are
+recorded at two TTIs; the HOP_CASES at every occasion of one hopping period and one more, the first index of srslte_refsignal_srs_put alone
+(.put_idx0); and sweep_M_sc / sweep_k0 hold srslte_refsignal_srs_M_sc and the first put index for every B and n_rrc of every row without hopping."""
 import os
 import sys
 
@@ -52,6 +54,41 @@ CASES = {
     "p15_bw5_T80": dict(nof_prb=15, cell_id=33, cp_ext=True, bw_cfg=5, subframe_config=1, gh=False, sh=False, delta_ss=0, B=1, b_hop=0, n_srs=4, I_srs=100,
                         k_tc=0, n_rrc=23, ttis=_occ(100, 4, 2)),
 }
+
+
+def _row_n_rrc(band, bw_cfg, B):
+    """The n_rrc of a row case: the one whose position indices n_b = floor(4 n_rrc / m_SRS,b) mod N_b (36.211 5.5.3.2, no hopping) add up highest
+    over b <= B, so that every level with N_b > 1 moves k0; the largest of equals."""
+    from srs_ref import M_SRS_B
+    m = [M_SRS_B[band][b][bw_cfg] for b in range(4)]
+    return max(range(24), key=lambda n: (sum((4 * n // m[b]) % (m[b - 1] // m[b]) for b in range(1, B + 1)), n))
+
+
+# One case per row of the four bandwidth tables (the first eight cases reach six of the 32): the smallest cell of the band that holds m_SRS,0,
+# every B (the wide B 0 and 1 on one bw_cfg each, to keep the fixture small), both combs, every cyclic shift, both CPs, T_srs 2 and 5, two
+# occasions each.
+ROW_B = (3, 2, 3, 3, 1, 2, 3, 0)
+ROW_PRB = ((40, 40, 25, 25, 25, 15, 15, 6), (50,) * 8, (75,) * 8, (100,) * 8)
+for _band in range(4):
+    for _bw in range(8):
+        _i, _B = 8 * _band + _bw, ROW_B[_bw]
+        CASES["row_b%d_c%d" % (_band, _bw)] = dict(
+            nof_prb=ROW_PRB[_band][_bw], cell_id=17 * _i % 504, cp_ext=(_band + _bw) % 3 == 0, bw_cfg=_bw, subframe_config=_i % 15, gh=_bw % 4 == 1,
+            sh=_bw % 4 == 2, delta_ss=(7 * _bw + _band) % 30, B=_B, b_hop=3, n_srs=(3 * _bw + _band) % 8, I_srs=_bw % 7, k_tc=_bw % 2,
+            n_rrc=_row_n_rrc(_band, _bw, _B), ttis=_occ(_bw % 7, 2, 3 + _band))
+
+# Hopping over a whole period (the product of the N_b above b_hop, in occasions) and one occasion more, positions only. Not in CASES: they carry
+# no values, so only the host walks them.
+HOP_CASES = {
+    # N_1 N_2 N_3 = 2 2 5 (an odd N_b last): 20 positions; T_srs 2
+    "hop_p100_bw2": dict(nof_prb=100, cell_id=421, cp_ext=False, bw_cfg=2, subframe_config=0, gh=False, sh=False, delta_ss=0, B=3, b_hop=0, n_srs=1, I_srs=1,
+                         k_tc=1, n_rrc=7, period=20, ttis=_occ(1, 21, 37)),
+    # b_hop 1 < B 3: level 1 stays where n_rrc puts it, N_2 N_3 = 2 4 (even N_b only): 8 positions; T_srs 5, extended CP
+    "hop_p75_bw1": dict(nof_prb=75, cell_id=88, cp_ext=True, bw_cfg=1, subframe_config=3, gh=False, sh=False, delta_ss=0, B=3, b_hop=1, n_srs=6, I_srs=4,
+                        k_tc=0, n_rrc=13, period=8, ttis=_occ(4, 9, 5)),
+}
+# every B and n_rrc of every row, without hopping, on the smallest usual cell of each band that holds every m_SRS,0 of it
+SWEEP_PRBS = [40, 50, 75, 100]
 # every offset of the longest period's first subframes (tti < T_offset for most I_srs), a stretch further on, and the end of the TTI range
 SEND_UE_TTIS = list(range(0, 24)) + [39, 40, 79, 80, 159, 160, 161, 319, 320, 321, 477, 636, 637, 5000, 5003, 10239]
 BW_PRBS = [6, 15, 25, 40, 41, 50, 60, 61, 75, 80, 81, 100, 110]
@@ -208,6 +245,33 @@ def record(ref_root):
             res[name + ".put_idx"] = np.stack(idxs)
             res[name + ".put_val"] = np.stack(vals)
             L.rec_free(q)
+        for name, c in sorted(HOP_CASES.items()):
+            q = L.rec_new(c["nof_prb"], c["cell_id"], 1 if c["cp_ext"] else 0)
+            assert q, name
+            w = cfg_words(c)
+            M = L.rec_M_sc(q, w.ctypes.data)
+            r, first = np.ones(2 * M, np.complex64), []
+            for tti in c["ttis"]:
+                grid = np.zeros((12 if c["cp_ext"] else 14) * 12 * c["nof_prb"], np.complex64)
+                assert L.rec_put(q, w.ctypes.data, tti, r.ctypes.data, grid.ctypes.data) == 0
+                first.append(np.flatnonzero(grid)[0])
+            res[name + ".put_idx0"] = np.array(first, np.uint32)
+            L.rec_free(q)
+        sw_M, sw_k0 = np.zeros((len(SWEEP_PRBS), 8, 4), np.uint32), np.zeros((len(SWEEP_PRBS), 8, 4, 24), np.uint32)
+        for pi, P in enumerate(SWEEP_PRBS):
+            q = L.rec_new(P, 1, 0)
+            assert q, P
+            r = np.ones(2 * 12 * P, np.complex64)
+            for bw in range(8):
+                for B in range(4):
+                    for n_rrc in range(24):
+                        w = np.array([0, bw, B, 3, 0, 0, 0, n_rrc, 1, 0], np.uint32)
+                        sw_M[pi, bw, B] = L.rec_M_sc(q, w.ctypes.data)
+                        grid = np.zeros(14 * 12 * P, np.complex64)
+                        assert L.rec_put(q, w.ctypes.data, 0, r.ctypes.data, grid.ctypes.data) == 0
+                        sw_k0[pi, bw, B, n_rrc] = np.flatnonzero(grid)[0] - 13 * 12 * P
+            L.rec_free(q)
+        res["sweep_M_sc"], res["sweep_k0"] = sw_M, sw_k0
         res["send_cs"] = np.array([[L.srslte_refsignal_srs_send_cs(sc, sf) for sf in range(10)] for sc in range(15)], np.int8)
         res["send_ue"] = np.array([[L.srslte_refsignal_srs_send_ue(I, t) for t in SEND_UE_TTIS] for I in range(637)], np.int8)
         res["rb_start_cs"] = np.array([[L.srslte_refsignal_srs_rb_start_cs(b, p) for b in range(8)] for p in BW_PRBS], np.uint32)

@@ -78,3 +78,29 @@ def e2e_channel(ue_grids, seed=7):
 def e2e_truth(u, k0, J):
     """gain times ramp at the centre of block j (RE k0 + 16 j + 7)."""
     return u["gain"] * np.exp(-2j * np.pi * 15e3 * u["tau_us"] * 1e-6 * (k0 + 16 * np.arange(J) + 7))
+
+
+# A second scene on the same cell, built to break what E2E cannot see. Comb 0 carries cyclic shifts 0, 1 and 3 (cs_used 0b1011, not its own mirror
+# image modulo 8) with gains 1.0, 0.1 and 3.0; comb 1 carries one UE. The strong UEs sit at +1.9 and -1.9 us, 0.18 us inside the +-2.083 us range of
+# ta_us: a delay tau moves a UE by 0.24 (tau / 1 us) bins of the block DFT, so at 1.9 us its power lies between its own bin and the next, its own
+# h_j drops to 0.70 |g| and it leaks 0.13-0.23 |g| into every other bin. The weak UE between them is therefore NOT recovered by this estimator
+# (the leakage into its bin is five times its gain); the scene checks that the device shows exactly the leakage the float64 model shows, in the
+# right bins and with the right sign of ta_us. sigma^2 as in E2E.
+E2E_HARD = dict(nof_prb=50, cell_id=150, bw_cfg=0, sigma2=0.09,
+                ues=[dict(k_tc=0, n_srs=0, cs_used=0b1011, gain=1.0 * np.exp(0.3j), tau_us=1.9),
+                     dict(k_tc=0, n_srs=1, cs_used=0b1011, gain=0.1 * np.exp(-1.1j), tau_us=0.0),
+                     dict(k_tc=0, n_srs=3, cs_used=0b1011, gain=3.0 * np.exp(2.0j), tau_us=-1.9),
+                     dict(k_tc=1, n_srs=6, cs_used=0b1000000, gain=0.5 * np.exp(0.7j), tau_us=1.9)])
+
+
+def scene_channel(scene, ue_grids, seed=7, noise=True):
+    """e2e_channel for any scene; noise=False leaves the noise out (float64, for the leakage the model shows by itself)."""
+    k = np.arange(12 * scene["nof_prb"])
+    y = np.zeros(k.size, np.complex128)
+    for u, g in zip(scene["ues"], ue_grids):
+        y += u["gain"] * np.exp(-2j * np.pi * 15e3 * u["tau_us"] * 1e-6 * k) * g
+    if not noise:
+        return y
+    rng = np.random.default_rng(seed)
+    s = np.sqrt(scene["sigma2"] / 2)
+    return (y + rng.normal(0, s, k.size) + 1j * rng.normal(0, s, k.size)).astype(np.complex64)

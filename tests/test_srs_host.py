@@ -1,6 +1,7 @@
 """The host side of the SRS (srs_host.cpp) against tests/golden/srs.npz, recorded from the reference's refsignal_ul.c by tests/gen_golden_srs.py:
-every helper's integers exactly, srslte_hip_srs_gen bit for bit, the refusals of create and of a call, and - where the reference build is
-present - the base sequence pinned live against srslte_refsignal_dmrs_pusch_gen."""
+every helper's integers exactly, srslte_hip_srs_gen bit for bit, every entry of the bandwidth tables through M_sc and k0, two hopping periods walked
+occasion by occasion, the refusals of create and of a call, and - where the reference build is present - the base sequence pinned live against
+srslte_refsignal_dmrs_pusch_gen. Also the cyclic-shift convention of the float64 receiver model of tests/srs_ref.py, which judges the device."""
 import ctypes as C
 import importlib
 
@@ -8,8 +9,8 @@ import numpy as np
 import pytest
 
 from _libs import OrcUlDmrsCfg, RefCell, opaque, ref
-from gen_golden_srs import BW_PRBS, CASES, SEND_UE_TTIS, shortened_inputs
-from srs_ref import case_cfg, case_ue, golden
+from gen_golden_srs import BW_PRBS, CASES, HOP_CASES, SEND_UE_TTIS, SWEEP_PRBS, shortened_inputs
+from srs_ref import M_SRS_B, bw_table_idx, case_cfg, case_ue, golden, rx_model
 
 pkg = importlib.import_module("srslte-emane_amd")
 
@@ -79,6 +80,80 @@ def test_cases_cover_what_the_issue_lists():
     rows = {next(i for i, hi in enumerate((2, 7, 17, 37, 77, 157, 317, 637)) if c["I_srs"] < hi) for c in cs}
     assert rows == set(range(8))
     assert {6, 25, 50, 75, 100} <= {c["nof_prb"] for c in cs}
+
+
+def test_cases_cover_every_row_of_the_bandwidth_tables():
+    """All 32 (band, bw_cfg) rows of 36.211 Tables 5.5.3.2-1..4 occur; in every band the cases use each B, both combs, both CPs and a non-zero
+    n_rrc; and every hopping case is recorded over one whole period and one occasion more."""
+    cs = list(CASES.values())
+    assert {(bw_table_idx(c["nof_prb"]), c["bw_cfg"]) for c in cs} == {(t, bw) for t in range(4) for bw in range(8)}
+    for t in range(4):
+        band = [c for c in cs if bw_table_idx(c["nof_prb"]) == t]
+        assert {c["B"] for c in band} == {0, 1, 2, 3} and {c["k_tc"] for c in band} == {0, 1} and {c["cp_ext"] for c in band} == {False, True}
+        assert any(c["n_rrc"] for c in band)
+    assert len(HOP_CASES) >= 2 and len({(bw_table_idx(c["nof_prb"]), c["bw_cfg"]) for c in HOP_CASES.values()}) == len(HOP_CASES)
+    for c in HOP_CASES.values():
+        t, T = bw_table_idx(c["nof_prb"]), c["ttis"][1] - c["ttis"][0]
+        period = int(np.prod([M_SRS_B[t][b - 1][c["bw_cfg"]] // M_SRS_B[t][b][c["bw_cfg"]] for b in range(c["b_hop"] + 1, c["B"] + 1)]))
+        assert c["b_hop"] < c["B"] and T in (2, 5) and period == c["period"] > 1
+        assert c["ttis"] == [c["ttis"][0] + T * i for i in range(period + 1)] and max(c["ttis"]) < 10240
+
+
+@pytest.mark.parametrize("name", sorted(HOP_CASES))
+def test_hopping_walks_a_whole_period(name):
+    """k0 at every occasion of one hopping period against the first index the reference's srslte_refsignal_srs_put wrote: every position of the
+    hopping tree once, M_sc apart at least, and back at the start one period later."""
+    c, g = HOP_CASES[name], golden()
+    cfg, ue = case_cfg(c), case_ue(c)
+    want = g[name + ".put_idx0"].astype(np.int64)
+    assert want.size == c["period"] + 1
+    nsym = 12 if c["cp_ext"] else 14
+    got = np.array([(nsym - 1) * 12 * c["nof_prb"] + pkg.srs_k0(cfg, ue, tti) for tti in c["ttis"]], np.int64)
+    assert np.array_equal(got, want), (name, got - want)
+    assert len(set(want[:-1].tolist())) == c["period"] and want[-1] == want[0]
+    assert np.diff(np.sort(want[:-1])).min() >= 2 * pkg.srs_M_sc(cfg, ue)
+    assert all(pkg.srs_send_ue(c["I_srs"], tti) == 1 for tti in c["ttis"]) and pkg.srs_send_ue(c["I_srs"], c["ttis"][0] + 1) == 0
+
+
+def test_every_table_entry_matches_the_reference():
+    """srslte_hip_srs_M_sc for every (band, bw_cfg, B) and srslte_hip_srs_k0 for every n_rrc of each, without hopping: m_SRS,b enters through
+    M_sc at b = B and through the stride of level b, N_b through the position index of level b. A wrong entry anywhere in the two tables of
+    srs_host.cpp changes one of these 3072 positions or 128 lengths."""
+    g = golden()
+    M, k0 = np.zeros((len(SWEEP_PRBS), 8, 4), np.uint32), np.zeros((len(SWEEP_PRBS), 8, 4, 24), np.uint32)
+    for pi, P in enumerate(SWEEP_PRBS):
+        for bw in range(8):
+            cfg = pkg.srs_cfg(P, 1, bw)
+            for B in range(4):
+                M[pi, bw, B] = pkg.srs_M_sc(cfg, pkg.SrsUe.make(0, B=B))
+                k0[pi, bw, B] = [pkg.srs_k0(cfg, pkg.SrsUe.make(0, B=B, b_hop=3, n_rrc=n), 0) for n in range(24)]
+    assert [bw_table_idx(P) for P in SWEEP_PRBS] == [0, 1, 2, 3]
+    assert np.array_equal(M, g["sweep_M_sc"]) and np.array_equal(M, 6 * np.array(M_SRS_B, np.uint32).transpose(0, 2, 1))
+    assert np.array_equal(k0, g["sweep_k0"]), np.argwhere(k0 != g["sweep_k0"])[:4]
+
+
+def test_the_model_follows_the_cyclic_shift_of_36_211():
+    """rx_model by arithmetic alone, no library: r_n(i) = rbar(i) exp(j 2 pi n i / 8) (36.211 5.5.3.1, alpha = 2 pi n_srs / 8) for a random
+    unit-modulus rbar. A noise-free UE on shift n seen by a receiver that expects n: every h_j is 1, every free bin 0. A UE on shift n + k
+    instead: nothing in bin 0, and its power - 1 in one bin of a block - in the bin the model attributes to shift n + k and in no other, as
+    the free-bin masks show: noise 0 with that shift marked used, 8 / 6 (one of six free bins full) with any other shift marked used."""
+    rng = np.random.default_rng(3)
+    J, i = 9, np.arange(72)
+    rbar = np.exp(2j * np.pi * rng.random(i.size))
+    r = [rbar * np.exp(2j * np.pi * n * i / 8) for n in range(8)]
+    for n in range(8):
+        m = rx_model(r[n], r[n], n, 1 << n)
+        assert m["nof_free"] == 7 and np.abs(m["ce"] - 1).max() <= 1e-12 and m["noise_estimate"] <= 1e-12 and abs(m["rsrp"] - 1) <= 1e-12
+        for k in range(1, 8):
+            other = (n + k) % 8
+            m = rx_model(r[other], r[n], n, 1 << n)
+            assert np.abs(m["ce"]).max() <= 1e-12 and abs(m["noise_estimate"] - 8 / 7) <= 1e-12  # all of it in the seven free bins
+            m = rx_model(r[other], r[n], n, (1 << n) | (1 << other))
+            assert m["nof_free"] == 6 and np.abs(m["ce"]).max() <= 1e-12 and m["noise_estimate"] <= 1e-12, (n, k)
+            for k2 in range(1, 8):
+                if k2 != k:
+                    m = rx_model(r[other], r[n], n, (1 << n) | (1 << (n + k2) % 8))
+                    assert m["nof_free"] == 6 and abs(m["noise_estimate"] - 8 / 6) <= 1e-12, (n, k, k2)
 
 
 # with sequence hopping on and delta_ss != 0 the SRS takes v at the case's delta_ss and u at 0: no single DMRS configuration makes that r_uv
