@@ -13,9 +13,10 @@
 //                     and noise. No atomics: the same bytes every run.
 //   ch_carry_kernel   the N samples of overlap past the end of the call and the last delay_cap samples of the fading output, for the next call
 //                     (ping-pong buffers: the kernels above read the previous call's).
+#include "cf32_dev.hpp"
 #include "common.hpp"
+#include "dev_buf.hpp"
 #include "phy_hip_internal.hpp"
-#include "pinned_ring.hpp"
 #include <math.h>
 #include <random>
 #include <string.h>
@@ -57,9 +58,6 @@ struct ChGeom {
   uint64_t in_cs, in_bs, out_cs, out_bs;
 };
 
-__device__ __forceinline__ cf32 cmul(cf32 a, cf32 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ cf32 cadd(cf32 a, cf32 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ cf32 csub(cf32 a, cf32 b) { return make_float2(a.x - b.x, a.y - b.y); }
 // exp(-j 2 pi k / N) from the table, conjugated for the inverse transform
 __device__ __forceinline__ cf32 twid(const cf32* __restrict__ tw, int i, float sgn)
 {
@@ -388,18 +386,15 @@ struct srslte_hip_channel {
   int                      model, N, ntaps, dcap;
   std::vector<double>      coef; // [channel][a, w, p][MAXTAPS]
   const cf32*              d_tw    = nullptr;
-  double*                  d_coef  = nullptr;
-  float*                   d_amp   = nullptr;
-  cf32*                    d_E     = nullptr;
-  cf32*                    d_y     = nullptr;
-  cf32*                    d_state[2] = {};
-  cf32*                    d_hist[2]  = {};
-  ChBlock*                 d_blk   = nullptr; // [4][max_calls], one row per pinned buffer
-  PinnedRing               ring;
-  bool                     ring_ok = false;
+  DevBuf<double>           d_coef;
+  DevBuf<float>            d_amp;
+  DevBuf<cf32>             d_E, d_y, d_state[2], d_hist[2];
+  DevBuf<ChBlock>          d_blk; // [4][max_calls], one row per pinned buffer
+  PinnedRing               ring;  // destroy() leaves a ring that was never initialised alone
   int                      cur     = 0; // which of d_state / d_hist the next call reads
   uint32_t                 avail   = 0; // samples in the delay line
   uint64_t                 samples = 0; // per channel, since creation or reset
+  ~srslte_hip_channel() { ring.destroy(); }
 };
 
 extern "C" {
@@ -429,16 +424,7 @@ int srslte_hip_channel_block_params(const srslte_hip_channel_cfg_t* cfg, uint32_
   return SRSLTE_SUCCESS;
 }
 
-void srslte_hip_channel_destroy(srslte_hip_channel_t* q)
-{
-  if (!q) return;
-  for (void* p : {(void*)q->d_coef, (void*)q->d_amp, (void*)q->d_E, (void*)q->d_y, (void*)q->d_state[0], (void*)q->d_state[1], (void*)q->d_hist[0],
-                  (void*)q->d_hist[1], (void*)q->d_blk}) {
-    if (p) (void)hipFree(p);
-  }
-  if (q->ring_ok) q->ring.destroy();
-  delete q;
-}
+void srslte_hip_channel_destroy(srslte_hip_channel_t* q) { delete q; }
 
 int srslte_hip_channel_reset(srslte_hip_channel_t* q)
 {
@@ -446,8 +432,8 @@ int srslte_hip_channel_reset(srslte_hip_channel_t* q)
   HIP_TRY(hipDeviceSynchronize()); // calls in flight still read the state
   const size_t C = q->cfg.nof_channels;
   for (int i = 0; i < 2; i++) {
-    if (q->d_state[i]) HIP_TRY(hipMemset(q->d_state[i], 0, sizeof(cf32) * C * q->N));
-    if (q->d_hist[i]) HIP_TRY(hipMemset(q->d_hist[i], 0, sizeof(cf32) * C * q->dcap));
+    if (q->d_state[i].get()) HIP_TRY(hipMemset(q->d_state[i].get(), 0, sizeof(cf32) * C * q->N));
+    if (q->d_hist[i].get()) HIP_TRY(hipMemset(q->d_hist[i].get(), 0, sizeof(cf32) * C * q->dcap));
   }
   q->cur     = 0;
   q->avail   = 0;
@@ -455,13 +441,19 @@ int srslte_hip_channel_reset(srslte_hip_channel_t* q)
   return SRSLTE_SUCCESS;
 }
 
+static int channel_alloc_failed()
+{
+  hip_log("[srslte_hip] channel: device allocation failed\n");
+  return SRSLTE_ERROR;
+}
+
+// returns at the first step that fails
 static int channel_init(srslte_hip_channel_t* q)
 {
   const srslte_hip_channel_cfg_t& c = q->cfg;
   const size_t                    C = c.nof_channels;
-  HIP_TRY(hipMalloc((void**)&q->d_blk, sizeof(ChBlock) * 4 * c.max_calls));
+  if (q->d_blk.alloc((size_t)4 * c.max_calls)) return channel_alloc_failed();
   if (q->ring.init(sizeof(ChBlock) * c.max_calls)) return SRSLTE_ERROR;
-  q->ring_ok = true;
   if (c.fading_enable) {
     FftFactors f;
     if (fft_get_plan(q->N, &f, &q->d_tw)) return SRSLTE_ERROR;
@@ -482,18 +474,11 @@ static int channel_init(srslte_hip_channel_t* q)
       draw_coeffs(q->model, c.doppler_hz, c.seed0 + (uint32_t)ch * c.seed_stride, cc, cc + MAXTAPS, cc + 2 * MAXTAPS);
     }
     const size_t nseg_max = (c.max_len + path_delay - 1) / path_delay;
-    HIP_TRY(hipMalloc((void**)&q->d_amp, sizeof(float) * MAXTAPS));
-    HIP_TRY(hipMalloc((void**)&q->d_E, sizeof(cf32) * E.size()));
-    HIP_TRY(hipMalloc((void**)&q->d_coef, sizeof(double) * q->coef.size()));
-    HIP_TRY(hipMalloc((void**)&q->d_y, sizeof(cf32) * C * c.max_calls * nseg_max * N));
-    HIP_TRY(hipMemcpy(q->d_amp, amp.data(), sizeof(float) * MAXTAPS, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(q->d_E, E.data(), sizeof(cf32) * E.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(q->d_coef, q->coef.data(), sizeof(double) * q->coef.size(), hipMemcpyHostToDevice));
-    for (int i = 0; i < 2; i++) HIP_TRY(hipMalloc((void**)&q->d_state[i], sizeof(cf32) * C * N));
+    if (q->d_amp.upload(amp) || q->d_E.upload(E) || q->d_coef.upload(q->coef) || q->d_y.alloc(C * c.max_calls * nseg_max * N) ||
+        q->d_state[0].alloc(C * N) || q->d_state[1].alloc(C * N))
+      return channel_alloc_failed();
   }
-  if (c.delay_enable) {
-    for (int i = 0; i < 2; i++) HIP_TRY(hipMalloc((void**)&q->d_hist[i], sizeof(cf32) * C * q->dcap));
-  }
+  if (c.delay_enable && (q->d_hist[0].alloc(C * q->dcap) || q->d_hist[1].alloc(C * q->dcap))) return channel_alloc_failed();
   return srslte_hip_channel_reset(q);
 }
 
@@ -523,7 +508,7 @@ int srslte_hip_channel_create(srslte_hip_channel_t** out, const srslte_hip_chann
     return SRSLTE_ERROR_INVALID_INPUTS;
   }
   if (channel_init(q)) {
-    srslte_hip_channel_destroy(q);
+    delete q;
     return SRSLTE_ERROR;
   }
   *out = q;
@@ -577,7 +562,7 @@ int srslte_hip_channel_run_batch(srslte_hip_channel_t* q, const void* d_in, uint
   uint8_t* h;
   if (q->ring.acquire(&h)) return SRSLTE_ERROR;
   memcpy(h, blocks.data(), sizeof(ChBlock) * nof_calls);
-  ChBlock* d_blk = q->d_blk + (size_t)q->ring.cur * c.max_calls;
+  ChBlock* d_blk = q->d_blk.get() + (size_t)q->ring.cur * c.max_calls;
   HIP_TRY(hipMemcpyAsync(d_blk, h, sizeof(ChBlock) * nof_calls, hipMemcpyHostToDevice, st));
   if (q->ring.release(st)) return SRSLTE_ERROR;
 
@@ -596,8 +581,8 @@ int srslte_hip_channel_run_batch(srslte_hip_channel_t* q, const void* d_in, uint
     const dim3 grid(g.nseg, nof_calls, c.nof_channels);
 #define CH_FADING(NN)                                                                                                                         \
   case NN:                                                                                                                                    \
-    hipLaunchKernelGGL(ch_fading_kernel<NN>, grid, dim3(ch_threads<NN>()), 0, st, in, q->d_y, g, (const ChBlock*)d_blk, (const double*)q->d_coef, \
-                       (const float*)q->d_amp, (const cf32*)q->d_E, q->d_tw);                                                                  \
+    hipLaunchKernelGGL(ch_fading_kernel<NN>, grid, dim3(ch_threads<NN>()), 0, st, in, q->d_y.get(), g, (const ChBlock*)d_blk,                    \
+                       (const double*)q->d_coef.get(), (const float*)q->d_amp.get(), (const cf32*)q->d_E.get(), q->d_tw);                      \
     break;
     switch (q->N) {
       CH_FADING(64)
@@ -612,12 +597,13 @@ int srslte_hip_channel_run_batch(srslte_hip_channel_t* q, const void* d_in, uint
   }
   const int cur = q->cur;
   hipLaunchKernelGGL(ch_output_kernel, dim3((len + CH_OUT_THREADS - 1) / CH_OUT_THREADS, nof_calls, c.nof_channels), dim3(CH_OUT_THREADS), 0, st, in,
-                     (cf32*)d_out, (const cf32*)q->d_y, g, (const ChBlock*)d_blk, (const cf32*)q->d_state[cur], (const cf32*)q->d_hist[cur]);
+                     (cf32*)d_out, (const cf32*)q->d_y.get(), g, (const ChBlock*)d_blk, (const cf32*)q->d_state[cur].get(), (const cf32*)q->d_hist[cur].get());
   LAUNCH_CHECK();
   const int ncarry = (g.fading ? g.N : 0) + g.dcap;
   if (ncarry) {
     hipLaunchKernelGGL(ch_carry_kernel, dim3((ncarry + CH_OUT_THREADS - 1) / CH_OUT_THREADS, c.nof_channels), dim3(CH_OUT_THREADS), 0, st, in,
-                       (const cf32*)q->d_y, g, (const cf32*)q->d_state[cur], q->d_state[cur ^ 1], (const cf32*)q->d_hist[cur], q->d_hist[cur ^ 1]);
+                       (const cf32*)q->d_y.get(), g, (const cf32*)q->d_state[cur].get(), q->d_state[cur ^ 1].get(), (const cf32*)q->d_hist[cur].get(),
+                       q->d_hist[cur ^ 1].get());
     LAUNCH_CHECK();
     q->cur = cur ^ 1;
   }

@@ -13,6 +13,7 @@
 // at a stride of 192 bytes: about 22 KB of the 538 KB of a 100 PRB subframe are touched, the kernel waits on latency, not bandwidth.
 // The sums are reduced in a fixed order (in-wave shuffles, then the four waves' partials in wave order), so a result does not change
 // from run to run. Lane 0 takes the decisions (csi_decide, shared with the host entry srslte_hip_csi_decide) and writes the 64-byte record.
+#include "cf32_dev.hpp"
 #include "common.hpp"
 #include "phy_hip_internal.hpp"
 #include <math.h>
@@ -28,13 +29,6 @@ struct CsiGeom {
   int   n_pmi, n_cn;          // samples of the PMI selection / of the condition number
   float offset;               // snr_to_cqi_offset
 };
-
-__host__ __device__ __forceinline__ cf32 cadd(cf32 a, cf32 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__host__ __device__ __forceinline__ cf32 csub(cf32 a, cf32 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__host__ __device__ __forceinline__ cf32 cmul(cf32 a, cf32 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__host__ __device__ __forceinline__ cf32 cconj(cf32 a) { return make_float2(a.x, -a.y); }
-__host__ __device__ __forceinline__ cf32 cmulj(cf32 a) { return make_float2(-a.y, a.x); } // _Complex_I * a
-__host__ __device__ __forceinline__ cf32 cscale(cf32 a, float s) { return make_float2(a.x * s, a.y * s); }
 
 // crealf(c) of srslte_precoding_pmi_select_1l_gen for codebook entry i (precoding.c:2166-2221)
 __device__ __forceinline__ float pmi_1l_term(int i, cf32 h00, cf32 h01, cf32 h10, cf32 h11)

@@ -13,6 +13,7 @@
 #include "ctrl_rx_dev.hpp"
 #include "ctrl_tx_dev.hpp"
 #include "demod_dev.hpp"
+#include "dev_buf.hpp"
 #include "phy_hip_internal.hpp"
 #include "viterbi_dev.hpp"
 #include <math.h>
@@ -258,23 +259,15 @@ __global__ __launch_bounds__(256) void dl_mib_kernel(const cf32* __restrict__ gr
 
 struct BcastTables {
   BcastGeom g;
-  uint32_t* d_tab = nullptr; // RE list, then the scrambling words
-  float*    d_sync = nullptr;
-  float*    d_llr = nullptr;   // receive: [max_batch][3][MAX_BITS]
-  srslte_hip_mib_cand_t* d_cand = nullptr; // receive: [max_batch][3][4]
+  DevBuf<uint32_t> tab; // RE list, then the scrambling words
+  DevBuf<float>    sync;
+  DevBuf<float>    llr;  // receive: [max_batch][3][MAX_BITS]
+  DevBuf<srslte_hip_mib_cand_t> cand; // receive: [max_batch][3][4]
   uint32_t  max_batch = 0;
   int       nof_rx = 1;
 };
 
-void bcast_tables_destroy(BcastTables* t)
-{
-  if (!t) return;
-  (void)hipFree(t->d_tab);
-  (void)hipFree(t->d_sync);
-  (void)hipFree(t->d_llr);
-  (void)hipFree(t->d_cand);
-  delete t;
-}
+void bcast_tables_destroy(BcastTables* t) { delete t; }
 
 BcastTables* bcast_tables_create(const srslte_hip_dl_ctrl_cfg_t* c, int phich_ext, int phich_resources, bool rx)
 {
@@ -289,17 +282,14 @@ BcastTables* bcast_tables_create(const srslte_hip_dl_ctrl_cfg_t* c, int phich_ex
   memcpy(sync + 144, h.sss, sizeof(h.sss));
   t->max_batch = rx ? c->max_batch : 0;
   t->nof_rx    = (int)c->nof_rx_antennas;
-  if (hipMalloc(&t->d_tab, tab.size() * 4) != hipSuccess || hipMalloc(&t->d_sync, sizeof(sync)) != hipSuccess ||
-      hipMemcpy(t->d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(t->d_sync, sync, sizeof(sync), hipMemcpyHostToDevice) != hipSuccess ||
-      (rx && (hipMalloc(&t->d_llr, (size_t)c->max_batch * 3 * MAX_BITS * 4) != hipSuccess ||
-              hipMalloc(&t->d_cand, (size_t)c->max_batch * 12 * sizeof(srslte_hip_mib_cand_t)) != hipSuccess))) {
+  if (t->tab.upload(tab) || t->sync.upload(sync, sizeof(sync) / sizeof(sync[0])) ||
+      (rx && (t->llr.alloc((size_t)c->max_batch * 3 * MAX_BITS) || t->cand.alloc((size_t)c->max_batch * 12)))) {
     hip_log("[srslte_hip] broadcast tables: device allocation failed\n");
-    bcast_tables_destroy(t);
+    delete t;
     return nullptr;
   }
   BcastGeom& g = t->g;
-  g.re = t->d_tab, g.scr = t->d_tab + h.pbch_re.size(), g.sync = t->d_sync;
+  g.re = t->tab.get(), g.scr = t->tab.get() + h.pbch_re.size(), g.sync = t->sync.get();
   g.pss_k0 = h.pss_k0, g.sss_k0 = h.sss_k0;
   g.nof_ports = (int)c->nof_ports, g.grid_len = (c->cp_ext ? 12 : 14) * 12 * (int)c->nof_prb, g.nof_bits = (int)h.nof_bits;
   g.mib_head = mib_head(c->nof_prb, phich_ext, phich_resources);
@@ -331,7 +321,7 @@ int srslte_hip_dl_ctrl_mib_batch(srslte_hip_dl_ctrl_t* q, const void* d_grid, co
   if (!t || !d_grid || !d_ce || !d_res || !d_mib || nof_sf > t->max_batch) return SRSLTE_ERROR_INVALID_INPUTS;
   if (nof_sf == 0) return SRSLTE_SUCCESS;
   hipLaunchKernelGGL(dl_mib_kernel, dim3(nof_sf), dim3(256), 0, (hipStream_t)stream, (const cf32*)d_grid, (const cf32*)d_ce, (const float*)d_res, tti0,
-                     search_all_ports ? 1 : 0, t->nof_rx, t->g, t->d_llr, t->d_cand, d_mib);
+                     search_all_ports ? 1 : 0, t->nof_rx, t->g, t->llr.get(), t->cand.get(), d_mib);
   LAUNCH_CHECK();
   return SRSLTE_SUCCESS;
 }
@@ -340,7 +330,7 @@ const void* srslte_hip_dl_ctrl_mib_debug_buffer(const srslte_hip_dl_ctrl_t* q, i
 {
   const BcastTables* t = dl_ctrl_bcast(q);
   if (!t) return nullptr;
-  return which == 0 ? (const void*)t->d_llr : which == 1 ? (const void*)t->d_cand : nullptr;
+  return which == 0 ? (const void*)t->llr.get() : which == 1 ? (const void*)t->cand.get() : nullptr;
 }
 
 int srslte_hip_pbch_re(const srslte_hip_dl_ctrl_cfg_t* cfg, uint32_t* re, uint32_t max)

@@ -11,6 +11,7 @@
 #include "ctrl_host.hpp"
 #include "ctrl_rx_dev.hpp"
 #include "demod_dev.hpp"
+#include "dev_buf.hpp"
 #include "phy_hip_internal.hpp"
 #include "viterbi_dev.hpp"
 #include <math.h>
@@ -329,18 +330,16 @@ static uint32_t dci_sizeof(uint32_t prb, uint32_t ports, int f)
 struct srslte_hip_dl_ctrl {
   srslte_hip_dl_ctrl_cfg_t cfg;
   CtrlGeom                 g;
-  uint32_t*                d_re = nullptr;
-  uint32_t*                d_scr = nullptr;
-  float*                   d_llr = nullptr;
-  srslte_hip_dl_ctrl_cand_t* d_cand = nullptr;
-  uint32_t*                d_ncand = nullptr;
+  DevBuf<uint32_t>         re, scr, ncand;
+  DevBuf<float>            llr;
+  DevBuf<srslte_hip_dl_ctrl_cand_t> cand;
   BcastTables*             bc = nullptr; // the MIB decoder (pbch.hip)
   PhichRx*                 ph = nullptr; // the PHICH receiver (phich.hip), once srslte_hip_dl_ctrl_set_max_phich has made it
 };
 
 const BcastTables* dl_ctrl_bcast(const srslte_hip_dl_ctrl_t* q) { return q ? q->bc : nullptr; }
 
-DlCtrlView dl_ctrl_view(srslte_hip_dl_ctrl_t* q) { return DlCtrlView{&q->cfg, q->g.scr_pcfich, q->d_cand, q->d_ncand}; }
+DlCtrlView dl_ctrl_view(srslte_hip_dl_ctrl_t* q) { return DlCtrlView{&q->cfg, q->g.scr_pcfich, q->cand.get(), q->ncand.get()}; }
 PhichRx*   dl_ctrl_phich(const srslte_hip_dl_ctrl_t* q) { return q->ph; }
 void       dl_ctrl_set_phich(srslte_hip_dl_ctrl_t* q, PhichRx* t) { q->ph = t; }
 
@@ -396,11 +395,6 @@ uint32_t srslte_hip_dci_format_sizeof(uint32_t nof_prb, uint32_t nof_ports, int 
 void srslte_hip_dl_ctrl_destroy(srslte_hip_dl_ctrl_t* q)
 {
   if (!q) return;
-  (void)hipFree(q->d_re);
-  (void)hipFree(q->d_scr);
-  (void)hipFree(q->d_llr);
-  (void)hipFree(q->d_cand);
-  (void)hipFree(q->d_ncand);
   bcast_tables_destroy(q->bc);
   phich_rx_destroy(q->ph);
   delete q;
@@ -433,16 +427,13 @@ srslte_hip_dl_ctrl_t* srslte_hip_dl_ctrl_create(const srslte_hip_dl_ctrl_cfg_t* 
   std::vector<uint32_t> scr;
   ctrl_scrambling(cfg->cell_id, 2 * g.n[2], scr, &g.scr_words);
   const size_t B = cfg->max_batch;
-  if (hipMalloc(&q->d_re, re.size() * 4) != hipSuccess || hipMalloc(&q->d_scr, scr.size() * 4) != hipSuccess ||
-      hipMalloc(&q->d_llr, B * g.llr_stride * 4) != hipSuccess || hipMalloc(&q->d_cand, B * MAX_CAND * sizeof(srslte_hip_dl_ctrl_cand_t)) != hipSuccess ||
-      hipMalloc(&q->d_ncand, B * 4) != hipSuccess || hipMemcpy(q->d_re, re.data(), re.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(q->d_scr, scr.data(), scr.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+  if (q->re.upload(re) || q->scr.upload(scr) || q->llr.alloc(B * g.llr_stride) || q->cand.alloc(B * MAX_CAND) || q->ncand.alloc(B) ||
       !(q->bc = bcast_tables_create(cfg, cfg->phich_ext, cfg->phich_resources, true))) {
     hip_log("[srslte_hip] srslte_hip_dl_ctrl_create: device allocation failed\n");
     srslte_hip_dl_ctrl_destroy(q);
     return nullptr;
   }
-  g.re = q->d_re, g.scr_pcfich = q->d_scr, g.scr_pdcch = q->d_scr + 10;
+  g.re = q->re.get(), g.scr_pcfich = q->scr.get(), g.scr_pdcch = q->scr.get() + 10;
   return q;
 }
 
@@ -458,12 +449,12 @@ int srslte_hip_dl_ctrl_batch(srslte_hip_dl_ctrl_t* q, const void* d_grid, const 
     memset(&r, 0, sizeof(r));
     for (uint32_t i = 0; i < n; i++) r.w[i] = reqs[s0 + i].rnti | reqs[s0 + i].tm << 16 | reqs[s0 + i].cfi << 20;
     hipLaunchKernelGGL(dl_ctrl_llr_kernel, dim3(n), dim3(256), 0, st, (const cf32*)d_grid, (const cf32*)d_ce, (const float*)d_res, tti0, (int)s0, r, q->g,
-                       q->d_llr, q->d_cand, q->d_ncand, d_out);
+                       q->llr.get(), q->cand.get(), q->ncand.get(), d_out);
     LAUNCH_CHECK();
   }
   for (uint32_t s0 = 0; s0 < nof_sf; s0 += DCI_CHUNK) { // gridDim.y stays below 65536 whatever max_batch is
     const uint32_t n = nof_sf - s0 < (uint32_t)DCI_CHUNK ? nof_sf - s0 : (uint32_t)DCI_CHUNK;
-    hipLaunchKernelGGL(dl_ctrl_dci_kernel, dim3(MAX_CAND, n), dim3(64), 0, st, q->d_llr, q->g.llr_stride, q->d_cand, q->d_ncand, (int)s0);
+    hipLaunchKernelGGL(dl_ctrl_dci_kernel, dim3(MAX_CAND, n), dim3(64), 0, st, q->llr.get(), q->g.llr_stride, q->cand.get(), q->ncand.get(), (int)s0);
     LAUNCH_CHECK();
   }
   for (uint32_t s0 = 0; s0 < nof_sf; s0 += REQ_CHUNK) {
@@ -471,7 +462,7 @@ int srslte_hip_dl_ctrl_batch(srslte_hip_dl_ctrl_t* q, const void* d_grid, const 
     CtrlReqs       r;
     memset(&r, 0, sizeof(r));
     for (uint32_t i = 0; i < n; i++) r.w[i] = reqs[s0 + i].rnti;
-    hipLaunchKernelGGL(dl_ctrl_select_kernel, dim3(ceil_div((int)n, 64)), dim3(64), 0, st, q->d_cand, q->d_ncand, (int)s0, r, (int)n, d_out, d_msg);
+    hipLaunchKernelGGL(dl_ctrl_select_kernel, dim3(ceil_div((int)n, 64)), dim3(64), 0, st, q->cand.get(), q->ncand.get(), (int)s0, r, (int)n, d_out, d_msg);
     LAUNCH_CHECK();
   }
   return SRSLTE_SUCCESS;
@@ -481,9 +472,9 @@ const void* srslte_hip_dl_ctrl_debug_buffer(const srslte_hip_dl_ctrl_t* q, int w
 {
   if (!q) return nullptr;
   switch (which) {
-    case 0: return q->d_llr;
-    case 1: return q->d_cand;
-    case 2: return q->d_ncand;
+    case 0: return q->llr.get();
+    case 1: return q->cand.get();
+    case 2: return q->ncand.get();
     default: return nullptr;
   }
 }

@@ -11,8 +11,8 @@
 #include "common.hpp"
 #include "ctrl_host.hpp"
 #include "ctrl_tx_dev.hpp"
+#include "dev_buf.hpp"
 #include "phy_hip_internal.hpp"
-#include "pinned_ring.hpp"
 #include <math.h>
 #include <string.h>
 #include <vector>
@@ -188,9 +188,8 @@ struct srslte_hip_dl_ctrl_tx {
   srslte_hip_dl_ctrl_tx_cfg_t cfg;
   CtrlTxGeom                  g;
   int                         nof_cce[3];
-  uint32_t *                  d_re = nullptr, *d_scr = nullptr, *d_desc = nullptr;
-  size_t                      desc_bytes = 0;
-  PinnedRing                  ring;
+  DevBuf<uint32_t>            re, scr;
+  DescStage                   desc;
   std::vector<uint32_t>       words;   // the descriptor block of a call, as it is built
   std::vector<uint8_t>        used;    // CCEs taken, per subframe
   std::vector<uint32_t>       ph_unit; // per PHICH of the call: its mapping unit
@@ -268,10 +267,6 @@ extern "C" {
 void srslte_hip_dl_ctrl_tx_destroy(srslte_hip_dl_ctrl_tx_t* q)
 {
   if (!q) return;
-  (void)hipFree(q->d_re);
-  (void)hipFree(q->d_scr);
-  (void)hipFree(q->d_desc);
-  q->ring.destroy();
   bcast_tables_destroy(q->bc);
   delete q;
 }
@@ -298,16 +293,14 @@ srslte_hip_dl_ctrl_tx_t* srslte_hip_dl_ctrl_tx_create(const srslte_hip_dl_ctrl_t
   g.s         = 1.0f / sqrtf(2.0f);
   std::vector<uint32_t> scr;
   ctrl_scrambling(cfg->cell_id, 72 * (uint32_t)q->nof_cce[2], scr, &g.scr_words);
-  q->desc_bytes = 4 * ((size_t)cfg->max_batch + (size_t)cfg->max_dci * (sizeof(DciTxDesc) / 4) + (size_t)cfg->max_batch * g.units + 1 + cfg->max_phich);
-  if (hipMalloc(&q->d_re, re.size() * 4) != hipSuccess || hipMalloc(&q->d_scr, scr.size() * 4) != hipSuccess ||
-      hipMalloc(&q->d_desc, q->desc_bytes) != hipSuccess || hipMemcpy(q->d_re, re.data(), re.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(q->d_scr, scr.data(), scr.size() * 4, hipMemcpyHostToDevice) != hipSuccess || q->ring.init(q->desc_bytes) != SRSLTE_SUCCESS ||
+  const size_t desc_bytes = 4 * ((size_t)cfg->max_batch + (size_t)cfg->max_dci * (sizeof(DciTxDesc) / 4) + (size_t)cfg->max_batch * g.units + 1 + cfg->max_phich);
+  if (q->re.upload(re) || q->scr.upload(scr) || q->desc.init(desc_bytes) ||
       !(q->bc = bcast_tables_create(&rc, cfg->phich_ext, cfg->phich_resources, false))) {
     hip_log("[srslte_hip] srslte_hip_dl_ctrl_tx_create: device allocation failed\n");
     srslte_hip_dl_ctrl_tx_destroy(q);
     return nullptr;
   }
-  g.re = q->d_re, g.scr_pcfich = q->d_scr, g.scr_pdcch = q->d_scr + 10;
+  g.re = q->re.get(), g.scr_pcfich = q->scr.get(), g.scr_pdcch = q->scr.get() + 10;
   return q;
 }
 
@@ -317,17 +310,16 @@ int srslte_hip_dl_ctrl_tx_put(srslte_hip_dl_ctrl_tx_t* q, uint32_t tti0, uint32_
   if (!q || !d_grid) return SRSLTE_ERROR_INVALID_INPUTS;
   if (int r = ctrl_tx_prepare(q, nof_sf, in, &ph_off, &ph_ent)) return r;
   if (nof_sf == 0) return SRSLTE_SUCCESS;
-  hipStream_t st    = (hipStream_t)stream;
-  uint8_t*    h_pin = nullptr;
-  if (int r = q->ring.acquire(&h_pin)) return r;
+  hipStream_t st = (hipStream_t)stream;
+  uint32_t*   h  = nullptr;
+  if (int r = q->desc.begin(&h)) return r;
   const size_t bytes = q->words.size() * 4;
-  memcpy(h_pin, q->words.data(), bytes);
-  HIP_TRY(hipMemcpyAsync(q->d_desc, h_pin, bytes, hipMemcpyHostToDevice, st));
-  if (int r = q->ring.release(st)) return r;
-  hipLaunchKernelGGL(dl_ctrl_tx_pcfich_phich_kernel, dim3(nof_sf), dim3(64), 0, st, (const uint32_t*)q->d_desc, ph_off, ph_ent, tti0, q->g, (cf32*)d_grid);
+  memcpy(h, q->words.data(), bytes);
+  if (int r = q->desc.commit(bytes, st)) return r;
+  hipLaunchKernelGGL(dl_ctrl_tx_pcfich_phich_kernel, dim3(nof_sf), dim3(64), 0, st, q->desc.dev<uint32_t>(), ph_off, ph_ent, tti0, q->g, (cf32*)d_grid);
   LAUNCH_CHECK();
   if (in->nof_dci) {
-    hipLaunchKernelGGL(dl_ctrl_tx_pdcch_kernel, dim3(in->nof_dci), dim3(64), 0, st, (const DciTxDesc*)(q->d_desc + nof_sf), tti0, q->g, (cf32*)d_grid);
+    hipLaunchKernelGGL(dl_ctrl_tx_pdcch_kernel, dim3(in->nof_dci), dim3(64), 0, st, (const DciTxDesc*)(q->desc.dev<uint32_t>() + nof_sf), tti0, q->g, (cf32*)d_grid);
     LAUNCH_CHECK();
   }
   return SRSLTE_SUCCESS;

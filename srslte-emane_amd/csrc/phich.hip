@@ -16,8 +16,8 @@
 #include "common.hpp"
 #include "ctrl_host.hpp"
 #include "ctrl_rx_dev.hpp"
+#include "dev_buf.hpp"
 #include "phy_hip_internal.hpp"
-#include "pinned_ring.hpp"
 #include <string.h>
 #include <vector>
 
@@ -198,22 +198,13 @@ __global__ __launch_bounds__(256) void dl_ctrl_ul_phich_kernel(const srslte_hip_
 // The PHICH receiver's tables and buffers of a srslte_hip_dl_ctrl_t, made by srslte_hip_dl_ctrl_set_max_phich
 struct PhichRx {
   uint32_t                 units = 0, ngroups = 0, max_phich = 0;
-  uint32_t*                d_re = nullptr;
-  uint32_t*                d_req = nullptr;
-  srslte_hip_phich_soft_t* d_soft = nullptr;
-  PinnedRing               ring;
+  DevBuf<uint32_t>         re;
+  DescStage                req;
+  DevBuf<srslte_hip_phich_soft_t> soft;
   std::vector<uint32_t>    words; // the requests of a call, as they are built
 };
 
-void phich_rx_destroy(PhichRx* t)
-{
-  if (!t) return;
-  (void)hipFree(t->d_re);
-  (void)hipFree(t->d_req);
-  (void)hipFree(t->d_soft);
-  t->ring.destroy();
-  delete t;
-}
+void phich_rx_destroy(PhichRx* t) { delete t; }
 
 namespace {
 
@@ -238,18 +229,17 @@ int phich_prepare(const srslte_hip_dl_ctrl_cfg_t& c, PhichRx* t, uint32_t nof_sf
 // the requests of t->words to the device through the pinned ring
 int phich_upload(PhichRx* t, uint32_t nof_phich, hipStream_t st)
 {
-  uint8_t* h_pin = nullptr;
-  if (int r = t->ring.acquire(&h_pin)) return r;
+  uint32_t* h = nullptr;
+  if (int r = t->req.begin(&h)) return r;
   const size_t bytes = 8 * (size_t)nof_phich;
-  memcpy(h_pin, t->words.data(), bytes);
-  HIP_TRY(hipMemcpyAsync(t->d_req, h_pin, bytes, hipMemcpyHostToDevice, st));
-  return t->ring.release(st);
+  memcpy(h, t->words.data(), bytes);
+  return t->req.commit(bytes, st);
 }
 
 PhichGeom phich_geom(const DlCtrlView& v, const PhichRx* t)
 {
   PhichGeom g;
-  g.re = t ? t->d_re : nullptr, g.scr = v.d_scr_pcfich;
+  g.re = t ? t->re.get() : nullptr, g.scr = v.d_scr_pcfich;
   g.nof_ports = (int)v.cfg->nof_ports, g.nof_rx = (int)v.cfg->nof_rx_antennas;
   g.grid_len = (v.cfg->cp_ext ? 12 : 14) * 12 * (int)v.cfg->nof_prb, g.cp_ext = v.cfg->cp_ext ? 1 : 0;
   return g;
@@ -272,10 +262,7 @@ int srslte_hip_dl_ctrl_set_max_phich(srslte_hip_dl_ctrl_t* q, uint32_t max_phich
   t->units     = regs.ngroups_m1;
   t->ngroups   = regs.ngroups_m1 * (v.cfg->cp_ext ? 2 : 1);
   t->max_phich = max_phich;
-  if (hipMalloc(&t->d_re, regs.phich.size() * 4) != hipSuccess || hipMalloc(&t->d_req, 8 * (size_t)max_phich) != hipSuccess ||
-      hipMalloc(&t->d_soft, sizeof(srslte_hip_phich_soft_t) * (size_t)max_phich) != hipSuccess ||
-      hipMemcpy(t->d_re, regs.phich.data(), regs.phich.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      t->ring.init(8 * (size_t)max_phich) != SRSLTE_SUCCESS) {
+  if (t->re.upload(regs.phich) || t->req.init(8 * (size_t)max_phich) || t->soft.alloc(max_phich)) {
     hip_log("[srslte_hip] srslte_hip_dl_ctrl_set_max_phich: device allocation failed\n");
     phich_rx_destroy(t);
     return SRSLTE_ERROR;
@@ -297,7 +284,7 @@ int srslte_hip_dl_ctrl_phich_batch(srslte_hip_dl_ctrl_t* q, const void* d_grid, 
   if (int r = phich_upload(t, nof_phich, st)) return r;
   hipLaunchKernelGGL(dl_ctrl_ul_phich_kernel, dim3(ceil_div((int)nof_phich, PH_BLOCK)), dim3(256), 0, st, v.d_cand, v.d_ncand, 0, UlReqs(), 0, 0,
                      (srslte_hip_dl_ctrl_ul_res_t*)nullptr, (srslte_hip_dci_msg_t*)nullptr, (const cf32*)d_grid, (const cf32*)d_ce, (const float*)d_res,
-                     tti0, phich_geom(v, t), (const uint32_t*)t->d_req, (int)nof_phich, d_phich_res, t->d_soft);
+                     tti0, phich_geom(v, t), t->req.dev<uint32_t>(), (int)nof_phich, d_phich_res, t->soft.get());
   LAUNCH_CHECK();
   return SRSLTE_SUCCESS;
 }
@@ -326,7 +313,7 @@ int srslte_hip_dl_ctrl_batch_ul(srslte_hip_dl_ctrl_t* q, const void* d_grid, con
     const int np = s0 == 0 ? (int)nof_phich : 0, ul_blocks = ceil_div((int)n, 256);
     hipLaunchKernelGGL(dl_ctrl_ul_phich_kernel, dim3(ul_blocks + ceil_div(np, PH_BLOCK)), dim3(256), 0, st, v.d_cand, v.d_ncand, (int)s0, r, (int)n,
                        ul_blocks, d_ul_out, d_ul_msg, (const cf32*)d_grid, (const cf32*)d_ce, (const float*)d_res, tti0, g,
-                       (const uint32_t*)(t ? t->d_req : nullptr), np, d_phich_res, t ? t->d_soft : nullptr);
+                       t ? t->req.dev<uint32_t>() : nullptr, np, d_phich_res, t ? t->soft.get() : nullptr);
     LAUNCH_CHECK();
   }
   return SRSLTE_SUCCESS;
@@ -336,7 +323,7 @@ const void* srslte_hip_dl_ctrl_phich_debug_buffer(const srslte_hip_dl_ctrl_t* q)
 {
   if (!q) return nullptr;
   const PhichRx* t = dl_ctrl_phich(q);
-  return t ? t->d_soft : nullptr;
+  return t ? t->soft.get() : nullptr;
 }
 
 } // extern "C"

@@ -9,9 +9,10 @@
 //                      twiddles in LDS, |.|^2, the mean and the first maximum of each window
 //   prach_pick_kernel  one workgroup per occasion: the peaks above detect_factor mean, placed in (root, window) order by a ballot prefix
 // Tables (sequence DFTs, twiddles) are made on the host once per object, in double, and kept as float.
+#include "cf32_dev.hpp"
 #include "common.hpp"
+#include "dev_buf.hpp"
 #include "phy_hip_internal.hpp"
-#include "pinned_ring.hpp"
 #include <math.h>
 #include <string.h>
 #include <vector>
@@ -91,15 +92,6 @@ struct PrachPeak {
   float    peak;
   uint32_t off;
 };
-
-__device__ __forceinline__ cf32 cmul(cf32 a, cf32 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ cf32 cmulconj(cf32 a, cf32 b) { return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); } // a conj(b)
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // the first occupied bin t of residue k1 (mod 12) and its k2: bins t = t0 + 12 j have transform index kb + t (mod N), = k1 + 12 (k2_0 + j) mod N
 __device__ __forceinline__ int first_bin(int k1, uint32_t kb) { return (k1 - (int)(kb % 12u) + 12) % 12; }
@@ -367,39 +359,12 @@ struct srslte_hip_prach {
   srslte_hip_prach_cfg_t  cfg;
   srslte_hip_prach_info_t info;
   PrachGeom               g;
-  cf32 *                  d_dft = nullptr, *d_tw = nullptr, *d_tw839 = nullptr, *d_bins = nullptr;
-  uint32_t*               d_roots = nullptr;
-  PrachPeak*              d_peaks = nullptr;
-  float*                  d_means = nullptr;
-  PrachGenDesc*           d_gen   = nullptr;
-  PrachOccDesc*           d_occ   = nullptr;
-  PinnedRing              ring;
+  DevBuf<cf32>            dft, tw, tw839, bins;
+  DevBuf<uint32_t>        roots;
+  DevBuf<PrachPeak>       peaks;
+  DevBuf<float>           means;
+  DescStage               gen, occ; // the generator's and the detector's descriptors
 };
-
-namespace {
-
-void prach_free(srslte_hip_prach* q)
-{
-  if (!q) return;
-  (void)hipFree(q->d_dft);
-  (void)hipFree(q->d_tw);
-  (void)hipFree(q->d_tw839);
-  (void)hipFree(q->d_bins);
-  (void)hipFree(q->d_roots);
-  (void)hipFree(q->d_peaks);
-  (void)hipFree(q->d_means);
-  (void)hipFree(q->d_gen);
-  (void)hipFree(q->d_occ);
-  q->ring.destroy();
-  delete q;
-}
-
-template <typename T> bool upload(T** d, const std::vector<T>& h)
-{
-  return hipMalloc((void**)d, sizeof(T) * h.size()) == hipSuccess && hipMemcpy(*d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice) == hipSuccess;
-}
-
-} // namespace
 
 extern "C" {
 
@@ -436,21 +401,17 @@ srslte_hip_prach_t* srslte_hip_prach_create(const srslte_hip_prach_cfg_t* cfg)
   for (int k = 0; k < NZC; k++) tw839[k] = make_float2((float)cos(2 * M_PI * k / NZC), (float)-sin(2 * M_PI * k / NZC));
   std::vector<uint32_t> roots(in.root_seqs_idx, in.root_seqs_idx + in.nof_roots);
   const size_t          n_occ = cfg->max_occasions ? cfg->max_occasions : 1, n_pre = cfg->max_preambles ? cfg->max_preambles : 1;
-  const size_t          ring_bytes = std::max(n_occ * sizeof(PrachOccDesc), n_pre * sizeof(PrachGenDesc));
-  if (!upload(&q->d_dft, dft) || !upload(&q->d_tw, tw) || !upload(&q->d_tw839, tw839) || !upload(&q->d_roots, roots) ||
-      hipMalloc((void**)&q->d_bins, sizeof(cf32) * NZC * n_occ) != hipSuccess ||
-      hipMalloc((void**)&q->d_peaks, sizeof(PrachPeak) * in.max_det * n_occ) != hipSuccess ||
-      hipMalloc((void**)&q->d_means, sizeof(float) * in.nof_roots * n_occ) != hipSuccess ||
-      hipMalloc((void**)&q->d_gen, sizeof(PrachGenDesc) * n_pre) != hipSuccess ||
-      hipMalloc((void**)&q->d_occ, sizeof(PrachOccDesc) * n_occ) != hipSuccess || q->ring.init(ring_bytes) != SRSLTE_SUCCESS) {
+  if (q->dft.upload(dft) || q->tw.upload(tw) || q->tw839.upload(tw839) || q->roots.upload(roots) || q->bins.alloc(NZC * n_occ) ||
+      q->peaks.alloc(in.max_det * n_occ) || q->means.alloc(in.nof_roots * n_occ) || q->gen.init(sizeof(PrachGenDesc) * n_pre) ||
+      q->occ.init(sizeof(PrachOccDesc) * n_occ)) {
     hip_log("[srslte_hip] prach: device allocation failed\n");
-    prach_free(q);
+    delete q;
     return nullptr;
   }
   return q;
 }
 
-void srslte_hip_prach_destroy(srslte_hip_prach_t* q) { prach_free(q); }
+void srslte_hip_prach_destroy(srslte_hip_prach_t* q) { delete q; }
 
 int srslte_hip_prach_info(const srslte_hip_prach_t* q, srslte_hip_prach_info_t* info)
 {
@@ -464,15 +425,13 @@ int srslte_hip_prach_gen_batch(srslte_hip_prach_t* q, const srslte_hip_prach_tx_
   if (!q || (n && !d_out)) return SRSLTE_ERROR_INVALID_INPUTS;
   if (int r = gen_check(&q->cfg, q->info, list, n)) return r;
   if (n == 0) return SRSLTE_SUCCESS;
-  hipStream_t st    = (hipStream_t)stream;
-  uint8_t*    h_pin = nullptr;
-  if (int r = q->ring.acquire(&h_pin)) return r;
-  auto* h = reinterpret_cast<PrachGenDesc*>(h_pin);
+  hipStream_t   st = (hipStream_t)stream;
+  PrachGenDesc* h  = nullptr;
+  if (int r = q->gen.begin(&h)) return r;
   for (uint32_t i = 0; i < n; i++) h[i] = {list[i].seq_index, prach_kb(q->info, list[i].freq_offset)};
-  HIP_TRY(hipMemcpyAsync(q->d_gen, h_pin, sizeof(PrachGenDesc) * n, hipMemcpyHostToDevice, st));
-  if (int r = q->ring.release(st)) return r;
-  hipLaunchKernelGGL(prach_gen_kernel, dim3(ceil_div(q->g.M, 256), n), dim3(256), 0, st, q->g, (const cf32*)q->d_dft, (const cf32*)q->d_tw,
-                     (const PrachGenDesc*)q->d_gen, (cf32*)d_out);
+  if (int r = q->gen.commit(sizeof(PrachGenDesc) * n, st)) return r;
+  hipLaunchKernelGGL(prach_gen_kernel, dim3(ceil_div(q->g.M, 256), n), dim3(256), 0, st, q->g, (const cf32*)q->dft.get(), (const cf32*)q->tw.get(),
+                     q->gen.dev<PrachGenDesc>(), (cf32*)d_out);
   LAUNCH_CHECK();
   return SRSLTE_SUCCESS;
 }
@@ -483,21 +442,19 @@ int srslte_hip_prach_detect_batch(srslte_hip_prach_t* q, const void* d_signal, s
   if (!q || (n && (!d_signal || !d_nof_det || !d_indices))) return SRSLTE_ERROR_INVALID_INPUTS;
   if (int r = detect_check(&q->cfg, q->info, sig_len, occ, n)) return r;
   if (n == 0) return SRSLTE_SUCCESS;
-  hipStream_t st    = (hipStream_t)stream;
-  uint8_t*    h_pin = nullptr;
-  if (int r = q->ring.acquire(&h_pin)) return r;
-  auto* h = reinterpret_cast<PrachOccDesc*>(h_pin);
+  hipStream_t   st = (hipStream_t)stream;
+  PrachOccDesc* h  = nullptr;
+  if (int r = q->occ.begin(&h)) return r;
   for (uint32_t i = 0; i < n; i++) h[i] = {occ[i].sample, prach_kb(q->info, occ[i].freq_offset), 0u};
-  HIP_TRY(hipMemcpyAsync(q->d_occ, h_pin, sizeof(PrachOccDesc) * n, hipMemcpyHostToDevice, st));
-  if (int r = q->ring.release(st)) return r;
-  hipLaunchKernelGGL(prach_fwd_kernel, dim3(12, n), dim3(256), 0, st, q->g, (const cf32*)d_signal, (const cf32*)q->d_tw, (const PrachOccDesc*)q->d_occ,
-                     q->d_bins);
+  if (int r = q->occ.commit(sizeof(PrachOccDesc) * n, st)) return r;
+  hipLaunchKernelGGL(prach_fwd_kernel, dim3(12, n), dim3(256), 0, st, q->g, (const cf32*)d_signal, (const cf32*)q->tw.get(), q->occ.dev<PrachOccDesc>(),
+                     q->bins.get());
   LAUNCH_CHECK();
-  hipLaunchKernelGGL(prach_corr_kernel, dim3(q->info.nof_roots, n), dim3(256), 0, st, q->g, (const cf32*)q->d_bins, (const cf32*)q->d_dft,
-                     (const cf32*)q->d_tw839, (const uint32_t*)q->d_roots, q->d_peaks, q->d_means);
+  hipLaunchKernelGGL(prach_corr_kernel, dim3(q->info.nof_roots, n), dim3(256), 0, st, q->g, (const cf32*)q->bins.get(), (const cf32*)q->dft.get(),
+                     (const cf32*)q->tw839.get(), (const uint32_t*)q->roots.get(), q->peaks.get(), q->means.get());
   LAUNCH_CHECK();
-  hipLaunchKernelGGL(prach_pick_kernel, dim3(1, n), dim3(128), 0, st, q->g, (const PrachPeak*)q->d_peaks, (const float*)q->d_means, d_nof_det, d_indices,
-                     d_t_offsets, d_peak_to_avg);
+  hipLaunchKernelGGL(prach_pick_kernel, dim3(1, n), dim3(128), 0, st, q->g, (const PrachPeak*)q->peaks.get(), (const float*)q->means.get(), d_nof_det,
+                     d_indices, d_t_offsets, d_peak_to_avg);
   LAUNCH_CHECK();
   return SRSLTE_SUCCESS;
 }

@@ -4,11 +4,12 @@
 //   ul_pucch_tx_kernel  one wavefront per request: encode_signal_format12 + pucch_put and srslte_refsignal_dmrs_pucch_gen / _put
 // The format and resource of a request are chosen on the host when the call is made (srslte_ue_ul_pucch_resource_selection); the device
 // derives the cyclic shifts from integer state and the per-(slot, symbol) tables the object keeps.
+#include "cf32_dev.hpp"
 #include "common.hpp"
 #include "ctrl_rx_dev.hpp"
 #include "demod_dev.hpp"
+#include "dev_buf.hpp"
 #include "phy_hip_internal.hpp"
-#include "pinned_ring.hpp"
 #include <math.h>
 #include <string.h>
 #include <vector>
@@ -56,21 +57,11 @@ struct PucchTxDesc {
   float    d0[2], z1[2];
 };
 
-__device__ __forceinline__ cf32 cmul(cf32 a, cf32 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ cf32 cmulconj(cf32 a, cf32 b) { return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); } // a conj(b)
-__device__ __forceinline__ cf32 cadd(cf32 a, cf32 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ cf32 cscale(cf32 a, float s) { return make_float2(a.x * s, a.y * s); }
 __device__ __forceinline__ cf32 cexpi(float x)
 {
   float s, c;
   sincosf(x, &s, &c);
   return make_float2(c, s);
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // get_N_sf (pucch.c:314-339) for formats 1-2b
@@ -547,25 +538,13 @@ bool req_ok(const srslte_hip_pucch_req_t& q, uint32_t nof_sf)
 struct srslte_hip_ul_ctrl {
   srslte_hip_ul_ctrl_cfg_t cfg;
   UlCtrlGeom               g;
-  UlCtrlTab*               d_tab  = nullptr;
-  void*                    d_desc = nullptr;
-  cf32*                    d_z    = nullptr;
-  short*                   d_llr  = nullptr;
-  PinnedRing               ring;
+  DevBuf<UlCtrlTab>        tab;
+  DescStage                desc;
+  DevBuf<cf32>             z;   // the receiver's alone, as llr
+  DevBuf<short>            llr;
 };
 
 namespace {
-
-void ul_ctrl_free(srslte_hip_ul_ctrl* q)
-{
-  if (!q) return;
-  (void)hipFree(q->d_tab);
-  (void)hipFree(q->d_desc);
-  (void)hipFree(q->d_z);
-  (void)hipFree(q->d_llr);
-  q->ring.destroy();
-  delete q;
-}
 
 srslte_hip_ul_ctrl* ul_ctrl_make(const srslte_hip_ul_ctrl_cfg_t* cfg, bool rx)
 {
@@ -578,12 +557,9 @@ srslte_hip_ul_ctrl* ul_ctrl_make(const srslte_hip_ul_ctrl_cfg_t* cfg, bool rx)
   UlCtrlTab t;
   build_tab(cfg, t);
   const size_t desc_bytes = (size_t)cfg->max_pucch * (rx ? sizeof(PucchDesc) : sizeof(PucchTxDesc));
-  if (hipMalloc((void**)&q->d_tab, sizeof(t)) != hipSuccess || hipMemcpy(q->d_tab, &t, sizeof(t), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMalloc(&q->d_desc, desc_bytes) != hipSuccess || q->ring.init(desc_bytes) != SRSLTE_SUCCESS ||
-      (rx && (hipMalloc((void**)&q->d_z, sizeof(cf32) * MAX_RE * cfg->max_pucch) != hipSuccess ||
-              hipMalloc((void**)&q->d_llr, sizeof(short) * 20 * cfg->max_pucch) != hipSuccess))) {
+  if (q->tab.upload(&t, 1) || q->desc.init(desc_bytes) || (rx && (q->z.alloc((size_t)MAX_RE * cfg->max_pucch) || q->llr.alloc((size_t)20 * cfg->max_pucch)))) {
     hip_log("[srslte_hip] ul_ctrl: device allocation failed\n");
-    ul_ctrl_free(q);
+    delete q;
     return nullptr;
   }
   UlCtrlGeom& g = q->g;
@@ -683,28 +659,27 @@ int ul_ctrl_check(const srslte_hip_ul_ctrl_t* q, uint32_t nof_sf, const srslte_h
 
 bool ul_ctrl_same_cell(const srslte_hip_ul_ctrl_t* q, uint32_t nof_prb, uint32_t cell_id, int cp_ext)
 {
-  return q && q->d_z && q->cfg.nof_prb == nof_prb && q->cfg.cell_id == cell_id && (q->cfg.cp_ext ? 1 : 0) == (cp_ext ? 1 : 0);
+  return q && q->z.get() && q->cfg.nof_prb == nof_prb && q->cfg.cell_id == cell_id && (q->cfg.cp_ext ? 1 : 0) == (cp_ext ? 1 : 0);
 }
 
 extern "C" {
 
 srslte_hip_ul_ctrl_t* srslte_hip_ul_ctrl_create(const srslte_hip_ul_ctrl_cfg_t* cfg) { return ul_ctrl_make(cfg, true); }
-void                  srslte_hip_ul_ctrl_destroy(srslte_hip_ul_ctrl_t* q) { ul_ctrl_free(q); }
+void                  srslte_hip_ul_ctrl_destroy(srslte_hip_ul_ctrl_t* q) { delete q; }
 
 int srslte_hip_ul_ctrl_pucch_batch(srslte_hip_ul_ctrl_t* q, const void* d_grid, uint32_t tti0, uint32_t nof_sf, const srslte_hip_pucch_req_t* reqs,
                                    uint32_t nof, srslte_hip_pucch_res_t* d_res, void* stream)
 {
-  if (!q || !q->d_z || !d_grid || (nof && !d_res)) return SRSLTE_ERROR_INVALID_INPUTS;
+  if (!q || !q->z.get() || !d_grid || (nof && !d_res)) return SRSLTE_ERROR_INVALID_INPUTS;
   if (int r = ul_ctrl_build(q, nof_sf, reqs, nof, nullptr)) return r;
   if (nof == 0) return SRSLTE_SUCCESS;
-  hipStream_t st    = (hipStream_t)stream;
-  uint8_t*    h_pin = nullptr;
-  if (int r = q->ring.acquire(&h_pin)) return r;
-  ul_ctrl_build(q, nof_sf, reqs, nof, reinterpret_cast<PucchDesc*>(h_pin));
-  HIP_TRY(hipMemcpyAsync(q->d_desc, h_pin, sizeof(PucchDesc) * nof, hipMemcpyHostToDevice, st));
-  if (int r = q->ring.release(st)) return r;
-  hipLaunchKernelGGL(ul_pucch_rx_kernel, dim3(nof), dim3(64), 0, st, (const UlCtrlTab*)q->d_tab, q->g, (const PucchDesc*)q->d_desc, (const cf32*)d_grid,
-                     tti0, d_res, q->d_z, q->d_llr);
+  hipStream_t st = (hipStream_t)stream;
+  PucchDesc*  h  = nullptr;
+  if (int r = q->desc.begin(&h)) return r;
+  ul_ctrl_build(q, nof_sf, reqs, nof, h);
+  if (int r = q->desc.commit(sizeof(PucchDesc) * nof, st)) return r;
+  hipLaunchKernelGGL(ul_pucch_rx_kernel, dim3(nof), dim3(64), 0, st, (const UlCtrlTab*)q->tab.get(), q->g, q->desc.dev<PucchDesc>(), (const cf32*)d_grid,
+                     tti0, d_res, q->z.get(), q->llr.get());
   LAUNCH_CHECK();
   return SRSLTE_SUCCESS;
 }
@@ -712,14 +687,14 @@ int srslte_hip_ul_ctrl_pucch_batch(srslte_hip_ul_ctrl_t* q, const void* d_grid, 
 const void* srslte_hip_ul_ctrl_debug_buffer(const srslte_hip_ul_ctrl_t* q, int which)
 {
   if (!q) return nullptr;
-  return which == 0 ? (const void*)q->d_z : which == 1 ? (const void*)q->d_llr : nullptr;
+  return which == 0 ? (const void*)q->z.get() : which == 1 ? (const void*)q->llr.get() : nullptr;
 }
 
 srslte_hip_ul_ctrl_tx_t* srslte_hip_ul_ctrl_tx_create(const srslte_hip_ul_ctrl_cfg_t* cfg)
 {
   return reinterpret_cast<srslte_hip_ul_ctrl_tx_t*>(ul_ctrl_make(cfg, false));
 }
-void srslte_hip_ul_ctrl_tx_destroy(srslte_hip_ul_ctrl_tx_t* q) { ul_ctrl_free(reinterpret_cast<srslte_hip_ul_ctrl*>(q)); }
+void srslte_hip_ul_ctrl_tx_destroy(srslte_hip_ul_ctrl_tx_t* q) { delete reinterpret_cast<srslte_hip_ul_ctrl*>(q); }
 
 int srslte_hip_ul_ctrl_tx_put_pucch(srslte_hip_ul_ctrl_tx_t* qt, uint32_t tti0, uint32_t nof_sf, const srslte_hip_pucch_tx_t* tx, uint32_t nof,
                                     void* d_grid, void* stream)
@@ -728,13 +703,12 @@ int srslte_hip_ul_ctrl_tx_put_pucch(srslte_hip_ul_ctrl_tx_t* qt, uint32_t tti0, 
   if (!q || !d_grid || (nof && !tx) || nof > q->cfg.max_pucch) return SRSLTE_ERROR_INVALID_INPUTS;
   if (int r = ul_ctrl_tx_build(q, nof_sf, tx, nof, nullptr)) return r;
   if (nof == 0) return SRSLTE_SUCCESS;
-  hipStream_t st    = (hipStream_t)stream;
-  uint8_t*    h_pin = nullptr;
-  if (int r = q->ring.acquire(&h_pin)) return r;
-  ul_ctrl_tx_build(q, nof_sf, tx, nof, reinterpret_cast<PucchTxDesc*>(h_pin));
-  HIP_TRY(hipMemcpyAsync(q->d_desc, h_pin, sizeof(PucchTxDesc) * nof, hipMemcpyHostToDevice, st));
-  if (int r = q->ring.release(st)) return r;
-  hipLaunchKernelGGL(ul_pucch_tx_kernel, dim3(nof), dim3(64), 0, st, (const UlCtrlTab*)q->d_tab, q->g, (const PucchTxDesc*)q->d_desc, tti0, (cf32*)d_grid);
+  hipStream_t  st = (hipStream_t)stream;
+  PucchTxDesc* h  = nullptr;
+  if (int r = q->desc.begin(&h)) return r;
+  ul_ctrl_tx_build(q, nof_sf, tx, nof, h);
+  if (int r = q->desc.commit(sizeof(PucchTxDesc) * nof, st)) return r;
+  hipLaunchKernelGGL(ul_pucch_tx_kernel, dim3(nof), dim3(64), 0, st, (const UlCtrlTab*)q->tab.get(), q->g, q->desc.dev<PucchTxDesc>(), tti0, (cf32*)d_grid);
   LAUNCH_CHECK();
   return SRSLTE_SUCCESS;
 }

@@ -6,9 +6,10 @@
 //                  h_{j+1} conj(h_j) (the neighbour lane's h, through LDS across the wavefront boundary at J > 64) summed in the wavefront and
 //                  then over the two wavefronts; lane 0 writes the record
 // The sequences come from srs_host.cpp: the first slot's of each subframe of a frame per (M_sc, n_srs), made on first use and kept.
+#include "cf32_dev.hpp"
 #include "common.hpp"
+#include "dev_buf.hpp"
 #include "phy_hip_internal.hpp"
-#include "pinned_ring.hpp"
 #include <map>
 #include <math.h>
 #include <vector>
@@ -25,15 +26,7 @@ struct SrsDesc {
   uint32_t    reserved;
 };
 
-__device__ __forceinline__ cf32 cmulconj(cf32 a, cf32 b) { return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); } // a conj(b)
-__device__ __forceinline__ cf32 cadd(cf32 a, cf32 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ cf32 csub(cf32 a, cf32 b) { return make_float2(a.x - b.x, a.y - b.y); }
 __device__ __forceinline__ cf32 mulmj(cf32 a) { return make_float2(a.y, -a.x); } // -j a
-__device__ __forceinline__ float wave_sum(float v)
-{
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // forward 4-point DFT: X[k] = sum_n x[n] exp(-j 2 pi k n / 4)
 __device__ __forceinline__ void dft4(cf32 a, cf32 b, cf32 c, cf32 d, cf32 X[4])
@@ -114,9 +107,8 @@ __global__ __launch_bounds__(SRS_RX_THREADS) void srs_rx_kernel(const SrsDesc* _
 struct srslte_hip_srs {
   srslte_hip_srs_cfg_t cfg;
   uint32_t             nsym;
-  SrsDesc*             d_desc = nullptr;
-  PinnedRing           ring;
-  std::map<std::pair<uint32_t, uint32_t>, cf32*> tables; // (M_sc, n_srs) -> [10][M_sc], every one seen so far
+  DescStage            desc;
+  std::map<std::pair<uint32_t, uint32_t>, DevBuf<cf32>> tables; // (M_sc, n_srs) -> [10][M_sc], every one seen so far
 };
 
 namespace {
@@ -127,20 +119,18 @@ int srs_table_cached(srslte_hip_srs* q, uint32_t M_sc, uint32_t n_srs, const cf3
   if (it == q->tables.end()) {
     std::vector<cf32> r;
     srs_first_slot_table(&q->cfg, M_sc, n_srs, r);
-    cf32* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, sizeof(cf32) * r.size()));
-    if (hipMemcpy(d, r.data(), sizeof(cf32) * r.size(), hipMemcpyHostToDevice) != hipSuccess) {
-      (void)hipFree(d);
+    DevBuf<cf32> d;
+    if (d.upload(r)) {
       hip_log("[srslte_hip] srs: the upload of a sequence table failed\n");
       return SRSLTE_ERROR;
     }
-    it = q->tables.emplace(std::make_pair(M_sc, n_srs), d).first;
+    it = q->tables.emplace(std::make_pair(M_sc, n_srs), std::move(d)).first;
   }
-  *d_r = it->second;
+  *d_r = it->second.get();
   return SRSLTE_SUCCESS;
 }
 
-// checks, tables and descriptors of a call; the descriptors are on their way to q->d_desc when it returns
+// checks, tables and descriptors of a call; the descriptors are on their way to the device when it returns
 int srs_stage(srslte_hip_srs* q, uint32_t tti0, uint32_t nof_sf, const srslte_hip_srs_ue_t* list, uint32_t nof, hipStream_t st)
 {
   if (int r = srs_list_check(&q->cfg, tti0, nof_sf, list, nof)) return r;
@@ -148,9 +138,8 @@ int srs_stage(srslte_hip_srs* q, uint32_t tti0, uint32_t nof_sf, const srslte_hi
   std::vector<const cf32*> tab(nof);
   for (uint32_t i = 0; i < nof; i++)
     if (int r = srs_table_cached(q, srslte_hip_srs_M_sc(&q->cfg, &list[i]), list[i].n_srs, &tab[i])) return r;
-  uint8_t* h_pin = nullptr;
-  if (int r = q->ring.acquire(&h_pin)) return r;
-  auto*          h   = reinterpret_cast<SrsDesc*>(h_pin);
+  SrsDesc* h = nullptr;
+  if (int r = q->desc.begin(&h)) return r;
   const uint32_t nre = 12 * q->cfg.nof_prb;
   for (uint32_t i = 0; i < nof; i++) {
     const srslte_hip_srs_ue_t& ue  = list[i];
@@ -160,8 +149,7 @@ int srs_stage(srslte_hip_srs* q, uint32_t tti0, uint32_t nof_sf, const srslte_hi
       if (!(ue.cs_used >> ((ue.n_srs + k) % 8) & 1u)) fb |= 1u << k;
     h[i] = {tab[i] + (size_t)(tti % 10) * M_sc, (ue.sf * q->nsym + q->nsym - 1) * nre + srslte_hip_srs_k0(&q->cfg, &ue, tti), M_sc, fb, 0u};
   }
-  HIP_TRY(hipMemcpyAsync(q->d_desc, h_pin, sizeof(SrsDesc) * nof, hipMemcpyHostToDevice, st));
-  return q->ring.release(st);
+  return q->desc.commit(sizeof(SrsDesc) * nof, st);
 }
 
 } // namespace
@@ -185,22 +173,15 @@ srslte_hip_srs_t* srslte_hip_srs_create(const srslte_hip_srs_cfg_t* cfg)
   q->cfg   = *cfg;
   q->nsym  = cfg->cp_ext ? 12 : 14;
   const size_t n = cfg->max_srs ? cfg->max_srs : 1;
-  if (hipMalloc((void**)&q->d_desc, sizeof(SrsDesc) * n) != hipSuccess || q->ring.init(sizeof(SrsDesc) * n) != SRSLTE_SUCCESS) {
+  if (q->desc.init(sizeof(SrsDesc) * n)) {
     hip_log("[srslte_hip] srs: device allocation failed\n");
-    srslte_hip_srs_destroy(q);
+    delete q;
     return nullptr;
   }
   return q;
 }
 
-void srslte_hip_srs_destroy(srslte_hip_srs_t* q)
-{
-  if (!q) return;
-  for (auto& kv : q->tables) (void)hipFree(kv.second);
-  (void)hipFree(q->d_desc);
-  q->ring.destroy();
-  delete q;
-}
+void srslte_hip_srs_destroy(srslte_hip_srs_t* q) { delete q; }
 
 int srslte_hip_srs_tx_put(srslte_hip_srs_t* q, uint32_t tti0, uint32_t nof_sf, const srslte_hip_srs_ue_t* list, uint32_t nof, void* d_grid, void* stream)
 {
@@ -208,7 +189,7 @@ int srslte_hip_srs_tx_put(srslte_hip_srs_t* q, uint32_t tti0, uint32_t nof_sf, c
   hipStream_t st = (hipStream_t)stream;
   if (int r = srs_stage(q, tti0, nof_sf, list, nof, st)) return r;
   if (nof == 0) return SRSLTE_SUCCESS;
-  hipLaunchKernelGGL(srs_tx_kernel, dim3(nof), dim3(256), 0, st, (const SrsDesc*)q->d_desc, (cf32*)d_grid);
+  hipLaunchKernelGGL(srs_tx_kernel, dim3(nof), dim3(256), 0, st, q->desc.dev<SrsDesc>(), (cf32*)d_grid);
   LAUNCH_CHECK();
   return SRSLTE_SUCCESS;
 }
@@ -220,7 +201,7 @@ int srslte_hip_srs_rx_batch(srslte_hip_srs_t* q, const void* d_grid, uint32_t tt
   hipStream_t st = (hipStream_t)stream;
   if (int r = srs_stage(q, tti0, nof_sf, list, nof, st)) return r;
   if (nof == 0) return SRSLTE_SUCCESS;
-  hipLaunchKernelGGL(srs_rx_kernel, dim3(nof), dim3(SRS_RX_THREADS), 0, st, (const SrsDesc*)q->d_desc, (const cf32*)d_grid, d_res, (cf32*)d_ce);
+  hipLaunchKernelGGL(srs_rx_kernel, dim3(nof), dim3(SRS_RX_THREADS), 0, st, q->desc.dev<SrsDesc>(), (const cf32*)d_grid, d_res, (cf32*)d_ce);
   LAUNCH_CHECK();
   return SRSLTE_SUCCESS;
 }
