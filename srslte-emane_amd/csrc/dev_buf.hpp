@@ -1,5 +1,6 @@
-// Owners of the control and auxiliary modules' device memory: an object struct holds these, and destroying the object is `delete`.
-// Neither prints: a constructor reports a failed one with its module's own "device allocation failed" line.
+// Owners of the objects' device and pinned memory (the pipelines of pdsch.hip, the control and auxiliary modules): an object struct holds
+// these, and destroying the object is `delete`.
+// None prints: a constructor reports a failed one with its module's own "device allocation failed" / "initialisation failed" line.
 #pragma once
 #include "common.hpp"
 #include "pinned_ring.hpp"
@@ -40,14 +41,35 @@ public:
 
   T*     get() const { return p_; }
   size_t size() const { return n_; }
+  // reads like the raw pointer it replaces: a launch argument, pointer arithmetic, a test for "present". Not copyable, so handing the owner
+  // itself to a kernel by value does not compile. get() where a cast changes the pointee type
+  operator T*() const { return p_; }
 
 private:
   T*     p_ = nullptr;
   size_t n_ = 0;
 };
 
+// One hipHostMalloc block of `bytes` bytes
+class PinBuf
+{
+public:
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() { (void)hipHostFree(p_); }
+  int      alloc(size_t bytes) { return hipHostMalloc((void**)&p_, bytes) == hipSuccess ? SRSLTE_SUCCESS : SRSLTE_ERROR; }
+  uint8_t* get() const { return p_; }
+  operator uint8_t*() const { return p_; }
+
+private:
+  uint8_t* p_ = nullptr;
+};
+
 // A call's descriptors on their way to the device: the pinned ring they are built in and the device block the kernels read them from.
 //   D* h; begin(&h); fill h[0..n); commit(sizeof(D) * n, st); launch with dev<D>()
+// Where a kernel of the call reads the pinned buffer itself and writes the device block (dev_bytes()), that launch stands for the copy:
+//   begin(&h); fill; the caller's launch on st; committed(st)
 struct DescStage {
   int init(size_t bytes)
   {
@@ -67,6 +89,9 @@ struct DescStage {
     HIP_TRY(hipMemcpyAsync(dev_.get(), pin_, bytes, hipMemcpyHostToDevice, st));
     return ring_.release(st);
   }
+  // the kernel-read variant: what st holds so far is the last reader of the buffer begin() handed out
+  int committed(hipStream_t st) { return ring_.release(st); }
+  uint8_t* dev_bytes() const { return dev_.get(); }
   template <typename D> const D* dev() const { return reinterpret_cast<const D*>(dev_.get()); }
 
   DescStage() = default;

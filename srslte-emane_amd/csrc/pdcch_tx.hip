@@ -7,7 +7,7 @@
 //                                   convolutional code, srslte_rm_conv_tx, scrambling, QPSK, layer mapping + precoding, the put on its CCEs
 // Every value is the reference's exactly: the modulator levels, products with +-1 / +-j and the precoding's 1/sqrt(2), and the PHICH sums in
 // entry order. The REG lists and sequences are built on the host when the object is made (ctrl_host.cpp); the per-call descriptors travel
-// through a PinnedRing.
+// through a DescStage (dev_buf.hpp).
 #include "common.hpp"
 #include "ctrl_host.hpp"
 #include "ctrl_tx_dev.hpp"

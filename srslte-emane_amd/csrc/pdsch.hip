@@ -20,12 +20,13 @@
 // through LDS with 16-byte stores: 16 B read and Qm * sizeof(LLR) B written per RE, no intermediate d/e round trips through HBM.
 #include "common.hpp"
 #include "demod_dev.hpp"
+#include "dev_buf.hpp"
 #include "phy_hip_internal.hpp"
-#include "pinned_ring.hpp"
 #include "viterbi_dev.hpp"
 #include <algorithm>
 #include <map>
 #include <math.h>
+#include <memory>
 #include <string.h>
 
 // One translation unit (the kernels share templates, descriptor structs and anonymous-namespace helpers), kept in fragments by pipeline:

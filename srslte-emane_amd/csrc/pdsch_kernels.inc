@@ -1061,17 +1061,20 @@ void pdsch_re_indices(uint32_t cell_id, uint32_t nof_prb, uint32_t nof_ports, ui
   }
 }
 
+// an empty vector still gets one element: the objects test these buffers for "present"
 template <typename T>
-int upload(T** d, const std::vector<T>& h)
+int upload(DevBuf<T>& d, const std::vector<T>& h)
 {
-  HIP_TRY(hipMalloc((void**)d, sizeof(T) * (h.size() ? h.size() : 1)));
-  HIP_TRY(hipMemcpy(*d, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
+  if (h.empty() ? d.alloc(1) : d.upload(h)) {
+    hip_log("[srslte_hip] upload of a %zu-byte table to the device failed\n", sizeof(T) * h.size());
+    return SRSLTE_ERROR;
+  }
   return SRSLTE_SUCCESS;
 }
 
 // rate de-matching table of (K, rv) (rm_turbo.c:160-260) in the turbo decoder's input layout, as rm_slot_table's slot table of w_stride; W != 0:
 // the windowed decoders' layout (stream s at s (K + 32), bit i at (i % (K / W)) W + i / (K / W), the tails behind the three streams)
-int rm_rx_table_upload(uint32_t K, uint32_t rv, uint32_t W, uint32_t w_stride, uint32_t** d_tbl)
+int rm_rx_table_upload(uint32_t K, uint32_t rv, uint32_t W, uint32_t w_stride, DevBuf<uint32_t>& d_tbl)
 {
   std::vector<uint32_t> t;
   lte_rm_rx_table(K, rv, t);
@@ -1083,7 +1086,7 @@ int rm_rx_table_upload(uint32_t K, uint32_t rv, uint32_t W, uint32_t w_stride, u
 
 // rate matching table of (K, rv) (rm_turbo.c:100-158): the coded bit of each circular-buffer position from k0(rv) on, addressed in the encoder's
 // byte streams (systematic byte p, tail bit (1 << 30) | p - K, parity bytes (2 << 30) | p of stream 1, K + 4 + p of stream 2)
-int rm_tx_table_upload(uint32_t K, uint32_t rv, uint32_t** d_tbl)
+int rm_tx_table_upload(uint32_t K, uint32_t rv, DevBuf<uint32_t>& d_tbl)
 {
   std::vector<uint32_t> t;
   lte_rm_rx_table(K, rv, t);

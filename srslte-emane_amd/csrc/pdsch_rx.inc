@@ -2,77 +2,67 @@
 // grids) and the state of the grants modes.
 // Device / host resources of the per-subframe-grant mode (srslte_hip_dl_rx_batch_grants)
 struct GrantsState {
-  srslte_hip_tdec_t* tdec;       // any block length up to 6144
-  uint32_t           Cmax, stride, max_re, max_bits, words;
-  uint32_t           V; // per-subframe slots: max_batch, twice that on a cell where two-layer grants can occur (codeword 1 of subframe b: slot max_batch + b)
-  uint32_t *         d_relist, *d_scr, *d_basis, *d_cb_iters;
-  int16_t *          d_e, *d_w;
-  uint8_t *          d_cb_bytes, *d_cb_ok, *d_desc;
-  float*             d_csi;     // [B][max_re], cfg.csi_enable
-  uint32_t*          d_csi_max; // [B]
-  size_t             desc_bytes;
-  PinnedRing         ring; // the host copies of the descriptor block, desc_bytes + 16 each
-  bool               tb_direct; // 16-bit calls: the decoders assemble the transport blocks (environment SRSLTE_HIP_GRANTS_TB_DIRECT=0: the assembly kernel, for A/B and tests)
-  std::map<std::pair<uint32_t, uint32_t>, uint32_t*>   rm_tbl; // (K, rv) -> slot table in the layout of that K's decoder
-  std::map<uint32_t, uint32_t*>                        crc_fac; // tbs -> tb_crc_bytes_kernel's 256 chunk weights
+  srslte_hip_tdec_t* tdec = nullptr; // any block length up to 6144
+  uint32_t           Cmax = 0, stride = 0, max_re = 0, max_bits = 0, words = 0;
+  uint32_t           V = 0; // per-subframe slots: max_batch, twice that on a cell where two-layer grants can occur (codeword 1 of subframe b: slot max_batch + b)
+  DevBuf<uint32_t>   d_relist, d_scr, d_basis, d_cb_iters;
+  DevBuf<int16_t>    d_e, d_w;
+  DevBuf<uint8_t>    d_cb_bytes, d_cb_ok;
+  DevBuf<float>      d_csi;     // [B][max_re], cfg.csi_enable
+  DevBuf<uint32_t>   d_csi_max; // [B]
+  size_t             desc_bytes = 0;
+  DescStage          desc; // the descriptor block: pinned host copies and the device block, desc_bytes + 16 each; a kernel of the call copies
+  bool               tb_direct = false; // 16-bit calls: the decoders assemble the transport blocks (environment SRSLTE_HIP_GRANTS_TB_DIRECT=0: the assembly kernel, for A/B and tests)
+  std::map<std::pair<uint32_t, uint32_t>, DevBuf<uint32_t>> rm_tbl;  // (K, rv) -> slot table in the layout of that K's decoder
+  std::map<uint32_t, DevBuf<uint32_t>>                      crc_fac; // tbs -> tb_crc_bytes_kernel's 256 chunk weights
+  ~GrantsState() { srslte_hip_tdec_destroy(tdec); }
 };
 
 struct srslte_hip_dl_rx {
-  srslte_hip_dl_rx_cfg_t cfg;
-  srslte_hip_ofdm_t*     ofdm;
-  srslte_hip_chest_dl_t* chest;
-  srslte_hip_tdec_t*     tdec;
-  srslte_hip_cbsegm_t    seg;
-  PdschGeom              pg;
-  RmGeom                 rg;
-  TbGeom                 tg;
-  uint32_t               W, in_stride;
-  uint32_t*              d_idx[3];
-  uint32_t*              d_scr;
-  uint32_t*              d_rm_tbl;      // rv 0
-  uint32_t*              d_rm_tbl_rv[4]; // [0] aliases d_rm_tbl; 1..3 built on first use (srslte_hip_dl_rx_batch_harq)
-  uint32_t               harq_rv;
-  int                    harq_combine;
-  uint32_t*              d_tbcrc;
-  cf32 *                 d_grid, *d_ce, *d_d;
-  const uint8_t*         direct_tb; // where the last decoder run (stage 4) assembled the transport blocks itself, or null: stage 5 has nothing to do then,
-  const uint8_t*         direct_ok; // if it is called with the same rows, verdicts, stride and subframe count as that run
-  uint32_t               direct_stride, direct_nof_sf;
-  cf32*                  d_ce_full; // debug view of a compact d_ce (pg.ce_nre != 0) expanded to whole grids, made on request
-  ChestResDev*           d_res;
-  int16_t *              d_e, *d_w;
-  uint8_t *              d_cb_bytes, *d_cb_ok;
-  uint32_t*              d_cb_iters;
-  uint32_t *             d_tb_rem, *d_cb_syn; // TB CRC shares from the windowed decoders ([C][K] table, [B*C] out); null for W = 0
-  float*                 d_csi;     // [B][max_re], cfg.csi_enable
-  uint32_t*              d_csi_max; // [B]
-  const cf32*            grid_in; // resource grids supplied by the caller (srslte_hip_dl_rx_grid_batch) instead of d_grid
-  struct GrantsState*    gs;      // srslte_hip_dl_rx_batch_grants: created on first use
-  struct srslte_hip_dl_rx* cw1;   // two-layer modes: the second codeword's back end (rate de-matching, decoder, TB assembly and their buffers)
-  srslte_hip_csi_t*      csi;        // srslte_hip_dl_rx_csi_batch: made on first use
-  uint32_t               est_nof_sf; // subframes the last estimator run (stage 1) left in d_ce / d_res; 0: none yet
-  float                  csi_offset; // snr_to_cqi_offset of srslte_hip_dl_rx_csi_batch
+  srslte_hip_dl_rx_cfg_t cfg   = {};
+  srslte_hip_ofdm_t*     ofdm  = nullptr;
+  srslte_hip_chest_dl_t* chest = nullptr;
+  srslte_hip_tdec_t*     tdec  = nullptr;
+  srslte_hip_cbsegm_t    seg   = {};
+  PdschGeom              pg    = {};
+  RmGeom                 rg    = {};
+  TbGeom                 tg    = {};
+  uint32_t               W = 0, in_stride = 0;
+  DevBuf<uint32_t>       d_idx[3];
+  DevBuf<uint32_t>       d_scr;
+  DevBuf<uint32_t>       d_rm_tbl_rv[4]; // [0] made with the object; 1..3 built on first use (srslte_hip_dl_rx_batch_harq)
+  uint32_t               harq_rv      = 0;
+  int                    harq_combine = 0;
+  DevBuf<uint32_t>       d_tbcrc;
+  DevBuf<cf32>           d_grid, d_ce, d_d;
+  const uint8_t*         direct_tb = nullptr; // where the last decoder run (stage 4) assembled the transport blocks itself, or null: stage 5 has nothing to do then,
+  const uint8_t*         direct_ok = nullptr; // if it is called with the same rows, verdicts, stride and subframe count as that run
+  uint32_t               direct_stride = 0, direct_nof_sf = 0;
+  DevBuf<cf32>           d_ce_full; // debug view of a compact d_ce (pg.ce_nre != 0) expanded to whole grids, made on request
+  DevBuf<ChestResDev>    d_res;
+  DevBuf<int16_t>        d_e, d_w;
+  DevBuf<uint8_t>        d_cb_bytes, d_cb_ok;
+  DevBuf<uint32_t>       d_cb_iters;
+  DevBuf<uint32_t>       d_tb_rem, d_cb_syn; // TB CRC shares from the windowed decoders ([C][K] table, [B*C] out); null for W = 0
+  DevBuf<float>          d_csi;     // [B][max_re], cfg.csi_enable
+  DevBuf<uint32_t>       d_csi_max; // [B]
+  const cf32*            grid_in = nullptr; // resource grids supplied by the caller (srslte_hip_dl_rx_grid_batch) instead of d_grid
+  std::unique_ptr<GrantsState> gs; // srslte_hip_dl_rx_batch_grants: created on first use
+  struct srslte_hip_dl_rx* cw1 = nullptr; // two-layer modes: the second codeword's back end (rate de-matching, decoder, TB assembly and their buffers)
+  srslte_hip_csi_t*      csi = nullptr; // srslte_hip_dl_rx_csi_batch: made on first use
+  uint32_t               est_nof_sf = 0; // subframes the last estimator run (stage 1) left in d_ce / d_res; 0: none yet
+  float                  csi_offset = 0.f; // snr_to_cqi_offset of srslte_hip_dl_rx_csi_batch
+  ~srslte_hip_dl_rx()
+  {
+    srslte_hip_dl_rx_destroy(cw1);
+    srslte_hip_ofdm_destroy(ofdm);
+    srslte_hip_chest_dl_destroy(chest);
+    srslte_hip_tdec_destroy(tdec);
+    srslte_hip_csi_destroy(csi);
+  }
 };
 
-static void grants_free(GrantsState* g);
-
-extern "C" void srslte_hip_dl_rx_destroy(srslte_hip_dl_rx_t* q)
-{
-  if (!q) return;
-  srslte_hip_dl_rx_destroy(q->cw1);
-  srslte_hip_ofdm_destroy(q->ofdm);
-  srslte_hip_chest_dl_destroy(q->chest);
-  srslte_hip_tdec_destroy(q->tdec);
-  srslte_hip_csi_destroy(q->csi);
-  void* bufs[] = {q->d_idx[0], q->d_idx[1], q->d_idx[2], q->d_scr, q->d_rm_tbl, q->d_tbcrc, q->d_grid, q->d_ce, q->d_ce_full, q->d_d,
-                  q->d_res,    q->d_e,      q->d_w,      q->d_cb_bytes, q->d_cb_ok, q->d_cb_iters, q->d_tb_rem, q->d_cb_syn,
-                  q->d_csi,    q->d_csi_max, q->d_rm_tbl_rv[1], q->d_rm_tbl_rv[2], q->d_rm_tbl_rv[3]};
-  for (void* b : bufs) {
-    if (b) (void)hipFree(b);
-  }
-  grants_free(q->gs);
-  delete q;
-}
+extern "C" void srslte_hip_dl_rx_destroy(srslte_hip_dl_rx_t* q) { delete q; }
 
 // cw: 0 = a whole pipeline; 1 = the back end of the second codeword of a two-layer mode (cfg->mod / tbs already those of that codeword):
 // no OFDM / estimator objects, no grids, scrambling sequence q = 1 (36.211 6.3.1)
@@ -94,12 +84,10 @@ static srslte_hip_dl_rx_t* dl_rx_create_impl(const srslte_hip_dl_rx_cfg_t* cfg, 
       return nullptr;
     }
   }
-  auto* q = new srslte_hip_dl_rx();
-  memset(q, 0, sizeof(*q));
+  std::unique_ptr<srslte_hip_dl_rx> q(new srslte_hip_dl_rx());
   q->cfg = *cfg;
   if (srslte_hip_cbsegm(&q->seg, cfg->tbs) || q->seg.F || q->seg.C2 || (cfg->tbs % 8)) {
     hip_log("[srslte_hip] dl_rx: TBS %u needs filler bits or two code-block sizes; not supported on device yet\n", cfg->tbs);
-    delete q;
     return nullptr;
   }
   const uint32_t P = cfg->nof_prb, nre = 12 * P, B = cfg->max_batch, C = q->seg.C, K = q->seg.K1, Qm = 2 * (uint32_t)cfg->mod;
@@ -111,13 +99,11 @@ static srslte_hip_dl_rx_t* dl_rx_create_impl(const srslte_hip_dl_rx_cfg_t* cfg, 
                      cfg->non_mbsfn_region < 1 || cfg->non_mbsfn_region > 2 || cw)) {
     // srslte_pmch_decode: one port (pmch.c:159), int16 LLRs (:377), no CSI weighting, no power allocation
     hip_log("[srslte_hip] dl_rx: an MBSFN pipeline is single-port FDD with 16-bit LLRs, area id 0-255, a non-MBSFN region of 1 or 2 symbols\n");
-    delete q;
     return nullptr;
   }
   if (cfg->mbsfn) q->cfg.chest_cfg.interpolate_subframe = 1;
   if (cfg->tdd && (cfg->tdd_sf_config > 6 || cfg->tdd_ss_config > 9)) {
     hip_log("[srslte_hip] dl_rx: TDD uplink-downlink configuration %u / special-subframe configuration %u\n", cfg->tdd_sf_config, cfg->tdd_ss_config);
-    delete q;
     return nullptr;
   }
   if (cw == 0) {
@@ -143,7 +129,7 @@ static srslte_hip_dl_rx_t* dl_rx_create_impl(const srslte_hip_dl_rx_cfg_t* cfg, 
     q->rg.nof_re[c]     = (int)idx.size();
     max_re              = idx.size() > max_re ? (uint32_t)idx.size() : max_re;
     if (cw) continue; // the lists are the first codeword's object's
-    ok                  = upload(&q->d_idx[c], idx) == SRSLTE_SUCCESS;
+    ok                  = upload(q->d_idx[c], idx) == SRSLTE_SUCCESS;
     q->pg.cls[c].idx    = q->d_idx[c];
   }
   const uint32_t max_bits = (max_re * Qm + 15) & ~15u, scr_words = (max_re * Qm + 31) / 32 + 1; // spare word: the demapper reads two per RE
@@ -157,15 +143,12 @@ static srslte_hip_dl_rx_t* dl_rx_create_impl(const srslte_hip_dl_rx_cfg_t* cfg, 
       lte_gold_sequence(c_init, max_re * Qm, c);
       for (uint32_t i = 0; i < max_re * Qm; i++) scr[(size_t)sf * scr_words + (i >> 5)] |= (uint32_t)c[i] << (i & 31);
     }
-    ok = upload(&q->d_scr, scr) == SRSLTE_SUCCESS;
+    ok = upload(q->d_scr, scr) == SRSLTE_SUCCESS;
   }
   // rate-dematching table in the decoder's input layout (rm_turbo.c:160-260)
   q->W         = cfg->llr_8bit ? srslte_hip_tdec_autoimp_get_subblocks_8bit(K) : srslte_hip_tdec_autoimp_get_subblocks(K);
   q->in_stride = (srslte_hip_tdec_input_len(K, q->W != 0) + 31) & ~31u;
-  if (ok) {
-    ok                = rm_rx_table_upload(K, 0, q->W, q->in_stride, &q->d_rm_tbl) == SRSLTE_SUCCESS;
-    q->d_rm_tbl_rv[0] = q->d_rm_tbl;
-  }
+  ok = ok && rm_rx_table_upload(K, 0, q->W, q->in_stride, q->d_rm_tbl_rv[0]) == SRSLTE_SUCCESS;
   // TB CRC24A remainders x^(tbs+24-1-j) mod g
   if (ok) {
     std::vector<uint32_t> rem(cfg->tbs + 24);
@@ -175,7 +158,7 @@ static srslte_hip_dl_rx_t* dl_rx_create_impl(const srslte_hip_dl_rx_cfg_t* cfg, 
       v <<= 1;
       if (v & 0x1000000) v ^= 0x1864CFB;
     }
-    ok = upload(&q->d_tbcrc, rem) == SRSLTE_SUCCESS;
+    ok = upload(q->d_tbcrc, rem) == SRSLTE_SUCCESS;
     if (ok && q->W) { // per code block, in the decoder's array order (window-interleaved); 0 on the CB CRC bits
       const uint32_t        rlen = C == 1 ? K : K - 24, Lw = K / q->W;
       std::vector<uint32_t> t((size_t)C * K, 0);
@@ -185,32 +168,25 @@ static srslte_hip_dl_rx_t* dl_rx_create_impl(const srslte_hip_dl_rx_cfg_t* cfg, 
           if (pos < cfg->tbs + 24) t[(size_t)c * K + (n % Lw) * q->W + n / Lw] = rem[pos];
         }
       }
-      ok = upload(&q->d_tb_rem, t) == SRSLTE_SUCCESS && hipMalloc((void**)&q->d_cb_syn, sizeof(uint32_t) * B * C) == hipSuccess;
+      ok = upload(q->d_tb_rem, t) == SRSLTE_SUCCESS && q->d_cb_syn.alloc((size_t)B * C) == SRSLTE_SUCCESS;
     }
   }
   const size_t glen = (size_t)2 * nsl * nre;
   if (cw == 0) {
-    ok = ok && hipMalloc((void**)&q->d_grid, sizeof(cf32) * glen * B * nrx) == hipSuccess &&
-         hipMalloc((void**)&q->d_ce, sizeof(cf32) * glen * B * nrx * npt) == hipSuccess &&
+    ok = ok && !q->d_grid.alloc(glen * B * nrx) && !q->d_ce.alloc(glen * B * nrx * npt) &&
          hipMemset(q->d_ce, 0, sizeof(cf32) * glen * B * nrx * npt) == hipSuccess && /* 4 ports + interpolate_subframe: ports 2/3 keep what is there */
-         hipMalloc((void**)&q->d_res, sizeof(ChestResDev) * B) == hipSuccess;
+         !q->d_res.alloc(B);
   }
-  ok = ok && hipMalloc((void**)&q->d_e, sizeof(int16_t) * ((size_t)max_bits * B + 16)) == hipSuccess /* +16: rm_rx_lds_kernel reads whole 16-byte words */ &&
-       hipMalloc((void**)&q->d_w, sizeof(int16_t) * (size_t)q->in_stride * B * C) == hipSuccess &&
-       hipMalloc((void**)&q->d_cb_bytes, (size_t)(K / 8) * B * C) == hipSuccess &&
-       hipMalloc((void**)&q->d_cb_ok, (size_t)B * C) == hipSuccess &&
-       hipMalloc((void**)&q->d_cb_iters, sizeof(uint32_t) * B * C) == hipSuccess;
-  if (ok && cfg->csi_enable) {
-    ok = hipMalloc((void**)&q->d_csi, sizeof(float) * (size_t)max_re * B) == hipSuccess &&
-         hipMalloc((void**)&q->d_csi_max, sizeof(uint32_t) * B) == hipSuccess;
-  }
+  ok = ok && !q->d_e.alloc((size_t)max_bits * B + 16) /* +16: rm_rx_lds_kernel reads whole 16-byte words */ &&
+       !q->d_w.alloc((size_t)q->in_stride * B * C) && !q->d_cb_bytes.alloc((size_t)(K / 8) * B * C) && !q->d_cb_ok.alloc((size_t)B * C) &&
+       !q->d_cb_iters.alloc((size_t)B * C);
+  if (ok && cfg->csi_enable) ok = !q->d_csi.alloc((size_t)max_re * B) && !q->d_csi_max.alloc(B);
   // HARQ state of slots that have not seen new data yet (a retransmission into such a slot combines with an empty soft buffer and
   // decodes every block); the memsets run on the null stream, which the callers' non-blocking streams do not order against: wait here
   ok = ok && hipMemset(q->d_cb_ok, 0, (size_t)B * C) == hipSuccess && hipMemset(q->d_w, 0, sizeof(int16_t) * (size_t)q->in_stride * B * C) == hipSuccess &&
        hipMemset(q->d_cb_bytes, 0, (size_t)(K / 8) * B * C) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
   if (!ok) {
     hip_log("[srslte_hip] dl_rx: initialisation failed\n");
-    srslte_hip_dl_rx_destroy(q);
     return nullptr;
   }
   q->pg.grid_len = (int)glen; q->pg.max_re = (int)max_re; q->pg.max_bits = (int)max_bits; q->pg.mod = cfg->mod; q->pg.Qm = (int)Qm;
@@ -236,15 +212,12 @@ static srslte_hip_dl_rx_t* dl_rx_create_impl(const srslte_hip_dl_rx_cfg_t* cfg, 
       srslte_hip_dl_rx_cfg_t c1 = *cfg;
       c1.mod = cfg->mod2; c1.tbs = cfg->tbs2; c1.mod2 = 0; c1.tbs2 = 0;
       q->cw1 = dl_rx_create_impl(&c1, 1);
-      if (!q->cw1) {
-        srslte_hip_dl_rx_destroy(q);
-        return nullptr;
-      }
+      if (!q->cw1) return nullptr;
       q->pg.mod1 = c1.mod; q->pg.Qm1 = q->cw1->pg.Qm; q->pg.max_bits1 = q->cw1->pg.max_bits; q->pg.scr_words1 = q->cw1->pg.scr_words;
       q->pg.scr1 = q->cw1->d_scr; q->pg.csi1 = q->cw1->d_csi; q->pg.csi_max1 = q->cw1->d_csi_max;
     }
   }
-  return q;
+  return q.release();
 }
 
 extern "C" srslte_hip_dl_rx_t* srslte_hip_dl_rx_create(const srslte_hip_dl_rx_cfg_t* cfg) { return dl_rx_create_impl(cfg, 0); }
@@ -255,12 +228,11 @@ extern "C" int srslte_hip_dl_rx_keep_symbols(srslte_hip_dl_rx_t* q, int enable)
   if (q->cw1) {
     if (int r = srslte_hip_dl_rx_keep_symbols(q->cw1, enable)) return r;
   }
-  if (enable && !q->d_d) {
-    HIP_TRY(hipMalloc((void**)&q->d_d, sizeof(cf32) * (size_t)q->pg.max_re * q->cfg.max_batch));
-  } else if (!enable && q->d_d) {
-    HIP_TRY(hipFree(q->d_d));
-    q->d_d = nullptr;
+  if (enable && !q->d_d && q->d_d.alloc((size_t)q->pg.max_re * q->cfg.max_batch)) {
+    hip_log("[srslte_hip] dl_rx: no device memory for the equalised symbols\n");
+    return SRSLTE_ERROR;
   }
+  if (!enable) q->d_d = DevBuf<cf32>();
   return SRSLTE_SUCCESS;
 }
 
@@ -282,7 +254,7 @@ static const void* dl_rx_ce_full(srslte_hip_dl_rx_t* q)
 {
   const size_t planes = (size_t)q->cfg.max_batch * q->pg.nof_rx;
   if (hipDeviceSynchronize() != hipSuccess) return nullptr;
-  if (!q->d_ce_full && hipMalloc((void**)&q->d_ce_full, sizeof(cf32) * planes * q->pg.grid_len) != hipSuccess) return nullptr;
+  if (!q->d_ce_full && q->d_ce_full.alloc(planes * q->pg.grid_len)) return nullptr;
   hipLaunchKernelGGL(ce_expand_kernel, dim3(ceil_div(q->pg.ce_nre, 256), (unsigned)planes), dim3(256), 0, 0, (const cf32*)q->d_ce, q->d_ce_full, q->pg.ce_nre,
                      q->pg.grid_len / q->pg.ce_nre);
   return hipDeviceSynchronize() == hipSuccess ? q->d_ce_full : nullptr;
@@ -362,8 +334,8 @@ extern "C" int srslte_hip_dl_rx_stage(srslte_hip_dl_rx_t* q, int stage, const vo
         if (g.csi_max1) HIP_TRY(hipMemsetAsync(g.csi_max1, 0, sizeof(uint32_t) * nof_sf, st));
         if (q->cfg.llr_8bit) { // pdsch.c:760-779: q->llr_is_8bit with any transmission scheme
           hipLaunchKernelGGL(pdsch_demod_mimo_kernel<int8_t>, dim3(ceil_div(g.max_re, 256), nof_sf), dim3(256), 0, st, grid, (const cf32*)q->d_ce,
-                             (const ChestResDev*)q->d_res, (const uint32_t*)q->d_scr, q->d_d, q->cw1 ? q->cw1->d_d : (cf32*)nullptr, (int8_t*)q->d_e,
-                             q->cw1 ? (int8_t*)q->cw1->d_e : (int8_t*)nullptr, g);
+                             (const ChestResDev*)q->d_res, (const uint32_t*)q->d_scr, q->d_d, q->cw1 ? q->cw1->d_d : (cf32*)nullptr, (int8_t*)q->d_e.get(),
+                             q->cw1 ? (int8_t*)q->cw1->d_e.get() : (int8_t*)nullptr, g);
         } else {
           hipLaunchKernelGGL(pdsch_demod_mimo_kernel<int16_t>, dim3(ceil_div(g.max_re, 256), nof_sf), dim3(256), 0, st, grid, (const cf32*)q->d_ce,
                              (const ChestResDev*)q->d_res, (const uint32_t*)q->d_scr, q->d_d, q->cw1 ? q->cw1->d_d : (cf32*)nullptr, q->d_e,
@@ -372,7 +344,7 @@ extern "C" int srslte_hip_dl_rx_stage(srslte_hip_dl_rx_t* q, int stage, const vo
       } else if (g.nof_ports == 4) {
         if (q->cfg.llr_8bit) {
           hipLaunchKernelGGL(pdsch_demod_div4_kernel<int8_t>, dim3(ceil_div(g.max_re, 1024), nof_sf), dim3(256), 0, st, grid, (const cf32*)q->d_ce,
-                             (const uint32_t*)q->d_scr, q->d_d, (int8_t*)q->d_e, g);
+                             (const uint32_t*)q->d_scr, q->d_d, (int8_t*)q->d_e.get(), g);
         } else {
           hipLaunchKernelGGL(pdsch_demod_div4_kernel<int16_t>, dim3(ceil_div(g.max_re, 1024), nof_sf), dim3(256), 0, st, grid, (const cf32*)q->d_ce,
                              (const uint32_t*)q->d_scr, q->d_d, q->d_e, g);
@@ -380,14 +352,14 @@ extern "C" int srslte_hip_dl_rx_stage(srslte_hip_dl_rx_t* q, int stage, const vo
       } else if (g.nof_ports == 2) {
         if (q->cfg.llr_8bit) {
           hipLaunchKernelGGL(pdsch_demod_div_kernel<int8_t>, dim3(ceil_div(g.max_re, 512), nof_sf), dim3(256), 0, st, grid, (const cf32*)q->d_ce,
-                             (const uint32_t*)q->d_scr, q->d_d, (int8_t*)q->d_e, g);
+                             (const uint32_t*)q->d_scr, q->d_d, (int8_t*)q->d_e.get(), g);
         } else {
           hipLaunchKernelGGL(pdsch_demod_div_kernel<int16_t>, dim3(ceil_div(g.max_re, 512), nof_sf), dim3(256), 0, st, grid, (const cf32*)q->d_ce,
                              (const uint32_t*)q->d_scr, q->d_d, q->d_e, g);
         }
       } else if (q->cfg.llr_8bit) {
         hipLaunchKernelGGL(pdsch_demod_kernel<int8_t>, dim3(ceil_div(g.max_re, 256), nof_sf), dim3(256), 0, st, grid,
-                           (const cf32*)q->d_ce, (const ChestResDev*)q->d_res, (const uint32_t*)q->d_scr, q->d_d, (int8_t*)q->d_e, g);
+                           (const cf32*)q->d_ce, (const ChestResDev*)q->d_res, (const uint32_t*)q->d_scr, q->d_d, (int8_t*)q->d_e.get(), g);
       } else {
         hipLaunchKernelGGL(pdsch_demod_kernel<int16_t>, dim3(ceil_div(g.max_re, 256), nof_sf), dim3(256), 0, st, grid,
                            (const cf32*)q->d_ce, (const ChestResDev*)q->d_res, (const uint32_t*)q->d_scr, q->d_d, q->d_e, g);
@@ -481,7 +453,7 @@ extern "C" int srslte_hip_dl_rx_batch_harq2(srslte_hip_dl_rx_t* q, const void* d
     srslte_hip_dl_rx_t* o = objs[c];
     if (!o) continue;
     if (!o->d_rm_tbl_rv[rv[c]]) {
-      if (int r = rm_rx_table_upload(o->seg.K1, rv[c], o->W, o->in_stride, &o->d_rm_tbl_rv[rv[c]])) return r;
+      if (int r = rm_rx_table_upload(o->seg.K1, rv[c], o->W, o->in_stride, o->d_rm_tbl_rv[rv[c]])) return r;
     }
     o->harq_rv      = rv[c];
     o->harq_combine = new_data[c] ? 0 : 1;

@@ -11,7 +11,7 @@
 // --------------------------------------------------------------------------------------------------------------------
 // Gold-sequence basis (sequence.c:48-79) for scr_gen_kernel: row 0 = the x1 sequence, row 1 + j = the x2 sequence of c_init = 1 << j, `words`
 // packed words each; all 31 x2 basis sequences advance together, bit j of the state word = basis j
-static int gold_basis_upload(uint32_t words, uint32_t** d_basis)
+static int gold_basis_upload(uint32_t words, DevBuf<uint32_t>& d_basis)
 {
   const uint32_t         nbits = words * 32, Nc = 1600, tot = nbits + Nc + 31;
   std::vector<uint8_t>   x1(tot);
@@ -49,42 +49,21 @@ static int grants_alloc(GrantsState* g, uint32_t max_re, uint32_t V, uint32_t Cm
   }
   g->tdec     = srslte_hip_tdec_create(6144, g->V * g->Cmax);
   if (!g->tdec) return SRSLTE_ERROR;
-  if (gold_basis_upload(g->words, &g->d_basis)) return SRSLTE_ERROR;
+  if (gold_basis_upload(g->words, g->d_basis)) return SRSLTE_ERROR;
   const size_t nblk = (size_t)g->V * g->Cmax;
   g->desc_bytes     = sizeof(GrantDev) * g->V + sizeof(SfDesc) * g->V + sizeof(CbDesc) * nblk + sizeof(uint32_t) * nblk + extra_desc_bytes + ((g->V + 15) & ~15u);
-  if (g->ring.init(g->desc_bytes + 16)) return SRSLTE_ERROR; // + 16: copied in 16-byte words (grants_prep_kernel, desc_copy_kernel)
-  if (relist_rows) HIP_TRY(hipMalloc((void**)&g->d_relist, sizeof(uint32_t) * (size_t)g->max_re * relist_rows));
-  HIP_TRY(hipMalloc((void**)&g->d_scr, sizeof(uint32_t) * (size_t)g->words * g->V));
-  HIP_TRY(hipMalloc((void**)&g->d_e, sizeof(int16_t) * ((size_t)g->max_bits * g->V + 16)));
-  HIP_TRY(hipMalloc((void**)&g->d_w, sizeof(int16_t) * (size_t)g->stride * nblk));
-  HIP_TRY(hipMalloc((void**)&g->d_cb_bytes, (size_t)768 * nblk));
-  HIP_TRY(hipMalloc((void**)&g->d_cb_ok, nblk));
-  HIP_TRY(hipMalloc((void**)&g->d_cb_iters, sizeof(uint32_t) * nblk));
-  HIP_TRY(hipMalloc((void**)&g->d_desc, g->desc_bytes + 16));
-  if (csi) {
-    HIP_TRY(hipMalloc((void**)&g->d_csi, sizeof(float) * (size_t)g->max_re * g->V));
-    HIP_TRY(hipMalloc((void**)&g->d_csi_max, sizeof(uint32_t) * g->V));
-  }
+  if (g->desc.init(g->desc_bytes + 16)) return SRSLTE_ERROR; // + 16: copied in 16-byte words (grants_prep_kernel, desc_copy_kernel)
+  if (relist_rows && g->d_relist.alloc((size_t)g->max_re * relist_rows)) return SRSLTE_ERROR;
+  if (g->d_scr.alloc((size_t)g->words * g->V) || g->d_e.alloc((size_t)g->max_bits * g->V + 16) || g->d_w.alloc((size_t)g->stride * nblk) ||
+      g->d_cb_bytes.alloc((size_t)768 * nblk) || g->d_cb_ok.alloc(nblk) || g->d_cb_iters.alloc(nblk))
+    return SRSLTE_ERROR;
+  if (csi && (g->d_csi.alloc((size_t)g->max_re * g->V) || g->d_csi_max.alloc(g->V))) return SRSLTE_ERROR;
   // HARQ state of slots that have not seen new data yet: nothing decoded, empty soft buffers
   HIP_TRY(hipMemset(g->d_cb_ok, 0, nblk));
   HIP_TRY(hipMemset(g->d_w, 0, sizeof(int16_t) * (size_t)g->stride * nblk));
   HIP_TRY(hipMemset(g->d_cb_bytes, 0, (size_t)768 * nblk));
   HIP_TRY(hipDeviceSynchronize());
   return SRSLTE_SUCCESS;
-}
-
-static void grants_free(GrantsState* g)
-{
-  if (!g) return;
-  srslte_hip_tdec_destroy(g->tdec);
-  void* gb[] = {g->d_relist, g->d_scr, g->d_basis, g->d_cb_iters, g->d_e, g->d_w, g->d_cb_bytes, g->d_cb_ok, g->d_desc, g->d_csi, g->d_csi_max};
-  for (void* b : gb) {
-    if (b) (void)hipFree(b);
-  }
-  for (auto& kv : g->rm_tbl) (void)hipFree(kv.second);
-  for (auto& kv : g->crc_fac) (void)hipFree(kv.second);
-  g->ring.destroy();
-  delete g;
 }
 
 // The sections of a descriptor block of a grants mode, host or device copy: GrantDev[V] | SfDesc[V] | CbDesc[V Cmax] | block map[V Cmax] |
@@ -124,10 +103,9 @@ static const uint8_t* grants_direct_cof(const GrantsState* g, const GrantsDesc& 
 
 static int grants_init(srslte_hip_dl_rx_t* q)
 {
-  auto*          g = new GrantsState();
   const uint32_t P = q->cfg.nof_prb, B = q->cfg.max_batch;
-  q->gs = g;
-  return grants_alloc(g, 14 * 12 * P, (q->pg.nof_ports == 2 && q->pg.nof_rx == 2) ? 2 * B : B, q->seg.C, B, q->cfg.csi_enable != 0, 0);
+  q->gs.reset(new GrantsState());
+  return grants_alloc(q->gs.get(), 14 * 12 * P, (q->pg.nof_ports == 2 && q->pg.nof_rx == 2) ? 2 * B : B, q->seg.C, B, q->cfg.csi_enable != 0, 0);
 }
 
 // slot table of (K, rv) in the input layout of the decoder AUTO selects for K, stride = that layout's length rounded up to 32
@@ -135,9 +113,9 @@ static int grants_rm_table(GrantsState* g, uint32_t K, uint32_t rv, uint32_t W, 
 {
   auto it = g->rm_tbl.find({K, rv});
   if (it == g->rm_tbl.end()) {
-    uint32_t* d = nullptr;
-    if (rm_rx_table_upload(K, rv, W, w_len, &d)) return SRSLTE_ERROR;
-    it = g->rm_tbl.emplace(std::make_pair(K, rv), d).first;
+    DevBuf<uint32_t> d;
+    if (rm_rx_table_upload(K, rv, W, w_len, d)) return SRSLTE_ERROR;
+    it = g->rm_tbl.emplace(std::make_pair(K, rv), std::move(d)).first;
   }
   *d_tbl = it->second;
   return SRSLTE_SUCCESS;
@@ -166,9 +144,9 @@ static int grants_crc_factors(GrantsState* g, uint32_t tbs, const uint32_t** d_f
     std::vector<uint32_t> w(256);
     w[255] = 1;
     for (int t = 254; t >= 0; t--) w[t] = mul(w[t + 1], m);
-    uint32_t* d = nullptr;
-    if (upload(&d, w)) return SRSLTE_ERROR;
-    it = g->crc_fac.emplace(tbs, d).first;
+    DevBuf<uint32_t> d;
+    if (upload(d, w)) return SRSLTE_ERROR;
+    it = g->crc_fac.emplace(tbs, std::move(d)).first;
   }
   *d_fac = it->second;
   return SRSLTE_SUCCESS;
@@ -405,17 +383,17 @@ static int grants_run(srslte_hip_dl_rx_t* q, const void* d_iq, uint32_t tti0, ui
   }
   if (nof_sf == 0) return SRSLTE_SUCCESS;
   if (!q->gs && grants_init(q)) { // a failed start leaves no half-made state behind
-    grants_free(q->gs);
-    q->gs = nullptr;
+    hip_log("[srslte_hip] dl_rx grants: initialisation failed\n");
+    q->gs.reset();
     return SRSLTE_ERROR;
   }
-  GrantsState*   g  = q->gs;
+  GrantsState*   g  = q->gs.get();
   hipStream_t    st = (hipStream_t)stream;
   const uint32_t P = q->cfg.nof_prb, cell_id = q->cfg.cell_id, B = q->cfg.max_batch, V = g->V;
   const int      npt = q->pg.nof_ports;
   uint8_t*       h_pin = nullptr;
-  if (int r = g->ring.acquire(&h_pin)) return r;
-  const GrantsDesc h(g, h_pin), d(g, g->d_desc);
+  if (int r = g->desc.begin(&h_pin)) return r;
+  const GrantsDesc h(g, h_pin), d(g, g->desc.dev_bytes());
   GrantDev*        h_gr = h.gr;
   SfDesc*          h_sf = h.sf;
   const bool         l8 = q->cfg.llr_8bit != 0; // the 8-bit LLR path the applications select (pdsch.c:760-779, sch.c:336-356): same buffers, as bytes
@@ -484,10 +462,10 @@ static int grants_run(srslte_hip_dl_rx_t* q, const void* d_iq, uint32_t tti0, ui
     hipLaunchKernelGGL(grants_prep_kernel, dim3(work + ceil_div(n16, RELIST_THREADS)), dim3(RELIST_THREADS), 0, st, src, g->d_relist, (int)P,
                        (int)cell_id, (int)g->max_re, q->pg.nof_ports, q->cfg.cp_ext ? 6 : 7, (int)nof_sf, (const uint32_t*)g->d_basis, g->d_scr,
                        any_mimo ? src + B : nullptr, g->d_scr + (size_t)B * g->words, (int)g->words, d_tb_ok,
-                       (int)nrows, (const uint4*)h_pin, (uint4*)g->d_desc, n16, work);
+                       (int)nrows, (const uint4*)h_pin, (uint4*)g->desc.dev_bytes(), n16, work);
   }
   LAUNCH_CHECK();
-  if (int r = g->ring.release(st)) return r; // the pinned buffer is free again when this launch has run
+  if (int r = g->desc.committed(st)) return r; // the pinned buffer is free again when this launch has run
   {
     PdschGeom pg = q->pg;
     pg.desc = d.sf; pg.tti0 = (int)tti0; pg.max_re = (int)g->max_re; pg.max_bits = (int)g->max_bits; pg.csi = g->d_csi; pg.csi_max = g->d_csi_max;
@@ -496,7 +474,7 @@ static int grants_run(srslte_hip_dl_rx_t* q, const void* d_iq, uint32_t tti0, ui
     if (pg.nof_ports == 4) {
       if (l8) {
         hipLaunchKernelGGL(pdsch_demod_div4_kernel<int8_t>, dim3(ceil_div((int)g->max_re, 1024), nof_sf), dim3(256), 0, st, grid, (const cf32*)q->d_ce,
-                           (const uint32_t*)g->d_scr, (cf32*)nullptr, (int8_t*)g->d_e, pg);
+                           (const uint32_t*)g->d_scr, (cf32*)nullptr, (int8_t*)g->d_e.get(), pg);
       } else {
         hipLaunchKernelGGL(pdsch_demod_div4_kernel<int16_t>, dim3(ceil_div((int)g->max_re, 1024), nof_sf), dim3(256), 0, st, grid, (const cf32*)q->d_ce,
                            (const uint32_t*)g->d_scr, (cf32*)nullptr, g->d_e, pg);
@@ -504,7 +482,7 @@ static int grants_run(srslte_hip_dl_rx_t* q, const void* d_iq, uint32_t tti0, ui
     } else if (pg.nof_ports == 2) {
       if (l8) {
         hipLaunchKernelGGL(pdsch_demod_div_kernel<int8_t>, dim3(ceil_div((int)g->max_re, 512), nof_sf), dim3(256), 0, st, grid, (const cf32*)q->d_ce,
-                           (const uint32_t*)g->d_scr, (cf32*)nullptr, (int8_t*)g->d_e, pg);
+                           (const uint32_t*)g->d_scr, (cf32*)nullptr, (int8_t*)g->d_e.get(), pg);
       } else {
         hipLaunchKernelGGL(pdsch_demod_div_kernel<int16_t>, dim3(ceil_div((int)g->max_re, 512), nof_sf), dim3(256), 0, st, grid, (const cf32*)q->d_ce,
                            (const uint32_t*)g->d_scr, (cf32*)nullptr, g->d_e, pg);
@@ -516,8 +494,8 @@ static int grants_run(srslte_hip_dl_rx_t* q, const void* d_iq, uint32_t tti0, ui
         pg.csi_max1 = g->d_csi_max ? g->d_csi_max + B : nullptr;
         if (l8) {
           hipLaunchKernelGGL(pdsch_demod_mimo_kernel<int8_t>, dim3(ceil_div((int)g->max_re, 256), nof_sf), dim3(256), 0, st, grid, (const cf32*)q->d_ce,
-                             (const ChestResDev*)q->d_res, (const uint32_t*)g->d_scr, (cf32*)nullptr, (cf32*)nullptr, (int8_t*)g->d_e,
-                             (int8_t*)g->d_e + (size_t)B * g->max_bits, pg);
+                             (const ChestResDev*)q->d_res, (const uint32_t*)g->d_scr, (cf32*)nullptr, (cf32*)nullptr, (int8_t*)g->d_e.get(),
+                             (int8_t*)g->d_e.get() + (size_t)B * g->max_bits, pg);
         } else {
           hipLaunchKernelGGL(pdsch_demod_mimo_kernel<int16_t>, dim3(ceil_div((int)g->max_re, 256), nof_sf), dim3(256), 0, st, grid, (const cf32*)q->d_ce,
                              (const ChestResDev*)q->d_res, (const uint32_t*)g->d_scr, (cf32*)nullptr, (cf32*)nullptr, g->d_e, g->d_e + (size_t)B * g->max_bits, pg);
@@ -525,7 +503,7 @@ static int grants_run(srslte_hip_dl_rx_t* q, const void* d_iq, uint32_t tti0, ui
       }
     } else if (l8) {
       hipLaunchKernelGGL(pdsch_demod_kernel<int8_t>, dim3(ceil_div((int)g->max_re, 256), nof_sf), dim3(256), 0, st, grid, (const cf32*)q->d_ce,
-                         (const ChestResDev*)q->d_res, (const uint32_t*)g->d_scr, (cf32*)nullptr, (int8_t*)g->d_e, pg);
+                         (const ChestResDev*)q->d_res, (const uint32_t*)g->d_scr, (cf32*)nullptr, (int8_t*)g->d_e.get(), pg);
     } else {
       hipLaunchKernelGGL(pdsch_demod_kernel<int16_t>, dim3(ceil_div((int)g->max_re, 256), nof_sf), dim3(256), 0, st, grid, (const cf32*)q->d_ce,
                          (const ChestResDev*)q->d_res, (const uint32_t*)g->d_scr, (cf32*)nullptr, g->d_e, pg);
@@ -542,24 +520,23 @@ struct srslte_hip_dl_rx_pool {
   std::vector<hipEvent_t>          ev;
   std::vector<int64_t>             last; // ticket of the batch each object works on, -1: none
   int64_t                          next = 0;
+  ~srslte_hip_dl_rx_pool()
+  {
+    for (size_t i = 0; i < rx.size(); i++) {
+      if (st[i]) (void)hipStreamSynchronize(st[i]); // before the object's buffers go
+      srslte_hip_dl_rx_destroy(rx[i]);
+      if (ev[i]) (void)hipEventDestroy(ev[i]);
+      if (st[i]) (void)hipStreamDestroy(st[i]);
+    }
+  }
 };
 
-extern "C" void srslte_hip_dl_rx_pool_destroy(srslte_hip_dl_rx_pool_t* p)
-{
-  if (!p) return;
-  for (size_t i = 0; i < p->rx.size(); i++) {
-    if (p->st[i]) (void)hipStreamSynchronize(p->st[i]);
-    srslte_hip_dl_rx_destroy(p->rx[i]);
-    if (p->ev[i]) (void)hipEventDestroy(p->ev[i]);
-    if (p->st[i]) (void)hipStreamDestroy(p->st[i]);
-  }
-  delete p;
-}
+extern "C" void srslte_hip_dl_rx_pool_destroy(srslte_hip_dl_rx_pool_t* p) { delete p; }
 
 extern "C" srslte_hip_dl_rx_pool_t* srslte_hip_dl_rx_pool_create(const srslte_hip_dl_rx_cfg_t* cfg, uint32_t depth)
 {
   if (!cfg || depth == 0 || depth > 16) return nullptr;
-  auto* p = new srslte_hip_dl_rx_pool();
+  std::unique_ptr<srslte_hip_dl_rx_pool> p(new srslte_hip_dl_rx_pool());
   p->rx.assign(depth, nullptr);
   p->st.assign(depth, nullptr);
   p->ev.assign(depth, nullptr);
@@ -567,12 +544,10 @@ extern "C" srslte_hip_dl_rx_pool_t* srslte_hip_dl_rx_pool_create(const srslte_hi
   for (uint32_t i = 0; i < depth; i++) {
     p->rx[i] = srslte_hip_dl_rx_create(cfg);
     if (!p->rx[i] || hipStreamCreateWithFlags(&p->st[i], hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&p->ev[i], hipEventDisableTiming) != hipSuccess) {
-      srslte_hip_dl_rx_pool_destroy(p);
+        hipEventCreateWithFlags(&p->ev[i], hipEventDisableTiming) != hipSuccess)
       return nullptr;
-    }
   }
-  return p;
+  return p.release();
 }
 
 extern "C" int64_t srslte_hip_dl_rx_pool_submit(srslte_hip_dl_rx_pool_t* p, const void* d_iq, uint32_t tti0, uint32_t nof_sf, const srslte_hip_dl_grant_t* grants,

@@ -115,7 +115,6 @@ struct TxDesc {
   // the descriptor of its codeword 1 (-1: one transport block)
   int             scheme, codebook, cw1;
 };
-struct TxLevels { float v[5][16]; };   // constellation levels of one axis per srslte_mod_t
 
 // grid = nof_pdsch: CRC24A of each transport block
 __global__ __launch_bounds__(256) void tx_tbcrc_grants_kernel(const uint8_t* __restrict__ tb, int tb_stride, const TxDesc* __restrict__ desc,
@@ -234,66 +233,36 @@ __global__ __launch_bounds__(256) void pdsch_tx_map_kernel(const cf32* __restric
 
 } // namespace
 
-struct srslte_hip_dl_tx {
-  srslte_hip_dl_tx_cfg_t cfg;
-  srslte_hip_ofdm_t*     ofdm;
-  srslte_hip_chest_dl_t* crs; // for its CRS table
-  srslte_hip_cbsegm_t    seg;
-  PuschTxGeom            cg; // CRC attachment / segmentation geometry (shared kernels)
-  PdschTxGeom            g;
-  uint32_t *             d_scr, *d_rm[4], *d_tbcrc, *d_idx[3];
-  int32_t*               d_src[3][4];
-  uint8_t *              d_cb, *d_parity, *d_sys_tail;
-  cf32 *                 d_y, *d_grid;
-  struct TxGrantsState*  gs; // srslte_hip_dl_tx_batch_grants / _grants2: created on first use
-  float                  rho_a; // pdsch.c:525: the precoders' `scaling`
-};
-
 // Device / host resources of the per-PDSCH grants mode of the transmit pipeline
-struct TxGrantsState {
-  uint32_t  V, W, Cmax, max_re, words, cb_stride, par_stride; // V PDSCHs of W codewords: W = V, or 2 V from the first srslte_hip_dl_tx_batch_grants2 call on
-  uint32_t *d_relist, *d_scr, *d_basis, *d_tbcrc;
-  uint8_t * d_cb, *d_parity, *d_sys_tail, *d_desc;
-  cf32*     d_y;
-  int32_t*  d_crs_src[4]; // per port: grid RE -> -1 (zero) or the CRS pilot -(v + 2), for pdsch_tx_map_kernel as the grid initialiser
-  int32_t*  d_crs_src_sp[4]; // the same for a TDD special subframe: the CRS symbols its DwPTS holds (refsignal_dl.c:162-225), or null
-  size_t    desc_bytes;
-  PinnedRing ring; // the host copies of the descriptor block
-  TxLevels   lv;
-  std::map<std::pair<uint32_t, uint32_t>, uint32_t*> rm_tbl; // (K, rv) -> rate-matching table over the encoder's byte streams
+struct TxGrantsState : TxGrantsEnc {
+  uint32_t         V = 0, W = 0, max_re = 0; // V PDSCHs of W codewords: W = V, or 2 V from the first srslte_hip_dl_tx_batch_grants2 call on
+  DevBuf<uint32_t> d_relist;
+  DevBuf<cf32>     d_y;
+  DevBuf<int32_t>  d_crs_src[4]; // per port: grid RE -> -1 (zero) or the CRS pilot -(v + 2), for pdsch_tx_map_kernel as the grid initialiser
+  DevBuf<int32_t>  d_crs_src_sp[4]; // the same for a TDD special subframe: the CRS symbols its DwPTS holds (refsignal_dl.c:162-225), or null
 };
 
-static void tx_grants_free(TxGrantsState* g)
-{
-  if (!g) return;
-  void* gb[] = {g->d_relist, g->d_scr, g->d_basis, g->d_tbcrc, g->d_cb, g->d_parity, g->d_sys_tail, g->d_desc, g->d_y,
-                g->d_crs_src[0], g->d_crs_src[1], g->d_crs_src[2], g->d_crs_src[3], g->d_crs_src_sp[0], g->d_crs_src_sp[1], g->d_crs_src_sp[2], g->d_crs_src_sp[3]};
-  for (void* b : gb) {
-    if (b) (void)hipFree(b);
+struct srslte_hip_dl_tx {
+  srslte_hip_dl_tx_cfg_t cfg  = {};
+  srslte_hip_ofdm_t*     ofdm = nullptr;
+  srslte_hip_chest_dl_t* crs  = nullptr; // for its CRS table
+  srslte_hip_cbsegm_t    seg  = {};
+  PuschTxGeom            cg   = {}; // CRC attachment / segmentation geometry (shared kernels)
+  PdschTxGeom            g    = {};
+  DevBuf<uint32_t>       d_scr, d_rm[4], d_tbcrc, d_idx[3];
+  DevBuf<int32_t>        d_src[3][4];
+  DevBuf<uint8_t>        d_cb, d_parity, d_sys_tail;
+  DevBuf<cf32>           d_y, d_grid;
+  std::unique_ptr<TxGrantsState> gs; // srslte_hip_dl_tx_batch_grants / _grants2: created on first use
+  float                  rho_a = 0.f; // pdsch.c:525: the precoders' `scaling`
+  ~srslte_hip_dl_tx()
+  {
+    srslte_hip_ofdm_destroy(ofdm);
+    srslte_hip_chest_dl_destroy(crs);
   }
-  for (auto& kv : g->rm_tbl) (void)hipFree(kv.second);
-  g->ring.destroy();
-  delete g;
-}
+};
 
-extern "C" void srslte_hip_dl_tx_destroy(srslte_hip_dl_tx_t* q)
-{
-  if (!q) return;
-  srslte_hip_ofdm_destroy(q->ofdm);
-  srslte_hip_chest_dl_destroy(q->crs);
-  void* bufs[] = {q->d_scr, q->d_rm[0], q->d_rm[1], q->d_rm[2], q->d_rm[3], q->d_tbcrc, q->d_idx[0], q->d_idx[1], q->d_idx[2],
-                  q->d_cb, q->d_parity, q->d_sys_tail, q->d_y, q->d_grid};
-  for (void* b : bufs) {
-    if (b) (void)hipFree(b);
-  }
-  for (auto& cls : q->d_src) {
-    for (int32_t* b : cls) {
-      if (b) (void)hipFree(b);
-    }
-  }
-  tx_grants_free(q->gs);
-  delete q;
-}
+extern "C" void srslte_hip_dl_tx_destroy(srslte_hip_dl_tx_t* q) { delete q; }
 
 extern "C" srslte_hip_dl_tx_t* srslte_hip_dl_tx_create(const srslte_hip_dl_tx_cfg_t* cfg)
 {
@@ -301,12 +270,10 @@ extern "C" srslte_hip_dl_tx_t* srslte_hip_dl_tx_create(const srslte_hip_dl_tx_cf
     hip_log("[srslte_hip] dl_tx: invalid configuration\n");
     return nullptr;
   }
-  auto* q = new srslte_hip_dl_tx();
-  memset(q, 0, sizeof(*q));
+  std::unique_ptr<srslte_hip_dl_tx> q(new srslte_hip_dl_tx());
   q->cfg = *cfg;
   if (srslte_hip_cbsegm(&q->seg, cfg->tbs) || q->seg.F || q->seg.C2 || (cfg->tbs % 8)) {
     hip_log("[srslte_hip] dl_tx: TBS %u needs filler bits or two code-block sizes; not supported on device yet\n", cfg->tbs);
-    delete q;
     return nullptr;
   }
   const uint32_t P = cfg->nof_prb, nre = 12 * P, B = cfg->max_batch, C = q->seg.C, K = q->seg.K1, Qm = 2 * (uint32_t)cfg->mod;
@@ -314,7 +281,6 @@ extern "C" srslte_hip_dl_tx_t* srslte_hip_dl_tx_create(const srslte_hip_dl_tx_cf
   const uint32_t lstart = cfg->cfi + (P < 10 ? 1 : 0), npt = cfg->nof_ports ? cfg->nof_ports : 1, glen = 2 * nsl * nre;
   if (cfg->mbsfn && (npt != 1 || cfg->tdd || cfg->mbsfn_area_id > 255 || cfg->non_mbsfn_region < 1 || cfg->non_mbsfn_region > 2 || cfg->p_a != 0.f)) {
     hip_log("[srslte_hip] dl_tx: an MBSFN pipeline is single-port FDD, area id 0-255, a non-MBSFN region of 1 or 2 symbols, no power offset\n");
-    delete q;
     return nullptr;
   }
   q->ofdm = srslte_hip_ofdm_create((int)P, nsl == 6 ? 0 : 1, 0);
@@ -333,7 +299,7 @@ extern "C" srslte_hip_dl_tx_t* srslte_hip_dl_tx_create(const srslte_hip_dl_tx_cf
     else pdsch_re_indices(cfg->cell_id, P, npt, rep_sf[c], lstart, idx, nsl);
     g.cls[c].nof_re = (int)idx.size();
     max_re          = idx.size() > max_re ? (uint32_t)idx.size() : max_re;
-    ok              = upload(&q->d_idx[c], idx) == SRSLTE_SUCCESS;
+    ok              = upload(q->d_idx[c], idx) == SRSLTE_SUCCESS;
     g.cls[c].idx    = q->d_idx[c];
     for (uint32_t port = 0; port < npt && ok; port++) {
       std::vector<int32_t> src(glen, -1);
@@ -347,7 +313,7 @@ extern "C" srslte_hip_dl_tx_t* srslte_hip_dl_tx_create(const srslte_hip_dl_tx_cf
       } else {
         crs_src_put(src.data(), port, port < 2 ? 4 : 2, nsl, P, cfg->cell_id);
       }
-      ok             = upload(&q->d_src[c][port], src) == SRSLTE_SUCCESS;
+      ok             = upload(q->d_src[c][port], src) == SRSLTE_SUCCESS;
       g.src[c][port] = q->d_src[c][port];
     }
   }
@@ -360,9 +326,9 @@ extern "C" srslte_hip_dl_tx_t* srslte_hip_dl_tx_create(const srslte_hip_dl_tx_cf
                                    : ((uint32_t)cfg->rnti << 14) + (sf << 9) + cfg->cell_id, max_bits, c);
       for (uint32_t i = 0; i < max_bits; i++) scr[(size_t)sf * scr_words + (i >> 5)] |= (uint32_t)c[i] << (i & 31);
     }
-    ok = upload(&q->d_scr, scr) == SRSLTE_SUCCESS;
+    ok = upload(q->d_scr, scr) == SRSLTE_SUCCESS;
   }
-  ok = ok && rm_tx_table_upload(K, 0, &q->d_rm[0]) == SRSLTE_SUCCESS;
+  ok = ok && rm_tx_table_upload(K, 0, q->d_rm[0]) == SRSLTE_SUCCESS;
   PuschTxGeom& cg = q->cg;
   cg.C = (int)C; cg.K = (int)K; cg.tbs = (int)cfg->tbs; cg.rlenB = (int)((C == 1 ? K : K - 24) / 8); cg.cb_stride = (int)((K / 8 + 15) & ~15u);
   cg.par_stride = (int)((K / 4 + 1 + 15) & ~15u);
@@ -375,18 +341,13 @@ extern "C" srslte_hip_dl_tx_t* srslte_hip_dl_tx_create(const srslte_hip_dl_tx_cf
   const float rho_a = powf(10.0f, cfg->p_a / 20.0f) * (npt == 1 ? 1.0f : sqrtf(2.0f)); // pdsch.c:525
   g.gain            = npt == 1 ? rho_a : rho_a / sqrtf(2.0f);                          // precoding.c:1859-1860
   q->rho_a          = rho_a;
-  ok = ok && hipMalloc((void**)&q->d_tbcrc, sizeof(uint32_t) * B) == hipSuccess &&
-       hipMalloc((void**)&q->d_cb, (size_t)cg.cb_stride * B * C) == hipSuccess &&
-       hipMalloc((void**)&q->d_parity, (size_t)cg.par_stride * B * C) == hipSuccess &&
-       hipMalloc((void**)&q->d_sys_tail, (size_t)B * C) == hipSuccess &&
-       hipMalloc((void**)&q->d_y, sizeof(cf32) * (size_t)max_re * B * npt) == hipSuccess &&
-       hipMalloc((void**)&q->d_grid, sizeof(cf32) * (size_t)glen * B * npt) == hipSuccess;
+  ok = ok && !q->d_tbcrc.alloc(B) && !q->d_cb.alloc((size_t)cg.cb_stride * B * C) && !q->d_parity.alloc((size_t)cg.par_stride * B * C) &&
+       !q->d_sys_tail.alloc((size_t)B * C) && !q->d_y.alloc((size_t)max_re * B * npt) && !q->d_grid.alloc((size_t)glen * B * npt);
   if (!ok) {
     hip_log("[srslte_hip] dl_tx: initialisation failed\n");
-    srslte_hip_dl_tx_destroy(q);
     return nullptr;
   }
-  return q;
+  return q.release();
 }
 
 extern "C" const void* srslte_hip_dl_tx_debug_buffer(const srslte_hip_dl_tx_t* q, int which)
@@ -411,7 +372,7 @@ extern "C" int srslte_hip_dl_tx_batch(srslte_hip_dl_tx_t* q, const uint8_t* d_tb
     return SRSLTE_ERROR;
   }
   if (!q->d_rm[rv]) {
-    if (int r = rm_tx_table_upload(q->seg.K1, rv, &q->d_rm[rv])) return r;
+    if (int r = rm_tx_table_upload(q->seg.K1, rv, q->d_rm[rv])) return r;
   }
   hipStream_t st = (hipStream_t)stream;
   PuschTxGeom cg = q->cg;
@@ -442,42 +403,28 @@ static int dl_tx_grants_init(srslte_hip_dl_tx_t* q, uint32_t V, uint32_t W)
 {
   const uint32_t P = q->cfg.nof_prb, cell_id = q->cfg.cell_id;
   const int      npt = q->g.nof_ports;
-  auto*          g = new TxGrantsState(); // value-initialised: every pointer and flag starts null / false
-  q->gs         = g;
-  g->V          = V;
-  g->W          = W;
-  g->Cmax       = q->seg.C;
-  g->max_re     = 14 * 12 * P;
-  g->words      = (g->max_re * 8 + 31) / 32 + 2;
-  g->cb_stride  = (6144 / 8 + 15) & ~15u;
-  g->par_stride = (6144 / 4 + 1 + 15) & ~15u;
-  const size_t nblk = (size_t)W * g->Cmax;
-  g->desc_bytes     = (sizeof(GrantDev) + sizeof(TxDesc)) * W;
-  if (g->ring.init(g->desc_bytes)) return SRSLTE_ERROR;
-  if (gold_basis_upload(g->words, &g->d_basis)) return SRSLTE_ERROR;
-  HIP_TRY(hipMalloc((void**)&g->d_relist, sizeof(uint32_t) * (size_t)g->max_re * V));
-  HIP_TRY(hipMalloc((void**)&g->d_scr, sizeof(uint32_t) * (size_t)g->words * W));
-  HIP_TRY(hipMalloc((void**)&g->d_tbcrc, sizeof(uint32_t) * W));
-  HIP_TRY(hipMalloc((void**)&g->d_cb, (size_t)g->cb_stride * nblk));
-  HIP_TRY(hipMalloc((void**)&g->d_parity, (size_t)g->par_stride * nblk));
-  HIP_TRY(hipMalloc((void**)&g->d_sys_tail, nblk));
-  HIP_TRY(hipMalloc((void**)&g->d_desc, g->desc_bytes));
-  HIP_TRY(hipMalloc((void**)&g->d_y, sizeof(cf32) * (size_t)g->max_re * V * npt));
+  q->gs.reset(new TxGrantsState());
+  TxGrantsState* g = q->gs.get();
+  g->V      = V;
+  g->W      = W;
+  g->max_re = 14 * 12 * P;
+  if (g->enc_init(W, q->seg.C, (g->max_re * 8 + 31) / 32 + 2, (sizeof(GrantDev) + sizeof(TxDesc)) * W) || g->d_relist.alloc((size_t)g->max_re * V) ||
+      g->d_y.alloc((size_t)g->max_re * V * npt))
+    return SRSLTE_ERROR;
   for (int port = 0; port < npt; port++) { // the CRS as srslte_hip_dl_tx_create maps them
     const uint32_t       nsl = q->cfg.cp_ext ? 6 : 7;
     std::vector<int32_t> src((size_t)14 * 12 * P, -1);
     crs_src_put(src.data(), port, port < 2 ? 4 : 2, nsl, P, cell_id);
-    if (upload(&g->d_crs_src[port], src)) return SRSLTE_ERROR;
+    if (upload(g->d_crs_src[port], src)) return SRSLTE_ERROR;
     if (q->cfg.tdd) { // srslte_refsignal_cs_nof_symbols for a special subframe: by the DwPTS length (phy_common.c:128-135)
       static const int dwt[10] = {3, 9, 10, 11, 12, 3, 9, 10, 11, 6};
       const int dw = dwt[q->cfg.tdd_ss_config % 10], t3 = nsl == 7 ? 12 : 10, t2 = nsl == 7 ? 9 : 8, t1 = nsl == 7 ? 5 : 4;
       const int nsym = dw >= t3 ? (port < 2 ? 4 : 2) : (dw >= t2 ? (port < 2 ? 3 : 2) : (dw >= t1 ? (port < 2 ? 2 : 1) : 1));
       std::vector<int32_t> sp((size_t)14 * 12 * P, -1);
       crs_src_put(sp.data(), port, nsym, nsl, P, cell_id);
-      if (upload(&g->d_crs_src_sp[port], sp)) return SRSLTE_ERROR;
+      if (upload(g->d_crs_src_sp[port], sp)) return SRSLTE_ERROR;
     }
   }
-  for (int mod = 1; mod <= 4; mod++) constellation_levels(mod, g->lv.v[mod]);
   return SRSLTE_SUCCESS;
 }
 
@@ -552,22 +499,20 @@ static int dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32
     n2 += g2.tbs2 ? 1 : 0;
   }
   const uint32_t W = two_cw ? 2 * V : V;
-  if (q->gs && q->gs->W < W) { // the first two-codeword call of an object that served single-codeword calls: the state is made anew for 2 V codewords
-    tx_grants_free(q->gs);     // (hipFree waits for what the device still runs on the old buffers)
-    q->gs = nullptr;
-  }
+  // the first two-codeword call of an object that served single-codeword calls: the state is made anew for 2 V codewords, the old one freed first
+  // (freeing waits for what the device still runs on the old buffers)
+  if (q->gs && q->gs->W < W) q->gs.reset();
   if (!q->gs && dl_tx_grants_init(q, V, W)) { // a failed start leaves no half-made state behind
-    tx_grants_free(q->gs);
-    q->gs = nullptr;
+    hip_log("[srslte_hip] dl_tx grants: initialisation failed\n");
+    q->gs.reset();
     return SRSLTE_ERROR;
   }
-  TxGrantsState* g     = q->gs;
-  uint8_t*       h_pin = nullptr;
-  if (int r = g->ring.acquire(&h_pin)) return r;
-  auto* h_gr = reinterpret_cast<GrantDev*>(h_pin);
+  TxGrantsState* g    = q->gs.get();
+  GrantDev*      h_gr = nullptr;
+  if (int r = g->desc.begin(&h_gr)) return r;
   auto* h_td = reinterpret_cast<TxDesc*>(h_gr + g->W);
-  auto* d_gr = reinterpret_cast<GrantDev*>(g->d_desc);
-  auto* d_td = reinterpret_cast<TxDesc*>(d_gr + g->W);
+  auto* d_gr = g->desc.dev<GrantDev>();
+  auto* d_td = reinterpret_cast<const TxDesc*>(d_gr + g->W);
   // the codewords: descriptor v < nof_grants = codeword 0 of a PDSCH, transmit diversity in front; then the codewords 1
   const uint32_t  ncw = nof_grants + n2;
   std::vector<Cw> cws(ncw);
@@ -599,20 +544,14 @@ static int dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32
     h_gr[c]    = gds[w.p];
     h_gr[c].cw = c < nof_grants ? 0 : 1; // the codeword's own scrambling sequence (36.211 6.3.1)
     const uint32_t K  = w.seg.K1;
-    auto           it = g->rm_tbl.find({K, w.rv});
-    if (it == g->rm_tbl.end()) {
-      uint32_t* d = nullptr;
-      if (rm_tx_table_upload(K, w.rv, &d)) return SRSLTE_ERROR;
-      it = g->rm_tbl.emplace(std::make_pair(K, w.rv), d).first;
-    }
-    TxDesc& td = h_td[c];
+    TxDesc&        td = h_td[c];
+    if (!(td.rm = g->rm_table(K, w.rv))) return SRSLTE_ERROR;
     td.row = (int)w.row; td.sf = (int)grants[w.p].sf; td.tbs = (int)w.tbs; td.C = (int)w.seg.C; td.K = (int)K; td.rlenB = (int)((w.seg.C == 1 ? K : K - 24) / 8);
-    td.cb0 = (int)cb0; td.nre = (int)nres[w.p]; td.mod = w.mod; td.Qm = 2 * w.mod; td.rm = it->second;
+    td.cb0 = (int)cb0; td.nre = (int)nres[w.p]; td.mod = w.mod; td.Qm = 2 * w.mod;
     td.scheme = g2.tx_scheme; td.codebook = (int)(g2.tbs2 ? g2.pmi + 1 : g2.pmi); td.cw1 = w.cw; // pdsch.c:1152
     cb0 += w.seg.C;
   }
-  HIP_TRY(hipMemcpyAsync(g->d_desc, h_pin, g->desc_bytes, hipMemcpyHostToDevice, st));
-  if (int r = g->ring.release(st)) return r;
+  if (int r = g->desc.commit(g->desc_bytes, st)) return r;
   PdschTxGeom tg = q->g; // ports, N_L, gain; the grid initialiser's maps
   tg.max_re = (int)g->max_re;
   tg.cb_stride = (int)g->cb_stride; tg.par_stride = (int)g->par_stride; // the slots of this mode are spaced for the largest block length

@@ -1,5 +1,5 @@
-// The pinned host buffers that carry a call's descriptors to the device, shared by the pipelines (pdsch.hip) and the control-region
-// encoder (pdcch_tx.hip).
+// The pinned host buffers that carry a call's descriptors to the device: the ring inside DescStage (dev_buf.hpp) and of the channel emulator
+// (channel.hip).
 #pragma once
 #include "common.hpp"
 

@@ -370,60 +370,56 @@ __global__ void pusch_ack_decide_kernel(const int* __restrict__ sum, uint8_t* __
 }
 } // namespace
 
+// srslte_hip_ul_rx_batch_grants: the shared grants machinery with one slot per PUSCH, plus the PUSCH front end's buffers; made on first use
+struct UlRxGrants {
+  GrantsState      gs;
+  DevBuf<cf32>     g_z, g_d;  // [max_grants][nsymb * 12 * nof_prb]
+  DevBuf<float>    g_res;     // [max_grants] x srslte_hip_chest_ul_res_t
+  DevBuf<int>      g_uci_sum; // [max_grants][4] HARQ-ACK accumulators, then the same for the rank indication
+  DevBuf<uint8_t>  g_uci;     // [max_grants][2] HARQ-ACK decisions of the last grants call, then [max_grants][2] rank indications
+  DevBuf<uint8_t>  g_cqi;     // [max_grants][64] CQI report bits of the last grants call, then [max_grants] CRC flags
+};
+
 struct srslte_hip_ul_rx {
-  srslte_hip_ul_rx_cfg_t cfg;
-  srslte_hip_ofdm_t*     ofdm;
-  srslte_hip_chest_ul_t* chest;
-  srslte_hip_tdec_t*     tdec;
-  srslte_hip_cbsegm_t    seg;
-  PuschGeom              pg;
-  RmGeom                 rg;
-  TbGeom                 tg;
-  uint32_t               W, in_stride;
-  uint32_t *             d_scr, *d_rm_tbl, *d_tbcrc, *d_tb_rem, *d_cb_syn, *d_cb_iters;
-  uint32_t*              d_rm_tbl_rv[4]; // rate de-matching tables of redundancy versions 1-3, made on first use ([0] unused: d_rm_tbl)
-  cf32 *                 d_grid, *d_ce, *d_z, *d_d;
-  float*                 d_res; // [B] x srslte_hip_chest_ul_res_t
-  int16_t *              d_g, *d_w;
-  uint8_t *              d_cb_bytes, *d_cb_ok;
-  int*                   d_ack_sum; // [B][4] ACK, then [B][4] RI
-  uint8_t*               d_ack;     // [B][2] HARQ-ACK decisions of the last call, then [B][2] rank indications
-  uint8_t*               d_cqi;     // [B][64] CQI report bits of the last call, then [B] CRC flags
-  int                    Qp_cqi;
-  // srslte_hip_ul_rx_batch_grants (created on first use): the shared grants machinery with one slot per PUSCH, plus the PUSCH front end's buffers
-  struct GrantsState*    gs;
-  cf32 *                 g_z, *g_d; // [max_grants][nsymb * 12 * nof_prb]
-  float*                 g_res;     // [max_grants] x srslte_hip_chest_ul_res_t
-  int*                   g_uci_sum; // [max_grants][4] HARQ-ACK accumulators, then the same for the rank indication
-  uint8_t*               g_uci;     // [max_grants][2] HARQ-ACK decisions of the last grants call, then [max_grants][2] rank indications
-  uint8_t*               g_cqi;     // [max_grants][64] CQI report bits of the last grants call, then [max_grants] CRC flags
+  srslte_hip_ul_rx_cfg_t cfg   = {};
+  srslte_hip_ofdm_t*     ofdm  = nullptr;
+  srslte_hip_chest_ul_t* chest = nullptr;
+  srslte_hip_tdec_t*     tdec  = nullptr;
+  srslte_hip_cbsegm_t    seg   = {};
+  PuschGeom              pg    = {};
+  RmGeom                 rg    = {};
+  TbGeom                 tg    = {};
+  uint32_t               W = 0, in_stride = 0;
+  DevBuf<uint32_t>       d_scr, d_tbcrc, d_tb_rem, d_cb_syn, d_cb_iters;
+  DevBuf<uint32_t>       d_rm_tbl_rv[4]; // rate de-matching tables: [0] made with the object, 1-3 on first use
+  DevBuf<cf32>           d_grid, d_ce, d_z, d_d;
+  DevBuf<float>          d_res; // [B] x srslte_hip_chest_ul_res_t
+  DevBuf<int16_t>        d_g, d_w;
+  DevBuf<uint8_t>        d_cb_bytes, d_cb_ok;
+  DevBuf<int>            d_ack_sum; // [B][4] ACK, then [B][4] RI
+  DevBuf<uint8_t>        d_ack;     // [B][2] HARQ-ACK decisions of the last call, then [B][2] rank indications
+  DevBuf<uint8_t>        d_cqi;     // [B][64] CQI report bits of the last call, then [B] CRC flags
+  int                    Qp_cqi = 0;
+  std::unique_ptr<UlRxGrants> ug; // srslte_hip_ul_rx_batch_grants: created on first use
+  ~srslte_hip_ul_rx()
+  {
+    srslte_hip_ofdm_destroy(ofdm);
+    srslte_hip_chest_ul_destroy(chest);
+    srslte_hip_tdec_destroy(tdec);
+  }
 };
 
 extern "C" const uint8_t* srslte_hip_ul_rx_ack(const srslte_hip_ul_rx_t* q) { return q ? q->d_ack : nullptr; }
 extern "C" const uint8_t* srslte_hip_ul_rx_ri(const srslte_hip_ul_rx_t* q) { return q ? q->d_ack + 2 * q->cfg.max_batch : nullptr; }
 extern "C" const uint8_t* srslte_hip_ul_rx_cqi(const srslte_hip_ul_rx_t* q) { return q ? q->d_cqi : nullptr; }
-extern "C" const uint8_t* srslte_hip_ul_rx_grants_ack(const srslte_hip_ul_rx_t* q) { return q ? q->g_uci : nullptr; }
-extern "C" const uint8_t* srslte_hip_ul_rx_grants_cqi(const srslte_hip_ul_rx_t* q) { return q ? q->g_cqi : nullptr; }
+extern "C" const uint8_t* srslte_hip_ul_rx_grants_ack(const srslte_hip_ul_rx_t* q) { return q && q->ug ? q->ug->g_uci : nullptr; }
+extern "C" const uint8_t* srslte_hip_ul_rx_grants_cqi(const srslte_hip_ul_rx_t* q) { return q && q->ug ? q->ug->g_cqi : nullptr; }
 extern "C" const uint8_t* srslte_hip_ul_rx_grants_ri(const srslte_hip_ul_rx_t* q)
 {
-  return q && q->g_uci ? q->g_uci + 2 * (q->cfg.max_grants ? q->cfg.max_grants : q->cfg.max_batch) : nullptr;
+  return q && q->ug ? q->ug->g_uci + 2 * (q->cfg.max_grants ? q->cfg.max_grants : q->cfg.max_batch) : nullptr;
 }
 
-extern "C" void srslte_hip_ul_rx_destroy(srslte_hip_ul_rx_t* q)
-{
-  if (!q) return;
-  srslte_hip_ofdm_destroy(q->ofdm);
-  srslte_hip_chest_ul_destroy(q->chest);
-  srslte_hip_tdec_destroy(q->tdec);
-  void* bufs[] = {q->d_scr, q->d_rm_tbl, q->d_tbcrc, q->d_tb_rem, q->d_cb_syn, q->d_cb_iters, q->d_grid, q->d_ce, q->d_z,
-                  q->d_d,   q->d_res,    q->d_g,     q->d_w,      q->d_cb_bytes, q->d_cb_ok, q->d_ack_sum, q->d_ack, q->d_cqi,
-                  q->d_rm_tbl_rv[1], q->d_rm_tbl_rv[2], q->d_rm_tbl_rv[3], q->g_z, q->g_d, q->g_res, q->g_uci_sum, q->g_uci, q->g_cqi};
-  for (void* b : bufs) {
-    if (b) (void)hipFree(b);
-  }
-  grants_free(q->gs);
-  delete q;
-}
+extern "C" void srslte_hip_ul_rx_destroy(srslte_hip_ul_rx_t* q) { delete q; }
 
 extern "C" srslte_hip_ul_rx_t* srslte_hip_ul_rx_create(const srslte_hip_ul_rx_cfg_t* cfg)
 {
@@ -433,18 +429,15 @@ extern "C" srslte_hip_ul_rx_t* srslte_hip_ul_rx_create(const srslte_hip_ul_rx_cf
     hip_log("[srslte_hip] ul_rx: invalid configuration\n");
     return nullptr;
   }
-  auto* q = new srslte_hip_ul_rx();
-  memset(q, 0, sizeof(*q));
+  std::unique_ptr<srslte_hip_ul_rx> q(new srslte_hip_ul_rx());
   q->cfg = *cfg;
   if (srslte_hip_cbsegm(&q->seg, cfg->tbs) || q->seg.F || q->seg.C2 || (cfg->tbs % 8)) {
     hip_log("[srslte_hip] ul_rx: TBS %u needs filler bits or two code-block sizes; not supported on device yet\n", cfg->tbs);
-    delete q;
     return nullptr;
   }
   // tbs = 0: a PUSCH without UL-SCH data carries a CQI report and nothing to decode (srslte_ulsch_decode, sch.c:1031-1065)
   if (cfg->tbs == 0 && cfg->cqi_len == 0) {
     hip_log("[srslte_hip] ul_rx: neither a transport block nor a CQI report\n");
-    delete q;
     return nullptr;
   }
   const uint32_t P = cfg->nof_prb, B = cfg->max_batch, C = q->seg.C, K = q->seg.K1, Qm = 2 * (uint32_t)cfg->mod, M_sc = 12 * cfg->L_prb;
@@ -464,11 +457,11 @@ extern "C" srslte_hip_ul_rx_t* srslte_hip_ul_rx_create(const srslte_hip_ul_rx_cf
       lte_gold_sequence(((uint32_t)cfg->rnti << 14) + (sf << 9) + cfg->cell_id, nbits, c);
       for (uint32_t i = 0; i < nbits; i++) scr[(size_t)sf * scr_words + (i >> 5)] |= (uint32_t)c[i] << (i & 31);
     }
-    ok = upload(&q->d_scr, scr) == SRSLTE_SUCCESS;
+    ok = upload(q->d_scr, scr) == SRSLTE_SUCCESS;
   }
   q->W         = C ? srslte_hip_tdec_autoimp_get_subblocks(K) : 0;
   q->in_stride = C ? (srslte_hip_tdec_input_len(K, q->W != 0) + 31) & ~31u : 0;
-  if (ok && C) ok = rm_rx_table_upload(K, 0, q->W, q->in_stride, &q->d_rm_tbl) == SRSLTE_SUCCESS; // as for the PDSCH
+  if (ok && C) ok = rm_rx_table_upload(K, 0, q->W, q->in_stride, q->d_rm_tbl_rv[0]) == SRSLTE_SUCCESS; // as for the PDSCH
   if (ok && C) {
     std::vector<uint32_t> rem(cfg->tbs + 24);
     uint32_t              v = 1;
@@ -477,7 +470,7 @@ extern "C" srslte_hip_ul_rx_t* srslte_hip_ul_rx_create(const srslte_hip_ul_rx_cf
       v <<= 1;
       if (v & 0x1000000) v ^= 0x1864CFB;
     }
-    ok = upload(&q->d_tbcrc, rem) == SRSLTE_SUCCESS;
+    ok = upload(q->d_tbcrc, rem) == SRSLTE_SUCCESS;
     if (ok && q->W) {
       const uint32_t        rlen = C == 1 ? K : K - 24, Lw = K / q->W;
       std::vector<uint32_t> t((size_t)C * K, 0);
@@ -487,30 +480,22 @@ extern "C" srslte_hip_ul_rx_t* srslte_hip_ul_rx_create(const srslte_hip_ul_rx_cf
           if (pos < cfg->tbs + 24) t[(size_t)c * K + (n % Lw) * q->W + n / Lw] = rem[pos];
         }
       }
-      ok = upload(&q->d_tb_rem, t) == SRSLTE_SUCCESS && hipMalloc((void**)&q->d_cb_syn, sizeof(uint32_t) * B * C) == hipSuccess;
+      ok = upload(q->d_tb_rem, t) == SRSLTE_SUCCESS && !q->d_cb_syn.alloc((size_t)B * C);
     }
   }
   const size_t glen = (size_t)2 * nsl * 12 * P;
-  ok = ok && hipMalloc((void**)&q->d_grid, sizeof(cf32) * glen * B) == hipSuccess &&
-       hipMalloc((void**)&q->d_ce, sizeof(cf32) * glen * B) == hipSuccess && hipMemset(q->d_ce, 0, sizeof(cf32) * glen * B) == hipSuccess &&
-       hipMalloc((void**)&q->d_z, sizeof(cf32) * (size_t)nof_re * B) == hipSuccess &&
-       hipMalloc((void**)&q->d_d, sizeof(cf32) * (size_t)nof_re * B) == hipSuccess &&
-       hipMalloc((void**)&q->d_res, sizeof(float) * 5 * B) == hipSuccess &&
-       hipMalloc((void**)&q->d_g, sizeof(int16_t) * ((size_t)nbits * B + 16)) == hipSuccess &&
-       (!C || (hipMalloc((void**)&q->d_w, sizeof(int16_t) * (size_t)q->in_stride * B * C) == hipSuccess &&
-               hipMalloc((void**)&q->d_cb_bytes, (size_t)(K / 8) * B * C) == hipSuccess &&
-               hipMalloc((void**)&q->d_cb_ok, (size_t)B * C) == hipSuccess && hipMemset(q->d_cb_ok, 0, (size_t)B * C) == hipSuccess &&
-               hipMemset(q->d_w, 0, sizeof(int16_t) * (size_t)q->in_stride * B * C) == hipSuccess &&
-               hipMalloc((void**)&q->d_cb_iters, sizeof(uint32_t) * B * C) == hipSuccess)) &&
-       hipMalloc((void**)&q->d_ack_sum, sizeof(int) * 8 * B) == hipSuccess && hipMalloc((void**)&q->d_ack, (size_t)4 * B) == hipSuccess &&
-       hipMemset(q->d_ack, 0, (size_t)4 * B) == hipSuccess &&
+  ok = ok && !q->d_grid.alloc(glen * B) && !q->d_ce.alloc(glen * B) && hipMemset(q->d_ce, 0, sizeof(cf32) * glen * B) == hipSuccess &&
+       !q->d_z.alloc((size_t)nof_re * B) && !q->d_d.alloc((size_t)nof_re * B) && !q->d_res.alloc((size_t)5 * B) && !q->d_g.alloc((size_t)nbits * B + 16) &&
+       (!C || (!q->d_w.alloc((size_t)q->in_stride * B * C) && !q->d_cb_bytes.alloc((size_t)(K / 8) * B * C) && !q->d_cb_ok.alloc((size_t)B * C) &&
+               hipMemset(q->d_cb_ok, 0, (size_t)B * C) == hipSuccess &&
+               hipMemset(q->d_w, 0, sizeof(int16_t) * (size_t)q->in_stride * B * C) == hipSuccess && !q->d_cb_iters.alloc((size_t)B * C))) &&
+       !q->d_ack_sum.alloc((size_t)8 * B) && !q->d_ack.alloc((size_t)4 * B) && hipMemset(q->d_ack, 0, (size_t)4 * B) == hipSuccess &&
        pusch_ack_qprime(cfg->ack_len, cfg->I_offset_ack, cfg->L_prb, nsymb, C * K, false, cfg->cqi_len, cfg->I_offset_cqi) >= 0 &&
        Qp_ri >= 0 && (uint32_t)Qp_ri < nof_re && Qp_cqi >= 0 && (C ? (uint32_t)(Qp_ri + Qp_cqi) + C < nof_re : (uint32_t)(Qp_ri + Qp_cqi) == nof_re) &&
-       hipMalloc((void**)&q->d_cqi, (size_t)65 * B) == hipSuccess && hipMemset(q->d_cqi, 0, (size_t)65 * B) == hipSuccess;
+       !q->d_cqi.alloc((size_t)65 * B) && hipMemset(q->d_cqi, 0, (size_t)65 * B) == hipSuccess;
   ok = ok && hipDeviceSynchronize() == hipSuccess; // the memsets above ran on the null stream
   if (!ok) {
     hip_log("[srslte_hip] ul_rx: initialisation failed\n");
-    srslte_hip_ul_rx_destroy(q);
     return nullptr;
   }
   q->pg.cell_nre = 12 * (int)P; q->pg.M_sc = (int)M_sc; q->pg.n_prb = (int)cfg->n_prb; q->pg.n_prb1 = (int)(cfg->hopping ? cfg->n_prb_slot1 : cfg->n_prb); q->pg.mod = cfg->mod; q->pg.Qm = (int)Qm;
@@ -525,7 +510,7 @@ extern "C" srslte_hip_ul_rx_t* srslte_hip_ul_rx_create(const srslte_hip_ul_rx_cf
   q->rg.e_off = Qp_cqi * (int)Qm;
   q->Qp_cqi   = Qp_cqi;
   q->tg.C = (int)C; q->tg.K = (int)K; q->tg.tbs = (int)cfg->tbs; q->tg.rlen = (int)(C <= 1 ? K : K - 24); q->tg.cb_stride = (int)(K / 8);
-  return q;
+  return q.release();
 }
 
 extern "C" const void* srslte_hip_ul_rx_debug_buffer(const srslte_hip_ul_rx_t* q, int which)
@@ -544,10 +529,10 @@ extern "C" const void* srslte_hip_ul_rx_debug_buffer(const srslte_hip_ul_rx_t* q
     case 9: return q->d_z;
     case 10: return q->d_ack;
     // per-PUSCH grants mode: estimator results, de-precoded symbols (at each PUSCH's offset), LLR rows, pass counts per block slot
-    case 20: return q->g_res;
-    case 21: return q->g_d;
-    case 22: return q->gs ? q->gs->d_e : nullptr;
-    case 23: return q->gs ? q->gs->d_cb_iters : nullptr;
+    case 20: return q->ug ? q->ug->g_res : nullptr;
+    case 21: return q->ug ? q->ug->g_d : nullptr;
+    case 22: return q->ug ? q->ug->gs.d_e : nullptr;
+    case 23: return q->ug ? q->ug->gs.d_cb_iters : nullptr;
   }
   return nullptr;
 }
@@ -570,13 +555,10 @@ extern "C" int srslte_hip_ul_rx_batch_harq(srslte_hip_ul_rx_t* q, const void* d_
   if (nof_sf == 0) return SRSLTE_SUCCESS;
   hipStream_t    st = (hipStream_t)stream;
   const uint32_t C = q->seg.C, K = q->seg.K1;
-  const uint32_t* d_rm_tbl = q->d_rm_tbl;
-  if (rv && C) {
-    if (!q->d_rm_tbl_rv[rv]) {
-      if (int rc = rm_rx_table_upload(K, rv, q->W, q->in_stride, &q->d_rm_tbl_rv[rv])) return rc;
-    }
-    d_rm_tbl = q->d_rm_tbl_rv[rv];
+  if (C && !q->d_rm_tbl_rv[rv]) {
+    if (int rc = rm_rx_table_upload(K, rv, q->W, q->in_stride, q->d_rm_tbl_rv[rv])) return rc;
   }
+  const uint32_t* d_rm_tbl = q->d_rm_tbl_rv[rv];
   const int combine = new_data ? 0 : 1;
   int            r = srslte_hip_ofdm_rx_sf_batch(q->ofdm, d_iq, q->d_grid, (int)nof_sf, stream);
   if (r) return r;
@@ -641,17 +623,15 @@ extern "C" int srslte_hip_ul_rx_batch_harq(srslte_hip_ul_rx_t* q, const void* d_
 static int ul_rx_grants_init(srslte_hip_ul_rx_t* q, uint32_t V, uint32_t max_re)
 {
   const uint32_t P = q->cfg.nof_prb;
-  q->gs = new GrantsState();
-  if (grants_alloc(q->gs, 12 * 12 * P, V, q->seg.C, 0, false, (sizeof(PuschDesc) + sizeof(ChestUlItem)) * V)) return SRSLTE_ERROR;
-  HIP_TRY(hipMalloc((void**)&q->g_z, sizeof(cf32) * (size_t)max_re * V));
-  HIP_TRY(hipMalloc((void**)&q->g_d, sizeof(cf32) * (size_t)max_re * V));
-  HIP_TRY(hipMalloc((void**)&q->g_res, sizeof(float) * 5 * V));
-  HIP_TRY(hipMalloc((void**)&q->g_uci_sum, sizeof(int) * 8 * V));
-  HIP_TRY(hipMalloc((void**)&q->g_uci, (size_t)4 * V));
-  HIP_TRY(hipMalloc((void**)&q->g_cqi, (size_t)65 * V));
-  HIP_TRY(hipMemset(q->g_cqi, 0, (size_t)65 * V));
+  q->ug.reset(new UlRxGrants());
+  UlRxGrants* u = q->ug.get();
+  if (grants_alloc(&u->gs, 12 * 12 * P, V, q->seg.C, 0, false, (sizeof(PuschDesc) + sizeof(ChestUlItem)) * V)) return SRSLTE_ERROR;
+  if (u->g_z.alloc((size_t)max_re * V) || u->g_d.alloc((size_t)max_re * V) || u->g_res.alloc((size_t)5 * V) || u->g_uci_sum.alloc((size_t)8 * V) ||
+      u->g_uci.alloc((size_t)4 * V) || u->g_cqi.alloc((size_t)65 * V))
+    return SRSLTE_ERROR;
+  HIP_TRY(hipMemset(u->g_cqi, 0, (size_t)65 * V));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemset(q->g_uci, 0, (size_t)4 * V));
+  HIP_TRY(hipMemset(u->g_uci, 0, (size_t)4 * V));
   HIP_TRY(hipDeviceSynchronize());
   return SRSLTE_SUCCESS;
 }
@@ -687,20 +667,16 @@ static int ul_rx_grants(srslte_hip_ul_rx_t* q, const void* d_iq, uint32_t tti0, 
   if (nof_sf == 0 || nof_grants == 0) return SRSLTE_SUCCESS;
   hipStream_t    st    = (hipStream_t)stream;
   const uint32_t nsymb = (uint32_t)q->pg.nsymb, max_re = nsymb * 12 * P;
-  if (!q->gs && ul_rx_grants_init(q, V, max_re)) { // a failed start leaves no half-made state behind
-    grants_free(q->gs);
-    q->gs = nullptr;
-    void** gb[] = {(void**)&q->g_z, (void**)&q->g_d, (void**)&q->g_res, (void**)&q->g_uci_sum, (void**)&q->g_uci, (void**)&q->g_cqi};
-    for (void** b : gb) { // the next call allocates them again; srslte_hip_ul_rx_grants_ack() must not hand out a buffer of a dead state
-      if (*b) (void)hipFree(*b);
-      *b = nullptr;
-    }
+  if (!q->ug && ul_rx_grants_init(q, V, max_re)) { // a failed start leaves no half-made state behind: srslte_hip_ul_rx_grants_ack() stays null
+    hip_log("[srslte_hip] ul_rx grants: initialisation failed\n");
+    q->ug.reset();
     return SRSLTE_ERROR;
   }
-  GrantsState* g     = q->gs;
+  UlRxGrants*  u     = q->ug.get();
+  GrantsState* g     = &u->gs;
   uint8_t*     h_pin = nullptr;
-  if (int r = g->ring.acquire(&h_pin)) return r;
-  const GrantsDesc h(g, h_pin), d(g, g->d_desc);
+  if (int r = g->desc.begin(&h_pin)) return r;
+  const GrantsDesc h(g, h_pin), d(g, g->desc.dev_bytes());
   GrantDev*        h_gr = h.gr;
   SfDesc*          h_sf = h.sf;
   auto*            h_pd = reinterpret_cast<PuschDesc*>(h.extra); // extra_desc_bytes: PuschDesc[V] | ChestUlItem[V]
@@ -779,40 +755,40 @@ static int ul_rx_grants(srslte_hip_ul_rx_t* q, const void* d_iq, uint32_t tti0, 
   if (pucch && (r = srslte_hip_ul_ctrl_pucch_batch(pucch->ctrl, q->d_grid, tti0, nof_sf, pucch->reqs, pucch->nof, pucch->d_res, stream))) return r;
   if (srs && (r = srslte_hip_srs_rx_batch(srs->srs, q->d_grid, tti0, nof_sf, srs->list, srs->nof, srs->d_res, srs->d_ce, stream))) return r;
   const int n16 = (int)((g->desc_bytes + 15) / 16);
-  hipLaunchKernelGGL(desc_copy_kernel, dim3(ceil_div(n16, 256)), dim3(256), 0, st, (const uint4*)h_pin, (uint4*)g->d_desc, n16);
+  hipLaunchKernelGGL(desc_copy_kernel, dim3(ceil_div(n16, 256)), dim3(256), 0, st, (const uint4*)h_pin, (uint4*)g->desc.dev_bytes(), n16);
   LAUNCH_CHECK();
-  if (int rc = g->ring.release(st)) return rc;
+  if (int rc = g->desc.committed(st)) return rc;
   for (uint32_t i = 0; i < nof_grants;) { // estimator: runs of equal (L_prb, n_dmrs)
     uint32_t j = i + 1;
     while (j < nof_grants && grants[order[j]].L_prb == grants[order[i]].L_prb && grants[order[j]].n_dmrs == grants[order[i]].n_dmrs) j++;
-    r = chest_ul_estimate_items(q->chest, tti0, grants[order[i]].L_prb, grants[order[i]].n_dmrs, d_it + i, (int)(j - i), q->d_grid, q->d_ce, q->g_res, st);
+    r = chest_ul_estimate_items(q->chest, tti0, grants[order[i]].L_prb, grants[order[i]].n_dmrs, d_it + i, (int)(j - i), q->d_grid, q->d_ce, u->g_res, st);
     if (r) return r;
     i = j;
   }
   hipLaunchKernelGGL(scr_gen_kernel, dim3(ceil_div((int)g->words, 256), nof_grants), dim3(256), 0, st, (const GrantDev*)d.gr, (const uint32_t*)g->d_basis, g->d_scr,
                      (int)g->words, (int)q->cfg.cell_id);
   hipLaunchKernelGGL(pusch_eq_grants_kernel, dim3(ceil_div((int)max_M, 256), nsymb, nof_grants), dim3(256), 0, st, (const cf32*)q->d_grid, (const cf32*)q->d_ce,
-                     (const float*)q->g_res, q->g_z, (const PuschDesc*)d_pd, 12 * (int)P, (int)nsymb, q->cfg.mmse, q->pg.nsl);
+                     (const float*)u->g_res, u->g_z, (const PuschDesc*)d_pd, 12 * (int)P, (int)nsymb, q->cfg.mmse, q->pg.nsl);
   LAUNCH_CHECK();
   for (uint32_t i = 0; i < nof_grants;) { // inverse transform precoding: runs of equal L_prb (srslte_dft_precoding_init_rx: inverse, 1/sqrt(N))
     uint32_t j = i + 1;
     while (j < nof_grants && grants[order[j]].L_prb == grants[order[i]].L_prb) j++;
     const size_t off = (size_t)h_pd[order[i]].zoff;
-    r = srslte_hip_dft_precoding_batch(q->g_z + off, q->g_d + off, grants[order[i]].L_prb, nsymb * (j - i), 0, stream);
+    r = srslte_hip_dft_precoding_batch(u->g_z + off, u->g_d + off, grants[order[i]].L_prb, nsymb * (j - i), 0, stream);
     if (r) return r;
     i = j;
   }
-  if (any_uci) HIP_TRY(hipMemsetAsync(q->g_uci_sum, 0, sizeof(int) * 8 * V, st));
-  hipLaunchKernelGGL(pusch_demod_grants_kernel, dim3(ceil_div((int)max_M, 64), nof_grants), dim3(256), 0, st, (const cf32*)q->g_d, (const uint32_t*)g->d_scr,
-                     (int)g->words, g->d_e, (int)g->max_bits, (const PuschDesc*)d_pd, (int)nsymb, q->g_uci_sum, q->g_uci_sum + 4 * V);
+  if (any_uci) HIP_TRY(hipMemsetAsync(u->g_uci_sum, 0, sizeof(int) * 8 * V, st));
+  hipLaunchKernelGGL(pusch_demod_grants_kernel, dim3(ceil_div((int)max_M, 64), nof_grants), dim3(256), 0, st, (const cf32*)u->g_d, (const uint32_t*)g->d_scr,
+                     (int)g->words, g->d_e, (int)g->max_bits, (const PuschDesc*)d_pd, (int)nsymb, u->g_uci_sum, u->g_uci_sum + 4 * V);
   LAUNCH_CHECK();
   if (any_uci) { // decisions of every row of the call (zero sums -> 0 where a PUSCH carries none); a call without any leaves the rows alone
-    hipLaunchKernelGGL(pusch_ack_decide_kernel, dim3(ceil_div((int)nof_grants, 64)), dim3(64), 0, st, (const int*)q->g_uci_sum, q->g_uci, (int)nof_grants);
-    hipLaunchKernelGGL(pusch_ack_decide_kernel, dim3(ceil_div((int)nof_grants, 64)), dim3(64), 0, st, (const int*)(q->g_uci_sum + 4 * V), q->g_uci + 2 * V,
+    hipLaunchKernelGGL(pusch_ack_decide_kernel, dim3(ceil_div((int)nof_grants, 64)), dim3(64), 0, st, (const int*)u->g_uci_sum, u->g_uci, (int)nof_grants);
+    hipLaunchKernelGGL(pusch_ack_decide_kernel, dim3(ceil_div((int)nof_grants, 64)), dim3(64), 0, st, (const int*)(u->g_uci_sum + 4 * V), u->g_uci + 2 * V,
                        (int)nof_grants);
   }
   if (any_cqi) { // the reports in front of the UL-SCH (sch.c:1031-1056); rows without one keep what they held
-    hipLaunchKernelGGL(pusch_cqi_decode_kernel, dim3(nof_grants), dim3(256), 0, st, (const int16_t*)g->d_e, (int)g->max_bits, 0, 0, q->g_cqi, q->g_cqi + 64 * V,
+    hipLaunchKernelGGL(pusch_cqi_decode_kernel, dim3(nof_grants), dim3(256), 0, st, (const int16_t*)g->d_e, (int)g->max_bits, 0, 0, u->g_cqi, u->g_cqi + 64 * V,
                        (const PuschDesc*)d_pd);
   }
   LAUNCH_CHECK();

@@ -182,36 +182,70 @@ __global__ __launch_bounds__(256) void pusch_tx_map_kernel(const cf32* __restric
   grid[((size_t)sf * 2 * g.nsl + l) * g.cell_nre + k] = v;
 }
 
+struct TxLevels { float v[5][16]; };   // constellation levels of one axis per srslte_mod_t (the grants modes of both transmit pipelines)
+
 } // namespace
 
-struct srslte_hip_ul_tx {
-  srslte_hip_ul_tx_cfg_t cfg;
-  srslte_hip_ofdm_t*     ofdm;
-  srslte_hip_chest_ul_t* dmrs;
-  srslte_hip_cbsegm_t    seg;
-  PuschTxGeom            g;
-  uint32_t *             d_scr, *d_rm, *d_tbcrc;
-  uint32_t*              d_rm_rv[4]; // rate-matching tables of redundancy versions 1-3, made on first use ([0] unused: d_rm)
-  uint8_t *              d_cb, *d_parity, *d_sys_tail, *d_qcqi;
-  uint16_t*              d_cqi_rm;
-  cf32 *                 d_d, *d_z, *d_grid;
-  struct UlTxGrantsState* gs; // srslte_hip_ul_tx_batch_grants: created on first use
-};
-static void ul_tx_grants_free(struct UlTxGrantsState* g);
-
-extern "C" void srslte_hip_ul_tx_destroy(srslte_hip_ul_tx_t* q)
-{
-  if (!q) return;
-  srslte_hip_ofdm_destroy(q->ofdm);
-  srslte_hip_chest_ul_destroy(q->dmrs);
-  void* bufs[] = {q->d_scr, q->d_rm, q->d_tbcrc, q->d_cb, q->d_parity, q->d_sys_tail, q->d_d, q->d_z, q->d_grid, q->d_qcqi, q->d_cqi_rm,
-                  q->d_rm_rv[1], q->d_rm_rv[2], q->d_rm_rv[3]};
-  for (void* b : bufs) {
-    if (b) (void)hipFree(b);
+// The encoder half of a transmit grants mode, downlink or uplink: ncw codewords of up to Cmax code blocks in slots spaced for the largest block
+// length, their scrambling rows and CRC words, the call's descriptor block and the rate-matching tables made on first use
+struct TxGrantsEnc {
+  uint32_t         Cmax = 0, words = 0, cb_stride = (6144 / 8 + 15) & ~15u, par_stride = (6144 / 4 + 1 + 15) & ~15u;
+  DevBuf<uint32_t> d_scr, d_basis, d_tbcrc;
+  DevBuf<uint8_t>  d_cb, d_parity, d_sys_tail;
+  size_t           desc_bytes = 0;
+  DescStage        desc; // the descriptor block: pinned host copies and the device block
+  TxLevels         lv = {};
+  std::map<std::pair<uint32_t, uint32_t>, DevBuf<uint32_t>> rm_tbl; // (K, rv) -> rate-matching table over the encoder's byte streams
+  int enc_init(uint32_t ncw, uint32_t Cmax_, uint32_t words_, size_t desc_bytes_)
+  {
+    Cmax = Cmax_; words = words_; desc_bytes = desc_bytes_;
+    const size_t nblk = (size_t)ncw * Cmax;
+    if (desc.init(desc_bytes) || gold_basis_upload(words, d_basis) || d_scr.alloc((size_t)words * ncw) || d_tbcrc.alloc(ncw) ||
+        d_cb.alloc((size_t)cb_stride * nblk) || d_parity.alloc((size_t)par_stride * nblk) || d_sys_tail.alloc(nblk))
+      return SRSLTE_ERROR;
+    for (int mod = 1; mod <= 4; mod++) constellation_levels(mod, lv.v[mod]);
+    return SRSLTE_SUCCESS;
   }
-  ul_tx_grants_free(q->gs);
-  delete q;
-}
+  const uint32_t* rm_table(uint32_t K, uint32_t rv) // null: the upload failed
+  {
+    auto it = rm_tbl.find({K, rv});
+    if (it == rm_tbl.end()) {
+      DevBuf<uint32_t> d;
+      if (rm_tx_table_upload(K, rv, d)) return nullptr;
+      it = rm_tbl.emplace(std::make_pair(K, rv), std::move(d)).first;
+    }
+    return it->second;
+  }
+};
+
+// Device / host resources of the per-PUSCH grants mode of the transmit pipeline (pusch_tx_grants.inc)
+struct UlTxGrantsState : TxGrantsEnc {
+  uint32_t        V = 0, max_sym = 0, cqi_stride = 0;
+  DevBuf<uint8_t> d_qcqi;
+  DevBuf<cf32>    d_d, d_z;
+  std::map<uint32_t, DevBuf<uint16_t>> cqi_w; // report size O > 11 -> srslte_rm_conv_tx order of its coded bits
+};
+
+struct srslte_hip_ul_tx {
+  srslte_hip_ul_tx_cfg_t cfg  = {};
+  srslte_hip_ofdm_t*     ofdm = nullptr;
+  srslte_hip_chest_ul_t* dmrs = nullptr;
+  srslte_hip_cbsegm_t    seg  = {};
+  PuschTxGeom            g    = {};
+  DevBuf<uint32_t>       d_scr, d_tbcrc;
+  DevBuf<uint32_t>       d_rm_rv[4]; // rate-matching tables: [0] made with the object, 1-3 on first use
+  DevBuf<uint8_t>        d_cb, d_parity, d_sys_tail, d_qcqi;
+  DevBuf<uint16_t>       d_cqi_rm;
+  DevBuf<cf32>           d_d, d_z, d_grid;
+  std::unique_ptr<UlTxGrantsState> gs; // srslte_hip_ul_tx_batch_grants: created on first use
+  ~srslte_hip_ul_tx()
+  {
+    srslte_hip_ofdm_destroy(ofdm);
+    srslte_hip_chest_ul_destroy(dmrs);
+  }
+};
+
+extern "C" void srslte_hip_ul_tx_destroy(srslte_hip_ul_tx_t* q) { delete q; }
 
 extern "C" srslte_hip_ul_tx_t* srslte_hip_ul_tx_create(const srslte_hip_ul_tx_cfg_t* cfg)
 {
@@ -221,12 +255,10 @@ extern "C" srslte_hip_ul_tx_t* srslte_hip_ul_tx_create(const srslte_hip_ul_tx_cf
     hip_log("[srslte_hip] ul_tx: invalid configuration\n");
     return nullptr;
   }
-  auto* q = new srslte_hip_ul_tx();
-  memset(q, 0, sizeof(*q));
+  std::unique_ptr<srslte_hip_ul_tx> q(new srslte_hip_ul_tx());
   q->cfg = *cfg;
   if (srslte_hip_cbsegm(&q->seg, cfg->tbs) || q->seg.F || q->seg.C2 || (cfg->tbs % 8)) {
     hip_log("[srslte_hip] ul_tx: TBS %u needs filler bits or two code-block sizes; not supported on device yet\n", cfg->tbs);
-    delete q;
     return nullptr;
   }
   const uint32_t P = cfg->nof_prb, B = cfg->max_batch, C = q->seg.C, K = q->seg.K1, Qm = 2 * (uint32_t)cfg->mod, M_sc = 12 * cfg->L_prb;
@@ -238,13 +270,11 @@ extern "C" srslte_hip_ul_tx_t* srslte_hip_ul_tx_create(const srslte_hip_ul_tx_cf
   g.nsl   = (int)nsl;
   if (cfg->tbs == 0 && cfg->cqi_len == 0) { // a PUSCH without UL-SCH data carries a CQI report (srslte_ulsch_encode, sch.c:1133-1165)
     hip_log("[srslte_hip] ul_tx: neither a transport block nor a CQI report\n");
-    delete q;
     return nullptr;
   }
   g.ack.O = (int)cfg->ack_len; g.ack.Qprime = pusch_ack_qprime(cfg->ack_len, cfg->I_offset_ack, cfg->L_prb, nsymb, C * K, false, cfg->cqi_len, cfg->I_offset_cqi);
   if (g.ack.Qprime < 0) {
     hip_log("[srslte_hip] ul_tx: invalid HARQ-ACK configuration\n");
-    delete q;
     return nullptr;
   }
   g.tbs = (int)cfg->tbs; g.rlenB = (int)((C <= 1 ? K : K - 24) / 8); g.cb_stride = (int)((K / 8 + 15) & ~15u);
@@ -252,13 +282,11 @@ extern "C" srslte_hip_ul_tx_t* srslte_hip_ul_tx_create(const srslte_hip_ul_tx_cf
   g.ri.O = (int)cfg->ri_len; g.ri.Qprime = pusch_ack_qprime(cfg->ri_len, cfg->I_offset_ri, cfg->L_prb, nsymb, C * K, true, cfg->cqi_len, cfg->I_offset_cqi);
   if (g.ri.Qprime < 0 || (uint32_t)g.ri.Qprime >= nof_re) {
     hip_log("[srslte_hip] ul_tx: invalid rank-indication configuration\n");
-    delete q;
     return nullptr;
   }
   g.Qp_cqi = pusch_cqi_qprime(cfg->cqi_len, cfg->I_offset_cqi, cfg->L_prb, nsymb, C * K, (uint32_t)g.ri.Qprime);
   if (g.Qp_cqi < 0 || (C ? (uint32_t)(g.ri.Qprime + g.Qp_cqi) + C >= nof_re : (uint32_t)(g.ri.Qprime + g.Qp_cqi) != nof_re)) {
     hip_log("[srslte_hip] ul_tx: invalid CQI configuration\n");
-    delete q;
     return nullptr;
   }
   g.cqi_stride = (g.Qp_cqi * (int)Qm + 15) & ~15;
@@ -276,31 +304,26 @@ extern "C" srslte_hip_ul_tx_t* srslte_hip_ul_tx_create(const srslte_hip_ul_tx_cf
       lte_gold_sequence(((uint32_t)cfg->rnti << 14) + (sf << 9) + cfg->cell_id, nbits, c);
       for (uint32_t i = 0; i < nbits; i++) scr[(size_t)sf * scr_words + (i >> 5)] |= (uint32_t)c[i] << (i & 31);
     }
-    ok = upload(&q->d_scr, scr) == SRSLTE_SUCCESS;
+    ok = upload(q->d_scr, scr) == SRSLTE_SUCCESS;
   }
-  if (ok && C) ok = rm_tx_table_upload(K, 0, &q->d_rm) == SRSLTE_SUCCESS; // rate matching, rv 0
+  if (ok && C) ok = rm_tx_table_upload(K, 0, q->d_rm_rv[0]) == SRSLTE_SUCCESS; // rate matching, rv 0
   if (ok && cfg->cqi_len > 11) { // the CQI report's rate matching: cqi_rm_conv_order read circularly up to Q
     const std::vector<uint16_t> w = cqi_rm_conv_order(cfg->cqi_len);
     const int                   Q = g.Qp_cqi * (int)Qm;
     std::vector<uint16_t>       t((size_t)(Q > 0 ? Q : 1));
     for (int i = 0; i < Q; i++) t[i] = w[(size_t)i % w.size()];
-    ok = upload(&q->d_cqi_rm, t) == SRSLTE_SUCCESS;
+    ok = upload(q->d_cqi_rm, t) == SRSLTE_SUCCESS;
   }
-  if (ok && cfg->cqi_len) ok = hipMalloc((void**)&q->d_qcqi, (size_t)g.cqi_stride * B + 16) == hipSuccess;
+  if (ok && cfg->cqi_len) ok = !q->d_qcqi.alloc((size_t)g.cqi_stride * B + 16);
   const size_t glen = (size_t)2 * nsl * 12 * P;
-  ok = ok && hipMalloc((void**)&q->d_tbcrc, sizeof(uint32_t) * B) == hipSuccess &&
-       (!C || (hipMalloc((void**)&q->d_cb, (size_t)g.cb_stride * B * C) == hipSuccess &&
-               hipMalloc((void**)&q->d_parity, (size_t)g.par_stride * B * C) == hipSuccess &&
-               hipMalloc((void**)&q->d_sys_tail, (size_t)B * C) == hipSuccess)) &&
-       hipMalloc((void**)&q->d_d, sizeof(cf32) * (size_t)nof_re * B) == hipSuccess &&
-       hipMalloc((void**)&q->d_z, sizeof(cf32) * (size_t)nof_re * B) == hipSuccess &&
-       hipMalloc((void**)&q->d_grid, sizeof(cf32) * glen * B) == hipSuccess;
+  ok = ok && !q->d_tbcrc.alloc(B) &&
+       (!C || (!q->d_cb.alloc((size_t)g.cb_stride * B * C) && !q->d_parity.alloc((size_t)g.par_stride * B * C) && !q->d_sys_tail.alloc((size_t)B * C))) &&
+       !q->d_d.alloc((size_t)nof_re * B) && !q->d_z.alloc((size_t)nof_re * B) && !q->d_grid.alloc(glen * B);
   if (!ok) {
     hip_log("[srslte_hip] ul_tx: initialisation failed\n");
-    srslte_hip_ul_tx_destroy(q);
     return nullptr;
   }
-  return q;
+  return q.release();
 }
 
 extern "C" const void* srslte_hip_ul_tx_debug_buffer(const srslte_hip_ul_tx_t* q, int which)
@@ -354,13 +377,10 @@ extern "C" int srslte_hip_ul_tx_batch_rv(srslte_hip_ul_tx_t* q, const uint8_t* d
   hipStream_t st = (hipStream_t)stream;
   const void* d_r = nullptr;
   if (int r = chest_ul_dmrs_table(q->dmrs, q->cfg.L_prb, q->cfg.n_dmrs, &d_r)) return r;
-  const uint32_t* d_rm = q->d_rm;
-  if (rv && q->seg.C) {
-    if (!q->d_rm_rv[rv]) {
-      if (int r = rm_tx_table_upload(q->seg.K1, rv, &q->d_rm_rv[rv])) return r;
-    }
-    d_rm = q->d_rm_rv[rv];
+  if (q->seg.C && !q->d_rm_rv[rv]) {
+    if (int r = rm_tx_table_upload(q->seg.K1, rv, q->d_rm_rv[rv])) return r;
   }
+  const uint32_t* d_rm = q->d_rm_rv[rv];
   PuschTxGeom g = q->g;
   g.tti0        = (int)tti0;
   g.tb_stride   = (int)tb_stride;

@@ -90,57 +90,17 @@ __global__ __launch_bounds__(256) void pusch_tx_scatter_kernel(const cf32* __res
 
 } // namespace
 
-struct UlTxGrantsState {
-  uint32_t  V, Cmax, words, cb_stride, par_stride, max_sym, cqi_stride;
-  uint32_t *d_scr, *d_basis, *d_tbcrc;
-  uint8_t * d_cb, *d_parity, *d_sys_tail, *d_desc, *d_qcqi;
-  cf32 *    d_d, *d_z;
-  size_t    desc_bytes;
-  PinnedRing ring; // the host copies of the descriptor block
-  TxLevels   lv;
-  std::map<std::pair<uint32_t, uint32_t>, uint32_t*> rm_tbl; // (K, rv)
-  std::map<uint32_t, std::pair<uint16_t*, uint32_t>> cqi_w;  // report size O > 11 -> (device table, length)
-};
-
-static void ul_tx_grants_free(UlTxGrantsState* g)
-{
-  if (!g) return;
-  void* gb[] = {g->d_scr, g->d_basis, g->d_tbcrc, g->d_cb, g->d_parity, g->d_sys_tail, g->d_desc, g->d_qcqi, g->d_d, g->d_z};
-  for (void* b : gb) {
-    if (b) (void)hipFree(b);
-  }
-  for (auto& kv : g->rm_tbl) (void)hipFree(kv.second);
-  for (auto& kv : g->cqi_w) (void)hipFree(kv.second.first);
-  g->ring.destroy();
-  delete g;
-}
-
 static int ul_tx_grants_init(srslte_hip_ul_tx_t* q, uint32_t V)
 {
   const uint32_t P = q->cfg.nof_prb, nsymb = (uint32_t)q->g.nsymb;
-  auto*          g = new UlTxGrantsState(); // value-initialised
-  q->gs         = g;
+  q->gs.reset(new UlTxGrantsState());
+  UlTxGrantsState* g = q->gs.get();
   g->V          = V;
-  g->Cmax       = q->seg.C;
   g->max_sym    = nsymb * 12 * P;
-  g->words      = (g->max_sym * 6 + 31) / 32 + 2;
-  g->cb_stride  = (6144 / 8 + 15) & ~15u;
-  g->par_stride = (6144 / 4 + 1 + 15) & ~15u;
   g->cqi_stride = (g->max_sym * 6 + 15) & ~15u; // a report may take the whole allocation (min(.., M_sc N_symb - Q'_ri), uci.c:264-281)
-  const size_t nblk = (size_t)V * g->Cmax;
-  g->desc_bytes     = (sizeof(GrantDev) + sizeof(TxDesc) + sizeof(PuschTxDesc)) * V;
-  if (g->ring.init(g->desc_bytes)) return SRSLTE_ERROR;
-  if (gold_basis_upload(g->words, &g->d_basis)) return SRSLTE_ERROR;
-  HIP_TRY(hipMalloc((void**)&g->d_scr, sizeof(uint32_t) * (size_t)g->words * V));
-  HIP_TRY(hipMalloc((void**)&g->d_tbcrc, sizeof(uint32_t) * V));
-  HIP_TRY(hipMalloc((void**)&g->d_cb, (size_t)g->cb_stride * nblk));
-  HIP_TRY(hipMalloc((void**)&g->d_parity, (size_t)g->par_stride * nblk));
-  HIP_TRY(hipMalloc((void**)&g->d_sys_tail, nblk));
-  HIP_TRY(hipMalloc((void**)&g->d_desc, g->desc_bytes));
-  HIP_TRY(hipMalloc((void**)&g->d_qcqi, (size_t)g->cqi_stride * V));
-  HIP_TRY(hipMalloc((void**)&g->d_d, sizeof(cf32) * (size_t)g->max_sym * V));
-  HIP_TRY(hipMalloc((void**)&g->d_z, sizeof(cf32) * (size_t)g->max_sym * V));
-  for (int mod = 1; mod <= 4; mod++) constellation_levels(mod, g->lv.v[mod]);
+  if (g->enc_init(V, q->seg.C, (g->max_sym * 6 + 31) / 32 + 2, (sizeof(GrantDev) + sizeof(TxDesc) + sizeof(PuschTxDesc)) * V) ||
+      g->d_qcqi.alloc((size_t)g->cqi_stride * V) || g->d_d.alloc((size_t)g->max_sym * V) || g->d_z.alloc((size_t)g->max_sym * V))
+    return SRSLTE_ERROR;
   return SRSLTE_SUCCESS;
 }
 
@@ -157,19 +117,18 @@ extern "C" int srslte_hip_ul_tx_batch_grants(srslte_hip_ul_tx_t* q, const uint8_
   if (nof_sf == 0) return SRSLTE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
   if (!q->gs && ul_tx_grants_init(q, V)) { // a failed start leaves no half-made state behind
-    ul_tx_grants_free(q->gs);
-    q->gs = nullptr;
+    hip_log("[srslte_hip] ul_tx grants: initialisation failed\n");
+    q->gs.reset();
     return SRSLTE_ERROR;
   }
-  UlTxGrantsState* g     = q->gs;
-  uint8_t*         h_pin = nullptr;
-  if (int r = g->ring.acquire(&h_pin)) return r;
-  auto* h_gr = reinterpret_cast<GrantDev*>(h_pin);
+  UlTxGrantsState* g    = q->gs.get();
+  GrantDev*        h_gr = nullptr;
+  if (int r = g->desc.begin(&h_gr)) return r;
   auto* h_td = reinterpret_cast<TxDesc*>(h_gr + V);
   auto* h_pd = reinterpret_cast<PuschTxDesc*>(h_td + V);
-  auto* d_gr = reinterpret_cast<GrantDev*>(g->d_desc);
-  auto* d_td = reinterpret_cast<TxDesc*>(d_gr + V);
-  auto* d_pd = reinterpret_cast<PuschTxDesc*>(d_td + V);
+  auto* d_gr = g->desc.dev<GrantDev>();
+  auto* d_td = reinterpret_cast<const TxDesc*>(d_gr + V);
+  auto* d_pd = reinterpret_cast<const PuschTxDesc*>(d_td + V);
   std::vector<srslte_hip_cbsegm_t> segs(nof_grants);
   std::vector<uint32_t>            by_k(nof_grants), by_l(nof_grants);
   uint32_t                         max_M = 0;
@@ -212,15 +171,11 @@ extern "C" int srslte_hip_ul_tx_batch_grants(srslte_hip_ul_tx_t* q, const uint8_
       hip_log("[srslte_hip] ul_tx grants: entry %u: invalid UCI configuration\n", p);
       return SRSLTE_ERROR_INVALID_INPUTS;
     }
-    auto it = g->rm_tbl.find({K, gr.rv});
-    if (it == g->rm_tbl.end() && C) {
-      uint32_t* d = nullptr;
-      if (rm_tx_table_upload(K, gr.rv, &d)) return SRSLTE_ERROR;
-      it = g->rm_tbl.emplace(std::make_pair(K, gr.rv), d).first;
-    }
     TxDesc& td = h_td[p];
+    td.rm      = C ? g->rm_table(K, gr.rv) : nullptr;
+    if (C && !td.rm) return SRSLTE_ERROR;
     td.row = (int)p; td.sf = (int)gr.sf; td.tbs = (int)gr.tbs; td.C = (int)C; td.K = (int)K; td.rlenB = (int)((C <= 1 ? K : K - 24) / 8);
-    td.nre = (int)nof_re; td.mod = gr.mod; td.Qm = 2 * gr.mod; td.rm = C ? it->second : nullptr;
+    td.nre = (int)nof_re; td.mod = gr.mod; td.Qm = 2 * gr.mod;
     PuschTxDesc& pd = h_pd[p];
     const uint32_t g_re = nof_re - (uint32_t)Qp_ri - (uint32_t)Qp_cqi; // UL-SCH symbols (sch.c:1157-1160)
     pd.M_sc = 12 * (int)gr.L_prb; pd.n_prb = (int)gr.n_prb; pd.n_prb1 = (int)gr.n_prb_slot1; pd.syms_lo = C ? (int)(g_re / C) : 0; pd.C_lo = C ? (int)(C - g_re % C) : 0;
@@ -229,19 +184,17 @@ extern "C" int srslte_hip_ul_tx_batch_grants(srslte_hip_ul_tx_t* q, const uint8_
     if (gr.cqi_len > 11) { // the CQI report's rate matching (cqi_rm_conv_order), read circularly by the kernel
       auto cw = g->cqi_w.find(gr.cqi_len);
       if (cw == g->cqi_w.end()) {
-        const std::vector<uint16_t> w = cqi_rm_conv_order(gr.cqi_len);
-        uint16_t*                   d = nullptr;
-        if (upload(&d, w)) return SRSLTE_ERROR;
-        cw = g->cqi_w.emplace(gr.cqi_len, std::make_pair(d, (uint32_t)w.size())).first;
+        DevBuf<uint16_t> d;
+        if (upload(d, cqi_rm_conv_order(gr.cqi_len))) return SRSLTE_ERROR;
+        cw = g->cqi_w.emplace(gr.cqi_len, std::move(d)).first;
       }
-      pd.cqi_w = cw->second.first; pd.cqi_wlen = (int)cw->second.second;
+      pd.cqi_w = cw->second; pd.cqi_wlen = (int)cw->second.size();
     }
     const void* d_r = nullptr;
     if (int r = chest_ul_dmrs_table_cached(q->dmrs, gr.L_prb, gr.n_dmrs, &d_r)) return r;
     pd.dmrs = (const cf32*)d_r;
   }
-  HIP_TRY(hipMemcpyAsync(g->d_desc, h_pin, g->desc_bytes, hipMemcpyHostToDevice, st));
-  if (int r = g->ring.release(st)) return r;
+  if (int r = g->desc.commit(g->desc_bytes, st)) return r;
   HIP_TRY(hipMemsetAsync(q->d_grid, 0, sizeof(cf32) * (size_t)2 * q->g.nsl * 12 * P * nof_sf, st)); // ue_ul.c:320: the grid is cleared, then pusch_put
   if (nof_grants) {
     hipLaunchKernelGGL(scr_gen_kernel, dim3(ceil_div((int)g->words, 256), nof_grants), dim3(256), 0, st, (const GrantDev*)d_gr, (const uint32_t*)g->d_basis,

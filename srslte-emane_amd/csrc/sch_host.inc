@@ -6,22 +6,20 @@
 // (unless all zero: a fresh buffer, srslte_softbuffer_rx_reset_tbs) and those that failed come back; blocks whose CRC passed in an
 // earlier transmission are neither combined nor decoded (sch.c:317-318). Built on the grants machinery (one slot).
 struct srslte_hip_sch {
-  GrantsState* gs = nullptr;
+  GrantsState  gs;
   uint32_t     max_tbs = 0, max_e = 0, Cmax = 0;
   bool         l8 = false;
   hipStream_t  st = nullptr;
-  uint8_t*     h_pin = nullptr; // pinned: e_bits | soft buffers [Cmax][stride] | bytes [Cmax][768] | flags [Cmax] | passes [Cmax]
+  PinBuf       h_pin; // pinned: e_bits | soft buffers [Cmax][stride] | bytes [Cmax][768] | flags [Cmax] | passes [Cmax]
   size_t       o_w = 0, o_bytes = 0, o_ok = 0, o_it = 0, pin_bytes = 0;
+  ~srslte_hip_sch()
+  {
+    if (st) (void)hipStreamSynchronize(st); // a decode that returned early may have left copies queued: they end before the buffers go
+    if (st) (void)hipStreamDestroy(st);
+  }
 };
 
-extern "C" void srslte_hip_sch_destroy(srslte_hip_sch_t* q)
-{
-  if (!q) return;
-  grants_free(q->gs);
-  if (q->h_pin) (void)hipHostFree(q->h_pin);
-  if (q->st) (void)hipStreamDestroy(q->st);
-  delete q;
-}
+extern "C" void srslte_hip_sch_destroy(srslte_hip_sch_t* q) { delete q; }
 
 extern "C" srslte_hip_sch_t* srslte_hip_sch_create(uint32_t max_tbs, uint32_t max_e_bits, int llr_8bit)
 {
@@ -30,25 +28,21 @@ extern "C" srslte_hip_sch_t* srslte_hip_sch_create(uint32_t max_tbs, uint32_t ma
     hip_log("[srslte_hip] sch: invalid max_tbs=%u / max_e_bits=%u\n", max_tbs, max_e_bits);
     return nullptr;
   }
-  auto* q    = new srslte_hip_sch();
+  std::unique_ptr<srslte_hip_sch> q(new srslte_hip_sch());
   q->max_tbs = max_tbs; q->max_e = max_e_bits; q->Cmax = seg.C; q->l8 = llr_8bit != 0;
-  q->gs      = new GrantsState();
   const size_t esz = q->l8 ? 1 : 2;
-  if (grants_alloc(q->gs, (max_e_bits + 7) / 8, 1, q->Cmax, 0, false, 0) != SRSLTE_SUCCESS ||
-      hipStreamCreateWithFlags(&q->st, hipStreamNonBlocking) != hipSuccess) {
-    srslte_hip_sch_destroy(q);
-    return nullptr;
-  }
-  q->o_w     = ((size_t)q->gs->max_bits * esz + 63) & ~(size_t)63;
-  q->o_bytes = q->o_w + (((size_t)q->Cmax * q->gs->stride * esz + 63) & ~(size_t)63);
+  bool ok = grants_alloc(&q->gs, (max_e_bits + 7) / 8, 1, q->Cmax, 0, false, 0) == SRSLTE_SUCCESS &&
+            hipStreamCreateWithFlags(&q->st, hipStreamNonBlocking) == hipSuccess;
+  q->o_w     = ((size_t)q->gs.max_bits * esz + 63) & ~(size_t)63;
+  q->o_bytes = q->o_w + (((size_t)q->Cmax * q->gs.stride * esz + 63) & ~(size_t)63);
   q->o_ok    = q->o_bytes + (size_t)q->Cmax * 768;
   q->o_it    = (q->o_ok + q->Cmax + 63) & ~(size_t)63;
   q->pin_bytes = q->o_it + (size_t)q->Cmax * 4;
-  if (hipHostMalloc((void**)&q->h_pin, q->pin_bytes) != hipSuccess) {
-    srslte_hip_sch_destroy(q);
+  if (!ok || q->h_pin.alloc(q->pin_bytes)) {
+    hip_log("[srslte_hip] sch: initialisation failed\n");
     return nullptr;
   }
-  return q;
+  return q.release();
 }
 
 // e_bits: nof_e_bits LLRs of the transport block (int16, or int8 if the object was made for 8-bit LLRs). mod: 1 QPSK .. 4 256QAM; Nl as
@@ -61,11 +55,11 @@ extern "C" int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, ui
   if (!q || !e_bits || !buffer_f || !cb_crc || !cb_bytes || nof_e_bits == 0 || nof_e_bits > q->max_e || max_iterations == 0 || Nl < 1 || Nl > 2 || mod < 1 ||
       mod > 4)
     return SRSLTE_ERROR_INVALID_INPUTS;
-  GrantsState*   g    = q->gs;
+  GrantsState*   g    = &q->gs;
   const size_t   esz  = q->l8 ? 1 : 2;
   uint8_t*       h_pin = nullptr;
-  if (int r = g->ring.acquire(&h_pin)) return r;
-  const GrantsDesc h(g, h_pin), d(g, g->d_desc);
+  if (int r = g->desc.begin(&h_pin)) return r;
+  const GrantsDesc h(g, h_pin), d(g, g->desc.dev_bytes());
   SfDesc*          h_sf = h.sf;
   CbDesc*          h_cb = h.cb;
   memset(h.gr, 0, sizeof(GrantDev));
@@ -98,7 +92,7 @@ extern "C" int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, ui
     }
     uint8_t* stage = q->h_pin + q->o_w + (size_t)c * g->stride * esz;
     memcpy(stage, src, (size_t)len * esz);
-    HIP_TRY(hipMemcpyAsync((uint8_t*)g->d_w + (size_t)c * g->stride * esz, stage, (size_t)len * esz, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync((uint8_t*)g->d_w.get() + (size_t)c * g->stride * esz, stage, (size_t)len * esz, hipMemcpyHostToDevice, st));
   }
   if (sum_passes) *sum_passes = 0;
   if (todo == 0) return SRSLTE_SUCCESS;
@@ -106,8 +100,7 @@ extern "C" int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, ui
   memcpy(q->h_pin, e_bits, (size_t)nof_e_bits * esz);
   HIP_TRY(hipMemcpyAsync(g->d_e, q->h_pin, (size_t)nof_e_bits * esz, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(g->d_cb_ok, h_ok, C, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(g->d_desc, h_pin, g->desc_bytes, hipMemcpyHostToDevice, st));
-  if (int r = g->ring.release(st)) return r;
+  if (int r = g->desc.commit(g->desc_bytes, st)) return r;
   // no transport-block assembly on the device: the caller (sch.c's decode_tb, compat) assembles from the blocks' bytes as upstream does
   if (int r = grants_back_end(g, bd, d.sf, d.cb, d.map, 0, max_iterations, 1, 1, 0, nullptr, 0, nullptr, st)) return r;
   // ---- results down: bytes, flags, pass counts; the soft buffers of blocks that failed (the next transmission combines into them)
@@ -127,7 +120,7 @@ extern "C" int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, ui
     cb_crc[c] = h_ok2[c];
     if (!h_ok2[c]) {
       failed++;
-      HIP_TRY(hipMemcpyAsync(q->h_pin + q->o_w + (size_t)c * g->stride * esz, (uint8_t*)g->d_w + (size_t)c * g->stride * esz, (size_t)len * esz,
+      HIP_TRY(hipMemcpyAsync(q->h_pin + q->o_w + (size_t)c * g->stride * esz, (uint8_t*)g->d_w.get() + (size_t)c * g->stride * esz, (size_t)len * esz,
                              hipMemcpyDeviceToHost, st));
     }
   }
