@@ -814,7 +814,7 @@ int srslte_hip_dl_ctrl_phich_re(const srslte_hip_dl_ctrl_tx_cfg_t* cfg, uint32_t
  * nant mask, which rejects an all-zero payload (pbch.c:373-391). The first hit in (nant, dst) order wins. Stateless: each subframe 0 of a
  * batch is decoded on its own. d_mib [nof_sf] may be device-visible pinned host memory. Buffers are allocated by srslte_hip_dl_ctrl_create.
  * Refused with SRSLTE_ERROR_INVALID_INPUTS: null pointers, nof_sf > max_batch.
- * Not here: soft combining across calls (the reference's frame_idx window and memmove), cell search (PSS / SSS detection), TDD positions of
+ * Not here: soft combining across calls (the reference's frame_idx window and memmove), cell search (PSS / SSS detection: srslte_hip_sync_find_batch below), TDD positions of
  * PSS / SSS, broadcast in the fixed-grant srslte_hip_dl_tx_batch, and the single-subframe drop-in's pbch.c / pss.c / sss.c, which remain
  * the reference's. */
 int srslte_hip_dl_ctrl_tx_put_bcast(srslte_hip_dl_ctrl_tx_t* q, uint32_t tti0, uint32_t nof_sf, void* d_grid, void* stream);
@@ -1268,6 +1268,113 @@ int      srslte_hip_srs_pusch_shortened(const srslte_hip_srs_cfg_t* cfg, const s
 int      srslte_hip_srs_pucch_shortened(const srslte_hip_srs_cfg_t* cfg, int ue_configured, int simul_ack, uint32_t format, uint32_t tti);
 int      srslte_hip_srs_gen(const srslte_hip_srs_cfg_t* cfg, const srslte_hip_srs_ue_t* ue, uint32_t sf_idx, void* r);
 int      srslte_hip_srs_check(const srslte_hip_srs_cfg_t* cfg, uint32_t tti0, uint32_t nof_sf, const srslte_hip_srs_ue_t* list, uint32_t nof);
+
+/* ------------------------------------------------------------------ UE synchronisation: PSS / SSS search, CFO estimate and correction, FDD
+ * srslte_hip_sync_find_batch runs, for every item of a batch, what the FIRST srslte_sync_find (lib/src/phy/sync/sync.c:618-839) on a freshly
+ * initialised and reset srslte_sync_t returns, with cfo_i_enable false, decimate 1, detect_frame_type false, frame_type FDD and
+ * sss_channel_equalize false: the moving averages are in their reset state, so the first CFO estimates are the means, M_norm_avg / M_ext_avg
+ * start from 0 and the correlation average starts from zeros. Averaging across calls is the caller's business (the call keeps no state).
+ * Item b is the cf32 samples d_in[b in_stride .. b in_stride + in_stride); the first frame_size of them are the reference's frame.
+ *   CP-based CFO (cfo_cp_enable): srslte_cp_synch (cp.c:61-77) over min(max_offset, fft_size) offsets and cfo_cp_nsymbols symbols of normal
+ *     CP, every seventh one sample longer; cfo_cp = -arg(corr[argmax |corr|]) / 2 pi. The frame is then read rotated by -cfo_cp / fft_size
+ *     cycles per sample (index 0 = the item's first sample) by every later stage; no corrected copy is written. The phase is exact at every
+ *     index (the reference multiplies by a table or a running phasor).
+ *   PSS search: the replica of srslte_pss_init_N_id_2 (offset 0, conjugated, 1 / sqrt(fft_size) / 62). max_offset >= fft_size: the linear
+ *     convolution of the max_offset samples from find_offset on with it, of which max_offset + fft_size - 2 values enter the maximum
+ *     (pss.c:493-506); max_offset < fft_size (tracking): the dot products of pss.c:485-490, max_offset - 1 values, peak_pos = index + fft_size.
+ *     |c|^2, times ema_alpha when 0 < ema_alpha < 1 (the first update of an average that starts from 0). ema_alpha: 0 selects the 0.2 of
+ *     srslte_pss_init, 1 is what ue_sync.c:369,397 set for the find object. First maximum; peak_value is compute_peak_sidelobe (pss.c:412-441)
+ *     and - as the reference passes no output when threshold is 0 - stays 0 then; corr_peak is the averaged |c|^2 at the peak.
+ *   Found: peak_value >= threshold or threshold == 0; else ret = SRSLTE_SYNC_NOFOUND (0) and nothing below runs.
+ *   PSS-based CFO (cfo_pss_enable and peak_pos >= fft_size): on the fft_size samples before find_offset + peak_pos; with pss_filt_enable
+ *     through srslte_pss_filter (the 62 bins around DC of the mirrored, unnormalised transform, transformed back - computed as the product of
+ *     those bins with the transform of the replica's halves, which is the same sum); srslte_pss_cfo_compute on the two halves.
+ *   peak_pos + find_offset >= 2 (fft_size + CP_EXT) (else ret = SRSLTE_SYNC_FOUND_NOSPACE, 2):
+ *     SSS (sss_en): the symbol at sss_idx = find_offset + peak_pos - 2 symbol_sz(cp) + cp_sz(cp) with cp the configured one; sss_idx < 0:
+ *     sss_available = 0. Rotated by -cfo_pss / fft_size when cfo_pss_enable; extract_pair_sss (find_sss.c:65-95), the m0 / m1 search of
+ *     sss_alg, srslte_sss_N_id_1 with sss_threshold, srslte_sss_subframe. item.N_id_1 >= 0: the known-cell branch (sync.c:507-536), the
+ *     ratio of the correlations with the cell's subframe-0 and subframe-5 sequences against 1.2 (taken on the 62 bins; the reference takes
+ *     it in the time domain after srslte_pss_filter, the same sums times fft_size); m0 = m1 = 0 then.
+ *     CP detection (detect_cp): srslte_sync_detect_cp (sync.c:440-495); cp is the configured one otherwise. ret = SRSLTE_SYNC_FOUND (1).
+ *   N_id_1 is -1 (the reference's field holds 1000) and cell_id -1 while no SSS was detected and none was given; sf_idx, sss_corr are 0 then.
+ *   cfo_cp, cfo_pss (the means after this first call; 0 for a stage that did not run) and cfo = cfo_cp + cfo_pss are in subcarriers.
+ * item.N_id_2 = 3 tries the three hypotheses: such an item has three result rows (N_id_2 = 0, 1, 2), every other item one. Rows are in item
+ * order: d_res must hold sum over items of (1 or 3) rows; the CP stage runs once per item. d_res may be device-visible pinned host memory.
+ * A call makes three launches (two without cfo_cp_enable) on the caller's stream and no host synchronisation; calls on one object queued
+ * back to back on one stream are each correct. Kernels use no scratch memory and at most 40 KB of LDS.
+ * srslte_hip_sync_create returns NULL, and srslte_hip_sync_find_batch / srslte_hip_sync_check return SRSLTE_ERROR_INVALID_INPUTS before anything
+ * is queued, for: an fft_size outside 64..2048 or no multiple of 64; tdd or decimate > 1; max_offset < 2; max_items 0 or above 21845 (three rows per item, 65535 rows per launch); frame_size <
+ * max_offset; cp not 0 / 1; sss_alg > 2; a negative threshold or ema_alpha; cfo_cp_enable with cfo_cp_nsymbols 0 or with the CP stage's reach
+ * (min(max_offset, fft_size) - 1 + the symbols' lengths) beyond frame_size; and per call: null pointers, n > max_items, frame_size >
+ * in_stride, N_id_2 > 3, N_id_1 >= 168, find_offset + max_offset > frame_size, and a window whose last possible peak would make the CFO, SSS
+ * or CP stage read past the item: find_offset + max_offset + fft_size - 2 > in_stride, or in the tracking branch find_offset + max_offset +
+ * fft_size > in_stride (the reference reads these samples from a buffer of frame_size; give items fft_size samples of room after the frame
+ * when max_offset = frame_size; the furthest sample actually read is find_offset + max_offset + fft_size - 4, so both bounds
+ * are on the safe side by one and by three samples, the second because the reference's loop forms all max_offset products although max_offset - 1 enter the maximum). Every read stays
+ * inside [0, in_stride) of its own item.
+ * srslte_hip_cfo_correct_batch: out[b stride + i] = in[b stride + i] exp(j 2 pi freq[b] i), i < len (srslte_cfo_correct / srslte_vec_apply_cfo
+ * with freq in cycles per sample); the phase is the fractional part of freq[b] i taken in double, so it is as exact at sample 150 000 as at
+ * sample 0 (the reference's running phasor drifts). d_out == d_in is allowed; freq is a host array read before the call returns.
+ * Not here: TDD positions and frame-type detection, decimation, the integer-CFO stage, SSS equalisation from the PSS channel estimate,
+ * srslte_pss_sic, averages across calls and ue_sync's find / track state machine, neighbour-cell measurement, NB-IoT, and the single-call
+ * drop-in, whose sync directory remains the reference's over srslte_dft_*. */
+typedef struct srslte_hip_sync_s srslte_hip_sync_t;
+typedef struct {
+  uint32_t fft_size;          /* 64..2048, multiple of 64 */
+  uint32_t frame_size;        /* samples of an item that make the reference's frame (srslte_sync_init's frame_size) */
+  uint32_t max_offset;        /* positions the PSS is searched over (srslte_sync_init's max_offset) */
+  uint32_t max_items;         /* items per call */
+  int      cp;                /* srslte_cp_t (0 normal, 1 extended): the CP assumed by the SSS stage, and the result's when detect_cp is 0 */
+  uint8_t  detect_cp, sss_en, cfo_cp_enable, cfo_pss_enable, pss_filt_enable;
+  uint8_t  sss_alg;           /* 0 DIFF, 1 PARTIAL_3, 2 FULL (sync.c:538-548) */
+  uint8_t  tdd, reserved;     /* tdd: refused */
+  uint32_t cfo_cp_nsymbols;   /* srslte_sync_set_cfo_cp_enable's second argument */
+  float    threshold;         /* on the peak-to-sidelobe ratio; 0: always found */
+  float    sss_threshold;     /* srslte_sss_set_threshold */
+  float    ema_alpha;         /* srslte_sync_set_em_alpha; 0: the default 0.2 */
+  uint32_t decimate;          /* 0 or 1; more is refused */
+} srslte_hip_sync_cfg_t;
+typedef struct {
+  uint32_t N_id_2;            /* 0..2, or 3: all three, one result row per hypothesis */
+  uint32_t find_offset;
+  int32_t  N_id_1;            /* >= 0: known cell (srslte_sync_set_N_id_1); < 0: the m0 / m1 search */
+} srslte_hip_sync_item_t;
+typedef struct {              /* one per (item, hypothesis), 16 x 4 bytes */
+  int32_t  ret;               /* srslte_sync_find_ret_t: 1 FOUND, 2 FOUND_NOSPACE, 0 NOFOUND */
+  uint32_t peak_pos;
+  float    peak_value;        /* the peak-to-sidelobe ratio */
+  float    corr_peak;         /* pss.peak_value */
+  float    cfo_cp, cfo_pss, cfo;
+  uint32_t sss_available, sss_detected, m0, m1, sf_idx;
+  int32_t  N_id_1, cell_id;
+  float    sss_corr;
+  int32_t  cp;
+} srslte_hip_sync_res_t;
+typedef struct {              /* srslte_ue_cellsearch_result_t without the frame type */
+  uint32_t cell_id;
+  int      cp;
+  float    peak;              /* mean corr_peak of the frames */
+  float    mode;              /* share of the frames that gave cell_id */
+  float    psr;               /* the last frame's peak_value */
+  float    cfo;               /* the last frame's cfo in Hz (15000 cfo) */
+  uint32_t nof_frames;        /* rows that counted */
+} srslte_hip_cell_search_result_t;
+srslte_hip_sync_t* srslte_hip_sync_create(const srslte_hip_sync_cfg_t* cfg);
+void               srslte_hip_sync_destroy(srslte_hip_sync_t* q);
+/* in_stride in cf32 samples per item; d_res [rows] */
+int srslte_hip_sync_find_batch(srslte_hip_sync_t* q, const void* d_in, size_t in_stride, const srslte_hip_sync_item_t* items, uint32_t n,
+                               srslte_hip_sync_res_t* d_res, void* stream);
+int srslte_hip_cfo_correct_batch(const void* d_in, void* d_out, size_t stride, uint32_t len, uint32_t n, const float* freq, void* stream);
+/* host (no device needed): what create and a call with these items would refuse; and get_cell of ue_cell_search.c:189-250 over the rows of
+ * one N_id_2, one per scanned 5 ms frame in scan order: rows with ret != 1 or cell_id < 0 do not count (:311-332); the mode of the cell ids
+ * (the first on a tie), normal CP if more than half of that id's rows (integer half) say so, the mean corr_peak, the last row's peak_value
+ * and cfo. Returns the number of rows that counted; 0: no cell, *out zeroed. Choosing the N_id_2 with the largest peak is
+ * srslte_ue_cellsearch_scan (:257-280). */
+int srslte_hip_sync_check(const srslte_hip_sync_cfg_t* cfg, size_t in_stride, const srslte_hip_sync_item_t* items, uint32_t n);
+int srslte_hip_cell_search_decide(const srslte_hip_sync_res_t* found, uint32_t nof_found, srslte_hip_cell_search_result_t* out);
+/* TEST AND DIAGNOSTIC ENTRY: the CP stage's correlations of item b of the last call, min(max_offset, fft_size) cf32 values to the host
+ * (synchronises the device) */
+int srslte_hip_sync_cp_corr(srslte_hip_sync_t* q, uint32_t item, void* h_corr);
 
 #ifdef __cplusplus
 }

@@ -142,6 +142,7 @@ def lib():
         _bind_csi(L)
         _bind_channel(L)
         _bind_srs(L)
+        _bind_sync(L)
         _lib = L
     return _lib
 
@@ -2243,3 +2244,138 @@ def _ul_rx_decode_grants_pucch_srs(self, iq, tti0, grants, ctrl, reqs, srs, ues)
 
 
 UlRx.decode_grants_pucch_srs = _ul_rx_decode_grants_pucch_srs
+
+
+# ---------------------------------------------------------------- UE synchronisation (phy_hip.h "UE synchronisation")
+SYNC_FOUND, SYNC_FOUND_NOSPACE, SYNC_NOFOUND = 1, 2, 0
+SSS_DIFF, SSS_PARTIAL_3, SSS_FULL = 0, 1, 2
+
+
+class SyncCfg(C.Structure):
+    """srslte_hip_sync_cfg_t."""
+    _fields_ = [("fft_size", C.c_uint32), ("frame_size", C.c_uint32), ("max_offset", C.c_uint32), ("max_items", C.c_uint32), ("cp", C.c_int),
+                ("detect_cp", C.c_uint8), ("sss_en", C.c_uint8), ("cfo_cp_enable", C.c_uint8), ("cfo_pss_enable", C.c_uint8),
+                ("pss_filt_enable", C.c_uint8), ("sss_alg", C.c_uint8), ("tdd", C.c_uint8), ("reserved", C.c_uint8), ("cfo_cp_nsymbols", C.c_uint32),
+                ("threshold", C.c_float), ("sss_threshold", C.c_float), ("ema_alpha", C.c_float), ("decimate", C.c_uint32)]
+
+
+class SyncItem(C.Structure):
+    """srslte_hip_sync_item_t."""
+    _fields_ = [("N_id_2", C.c_uint32), ("find_offset", C.c_uint32), ("N_id_1", C.c_int32)]
+
+    @classmethod
+    def make(cls, N_id_2, find_offset=0, N_id_1=-1):
+        return cls(N_id_2, find_offset, N_id_1)
+
+
+class SyncRes(C.Structure):
+    """srslte_hip_sync_res_t."""
+    _fields_ = [("ret", C.c_int32), ("peak_pos", C.c_uint32), ("peak_value", C.c_float), ("corr_peak", C.c_float), ("cfo_cp", C.c_float),
+                ("cfo_pss", C.c_float), ("cfo", C.c_float), ("sss_available", C.c_uint32), ("sss_detected", C.c_uint32), ("m0", C.c_uint32),
+                ("m1", C.c_uint32), ("sf_idx", C.c_uint32), ("N_id_1", C.c_int32), ("cell_id", C.c_int32), ("sss_corr", C.c_float), ("cp", C.c_int32)]
+
+
+class CellSearchResult(C.Structure):
+    """srslte_hip_cell_search_result_t."""
+    _fields_ = [("cell_id", C.c_uint32), ("cp", C.c_int), ("peak", C.c_float), ("mode", C.c_float), ("psr", C.c_float), ("cfo", C.c_float),
+                ("nof_frames", C.c_uint32)]
+
+
+def _bind_sync(L):
+    vp, u32 = C.c_void_p, C.c_uint32
+    L.srslte_hip_sync_create.restype = vp
+    L.srslte_hip_sync_create.argtypes = [C.POINTER(SyncCfg)]
+    L.srslte_hip_sync_destroy.argtypes = [vp]
+    L.srslte_hip_sync_find_batch.argtypes = [vp, vp, C.c_size_t, vp, u32, vp, vp]
+    L.srslte_hip_cfo_correct_batch.argtypes = [vp, vp, C.c_size_t, u32, u32, vp, vp]
+    L.srslte_hip_sync_check.argtypes = [C.POINTER(SyncCfg), C.c_size_t, vp, u32]
+    L.srslte_hip_cell_search_decide.argtypes = [vp, u32, C.POINTER(CellSearchResult)]
+    L.srslte_hip_sync_cp_corr.argtypes = [vp, u32, vp]
+    return L
+
+
+def sync_cfg(fft_size, frame_size, max_offset, max_items=1, cp_ext=False, detect_cp=True, sss_en=True, cfo_cp_enable=False, cfo_pss_enable=False,
+             pss_filt_enable=False, sss_alg=SSS_FULL, cfo_cp_nsymbols=3, threshold=0.0, sss_threshold=0.0, ema_alpha=0.0, tdd=False, decimate=0):
+    """The defaults are those of srslte_sync_init (sync.c:64-82) but for the frame type, which is FDD."""
+    return SyncCfg(fft_size, frame_size, max_offset, max_items, 1 if cp_ext else 0, int(bool(detect_cp)), int(bool(sss_en)), int(bool(cfo_cp_enable)),
+                   int(bool(cfo_pss_enable)), int(bool(pss_filt_enable)), sss_alg, int(bool(tdd)), 0, cfo_cp_nsymbols, threshold, sss_threshold,
+                   ema_alpha, decimate)
+
+
+def sync_rows(items):
+    """Result rows of a call: three for an item with N_id_2 = 3, one otherwise."""
+    return sum(3 if it.N_id_2 == 3 else 1 for it in items)
+
+
+def sync_check(cfg, in_stride, items):
+    """What srslte_hip_sync_create and a call with these items would answer, without a device."""
+    arr = (SyncItem * max(1, len(items)))(*items)
+    return _bind_sync(lib()).srslte_hip_sync_check(C.byref(cfg), in_stride, arr, len(items))
+
+
+def cell_search_decide(rows):
+    """srslte_hip_cell_search_decide (host): (number of frames that counted, CellSearchResult)."""
+    arr = (SyncRes * max(1, len(rows)))(*rows)
+    out = CellSearchResult()
+    return _bind_sync(lib()).srslte_hip_cell_search_decide(arr, len(rows), C.byref(out)), out
+
+
+def cfo_correct_device(d_in, d_out, stride, length, n, freq, stream=None):
+    f = np.ascontiguousarray(freq, np.float32)
+    return _bind_sync(lib()).srslte_hip_cfo_correct_batch(d_in, d_out, stride, length, n, f.ctypes.data, stream)
+
+
+def cfo_correct(x, freq, in_place=False):
+    """x [n][len] complex64, freq [n] cycles per sample -> x exp(j 2 pi freq i) from the device."""
+    a = np.ascontiguousarray(x, np.complex64)
+    a = a.reshape(1, -1) if a.ndim == 1 else a
+    din = DevBuf.from_host(a)
+    dout = din if in_place else DevBuf(a.nbytes)
+    _check(cfo_correct_device(din.ptr, dout.ptr, a.shape[1], a.shape[1], a.shape[0], freq), "cfo_correct_batch")
+    sync()
+    return dout.to_host(np.complex64).reshape(a.shape)
+
+
+class Sync:
+    """Batched PSS / SSS synchronisation: the first srslte_sync_find of a reset object per item."""
+
+    def __init__(self, fft_size, frame_size, max_offset, max_items=1, **kw):
+        L = _bind_sync(lib())
+        self.cfg = sync_cfg(fft_size, frame_size, max_offset, max_items=max_items, **kw)
+        self.h = L.srslte_hip_sync_create(C.byref(self.cfg))
+        if not self.h:
+            raise RuntimeError("srslte_hip_sync_create failed")
+
+    def find_device(self, d_in, in_stride, items, d_res, stream=None):
+        arr = (SyncItem * max(1, len(items)))(*items)
+        return lib().srslte_hip_sync_find_batch(self.h, d_in, in_stride, arr, len(items), d_res, stream)
+
+    @staticmethod
+    def read(d_res, rows):
+        out = (SyncRes * max(1, rows))()
+        _check(lib().srslte_hip_memcpy_d2h(C.addressof(out), d_res.ptr, C.sizeof(SyncRes) * max(1, rows)), "memcpy_d2h")
+        return list(out)[:rows]
+
+    def find(self, x, items):
+        """x [n][in_stride] complex64 -> (rc, [SyncRes] in row order or None)."""
+        a = np.ascontiguousarray(x, np.complex64)
+        a = a.reshape(1, -1) if a.ndim == 1 else a
+        rows = sync_rows(items)
+        din, dres = DevBuf.from_host(a), DevBuf(C.sizeof(SyncRes) * max(1, rows))
+        rc = self.find_device(din.ptr, a.shape[1], items, dres.ptr)
+        if rc != SRSLTE_SUCCESS:
+            return rc, None
+        sync()
+        return rc, self.read(dres, rows)
+
+    def cp_corr(self, item):
+        """The CP stage's correlations of an item of the last call (diagnostic)."""
+        M = min(self.cfg.max_offset, self.cfg.fft_size)
+        out = np.zeros(M, np.complex64)
+        _check(lib().srslte_hip_sync_cp_corr(self.h, item, out.ctypes.data), "sync_cp_corr")
+        return out
+
+    def free(self):
+        if self.h:
+            lib().srslte_hip_sync_destroy(self.h)
+            self.h = None

@@ -123,3 +123,16 @@ void srs_first_slot_table(const srslte_hip_srs_cfg_t* c, uint32_t M_sc, uint32_t
 // srs.hip: whether an object was made for a receiver's cell, and the configuration it was made with
 bool                        srs_same_cell(const srslte_hip_srs_t* q, uint32_t nof_prb, uint32_t cell_id, int cp_ext);
 const srslte_hip_srs_cfg_t* srs_cfg(const srslte_hip_srs_t* q);
+// sync_host.cpp: the tables of an fft_size - the conjugated, scaled time-domain PSS replicas [3][N], their half-symbol transforms [3][2][62],
+// the DFT twiddles exp(-j 2 pi k / N), the SSS tables s, z1 [31][31], c [3][2][31] and the N_id_1 table [30][30] -, the frequency of bin j of
+// the 62 around DC, generate_m0m1, and the checks of a configuration alone
+struct SyncTables {
+  std::vector<cf32>    replica, half, tw;
+  std::vector<float>   s, z1, c;
+  std::vector<int32_t> nid1;
+};
+void sync_tables(uint32_t N, SyncTables& t);
+int  sync_bin_freq(int j);
+void sync_m0m1(uint32_t N_id_1, uint32_t* m0, uint32_t* m1);
+bool sync_fft_size_valid(uint32_t N);
+bool sync_cfg_valid(const srslte_hip_sync_cfg_t* c);

@@ -1,0 +1,558 @@
+// PSS / SSS synchronisation for gfx950, FDD (include/srslte_hip/phy_hip.h, "UE synchronisation"): the first srslte_sync_find of a reset
+// srslte_sync_t for a batch of items, and the batched CFO correction.
+//   sync_cp_kernel      one workgroup per item: srslte_cp_synch's correlations, their first maximum, cfo_cp
+//   sync_corr_kernel    grid (tile of 256 outputs, item x hypothesis): the replica and the tile's input samples - rotated by -cfo_cp / N as
+//                       they are loaded - in LDS, a lane per output with consecutive-address LDS reads; writes the averaged |c|^2 and the
+//                       tile's (maximum, first index)
+//   sync_decide_kernel  one workgroup per (item, hypothesis): the peak over the tiles, the lobe ends (a parallel find-first over blocks of 256
+//                       positions) and the side-lobe maxima, the 62-bin direct DFTs of the PSS and SSS symbols, the CFO from the replica's
+//                       halves, the m0 / m1 correlations, the CP metrics, and the result row
+//   cfo_correct_kernel  a lane per sample, the phase reduced in double before sincospif
+// The tables come from sync_host.cpp.
+#include "cf32_dev.hpp"
+#include "common.hpp"
+#include "dev_buf.hpp"
+#include "phy_hip_internal.hpp"
+#include <limits.h>
+#include <math.h>
+#include <vector>
+
+namespace {
+
+constexpr int      SYNC_THREADS = 256;
+constexpr uint32_t SYNC_TILE    = 256;
+constexpr uint32_t NO_INDEX     = 0xffffffffu;
+
+struct SyncRow {
+  uint32_t item, N_id_2, find_offset;
+  int32_t  N_id_1;
+  uint32_t m0, m1, pad[2]; // generate_m0m1 of a known N_id_1
+};
+
+struct SyncParams {
+  uint32_t N, max_offset, nout, ntiles, track; // nout: values that enter the maximum
+  uint32_t cpn, cpe;                           // CP_LEN_NORM(1, N) = CP_LEN_NORM(7, N), CP_LEN_EXT(N)
+  uint32_t cp_nsym;
+  int      cp;
+  uint32_t detect_cp, sss_en, cfo_cp_enable, cfo_pss_enable, pss_filt_enable, sss_alg;
+  float    threshold, sss_threshold, alpha; // alpha: 0 = no scaling
+  size_t   in_stride;
+  const cf32 *   replica, *half, *tw;
+  const float *  s, *z1, *c;
+  const int32_t* nid1;
+  float*         avg;      // [row][nout]
+  float2*        tile_max; // [row][ntiles]: value, index as bits
+  float*         cfo_cp;   // [item]
+  cf32*          cp_corr;  // [item][min(max_offset, N)]
+};
+
+// x exp(j 2 pi f idx): the fractional part of f idx in double, so the phase is as exact at the end of a frame as at its start
+__device__ __forceinline__ cf32 rot(cf32 x, float f, uint32_t idx)
+{
+  double p = (double)f * (double)idx;
+  p -= rint(p);
+  float s, c;
+  sincospif(2.f * (float)p, &s, &c);
+  return cmul(x, make_float2(c, s));
+}
+__device__ __forceinline__ cf32 ld_rot(const cf32* x, uint32_t idx, float f) { return f != 0.f ? rot(x[idx], f, idx) : x[idx]; }
+
+// the first maximum over the workgroup (srslte_vec_max_fi: strict >, so the lowest index among equals); every thread gets the result
+__device__ void block_argmax(float& v, uint32_t& i, float* s_v, uint32_t* s_i)
+{
+  const int tid = threadIdx.x;
+  s_v[tid] = v, s_i[tid] = i;
+  __syncthreads();
+  for (int o = SYNC_THREADS / 2; o > 0; o >>= 1) {
+    if (tid < o) {
+      const float    v2 = s_v[tid + o];
+      const uint32_t i2 = s_i[tid + o];
+      if (v2 > s_v[tid] || (v2 == s_v[tid] && i2 < s_i[tid])) s_v[tid] = v2, s_i[tid] = i2;
+    }
+    __syncthreads();
+  }
+  v = s_v[0], i = s_i[0];
+  __syncthreads();
+}
+__device__ int block_max_int(int v, uint32_t* s_i)
+{
+  const int tid = threadIdx.x;
+  s_i[tid]      = (uint32_t)v;
+  __syncthreads();
+  for (int o = SYNC_THREADS / 2; o > 0; o >>= 1) {
+    if (tid < o && (int)s_i[tid + o] > (int)s_i[tid]) s_i[tid] = s_i[tid + o];
+    __syncthreads();
+  }
+  v = (int)s_i[0];
+  __syncthreads();
+  return v;
+}
+__device__ float block_max_float(float v, float* s_v)
+{
+  const int tid = threadIdx.x;
+  s_v[tid]      = v;
+  __syncthreads();
+  for (int o = SYNC_THREADS / 2; o > 0; o >>= 1) {
+    if (tid < o) s_v[tid] = fmaxf(s_v[tid], s_v[tid + o]);
+    __syncthreads();
+  }
+  v = s_v[0];
+  __syncthreads();
+  return v;
+}
+__device__ float block_sum(float v, float* s_red)
+{
+  v = wave_sum(v);
+  if (threadIdx.x % 64 == 0) s_red[threadIdx.x / 64] = v;
+  __syncthreads();
+  v = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+  __syncthreads();
+  return v;
+}
+
+__global__ __launch_bounds__(SYNC_THREADS) void sync_cp_kernel(SyncParams p, const cf32* __restrict__ in)
+{
+  __shared__ float    s_v[SYNC_THREADS];
+  __shared__ uint32_t s_i[SYNC_THREADS];
+  const uint32_t item = blockIdx.x, M = p.max_offset < p.N ? p.max_offset : p.N;
+  const cf32*    x    = in + (size_t)item * p.in_stride;
+  cf32*          corr = p.cp_corr + (size_t)item * M;
+  const float    ns   = (float)p.cp_nsym;
+  float          best = -INFINITY;
+  uint32_t       bi   = NO_INDEX;
+  for (uint32_t i = threadIdx.x; i < M; i += SYNC_THREADS) {
+    cf32     acc = make_float2(0.f, 0.f);
+    uint32_t off = i;
+    for (uint32_t n = 0; n < p.cp_nsym; n++) {
+      const uint32_t cpl = p.cpn + (n % 7 ? 0u : 1u);
+      cf32           d   = make_float2(0.f, 0.f);
+      for (uint32_t k = 0; k < cpl; k++) d = cadd(d, cmulconj(x[off + k], x[off + p.N + k]));
+      acc.x += d.x / ns, acc.y += d.y / ns;
+      off += p.N + cpl;
+    }
+    corr[i]       = acc;
+    const float v = acc.x * acc.x + acc.y * acc.y;
+    if (v > best) best = v, bi = i;
+  }
+  block_argmax(best, bi, s_v, s_i);
+  if (threadIdx.x == 0) {
+    const cf32 c   = corr[bi == NO_INDEX ? 0u : bi];
+    p.cfo_cp[item] = (float)(-atan2((double)c.y, (double)c.x) / M_PI / 2); // cfo_cp_estimate (sync.c:572-579)
+  }
+}
+
+__global__ __launch_bounds__(SYNC_THREADS) void sync_corr_kernel(SyncParams p, const SyncRow* __restrict__ rows, const cf32* __restrict__ in)
+{
+  extern __shared__ cf32 s_mem[];
+  __shared__ float       s_v[SYNC_THREADS];
+  __shared__ uint32_t    s_i[SYNC_THREADS];
+  cf32*                  s_h = s_mem;       // [N]
+  cf32*                  s_x = s_mem + p.N; // [SYNC_TILE + N - 1]
+  const SyncRow          r   = rows[blockIdx.y];
+  const cf32*            x   = in + (size_t)r.item * p.in_stride;
+  const float            f   = p.cfo_cp_enable ? -p.cfo_cp[r.item] / (float)p.N : 0.f;
+  const uint32_t         N = p.N, m0 = blockIdx.x * SYNC_TILE, tid = threadIdx.x;
+  for (uint32_t k = tid; k < N; k += SYNC_THREADS) s_h[k] = p.replica[(size_t)r.N_id_2 * N + k];
+  if (!p.track) {
+    // s_x[u] = w[m0 - (N - 1) + u], w the window's max_offset samples with zeros on both sides
+    for (uint32_t u = tid; u < SYNC_TILE + N - 1; u += SYNC_THREADS) {
+      const int64_t j = (int64_t)m0 - (int64_t)(N - 1) + u;
+      s_x[u]          = (j >= 0 && j < (int64_t)p.max_offset) ? ld_rot(x, r.find_offset + (uint32_t)j, f) : make_float2(0.f, 0.f);
+    }
+  } else {
+    for (uint32_t u = tid; u < SYNC_TILE + N - 1; u += SYNC_THREADS)
+      s_x[u] = (m0 + u < p.nout + N - 1) ? ld_rot(x, r.find_offset + m0 + u, f) : make_float2(0.f, 0.f);
+  }
+  __syncthreads();
+  const uint32_t m    = m0 + tid;
+  float          best = -INFINITY;
+  uint32_t       bi   = NO_INDEX;
+  if (m < p.nout) {
+    cf32 acc = make_float2(0.f, 0.f);
+    if (!p.track) {
+      const cf32* xe = s_x + tid + N - 1; // conv[m] = sum_k h[k] w[m - k]
+#pragma unroll 4
+      for (uint32_t k = 0; k < N; k++) acc = cadd(acc, cmul(s_h[k], xe[-(int)k]));
+    } else {
+      const cf32* xb = s_x + tid; // sum_k h[k] x[m + k]
+#pragma unroll 4
+      for (uint32_t k = 0; k < N; k++) acc = cadd(acc, cmul(s_h[k], xb[k]));
+    }
+    float v = acc.x * acc.x + acc.y * acc.y;
+    if (p.alpha != 0.f) v *= p.alpha;
+    p.avg[(size_t)blockIdx.y * p.nout + m] = v;
+    best = v, bi = m;
+  }
+  block_argmax(best, bi, s_v, s_i);
+  if (tid == 0) p.tile_max[(size_t)blockIdx.y * p.ntiles + blockIdx.x] = make_float2(best, __uint_as_float(bi));
+}
+
+// the 62 bins around DC of the mirrored, unnormalised forward transform of s_sym[0 .. N) (dft_fftw.c:249-272 with mirror and dc)
+__device__ void dft62(const SyncParams& p, const cf32* s_sym, cf32 (*s_part)[64], cf32* s_bins)
+{
+  const uint32_t tid = threadIdx.x, j = tid & 63u, part = tid >> 6, N = p.N;
+  if (j < 62) {
+    const int      fj   = j < 31 ? (int)j - 31 : (int)j - 30;
+    const uint32_t step = (uint32_t)(fj + (int)N) % N, n0 = part * (N / 4);
+    uint32_t       idx  = (uint32_t)(((uint64_t)step * n0) % N);
+    cf32           acc  = make_float2(0.f, 0.f);
+    for (uint32_t n = n0; n < n0 + N / 4; n++) {
+      acc = cadd(acc, cmul(s_sym[n], p.tw[idx]));
+      idx += step;
+      if (idx >= N) idx -= N;
+    }
+    s_part[part][j] = acc;
+  }
+  __syncthreads();
+  if (tid < 62) s_bins[tid] = cadd(cadd(s_part[0][tid], s_part[1][tid]), cadd(s_part[2][tid], s_part[3][tid]));
+  __syncthreads();
+}
+
+// corr[m], m < 31, of one SSS half against the table (find_sss.c:32-63), and its first maximum
+__device__ uint32_t sss_half(const SyncParams& p, const cf32* y, float* s_corr)
+{
+  const uint32_t m = threadIdx.x;
+  if (m < 31) {
+    const float* s = p.s + m * 31;
+    float        o = 0.f;
+    if (p.sss_alg == 0) { // corr_all_zs over y[i + 1] conj(y[i]) and sd[m][i] = s[m][i + 1] s[m][i]
+      cf32 a = make_float2(0.f, 0.f);
+      for (int i = 0; i < 30; i++) a = cadd(a, cscale(cmulconj(y[i + 1], y[i]), s[i + 1] * s[i]));
+      o = a.x * a.x + a.y * a.y;
+    } else { // corr_all_sz_partial with M = 3 / 1
+      const int M = p.sss_alg == 1 ? 3 : 1, Nm = 31 / M;
+      for (int j = 0; j < M; j++) {
+        cf32 a = make_float2(0.f, 0.f);
+        for (int i = 0; i < Nm; i++) a = cadd(a, cscale(y[j * Nm + i], s[j * Nm + i]));
+        o += a.x * a.x + a.y * a.y;
+      }
+    }
+    s_corr[m] = o;
+  }
+  __syncthreads();
+  float    best = -INFINITY;
+  uint32_t bi   = 0;
+  for (uint32_t i = 0; i < 31; i++)
+    if (s_corr[i] > best) best = s_corr[i], bi = i;
+  return bi;
+}
+
+__global__ __launch_bounds__(SYNC_THREADS) void sync_decide_kernel(SyncParams p, const SyncRow* __restrict__ rows, const cf32* __restrict__ in,
+                                                                  srslte_hip_sync_res_t* __restrict__ res)
+{
+  __shared__ cf32     s_sym[2048];
+  __shared__ cf32     s_part[4][64];
+  __shared__ cf32     s_bins[62];
+  __shared__ cf32     s_y[2][31];
+  __shared__ float    s_corr[31];
+  __shared__ float    s_v[SYNC_THREADS];
+  __shared__ uint32_t s_i[SYNC_THREADS];
+  __shared__ float    s_red[4];
+  __shared__ float    s_scale[2];
+  const SyncRow  r   = rows[blockIdx.x];
+  const cf32*    x   = in + (size_t)r.item * p.in_stride;
+  const float*   A   = p.avg + (size_t)blockIdx.x * p.nout;
+  const uint32_t tid = threadIdx.x, N = p.N, fo = r.find_offset;
+  const int      nout = (int)p.nout, len = nout + 1; // len: conv_output_len of pss.c
+  const float    cfo_cp = p.cfo_cp_enable ? p.cfo_cp[r.item] : 0.f;
+  const float    f_cp   = p.cfo_cp_enable ? -cfo_cp / (float)N : 0.f;
+  auto           Aat    = [&](int i) -> float { return (i >= 0 && i < nout) ? A[i] : 0.f; }; // conv_output_avg is zero where nothing was written
+
+  // the peak: first maximum over the tiles
+  float    pv = -INFINITY;
+  uint32_t pi = NO_INDEX;
+  for (uint32_t t = tid; t < p.ntiles; t += SYNC_THREADS) {
+    const float2   tm = p.tile_max[(size_t)blockIdx.x * p.ntiles + t];
+    const uint32_t ti = __float_as_uint(tm.y);
+    if (tm.x > pv || (tm.x == pv && ti < pi)) pv = tm.x, pi = ti;
+  }
+  block_argmax(pv, pi, s_v, s_i);
+  const int   peak = pi == NO_INDEX ? 0 : (int)pi;
+  const float cpk  = Aat(peak);
+
+  // compute_peak_sidelobe (pss.c:412-441); the reference is handed no output for it when threshold is 0
+  float peak_value = 0.f;
+  if (p.threshold > 0.f) {
+    int pl_ub = 0, pl_lb = 0;
+    for (int base = peak + 1;; base += SYNC_THREADS) { // the first c >= peak + 1 at which the walk to the right stops
+      const int  c    = base + (int)tid;
+      const bool stop = c >= len || !(Aat(c + 1) <= Aat(c));
+      const int  got  = block_max_int(stop ? -c : INT_MIN, s_i);
+      if (got != INT_MIN) {
+        pl_ub = -got;
+        break;
+      }
+    }
+    if (peak > 2) {
+      for (int base = peak - 1;; base -= SYNC_THREADS) { // the first c <= peak - 1 at which the walk to the left stops
+        const int  c    = base - (int)tid;
+        const bool stop = c <= 1 || !(Aat(c - 1) <= Aat(c));
+        const int  got  = block_max_int(stop ? c : INT_MIN, s_i);
+        if (got != INT_MIN) {
+          pl_lb = got;
+          break;
+        }
+      }
+    }
+    const int dist_right = len - 1 - pl_ub > 0 ? len - 1 - pl_ub : 0;
+    float     right = -INFINITY, left = -INFINITY;
+    for (int i = pl_ub + (int)tid; i < pl_ub + dist_right; i += SYNC_THREADS) right = fmaxf(right, Aat(i));
+    for (int i = (int)tid; i < pl_lb; i += SYNC_THREADS) left = fmaxf(left, Aat(i));
+    right = dist_right > 0 ? block_max_float(right, s_v) : Aat(pl_ub);
+    left  = pl_lb > 0 ? block_max_float(left, s_v) : Aat(0);
+    peak_value = cpk / (right > left ? right : left);
+  }
+  const bool     found    = peak_value >= p.threshold || p.threshold == 0.f;
+  const uint32_t peak_pos = (uint32_t)peak + (p.track ? N : 0u);
+  const uint32_t tot      = peak_pos + fo;
+
+  srslte_hip_sync_res_t o;
+  o.ret = 0, o.peak_pos = peak_pos, o.peak_value = peak_value, o.corr_peak = cpk;
+  o.cfo_cp = cfo_cp, o.cfo_pss = 0.f;
+  o.sss_available = 0, o.sss_detected = 0, o.m0 = 0, o.m1 = 0, o.sf_idx = 0;
+  o.N_id_1 = r.N_id_1 >= 0 ? r.N_id_1 : -1;
+  o.sss_corr = 0.f, o.cp = p.cp;
+
+  if (found) {
+    // PSS-based CFO on the symbol that ends at the peak (sync.c:704-726)
+    if (p.cfo_pss_enable && peak_pos >= N) {
+      const uint32_t b = tot - N;
+      for (uint32_t n = tid; n < N; n += SYNC_THREADS) s_sym[n] = ld_rot(x, b + n, f_cp);
+      __syncthreads();
+      const cf32* h = p.replica + (size_t)r.N_id_2 * N;
+      cf32        y0 = make_float2(0.f, 0.f), y1 = y0;
+      if (p.pss_filt_enable) {
+        dft62(p, s_sym, s_part, s_bins);
+        const cf32* H = p.half + (size_t)r.N_id_2 * 2 * 62;
+        if (tid < 62) y0 = cmul(s_bins[tid], H[tid]), y1 = cmul(s_bins[tid], H[62 + tid]);
+      } else {
+        for (uint32_t n = tid; n < N / 2; n += SYNC_THREADS) y0 = cadd(y0, cmul(h[n], s_sym[n])), y1 = cadd(y1, cmul(h[N / 2 + n], s_sym[N / 2 + n]));
+      }
+      y0.x = block_sum(y0.x, s_red), y0.y = block_sum(y0.y, s_red), y1.x = block_sum(y1.x, s_red), y1.y = block_sum(y1.y, s_red);
+      const cf32 z = cmulconj(y1, y0); // conjf(y0) * y1 (pss.c:619)
+      o.cfo_pss    = (float)(atan2((double)z.y, (double)z.x) / M_PI);
+    }
+    if (tot >= 2 * (N + p.cpe)) {
+      if (p.sss_en) {
+        o.sss_available       = 1;
+        const int     cp_sz   = p.cp == 0 ? (int)p.cpn : (int)p.cpe;
+        const int64_t sss_idx = (int64_t)tot - 2 * ((int64_t)N + cp_sz) + cp_sz;
+        if (sss_idx >= 0) {
+          const float f_pss = p.cfo_pss_enable ? -o.cfo_pss / (float)N : 0.f;
+          __syncthreads();
+          for (uint32_t n = tid; n < N; n += SYNC_THREADS) {
+            cf32 v = ld_rot(x, (uint32_t)sss_idx + n, f_cp);
+            if (f_pss != 0.f) v = rot(v, f_pss, n);
+            s_sym[n] = v;
+          }
+          __syncthreads();
+          dft62(p, s_sym, s_part, s_bins);
+          if (r.N_id_1 >= 0) {
+            // the known cell's subframe-0 and subframe-5 sequences (srslte_sss_generate) against the bins (sync.c:507-536)
+            const uint32_t m0 = r.m0, m1 = r.m1;
+            cf32 a0 = make_float2(0.f, 0.f), a5 = a0;
+            if (tid < 62) {
+              const uint32_t i  = tid / 2;
+              const float    c0 = p.c[(r.N_id_2 * 2) * 31 + i], c1 = p.c[(r.N_id_2 * 2 + 1) * 31 + i];
+              const float    s0 = p.s[m0 * 31 + i], s1 = p.s[m1 * 31 + i];
+              const float    v0 = tid & 1 ? s1 * c1 * p.z1[m0 * 31 + i] : s0 * c0, v5 = tid & 1 ? s0 * c1 * p.z1[m1 * 31 + i] : s1 * c0;
+              a0 = cscale(cconj(s_bins[tid]), v0), a5 = cscale(cconj(s_bins[tid]), v5);
+            }
+            a0.x = block_sum(a0.x, s_red), a0.y = block_sum(a0.y, s_red), a5.x = block_sum(a5.x, s_red), a5.y = block_sum(a5.y, s_red);
+            const float r0 = sqrtf(a0.x * a0.x + a0.y * a0.y), r5 = sqrtf(a5.x * a5.x + a5.y * a5.y);
+            const float ratio = r0 > r5 ? r0 / r5 : r5 / r0;
+            if (ratio > 1.2f) o.sss_detected = 1, o.sf_idx = r0 > r5 ? 0 : 5, o.sss_corr = ratio;
+          } else {
+            // extract_pair_sss (find_sss.c:65-95): even and odd bins, each scaled to unit power and unmasked with c0 / c1
+            if (tid < 2) {
+              float pw = 0.f;
+              for (int i = 0; i < 31; i++) pw += s_bins[2 * i + tid].x * s_bins[2 * i + tid].x + s_bins[2 * i + tid].y * s_bins[2 * i + tid].y;
+              pw /= 31.f;
+              s_scale[tid] = (float)(1.0 / (double)(pw != 0.f ? sqrtf(pw) : 1.f));
+            }
+            __syncthreads();
+            if (tid < 62) {
+              const uint32_t w = tid / 31, i = tid % 31;
+              s_y[w][i]        = cscale(cscale(s_bins[2 * i + w], s_scale[w]), p.c[(r.N_id_2 * 2 + w) * 31 + i]);
+            }
+            __syncthreads();
+            const uint32_t m0  = sss_half(p, s_y[0], s_corr);
+            const float    m0v = s_corr[m0];
+            __syncthreads();
+            if (tid < 31) s_y[1][tid] = cscale(s_y[1][tid], p.z1[m0 * 31 + tid]);
+            __syncthreads();
+            const uint32_t m1  = sss_half(p, s_y[1], s_corr);
+            const float    m1v = s_corr[m1];
+            __syncthreads();
+            const float corr = m0v + m1v;
+            o.m0 = m0, o.m1 = m1;
+            int id = -1; // srslte_sss_N_id_1 (sss.c:136-154)
+            if (corr > p.sss_threshold) {
+              if (m1 > m0) {
+                if (m0 < 30 && m1 - 1 < 30) id = p.nid1[m0 * 30 + m1 - 1];
+              } else if (m1 < 30 && m0 - 1 < 30) {
+                id = p.nid1[m1 * 30 + m0 - 1];
+              }
+            }
+            if (id >= 0) o.sss_detected = 1, o.sf_idx = m1 > m0 ? 0 : 5, o.N_id_1 = id, o.sss_corr = corr;
+          }
+        } else {
+          o.sss_available = 0;
+        }
+      }
+      if (p.detect_cp) { // srslte_sync_detect_cp (sync.c:440-495) from M_norm_avg = M_ext_avg = 0
+        uint32_t ns = tot / (N + p.cpe);
+        if (ns > 3) ns = 3;
+        o.cp = 0;
+        if (ns > 0) {
+          float R[2], M[2];
+#pragma unroll
+          for (int e = 0; e < 2; e++) {
+            const uint32_t cpl = e ? p.cpe : p.cpn, b = tot - ns * (N + cpl);
+            float          rr = 0.f, cc = 0.f;
+            for (uint32_t u = tid; u < ns * cpl; u += SYNC_THREADS) {
+              const uint32_t i0 = b + (u / cpl) * (N + cpl) + u % cpl;
+              const cf32     a = ld_rot(x, i0, f_cp), c = ld_rot(x, i0 + N, f_cp);
+              rr += c.x * a.x + c.y * a.y; // Re(x[N + i] conj(x[i]))
+              cc += a.x * a.x + a.y * a.y;
+            }
+            rr = block_sum(rr, s_red), cc = block_sum(cc, s_red);
+            const float m = cc > 0.f ? rr / cc : 0.f;
+            R[e]          = rr;
+            M[e]          = (float)(0.1 * (double)(m / (float)ns) + (1 - 0.1) * 0.0);
+          }
+          o.cp = M[0] > M[1] ? 0 : M[0] < M[1] ? 1 : R[0] > R[1] ? 0 : 1;
+        }
+      }
+      o.ret = 1;
+    } else {
+      o.ret = 2;
+    }
+  }
+  o.cfo     = o.cfo_cp + o.cfo_pss;
+  o.cell_id = (o.N_id_1 >= 0 && o.N_id_1 < 168) ? 3 * o.N_id_1 + (int32_t)r.N_id_2 : -1;
+  if (tid == 0) res[blockIdx.x] = o;
+}
+
+constexpr uint32_t CFO_ITEMS = 64; // frequencies a launch carries in its arguments
+struct CfoFreqs {
+  float f[CFO_ITEMS];
+};
+
+__global__ __launch_bounds__(256) void cfo_correct_kernel(const cf32* in, cf32* out, size_t stride, uint32_t len, CfoFreqs fr)
+{
+  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= len) return;
+  const size_t a = (size_t)blockIdx.y * stride + i;
+  out[a]         = rot(in[a], fr.f[blockIdx.y], i);
+}
+
+} // namespace
+
+struct srslte_hip_sync_s {
+  srslte_hip_sync_cfg_t cfg;
+  SyncParams            p;
+  DescStage             desc;
+  DevBuf<cf32>          replica, half, tw, cp_corr;
+  DevBuf<float>         s, z1, c, avg, cfo_cp;
+  DevBuf<int32_t>       nid1;
+  DevBuf<float2>        tile_max;
+};
+
+extern "C" {
+
+srslte_hip_sync_t* srslte_hip_sync_create(const srslte_hip_sync_cfg_t* cfg)
+{
+  if (!sync_cfg_valid(cfg)) {
+    hip_log("[srslte_hip] sync: invalid configuration (TDD and decimation are not supported; see phy_hip.h for the sizes)\n");
+    return nullptr;
+  }
+  auto* q = new srslte_hip_sync_s();
+  q->cfg  = *cfg;
+  SyncTables t;
+  sync_tables(cfg->fft_size, t);
+  SyncParams&    p    = q->p;
+  const uint32_t N    = cfg->fft_size, rows = 3 * cfg->max_items;
+  p.N = N, p.max_offset = cfg->max_offset, p.track = cfg->max_offset < N ? 1u : 0u;
+  p.nout    = p.track ? cfg->max_offset - 1 : cfg->max_offset + N - 2;
+  p.ntiles  = (p.nout + SYNC_TILE - 1) / SYNC_TILE;
+  p.cpn = (uint32_t)lte_cp_len((int)N, 144), p.cpe = (uint32_t)lte_cp_len((int)N, 512);
+  p.cp_nsym = cfg->cfo_cp_nsymbols, p.cp = cfg->cp;
+  p.detect_cp = cfg->detect_cp, p.sss_en = cfg->sss_en, p.cfo_cp_enable = cfg->cfo_cp_enable, p.cfo_pss_enable = cfg->cfo_pss_enable;
+  p.pss_filt_enable = cfg->pss_filt_enable, p.sss_alg = cfg->sss_alg;
+  p.threshold = cfg->threshold, p.sss_threshold = cfg->sss_threshold;
+  const float alpha = cfg->ema_alpha == 0.f ? 0.2f : cfg->ema_alpha;
+  p.alpha           = (alpha < 1.0f && alpha > 0.0f) ? alpha : 0.f; // pss.c:496-503
+  const size_t M    = cfg->max_offset < N ? cfg->max_offset : N;
+  if (q->replica.upload(t.replica) || q->half.upload(t.half) || q->tw.upload(t.tw) || q->s.upload(t.s) || q->z1.upload(t.z1) || q->c.upload(t.c) ||
+      q->nid1.upload(t.nid1) || q->avg.alloc((size_t)rows * p.nout) || q->tile_max.alloc((size_t)rows * p.ntiles) || q->cfo_cp.alloc(cfg->max_items) ||
+      q->cp_corr.alloc(cfg->max_items * M) || q->desc.init(sizeof(SyncRow) * rows) ||
+      hipMemset(q->cfo_cp.get(), 0, sizeof(float) * cfg->max_items) != hipSuccess ||
+      hipMemset(q->cp_corr.get(), 0, sizeof(cf32) * cfg->max_items * M) != hipSuccess) {
+    hip_log("[srslte_hip] sync: device allocation failed\n");
+    delete q;
+    return nullptr;
+  }
+  p.replica = q->replica, p.half = q->half, p.tw = q->tw, p.s = q->s, p.z1 = q->z1, p.c = q->c, p.nid1 = q->nid1;
+  p.avg = q->avg, p.tile_max = q->tile_max, p.cfo_cp = q->cfo_cp, p.cp_corr = q->cp_corr;
+  return q;
+}
+
+void srslte_hip_sync_destroy(srslte_hip_sync_t* q) { delete q; }
+
+int srslte_hip_sync_find_batch(srslte_hip_sync_t* q, const void* d_in, size_t in_stride, const srslte_hip_sync_item_t* items, uint32_t n,
+                               srslte_hip_sync_res_t* d_res, void* stream)
+{
+  if (!q || (n && (!d_in || !d_res || !items))) return SRSLTE_ERROR_INVALID_INPUTS;
+  if (int r = srslte_hip_sync_check(&q->cfg, in_stride, items, n)) return r;
+  if (n == 0) return SRSLTE_SUCCESS;
+  hipStream_t st = (hipStream_t)stream;
+  SyncRow*    h  = nullptr;
+  if (int r = q->desc.begin(&h)) return r;
+  uint32_t rows = 0;
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t v0 = items[i].N_id_2 == 3 ? 0 : items[i].N_id_2, v1 = items[i].N_id_2 == 3 ? 2 : items[i].N_id_2;
+    uint32_t       m0 = 0, m1 = 0;
+    if (items[i].N_id_1 >= 0) sync_m0m1((uint32_t)items[i].N_id_1, &m0, &m1);
+    for (uint32_t v = v0; v <= v1; v++) h[rows++] = {i, v, items[i].find_offset, items[i].N_id_1 >= 0 ? items[i].N_id_1 : -1, m0, m1, {0u, 0u}};
+  }
+  if (int r = q->desc.commit(sizeof(SyncRow) * rows, st)) return r;
+  SyncParams p = q->p;
+  p.in_stride  = in_stride;
+  if (p.cfo_cp_enable) {
+    hipLaunchKernelGGL(sync_cp_kernel, dim3(n), dim3(SYNC_THREADS), 0, st, p, (const cf32*)d_in);
+    LAUNCH_CHECK();
+  }
+  const size_t lds = sizeof(cf32) * (2 * (size_t)p.N + SYNC_TILE - 1);
+  hipLaunchKernelGGL(sync_corr_kernel, dim3(p.ntiles, rows), dim3(SYNC_THREADS), lds, st, p, q->desc.dev<SyncRow>(), (const cf32*)d_in);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(sync_decide_kernel, dim3(rows), dim3(SYNC_THREADS), 0, st, p, q->desc.dev<SyncRow>(), (const cf32*)d_in, d_res);
+  LAUNCH_CHECK();
+  return SRSLTE_SUCCESS;
+}
+
+int srslte_hip_cfo_correct_batch(const void* d_in, void* d_out, size_t stride, uint32_t len, uint32_t n, const float* freq, void* stream)
+{
+  if ((n && len && (!d_in || !d_out || !freq)) || (n > 1 && stride < len)) return SRSLTE_ERROR_INVALID_INPUTS;
+  if (n == 0 || len == 0) return SRSLTE_SUCCESS;
+  for (uint32_t b = 0; b < n; b += CFO_ITEMS) {
+    const uint32_t nb = n - b < CFO_ITEMS ? n - b : CFO_ITEMS;
+    CfoFreqs       fr;
+    for (uint32_t i = 0; i < CFO_ITEMS; i++) fr.f[i] = i < nb ? freq[b + i] : 0.f;
+    hipLaunchKernelGGL(cfo_correct_kernel, dim3((len + 255) / 256, nb), dim3(256), 0, (hipStream_t)stream, (const cf32*)d_in + (size_t)b * stride,
+                       (cf32*)d_out + (size_t)b * stride, stride, len, fr);
+    LAUNCH_CHECK();
+  }
+  return SRSLTE_SUCCESS;
+}
+
+int srslte_hip_sync_cp_corr(srslte_hip_sync_t* q, uint32_t item, void* h_corr)
+{
+  if (!q || !h_corr || item >= q->cfg.max_items) return SRSLTE_ERROR_INVALID_INPUTS;
+  const size_t M = q->cfg.max_offset < q->cfg.fft_size ? q->cfg.max_offset : q->cfg.fft_size;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(h_corr, q->cp_corr.get() + item * M, sizeof(cf32) * M, hipMemcpyDeviceToHost));
+  return SRSLTE_SUCCESS;
+}
+
+} // extern "C"
