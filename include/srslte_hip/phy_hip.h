@@ -1316,7 +1316,7 @@ int      srslte_hip_srs_check(const srslte_hip_srs_cfg_t* cfg, uint32_t tti0, ui
  * with freq in cycles per sample); the phase is the fractional part of freq[b] i taken in double, so it is as exact at sample 150 000 as at
  * sample 0 (the reference's running phasor drifts). d_out == d_in is allowed; freq is a host array read before the call returns.
  * Not here: TDD positions and frame-type detection, decimation, the integer-CFO stage, SSS equalisation from the PSS channel estimate,
- * srslte_pss_sic, averages across calls and ue_sync's find / track state machine, neighbour-cell measurement, NB-IoT, and the single-call
+ * srslte_pss_sic, averages across calls and ue_sync's find / track state machine, NB-IoT, and the single-call
  * drop-in, whose sync directory remains the reference's over srslte_dft_*. */
 typedef struct srslte_hip_sync_s srslte_hip_sync_t;
 typedef struct {
@@ -1375,6 +1375,79 @@ int srslte_hip_cell_search_decide(const srslte_hip_sync_res_t* found, uint32_t n
 /* TEST AND DIAGNOSTIC ENTRY: the CP stage's correlations of item b of the last call, min(max_offset, fft_size) cf32 values to the host
  * (synchronises the device) */
 int srslte_hip_sync_cp_corr(srslte_hip_sync_t* q, uint32_t item, void* h_corr);
+
+/* ------------------------------------------------------------------ Neighbour-cell measurement: CRS search, RSRP, RSRQ and CFO, FDD, normal CP
+ * srslte_hip_meas_run_batch leaves, per (capture, candidate cell), what srslte_refsignal_dl_sync_run (lib/src/phy/sync/refsignal_dl_sync.c:
+ * 242-301) leaves in a srslte_refsignal_dl_sync_t after srslte_refsignal_dl_sync_set_cell - the job srsue/src/phy/scell/intra_measure.cc:
+ * 160-235 runs once per candidate cell on a capture of intra_freq_meas_len_ms subframes. Capture c is the cf32 samples d_in[c in_stride ..
+ * c in_stride + nof_sf sf_len), sf_len = 15 symbol_sz; L below is sf_len.
+ *   Replicas (set_cell, :84-154; srslte_hip_meas_set_cells): for subframe i = 0..9 of a cell a grid with PSS + SSS in subframes 0 and 5
+ *     (srslte_pss_put_slot / srslte_sss_put_slot) and the CRS of ports 0 AND 1 whatever the cell's port count (:128-139; both ports carry the
+ *     same r_l,ns(m) at their own positions), through the un-normalised OFDM modulator, times 1 / (8 nof_prb) (:145, nof_re of port 0).
+ *   Search (find_peak, :185-240): min(nof_sf - 1, 10) blocks; block b gives c[k] = sum_{m<L} x[b L + k + m] conj(seq0[m]), k < L - what the
+ *     reference's normalised forward and un-normalised backward transforms of 2 L points leave in the first L outputs, a linear correlation
+ *     with no wrap-around. Per block the first maximum of |c|^2, peak = |c[imax]|, rms = sqrt(mean |c|^2); the overall peak is the first block
+ *     whose peak is strictly larger; found when peak > threshold mean(rms).
+ *   Measurement (run :255-291, measure_sf :303-355): from n = peak_index % L and sf_idx = (20 - peak_index / L) % 10, stepping by L while
+ *     n < nof_sf L - L + 1: on the four CRS symbols of port 0 (symbols 0, 4, 7, 11 at the window offsets of :317-327) corr[l] over symbol_sz
+ *     samples against the replica of that subframe index and the symbol's power; rsrp = 4 sum |corr[l]|^2, rssi = nof_prb sum power / 4 x 7.41,
+ *     cfo = the mean of arg(corr[2] conj corr[0]) and arg(corr[3] conj corr[1]) over 2 pi 7.5 x 15000. Averages over the subframes (nof_sf of
+ *     the row: how many were measured; sf_idx: the first one's index); dB figures carry + 30; rsrq = 10 log10(nof_prb) + rsrp - rssi.
+ *   Not found: found = 0, rsrp_lin, rssi_lin, the three dB figures and cfo_Hz are NaN, peak_index = UINT32_MAX, sf_idx = nof_sf = 0;
+ *     peak_value and rms_avg are what the search saw.
+ * Device side (csrc/meas.hip, the row transforms in csrc/fft.hip). 2 L = 30 symbol_sz for every symbol size, so the 2 L-point transforms are
+ * four-step: 30-point column DFTs (a lane per n2 reads 30 rows at stride symbol_sz), the inter-stage twiddle from a 2 L-entry table built in
+ * double on the host, and symbol_sz-point row FFTs through the fixed LDS plans of the OFDM kernels. Spectra stay in [k1][k2] order (k = k1 +
+ * 30 k2): the product is pointwise, so nothing is transposed. The forward transform of a block is computed once and shared by all candidate
+ * cells; per (capture, cell, block) the product with the conjugated filter spectrum rides on the loads of the inverse's row pass; the closing
+ * 30-point pass forms only the L outputs that count and reduces them on the spot to (max |c|^2, first index, sum |c|^2) per workgroup: the
+ * correlation itself is never written to memory.
+ *   srslte_hip_meas_set_cells: copy + memset + 5 launches (fill, OFDM transmit, scale, column pass, row pass); reads the id list before it
+ *     returns and is otherwise asynchronous on the stream. A later run_batch on another stream needs the caller's ordering.
+ *   srslte_hip_meas_run_batch: 7 launches (column pass, row pass, product + inverse row pass, closing column pass + reduction, decide, measure -
+ *     one workgroup per (row, subframe) -, finish) and no host synchronisation; calls queued back to back on one stream are each correct.
+ *   No kernel uses scratch memory or spills. LDS per workgroup: meas_col_inv_kernel at most 2 KB (the reduction), meas_sf_kernel at most 1 KB,
+ *   the row passes and the OFDM transmit kernel (N + N / 16 + 2) x 8 bytes of dynamic LDS, 17 424 at N = 2048; the other kernels none.
+ * Result rows are capture-major: d_res[c n_cells + k]; d_res may be device-visible pinned host memory. Every read stays inside
+ * [0, nof_sf sf_len) of its own capture.
+ * srslte_hip_meas_create returns NULL, and the calls return SRSLTE_ERROR_INVALID_INPUTS before anything is queued (result rows untouched),
+ * for: extended CP (cp_ext != 0; measure_sf uses normal-CP offsets whatever the cell's CP, so there is nothing to be faithful to); nof_prb
+ * outside 6..110 or a symbol_sz srslte_hip_ofdm_create_sz would refuse; max_captures or max_cells 0, max_cells above 504, max_captures
+ * max_cells above 65535, max_sf < 2 or max_sf sf_len beyond 32 bits; a negative threshold; nof_sf < 2 or > max_sf; in_stride < nof_sf sf_len; more captures or cells than the object was made for; a
+ * cell id above 503; null pointers; run_batch before any set_cells. The capture length is given in whole subframes, as intra_measure.cc does;
+ * for other lengths the reference reads past its buffer.
+ * Not here: extended CP, TDD positions, MBSFN; the neighbour-list bookkeeping of intra_measure.cc:195-230; averaging across calls; and the
+ * single-call drop-in, whose refsignal_dl_sync.c stays the reference's over srslte_dft_*. */
+typedef struct srslte_hip_meas_s srslte_hip_meas_t;
+typedef struct {
+  uint32_t nof_prb;
+  uint32_t symbol_sz;         /* 0: srslte_symbol_sz(nof_prb) of the default family */
+  uint32_t max_captures, max_cells;
+  uint32_t max_sf;            /* subframes per capture */
+  float    threshold;         /* on peak / mean(rms); 0: the reference's 5.5 */
+  uint32_t cp_ext;            /* refused when not 0 */
+} srslte_hip_meas_cfg_t;
+typedef struct {              /* one per (capture, cell), 16 x 4 bytes */
+  int32_t  found;
+  uint32_t peak_index;        /* UINT32_MAX when not found */
+  uint32_t sf_idx;            /* subframe index of the first measured subframe */
+  uint32_t nof_sf;            /* subframes measured */
+  float    peak_value, rms_avg;
+  float    rsrp_lin, rssi_lin;
+  float    rsrp_dBfs, rssi_dBfs, rsrq_dB, cfo_Hz;
+  uint32_t cell_id, capture, reserved[2];
+} srslte_hip_meas_res_t;
+srslte_hip_meas_t* srslte_hip_meas_create(const srslte_hip_meas_cfg_t* cfg);
+void               srslte_hip_meas_destroy(srslte_hip_meas_t* q);
+int srslte_hip_meas_set_cells(srslte_hip_meas_t* q, const uint16_t* cell_ids, uint32_t n_cells, void* stream);
+/* in_stride in cf32 samples per capture; d_res [n_captures][n_cells of the last set_cells] */
+int srslte_hip_meas_run_batch(srslte_hip_meas_t* q, const void* d_in, size_t in_stride, uint32_t nof_sf, uint32_t n_captures,
+                              srslte_hip_meas_res_t* d_res, void* stream);
+/* host (no device needed): what create and a call of this shape would refuse */
+int srslte_hip_meas_check(const srslte_hip_meas_cfg_t* cfg, size_t in_stride, uint32_t nof_sf, uint32_t n_captures, uint32_t n_cells);
+/* TEST AND DIAGNOSTIC ENTRY: the time-domain replicas of cell k of the last set_cells, [10][sf_len] cf32, to the host (synchronises the
+ * device) */
+int srslte_hip_meas_replicas(srslte_hip_meas_t* q, uint32_t cell, void* h_seq);
 
 #ifdef __cplusplus
 }

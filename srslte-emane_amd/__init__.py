@@ -143,6 +143,7 @@ def lib():
         _bind_channel(L)
         _bind_srs(L)
         _bind_sync(L)
+        _bind_meas(L)
         _lib = L
     return _lib
 
@@ -2378,4 +2379,92 @@ class Sync:
     def free(self):
         if self.h:
             lib().srslte_hip_sync_destroy(self.h)
+            self.h = None
+
+
+# ---------------------------------------------------------------- neighbour-cell measurement (phy_hip.h "Neighbour-cell measurement")
+class MeasCfg(C.Structure):
+    """srslte_hip_meas_cfg_t."""
+    _fields_ = [("nof_prb", C.c_uint32), ("symbol_sz", C.c_uint32), ("max_captures", C.c_uint32), ("max_cells", C.c_uint32), ("max_sf", C.c_uint32),
+                ("threshold", C.c_float), ("cp_ext", C.c_uint32)]
+
+
+class MeasRes(C.Structure):
+    """srslte_hip_meas_res_t."""
+    _fields_ = [("found", C.c_int32), ("peak_index", C.c_uint32), ("sf_idx", C.c_uint32), ("nof_sf", C.c_uint32), ("peak_value", C.c_float),
+                ("rms_avg", C.c_float), ("rsrp_lin", C.c_float), ("rssi_lin", C.c_float), ("rsrp_dBfs", C.c_float), ("rssi_dBfs", C.c_float),
+                ("rsrq_dB", C.c_float), ("cfo_Hz", C.c_float), ("cell_id", C.c_uint32), ("capture", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+def _bind_meas(L):
+    vp, u32 = C.c_void_p, C.c_uint32
+    L.srslte_hip_meas_create.restype = vp
+    L.srslte_hip_meas_create.argtypes = [C.POINTER(MeasCfg)]
+    L.srslte_hip_meas_destroy.argtypes = [vp]
+    L.srslte_hip_meas_set_cells.argtypes = [vp, vp, u32, vp]
+    L.srslte_hip_meas_run_batch.argtypes = [vp, vp, C.c_size_t, u32, u32, vp, vp]
+    L.srslte_hip_meas_check.argtypes = [C.POINTER(MeasCfg), C.c_size_t, u32, u32, u32]
+    L.srslte_hip_meas_replicas.argtypes = [vp, u32, vp]
+    return L
+
+
+def meas_cfg(nof_prb, max_captures=1, max_cells=1, max_sf=5, symbol_sz=0, threshold=0.0, cp_ext=False):
+    return MeasCfg(nof_prb, symbol_sz, max_captures, max_cells, max_sf, threshold, 1 if cp_ext else 0)
+
+
+def meas_check(cfg, in_stride, nof_sf, n_captures, n_cells):
+    """What srslte_hip_meas_create and a call of this shape would answer, without a device."""
+    return _bind_meas(lib()).srslte_hip_meas_check(C.byref(cfg), in_stride, nof_sf, n_captures, n_cells)
+
+
+class Meas:
+    """Batched neighbour-cell measurement: srslte_refsignal_dl_sync_run per (capture, candidate cell)."""
+
+    def __init__(self, nof_prb, max_captures=1, max_cells=1, max_sf=5, **kw):
+        L = _bind_meas(lib())
+        self.cfg = meas_cfg(nof_prb, max_captures, max_cells, max_sf, **kw)
+        self.h = L.srslte_hip_meas_create(C.byref(self.cfg))
+        if not self.h:
+            raise RuntimeError("srslte_hip_meas_create failed")
+        self.symbol_sz = self.cfg.symbol_sz or symbol_sz(nof_prb)
+        self.sf_len = 15 * self.symbol_sz
+        self.n_cells = 0
+
+    def set_cells(self, cell_ids, stream=None):
+        ids = np.ascontiguousarray(cell_ids, np.uint16)
+        rc = lib().srslte_hip_meas_set_cells(self.h, ids.ctypes.data, ids.size, stream)
+        if rc == SRSLTE_SUCCESS:
+            self.n_cells = ids.size
+        return rc
+
+    def run_device(self, d_in, in_stride, nof_sf, n_captures, d_res, stream=None):
+        return lib().srslte_hip_meas_run_batch(self.h, d_in, in_stride, nof_sf, n_captures, d_res, stream)
+
+    @staticmethod
+    def read(d_res, rows):
+        out = (MeasRes * max(1, rows))()
+        _check(lib().srslte_hip_memcpy_d2h(C.addressof(out), d_res.ptr, C.sizeof(MeasRes) * max(1, rows)), "memcpy_d2h")
+        return list(out)[:rows]
+
+    def run(self, x, nof_sf):
+        """x [n_captures][in_stride] complex64 -> (rc, [MeasRes] capture-major or None)."""
+        a = np.ascontiguousarray(x, np.complex64)
+        a = a.reshape(1, -1) if a.ndim == 1 else a
+        rows = a.shape[0] * self.n_cells
+        din, dres = DevBuf.from_host(a), DevBuf(C.sizeof(MeasRes) * max(1, rows))
+        rc = self.run_device(din.ptr, a.shape[1], nof_sf, a.shape[0], dres.ptr)
+        if rc != SRSLTE_SUCCESS:
+            return rc, None
+        sync()
+        return rc, self.read(dres, rows)
+
+    def replicas(self, cell):
+        """The time-domain replicas [10][sf_len] of cell `cell` of the last set_cells (diagnostic)."""
+        out = np.zeros(10 * self.sf_len, np.complex64)
+        _check(lib().srslte_hip_meas_replicas(self.h, cell, out.ctypes.data), "meas_replicas")
+        return out.reshape(10, self.sf_len)
+
+    def free(self):
+        if self.h:
+            lib().srslte_hip_meas_destroy(self.h)
             self.h = None

@@ -614,6 +614,25 @@ inline void gold(uint32_t c_init, uint32_t len, std::vector<uint8_t>& c) { lte_g
 } // namespace
 
 
+void lte_crs_values(uint32_t cell_id, uint32_t nof_prb, bool cp_is_norm, std::vector<cf32>& pil)
+{
+  const int nref = 2 * (int)nof_prb, MAX_PRB = 110;
+  pil.assign((size_t)10 * 6 * nref, make_float2(0.f, 0.f));
+  std::vector<uint8_t> c;
+  for (uint32_t ns = 0; ns < 20; ns++) {
+    for (uint32_t l = 0; l < 3; l++) { // l = 0, 1: symbols 0 and 4 of the slot (ports 0/1); l = 2: symbol 1 (ports 2/3)
+      const uint32_t lp     = l == 0 ? 0 : (l == 1 ? (cp_is_norm ? 4 : 3) : 1);
+      const uint32_t c_init = 1024 * (7 * (ns + 1) + lp + 1) * (2 * cell_id + 1) + 2 * cell_id + (cp_is_norm ? 1 : 0); // N_cp (refsignal_dl.c:92)
+      gold(c_init, 4 * MAX_PRB, c);
+      cf32* dst = l < 2 ? &pil[((size_t)(ns / 2) * 4 + (ns % 2) * 2 + l) * nref] : &pil[(size_t)10 * 4 * nref + ((size_t)(ns / 2) * 2 + ns % 2) * nref];
+      for (int i = 0; i < nref; i++) {
+        const int mp = i + MAX_PRB - (int)nof_prb;
+        dst[i]       = make_float2((float)((1 - 2 * (float)c[2 * mp]) / sqrt(2.0)), (float)((1 - 2 * (float)c[2 * mp + 1]) / sqrt(2.0)));
+      }
+    }
+  }
+}
+
 struct srslte_hip_chest_dl {
   int       cell_id, nof_prb, nof_ports, nsl; // nsl: symbols per slot (7, extended CP 6)
   cf32*     d_pilots; // [10][4][2*nof_prb] ports 0 and 1, then [10][2][2*nof_prb] ports 2 and 3 (4-port cells)
@@ -633,21 +652,8 @@ extern "C" srslte_hip_chest_dl_t* srslte_hip_chest_dl_create(uint32_t cell_id, u
             nof_prb, nof_ports, cp_is_norm);
     return nullptr;
   }
-  const int            nref = 2 * nof_prb, MAX_PRB = 110;
-  std::vector<cf32>    pil((size_t)10 * 6 * nref);
-  std::vector<uint8_t> c;
-  for (uint32_t ns = 0; ns < 20; ns++) {
-    for (uint32_t l = 0; l < 3; l++) { // l = 0, 1: symbols 0 and 4 of the slot (ports 0/1); l = 2: symbol 1 (ports 2/3)
-      const uint32_t lp     = l == 0 ? 0 : (l == 1 ? (cp_is_norm ? 4 : 3) : 1);
-      const uint32_t c_init = 1024 * (7 * (ns + 1) + lp + 1) * (2 * cell_id + 1) + 2 * cell_id + (cp_is_norm ? 1 : 0); // N_cp (refsignal_dl.c:92)
-      gold(c_init, 4 * MAX_PRB, c);
-      cf32* dst = l < 2 ? &pil[((size_t)(ns / 2) * 4 + (ns % 2) * 2 + l) * nref] : &pil[(size_t)10 * 4 * nref + ((size_t)(ns / 2) * 2 + ns % 2) * nref];
-      for (int i = 0; i < nref; i++) {
-        const int mp = i + MAX_PRB - nof_prb;
-        dst[i]       = make_float2((float)((1 - 2 * (float)c[2 * mp]) / sqrt(2.0)), (float)((1 - 2 * (float)c[2 * mp + 1]) / sqrt(2.0)));
-      }
-    }
-  }
+  std::vector<cf32> pil;
+  lte_crs_values(cell_id, nof_prb, cp_is_norm != 0, pil);
   auto* q     = new srslte_hip_chest_dl();
   q->cell_id  = cell_id;
   q->nof_prb  = nof_prb;

@@ -307,6 +307,32 @@ __global__ FFT_BOUNDS void dft_batch_kernel(const cf32* __restrict__ in, cf32* _
       [&](int n, cf32 v) { dst[n] = make_float2(v.x * scale, v.y * scale); });
 }
 
+// Inverse row pass of a four-step transform of 30 N points (phy_hip_internal.hpp, fft_rows30_mulconj_inverse): grid (k1 < 30, block, ix n_h +
+// ih). The product with the conjugated filter spectrum rides on the first pass's loads, the scale and the conjugated inter-stage twiddle on the
+// last pass's stores: each spectrum value is read once per cell, each intermediate written once, both coalesced.
+template <int R0, int R1, int R2>
+__global__ FFT_BOUNDS void dft_rows30_mulconj_kernel(const cf32* __restrict__ x, const cf32* __restrict__ h, cf32* __restrict__ out, FftFactors f,
+                                                      uint32_t n_h, float scale, const cf32* __restrict__ tw, const cf32* __restrict__ tw2)
+{
+  extern __shared__ __align__(16) unsigned char lds_raw[];
+  const uint32_t k1 = blockIdx.x, b = blockIdx.y, nblk = gridDim.y, ix = blockIdx.z / n_h, ih = blockIdx.z % n_h;
+  const size_t   N   = (size_t)f.N;
+  const cf32*    xs  = x + (((size_t)ix * nblk + b) * 30 + k1) * N;
+  const cf32*    hs  = h + ((size_t)ih * 30 + k1) * N;
+  cf32*          dst = out + (((size_t)blockIdx.z * nblk + b) * 30 + k1) * N;
+  fft_any<R0, R1, R2>(
+      f, tw, 1.0f, reinterpret_cast<cf32*>(lds_raw),
+      [&](int n) {
+        const cf32 a = xs[n], c = hs[n];
+        return make_float2(a.x * c.x + a.y * c.y, a.y * c.x - a.x * c.y); // a conj(c)
+      },
+      [&](int n, cf32 v) {
+        const cf32 w = tw2[(uint32_t)n * k1];
+        v            = make_float2(v.x * scale, v.y * scale);
+        dst[n]       = make_float2(v.x * w.x + v.y * w.y, v.y * w.x - v.x * w.y); // v conj(w)
+      });
+}
+
 // Any other length (a prime factor beyond 5, or N > 2048): the DFT sum itself, one thread per output bin, double accumulation.
 // FFTW plans every N (dft_fftw.c:93-117) and callers outside the hot path rely on it (PRACH: N_zc = 839 / 139, prach.c; the PSS / SSS
 // correlators' conv_fft_cc lengths; utils/test/dft_test.c -N 255): they keep working through the boundary, at O(N^2) cost.
@@ -613,4 +639,19 @@ extern "C" int srslte_hip_dft_precoding_batch(const void* d_in, void* d_out, uin
   }
   const int N = 12 * (int)nof_prb;
   return srslte_hip_dft_batch(d_in, d_out, N, (int)nof_symbols, N, N, forward, 1.0f / sqrtf((float)N), stream);
+}
+
+// ---------------------------------------------------------------- row passes of the 30 N-point four-step transforms (meas.hip)
+int fft_rows30_mulconj_inverse(const cf32* d_x, const cf32* d_h, const cf32* d_tw2, cf32* d_out, int N, uint32_t nblk, uint32_t n_x, uint32_t n_h,
+                               float scale, hipStream_t st)
+{
+  if (!d_x || !d_h || !d_tw2 || !d_out || !fft_is_fixed(N) || nblk == 0 || nblk > 65535 || n_x == 0 || n_h == 0 || (uint64_t)n_x * n_h > 65535)
+    return SRSLTE_ERROR_INVALID_INPUTS;
+  FftFactors  f;
+  const cf32* d_tw;
+  if (int r = fft_get_plan(N, &f, &d_tw)) return r;
+  FFT_DISPATCH(dft_rows30_mulconj_kernel, N, dim3(30, nblk, n_x * n_h), dim3(fft_threads(N)), fft_lds_bytes(f), st, d_x, d_h, d_out, f, n_h, scale,
+               d_tw, d_tw2);
+  LAUNCH_CHECK();
+  return SRSLTE_SUCCESS;
 }

@@ -136,3 +136,20 @@ int  sync_bin_freq(int j);
 void sync_m0m1(uint32_t N_id_1, uint32_t* m0, uint32_t* m1);
 bool sync_fft_size_valid(uint32_t N);
 bool sync_cfg_valid(const srslte_hip_sync_cfg_t* c);
+// sync_host.cpp: the 62 PSS values of srslte_pss_generate (pss.c:348-376) for N_id_2 = v
+void sync_pss_seq(int v, cf32* pss);
+// chest.hip: the CRS values r_l,ns(m) of a cell (refsignal_dl.c:66-116; 36.211 6.10.1.1): [10][4][2 nof_prb] for ports 0 and 1 (symbols 0 and
+// N_symb - 3 of each slot), then [10][2][2 nof_prb] for ports 2 and 3 (symbol 1 of each slot) (host)
+void lte_crs_values(uint32_t cell_id, uint32_t nof_prb, bool cp_is_norm, std::vector<cf32>& pil);
+// fft.hip: the N-point row passes of the four-step transforms of 30 N points (meas.hip) on the plans of the OFDM sizes.
+// Inverse rows with the spectral product on their loads and the inter-stage twiddle on their stores: for x in [n_x][nblk][30][N], h in
+// [n_h][30][N] (both in [k1][k2] order), out[((ix n_h + ih) nblk + b)][k1][n2] = scale conj(tw2[n2 k1]) sum_k2 x[ix][b][k1][k2]
+// conj(h[ih][k1][k2]) exp(+j 2 pi n2 k2 / N); tw2[i] = exp(-j 2 pi i / (30 N)). n_x n_h <= 65535, nblk <= 65535
+int fft_rows30_mulconj_inverse(const cf32* d_x, const cf32* d_h, const cf32* d_tw2, cf32* d_out, int N, uint32_t nblk, uint32_t n_x, uint32_t n_h,
+                               float scale, hipStream_t st);
+// meas_host.cpp: the checks of a measurement configuration alone, its symbol size, the inter-stage twiddles exp(-j 2 pi i / (30 N)), i < 30 N,
+// formed in double, and the SSS values of subframes 0 and 5 of a cell (srslte_sss_generate, gen_sss.c:121-155)
+bool     meas_cfg_valid(const srslte_hip_meas_cfg_t* c);
+uint32_t meas_symbol_sz(const srslte_hip_meas_cfg_t* c);
+void     meas_twiddles(uint32_t N, std::vector<cf32>& tw2);
+void     meas_sss_seq(uint32_t cell_id, float* s0, float* s5);

@@ -18,6 +18,16 @@ bool sync_fft_size_valid(uint32_t N) { return N >= 64 && N <= 2048 && N % 64 == 
 
 int sync_bin_freq(int j) { return j < 31 ? j - 31 : j - 30; } // bin j of the 62 around DC in a mirrored transform that skips DC (dft_fftw.c:249-272)
 
+void sync_pss_seq(int v, cf32* pss)
+{ // srslte_pss_generate (pss.c:348-376): the phase formed in double, rounded to float, then cosf / sinf
+  const float root = v == 0 ? 25.0f : v == 1 ? 29.0f : 34.0f;
+  for (int i = 0; i < 62; i++) {
+    const float fi  = (float)i;
+    float       arg = (float)((float)-1 * M_PI * root * (i < 31 ? fi * (fi + 1.0) : (fi + 2.0) * (fi + 1.0)) / 63.0);
+    pss[i]          = make_float2(cosf(arg), sinf(arg));
+  }
+}
+
 void sync_tables(uint32_t N, SyncTables& t)
 {
   t.replica.assign(3 * (size_t)N, make_float2(0.f, 0.f));
@@ -28,14 +38,10 @@ void sync_tables(uint32_t N, SyncTables& t)
     t.tw[k]        = make_float2((float)cos(a), (float)sin(a));
   }
   for (int v = 0; v < 3; v++) {
-    // srslte_pss_generate (pss.c:348-376): the phase formed in double, rounded to float, then cosf / sinf
-    const float root = v == 0 ? 25.0f : v == 1 ? 29.0f : 34.0f;
-    double      pr[62], pi[62];
-    for (int i = 0; i < 62; i++) {
-      const float fi  = (float)i;
-      float       arg = (float)((float)-1 * M_PI * root * (i < 31 ? fi * (fi + 1.0) : (fi + 2.0) * (fi + 1.0)) / 63.0);
-      pr[i] = cosf(arg), pi[i] = sinf(arg);
-    }
+    cf32   pss[62];
+    double pr[62], pi[62];
+    sync_pss_seq(v, pss);
+    for (int i = 0; i < 62; i++) pr[i] = pss[i].x, pi[i] = pss[i].y;
     // srslte_pss_init_N_id_2 (pss.c:32-66): the 62 values around DC, inverse transform scaled by 1 / sqrt(N), conjugated, times 1 / 62
     cf32* h = &t.replica[(size_t)v * N];
     for (uint32_t n = 0; n < N; n++) {
