@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Soak of the decoders' own transport-block assembly for ragged batches (tdec_set_tb_ragged: per-slot atomics, the last block to arrive gives the
+"""Soak of the decoders' own transport-block assembly for ragged batches (TdecOpts::tb_Cof: per-slot atomics, the last block to arrive gives the
 verdict; a block kept from an earlier transmission contributes its stored bytes) under concurrency: eight pipeline objects on eight streams decode
 four different mixed-grant batches, each followed by the retransmission of the same data, over and over without a host synchronisation in between;
 after every round each object's transport blocks and verdicts must equal what ONE object produced serially.

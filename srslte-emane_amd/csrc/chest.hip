@@ -11,6 +11,7 @@
 // estimates stay in LDS; HBM traffic is the pilot-bearing symbols in and the 14-symbol estimate out (store-bound,
 // coalesced one RE per thread). chest_fill_res_kernel combines the per-(port, antenna) scalars the way fill_res does.
 #include "common.hpp"
+#include "dev_buf.hpp"
 #include "phy_hip_internal.hpp"
 #include <map>
 #include <math.h>
@@ -634,16 +635,27 @@ void lte_crs_values(uint32_t cell_id, uint32_t nof_prb, bool cp_is_norm, std::ve
 }
 
 struct srslte_hip_chest_dl {
-  int       cell_id, nof_prb, nof_ports, nsl; // nsl: symbols per slot (7, extended CP 6)
-  cf32*     d_pilots; // [10][4][2*nof_prb] ports 0 and 1, then [10][2][2*nof_prb] ports 2 and 3 (4-port cells)
-  ChestRaw* d_raw;    // per (subframe, port, antenna) scalars of multi-antenna / multi-port calls, grown on demand
-  size_t    raw_cap;
-  cf32*     d_mbsfn[256]; // per MBSFN area id: [10][3][6*nof_prb] (set_mbsfn_area_id), or null
-  cf32*     d_pss;        // the cell's 62 PSS values (pss.c:348-376), for the PSS noise algorithm
-  float*    d_noise_state; // [port][antenna] noise estimates kept between calls by the PSS / EMPTY algorithms
-  int       symbol_sz;     // srslte_symbol_sz(nof_prb) as the CFO and timing estimates use it (chest_dl.c:575,:695)
-  int       tdd_s6, tdd_dw; // srslte_hip_chest_dl_set_tdd: -1 = FDD (ChestParams)
+  int              cell_id = 0, nof_prb = 0, nof_ports = 0, nsl = 0; // nsl: symbols per slot (7, extended CP 6)
+  DevBuf<cf32>     d_pilots; // [10][4][2*nof_prb] ports 0 and 1, then [10][2][2*nof_prb] ports 2 and 3 (4-port cells)
+  DevBuf<ChestRaw> d_raw;    // per (subframe, port, antenna) scalars of multi-antenna / multi-port calls, grown on demand
+  DevBuf<cf32>     d_mbsfn[256]; // per MBSFN area id: [10][3][6*nof_prb] (set_mbsfn_area_id), or null
+  DevBuf<cf32>     d_pss;        // the cell's 62 PSS values (pss.c:348-376), for the PSS noise algorithm
+  DevBuf<float>    d_noise_state; // [port][antenna] noise estimates kept between calls by the PSS / EMPTY algorithms
+  int              symbol_sz = 0; // srslte_symbol_sz(nof_prb) as the CFO and timing estimates use it (chest_dl.c:575,:695)
+  int              tdd_s6 = -1, tdd_dw = 0; // srslte_hip_chest_dl_set_tdd: -1 = FDD (ChestParams)
 };
+
+static int chest_dl_alloc_failed()
+{
+  hip_log("[srslte_hip] chest_dl: device allocation failed\n");
+  return SRSLTE_ERROR;
+}
+
+// q->d_raw with room for `need` records; a larger one replaces it, what it held is not kept
+static int chest_dl_raw_reserve(srslte_hip_chest_dl_t* q, size_t need)
+{
+  return need > q->d_raw.size() && q->d_raw.alloc(need) ? chest_dl_alloc_failed() : SRSLTE_SUCCESS;
+}
 
 extern "C" srslte_hip_chest_dl_t* srslte_hip_chest_dl_create(uint32_t cell_id, uint32_t nof_prb, uint32_t nof_ports, int cp_is_norm)
 {
@@ -659,15 +671,7 @@ extern "C" srslte_hip_chest_dl_t* srslte_hip_chest_dl_create(uint32_t cell_id, u
   q->nof_prb  = nof_prb;
   q->nof_ports = (int)nof_ports;
   q->nsl      = cp_is_norm ? 7 : 6;
-  q->tdd_s6   = -1;
-  q->tdd_dw   = 0;
-  q->d_pilots = nullptr;
-  q->d_raw    = nullptr;
-  q->raw_cap  = 0;
-  for (auto& m : q->d_mbsfn) m = nullptr;
-  q->d_pss = nullptr;
-  q->d_noise_state = nullptr;
-  q->symbol_sz     = lte_symbol_sz((int)nof_prb);
+  q->symbol_sz = lte_symbol_sz((int)nof_prb);
   cf32 pss[62];
   {
     const float root_value[] = {25.0, 29.0, 34.0};
@@ -677,12 +681,10 @@ extern "C" srslte_hip_chest_dl_t* srslte_hip_chest_dl_create(uint32_t cell_id, u
       pss[i] = make_float2(cosf(arg), sinf(arg));
     }
   }
-  if (hipMalloc((void**)&q->d_pilots, sizeof(cf32) * pil.size()) != hipSuccess ||
-      hipMalloc((void**)&q->d_pss, sizeof(pss)) != hipSuccess || hipMemcpy(q->d_pss, pss, sizeof(pss), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMalloc((void**)&q->d_noise_state, sizeof(float) * 16) != hipSuccess || hipMemset(q->d_noise_state, 0, sizeof(float) * 16) != hipSuccess ||
-      hipDeviceSynchronize() != hipSuccess /* null-stream memset vs the callers' non-blocking streams */ ||
-      hipMemcpy(q->d_pilots, pil.data(), sizeof(cf32) * pil.size(), hipMemcpyHostToDevice) != hipSuccess) {
-    hip_log("[srslte_hip] chest_dl: device allocation failed\n");
+  if (q->d_pilots.upload(pil) || q->d_pss.upload(pss, 62) || q->d_noise_state.alloc(16) ||
+      hipMemset(q->d_noise_state, 0, sizeof(float) * 16) != hipSuccess ||
+      hipDeviceSynchronize() != hipSuccess /* null-stream memset vs the callers' non-blocking streams */) {
+    chest_dl_alloc_failed();
     delete q;
     return nullptr;
   }
@@ -696,18 +698,7 @@ extern "C" int srslte_hip_chest_dl_set_symbol_sz(srslte_hip_chest_dl_t* q, int s
   return SRSLTE_SUCCESS;
 }
 
-extern "C" void srslte_hip_chest_dl_destroy(srslte_hip_chest_dl_t* q)
-{
-  if (!q) return;
-  if (q->d_pilots) (void)hipFree(q->d_pilots);
-  if (q->d_raw) (void)hipFree(q->d_raw);
-  if (q->d_pss) (void)hipFree(q->d_pss);
-  if (q->d_noise_state) (void)hipFree(q->d_noise_state);
-  for (auto m : q->d_mbsfn) {
-    if (m) (void)hipFree(m);
-  }
-  delete q;
-}
+extern "C" void srslte_hip_chest_dl_destroy(srslte_hip_chest_dl_t* q) { delete q; }
 
 extern "C" int srslte_hip_chest_dl_set_mbsfn_area_id(srslte_hip_chest_dl_t* q, uint16_t mbsfn_area_id)
 { // srslte_chest_dl_set_mbsfn_area_id (chest_dl.c:244-262) with srslte_refsignal_mbsfn_gen_seq (refsignal_dl.c:361-400)
@@ -727,19 +718,12 @@ extern "C" int srslte_hip_chest_dl_set_mbsfn_area_id(srslte_hip_chest_dl_t* q, u
       }
     }
   }
-  cf32* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, sizeof(cf32) * pil.size()));
-  if (hipMemcpy(d, pil.data(), sizeof(cf32) * pil.size(), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(d);
-    return SRSLTE_ERROR;
-  }
-  q->d_mbsfn[mbsfn_area_id] = d;
-  return SRSLTE_SUCCESS;
+  return q->d_mbsfn[mbsfn_area_id].upload(pil) ? chest_dl_alloc_failed() : SRSLTE_SUCCESS; // nothing is held after a failure
 }
 
 extern "C" const void* srslte_hip_chest_dl_mbsfn_pilots(const srslte_hip_chest_dl_t* q, uint16_t mbsfn_area_id)
 {
-  return q && mbsfn_area_id < 256 ? q->d_mbsfn[mbsfn_area_id] : nullptr;
+  return q && mbsfn_area_id < 256 ? q->d_mbsfn[mbsfn_area_id].get() : nullptr;
 }
 
 // fill_res after an MBSFN estimate (chest_dl.c:845-871): only the noise figure is new - get_noise (:747-758), the mean over the antennas of the
@@ -784,14 +768,8 @@ int chest_dl_estimate_mbsfn_rows(srslte_hip_chest_dl_t* q, const srslte_hip_ches
   }
   if (nof_sf == 0) return SRSLTE_SUCCESS;
   const size_t need = ((size_t)nof_sf * nof_rx * q->nof_ports * sizeof(float) + sizeof(ChestRaw) - 1) / sizeof(ChestRaw);
-  if (need > q->raw_cap) {
-    if (q->d_raw) (void)hipFree(q->d_raw);
-    q->d_raw = nullptr;
-    q->raw_cap = 0;
-    HIP_TRY(hipMalloc((void**)&q->d_raw, sizeof(ChestRaw) * need));
-    q->raw_cap = need;
-  }
-  float* d_noise = reinterpret_cast<float*>(q->d_raw);
+  if (int rc = chest_dl_raw_reserve(q, need)) return rc;
+  float* d_noise = reinterpret_cast<float*>(q->d_raw.get());
   if (int rc = chest_dl_mbsfn_impl(q, cfg, tti0, d_grid, d_ce, d_noise, nof_sf, nof_rx, nsl, stream)) return rc;
   hipLaunchKernelGGL(chest_mbsfn_res_kernel, dim3(ceil_div(nof_sf, 64)), dim3(64), 0, (hipStream_t)stream, (const float*)d_noise, (ChestResDev*)d_res,
                      nof_sf, nof_rx, q->nof_ports);
@@ -851,7 +829,7 @@ int chest_dl_set_noise_state(srslte_hip_chest_dl_t* q, const float* noise /* [po
   return hipMemcpy(q->d_noise_state, noise, sizeof(float) * 16, hipMemcpyHostToDevice) == hipSuccess ? SRSLTE_SUCCESS : SRSLTE_ERROR;
 }
 
-extern "C" const void* srslte_hip_chest_dl_pilots(const srslte_hip_chest_dl_t* q) { return q ? q->d_pilots : nullptr; }
+extern "C" const void* srslte_hip_chest_dl_pilots(const srslte_hip_chest_dl_t* q) { return q ? q->d_pilots.get() : nullptr; }
 
 // d_grid: [nof_sf][nof_rx][14][12*prb]; d_ce: [nof_sf][nof_ports][nof_rx][14][12*prb] or NULL (measurements only); d_res: [nof_sf]
 // srslte_hip_chest_res_t or NULL.
@@ -898,13 +876,7 @@ int chest_dl_estimate_batch_rows(srslte_hip_chest_dl_t* q, const srslte_hip_ches
   const int nslice = nof_rx * q->nof_ports;
   ChestRaw* raw = nullptr;
   if (d_res || cfg->noise_alg) {
-    const size_t need = (size_t)nof_sf * nslice;
-    if (need > q->raw_cap) {
-      if (q->d_raw) (void)hipFree(q->d_raw);
-      q->d_raw = nullptr;
-      HIP_TRY(hipMalloc((void**)&q->d_raw, sizeof(ChestRaw) * need));
-      q->raw_cap = need;
-    }
+    if (int rc = chest_dl_raw_reserve(q, (size_t)nof_sf * nslice)) return rc;
     raw = q->d_raw;
   }
   const int nref = 2 * q->nof_prb, nre = 12 * q->nof_prb;
@@ -929,7 +901,7 @@ int chest_dl_estimate_batch_rows(srslte_hip_chest_dl_t* q, const srslte_hip_ches
 // [nof_sf][nof_ports][nof_rx] x {noise, rsrp, rssi, cfo, sync, corr} of the last call with d_res != NULL and more than one (port,
 // antenna) or cfg.rsrp_neighbour (device memory owned by q): what
 // the per-antenna fields of srslte_chest_dl_res_t are made of (chest_dl.c:860-870)
-extern "C" const float* srslte_hip_chest_dl_last_raw(const srslte_hip_chest_dl_t* q) { return q ? (const float*)q->d_raw : nullptr; }
+extern "C" const float* srslte_hip_chest_dl_last_raw(const srslte_hip_chest_dl_t* q) { return q ? (const float*)q->d_raw.get() : nullptr; }
 
 extern "C" int srslte_hip_chest_dl_estimate_batch(srslte_hip_chest_dl_t* q, const srslte_hip_chest_dl_cfg_t* cfg, uint32_t tti0,
                                                   const void* d_grid, void* d_ce, void* d_res, int nof_sf, void* stream)
@@ -1138,10 +1110,10 @@ struct srslte_hip_chest_ul {
   srslte_hip_dmrs_pusch_cfg_t cfg;
   uint32_t n_prs[30][20], f_gh[20], v[20][30];
   // device DMRS of the grant last used: [10][2][12 * L_prb]
-  cf32*    d_r;
-  uint32_t r_L, r_n_dmrs;
+  DevBuf<cf32> d_r;
+  uint32_t     r_L = 0xffffffffu, r_n_dmrs = 0xffffffffu;
   // per-PUSCH grants: every (L_prb, n_dmrs) seen so far keeps its table (srslte_chest_ul_pregen holds all of them at once, refsignal_ul.c:420-457)
-  std::map<std::pair<uint32_t, uint32_t>, cf32*>* tables;
+  std::map<std::pair<uint32_t, uint32_t>, DevBuf<cf32>> tables;
 };
 
 extern "C" srslte_hip_chest_ul_t* srslte_hip_chest_ul_create(uint32_t cell_id, uint32_t nof_prb, int cp_is_norm, const srslte_hip_dmrs_pusch_cfg_t* cfg)
@@ -1155,9 +1127,6 @@ extern "C" srslte_hip_chest_ul_t* srslte_hip_chest_ul_create(uint32_t cell_id, u
   q->nof_prb = nof_prb;
   q->nsl     = cp_is_norm ? 7 : 6;
   q->cfg     = *cfg;
-  q->d_r     = nullptr;
-  q->r_L = q->r_n_dmrs = 0xffffffffu;
-  q->tables = new std::map<std::pair<uint32_t, uint32_t>, cf32*>();
   std::vector<uint8_t> c;
   for (uint32_t ds = 0; ds < 30; ds++) { // generate_n_prs :118-141 and generate_srslte_sequence_hopping_v :149-163 share the seed
     gold(((cell_id / 30) << 5) + (((cell_id % 30) + ds) % 30), 8 * q->nsl * 20, c); // 8 bits per SC-FDMA symbol: the CP sets the stride
@@ -1176,14 +1145,7 @@ extern "C" srslte_hip_chest_ul_t* srslte_hip_chest_ul_create(uint32_t cell_id, u
   return q;
 }
 
-extern "C" void srslte_hip_chest_ul_destroy(srslte_hip_chest_ul_t* q)
-{
-  if (!q) return;
-  if (q->d_r) (void)hipFree(q->d_r);
-  for (auto& kv : *q->tables) (void)hipFree(kv.second);
-  delete q->tables;
-  delete q;
-}
+extern "C" void srslte_hip_chest_ul_destroy(srslte_hip_chest_ul_t* q) { delete q; }
 
 // srslte_refsignal_dmrs_pusch_gen (refsignal_ul.c:459-487): r_host [2][12 * L_prb]. The float / double mix of the reference is kept
 // operation by operation (at 100 PRB the exponent's argument reaches 4e6 rad, where a float resolves 0.5 rad), including the
@@ -1218,19 +1180,25 @@ extern "C" int srslte_hip_refsignal_dmrs_pusch_gen(const srslte_hip_chest_ul_t* 
   return SRSLTE_SUCCESS;
 }
 
+// The DMRS of (L_prb, n_dmrs) for the ten subframes, [10][2][12 * L_prb], on the device; d holds nothing after a failure
+static int chest_ul_dmrs_build(const srslte_hip_chest_ul_t* q, uint32_t L_prb, uint32_t n_dmrs, DevBuf<cf32>& d)
+{
+  std::vector<cf32> r((size_t)10 * 2 * 12 * L_prb);
+  for (uint32_t sf = 0; sf < 10; sf++) {
+    if (int rc = srslte_hip_refsignal_dmrs_pusch_gen(q, L_prb, sf, n_dmrs, r.data() + (size_t)sf * 2 * 12 * L_prb)) return rc;
+  }
+  if (d.upload(r) == SRSLTE_SUCCESS) return SRSLTE_SUCCESS;
+  hip_log("[srslte_hip] chest_ul: device allocation failed\n");
+  return SRSLTE_ERROR;
+}
+
 // Device DMRS of a grant, [10][2][12 * L_prb] (what srslte_chest_ul_pregen keeps for every (n_dmrs, sf, L): built per grant here)
 int chest_ul_dmrs_table(srslte_hip_chest_ul_t* q, uint32_t L_prb, uint32_t n_dmrs, const void** d_r)
 {
   if (q->r_L != L_prb || q->r_n_dmrs != n_dmrs) {
-    std::vector<cf32> r((size_t)10 * 2 * 12 * L_prb);
-    for (uint32_t sf = 0; sf < 10; sf++) {
-      int rc = srslte_hip_refsignal_dmrs_pusch_gen(q, L_prb, sf, n_dmrs, r.data() + (size_t)sf * 2 * 12 * L_prb);
-      if (rc) return rc;
-    }
-    if (q->d_r) (void)hipFree(q->d_r);
-    q->d_r = nullptr;
-    HIP_TRY(hipMalloc((void**)&q->d_r, sizeof(cf32) * r.size()));
-    HIP_TRY(hipMemcpy(q->d_r, r.data(), sizeof(cf32) * r.size(), hipMemcpyHostToDevice));
+    DevBuf<cf32> d; // replaces the grant's before once complete
+    if (int rc = chest_ul_dmrs_build(q, L_prb, n_dmrs, d)) return rc;
+    q->d_r      = std::move(d);
     q->r_L      = L_prb;
     q->r_n_dmrs = n_dmrs;
   }
@@ -1242,16 +1210,11 @@ int chest_ul_dmrs_table(srslte_hip_chest_ul_t* q, uint32_t L_prb, uint32_t n_dmr
 int chest_ul_dmrs_table_cached(srslte_hip_chest_ul_t* q, uint32_t L_prb, uint32_t n_dmrs, const void** d_r)
 {
   if (!q || !d_r || L_prb == 0 || L_prb > q->nof_prb || n_dmrs >= 8) return SRSLTE_ERROR_INVALID_INPUTS;
-  auto it = q->tables->find({L_prb, n_dmrs});
-  if (it == q->tables->end()) {
-    std::vector<cf32> r((size_t)10 * 2 * 12 * L_prb);
-    for (uint32_t sf = 0; sf < 10; sf++) {
-      if (int rc = srslte_hip_refsignal_dmrs_pusch_gen(q, L_prb, sf, n_dmrs, r.data() + (size_t)sf * 2 * 12 * L_prb)) return rc;
-    }
-    cf32* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, sizeof(cf32) * r.size()));
-    HIP_TRY(hipMemcpy(d, r.data(), sizeof(cf32) * r.size(), hipMemcpyHostToDevice));
-    it = q->tables->emplace(std::make_pair(L_prb, n_dmrs), d).first;
+  auto it = q->tables.find({L_prb, n_dmrs});
+  if (it == q->tables.end()) {
+    DevBuf<cf32> d;
+    if (int rc = chest_ul_dmrs_build(q, L_prb, n_dmrs, d)) return rc;
+    it = q->tables.emplace(std::make_pair(L_prb, n_dmrs), std::move(d)).first;
   }
   *d_r = it->second;
   return SRSLTE_SUCCESS;
@@ -1298,7 +1261,7 @@ extern "C" int srslte_hip_chest_ul_estimate_pusch_batch_hop(srslte_hip_chest_ul_
   ChestUlGeom g;
   g.cell_nre = 12 * (int)q->nof_prb; g.L_prb = (int)L_prb; g.n_prb = (int)n_prb; g.n_prb1 = (int)n_prb_slot1; g.tti0 = (int)tti0; g.w = 0.3333f; g.nsl = (int)q->nsl;
   hipLaunchKernelGGL(chest_ul_kernel, dim3(nof_sf), dim3(CH_THREADS), sizeof(cf32) * 2 * 12 * L_prb, (hipStream_t)stream, (const cf32*)d_grid,
-                     (cf32*)d_ce, (ChestUlResDev*)d_res, (const cf32*)q->d_r, g, (const ChestUlItem*)nullptr);
+                     (cf32*)d_ce, (ChestUlResDev*)d_res, (const cf32*)d_r, g, (const ChestUlItem*)nullptr);
   LAUNCH_CHECK();
   return SRSLTE_SUCCESS;
 }

@@ -943,8 +943,9 @@ static int tdec_passes(srslte_tdec_t* h, const void* input, bool api8, uint8_t* 
     for (uint32_t i = 0; i < len; i++) c[i] = ((const int8_t*)input)[i];
     if (!h2d(di, c.data(), len * 2)) return SRSLTE_ERROR;
   }
-  tdec_set_resume(st->h, start);
-  if (tdec_run_batch_w(st->h, di, dec8 ? 1 : 0, len, sb, K, W, 1, passes, 0, 0, (uint8_t*)dout, K / 8, nullptr, nullptr, (hipStream_t)tl_stream()))
+  TdecOpts o;
+  o.start_iter = start;
+  if (tdec_run_batch_w(st->h, di, dec8 ? 1 : 0, len, sb, K, W, 1, passes, 0, 0, (uint8_t*)dout, K / 8, nullptr, nullptr, (hipStream_t)tl_stream(), o))
     return SRSLTE_ERROR;
   return d2h(output, dout, K / 8) ? SRSLTE_SUCCESS : SRSLTE_ERROR;
 }

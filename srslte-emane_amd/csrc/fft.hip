@@ -9,6 +9,7 @@
 // guard strip, fftshift and 1/sqrt(N) are fused into the global load/store indexing, so HBM traffic is exactly
 // the algorithmic bytes: each time sample is read once, each used bin written once, both coalesced.
 #include "common.hpp"
+#include "dev_buf.hpp"
 #include "phy_hip_internal.hpp"
 #include <math.h>
 #include <map>
@@ -436,14 +437,14 @@ int fft_get_plan(int N, FftFactors* f, const cf32** d_tw)
 
 // ---------------------------------------------------------------- OFDM object
 struct srslte_hip_ofdm {
-  OfdmGeom    g;  // regular subframe
-  OfdmGeom    gm; // MBSFN subframe (slot 0: non-MBSFN region + guard + extended-CP symbols), valid when mbsfn
-  bool        mbsfn;
-  const cf32* d_tw;
-  cf32*       d_shift; // [cp_max + N], exp(j 2 pi m f / N), m = -cp_max .. N-1; nullptr when no shift
-  bool        is_rx, normalize;
-  float       freq_shift_f;
-  int         nof_prb;
+  OfdmGeom     g;  // regular subframe
+  OfdmGeom     gm; // MBSFN subframe (slot 0: non-MBSFN region + guard + extended-CP symbols), valid when mbsfn
+  bool         mbsfn = false;
+  const cf32*  d_tw  = nullptr;
+  DevBuf<cf32> d_shift; // [cp_max + N], exp(j 2 pi m f / N), m = -cp_max .. N-1; null when no shift
+  bool         is_rx = false, normalize = false;
+  float        freq_shift_f = 0.f;
+  int          nof_prb      = 0;
 };
 
 extern "C" srslte_hip_ofdm_t* srslte_hip_ofdm_create(int nof_prb, int cp_is_norm, int is_rx)
@@ -475,7 +476,6 @@ extern "C" srslte_hip_ofdm_t* srslte_hip_ofdm_create_sz(int nof_prb, int symbol_
   q->g.norm   = 1.0f;
   q->g.cp_max = 0;
   q->g.sym0   = 0;
-  q->mbsfn    = false;
   int pos = 0;
   for (int s = 0; s < q->g.nsym; s++) {
     const int cp   = cp_is_norm ? lte_cp_len_norm(s % nsym_slot, N) : lte_cp_len_ext(N);
@@ -484,11 +484,8 @@ extern "C" srslte_hip_ofdm_t* srslte_hip_ofdm_create_sz(int nof_prb, int symbol_
     q->g.cp_max     = cp > q->g.cp_max ? cp : q->g.cp_max;
     pos += cp + N;
   }
-  q->d_shift      = nullptr;
-  q->is_rx        = is_rx != 0;
-  q->normalize    = false;
-  q->freq_shift_f = 0.f;
-  q->nof_prb      = nof_prb;
+  q->is_rx   = is_rx != 0;
+  q->nof_prb = nof_prb;
   return q;
 }
 
@@ -546,19 +543,17 @@ extern "C" int srslte_hip_ofdm_set_freq_shift(srslte_hip_ofdm_t* q, float freq_s
     const double ph = 2.0 * M_PI * ((float)(i - q->g.cp_max)) * freq_shift / N;
     tab[i]          = make_float2((float)cos(ph), (float)sin(ph));
   }
-  if (!q->d_shift) HIP_TRY(hipMalloc((void**)&q->d_shift, sizeof(cf32) * len));
+  if (!q->d_shift && q->d_shift.alloc(len)) {
+    hip_log("[srslte_hip] ofdm: device allocation failed\n");
+    return SRSLTE_ERROR;
+  }
   HIP_TRY(hipMemcpy(q->d_shift, tab.data(), sizeof(cf32) * len, hipMemcpyHostToDevice));
   q->g.dc         = 0;
   q->freq_shift_f = freq_shift;
   return SRSLTE_SUCCESS;
 }
 
-extern "C" void srslte_hip_ofdm_destroy(srslte_hip_ofdm_t* q)
-{
-  if (!q) return;
-  if (q->d_shift) (void)hipFree(q->d_shift);
-  delete q;
-}
+extern "C" void srslte_hip_ofdm_destroy(srslte_hip_ofdm_t* q) { delete q; }
 
 static int ofdm_launch(srslte_hip_ofdm_t* q, const void* d_in, void* d_out, int nof_sf, int sym0, int nsym, bool mbsfn_layout, void* stream)
 {
@@ -568,10 +563,10 @@ static int ofdm_launch(srslte_hip_ofdm_t* q, const void* d_in, void* d_out, int 
   dim3 grid(nsym, nof_sf);
   if (q->is_rx) {
     FFT_DISPATCH(ofdm_rx_kernel, g.f.N, grid, dim3(fft_threads(g.f.N)), fft_lds_bytes(g.f), (hipStream_t)stream, (const cf32*)d_in,
-                 (cf32*)d_out, g, q->d_tw, (const cf32*)q->d_shift);
+                 (cf32*)d_out, g, q->d_tw, (const cf32*)q->d_shift.get());
   } else {
     FFT_DISPATCH(ofdm_tx_kernel, g.f.N, grid, dim3(fft_threads(g.f.N)), fft_lds_bytes(g.f), (hipStream_t)stream, (const cf32*)d_in,
-                 (cf32*)d_out, g, q->d_tw, (const cf32*)q->d_shift);
+                 (cf32*)d_out, g, q->d_tw, (const cf32*)q->d_shift.get());
   }
   LAUNCH_CHECK();
   return SRSLTE_SUCCESS;

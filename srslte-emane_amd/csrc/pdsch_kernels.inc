@@ -946,7 +946,7 @@ __global__ __launch_bounds__(RELIST_THREADS) void grants_prep_kernel(const Grant
   scr_gen_body(cw ? gr1 : gr, basis, cw ? scr1 : scr0, words, cell_id, sf, w);
 }
 
-// Same result from the per-block syndrome shares the windowed turbo decoders emit (tdec_set_tb_syndrome): the CRC is linear,
+// Same result from the per-block syndrome shares the windowed turbo decoders emit (TdecOpts::tb_rem): the CRC is linear,
 // so the TB syndrome is the XOR of the C shares; what is left is the payload copy.
 __global__ __launch_bounds__(256) void tb_asm_kernel(const uint8_t* __restrict__ cb_bytes, const uint8_t* __restrict__ cb_ok,
                                                      const uint32_t* __restrict__ cb_syn, uint8_t* __restrict__ tb, uint8_t* __restrict__ tb_ok,

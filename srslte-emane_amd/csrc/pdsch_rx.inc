@@ -379,19 +379,21 @@ extern "C" int srslte_hip_dl_rx_stage(srslte_hip_dl_rx_t* q, int stage, const vo
       if (q->cfg.llr_8bit) return rm_rx_launch<int8_t>(rm_lds_bytes(g, 1), nof_sf * C, q->d_e, q->d_w, tbl, g, st);
       return rm_rx_launch<int16_t>(rm_lds_bytes(g, 2), nof_sf * C, q->d_e, q->d_w, tbl, g, st);
     }
-    case 4:
+    case 4: {
       if (q->cw1) {
         if (int r = srslte_hip_dl_rx_stage(q->cw1, 4, nullptr, tti0, nof_sf, nullptr, 0, nullptr, stream)) return r;
       }
-      tdec_set_tb_syndrome(q->tdec, q->d_tb_rem, C, q->d_cb_syn);
-      tdec_set_skip(q->tdec, q->harq_combine ? q->d_cb_ok : nullptr);
+      TdecOpts o;
+      o.tb_rem = q->d_tb_rem; o.tb_C = C; o.tb_syn = q->d_cb_syn;
+      o.skip   = q->harq_combine ? q->d_cb_ok.get() : nullptr;
       q->direct_tb = nullptr;
       if (dl_rx_tb_direct(q, d_tb, tb_stride, d_tb_ok)) {
-        if (int r = tdec_set_tb_direct(q->tdec, d_tb, tb_stride, q->tg.rlen / 8, d_tb_ok)) return r;
+        o.tb_out = d_tb; o.tb_out_stride = tb_stride; o.tb_rb = q->tg.rlen / 8; o.tb_ok_out = d_tb_ok;
         q->direct_tb = d_tb; q->direct_ok = d_tb_ok; q->direct_stride = tb_stride; q->direct_nof_sf = nof_sf;
       }
       return tdec_run_batch_w(q->tdec, q->d_w, q->cfg.llr_8bit ? 1 : 0, q->in_stride, q->W != 0, K, -1, nof_sf * C, q->cfg.max_iterations,
-                              C > 1 ? 0x1800063u : 0x1864CFBu, C > 1 ? K : q->cfg.tbs + 24, q->d_cb_bytes, K / 8, q->d_cb_iters, q->d_cb_ok, st);
+                              C > 1 ? 0x1800063u : 0x1864CFBu, C > 1 ? K : q->cfg.tbs + 24, q->d_cb_bytes, K / 8, q->d_cb_iters, q->d_cb_ok, st, o);
+    }
     case 5: {
       if (!d_tb || !d_tb_ok || tb_stride < q->cfg.tbs / 8 + 6) return SRSLTE_ERROR_INVALID_INPUTS;
       if (q->cw1) { // rows nof_sf .. 2 nof_sf - 1 of d_tb / d_tb_ok: the second transport block of every subframe

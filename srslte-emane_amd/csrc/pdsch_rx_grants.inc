@@ -68,7 +68,7 @@ static int grants_alloc(GrantsState* g, uint32_t max_re, uint32_t V, uint32_t Cm
 
 // The sections of a descriptor block of a grants mode, host or device copy: GrantDev[V] | SfDesc[V] | CbDesc[V Cmax] | block map[V Cmax] |
 // the caller's extra_desc_bytes | cof[(V + 15) & ~15], one byte per slot: its transport block's code-block count (the decoders' own
-// transport-block assembly, tdec_set_tb_ragged)
+// transport-block assembly, TdecOpts::tb_Cof)
 struct GrantsDesc {
   GrantDev* gr;
   SfDesc*   sf;
@@ -303,8 +303,12 @@ static int grants_back_end(GrantsState* g, const GrantsBuild& bd, const SfDesc* 
     const int lds = (int)((bd.max_seg + 15) & ~15u);
     if (int r = l8 ? rm_rx_launch<int8_t>(lds, bd.ncb, g->d_e, g->d_w, nullptr, rg, st) : rm_rx_launch<int16_t>(lds, bd.ncb, g->d_e, g->d_w, nullptr, rg, st))
       return r;
-    tdec_set_tb_syndrome(g->tdec, nullptr, 1, nullptr);
-    tdec_set_skip(g->tdec, g->d_cb_ok);
+    TdecOpts o;
+    o.skip = g->d_cb_ok;
+    if (direct) {
+      o.tb_out = d_tb; o.tb_out_stride = tb_stride; o.tb_ok_out = d_tb_ok;
+      o.tb_Cof = d_cof; o.tb_width = g->Cmax; o.tb_B = cw1_off; o.tb_rows0 = nof_rows0;
+    }
     // every block length of the batch in one call: one launch per decoder kernel, not one per length (tdec_run_groups)
     std::vector<srslte_hip_tdec_group_t> gv;
     gv.reserve(bd.groups.size());
@@ -312,14 +316,11 @@ static int grants_back_end(GrantsState* g, const GrantsBuild& bd, const SfDesc* 
     int rc = SRSLTE_SUCCESS;
     for (size_t first = 0, off = 0; first < gv.size() && rc == SRSLTE_SUCCESS;) { // more lengths than a launch's table holds: several calls
       const size_t cnt = gv.size() - first < 24 ? gv.size() - first : 24;
-      tdec_set_cb_map(g->tdec, d_map + off);
-      if (direct) rc = tdec_set_tb_ragged(g->tdec, d_tb, tb_stride, d_tb_ok, d_cof, g->Cmax, cw1_off, nof_rows0);
-      if (rc) break;
-      rc = tdec_run_groups(g->tdec, g->d_w, l8 ? 1 : 0, g->stride, gv.data() + first, (uint32_t)cnt, max_iterations, g->d_cb_bytes, 768, g->d_cb_iters, g->d_cb_ok, st);
+      o.cb_map = d_map + off;
+      rc = tdec_run_groups(g->tdec, g->d_w, l8 ? 1 : 0, g->stride, gv.data() + first, (uint32_t)cnt, max_iterations, g->d_cb_bytes, 768, g->d_cb_iters, g->d_cb_ok, st, o);
       for (size_t i = first; i < first + cnt; i++) off += gv[i].nof_cb;
       first += cnt;
     }
-    tdec_set_cb_map(g->tdec, nullptr);
     if (rc) return rc;
   }
   if (direct || !d_tb) return SRSLTE_SUCCESS; // d_tb = null: the caller takes the blocks' bytes and flags and assembles on the host (sch_host.inc)

@@ -48,40 +48,51 @@ int chest_dl_estimate_batch_rows(srslte_hip_chest_dl_t* q, const srslte_hip_ches
 // chest.hip: the MBSFN estimate on grids of 2 nsl symbols per subframe with a result record (noise figure) per subframe, for the PMCH pipeline
 int chest_dl_estimate_mbsfn_rows(srslte_hip_chest_dl_t* q, const srslte_hip_chest_dl_cfg_t* cfg, uint32_t tti0, const void* d_grid, void* d_ce,
                                  int nof_sf, int nof_rx, int nsl, void* d_res, void* stream);
-// tdec.hip: let the windowed decoders also emit each block's share of the transport-block CRC syndrome (nullptr: off).
-// d_rem: [C][K] words, x^(tbs+24-1-position in the TB) mod g for the block's payload bits in the decoder's array order, 0 elsewhere
-void tdec_set_tb_syndrome(srslte_hip_tdec_t* q, const uint32_t* d_rem, uint32_t C, uint32_t* d_syn);
-// tdec.hip: the NEXT run (16-window 16-bit decoder with tdec_set_tb_syndrome, no skip flags, no block map) writes every block's payload bytes
-// straight into its transport block d_tb[cb / C][...] and the last block of a transport block to finish writes d_tb_ok[cb / C] (all block CRCs,
-// the XOR of the TB-CRC shares, a non-zero parity: sch.c:470-488): no assembly kernel behind the decoder. d_tb = nullptr: off
-int tdec_set_tb_direct(srslte_hip_tdec_t* q, uint8_t* d_tb, uint32_t tb_stride, uint32_t payload_bytes_per_block, uint8_t* d_tb_ok);
-// ... for the next tdec_run_groups (a ragged batch of 16-bit blocks, none skipped): transport-block slot v = block slot / width has d_Cof[v] blocks and
-// row v (v < B) or rows0 + v - B of d_tb / d_tb_ok
-int tdec_set_tb_ragged(srslte_hip_tdec_t* q, uint8_t* d_tb, uint32_t tb_stride, uint8_t* d_tb_ok, const uint8_t* d_Cof, uint32_t width, uint32_t B,
-                       uint32_t rows0);
-// The largest block count of a transport block that tdec_set_tb_ragged may be given: block r of C multiplies its CRC24A share by factor C-1-r of
+// tdec.hip: what one run of the decoder does beyond its arguments. A run depends on its own options only: the object keeps none of them.
+struct TdecOpts {
+  // The windowed decoders also emit each block's share of the transport-block CRC syndrome into tb_syn[cb] (tdec_run_batch_w only).
+  // tb_rem: [tb_C][K] words, x^(tbs+24-1-position in the TB) mod g for the block's payload bits in the decoder's array order, 0 elsewhere;
+  // ignored by the unwindowed decoder. tb_C = 0 counts as 1
+  const uint32_t* tb_rem = nullptr;
+  uint32_t        tb_C   = 1;
+  uint32_t*       tb_syn = nullptr;
+  // Blocks with skip[cb] != 0 are left alone: bytes, CRC flag, TB-CRC share stay
+  const uint8_t* skip = nullptr;
+  // The run works on the block slots cb_map[0 .. nof_cb) instead of 0 .. nof_cb-1 (input, output, iteration count, CRC flag, skip flag). For
+  // ragged batches, where the code blocks of one length are scattered over the batch's slots
+  const uint32_t* cb_map = nullptr;
+  // The run continues blocks whose passes 0..start_iter-1 the previous run on this object did (same inputs, same block slots):
+  // srslte_tdec_iteration's one-more-pass without redoing the earlier ones (turbodecoder.c:539-545). tdec_run_batch_w only; a value of
+  // nof_iterations or more counts as 0
+  uint32_t start_iter = 0;
+  // The decoder writes every block's payload bytes (tb_rb per block) straight into its transport block tb_out[cb / tb_C][...] and the last
+  // block of a transport block to finish writes tb_ok_out[cb / tb_C] (all block CRCs, the XOR of the TB-CRC shares, a non-zero parity:
+  // sch.c:470-488): no assembly kernel behind the decoder. tdec_run_batch_w: the 16-window 16-bit decoder or an 8-bit one, with tb_rem,
+  // without skip, cb_map or start_iter, nof_cb a multiple of tb_C - anything else is refused
+  uint8_t* tb_out        = nullptr;
+  uint32_t tb_out_stride = 0, tb_rb = 0;
+  uint8_t* tb_ok_out     = nullptr;
+  // ... tdec_run_groups (a ragged batch of 16-bit blocks; tb_Cof is required there): transport-block slot v = block slot / tb_width has
+  // tb_Cof[v] blocks and row v (v < tb_B) or tb_rows0 + v - tb_B of tb_out / tb_ok_out; tb_rb is not read
+  const uint8_t* tb_Cof   = nullptr;
+  uint32_t       tb_width = 0, tb_B = 0, tb_rows0 = 0;
+};
+// The largest block count of a transport block that TdecOpts::tb_Cof may hold: block r of C multiplies its CRC24A share by factor C-1-r of
 // tdec_tbA_table (tdec.hip), which holds 16 factors. A grants call with a larger transport block has tb_crc_bytes_kernel assemble and judge them.
 constexpr uint32_t TDEC_TB_MAX_C_DIRECT = 16;
-// tdec.hip: blocks with d_skip[cb] != 0 are left alone by the following runs: bytes, CRC flag, TB-CRC share stay (nullptr: off)
-void tdec_set_skip(srslte_hip_tdec_t* q, const uint8_t* d_skip);
-// tdec.hip: the following runs work on the block slots d_map[0 .. nof_cb) instead of 0 .. nof_cb-1 (input, output, iteration count, CRC flag,
-// skip flag; nullptr: off). For ragged batches, where the code blocks of one length are scattered over the batch's slots
-void tdec_set_cb_map(srslte_hip_tdec_t* q, const uint32_t* d_map);
-// tdec.hip: the NEXT run continues blocks whose passes 0..start_iter-1 the previous run on this object did (same inputs, same block
-// slots): srslte_tdec_iteration's one-more-pass without redoing the earlier ones (turbodecoder.c:539-545)
-void tdec_set_resume(srslte_hip_tdec_t* q, uint32_t start_iter);
-// tdec.hip: a ragged batch in one call - groups of equal block length, in the order of the block map set with tdec_set_cb_map - with ONE launch
+// tdec.hip: a ragged batch in one call - groups of equal block length, in the order of the block map opts.cb_map - with ONE launch
 // per decoder kernel the lengths need instead of one per length (back-ends chosen per length as on an AVX2 host; CRC per group for the early stop)
 struct srslte_hip_tdec_group_t {
   uint32_t K, nof_cb, crc_poly, crc_nbits;
 };
 int tdec_run_groups(srslte_hip_tdec_t* q, const void* d_input, int llr8, uint32_t in_stride, const srslte_hip_tdec_group_t* groups, uint32_t nof_groups,
-                    uint32_t nof_iterations, uint8_t* d_output, uint32_t out_stride, uint32_t* d_iters, uint8_t* d_crc_ok, hipStream_t st);
+                    uint32_t nof_iterations, uint8_t* d_output, uint32_t out_stride, uint32_t* d_iters, uint8_t* d_crc_ok, hipStream_t st,
+                    const TdecOpts& opts);
 // tdec.hip: srslte_hip_tdec_run_batch with an optional forced back-end (force_w = -1 auto, 0 generic, 8, 16, 32 with llr8);
 // llr8: d_input is int8 and the 8-bit numerics / fall-backs of turbodecoder.c:438-487 apply
 int tdec_run_batch_w(srslte_hip_tdec_t* q, const void* d_input, int llr8, uint32_t in_stride, int sb_layout, uint32_t K, int force_w,
                      uint32_t nof_cb, uint32_t nof_iterations, uint32_t crc_poly, uint32_t crc_nbits, uint8_t* d_output,
-                     uint32_t out_stride, uint32_t* d_iters, uint8_t* d_crc_ok, hipStream_t st);
+                     uint32_t out_stride, uint32_t* d_iters, uint8_t* d_crc_ok, hipStream_t st, const TdecOpts& opts);
 // pdcch_tx.hip: the checks of srslte_hip_dl_ctrl_tx_put alone (nothing is queued), and the cell an object was made for
 int                                dl_ctrl_tx_check(srslte_hip_dl_ctrl_tx_t* q, uint32_t nof_sf, const srslte_hip_dl_ctrl_tx_in_t* in);
 const srslte_hip_dl_ctrl_tx_cfg_t* dl_ctrl_tx_cfg(const srslte_hip_dl_ctrl_tx_t* q);

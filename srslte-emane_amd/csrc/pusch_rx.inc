@@ -601,10 +601,11 @@ extern "C" int srslte_hip_ul_rx_batch_harq(srslte_hip_ul_rx_t* q, const void* d_
   rg.combine = combine;
   rg.skip    = combine ? q->d_cb_ok : nullptr;
   if (int rc = rm_rx_launch<int16_t>(rm_lds_bytes(rg, 2), nof_sf * C, q->d_g, q->d_w, d_rm_tbl, rg, st)) return rc;
-  tdec_set_tb_syndrome(q->tdec, q->d_tb_rem, C, q->d_cb_syn);
-  tdec_set_skip(q->tdec, combine ? q->d_cb_ok : nullptr);
+  TdecOpts o;
+  o.tb_rem = q->d_tb_rem; o.tb_C = C; o.tb_syn = q->d_cb_syn;
+  o.skip   = combine ? q->d_cb_ok.get() : nullptr;
   r = tdec_run_batch_w(q->tdec, q->d_w, 0, q->in_stride, q->W != 0, K, -1, nof_sf * C, q->cfg.max_iterations, C > 1 ? 0x1800063u : 0x1864CFBu,
-                       C > 1 ? K : q->cfg.tbs + 24, q->d_cb_bytes, K / 8, q->d_cb_iters, q->d_cb_ok, st);
+                       C > 1 ? K : q->cfg.tbs + 24, q->d_cb_bytes, K / 8, q->d_cb_iters, q->d_cb_ok, st, o);
   if (r) return r;
   TbGeom tg    = q->tg;
   tg.tb_stride = (int)tb_stride;

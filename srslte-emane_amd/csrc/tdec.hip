@@ -18,6 +18,7 @@
 //   * 40-step warm-ups from -INF over the neighbouring window, the one-window shift of the start metrics and the
 //     scalar tail trellis are as turbodecoder_win.h:398-456,:529-583,:351-395.
 #include "common.hpp"
+#include "dev_buf.hpp"
 #include "phy_hip_internal.hpp"
 #include <map>
 #include <mutex>
@@ -230,7 +231,7 @@ struct TdecArgs {
   const uint32_t* cb_map;      // optional [nof_cb]: launched block i works on block slot cb_map[i] of in / out / iters / crc_ok / skip (ragged
                                // batches: the blocks of one length are scattered over the batch); the work arrays stay per launched block
   // tdec_pair_kernel, optional: the blocks of transport block cb / tb_C write their payload bytes straight into it (sch.c:360,:401-410) and
-  // the last one to finish gives the verdict of sch.c:470-488 - no assembly kernel behind the decoder (tdec_set_tb_direct)
+  // the last one to finish gives the verdict of sch.c:470-488 - no assembly kernel behind the decoder (TdecOpts::tb_out)
   uint8_t*        tb_out;      // [nof_cb / tb_C][tb_out_stride] or nullptr
   uint32_t        tb_out_stride, tb_rb; // tb_rb: payload bytes per block (K / 8 - 3 with several blocks, K / 8 with one)
   uint8_t*        tb_ok_out;   // [nof_cb / tb_C]
@@ -238,7 +239,7 @@ struct TdecArgs {
   unsigned long long* prof;    // -DTDEC_PROF builds: [nof_cb][10] cycles per phase, else unused
   int            dbg;          // timing experiments only (SRSLTE_HIP_TDEC_DBG): 1 skips the SISO sweeps, 2 the element-wise subtractions,
                                // 4 replaces the interleaver scatters by in-order stores, 8 points every branch-metric load at the zero buffer
-  // tdec_mix_kernel only (behind everything the other kernels read), with tb_out: transport blocks of DIFFERENT sizes (a ragged batch, tdec_set_tb_ragged).
+  // tdec_mix_kernel only (behind everything the other kernels read), with tb_out: transport blocks of DIFFERENT sizes (a ragged batch, TdecOpts::tb_Cof).
   // Block slot cb belongs to transport-block slot cb / tb_C (tb_C = the slots' width), which has tb_Cof[cb / tb_C] blocks; its row of tb_out /
   // tb_ok_out is the slot itself below tb_B, tb_rows0 + slot - tb_B from there on (second codewords). tbA: the group's CRC24A tables (tdec_tbA_table)
   const uint8_t*  tb_Cof;
@@ -295,7 +296,7 @@ __device__ __forceinline__ uint32_t tdec_gf24_mul(uint32_t a, uint32_t b)
 }
 
 #ifdef TDEC_MIX_TU
-// Ragged batches (tdec_set_tb_ragged) with HARQ: a block whose CRC passed in an earlier transmission is not decoded again (sch.c:317-318) - its bytes
+// Ragged batches (TdecOpts::tb_Cof) with HARQ: a block whose CRC passed in an earlier transmission is not decoded again (sch.c:317-318) - its bytes
 // are in its row of a.out since then. It still owes its transport block what a decoded block gives in its last phase: its bytes in the block's
 // place, the CRC24A share of those bytes (table lookups in natural bit order: array position (n % Lw) * 16 + n / Lw) and its arrival. What it
 // does not give is the "a block was decoded in this call" flag (bit 2): a transport block whose blocks had all passed before is not delivered
@@ -1051,7 +1052,7 @@ __device__ __forceinline__ void tdec_win_body(const TdecArgs& a0, const TdecGrou
   };
   const int K8 = K / 8;
   constexpr int EWU = TDEC_EWU; // 16-byte elements in flight per lane in the element-wise phases
-  uint32_t       n_iter = a.start_iter; // > 0: the work arrays hold the state after that many passes (tdec_set_resume)
+  uint32_t       n_iter = a.start_iter; // > 0: the work arrays hold the state after that many passes (TdecOpts::start_iter)
   bool           ok     = false;
   const int16_t* dec    = ext1;
   while (n_iter < a.nof_iter && !ok) {
@@ -1165,7 +1166,7 @@ __device__ __forceinline__ void tdec_win_body(const TdecArgs& a0, const TdecGrou
     for (int i8 = L.lane; i8 < K8; i8 += 64) *reinterpret_cast<v8s*>(perm + 8 * i8) = ld8(dec, i8);
   }
   __syncthreads();
-  // transport-block assembly by the decoder itself (tdec_set_tb_direct, as tdec_pair_kernel's last phase; sch.c:360,:401-410,:470-488): block r of
+  // transport-block assembly by the decoder itself (TdecOpts::tb_out, as tdec_pair_kernel's last phase; sch.c:360,:401-410,:470-488): block r of
   // transport block cb / C owns bytes [r rb, r rb + rb) of it, the last block also leaves its own CRC behind the TB's
   const int tbr = (int)(cb % a.tb_C), tbi = (int)(cb / a.tb_C);
   int       rb = (int)a.tb_rb, tbC = (int)a.tb_C;
@@ -1336,7 +1337,7 @@ __global__ __launch_bounds__(64) TDEC_WAVES_ATTR AR16_NVGPR_ATTR void tdec_ar16_
         lane, K / 8, [&](int i) { return Q2{hi8(in4[i]), app ? hi8(app4[i]) : make_int4(0, 0, 0, 0)}; },
         [&](int i, Q2 t) { X4[i] = app ? make_int4(s_add<1>(t.b.x, t.a.x), s_add<1>(t.b.y, t.a.y), s_add<1>(t.b.z, t.a.z), s_add<1>(t.b.w, t.a.w)) : t.a; });
   };
-  uint32_t n_iter = a.start_iter; // > 0: the work arrays hold the state after that many passes (tdec_set_resume)
+  uint32_t n_iter = a.start_iter; // > 0: the work arrays hold the state after that many passes (TdecOpts::start_iter)
   while (n_iter < a.nof_iter && !(B[0].ok && B[1].ok)) {
     const bool odd = (n_iter & 1) != 0;
     for (int s_ = 0; s_ < 2; s_++) {
@@ -1778,34 +1779,24 @@ struct TabKey {
   bool     operator<(const TabKey& o) const { return memcmp(this, &o, sizeof(*this)) < 0; }
 };
 struct TabDev {
-  uint16_t *inter, *deinter;
-  uint32_t *crc_rem, *crc_rem_i;
+  DevBuf<uint16_t> inter, deinter;
+  DevBuf<uint32_t> crc_rem, crc_rem_i; // absent without a CRC / below 16 windows
 };
 
 } // namespace
 
+// Holds no per-run state: what a run does beyond its arguments is its TdecOpts
 struct srslte_hip_tdec {
-  uint32_t                 max_long_cb, max_nof_cb, Kp;
-  int16_t*                 d_work;
-  pk_t*                    d_beta;
-  int4*                    d_xy;
-  pk_t*                    d_zeros;
-  int16_t*                 d_conv; // widened LLRs of the 8-bit API's 16-bit fall-backs, allocated on first use
-  uint32_t                 beta_stride;
+  uint32_t                 max_long_cb = 0, max_nof_cb = 0, Kp = 0;
+  DevBuf<int16_t>          d_work;
+  DevBuf<pk_t>             d_beta;
+  DevBuf<int4>             d_xy;
+  DevBuf<pk_t>             d_zeros;
+  DevBuf<int16_t>          d_conv;   // widened LLRs of the 8-bit API's 16-bit fall-backs, allocated on first use
+  DevBuf<uint32_t>         d_tb_acc; // the accumulators of the decoders' own transport-block assembly (TdecOpts::tb_out), allocated on first use
+  uint32_t                 beta_stride = 0;
   std::map<TabKey, TabDev> tabs;
-  const uint32_t*          tb_rem = nullptr; // see tdec_set_tb_syndrome
-  uint32_t                 tb_C   = 0;
-  uint32_t*                tb_syn = nullptr;
-  const uint8_t*           skip   = nullptr; // see tdec_set_skip
-  const uint32_t*          cb_map = nullptr; // see tdec_set_cb_map
-  uint32_t                 start_iter = 0;   // see tdec_set_resume; consumed by the next run
-  uint8_t*                 tb_out = nullptr; // see tdec_set_tb_direct; consumed by the next run
-  uint32_t                 tb_out_stride = 0, tb_rb = 0;
-  uint8_t*                 tb_ok_out = nullptr;
-  uint32_t*                d_tb_acc = nullptr;
-  const uint8_t*           tb_Cof = nullptr; // tdec_set_tb_ragged; consumed by the next tdec_run_groups
-  uint32_t                 tb_width = 0, tb_B = 0, tb_rows0 = 0;
-  std::map<uint32_t, uint32_t*> tbA_tabs;    // K -> device CRC24A share tables of the ragged mode
+  std::map<uint32_t, DevBuf<uint32_t>> tbA_tabs; // K -> device CRC24A share tables of the ragged mode
   std::mutex               mtx;
 };
 
@@ -1826,6 +1817,12 @@ extern "C" uint32_t srslte_hip_tdec_autoimp_get_subblocks_8bit(uint32_t K)
 
 extern "C" uint32_t srslte_hip_tdec_input_len(uint32_t K, int sb_layout) { return sb_layout ? 3 * (K + 32) + 12 : 3 * K + 12; }
 
+static int tdec_alloc_failed()
+{
+  hip_log("[srslte_hip] tdec: device allocation failed\n");
+  return SRSLTE_ERROR;
+}
+
 extern "C" srslte_hip_tdec_t* srslte_hip_tdec_create(uint32_t max_long_cb, uint32_t max_nof_cb)
 {
   if (max_long_cb < 40 || max_long_cb > 6144 || max_nof_cb == 0) {
@@ -1837,46 +1834,21 @@ extern "C" srslte_hip_tdec_t* srslte_hip_tdec_create(uint32_t max_long_cb, uint3
   q->max_nof_cb   = max_nof_cb;
   q->Kp           = (max_long_cb + 16 + 31) & ~31u;
   q->beta_stride  = (max_long_cb + 8) * 64; // generic: K+4 steps; windowed: K/8+1
-  q->d_work       = nullptr;
-  q->d_beta       = nullptr;
-  q->d_xy         = nullptr;
-  q->d_conv       = nullptr;
-  q->d_zeros      = nullptr;
   // windowed kernels need (K/W+1)*64 dwords per block; the generic one (K+4)*64 per 8 blocks: size for the worst
   const size_t beta_words = (size_t)max_nof_cb * (max_long_cb / 8 + 2) * 64;
   const size_t gen_words  = (size_t)((max_nof_cb + 7) / 8) * (max_long_cb + 8) * 64;
-  if (hipMalloc((void**)&q->d_work, (size_t)max_nof_cb * 7 * q->Kp * sizeof(int16_t)) != hipSuccess ||
-      hipMalloc((void**)&q->d_beta, sizeof(pk_t) * (beta_words > gen_words ? beta_words : gen_words)) != hipSuccess ||
-      hipMalloc((void**)&q->d_xy, sizeof(int4) * (size_t)max_nof_cb * max_long_cb) != hipSuccess ||
-      hipMalloc((void**)&q->d_zeros, sizeof(pk_t) * (size_t)max_long_cb) != hipSuccess ||
+  if (q->d_work.alloc((size_t)max_nof_cb * 7 * q->Kp) || q->d_beta.alloc(beta_words > gen_words ? beta_words : gen_words) ||
+      q->d_xy.alloc((size_t)max_nof_cb * max_long_cb) || q->d_zeros.alloc(max_long_cb) ||
       hipMemset(q->d_zeros, 0, sizeof(pk_t) * (size_t)max_long_cb) != hipSuccess ||
       hipDeviceSynchronize() != hipSuccess /* the memset ran on the null stream; callers launch on non-blocking streams */) {
-    hip_log("[srslte_hip] tdec: device allocation failed\n");
-    if (q->d_work) (void)hipFree(q->d_work);
+    tdec_alloc_failed();
     delete q;
     return nullptr;
   }
   return q;
 }
 
-extern "C" void srslte_hip_tdec_destroy(srslte_hip_tdec_t* q)
-{
-  if (!q) return;
-  for (auto& kv : q->tabs) {
-    (void)hipFree(kv.second.inter);
-    (void)hipFree(kv.second.deinter);
-    if (kv.second.crc_rem) (void)hipFree(kv.second.crc_rem);
-    if (kv.second.crc_rem_i) (void)hipFree(kv.second.crc_rem_i);
-  }
-  (void)hipFree(q->d_work);
-  (void)hipFree(q->d_beta);
-  (void)hipFree(q->d_xy);
-  (void)hipFree(q->d_zeros);
-  if (q->d_tb_acc) (void)hipFree(q->d_tb_acc);
-  for (auto& kv : q->tbA_tabs) (void)hipFree(kv.second);
-  if (q->d_conv) (void)hipFree(q->d_conv);
-  delete q;
-}
+extern "C" void srslte_hip_tdec_destroy(srslte_hip_tdec_t* q) { delete q; }
 
 static int tdec_get_tables(srslte_hip_tdec_t* q, uint32_t K, uint32_t W, uint32_t poly, uint32_t nbits, TdecTables* t)
 {
@@ -1888,11 +1860,8 @@ static int tdec_get_tables(srslte_hip_tdec_t* q, uint32_t K, uint32_t W, uint32_
   if (it == q->tabs.end()) {
     std::vector<uint16_t> f, r;
     lte_qpp_tables(K, W, f, r);
-    TabDev d = {nullptr, nullptr, nullptr, nullptr};
-    HIP_TRY(hipMalloc((void**)&d.inter, K * 2));
-    HIP_TRY(hipMalloc((void**)&d.deinter, K * 2));
-    HIP_TRY(hipMemcpy(d.inter, f.data(), K * 2, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d.deinter, r.data(), K * 2, hipMemcpyHostToDevice));
+    TabDev d; // enters the map once complete: a failure on the way frees what it got
+    if (d.inter.upload(f) || d.deinter.upload(r)) return tdec_alloc_failed();
     if (poly) {
       // rem[j] = x^(nbits-1-j) mod g (24-bit CRC, crc.c:33-47 polynomial convention with the x^24 term included)
       std::vector<uint32_t> nat(K, 0), pos(K, 0);
@@ -1903,46 +1872,19 @@ static int tdec_get_tables(srslte_hip_tdec_t* q, uint32_t K, uint32_t W, uint32_
         if (v & 0x1000000) v ^= poly;
       }
       for (uint32_t n = 0; n < K; n++) pos[W ? (n % (K / W)) * W + n / (K / W) : n] = nat[n];
-      HIP_TRY(hipMalloc((void**)&d.crc_rem, K * 4));
-      HIP_TRY(hipMemcpy(d.crc_rem, pos.data(), K * 4, hipMemcpyHostToDevice));
+      if (d.crc_rem.upload(pos)) return tdec_alloc_failed();
       if (W == 16) { // sign(app1'[inter[j]]) = sign(ext2[j]): the syndrome of a DEC2 pass is taken before the interleaver (tdec_pair.inc)
         std::vector<uint32_t> posi(K);
         for (uint32_t j = 0; j < K; j++) posi[j] = pos[f[j]];
-        HIP_TRY(hipMalloc((void**)&d.crc_rem_i, K * 4));
-        HIP_TRY(hipMemcpy(d.crc_rem_i, posi.data(), K * 4, hipMemcpyHostToDevice));
+        if (d.crc_rem_i.upload(posi)) return tdec_alloc_failed();
       }
     }
-    it = q->tabs.emplace(key, d).first;
+    it = q->tabs.emplace(key, std::move(d)).first;
   }
   t->inter   = it->second.inter;
   t->deinter = it->second.deinter;
   t->crc_rem = it->second.crc_rem;
   t->crc_rem_i = it->second.crc_rem_i;
-  return SRSLTE_SUCCESS;
-}
-
-void tdec_set_skip(srslte_hip_tdec_t* q, const uint8_t* d_skip) { q->skip = d_skip; }
-void tdec_set_cb_map(srslte_hip_tdec_t* q, const uint32_t* d_map) { q->cb_map = d_map; }
-void tdec_set_resume(srslte_hip_tdec_t* q, uint32_t start_iter) { q->start_iter = start_iter; }
-
-int tdec_set_tb_direct(srslte_hip_tdec_t* q, uint8_t* d_tb, uint32_t tb_stride, uint32_t payload_bytes_per_block, uint8_t* d_tb_ok)
-{ // the NEXT run (16 windows, 16 bit, with tdec_set_tb_syndrome, without skip flags or a block map) assembles the transport blocks itself
-  if (d_tb && !q->d_tb_acc) {
-    HIP_TRY(hipMalloc((void**)&q->d_tb_acc, sizeof(uint32_t) * 4 * q->max_nof_cb));
-    HIP_TRY(hipMemset(q->d_tb_acc, 0, sizeof(uint32_t) * 4 * q->max_nof_cb));
-    HIP_TRY(hipDeviceSynchronize());
-  }
-  q->tb_out = d_tb; q->tb_out_stride = tb_stride; q->tb_rb = payload_bytes_per_block; q->tb_ok_out = d_tb_ok;
-  return SRSLTE_SUCCESS;
-}
-
-// The same for a RAGGED batch (the next tdec_run_groups, 16-bit LLRs; a skipped block contributes its stored bytes): block slot cb belongs to transport-block slot cb / width,
-// which has d_Cof[cb / width] code blocks; row of d_tb / d_tb_ok: the slot itself below B, rows0 + slot - B from there on.
-int tdec_set_tb_ragged(srslte_hip_tdec_t* q, uint8_t* d_tb, uint32_t tb_stride, uint8_t* d_tb_ok, const uint8_t* d_Cof, uint32_t width, uint32_t B,
-                       uint32_t rows0)
-{
-  if (int r = tdec_set_tb_direct(q, d_tb, tb_stride, 0, d_tb_ok)) return r;
-  q->tb_Cof = d_Cof; q->tb_width = width; q->tb_B = B; q->tb_rows0 = rows0;
   return SRSLTE_SUCCESS;
 }
 
@@ -1982,25 +1924,37 @@ static int tdec_tbA_table(srslte_hip_tdec_t* q, uint32_t K, const uint32_t** d_t
       t[2 * (size_t)K + j] = f;
       f = mul(f, step);
     }
-    uint32_t* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, sizeof(uint32_t) * t.size()));
-    HIP_TRY(hipMemcpy(d, t.data(), sizeof(uint32_t) * t.size(), hipMemcpyHostToDevice));
-    it = q->tbA_tabs.emplace(K, d).first;
+    DevBuf<uint32_t> d;
+    if (d.upload(t)) return tdec_alloc_failed();
+    it = q->tbA_tabs.emplace(K, std::move(d)).first;
   }
   *d_tab = it->second;
   return SRSLTE_SUCCESS;
 }
 
-void tdec_set_tb_syndrome(srslte_hip_tdec_t* q, const uint32_t* d_rem, uint32_t C, uint32_t* d_syn)
-{ // windowed decoders only; the caller (pdsch.hip) builds d_rem in the decoder's array order
-  q->tb_rem = d_rem;
-  q->tb_C   = C;
-  q->tb_syn = d_syn;
+// The widened copy of an 8-bit call's LLRs (allocated on first use), for blocks of in_stride elements
+static int tdec_conv_buf(srslte_hip_tdec_t* q, uint32_t in_stride)
+{
+  const size_t per_max = ((size_t)3 * (q->max_long_cb + 32) + 12 + 31) & ~(size_t)31; // the pipelines round their strides up to 32
+  if (!q->d_conv && q->d_conv.alloc((size_t)q->max_nof_cb * per_max)) return tdec_alloc_failed();
+  return in_stride > per_max ? SRSLTE_ERROR_INVALID_INPUTS : SRSLTE_SUCCESS;
+}
+
+// The accumulators of a run with TdecOpts::tb_out (allocated on first use), before anything of that run is launched
+static int tdec_tb_acc_buf(srslte_hip_tdec_t* q)
+{
+  if (q->d_tb_acc) return SRSLTE_SUCCESS;
+  DevBuf<uint32_t> acc; // kept once zeroed
+  if (acc.alloc((size_t)4 * q->max_nof_cb)) return tdec_alloc_failed();
+  HIP_TRY(hipMemset(acc, 0, sizeof(uint32_t) * acc.size()));
+  HIP_TRY(hipDeviceSynchronize()); // the memset ran on the null stream; callers launch on non-blocking streams
+  q->d_tb_acc = std::move(acc);
+  return SRSLTE_SUCCESS;
 }
 
 int tdec_run_batch_w(srslte_hip_tdec_t* q, const void* d_input_any, int llr8, uint32_t in_stride, int sb_layout, uint32_t K, int force_w,
                      uint32_t nof_cb, uint32_t nof_iterations, uint32_t crc_poly, uint32_t crc_nbits, uint8_t* d_output,
-                     uint32_t out_stride, uint32_t* d_iters, uint8_t* d_crc_ok, hipStream_t st)
+                     uint32_t out_stride, uint32_t* d_iters, uint8_t* d_crc_ok, hipStream_t st, const TdecOpts& opts)
 {
   const int16_t* d_input = (const int16_t*)d_input_any;
   if (!q || !d_input || !d_output) return SRSLTE_ERROR_INVALID_INPUTS;
@@ -2025,16 +1979,21 @@ int tdec_run_batch_w(srslte_hip_tdec_t* q, const void* d_input_any, int llr8, ui
   if ((W != 0 && W != 8 && W != 16 && !(llr8 && W == 32)) || (W && (K % W || K / W < WIN_OVERLAP)) || (sb_layout && !W))
     return SRSLTE_ERROR_INVALID_INPUTS;
   const bool ar8 = llr8 && W >= 16; // sse8 / avx8 numerics; below that the 8-bit API widens and runs a 16-bit back-end (turbodecoder.c:465-469)
+  const uint32_t tb_C = opts.tb_C ? opts.tb_C : 1, start_iter = opts.start_iter < nof_iterations ? opts.start_iter : 0;
+  const uint32_t* const tb_rem = W ? opts.tb_rem : nullptr; // windowed decoders only
+  if (opts.tb_out) { // the decoder assembles the transport blocks itself
+    const bool direct = llr8 ? ar8 : (W == 16 && !old_map); // the kernels whose last phase assembles: pair, avx8 (tdec_win_body), sse8
+    if (!direct || !tb_rem || opts.skip || opts.cb_map || nof_cb % tb_C || start_iter) return SRSLTE_ERROR_INVALID_INPUTS;
+    if (int r = tdec_tb_acc_buf(q)) return r;
+  }
   if (llr8 && !ar8) {
     // upstream widens 3K+12 elements whatever the layout (turbodecoder.c:466), which leaves part of an SB-layout buffer stale;
     // the whole buffer is widened here
     // with a block map (ragged batches) the launched blocks sit in arbitrary slots of the buffer: every slot is widened
-    const size_t per_max = ((size_t)3 * (q->max_long_cb + 32) + 12 + 31) & ~(size_t)31; // the pipelines round their strides up to 32
-    const size_t per = in_stride, n = (size_t)(q->cb_map ? q->max_nof_cb : nof_cb) * per;
-    if (!q->d_conv) HIP_TRY(hipMalloc((void**)&q->d_conv, (size_t)q->max_nof_cb * per_max * sizeof(int16_t)));
-    if (per > per_max) return SRSLTE_ERROR_INVALID_INPUTS;
+    const size_t n = (size_t)(opts.cb_map ? q->max_nof_cb : nof_cb) * in_stride;
+    if (int r = tdec_conv_buf(q, in_stride)) return r;
     hipLaunchKernelGGL(widen_kernel, dim3((unsigned)((n + 1023) / 1024 < 4096 ? (n + 1023) / 1024 : 4096)), dim3(256), 0, st, (const int8_t*)d_input_any,
-                       q->d_conv, n);
+                       q->d_conv.get(), n);
     LAUNCH_CHECK();
     d_input = q->d_conv;
   }
@@ -2046,18 +2005,11 @@ int tdec_run_batch_w(srslte_hip_tdec_t* q, const void* d_input_any, int llr8, ui
   a.dbg = getenv("SRSLTE_HIP_TDEC_DBG") ? atoi(getenv("SRSLTE_HIP_TDEC_DBG")) : 0;
 #endif
   a.out = d_output; a.out_stride = out_stride; a.iters = d_iters; a.crc_ok = d_crc_ok;
-  a.tb_rem = W ? q->tb_rem : nullptr; a.tb_C = q->tb_C ? q->tb_C : 1; a.tb_syn = q->tb_syn;
-  a.skip = q->skip;
-  a.cb_map = q->cb_map;
-  a.start_iter = q->start_iter < nof_iterations ? q->start_iter : 0;
-  q->start_iter = 0;
-  a.tb_out = nullptr; a.tb_out_stride = 0; a.tb_rb = 0; a.tb_ok_out = nullptr; a.tb_acc = q->d_tb_acc;
-  if (q->tb_out) { // consumed by this run, whichever kernel it takes
-    const bool direct = llr8 ? ar8 : (W == 16 && !old_map); // the kernels whose last phase assembles: pair, avx8 (tdec_win_body), sse8
-    if (!direct || !a.tb_rem || a.skip || a.cb_map || nof_cb % a.tb_C || a.start_iter) return SRSLTE_ERROR_INVALID_INPUTS;
-    a.tb_out = q->tb_out; a.tb_out_stride = q->tb_out_stride; a.tb_rb = q->tb_rb; a.tb_ok_out = q->tb_ok_out;
-    q->tb_out = nullptr;
-  }
+  a.tb_rem = tb_rem; a.tb_C = tb_C; a.tb_syn = opts.tb_syn;
+  a.skip = opts.skip;
+  a.cb_map = opts.cb_map;
+  a.start_iter = start_iter;
+  a.tb_out = opts.tb_out; a.tb_out_stride = opts.tb_out_stride; a.tb_rb = opts.tb_rb; a.tb_ok_out = opts.tb_ok_out; a.tb_acc = q->d_tb_acc;
   a.prof = nullptr;
 #ifdef TDEC_PROF
   static unsigned long long* d_prof = nullptr;
@@ -2110,20 +2062,20 @@ int tdec_run_batch_w(srslte_hip_tdec_t* q, const void* d_input_any, int llr8, ui
   return SRSLTE_SUCCESS;
 }
 
-// One call for a ragged batch: groups[i] = nof_cb blocks of length K, in the order of the block map (tdec_set_cb_map: group i's slots behind those
+// One call for a ragged batch: groups[i] = nof_cb blocks of length K, in the order of the block map (opts.cb_map: group i's slots behind those
 // of groups 0 .. i-1). ONE launch per decoder kernel the lengths need - the two-blocks-per-wavefront kernel for every K > 800, the 8-window one,
-// the unwindowed one (8-bit LLRs: the 32- and 16-window 8-bit kernels, the rest widened) - instead of one per length. Skip flags as set.
+// the unwindowed one (8-bit LLRs: the 32- and 16-window 8-bit kernels, the rest widened) - instead of one per length. Skip flags as opts.skip gives them.
 int tdec_run_groups(srslte_hip_tdec_t* q, const void* d_input_any, int llr8, uint32_t in_stride, const srslte_hip_tdec_group_t* groups, uint32_t nof_groups,
-                    uint32_t nof_iterations, uint8_t* d_output, uint32_t out_stride, uint32_t* d_iters, uint8_t* d_crc_ok, hipStream_t st)
+                    uint32_t nof_iterations, uint8_t* d_output, uint32_t out_stride, uint32_t* d_iters, uint8_t* d_crc_ok, hipStream_t st,
+                    const TdecOpts& opts)
 {
   if (!q || !d_input_any || !d_output || !groups || nof_groups > (uint32_t)TDEC_MAX_GROUPS || nof_iterations == 0) return SRSLTE_ERROR_INVALID_INPUTS;
-  // tdec_set_tb_ragged: the decoders assemble the transport blocks (one mixed launch, 16-bit kinds only); consumed by this call whatever its outcome
-  uint8_t* const       rg_tb = q->tb_out;
-  const uint8_t* const rg_Cof = q->tb_Cof;
-  q->tb_out = nullptr;
-  q->tb_Cof = nullptr;
-  const bool ragged = rg_tb != nullptr;
-  if ((ragged && (!rg_Cof || llr8)) || q->start_iter || q->tb_rem) return SRSLTE_ERROR_INVALID_INPUTS; // modes of the one-length call
+  // opts.tb_out with opts.tb_Cof: the decoders assemble the transport blocks (one mixed launch, 16-bit kinds only)
+  const bool ragged = opts.tb_out != nullptr;
+  if ((ragged && (!opts.tb_Cof || llr8)) || opts.start_iter || opts.tb_rem) return SRSLTE_ERROR_INVALID_INPUTS; // modes of the one-length call
+  if (ragged) {
+    if (int r = tdec_tb_acc_buf(q)) return r;
+  }
   enum { T_PAIR, T_WIN8, T_GEN, T_AR32, T_AR16, T_N };
   struct Plan { TdecGroups gs; uint32_t waves, stride, blocks; bool widened; };
   static const TdecGroups none = {};
@@ -2169,11 +2121,9 @@ int tdec_run_groups(srslte_hip_tdec_t* q, const void* d_input_any, int llr8, uin
   if (total > q->max_nof_cb) return SRSLTE_ERROR_INVALID_INPUTS;
   if (total == 0) return SRSLTE_SUCCESS;
   if (any_widen) { // the 8-bit API's 16-bit fall-backs (turbodecoder.c:465-469): the blocks of the widened groups, each in its slot of the buffer
-    const size_t per_max = ((size_t)3 * (q->max_long_cb + 32) + 12 + 31) & ~(size_t)31;
-    if (in_stride > per_max) return SRSLTE_ERROR_INVALID_INPUTS;
-    if (!q->d_conv) HIP_TRY(hipMalloc((void**)&q->d_conv, (size_t)q->max_nof_cb * per_max * sizeof(int16_t)));
+    if (int r = tdec_conv_buf(q, in_stride)) return r;
     const Plan& pw = plan[T_PAIR]; // all widened groups are in the mixable plan
-    hipLaunchKernelGGL(widen_groups_kernel, dim3(pw.blocks), dim3(256), 0, st, (const int8_t*)d_input_any, q->d_conv, q->cb_map, in_stride, pw.gs);
+    hipLaunchKernelGGL(widen_groups_kernel, dim3(pw.blocks), dim3(256), 0, st, (const int8_t*)d_input_any, q->d_conv.get(), opts.cb_map, in_stride, pw.gs);
     LAUNCH_CHECK();
   }
   for (int type = 0; type < T_N; type++) {
@@ -2184,14 +2134,14 @@ int tdec_run_groups(srslte_hip_tdec_t* q, const void* d_input_any, int llr8, uin
     const int run = type != T_PAIR ? type : (ragged ? T_N : (kinds == (1u << T_PAIR) ? T_PAIR : (kinds == (1u << T_WIN8) ? T_WIN8 : (kinds == (1u << T_GEN) ? T_GEN : T_N))));
     TdecArgs a;
     memset(&a, 0, sizeof(a));
-    a.in = p_.widened ? q->d_conv : (const int16_t*)d_input_any; a.in_stride = in_stride; a.sb_layout = run != T_GEN; a.nof_iter = nof_iterations;
+    a.in = p_.widened ? q->d_conv.get() : (const int16_t*)d_input_any; a.in_stride = in_stride; a.sb_layout = run != T_GEN; a.nof_iter = nof_iterations;
     a.K = p_.gs.g[0].K; a.nof_cb = p_.gs.g[0].nof_cb; a.t = p_.gs.g[0].t; // replaced per wavefront (tdec_enter_group)
     a.work = q->d_work; a.Kp = q->Kp; a.beta = q->d_beta; a.xy = q->d_xy; a.zeros = q->d_zeros; a.beta_stride = p_.stride;
     a.out = d_output; a.out_stride = out_stride; a.iters = d_iters; a.crc_ok = d_crc_ok; a.tb_C = 1;
-    a.skip = q->skip; a.cb_map = q->cb_map;
-    if (ragged && type == T_PAIR) { // consumed below
-      a.tb_out = rg_tb; a.tb_out_stride = q->tb_out_stride; a.tb_ok_out = q->tb_ok_out; a.tb_acc = q->d_tb_acc;
-      a.tb_Cof = rg_Cof; a.tb_C = q->tb_width; a.tb_B = q->tb_B; a.tb_rows0 = q->tb_rows0;
+    a.skip = opts.skip; a.cb_map = opts.cb_map;
+    if (ragged && type == T_PAIR) {
+      a.tb_out = opts.tb_out; a.tb_out_stride = opts.tb_out_stride; a.tb_ok_out = opts.tb_ok_out; a.tb_acc = q->d_tb_acc;
+      a.tb_Cof = opts.tb_Cof; a.tb_C = opts.tb_width; a.tb_B = opts.tb_B; a.tb_rows0 = opts.tb_rows0;
     }
     switch (run) {
       case T_PAIR: hipLaunchKernelGGL(tdec_pair_kernel, dim3(p_.waves), dim3(64), 0, st, a, p_.gs); break;
@@ -2216,7 +2166,7 @@ extern "C" int srslte_hip_tdec_run_batch(srslte_hip_tdec_t* q, const int16_t* d_
                                          uint8_t* d_output, uint32_t out_stride, uint32_t* d_iters, uint8_t* d_crc_ok, void* stream)
 {
   return tdec_run_batch_w(q, d_input, 0, in_stride, sb_layout, long_cb, -1, nof_cb, nof_iterations, crc_poly, crc_nbits, d_output, out_stride,
-                          d_iters, d_crc_ok, (hipStream_t)stream);
+                          d_iters, d_crc_ok, (hipStream_t)stream, TdecOpts());
 }
 
 // 8-bit LLRs (srslte_tdec_run_all_8bit / srslte_tdec_iteration_8bit, turbodecoder.c:565-593): back-end per K as on an AVX2 host
@@ -2225,7 +2175,7 @@ extern "C" int srslte_hip_tdec_run_batch_8bit(srslte_hip_tdec_t* q, const int8_t
                                               uint8_t* d_output, uint32_t out_stride, uint32_t* d_iters, uint8_t* d_crc_ok, void* stream)
 {
   return tdec_run_batch_w(q, d_input, 1, in_stride, sb_layout, long_cb, -1, nof_cb, nof_iterations, crc_poly, crc_nbits, d_output, out_stride,
-                          d_iters, d_crc_ok, (hipStream_t)stream);
+                          d_iters, d_crc_ok, (hipStream_t)stream, TdecOpts());
 }
 
 // srslte_tdec_init_manual equivalent (turbodecoder.c:168-215): force the numerics, W = 0 generic / 8 sse16 / 16 avx16
@@ -2235,6 +2185,6 @@ extern "C" int srslte_hip_tdec_run_batch_manual(srslte_hip_tdec_t* q, const int1
                                                 uint32_t* d_iters, uint8_t* d_crc_ok, void* stream)
 {
   return tdec_run_batch_w(q, d_input, 0, in_stride, sb_layout, long_cb, (int)nof_subblocks, nof_cb, nof_iterations, crc_poly, crc_nbits,
-                          d_output, out_stride, d_iters, d_crc_ok, (hipStream_t)stream);
+                          d_output, out_stride, d_iters, d_crc_ok, (hipStream_t)stream, TdecOpts());
 }
 #endif // TDEC_MIX_TU

@@ -757,7 +757,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TDEC_PAIR_MI
   PROF(0)
 
   int2*    ck     = reinterpret_cast<int2*>(a.beta) + (size_t)bx * (a.beta_stride / 2);
-  uint32_t n_iter = a.start_iter; // > 0: the work arrays hold the state this kernel leaves after that many passes (tdec_set_resume)
+  uint32_t n_iter = a.start_iter; // > 0: the work arrays hold the state this kernel leaves after that many passes (TdecOpts::start_iter)
   constexpr int EWU = TDEC_PAIR_EWU;             // table elements (16 bytes) in flight per lane in the element-wise phases
   constexpr int EWC = TDEC_PAIR_EWC;             // elements of the block's own arrays in flight per lane (12 = the longest block in one round trip)
   // The extrinsic exchange of turbodecoder_iter.h:71-139 happens AFTER each pass, in one element-wise phase that also takes the CRC of the

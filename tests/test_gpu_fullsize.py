@@ -242,7 +242,7 @@ def test_pool_one_call_per_batch(hp):
 @pytest.mark.parametrize("prb,mod,tbs,snr,llr8", [(100, 3, 75376, 18.0, False), (25, 2, 4008, 10.0, False), (6, 1, 152, 4.0, False), (100, 3, 75376, 30.0, True)])
 def test_results_straight_into_pinned_host_memory(hp, prb, mod, tbs, snr, llr8):
     """d_tb / d_tb_ok of the C-ABI may point into device-visible (pinned) host memory: the pipeline's last phase - the decoder itself for blocks of
-    more than 800 bits (tdec_set_tb_direct), tb_asm / tb_crc otherwise - stores the transport blocks and CRC flags there, no copy after the batch
+    more than 800 bits (TdecOpts::tb_out), tb_asm / tb_crc otherwise - stores the transport blocks and CRC flags there, no copy after the batch
     (bench.py's N = 1 line, +2.3 %). Same bytes and flags as with a device record, for decodable and undecodable blocks."""
     import torch
     from lte_sim import DlConfig, make_subframe

@@ -431,7 +431,7 @@ def test_every_decoder_kind_in_one_call(hp, llr8):
 
 
 def test_transport_blocks_assembled_by_the_decoders_equal_the_assembly_kernel(hp):
-    """A 16-bit grants call has its transport blocks assembled and judged by the decoders themselves (tdec_set_tb_ragged: per-slot block counts, CRC24A
+    """A 16-bit grants call has its transport blocks assembled and judged by the decoders themselves (TdecOpts::tb_Cof: per-slot block counts, CRC24A
     shares with the factor of the block's position, the last block to arrive gives the verdict; a block kept from an earlier transmission contributes
     its stored bytes); with SRSLTE_HIP_GRANTS_TB_DIRECT=0 in the environment an object uses the assembly kernel (tb_crc_bytes_kernel) instead.
     Same subframes both ways - blocks of every decoder kind, transport blocks of one, two and three blocks, SNRs around the thresholds so that

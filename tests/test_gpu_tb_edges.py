@@ -1,6 +1,6 @@
 """The top of the per-grant transport-block range: srslte_hip_dl_rx_batch_grants / _grants2 take any transport block up to 105 528 bits, which
 is up to 18 code blocks of K = 5888 (110 PRB, 256QAM). With 16-bit LLRs the decoders assemble and judge the transport blocks themselves
-(tdec_set_tb_ragged), multiplying block r's CRC24A share by a factor x^((C-1-r)(K-24)) of a table that holds 16 of them; a call with a larger
+(TdecOpts::tb_Cof), multiplying block r's CRC24A share by a factor x^((C-1-r)(K-24)) of a table that holds 16 of them; a call with a larger
 transport block has the assembly kernel (tb_crc_bytes_kernel) do it. Transport blocks of 16, 17 and 18 blocks - the last factor of the table,
 and both sides of the limit - against the oracle chain on the same samples (bytes, verdicts, passes of every block), against the assembly
 kernel (SRSLTE_HIP_GRANTS_TB_DIRECT=0) and against the fixed-grant pipeline; HARQ with blocks kept from the first transmission; two codewords;
