@@ -239,13 +239,21 @@ struct TdecArgs {
   unsigned long long* prof;    // -DTDEC_PROF builds: [nof_cb][10] cycles per phase, else unused
   int            dbg;          // timing experiments only (SRSLTE_HIP_TDEC_DBG): 1 skips the SISO sweeps, 2 the element-wise subtractions,
                                // 4 replaces the interleaver scatters by in-order stores, 8 points every branch-metric load at the zero buffer
-  // tdec_mix_kernel only (behind everything the other kernels read), with tb_out: transport blocks of DIFFERENT sizes (a ragged batch, TdecOpts::tb_Cof).
+  // Read where TDEC_RAGGED_TB only, i.e. by tdec_mix_kernel (behind everything the other kernels read), with tb_out: transport blocks of DIFFERENT sizes (a ragged batch, TdecOpts::tb_Cof).
   // Block slot cb belongs to transport-block slot cb / tb_C (tb_C = the slots' width), which has tb_Cof[cb / tb_C] blocks; its row of tb_out /
   // tb_ok_out is the slot itself below tb_B, tb_rows0 + slot - tb_B from there on (second codewords). tbA: the group's CRC24A tables (tdec_tbA_table)
   const uint8_t*  tb_Cof;
   uint32_t        tb_B, tb_rows0;
   const uint32_t* tbA;
 };
+// What tells the two translation units that compile this file apart, said once: tdec_mix.hip reads the decoders below as BODIES of its
+// tdec_mix_kernel, which alone serves ragged batches with the decoders' own transport-block assembly (TdecArgs::tb_Cof), and its 8-window
+// body meets K <= 800 only. Everything else that differs between the units is one of the three entry seams (pair, windowed, unwindowed).
+#ifdef TDEC_MIX_TU
+constexpr bool TDEC_RAGGED_TB = true;
+#else
+constexpr bool TDEC_RAGGED_TB = false;
+#endif
 
 // Several block lengths in ONE launch (ragged batches: tdec_run_groups). A launch per length is a serial chain of latency-bound kernels - a few
 // blocks each, up to six passes - and that chain, not the work, is what a mixed batch then takes. The table travels by value as a kernel
@@ -295,7 +303,6 @@ __device__ __forceinline__ uint32_t tdec_gf24_mul(uint32_t a, uint32_t b)
   return r;
 }
 
-#ifdef TDEC_MIX_TU
 // Ragged batches (TdecOpts::tb_Cof) with HARQ: a block whose CRC passed in an earlier transmission is not decoded again (sch.c:317-318) - its bytes
 // are in its row of a.out since then. It still owes its transport block what a decoded block gives in its last phase: its bytes in the block's
 // place, the CRC24A share of those bytes (table lookups in natural bit order: array position (n % Lw) * 16 + n / Lw) and its arrival. What it
@@ -344,7 +351,6 @@ __device__ __forceinline__ void tdec_tb_stored_block(const TdecArgs& a, int cb, 
     }
   }
 }
-#endif
 
 // ------------------------------------------------------------------------------------------------------------------
 // Windowed SISO (W = 16: packed pairs w = 2g+h; W = 8: w = g in the low half, high half idle)
@@ -401,7 +407,7 @@ __device__ __forceinline__ void win_normalize(pk_t& v)
   }
 }
 
-// gg = window pair within the step (0..7, or 0..15 for 32 windows)
+// gg = window pair within the step (0..7)
 template <int W>
 __device__ __forceinline__ void store_out(int16_t* out, int k, int gg, pk_t o)
 {
@@ -422,8 +428,7 @@ constexpr int ST_STEPS = 24;
 constexpr int ST_ARR   = ST_STEPS * 8;            // dwords of one array in one buffer: 24 steps x 8 window pairs
 constexpr int ST_BUF   = 3 * ST_ARR;              // x, y, x + y
 constexpr int ST_TOTAL = 2 * ST_BUF + ST_ARR;     // two buffers + zeros
-template <int W>
-constexpr int pairs_per_step() { return W == 32 ? 16 : 8; }
+constexpr int ST_PAIRS = 8;                       // window pairs per step (8 windows: the high halves idle)
 typedef int v8i __attribute__((ext_vector_type(8)));
 struct Src {                 // global arrays of one SISO pass, offset to the first pair of the half being processed
   const pk_t *x, *y;         // x + y is not an array: it is formed when the rows are staged (one saturating add per dword)
@@ -463,7 +468,7 @@ __device__ __forceinline__ StRegs stage_load(const Src& S, const Stage& st, int 
   r.b = *reinterpret_cast<const int4*>(S.y + off);
   return r;
 }
-// AR (the 8-bit back-ends with 16 / 32 windows): the y rows come straight from the parity array (int8 values in int16 containers) and move
+// AR (the 8-bit back-end with 16 windows): the y rows come straight from the parity array (int8 values in int16 containers) and move
 // to the high bytes HERE, where the row is consumed - not behind the load, which would wait for it (the rows are requested two blocks
 // ahead). The combine pass then reads and writes one array less. (Forming x = sat(a-priori + systematic) here as well, i.e. no combine
 // pass at all, is bit-exact too but takes the kernel from 168 to 242 VGPRs: profiles/r03/ab_llr8_staging.txt.)
@@ -502,7 +507,7 @@ __device__ __forceinline__ void win_run(const LaneGeom& L, pk_t& v, const Src& S
                                         pk_t* __restrict__ beta)
 {
   static_assert(MODE != 2, "the alpha main pass has its own loop (win_siso)");
-  constexpr int G = pairs_per_step<W>();
+  constexpr int G = ST_PAIRS;
   if (nb <= 0) return;
   // staged rows of block b: [k0 - (BLK-1), k0] (DIR < 0) or [k0, k0 + BLK) (DIR > 0); row jj of step j
   auto   lo  = [&](int b) { return DIR > 0 ? k_first + BLK * b : k_first - BLK * b - (BLK - 1); };
@@ -552,7 +557,7 @@ __device__ __forceinline__ void win_rem(const LaneGeom& L, pk_t& v, const Src& S
                                         int r, pk_t* __restrict__ beta)
 {
   static_assert(MODE != 2, "the alpha main pass has its own loop (win_siso)");
-  constexpr int G = pairs_per_step<W>();
+  constexpr int G = ST_PAIRS;
   if (r <= 0) return;
   const int k_lo = DIR > 0 ? k_first : k_first - (r - 1);
   stage_store<(W == 8 ? 0 : AR)>(st, 0, r, stage_load<G>(S, st, k_lo, r));
@@ -609,15 +614,18 @@ __device__ __forceinline__ v8u ld8u(const uint16_t* p, int i8) { return *reinter
 __device__ __forceinline__ void st8(int16_t* p, int i8, v8s v) { *reinterpret_cast<v8s*>(p + 8 * i8) = v; }
 
 // One SISO pass over W windows. W = 8/16 (AR = 0: sse16/avx16; AR = 1, W = 16: sse8): one pass of the wave over its 8 window
-// pairs. W = 32 (avx8): the wave handles the windows as NH = 2 halves of 16, one after the other in every phase - the windows
-// only meet in the two hand-overs, which see both halves' registers.
+// pairs. (The 32 windows of avx8 take the sweeps of tdec_pair.inc: pair_siso_ar32.)
 template <int W, int AR>
 __device__ __forceinline__ void win_siso(const LaneGeom& L, const int16_t* __restrict__ in, const int16_t* __restrict__ app,
                          const int16_t* __restrict__ par, const int16_t* tail_in, const int16_t* tail_par, int16_t* __restrict__ out,
                          pk_t* __restrict__ beta, pk_t* __restrict__ seg, pk_t* __restrict__ scratch, const Stage& st, int K PROF_ARGS)
 {
-  constexpr int NH = W == 32 ? 2 : 1;
-  constexpr int G  = 8 * NH; // window pairs per step
+  static_assert(W == 8 || W == 16, "one pass of the wavefront over its 8 window pairs");
+  // The loops over NH = 1 "halves" are what is left of a 32-window arm. They stay: written without them the same arithmetic reaches the
+  // optimiser in another order and every tdec_win_kernel instance and tdec_mix_kernel come out differently scheduled
+  // (profiles/tdec_seams/README.md).
+  constexpr int NH = 1;
+  constexpr int G  = ST_PAIRS;
   const int     Lw = K / W;
   const pk_t    NEG = AR ? 0 : pk_make(-TD_INF, -TD_INF); // INF = 0 for the 8-bit back-ends (turbodecoder_win.h:120,:152)
   pk_t          v[NH];
@@ -714,7 +722,7 @@ __device__ __forceinline__ void win_siso(const LaneGeom& L, const int16_t* __res
     } else {
 #pragma unroll
       for (int h = 0; h < NH; h++) {
-        const int nxt = L.g < 7 ? pk_lo(b[h]) : (h + 1 < NH ? pk_lo(b[(h + 1) % NH]) : ts);
+        const int nxt = L.g < 7 ? pk_lo(b[h]) : ts;
         v[h]          = pk_make(pk_hi(a[h]), nxt);
       }
     }
@@ -760,7 +768,7 @@ __device__ __forceinline__ void win_siso(const LaneGeom& L, const int16_t* __res
     } else {
 #pragma unroll
       for (int h = 0; h < NH; h++) {
-        const int prv = L.g > 0 ? pk_hi(b[h]) : (h > 0 ? pk_hi(b[(h + NH - 1) % NH]) : init);
+        const int prv = L.g > 0 ? pk_hi(b[h]) : init;
         v[h]          = pk_make(prv, pk_lo(a[h]));
       }
     }
@@ -866,12 +874,9 @@ __device__ __forceinline__ int win_pos(int n, int K)
 
 #include "tdec_pair.inc"
 
-// avx8 (32 windows, 8 bit) on the pair mapping: the combine pass of win_siso<32, 1> (x = sat(a-priori + systematic) in the high bytes, to the
+// avx8 (32 windows, 8 bit) on the pair mapping: the combine pass of the 8-bit windowed SISO (x = sat(a-priori + systematic) in the high bytes, to the
 // xy scratch; the parity array is read in place), then the sweeps of tdec_pair.inc with the wavefront's 16 window pairs = the block's 32 windows.
 // Every beta checkpoint of a window of at most 192 steps fits the LDS rows (P_CK_LDS); `ckg` only backs the clamped prefetch.
-#ifndef TDEC_AR32_PAIR
-#define TDEC_AR32_PAIR 1
-#endif
 __device__ __forceinline__ void pair_siso_ar32(const PLane& PL, int lane, const int16_t* __restrict__ in, const int16_t* __restrict__ app,
                                                const int16_t* __restrict__ par, const int16_t* tail_in, const int16_t* tail_par, int16_t* __restrict__ out,
                                                pk_t* __restrict__ pool, int2* __restrict__ ckg, pk_t* __restrict__ scratch, int K PROF_ARGS)
@@ -913,16 +918,6 @@ __device__ __forceinline__ void tdec_tb_fold(const TdecArgs& a, int tbi, int tbr
 #define TDEC_WAVES 2
 #endif
 #define TDEC_WAVES_ATTR __attribute__((amdgpu_waves_per_eu(TDEC_WAVES, TDEC_WAVES)))
-// AR = 1: int8 LLRs in (a.in is an int8 array), the work arrays hold int8 values in int16 containers
-#ifndef TDEC_MIX_TU
-template <int W, int AR>
-__device__ __forceinline__ void tdec_win_body(const TdecArgs& a0, const TdecGroups& gs);
-template <int W, int AR>
-__global__ __launch_bounds__(64) TDEC_WAVES_ATTR void tdec_win_kernel(TdecArgs a0, TdecGroups gs)
-{
-  tdec_win_body<W, AR>(a0, gs);
-}
-#endif
 // the avx8 back-end with the pair-mapped sweeps has its own register budget (see tdec_pair.inc on the 216-register rule)
 #ifndef TDEC_AR32_NVGPR
 #define TDEC_AR32_NVGPR 108
@@ -932,36 +927,55 @@ __global__ __launch_bounds__(64) TDEC_WAVES_ATTR void tdec_win_kernel(TdecArgs a
 #else
 #define AR32_NVGPR_ATTR
 #endif
-#ifndef TDEC_MIX_TU
-__global__ __launch_bounds__(64) TDEC_WAVES_ATTR AR32_NVGPR_ATTR void tdec_ar32_kernel(TdecArgs a0, TdecGroups gs) { tdec_win_body<32, 1>(a0, gs); }
-#endif
+// The longest block the windowed body's LDS is laid out for. A ragged batch gives the 8-window decoder K <= 800 only (AUTO): 6 checkpoint rows
+// instead of 34. One LDS pool: beta checkpoints (lane-private columns, ceil(Lw / CKPT) + 1 rows with Lw <= WIN_MAX_K / W; twice that for the 32
+// windows of tdec_ar32_kernel, whose pair sweeps lay the same pool out as P_POOL) | beta metrics of the segment being consumed | branch-metric
+// staging (Stage)
+constexpr int WIN_MAX_K = TDEC_RAGGED_TB ? 800 : SRSLTE_HIP_MAX_K;
+template <int W>
+constexpr int WIN_POOL_BETA = (W == 32 ? 2 : 1) * (WIN_MAX_K / W / CKPT + 2) * 64;
+constexpr int WIN_POOL_SEG  = (CKPT + 1) * 64;
+template <int W>
+constexpr int WIN_POOL = WIN_POOL_BETA<W> + WIN_POOL_SEG + ST_TOTAL;
+// AR = 1: int8 LLRs in (a.in is an int8 array), the work arrays hold int8 values in int16 containers
+//
+// ENTRY SEAM (windowed), to be left a preprocessor seam: either kernels with their own LDS that find their group themselves, or a body that
+// the mixed kernel calls with `a` already describing the wavefront's group and with its LDS (pool / tl). Giving both units the second form
+// behind thin kernels kept every resource figure but changed schedule and register assignment of tdec_ar32_kernel and of every
+// tdec_win_kernel instance (80-90 lines each; profiles/tdec_seams/README.md, finding 3).
 #ifdef TDEC_MIX_TU
-// tdec_mix.hip: the body for a wavefront of a mixed launch - `a` already describes its group, pool / tl are the mixed kernel's LDS, laid out for
-// blocks of at most WIN_MAX_K bits (AUTO gives the 8-window decoder K <= 800 only: 6 checkpoint rows instead of 34)
-constexpr int WIN_MAX_K = 800;
 template <int W, int AR>
 __device__ __forceinline__ void tdec_win_body(TdecArgs& a, const uint32_t bx, pk_t* pool, int16_t* tl)
 {
 #else
-constexpr int WIN_MAX_K = SRSLTE_HIP_MAX_K;
+template <int W, int AR>
+__device__ __forceinline__ void tdec_win_body(const TdecArgs& a0, const TdecGroups& gs);
+template <int W, int AR>
+__global__ __launch_bounds__(64) TDEC_WAVES_ATTR void tdec_win_kernel(TdecArgs a0, TdecGroups gs)
+{
+  tdec_win_body<W, AR>(a0, gs);
+}
+__global__ __launch_bounds__(64) TDEC_WAVES_ATTR AR32_NVGPR_ATTR void tdec_ar32_kernel(TdecArgs a0, TdecGroups gs) { tdec_win_body<32, 1>(a0, gs); }
 template <int W, int AR>
 __device__ __forceinline__ void tdec_win_body(const TdecArgs& a0, const TdecGroups& gs)
 {
   TdecArgs       a  = a0;
   const uint32_t bx = tdec_enter_group(a, gs);
+  __shared__ __attribute__((aligned(16))) pk_t pool[WIN_POOL<W>];
+  __shared__ int16_t tl[12];
 #endif
   using in_t = typename std::conditional<AR != 0, int8_t, int16_t>::type;
   const int      lcb = (int)bx, cb = a.cb_map ? (int)a.cb_map[lcb] : lcb, K = (int)a.K;
   if (a.skip && a.skip[cb]) { // "Do not process blocks with CRC Ok" (sch.c:317-318): bytes, flag and TB-CRC share stay
     if (threadIdx.x == 0 && a.iters) a.iters[cb] = 0;
-#ifdef TDEC_MIX_TU
-    if (a.tb_out && a.tb_Cof) { // a ragged batch: the block (K <= 800) is a transport block that was delivered before; its row, no second delivery
-      const uint32_t tbi = (uint32_t)cb / a.tb_C;
-      const size_t   row = tbi < a.tb_B ? (size_t)tbi : (size_t)a.tb_rows0 + tbi - a.tb_B;
-      for (int b = (int)threadIdx.x; b < K / 8; b += 64) a.tb_out[row * a.tb_out_stride + b] = a.out[(size_t)cb * a.out_stride + b];
-      if (threadIdx.x == 0) a.tb_ok_out[row] = 0;
+    if constexpr (TDEC_RAGGED_TB) {
+      if (a.tb_out && a.tb_Cof) { // a ragged batch: the block (K <= 800) is a transport block that was delivered before; its row, no second delivery
+        const uint32_t tbi = (uint32_t)cb / a.tb_C;
+        const size_t   row = tbi < a.tb_B ? (size_t)tbi : (size_t)a.tb_rows0 + tbi - a.tb_B;
+        for (int b = (int)threadIdx.x; b < K / 8; b += 64) a.tb_out[row * a.tb_out_stride + b] = a.out[(size_t)cb * a.out_stride + b];
+        if (threadIdx.x == 0) a.tb_ok_out[row] = 0;
+      }
     }
-#endif
     return;
   }
   const LaneGeom L  = lane_geom();
@@ -969,25 +983,20 @@ __device__ __forceinline__ void tdec_win_body(const TdecArgs& a0, const TdecGrou
   int16_t*       wk = a.work + (size_t)lcb * 7 * a.Kp;
   int16_t *syst = wk, *par0 = wk + a.Kp, *par1 = wk + 2 * a.Kp, *app1 = wk + 3 * a.Kp, *app2 = wk + 4 * a.Kp, *ext1 = wk + 5 * a.Kp,
           *ext2 = wk + 6 * a.Kp;
-  // beta checkpoints (lane-private columns): ceil(Lw / CKPT) + 1 rows per half; Lw <= MAX_K / W (two halves for W = 32)
-  constexpr int BETA_ROWS = (W == 32 ? 2 : 1) * (WIN_MAX_K / W / CKPT + 2);
-  // One LDS pool: beta checkpoints | beta metrics of the segment being consumed | branch-metric staging (Stage). Between SISO
-  // passes the front of it (everything but the staging area's constant zero region) doubles as the buffer in which the
+  // Between SISO passes the front of the pool (everything but the staging area's constant zero region) doubles as the buffer in which the
   // interleaver permutations are done: a 2-byte scatter costs the L1 one cache line per lane (64 cycles per wavefront
   // instruction), an LDS scatter a few bank-conflict cycles.
-  constexpr int POOL_BETA = BETA_ROWS * 64, POOL_SEG = (CKPT + 1) * 64;
-#ifndef TDEC_MIX_TU
-  __shared__ __attribute__((aligned(16))) pk_t pool[POOL_BETA + POOL_SEG + ST_TOTAL];
-#endif
+  constexpr int POOL_BETA = WIN_POOL_BETA<W>, POOL_SEG = WIN_POOL_SEG;
   pk_t *                                       beta = pool, *seg = pool + POOL_BETA, *mt = pool + POOL_BETA + POOL_SEG;
   int16_t*                                     perm = reinterpret_cast<int16_t*>(pool);
   static_assert(2 * (POOL_BETA + POOL_SEG + 2 * ST_BUF) >= WIN_MAX_K, "permutation buffer must hold one code block");
-  constexpr bool  PAIR32 = W == 32 && AR && TDEC_AR32_PAIR; // the sweeps of tdec_pair.inc; this kernel keeps extraction, exchange, CRC and decisions
+  constexpr bool  PAIR32 = W == 32; // avx8: the sweeps of tdec_pair.inc; this body keeps extraction, exchange, CRC and decisions
+  static_assert(!PAIR32 || AR, "32 windows exist for 8-bit LLRs only");
   Stage st;
   if constexpr (!PAIR32) stage_init(st, mt, L);
   PROF_DECL;
   pk_t*           xy = reinterpret_cast<pk_t*>(a.xy + (size_t)lcb * a.K); // 16 B per trellis step: room for the x, y and x + y arrays
-  static_assert(!PAIR32 || POOL_BETA + POOL_SEG + ST_TOTAL >= P_POOL, "the pair sweeps' LDS pool");
+  static_assert(!PAIR32 || WIN_POOL<W> >= P_POOL, "the pair sweeps' LDS pool");
   const PLane     PL = p_lane<true>();
   int2*           ckg = reinterpret_cast<int2*>(a.beta) + (size_t)bx * ((K / 32 / PB + 3) * 64);
   if constexpr (PAIR32) {
@@ -997,9 +1006,7 @@ __device__ __forceinline__ void tdec_win_body(const TdecArgs& a0, const TdecGrou
   // ---- input extraction (turbodecoder_win.h:727-769 / turbodecoder_iter.h:58-68,84-91). The 12 tail LLRs go to LDS. A 16-bit
   //      SB-layout buffer already is three window-ordered arrays: like upstream (turbodecoder_iter.h:84-91) the decoder then
   //      reads systematic and parity LLRs in place instead of copying them.
-#ifndef TDEC_MIX_TU
-  __shared__ int16_t tl[12]; // [0..2] systematic tail, [3..5] parity-0 tail, [6..8] interleaved systematic tail, [9..11] parity-1 tail
-#endif
+  //      tl: [0..2] systematic tail, [3..5] parity-0 tail, [6..8] interleaved systematic tail, [9..11] parity-1 tail
   const int  tb      = a.sb_layout ? 3 * (K + 32) : 3 * K;
   const bool inplace = !AR && a.sb_layout && ((reinterpret_cast<uintptr_t>(in) | (a.in_stride * sizeof(int16_t))) & 15) == 0;
   const int16_t *syst_r = syst, *par0_r = par0, *par1_r = par1;
@@ -1171,13 +1178,13 @@ __device__ __forceinline__ void tdec_win_body(const TdecArgs& a0, const TdecGrou
   const int tbr = (int)(cb % a.tb_C), tbi = (int)(cb / a.tb_C);
   int       rb = (int)a.tb_rb, tbC = (int)a.tb_C;
   size_t    row = (size_t)tbi;
-#ifdef TDEC_MIX_TU
-  if (a.tb_Cof) { // a ragged batch: the blocks this decoder takes (K <= 800) are transport blocks of their own, their CRC24A is the block's CRC
-    tbC = 1;
-    rb  = K8;
-    row = (uint32_t)tbi < a.tb_B ? (size_t)tbi : (size_t)a.tb_rows0 + tbi - a.tb_B;
+  if constexpr (TDEC_RAGGED_TB) {
+    if (a.tb_Cof) { // a ragged batch: the blocks this decoder takes (K <= 800) are transport blocks of their own, their CRC24A is the block's CRC
+      tbC = 1;
+      rb  = K8;
+      row = (uint32_t)tbi < a.tb_B ? (size_t)tbi : (size_t)a.tb_rows0 + tbi - a.tb_B;
+    }
   }
-#endif
   uint8_t*  tbo = a.tb_out ? a.tb_out + row * a.tb_out_stride + (size_t)tbr * rb : nullptr;
   const int tlim = tbr == tbC - 1 ? K8 : rb;
   bool      par_nz = false; // the TB's CRC24A bytes, the last three of the last block's rb: not all zero (sch.c:481)
@@ -1203,11 +1210,9 @@ __device__ __forceinline__ void tdec_win_body(const TdecArgs& a0, const TdecGrou
   if (tbo) par_nz = __ballot(par_nz) != 0;
   PROF(8)
   if (L.lane == 0) {
-#ifdef TDEC_MIX_TU
-    if (tbo && a.tb_Cof) a.tb_ok_out[row] = (ok && par_nz) ? 1 : 0; // one block: the verdict of sch.c:470-488 is the block's CRC and a non-zero parity
-    else
-#endif
-    if (tbo) tdec_tb_fold(a, tbi, tbr, tsyn, ok, par_nz);
+    // a ragged batch, one block: the verdict of sch.c:470-488 is the block's CRC and a non-zero parity (a plain `if`: the else arm is shared)
+    if (TDEC_RAGGED_TB && tbo && a.tb_Cof) a.tb_ok_out[row] = (ok && par_nz) ? 1 : 0;
+    else if (tbo) tdec_tb_fold(a, tbi, tbr, tsyn, ok, par_nz);
     if (a.iters) a.iters[cb] = n_iter;
     if (a.crc_ok) a.crc_ok[cb] = ok ? 1 : 0;
     if (a.tb_rem) a.tb_syn[cb] = tsyn;
@@ -1228,9 +1233,6 @@ __device__ __forceinline__ void tdec_win_body(const TdecArgs& a0, const TdecGrou
 // permutations through LDS, the CRC syndrome of every pass, decisions. A slot whose block has passed its CRC (or that has no block: an odd
 // count, a skipped block) waits in lockstep: its lanes read its partner's first rows over and over and store nothing.
 // ------------------------------------------------------------------------------------------------------------------
-#ifndef TDEC_AR16_PAIR
-#define TDEC_AR16_PAIR 1 // 0: the state-per-lane kernel of rounds 1-3 (tdec_win_kernel<16, 1>), for A/B builds
-#endif
 #ifndef TDEC_AR16_NVGPR
 #define TDEC_AR16_NVGPR 108
 #endif
@@ -1239,7 +1241,7 @@ __device__ __forceinline__ void tdec_win_body(const TdecArgs& a0, const TdecGrou
 #else
 #define AR16_NVGPR_ATTR
 #endif
-#ifndef TDEC_MIX_TU
+#ifndef TDEC_MIX_TU // an 8-bit kernel: no part of the mixed launch
 __global__ __launch_bounds__(64) TDEC_WAVES_ATTR AR16_NVGPR_ATTR void tdec_ar16_kernel(TdecArgs a0, TdecGroups gs)
 {
   TdecArgs       a  = a0;
@@ -1497,8 +1499,7 @@ __global__ __launch_bounds__(64) TDEC_WAVES_ATTR AR16_NVGPR_ATTR void tdec_ar16_
   PROF(8)
 }
 
-
-#endif // !TDEC_MIX_TU
+#endif // tdec_ar16_kernel
 
 // ------------------------------------------------------------------------------------------------------------------
 // Generic decoder (turbodecoder_gen.c:54-233): 8 code blocks per wave (group g = block slot), low half only, wrapping
@@ -1586,6 +1587,9 @@ __device__ void gen_siso(const LaneGeom& L, const int16_t* __restrict__ in, cons
 #undef ACS
 }
 
+// ENTRY SEAM (unwindowed), to be left a preprocessor seam: a body for the mixed kernel, `a` already describing the wavefront's group, or a
+// kernel that finds its group itself. One signature behind a thin kernel kept tdec_gen_kernel's resource figures but not its schedule
+// (profiles/tdec_seams/README.md, finding 3).
 #ifdef TDEC_MIX_TU
 __device__ __forceinline__ void tdec_gen_body(TdecArgs& a, const uint32_t bx)
 {
@@ -1680,8 +1684,7 @@ __global__ __launch_bounds__(64) void tdec_gen_kernel(TdecArgs a0, TdecGroups gs
     }
     if (__all(ok || !active)) break; // sch.c:383 per block; the wave leaves when every block has stopped
   }
-#ifdef TDEC_MIX_TU
-  if (a.tb_out && a.tb_Cof && active) { // a ragged batch: the block is a transport block of its own (K <= 400): its bytes and its verdict
+  if (TDEC_RAGGED_TB && a.tb_out && a.tb_Cof && active) { // a ragged batch: the block is a transport block of its own (K <= 400): its bytes and its verdict
     const uint32_t tbi = cb / a.tb_C;
     const size_t   row = tbi < a.tb_B ? (size_t)tbi : (size_t)a.tb_rows0 + tbi - a.tb_B;
     uint8_t*       tbo = a.tb_out + row * a.tb_out_stride;
@@ -1697,58 +1700,23 @@ __global__ __launch_bounds__(64) void tdec_gen_kernel(TdecArgs a0, TdecGroups gs
     pz |= __builtin_amdgcn_update_dpp(pz, pz, 0x128, 0xf, 0xf, false);
     if (L.p == 0) a.tb_ok_out[row] = (ok && pz) ? 1 : 0;
   }
-#endif
   if (L.p == 0 && active) {
     if (a.iters) a.iters[cb] = my_iters;
     if (a.crc_ok) a.crc_ok[cb] = ok ? 1 : 0;
   }
   if (L.p == 0 && skipped && a.iters) a.iters[cb] = 0;
-#ifdef TDEC_MIX_TU
-  if (a.tb_out && a.tb_Cof && skipped) { // delivered by an earlier transmission: the stored bytes, no second delivery
+  if (TDEC_RAGGED_TB && a.tb_out && a.tb_Cof && skipped) { // delivered by an earlier transmission: the stored bytes, no second delivery
     const uint32_t tbi = cb / a.tb_C;
     const size_t   row = tbi < a.tb_B ? (size_t)tbi : (size_t)a.tb_rows0 + tbi - a.tb_B;
     for (uint32_t b = L.p; b < (uint32_t)K / 8; b += 8) a.tb_out[row * a.tb_out_stride + b] = a.out[(size_t)cb * a.out_stride + b];
     if (L.p == 0) a.tb_ok_out[row] = 0;
   }
-#endif
 }
 
-#ifdef TDEC_MIX_TU
-// ------------------------------------------------------------------------------------------------------------------
-// A ragged batch (tdec_run_groups) in ONE launch: its groups of equal block length may be of different KINDS - the two-blocks-per-wavefront
-// decoder (K > 800), the 8-window one (400 < K <= 800), the unwindowed one (K <= 400). Launched one kind after the other on the batch's stream
-// they were a chain: the short-block launches are a few wavefronts each and as long as their longest recursion (unwindowed 127 us, 8-window
-// 59 us behind the 376 us of the long blocks in the mixed-grant workload). Here every wavefront looks up its group, reads its kind and runs
-// that decoder's body; the LDS pool is laid out for the larger need (pair sweeps / the 8-window body with the checkpoint rows of K <= 800).
-// Register budget and occupancy: the pair kernel's. Mixed-grant line 622 k -> 791 k subframes/s (profiles/r04/ab_mix_kernel.txt).
-// ------------------------------------------------------------------------------------------------------------------
-constexpr int MIX_WIN8_POOL = (WIN_MAX_K / 8 / CKPT + 2) * 64 + (CKPT + 1) * 64 + ST_TOTAL;
-constexpr int MIX_POOL      = MIX_WIN8_POOL > P_POOL ? MIX_WIN8_POOL : P_POOL;
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TDEC_PAIR_MINW, TDEC_PAIR_WAVES))) P_NVGPR_ATTR void tdec_mix_kernel(TdecArgs a0, TdecGroups gs)
-{
-  TdecArgs       a = a0;
-  uint32_t       gi = 0;
-  for (uint32_t i = 1; i < gs.n; i++) gi = blockIdx.x >= gs.g[i].first_wave ? i : gi;
-  const uint32_t kind = gs.kind[gi];
-  const uint32_t bx   = tdec_enter_group(a, gs);
-  __shared__ __attribute__((aligned(16))) pk_t pool[MIX_POOL];
-  __shared__ int16_t tl[2][12];
-  a.sb_layout = kind != TDEC_KIND_GEN; // the unwindowed decoder reads the plain [s p0 p1] layout, the windowed ones the rate de-matcher's
-  a.tbA       = gs.tbA[gi];
-  if (kind == TDEC_KIND_PAIR) tdec_pair_body(a, bx, pool, tl);
-  else if (kind == TDEC_KIND_WIN8) tdec_win_body<8, 0>(a, bx, pool, tl[0]);
-  else tdec_gen_body(a, bx);
-}
 } // namespace
-// called by tdec_run_groups (tdec.hip); args / groups: that unit's TdecArgs / TdecGroups (the same definitions)
-int tdec_mix_launch(const void* args, const void* groups, unsigned waves, hipStream_t st)
-{
-  hipLaunchKernelGGL(tdec_mix_kernel, dim3(waves), dim3(64), 0, st, *static_cast<const TdecArgs*>(args), *static_cast<const TdecGroups*>(groups));
-  LAUNCH_CHECK();
-  return SRSLTE_SUCCESS;
-}
-#else // !TDEC_MIX_TU: the rest of this file
-} // namespace
+// Here ends what tdec_mix.hip reads of this file (the decoders as bodies; its kernel follows its #include): the kernels' launches, the
+// widening kernels and the host side are this unit's alone.
+#ifndef TDEC_MIX_TU
 int tdec_mix_launch(const void* args, const void* groups, unsigned waves, hipStream_t st); // tdec_mix.hip
 namespace {
 // int8 -> int16 widening for the 8-bit API's 16-bit fall-backs (convert_8_to_16, turbodecoder.c:451-456)
@@ -1972,7 +1940,7 @@ int tdec_run_batch_w(srslte_hip_tdec_t* q, const void* d_input_any, int llr8, ui
     return SRSLTE_ERROR_INVALID_INPUTS;
   if (nof_cb == 0) return SRSLTE_SUCCESS;
   // force_w 3016: the 16-window numerics in the state-per-lane mapping of rounds 1-2 (tdec_win_kernel<16, 0>: the tests' second opinion on
-  // tdec_pair_kernel, which AUTO and 16 select)
+  // tdec_pair_kernel, which AUTO and 16 select). 16-bit LLRs only: 8-bit ones with 16 windows take tdec_ar16_kernel whatever the mapping asked for
   const bool old_map = force_w == 3016;
   if (old_map) force_w = 16;
   const uint32_t W = force_w >= 0 ? (uint32_t)force_w : (llr8 ? srslte_hip_tdec_autoimp_get_subblocks_8bit(K) : srslte_hip_tdec_autoimp_get_subblocks(K));
@@ -2021,10 +1989,8 @@ int tdec_run_batch_w(srslte_hip_tdec_t* q, const void* d_input_any, int llr8, ui
   static const TdecGroups no_groups = {};
   if (ar8 && W == 32) {
     hipLaunchKernelGGL(tdec_ar32_kernel, dim3(nof_cb), dim3(64), 0, st, a, no_groups);
-  } else if (ar8 && !old_map && TDEC_AR16_PAIR) {
-    hipLaunchKernelGGL(tdec_ar16_kernel, dim3((nof_cb + 1) / 2), dim3(64), 0, st, a, no_groups);
   } else if (ar8) {
-    hipLaunchKernelGGL((tdec_win_kernel<16, 1>), dim3(nof_cb), dim3(64), 0, st, a, no_groups);
+    hipLaunchKernelGGL(tdec_ar16_kernel, dim3((nof_cb + 1) / 2), dim3(64), 0, st, a, no_groups);
   } else if (W == 16 && !old_map) {
     a.beta_stride = (K / 16 / PB + 2) * 128; // checkpoint rows of a wavefront: 64 lanes x 2 dwords
     hipLaunchKernelGGL(tdec_pair_kernel, dim3((nof_cb + 1) / 2), dim3(64), 0, st, a, no_groups);
@@ -2108,7 +2074,7 @@ int tdec_run_groups(srslte_hip_tdec_t* q, const void* d_input_any, int llr8, uin
     TdecGroup& d  = p_.gs.g[p_.gs.n++];
     d.K = g.K; d.nof_cb = g.nof_cb; d.first_lcb = total; d.first_wave = p_.waves;
     if (int r = tdec_get_tables(q, g.K, W, g.crc_poly, g.crc_nbits, &d.t)) return r;
-    const uint32_t waves = (type == T_PAIR || (type == T_AR16 && TDEC_AR16_PAIR)) ? (g.nof_cb + 1) / 2 : (type == T_GEN ? (g.nof_cb + 7) / 8 : g.nof_cb);
+    const uint32_t waves = (type == T_PAIR || type == T_AR16) ? (g.nof_cb + 1) / 2 : (type == T_GEN ? (g.nof_cb + 7) / 8 : g.nof_cb);
     const uint32_t stride = type == T_PAIR ? (g.K / 16 / PB + 2) * 128 : (type == T_GEN ? (g.K + 4) * 64 : (g.K / (W == 32 ? 16 : W) + 1) * 64);
     p_.waves += waves;
     p_.stride = stride > p_.stride ? stride : p_.stride;
@@ -2148,10 +2114,7 @@ int tdec_run_groups(srslte_hip_tdec_t* q, const void* d_input_any, int llr8, uin
       case T_WIN8: hipLaunchKernelGGL((tdec_win_kernel<8, 0>), dim3(p_.waves), dim3(64), 0, st, a, p_.gs); break;
       case T_GEN: hipLaunchKernelGGL(tdec_gen_kernel, dim3(p_.waves), dim3(64), 0, st, a, p_.gs); break;
       case T_AR32: hipLaunchKernelGGL(tdec_ar32_kernel, dim3(p_.waves), dim3(64), 0, st, a, p_.gs); break;
-      case T_AR16:
-        if (TDEC_AR16_PAIR) hipLaunchKernelGGL(tdec_ar16_kernel, dim3(p_.waves), dim3(64), 0, st, a, p_.gs);
-        else hipLaunchKernelGGL((tdec_win_kernel<16, 1>), dim3(p_.waves), dim3(64), 0, st, a, p_.gs);
-        break;
+      case T_AR16: hipLaunchKernelGGL(tdec_ar16_kernel, dim3(p_.waves), dim3(64), 0, st, a, p_.gs); break;
       default: // the mixed launch sets sb_layout per kind itself
         if (int r = tdec_mix_launch(&a, &p_.gs, p_.waves, st)) return r;
         break;
@@ -2187,4 +2150,4 @@ extern "C" int srslte_hip_tdec_run_batch_manual(srslte_hip_tdec_t* q, const int1
   return tdec_run_batch_w(q, d_input, 0, in_stride, sb_layout, long_cb, (int)nof_subblocks, nof_cb, nof_iterations, crc_poly, crc_nbits,
                           d_output, out_stride, d_iters, d_crc_ok, (hipStream_t)stream, TdecOpts());
 }
-#endif // TDEC_MIX_TU
+#endif // the host side

@@ -664,10 +664,12 @@ struct PBlk {
 #else
 #define P_NVGPR_ATTR
 #endif
+// ENTRY SEAM (pair), to be left a preprocessor seam. tdec_mix.hip compiles this file's kernel as a BODY that tdec_mix_kernel calls for the
+// wavefronts of its K > 800 groups: `a` describes the wavefront's group, bx is its index there, pool / tl are the mixed kernel's LDS. (A second
+// translation unit, so that nothing about the kernel below - inlining order, register allocation - depends on the mixed kernel's existence:
+// with both in one unit it lost 1.5 % of the headline.) A thin kernel around one shared body was tried: the headline kernel changed, 14016 ->
+// 14149 assembly lines with `a` by reference, 13985 and other spills by value (profiles/tdec_seams/README.md, finding 2).
 #ifdef TDEC_MIX_TU
-// tdec_mix.hip compiles this file's kernel as a BODY that tdec_mix_kernel calls for the wavefronts of its K > 800 groups: `a` describes the
-// wavefront's group, bx is its index there, pool / tl are the mixed kernel's LDS. (A second translation unit, so that nothing about the kernel
-// below - inlining order, register allocation - depends on the mixed kernel's existence: with both in one unit it lost 1.5 % of the headline.)
 __device__ __forceinline__ void tdec_pair_body(TdecArgs& a, const uint32_t bx, pk_t* pool, int16_t (*tl)[12])
 {
   constexpr int W   = 16;
@@ -696,16 +698,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TDEC_PAIR_MI
   if (a.skip && a.skip[cb_a]) {
     if (L.lane == 0 && a.iters) a.iters[cb_a] = 0;
     live_a = false;
-#ifdef TDEC_MIX_TU
-    if (a.tb_out && a.tb_Cof) tdec_tb_stored_block(a, cb_a, K, L.lane);
-#endif
+    if (TDEC_RAGGED_TB && a.tb_out && a.tb_Cof) tdec_tb_stored_block(a, cb_a, K, L.lane);
   }
   if (live_b && a.skip && a.skip[cb_b]) {
     if (L.lane == 0 && a.iters) a.iters[cb_b] = 0;
     live_b = false;
-#ifdef TDEC_MIX_TU
-    if (a.tb_out && a.tb_Cof) tdec_tb_stored_block(a, cb_b, K, L.lane);
-#endif
+    if (TDEC_RAGGED_TB && a.tb_out && a.tb_Cof) tdec_tb_stored_block(a, cb_b, K, L.lane);
   }
   if (!live_a && !live_b) return;
   // slot 0 always holds a live block; a slot 1 without one shadows slot 0: same loads, same stores of the same values
@@ -938,15 +936,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TDEC_PAIR_MI
     int             tbC  = (int)a.tb_C, rb = (int)a.tb_rb;
     size_t          row  = (size_t)tbi;
     uint32_t        fac  = 1;
-#ifdef TDEC_MIX_TU
-    if (a.tb_Cof) { // a ragged batch: this transport block's own block count; the share tables do not depend on the block's position, its factor does
+    if (TDEC_RAGGED_TB && a.tb_Cof) { // a ragged batch: this transport block's own block count; the share tables do not depend on the block's position, its factor does
       tbC = (int)a.tb_Cof[tbi];
       rb  = (tbC == 1 ? K : K - 24) / 8;
       tab = a.tbA + (tbC == 1 ? 0 : K);
       fac = a.tbA[2 * K + (tbC - 1 - tbr)];
       row = (uint32_t)tbi < a.tb_B ? (size_t)tbi : (size_t)a.tb_rows0 + tbi - a.tb_B;
     }
-#endif
     uint8_t*        tbo  = a.tb_out ? a.tb_out + row * a.tb_out_stride + (size_t)tbr * rb : nullptr;
     const int       tlim = tbr == tbC - 1 ? K8 : rb;
     bool            par_nz = false; // the TB's CRC24A bytes, the last rb - 3 .. rb - 1 of the last block: not all zero (sch.c:481)
@@ -1025,12 +1021,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TDEC_PAIR_MI
         uint32_t* acc = a.tb_acc + 4 * (size_t)tbi;
         const uint32_t o1 = atomicXor(acc, tsyn);
         uint32_t want = 2u, flags = (b.ok ? 0u : 1u) | ((tbr == tbC - 1 && par_nz) ? 2u : 0u);
-#ifdef TDEC_MIX_TU
-        if (a.tb_Cof) { // ragged batches: bit 2 = a block of this transport block was decoded in this call (skipped ones do not set it, tdec_tb_stored_block)
+        if (TDEC_RAGGED_TB && a.tb_Cof) { // ragged batches: bit 2 = a block of this transport block was decoded in this call (skipped ones do not set it, tdec_tb_stored_block)
           flags |= 4u;
           want = 6u;
         }
-#endif
         const uint32_t o2 = atomicOr(acc + 1, flags);
         uint32_t dep = o1 | o2;
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(dep)::"memory");
