@@ -1315,9 +1315,9 @@ int      srslte_hip_srs_check(const srslte_hip_srs_cfg_t* cfg, uint32_t tti0, ui
  * srslte_hip_cfo_correct_batch: out[b stride + i] = in[b stride + i] exp(j 2 pi freq[b] i), i < len (srslte_cfo_correct / srslte_vec_apply_cfo
  * with freq in cycles per sample); the phase is the fractional part of freq[b] i taken in double, so it is as exact at sample 150 000 as at
  * sample 0 (the reference's running phasor drifts). d_out == d_in is allowed; freq is a host array read before the call returns.
- * Not here: TDD positions and frame-type detection, decimation, the integer-CFO stage, SSS equalisation from the PSS channel estimate,
- * srslte_pss_sic, averages across calls and ue_sync's find / track state machine, NB-IoT, and the single-call
- * drop-in, whose sync directory remains the reference's over srslte_dft_*. */
+ * Not here: decimation, the integer-CFO stage, SSS equalisation from the PSS channel estimate, srslte_pss_sic, ue_sync's find / track state
+ * machine, NB-IoT, and the single-call drop-in, whose sync directory remains the reference's over srslte_dft_*. TDD positions, frame-type
+ * detection and the averages across calls are the tracked call's ("UE synchronisation: tracks" below); this call stays FDD and stateless. */
 typedef struct srslte_hip_sync_s srslte_hip_sync_t;
 typedef struct {
   uint32_t fft_size;          /* 64..2048, multiple of 64 */
@@ -1375,6 +1375,94 @@ int srslte_hip_cell_search_decide(const srslte_hip_sync_res_t* found, uint32_t n
 /* TEST AND DIAGNOSTIC ENTRY: the CP stage's correlations of item b of the last call, min(max_offset, fft_size) cf32 values to the host
  * (synchronises the device) */
 int srslte_hip_sync_cp_corr(srslte_hip_sync_t* q, uint32_t item, void* h_corr);
+
+/* ------------------------------------------------------------------ UE synchronisation: tracks - a srslte_sync_t's state across calls, TDD
+ * A tracks object belongs to a srslte_hip_sync_t (destroy it first) and holds, on the device, the state of n_tracks independent srslte_sync_t
+ * that share the sync object's configuration: one track per UE or per scan. srslte_hip_sync_track_batch runs ONE srslte_sync_find per item on
+ * the item's track - whatever number of calls the track has seen - and leaves the row the reference's getters would show afterwards. A track
+ * that was just created or reset with flags 7, in frame mode 0, gives in the first 16 words the very row of srslte_hip_sync_find_batch.
+ * State a call reads and leaves (lines of lib/src/phy/sync/):
+ *   pss.conv_output_avg (pss.c:495-503): with 0 < ema_alpha < 1 the track's own row, avg = alpha |c|^2 + (1 - alpha) avg, kept; otherwise
+ *     |c|^2 overwrites it and nothing is kept. The maximum, the lobe search (peak_value) and corr_peak work on the averaged values.
+ *   cfo_cp_mean / cfo_cp_is_set (sync.c:660-676): the first estimate is the mean, later ones enter by SRSLTE_VEC_EMA with cfo_ema_alpha; the
+ *     frame is read rotated by the mean AFTER the update. cfo_cp is the mean, cfo_cp_inst this call's estimate.
+ *   cfo_pss_mean / cfo_pss_is_set (sync.c:704-726): the first estimate is the mean; later ones are averaged in only while
+ *     15000 |cfo_pss| < 7000. The SSS symbol is rotated by the mean (also in a call whose PSS stage did not run). cfo_pss is the mean.
+ *   M_norm_avg / M_ext_avg: srslte_sync_detect_cp's averages with the constant 0.1 (sync.c:468,479).
+ *   cp: detect_cp writes it (sync.c:813); the NEXT call's SSS position uses it. It starts as cfg.cp.
+ *   N_id_1, sf_idx, sss_corr, peak_value, frame_type: a call that does not write them leaves the previous values, and the row shows those -
+ *     an undetected SSS outside detect mode, a peak with no room for the SSS stage (ret 2), no peak (ret 0), and for peak_value threshold 0
+ *     (the found test then reads the kept value, as sync.c:702 does). They start as -1 (cell_id -1), 0, 0, 0 and FDD (TDD in frame mode 1).
+ *     item.N_id_1 >= 0 is srslte_sync_set_N_id_1 before the call: the known-cell branch, and the track's N_id_1 from then on.
+ *   sss_detected is cleared by every call; sss_available is written where the SSS stage runs and kept otherwise; m0 / m1 are this call's
+ *     (0 where no m0 / m1 search ran); nof_calls counts the calls since the track was made or reset with flag 4.
+ * Frame modes (sync.c:732-809). 0: FDD, as the stateless call. 1 (TDD): the SSS symbol at find_offset + peak_pos - 4 symbol_sz(cp) +
+ * cp_sz(cp) - the reference's expression, which neglects the slot's longer first CP - and sf_idx = srslte_sss_subframe + 1. 2 (detect, what
+ * srslte_sync_init leaves): both trials, FDD then TDD, each through sss_alg or the known-cell branch; sss_detected is the OR; FDD wins when
+ * sss_corr[0] > sss_corr[1], otherwise TDD; frame_type, sf_idx (+ 1 for TDD), sss_corr, m0 / m1 and N_id_1 are the winning trial's, whether
+ * or not it detected. The CP and PSS stages do not depend on the frame type. Two cases the reference leaves to uninitialised stack values
+ * are defined here: a trial whose symbol would start before the item's first sample (sss_idx < 0) does not run, sss_available = 0, its
+ * correlation counts as lower than any other so it cannot win, and its sss_corr_trial is NaN (only the TDD trial can lack room once ret is
+ * 1: in mode 1 nothing is written then, in mode 2 the FDD trial wins); and a winning m0 / m1 trial that detected nothing leaves the track's
+ * previous N_id_1 and cell_id.
+ * Reads: the TDD trial reads two symbols further back than the FDD one, never further on, and a trial with sss_idx < 0 reads nothing; so the
+ * window checks are those of srslte_hip_sync_find_batch and every read stays inside [0, in_stride) of its own item.
+ * One call holds at most one item per track. Calls on one tracks object queued back to back on one stream see each other's state in order;
+ * there is no host synchronisation and no allocation in a call, three launches (two without cfo_cp_enable). The calls' temporaries are the
+ * sync object's: tracked and stateless calls on one sync object belong on one stream. reset and copy_cfo are one launch each.
+ * Refused with SRSLTE_ERROR_INVALID_INPUTS before anything is queued, d_res and the state untouched: what srslte_hip_sync_find_batch refuses,
+ * n_tracks 0 or above 65535, frame_mode > 2, a negative cfo_ema_alpha, track >= n_tracks, a track named twice in one call, N_id_2 > 2 (one
+ * srslte_sync_t has one PSS object), reset flags > 7, and in copy_cfo an index out of range or a destination named twice.
+ * Not here: see the list above; cfg.tdd of srslte_hip_sync_cfg_t stays refused - the frame mode is a property of the tracks object. */
+typedef struct srslte_hip_sync_tracks_s srslte_hip_sync_tracks_t;
+typedef struct {
+  uint32_t n_tracks;
+  float    cfo_ema_alpha;     /* srslte_sync_set_cfo_ema_alpha; 0: the 0.1 of sync.c:34 */
+  uint32_t frame_mode;        /* 0 FDD (srslte_sync_set_frame_type FDD), 1 TDD, 2 detect */
+} srslte_hip_sync_tracks_cfg_t;
+typedef struct {
+  uint32_t track, N_id_2 /* 0..2 */, find_offset;
+  int32_t  N_id_1;            /* >= 0: known cell; < 0: the m0 / m1 search */
+} srslte_hip_sync_track_item_t;
+typedef struct {              /* 24 x 4 bytes; the first 16 words are srslte_hip_sync_res_t */
+  srslte_hip_sync_res_t r;
+  int32_t  frame_type;        /* 0 FDD, 1 TDD: q->frame_type after the call */
+  float    sss_corr_trial[2]; /* FDD, TDD trial of this call; NaN for a trial that did not run */
+  uint32_t nof_calls;         /* this one included */
+  float    cfo_cp_inst, cfo_pss_inst; /* this call's estimates before averaging; 0 for a stage that did not run */
+  float    M_norm_avg, M_ext_avg;
+} srslte_hip_sync_track_res_t;
+typedef struct {              /* the scalars of one track, 16 x 4 bytes */
+  float    cfo_cp_mean, cfo_pss_mean;
+  uint32_t cfo_cp_is_set, cfo_pss_is_set;
+  float    M_norm_avg, M_ext_avg, peak_value, sss_corr;
+  int32_t  cp, N_id_1, frame_type;
+  uint32_t sf_idx, sss_available, nof_calls;
+  float    cfo_cp_inst;       /* the CP stage's last estimate */
+  uint32_t reserved;
+} srslte_hip_sync_track_state_t;
+#define SRSLTE_HIP_SYNC_RESET_AVG 1u   /* srslte_sync_reset (sync.c:841-845): M_norm_avg, M_ext_avg and the PSS average to zero */
+#define SRSLTE_HIP_SYNC_RESET_CFO 2u   /* srslte_sync_cfo_reset (sync.c:346-352) */
+#define SRSLTE_HIP_SYNC_RESET_REST 4u  /* cp = cfg.cp, N_id_1, sf_idx, sss_corr, peak_value, sss_available, frame type, nof_calls as created */
+srslte_hip_sync_tracks_t* srslte_hip_sync_tracks_create(srslte_hip_sync_t* q, const srslte_hip_sync_tracks_cfg_t* cfg);
+void                      srslte_hip_sync_tracks_destroy(srslte_hip_sync_tracks_t* k);
+int srslte_hip_sync_track_batch(srslte_hip_sync_tracks_t* k, const void* d_in, size_t in_stride, const srslte_hip_sync_track_item_t* items, uint32_t n,
+                                srslte_hip_sync_track_res_t* d_res, void* stream);
+/* idx NULL: all tracks (n is ignored) */
+int srslte_hip_sync_tracks_reset(srslte_hip_sync_tracks_t* k, const uint32_t* idx, uint32_t n, uint32_t flags, void* stream);
+/* srslte_sync_copy_cfo (sync.c:354-360) from src's track src_idx[i] to dst's track dst_idx[i]: the two means, and both is_set flags cleared, so
+ * the destination's next estimate REPLACES the mean. dst and src may belong to different sync objects (queue both on one stream). */
+int srslte_hip_sync_tracks_copy_cfo(srslte_hip_sync_tracks_t* dst, const uint32_t* dst_idx, srslte_hip_sync_tracks_t* src, const uint32_t* src_idx,
+                                    uint32_t n, void* stream);
+/* TEST AND DIAGNOSTIC ENTRY: the scalars of one track to the host (synchronises the device) */
+int srslte_hip_sync_tracks_read(srslte_hip_sync_tracks_t* k, uint32_t track, srslte_hip_sync_track_state_t* h_state);
+/* host (no device needed): what create and a call with these items would refuse; and srslte_hip_cell_search_decide over tracked rows, with
+ * the frame type by get_cell's majority rule (ue_cell_search.c:216-242): FDD (0) when more than the integer half of the winning id's rows
+ * say FDD, else TDD (1) */
+int srslte_hip_sync_tracks_check(const srslte_hip_sync_cfg_t* cfg, const srslte_hip_sync_tracks_cfg_t* tracks_cfg, size_t in_stride,
+                                 const srslte_hip_sync_track_item_t* items, uint32_t n);
+int srslte_hip_cell_search_decide_ft(const srslte_hip_sync_track_res_t* found, uint32_t nof_found, srslte_hip_cell_search_result_t* out,
+                                     int32_t* frame_type);
 
 /* ------------------------------------------------------------------ Neighbour-cell measurement: CRS search, RSRP, RSRQ and CFO, FDD, normal CP
  * srslte_hip_meas_run_batch leaves, per (capture, candidate cell), what srslte_refsignal_dl_sync_run (lib/src/phy/sync/refsignal_dl_sync.c:

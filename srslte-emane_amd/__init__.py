@@ -2382,6 +2382,127 @@ class Sync:
             self.h = None
 
 
+# ---------------------------------------------------------------- UE synchronisation: tracks (phy_hip.h "UE synchronisation: tracks")
+FRAME_FDD, FRAME_TDD, FRAME_DETECT = 0, 1, 2
+SYNC_RESET_AVG, SYNC_RESET_CFO, SYNC_RESET_REST, SYNC_RESET_ALL = 1, 2, 4, 7
+
+
+class SyncTracksCfg(C.Structure):
+    """srslte_hip_sync_tracks_cfg_t."""
+    _fields_ = [("n_tracks", C.c_uint32), ("cfo_ema_alpha", C.c_float), ("frame_mode", C.c_uint32)]
+
+
+class SyncTrackItem(C.Structure):
+    """srslte_hip_sync_track_item_t."""
+    _fields_ = [("track", C.c_uint32), ("N_id_2", C.c_uint32), ("find_offset", C.c_uint32), ("N_id_1", C.c_int32)]
+
+    @classmethod
+    def make(cls, track, N_id_2, find_offset=0, N_id_1=-1):
+        return cls(track, N_id_2, find_offset, N_id_1)
+
+
+class SyncTrackRes(C.Structure):
+    """srslte_hip_sync_track_res_t: r is the SyncRes; its fields also read as attributes of the row."""
+    _fields_ = [("r", SyncRes), ("frame_type", C.c_int32), ("sss_corr_trial", C.c_float * 2), ("nof_calls", C.c_uint32), ("cfo_cp_inst", C.c_float),
+                ("cfo_pss_inst", C.c_float), ("M_norm_avg", C.c_float), ("M_ext_avg", C.c_float)]
+
+    def __getattr__(self, k):
+        if k in _SYNC_RES_FIELDS:
+            return getattr(self.r, k)
+        raise AttributeError(k)
+
+
+_SYNC_RES_FIELDS = frozenset(k for k, _ in SyncRes._fields_)
+
+
+class SyncTrackState(C.Structure):
+    """srslte_hip_sync_track_state_t."""
+    _fields_ = [("cfo_cp_mean", C.c_float), ("cfo_pss_mean", C.c_float), ("cfo_cp_is_set", C.c_uint32), ("cfo_pss_is_set", C.c_uint32),
+                ("M_norm_avg", C.c_float), ("M_ext_avg", C.c_float), ("peak_value", C.c_float), ("sss_corr", C.c_float), ("cp", C.c_int32),
+                ("N_id_1", C.c_int32), ("frame_type", C.c_int32), ("sf_idx", C.c_uint32), ("sss_available", C.c_uint32), ("nof_calls", C.c_uint32),
+                ("cfo_cp_inst", C.c_float), ("reserved", C.c_uint32)]
+
+
+def _bind_sync_tracks(L):
+    vp, u32 = C.c_void_p, C.c_uint32
+    _bind_sync(L)
+    L.srslte_hip_sync_tracks_create.restype = vp
+    L.srslte_hip_sync_tracks_create.argtypes = [vp, C.POINTER(SyncTracksCfg)]
+    L.srslte_hip_sync_tracks_destroy.argtypes = [vp]
+    L.srslte_hip_sync_track_batch.argtypes = [vp, vp, C.c_size_t, vp, u32, vp, vp]
+    L.srslte_hip_sync_tracks_reset.argtypes = [vp, vp, u32, u32, vp]
+    L.srslte_hip_sync_tracks_copy_cfo.argtypes = [vp, vp, vp, vp, u32, vp]
+    L.srslte_hip_sync_tracks_read.argtypes = [vp, u32, C.POINTER(SyncTrackState)]
+    L.srslte_hip_sync_tracks_check.argtypes = [C.POINTER(SyncCfg), C.POINTER(SyncTracksCfg), C.c_size_t, vp, u32]
+    L.srslte_hip_cell_search_decide_ft.argtypes = [vp, u32, C.POINTER(CellSearchResult), C.POINTER(C.c_int32)]
+    return L
+
+
+def sync_tracks_check(cfg, tracks_cfg, in_stride, items):
+    """What srslte_hip_sync_tracks_create and a tracked call with these items would answer, without a device."""
+    arr = (SyncTrackItem * max(1, len(items)))(*items)
+    return _bind_sync_tracks(lib()).srslte_hip_sync_tracks_check(C.byref(cfg), C.byref(tracks_cfg), in_stride, arr, len(items))
+
+
+def cell_search_decide_ft(rows):
+    """srslte_hip_cell_search_decide_ft (host): (number of frames that counted, CellSearchResult, frame type)."""
+    arr = (SyncTrackRes * max(1, len(rows)))(*rows)
+    out, ft = CellSearchResult(), C.c_int32(0)
+    return _bind_sync_tracks(lib()).srslte_hip_cell_search_decide_ft(arr, len(rows), C.byref(out), C.byref(ft)), out, ft.value
+
+
+def _u32_list(idx):
+    return None if idx is None else (C.c_uint32 * max(1, len(idx)))(*idx)
+
+
+class SyncTracks:
+    """The state of n_tracks srslte_sync_t on the device, over one Sync object's configuration: one srslte_sync_find per item and call."""
+
+    def __init__(self, sync_obj, n_tracks, cfo_ema_alpha=0.0, frame_mode=FRAME_FDD):
+        L = _bind_sync_tracks(lib())
+        self.sync, self.cfg = sync_obj, SyncTracksCfg(n_tracks, cfo_ema_alpha, frame_mode)
+        self.h = L.srslte_hip_sync_tracks_create(sync_obj.h, C.byref(self.cfg))
+        if not self.h:
+            raise RuntimeError("srslte_hip_sync_tracks_create failed")
+
+    def track_device(self, d_in, in_stride, items, d_res, stream=None):
+        arr = (SyncTrackItem * max(1, len(items)))(*items)
+        return lib().srslte_hip_sync_track_batch(self.h, d_in, in_stride, arr, len(items), d_res, stream)
+
+    @staticmethod
+    def read_rows(d_res, rows):
+        out = (SyncTrackRes * max(1, rows))()
+        _check(lib().srslte_hip_memcpy_d2h(C.addressof(out), d_res.ptr, C.sizeof(SyncTrackRes) * max(1, rows)), "memcpy_d2h")
+        return list(out)[:rows]
+
+    def track(self, x, items):
+        """x [n][in_stride] complex64, item i on row i -> (rc, [SyncTrackRes] or None)."""
+        a = np.ascontiguousarray(x, np.complex64)
+        a = a.reshape(1, -1) if a.ndim == 1 else a
+        din, dres = DevBuf.from_host(a), DevBuf(C.sizeof(SyncTrackRes) * max(1, len(items)))
+        rc = self.track_device(din.ptr, a.shape[1], items, dres.ptr)
+        if rc != SRSLTE_SUCCESS:
+            return rc, None
+        sync()
+        return rc, self.read_rows(dres, len(items))
+
+    def reset(self, idx=None, flags=SYNC_RESET_ALL, stream=None):
+        return lib().srslte_hip_sync_tracks_reset(self.h, _u32_list(idx), 0 if idx is None else len(idx), flags, stream)
+
+    def copy_cfo(self, dst_idx, src, src_idx, stream=None):
+        return lib().srslte_hip_sync_tracks_copy_cfo(self.h, _u32_list(dst_idx), src.h, _u32_list(src_idx), len(dst_idx), stream)
+
+    def state(self, track):
+        out = SyncTrackState()
+        _check(lib().srslte_hip_sync_tracks_read(self.h, track, C.byref(out)), "sync_tracks_read")
+        return out
+
+    def free(self):
+        if self.h:
+            lib().srslte_hip_sync_tracks_destroy(self.h)
+            self.h = None
+
+
 # ---------------------------------------------------------------- neighbour-cell measurement (phy_hip.h "Neighbour-cell measurement")
 class MeasCfg(C.Structure):
     """srslte_hip_meas_cfg_t."""

@@ -147,6 +147,7 @@ int  sync_bin_freq(int j);
 void sync_m0m1(uint32_t N_id_1, uint32_t* m0, uint32_t* m1);
 bool sync_fft_size_valid(uint32_t N);
 bool sync_cfg_valid(const srslte_hip_sync_cfg_t* c);
+bool sync_tracks_cfg_valid(const srslte_hip_sync_tracks_cfg_t* c);
 // sync_host.cpp: the 62 PSS values of srslte_pss_generate (pss.c:348-376) for N_id_2 = v
 void sync_pss_seq(int v, cf32* pss);
 // chest.hip: the CRS values r_l,ns(m) of a cell (refsignal_dl.c:66-116; 36.211 6.10.1.1): [10][4][2 nof_prb] for ports 0 and 1 (symbols 0 and

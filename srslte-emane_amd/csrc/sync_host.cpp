@@ -122,6 +122,11 @@ bool sync_cfg_valid(const srslte_hip_sync_cfg_t* c)
   return true;
 }
 
+bool sync_tracks_cfg_valid(const srslte_hip_sync_tracks_cfg_t* c)
+{
+  return c && c->n_tracks > 0 && c->n_tracks <= 65535 && c->frame_mode <= 2 && c->cfo_ema_alpha >= 0.f; // a launch's grid holds 65535 tracks
+}
+
 extern "C" {
 
 int srslte_hip_sync_check(const srslte_hip_sync_cfg_t* c, size_t in_stride, const srslte_hip_sync_item_t* items, uint32_t n)
@@ -137,6 +142,24 @@ int srslte_hip_sync_check(const srslte_hip_sync_cfg_t* c, size_t in_stride, cons
     if ((uint64_t)it.find_offset + c->max_offset > c->frame_size) return SRSLTE_ERROR_INVALID_INPUTS;
     const uint64_t reach = (uint64_t)it.find_offset + c->max_offset + N - (c->max_offset < N ? 0 : 2);
     if (reach > in_stride) return SRSLTE_ERROR_INVALID_INPUTS;
+  }
+  return SRSLTE_SUCCESS;
+}
+
+// The TDD trial reads the symbol two symbols before the FDD one's: further back, never further on, and a trial whose symbol would start before
+// the item's first sample does not run. So the window checks are those of the stateless call.
+int srslte_hip_sync_tracks_check(const srslte_hip_sync_cfg_t* c, const srslte_hip_sync_tracks_cfg_t* tc, size_t in_stride,
+                                 const srslte_hip_sync_track_item_t* items, uint32_t n)
+{
+  if (!sync_cfg_valid(c) || !sync_tracks_cfg_valid(tc) || (n && !items) || n > c->max_items || n > tc->n_tracks) return SRSLTE_ERROR_INVALID_INPUTS;
+  if (c->frame_size > in_stride) return SRSLTE_ERROR_INVALID_INPUTS;
+  std::vector<uint8_t> seen(tc->n_tracks, 0);
+  for (uint32_t i = 0; i < n; i++) {
+    const srslte_hip_sync_track_item_t& it = items[i];
+    if (it.track >= tc->n_tracks || seen[it.track] || it.N_id_2 > 2 || it.N_id_1 >= 168) return SRSLTE_ERROR_INVALID_INPUTS;
+    seen[it.track] = 1;
+    const srslte_hip_sync_item_t one = {it.N_id_2, it.find_offset, it.N_id_1};
+    if (int r = srslte_hip_sync_check(c, in_stride, &one, 1)) return r;
   }
   return SRSLTE_SUCCESS;
 }
@@ -176,6 +199,22 @@ int srslte_hip_cell_search_decide(const srslte_hip_sync_res_t* found, uint32_t n
   out->cfo        = 15000 * cand[n - 1]->cfo;
   out->nof_frames = n;
   return (int)n;
+}
+
+// the same over tracked rows, with the frame type by the rule of the CP (ue_cell_search.c:216-242)
+int srslte_hip_cell_search_decide_ft(const srslte_hip_sync_track_res_t* found, uint32_t nof_found, srslte_hip_cell_search_result_t* out, int32_t* frame_type)
+{
+  if (!out || !frame_type || (nof_found && !found)) return SRSLTE_ERROR_INVALID_INPUTS;
+  std::vector<srslte_hip_sync_res_t> rows(nof_found);
+  for (uint32_t i = 0; i < nof_found; i++) rows[i] = found[i].r;
+  *frame_type = 0;
+  const int n = srslte_hip_cell_search_decide(rows.data(), nof_found, out);
+  if (n <= 0) return n;
+  uint32_t times = 0, nof_fdd = 0;
+  for (uint32_t i = 0; i < nof_found; i++)
+    if (found[i].r.ret == 1 && found[i].r.cell_id == (int32_t)out->cell_id) times++, nof_fdd += found[i].frame_type == 0 ? 1 : 0;
+  *frame_type = nof_fdd > times / 2 ? 0 : 1;
+  return n;
 }
 
 } // extern "C"
