@@ -1316,7 +1316,7 @@ int      srslte_hip_srs_check(const srslte_hip_srs_cfg_t* cfg, uint32_t tti0, ui
  * with freq in cycles per sample); the phase is the fractional part of freq[b] i taken in double, so it is as exact at sample 150 000 as at
  * sample 0 (the reference's running phasor drifts). d_out == d_in is allowed; freq is a host array read before the call returns.
  * Not here: decimation, the integer-CFO stage, SSS equalisation from the PSS channel estimate, srslte_pss_sic, ue_sync's find / track state
- * machine, NB-IoT, and the single-call drop-in, whose sync directory remains the reference's over srslte_dft_*. TDD positions, frame-type
+ * machine, and the single-call drop-in (NB-IoT: see "NB-IoT synchronisation" below), whose sync directory remains the reference's over srslte_dft_*. TDD positions, frame-type
  * detection and the averages across calls are the tracked call's ("UE synchronisation: tracks" below); this call stays FDD and stateless. */
 typedef struct srslte_hip_sync_s srslte_hip_sync_t;
 typedef struct {
@@ -1536,6 +1536,137 @@ int srslte_hip_meas_check(const srslte_hip_meas_cfg_t* cfg, size_t in_stride, ui
 /* TEST AND DIAGNOSTIC ENTRY: the time-domain replicas of cell k of the last set_cells, [10][sf_len] cf32, to the host (synchronises the
  * device) */
 int srslte_hip_meas_replicas(srslte_hip_meas_t* q, uint32_t cell, void* h_seq);
+
+/* ------------------------------------------------------------------ NB-IoT synchronisation: NPSS / NSSS search and CFO, fft_size 128
+ * One object serves both signals of lib/src/phy/sync/{npss.c, nsss.c, sync_nbiot.c}. Item b of a call is the cf32 samples d_in[b in_stride ..
+ * b in_stride + in_stride). Both replicas have 1508 samples: 11 OFDM symbols of 128 samples with CP 9, and CP 10 for the fifth one.
+ * A replica symbol i with frequency values S[i][sc] is, for t < 128 + cp_i (npss.c:170-239, nsss.c:144-229),
+ *   h[s_i + t] = 1 / sqrt(128) sum_sc S[i][sc] exp(j 2 pi (f_sc + 1/2) (t - cp_i) / 128),   s_i = 137 i + (i > 4)
+ * - the mirrored inverse transform with set_dc(false), which maps buffer index k to frequency k - 64 (dft_fftw.c:249-260: no bin is skipped),
+ * so f_sc = sc - 6 for the 11 NPSS values at index (128 - 12) / 2 and f_sc = sc - 7 for the 12 NSSS values at index 57; the CP is the
+ * periodic continuation, and the half-subcarrier table (offset 412 = SRSLTE_NPSS_CORR_OFFSET into a subframe) restarts in every symbol.
+ * The NPSS replica carries the further factor 1 / 3, the NSSS one does not (nsss.c:213).
+ *
+ * srslte_hip_nbiot_npss_find_batch: one srslte_sync_nbiot_find (sync_nbiot.c:189-254) per item on the item's track. A track is a
+ * srslte_sync_nbiot_t's state on the device: conv_output_avg and mean_cfo.
+ *   CFO pre-correction: every sample the search reads is rotated by -mean_cfo / 128 cycles per sample, index 0 = the item's first sample, the
+ *     phase exact at every index (as srslte_hip_cfo_correct_batch); no corrected copy is written. (The reference's srslte_vec_apply_cfo runs a
+ *     float phasor that drifts along the frame, and corrects frame_size samples from the item's start, so with find_offset > 0 the tail of
+ *     its window is whatever its buffer held before; here every sample of the window is the item's own, rotated.)
+ *   Correlation, frame_size >= 128 (npss.c:257-264, convolution.c:31-63,130-136): c[n] = sum_k x[(n + k) mod L] conj(h[k]), L = frame_size +
+ *     1508, x the frame_size samples from find_offset on and zero from frame_size on - the two 1 / sqrt(L) and the unnormalised inverse
+ *     cancel. srslte_corr_fft_cc_run_opt returns L - 1 as conv_output_len, and npss.c:273-288 works on conv_output_len - 1 values: nout = L - 2
+ *     lags enter the average and the maximum; lags frame_size .. L - 3 are the partial overlaps before the frame.
+ *     frame_size < 128 (npss.c:266-269): c[i] = sum_{t<128} h[t] x[i + t], NOT conjugated, conv_output_len = frame_size, nout = frame_size - 1.
+ *     The reference reads these samples from a buffer it corrected only up to frame_size; here they are the item's samples, rotated.
+ *   |c|^2; with 0 < npss_ema_alpha < 1 avg = alpha |c|^2 + (1 - alpha) avg over the nout values (npss.c:278-285), otherwise avg = |c|^2.
+ *   peak_pos = the first maximum of avg; corr_peak = avg[peak_pos]; peak_value = the peak-to-sidelobe ratio of npss.c:301-343 as it walks:
+ *     the right walk tests avg[pl_ub + 1] before pl_ub < conv_output_len, so it reads up to index conv_output_len + 1 of a buffer whose
+ *     entries from nout on are zero and may end at conv_output_len; the left walk stops at 1; an empty side-lobe range gives index pl_ub
+ *     on the right and index 0 on the left (srslte_vec_max_fi of length 0). ret = 1 when peak_value >= threshold, else 0.
+ *   CFO stage (cfo_enable; sync_nbiot.c:224-242, :257-265): entered only when peak_pos + 548 + 823 + 128 < frame_size (SRSLTE_NPSS_CFO_OFFSET,
+ *     SRSLTE_NPSS_CFO_NUM_SAMPS). It reads the UNCORRECTED item from index peak_pos + 548 - not offset by find_offset, as the reference
+ *     indexes it -, the first 823 samples multiplied by the second half of the half-subcarrier table on the fly (the reference overwrites
+ *     its input, the device leaves it alone; samples from 823 on are read as they are); srslte_cp_synch (cp.c:61-77) over min(max_offset,
+ *     128) offsets, 6 symbols of CP 9, the first one sample longer; cfo = -arg(corr[first argmax |corr|^2]) / 2 pi, then mean_cfo = alpha
+ *     cfo + (1 - alpha) mean_cfo with cfo_ema_alpha. The stage's furthest read is peak_pos + 548 + 127 + 822 < frame_size.
+ *   Row: ret, peak_pos, peak_value, corr_peak, cfo (this call's estimate; NaN when the stage did not run), mean_cfo after the call.
+ *   A track may be named once per call. Calls queued on one stream apply in order. The candidate test of sync_nbiot.c:200-203 is a caller's
+ *   loop over srslte_hip_nbiot_sync_tracks_set_cfo.
+ * srslte_hip_nbiot_nsss_find_batch: srslte_nsss_sync_find (nsss.c:231-281, :284-344) on the first 3840 samples of every item.
+ *   Per cell id the circular correlation over L = 5348 with that id's replica, |c| = sqrt(re^2 + im^2) (srslte_vec_abs_cf: not squared), the
+ *   first maximum over L - 2 = 5346 lags (conv_output_len - 1, as above). cell_ids[b] in 0..503 runs that id; -1 runs all 504 and the first
+ *   maximum of the 504 peaks wins. found = peak_value > nsss_threshold (strictly). cell_id in the row is the id that was run / that won, also
+ *   when found is 0 (the reference leaves its argument alone then); sfn_partial is 0: only theta_f = 0 is searched (nsss.c:192-196,:274).
+ *   Sequences: srslte_nsss_generate (nsss.c:348-377) in its float expression order, including its theta_f factor exp(-j 2 pi theta_f n) formed
+ *   from an integer theta_f in float. b_q(m) = (-1)^popcount(m & c_q), c_q = 0, 31, 63, 127: columns of the 128-point Hadamard matrix.
+ *   srslte_hip_nbiot_nsss_debug copies, for an item of the last call, peak_values [504] (entries of ids that did not run are 0) and the
+ *   |c| row [5346] of the row's cell_id.
+ * Device side (csrc/nbiot_sync.hip), the structure route: with Y_cls,sc[m] = 1 / sqrt(128) sum_t x[(m + t) mod L] exp(-j 2 pi (f_sc + 1/2) (t -
+ * cp_cls) / 128), t < 128 + cp_cls, c_id[n] = sum_{i,sc} conj(S_id[i][sc]) Y_cls(i),sc[n + s_i]: 24 sliding correlations of 137 / 138 taps per
+ * item, then a [504 x 132] x [132 x lags] complex product in fp32 FMAs on the VALU, 64 ids x 64 lags per workgroup, the table [132][504] and
+ * Y streamed through LDS a symbol (12 rows) at a time; only each tile's (maximum, first index) is written. The NPSS has one shared 11-value
+ * symbol and 11 signs: one sliding correlation per CP class, then c[n] = sum_i sign_i W_cls(i)[n + s_i].
+ *   npss_find_batch: descriptor copy + 3 launches (slide, combine + average + tile maxima, decide + CFO); 2 for frame_size < 128.
+ *   nsss_find_batch: descriptor copy + 3 launches (slide, product + tile maxima, decide + debug row). Independent of n and of 504.
+ *   tracks_reset, tracks_set_cfo: one launch each. No host synchronisation in any of them; d_res may be device-visible pinned host memory.
+ *   No kernel uses scratch memory or spills. Static LDS per workgroup: at most 12 288 bytes (the product kernel: 2 x 12 x 64 cf32; the slide
+ *   kernels 4 256; the others at most 4 KB). Temporaries per item: 24 x 6912 cf32 (NSSS), 2 x (L + 1369) cf32 (NPSS).
+ * srslte_hip_nbiot_sync_create returns NULL, and the calls and checks return SRSLTE_ERROR_INVALID_INPUTS before anything is queued (result
+ * rows and tracks untouched), for: fft_size != 128 (the reference hard-codes SRSLTE_NBIOT_FFT_SIZE in the CP lengths, k = 57 and the offsets);
+ * frame_size 0 or above 307 200 (srslte_sync_nbiot_resize's bound; 32-bit indices); max_items 0 or above 8191 (eight product rows per item,
+ * 65535 per launch); n_tracks 0 or above 65535; negative thresholds or alphas; and per call: null pointers, n > max_items, track >= n_tracks,
+ * a track named twice, find_offset + frame_size (+ 127 for frame_size < 128) > in_stride or beyond 32 bits - which also keeps the CFO stage inside the item -, a
+ * cell id outside -1..503, in_stride < 3840 for the NSSS. Every read stays inside [0, in_stride) of its own item.
+ * Not here: srslte_ue_sync_nbiot's state machine, the theta_f != 0 hypotheses (the reference searches none), fft_size != 128, decimation,
+ * the NSSS peak-to-sidelobe variant (compiled out in the reference), and the single-call drop-in, whose npss.c / nsss.c / sync_nbiot.c remain
+ * the reference's over srslte_dft_*. */
+#define SRSLTE_HIP_NBIOT_REPLICA_LEN 1508
+#define SRSLTE_HIP_NBIOT_NSSS_IN_LEN 3840  /* SRSLTE_NSSS_NUM_SF_DETECT x 1920 */
+#define SRSLTE_HIP_NBIOT_NSSS_NOUT 5346    /* 3840 + 1508 - 2 */
+#define SRSLTE_HIP_NBIOT_NUM_PCI 504
+typedef struct srslte_hip_nbiot_sync_s srslte_hip_nbiot_sync_t;
+typedef struct {
+  uint32_t fft_size;          /* 128 */
+  uint32_t frame_size;        /* what srslte_sync_nbiot_init passes to srslte_npss_synch_init */
+  uint32_t max_offset;        /* the CFO stage's srslte_cp_synch offsets (at most 128 count) */
+  uint32_t max_items;         /* items per call */
+  uint32_t n_tracks;
+  float    threshold;         /* on the NPSS peak-to-sidelobe ratio; 0: 5.0 */
+  float    nsss_threshold;    /* 0: 2.0 */
+  float    npss_ema_alpha;    /* 0: 0.2; 1: no averaging */
+  float    cfo_ema_alpha;     /* 0: 0.1 */
+  uint32_t cfo_enable;        /* srslte_sync_nbiot_set_cfo_enable */
+} srslte_hip_nbiot_sync_cfg_t;
+typedef struct {
+  uint32_t track, find_offset;
+} srslte_hip_nbiot_npss_item_t;
+typedef struct {              /* 8 x 4 bytes */
+  int32_t  ret;               /* 1 FOUND, 0 NOFOUND */
+  uint32_t peak_pos;
+  float    peak_value;        /* the peak-to-sidelobe ratio */
+  float    corr_peak;         /* the average at the peak */
+  float    cfo;               /* this call's estimate in subcarriers; NaN when the CFO stage did not run */
+  float    mean_cfo;          /* after the call */
+  uint32_t reserved[2];
+} srslte_hip_nbiot_npss_res_t;
+typedef struct {              /* 8 x 4 bytes */
+  int32_t  found;
+  int32_t  cell_id;
+  float    peak_value;
+  uint32_t peak_pos;
+  uint32_t sfn_partial;       /* 0 */
+  uint32_t reserved[3];
+} srslte_hip_nbiot_nsss_res_t;
+srslte_hip_nbiot_sync_t* srslte_hip_nbiot_sync_create(const srslte_hip_nbiot_sync_cfg_t* cfg);
+void                     srslte_hip_nbiot_sync_destroy(srslte_hip_nbiot_sync_t* q);
+/* srslte_npss_synch_reset plus mean_cfo = 0 for tracks first .. first + n - 1 */
+int srslte_hip_nbiot_sync_tracks_reset(srslte_hip_nbiot_sync_t* q, uint32_t first, uint32_t n, void* stream);
+/* mean_cfo of tracks first .. first + n - 1 = cfo[0 .. n) (srslte_sync_nbiot_set_cfo); cfo is a host array read before the call returns */
+int srslte_hip_nbiot_sync_tracks_set_cfo(srslte_hip_nbiot_sync_t* q, uint32_t first, uint32_t n, const float* cfo, void* stream);
+/* TEST AND DIAGNOSTIC ENTRY: mean_cfo and, when h_avg is not NULL, the nout averaged values of one track to the host (synchronises the device) */
+int srslte_hip_nbiot_sync_tracks_read(srslte_hip_nbiot_sync_t* q, uint32_t track, float* h_mean_cfo, float* h_avg);
+/* in_stride in cf32 samples per item; d_res [n] */
+int srslte_hip_nbiot_npss_find_batch(srslte_hip_nbiot_sync_t* q, const void* d_in, size_t in_stride, const srslte_hip_nbiot_npss_item_t* items, uint32_t n,
+                                     srslte_hip_nbiot_npss_res_t* d_res, void* stream);
+int srslte_hip_nbiot_nsss_find_batch(srslte_hip_nbiot_sync_t* q, const void* d_in, size_t in_stride, const int32_t* cell_ids, uint32_t n,
+                                     srslte_hip_nbiot_nsss_res_t* d_res, void* stream);
+/* TEST AND DIAGNOSTIC ENTRY: of item b of the last NSSS call (synchronises the device); either pointer may be NULL */
+int srslte_hip_nbiot_nsss_debug(srslte_hip_nbiot_sync_t* q, uint32_t item, float* h_peak_values, float* h_abs_row);
+/* host (no device needed). The checks: what create (items NULL, n 0) and a call with these items / ids would refuse. nout of a frame_size.
+ * The sequences: srslte_npss_generate into out [121] cf32, srslte_nsss_generate into out [528] cf32 (nothing written, error, for an id above
+ * 503); the two time-domain replicas, [1508] cf32 each. The RE indices srslte_npss_put_subframe (npss.c:425-436) and srslte_nsss_put_subframe
+ * (nsss.c:379-398) write in a subframe grid [14][12 nof_prb]: re [121] resp. re [132], entry i receives value i of the NPSS resp. value
+ * *first + i of the 528 NSSS values (first = 132 theta_f, theta_f = floor(33 / 132 (nf / 2)) % 4). */
+int      srslte_hip_nbiot_sync_check(const srslte_hip_nbiot_sync_cfg_t* cfg, size_t in_stride, const srslte_hip_nbiot_npss_item_t* items, uint32_t n);
+int      srslte_hip_nbiot_nsss_check(const srslte_hip_nbiot_sync_cfg_t* cfg, size_t in_stride, const int32_t* cell_ids, uint32_t n);
+uint32_t srslte_hip_nbiot_npss_nout(uint32_t frame_size);
+int      srslte_hip_nbiot_npss_generate(void* out);
+int      srslte_hip_nbiot_nsss_generate(void* out, uint32_t cell_id);
+int      srslte_hip_nbiot_npss_replica(void* out);
+int      srslte_hip_nbiot_nsss_replica(void* out, uint32_t cell_id);
+int      srslte_hip_nbiot_npss_re(uint32_t nof_prb, uint32_t prb_offset, uint32_t* re);
+int      srslte_hip_nbiot_nsss_re(uint32_t nof_prb, uint32_t prb_offset, int nf, uint32_t* re, uint32_t* first);
 
 #ifdef __cplusplus
 }

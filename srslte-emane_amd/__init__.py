@@ -144,6 +144,7 @@ def lib():
         _bind_srs(L)
         _bind_sync(L)
         _bind_meas(L)
+        _bind_nbiot(L)
         _lib = L
     return _lib
 
@@ -2588,4 +2589,189 @@ class Meas:
     def free(self):
         if self.h:
             lib().srslte_hip_meas_destroy(self.h)
+            self.h = None
+
+
+# ---------------------------------------------------------------- NB-IoT synchronisation (phy_hip.h "NB-IoT synchronisation")
+NBIOT_REPLICA_LEN, NBIOT_NSSS_IN_LEN, NBIOT_NSSS_NOUT, NBIOT_NUM_PCI = 1508, 3840, 5346, 504
+
+
+class NbiotSyncCfg(C.Structure):
+    """srslte_hip_nbiot_sync_cfg_t."""
+    _fields_ = [("fft_size", C.c_uint32), ("frame_size", C.c_uint32), ("max_offset", C.c_uint32), ("max_items", C.c_uint32), ("n_tracks", C.c_uint32),
+                ("threshold", C.c_float), ("nsss_threshold", C.c_float), ("npss_ema_alpha", C.c_float), ("cfo_ema_alpha", C.c_float),
+                ("cfo_enable", C.c_uint32)]
+
+
+class NbiotNpssItem(C.Structure):
+    """srslte_hip_nbiot_npss_item_t."""
+    _fields_ = [("track", C.c_uint32), ("find_offset", C.c_uint32)]
+
+
+class NbiotNpssRes(C.Structure):
+    """srslte_hip_nbiot_npss_res_t."""
+    _fields_ = [("ret", C.c_int32), ("peak_pos", C.c_uint32), ("peak_value", C.c_float), ("corr_peak", C.c_float), ("cfo", C.c_float),
+                ("mean_cfo", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+class NbiotNsssRes(C.Structure):
+    """srslte_hip_nbiot_nsss_res_t."""
+    _fields_ = [("found", C.c_int32), ("cell_id", C.c_int32), ("peak_value", C.c_float), ("peak_pos", C.c_uint32), ("sfn_partial", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+def _bind_nbiot(L):
+    vp, u32 = C.c_void_p, C.c_uint32
+    L.srslte_hip_nbiot_sync_create.restype = vp
+    L.srslte_hip_nbiot_sync_create.argtypes = [C.POINTER(NbiotSyncCfg)]
+    L.srslte_hip_nbiot_sync_destroy.argtypes = [vp]
+    L.srslte_hip_nbiot_sync_tracks_reset.argtypes = [vp, u32, u32, vp]
+    L.srslte_hip_nbiot_sync_tracks_set_cfo.argtypes = [vp, u32, u32, vp, vp]
+    L.srslte_hip_nbiot_sync_tracks_read.argtypes = [vp, u32, vp, vp]
+    L.srslte_hip_nbiot_npss_find_batch.argtypes = [vp, vp, C.c_size_t, vp, u32, vp, vp]
+    L.srslte_hip_nbiot_nsss_find_batch.argtypes = [vp, vp, C.c_size_t, vp, u32, vp, vp]
+    L.srslte_hip_nbiot_nsss_debug.argtypes = [vp, u32, vp, vp]
+    L.srslte_hip_nbiot_sync_check.argtypes = [C.POINTER(NbiotSyncCfg), C.c_size_t, vp, u32]
+    L.srslte_hip_nbiot_nsss_check.argtypes = [C.POINTER(NbiotSyncCfg), C.c_size_t, vp, u32]
+    L.srslte_hip_nbiot_npss_nout.restype = u32
+    L.srslte_hip_nbiot_npss_nout.argtypes = [u32]
+    L.srslte_hip_nbiot_npss_generate.argtypes = [vp]
+    L.srslte_hip_nbiot_nsss_generate.argtypes = [vp, u32]
+    L.srslte_hip_nbiot_npss_replica.argtypes = [vp]
+    L.srslte_hip_nbiot_nsss_replica.argtypes = [vp, u32]
+    L.srslte_hip_nbiot_npss_re.argtypes = [u32, u32, vp]
+    L.srslte_hip_nbiot_nsss_re.argtypes = [u32, u32, C.c_int, vp, C.POINTER(u32)]
+    return L
+
+
+def nbiot_sync_cfg(frame_size, max_offset=128, max_items=1, n_tracks=1, threshold=0.0, nsss_threshold=0.0, npss_ema_alpha=0.0, cfo_ema_alpha=0.0,
+                   cfo_enable=True, fft_size=128):
+    """The zeros select the defaults of srslte_sync_nbiot_init / srslte_npss_synch_init / srslte_nsss_synch_init."""
+    return NbiotSyncCfg(fft_size, frame_size, max_offset, max_items, n_tracks, threshold, nsss_threshold, npss_ema_alpha, cfo_ema_alpha,
+                        int(bool(cfo_enable)))
+
+
+def nbiot_sync_check(cfg, in_stride, items):
+    """What srslte_hip_nbiot_sync_create and an NPSS call with these items would answer, without a device."""
+    arr = (NbiotNpssItem * max(1, len(items)))(*items)
+    return _bind_nbiot(lib()).srslte_hip_nbiot_sync_check(C.byref(cfg), in_stride, arr, len(items))
+
+
+def nbiot_nsss_check(cfg, in_stride, cell_ids):
+    ids = np.ascontiguousarray(cell_ids, np.int32)
+    return _bind_nbiot(lib()).srslte_hip_nbiot_nsss_check(C.byref(cfg), in_stride, ids.ctypes.data, ids.size)
+
+
+def nbiot_npss_nout(frame_size):
+    return _bind_nbiot(lib()).srslte_hip_nbiot_npss_nout(frame_size)
+
+
+def nbiot_npss_generate():
+    out = np.zeros(121, np.complex64)
+    _check(_bind_nbiot(lib()).srslte_hip_nbiot_npss_generate(out.ctypes.data), "nbiot_npss_generate")
+    return out
+
+
+def nbiot_nsss_generate(cell_id):
+    out = np.zeros(528, np.complex64)
+    _check(_bind_nbiot(lib()).srslte_hip_nbiot_nsss_generate(out.ctypes.data, cell_id), "nbiot_nsss_generate")
+    return out
+
+
+def nbiot_npss_replica():
+    out = np.zeros(NBIOT_REPLICA_LEN, np.complex64)
+    _check(_bind_nbiot(lib()).srslte_hip_nbiot_npss_replica(out.ctypes.data), "nbiot_npss_replica")
+    return out
+
+
+def nbiot_nsss_replica(cell_id):
+    out = np.zeros(NBIOT_REPLICA_LEN, np.complex64)
+    _check(_bind_nbiot(lib()).srslte_hip_nbiot_nsss_replica(out.ctypes.data, cell_id), "nbiot_nsss_replica")
+    return out
+
+
+def nbiot_npss_re(nof_prb, prb_offset=0):
+    """RE indices of srslte_npss_put_subframe in a subframe grid [14][12 nof_prb]: entry i receives NPSS value i."""
+    re = np.zeros(121, np.uint32)
+    _check(_bind_nbiot(lib()).srslte_hip_nbiot_npss_re(nof_prb, prb_offset, re.ctypes.data), "nbiot_npss_re")
+    return re
+
+
+def nbiot_nsss_re(nof_prb, prb_offset=0, nf=0):
+    """(RE indices of srslte_nsss_put_subframe, index of the first of the 528 NSSS values frame nf carries)."""
+    re, first = np.zeros(132, np.uint32), C.c_uint32(0)
+    _check(_bind_nbiot(lib()).srslte_hip_nbiot_nsss_re(nof_prb, prb_offset, nf, re.ctypes.data, C.byref(first)), "nbiot_nsss_re")
+    return re, first.value
+
+
+class NbiotSync:
+    """Batched NB-IoT synchronisation: srslte_sync_nbiot_find per item on device-resident tracks, and srslte_nsss_sync_find per capture."""
+
+    def __init__(self, frame_size, **kw):
+        L = _bind_nbiot(lib())
+        self.cfg = nbiot_sync_cfg(frame_size, **kw)
+        self.h = L.srslte_hip_nbiot_sync_create(C.byref(self.cfg))
+        if not self.h:
+            raise RuntimeError("srslte_hip_nbiot_sync_create failed")
+        self.nout = L.srslte_hip_nbiot_npss_nout(frame_size)
+
+    def npss_device(self, d_in, in_stride, items, d_res, stream=None):
+        arr = (NbiotNpssItem * max(1, len(items)))(*items)
+        return lib().srslte_hip_nbiot_npss_find_batch(self.h, d_in, in_stride, arr, len(items), d_res, stream)
+
+    def nsss_device(self, d_in, in_stride, cell_ids, d_res, stream=None):
+        ids = np.ascontiguousarray(cell_ids, np.int32)
+        return lib().srslte_hip_nbiot_nsss_find_batch(self.h, d_in, in_stride, ids.ctypes.data, ids.size, d_res, stream)
+
+    @staticmethod
+    def read(d_res, rows, cls):
+        out = (cls * max(1, rows))()
+        _check(lib().srslte_hip_memcpy_d2h(C.addressof(out), d_res.ptr, C.sizeof(cls) * max(1, rows)), "memcpy_d2h")
+        return list(out)[:rows]
+
+    def npss_find(self, x, items):
+        """x [n][in_stride] complex64, items [(track, find_offset)] -> (rc, [NbiotNpssRes] or None)."""
+        a = np.ascontiguousarray(x, np.complex64)
+        a = a.reshape(1, -1) if a.ndim == 1 else a
+        its = [NbiotNpssItem(*it) for it in items]
+        din, dres = DevBuf.from_host(a), DevBuf(C.sizeof(NbiotNpssRes) * max(1, len(its)))
+        rc = self.npss_device(din.ptr, a.shape[1], its, dres.ptr)
+        if rc != SRSLTE_SUCCESS:
+            return rc, None
+        sync()
+        return rc, self.read(dres, len(its), NbiotNpssRes)
+
+    def nsss_find(self, x, cell_ids):
+        """x [n][in_stride] complex64, cell_ids [n] (-1: all 504) -> (rc, [NbiotNsssRes] or None)."""
+        a = np.ascontiguousarray(x, np.complex64)
+        a = a.reshape(1, -1) if a.ndim == 1 else a
+        din, dres = DevBuf.from_host(a), DevBuf(C.sizeof(NbiotNsssRes) * max(1, len(cell_ids)))
+        rc = self.nsss_device(din.ptr, a.shape[1], cell_ids, dres.ptr)
+        if rc != SRSLTE_SUCCESS:
+            return rc, None
+        sync()
+        return rc, self.read(dres, len(cell_ids), NbiotNsssRes)
+
+    def nsss_debug(self, item):
+        """(peak_values [504], the |c| row [5346] of the row's cell id) of an item of the last NSSS call."""
+        pv, row = np.zeros(NBIOT_NUM_PCI, np.float32), np.zeros(NBIOT_NSSS_NOUT, np.float32)
+        _check(lib().srslte_hip_nbiot_nsss_debug(self.h, item, pv.ctypes.data, row.ctypes.data), "nbiot_nsss_debug")
+        return pv, row
+
+    def tracks_reset(self, first=0, n=None, stream=None):
+        return lib().srslte_hip_nbiot_sync_tracks_reset(self.h, first, self.cfg.n_tracks - first if n is None else n, stream)
+
+    def tracks_set_cfo(self, first, cfo, stream=None):
+        v = np.ascontiguousarray(cfo, np.float32).reshape(-1)
+        return lib().srslte_hip_nbiot_sync_tracks_set_cfo(self.h, first, v.size, v.ctypes.data, stream)
+
+    def track(self, k):
+        """(mean_cfo, the averaged |c|^2 [nout]) of track k."""
+        m, avg = np.zeros(1, np.float32), np.zeros(max(1, self.nout), np.float32)
+        _check(lib().srslte_hip_nbiot_sync_tracks_read(self.h, k, m.ctypes.data, avg.ctypes.data), "nbiot_sync_tracks_read")
+        return float(m[0]), avg[:self.nout]
+
+    def free(self):
+        if self.h:
+            lib().srslte_hip_nbiot_sync_destroy(self.h)
             self.h = None

@@ -165,3 +165,11 @@ bool     meas_cfg_valid(const srslte_hip_meas_cfg_t* c);
 uint32_t meas_symbol_sz(const srslte_hip_meas_cfg_t* c);
 void     meas_twiddles(uint32_t N, std::vector<cf32>& tw2);
 void     meas_sss_seq(uint32_t cell_id, float* s0, float* s5);
+// nbiot_sync_host.cpp: the tables nbiot_sync.hip uploads, formed in double on the host - the NPSS taps of the two CP classes [2][138]
+// (conjugated, 1 / 3 / sqrt(128)), the first 128 replica samples (the frame_size < 128 branch), the second half of the half-subcarrier table
+// [823], the NSSS slide twiddles [2][12][138] and the conjugated NSSS values of theta_f = 0 [132][504] - and the check of a configuration
+struct NbiotTables {
+  std::vector<cf32> npss_taps, npss_head, shift2, nsss_tw, nsss_seq;
+};
+void nbiot_tables(NbiotTables& t);
+bool nbiot_cfg_valid(const srslte_hip_nbiot_sync_cfg_t* c);
