@@ -175,11 +175,30 @@ def detect_cp(x, N, tot):
     return cp, abs(M[0] - M[1]) / max(abs(M[0]), abs(M[1]), 1e-30)
 
 
-def find_one(x, cfg, N_id_2, find_offset=0, N_id_1=-1, force_peak=None):
+def exact_cfo(f, length):
+    """exp(j 2 pi f n), n < length."""
+    return np.exp(2j * np.pi * f * np.arange(length))
+
+
+def reference_cfo(f, length, lanes=8):
+    """What srslte_vec_apply_cfo (vector_simd.c:1556-1604) multiplies by in the reference build of oracle/ref.mk (AVX2: 8 complex lanes): a
+    float32 phasor per lane, started at cexpf(j 2 pi f k) and multiplied once per vector by cexpf(j 2 pi f lanes). The step is rounded to
+    float32 once, so its modulus and its angle are off by a few 1e-8 and the factors drift from the exact ones in proportion to the
+    sample index: 6e-5 of peak_value over the 9600 samples of a 128-point window of 5 ms, 1.7e-4 over the 28 800 of a 384-point one. The
+    rounding of the single products, which has no preferred direction, is left out."""
+    f32 = np.float32
+    w = f32(2.0) * f32(np.pi) * f32(f)
+    cexpf = lambda a: np.cos(f32(a)).astype(f32).astype(float) + 1j * np.sin(f32(a)).astype(f32).astype(float)
+    n = np.arange(length)
+    return cexpf(w * np.arange(lanes, dtype=f32))[n % lanes] * complex(cexpf(w * f32(lanes))) ** (n // lanes)
+
+
+def find_one(x, cfg, N_id_2, find_offset=0, N_id_1=-1, force_peak=None, force_cp=None, frame_cfo=None):
     """x: the item's samples. cfg: a dict with the fields of srslte_hip_sync_cfg_t. -> dict with the fields of srslte_hip_sync_res_t, "margins"
     {stage: relative margin} of every decision taken, "cp_corr" and "avg" (the averaged |c|^2). force_peak: take this index as the maximum
     of the correlation (for a caller that has checked it to be one within its tolerance: at large fft_size the peak's neighbours are within
-    0.3 % of it) and go on from there."""
+    0.3 % of it) and go on from there. force_cp: the same for the maximum of the CP correlation, whose neighbours are as close at those sizes. frame_cfo(f, length): the factors that correct the frame by the CP-based CFO (sync.c:674), exact_cfo
+    unless given; reference_cfo is what the reference's own build multiplies by."""
     N, mo, fo = cfg["fft_size"], cfg["max_offset"], find_offset
     x = np.asarray(x, complex)
     mg = {}
@@ -188,9 +207,12 @@ def find_one(x, cfg, N_id_2, find_offset=0, N_id_1=-1, force_peak=None):
     if cfg["cfo_cp_enable"]:
         corr = cp_corr(x, N, mo, cfg["cfo_cp_nsymbols"])
         i, mg["cp_argmax"] = _top2(np.abs(corr) ** 2)
+        if force_cp is not None:
+            i = int(force_cp)
+            del mg["cp_argmax"]
         o["cp_corr"] = corr
         o["cfo_cp"] = float(-np.angle(corr[i]) / np.pi / 2)
-        x = x * np.exp(-2j * np.pi * o["cfo_cp"] / N * np.arange(x.size))
+        x = x * (frame_cfo or exact_cfo)(-o["cfo_cp"] / N, x.size)
     h = replica(N, N_id_2)
     if mo >= N:
         conv = np.convolve(x[fo:fo + mo], h)[:mo + N - 2]

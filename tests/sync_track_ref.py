@@ -81,9 +81,9 @@ class Track:
                 nid = int(sr.N_ID_1_TABLE[m1, m0 - 1])
         return nid >= 0, 0 if m1 > m0 else 5, nid if nid >= 0 else None, corr, m0, m1
 
-    def find(self, x, N_id_2, find_offset=0, N_id_1=-1, force_peak=None):
+    def find(self, x, N_id_2, find_offset=0, N_id_1=-1, force_peak=None, force_cp=None):
         """One srslte_sync_find on the item's samples x -> dict with the fields of srslte_hip_sync_track_res_t (those of srslte_hip_sync_res_t
-        flat), "margins", "avg" and "cp_corr". force_peak as in sync_ref.find_one."""
+        flat), "margins", "avg" and "cp_corr". force_peak and force_cp as in sync_ref.find_one."""
         cfg = self.cfg
         N, mo, fo = cfg["fft_size"], cfg["max_offset"], find_offset
         x = np.asarray(x, complex)
@@ -96,6 +96,9 @@ class Track:
         if cfg["cfo_cp_enable"]:
             corr = sr.cp_corr(x, N, mo, cfg["cfo_cp_nsymbols"])
             i, mg["cp_argmax"] = sr._top2(np.abs(corr) ** 2)
+            if force_cp is not None:
+                i = int(force_cp)
+                del mg["cp_argmax"]
             o["cp_corr"] = corr
             est = float(-np.angle(corr[i]) / np.pi / 2)
             self.cfo_cp_mean = _ema(est, self.cfo_cp_mean, self.cfo_alpha) if self.cfo_cp_is_set else est

@@ -1,8 +1,10 @@
 """PSS / SSS synchronisation on the device (srslte_hip_sync_find_batch, srslte_hip_cfo_correct_batch): the sync_test matrix against its
 construction, parity with the float64 restatement of tests/sync_ref.py and - where oracle/_ref/hip/libsrslte_upper.a exists - with the
 reference's own sync.c (tests/sync_dropin_driver.c, compiled here with gcc as tests/test_gpu_prach.py compiles its driver), the tracking
-branch at six transform sizes in guarded buffers, the CP stage alone, the CFO correction, the recorded captures, a transmit - impair -
-synchronise - decode-MIB chain, refusals and queued calls.
+branch at every accepted transform size in guarded buffers, the full-window search at 64, 192, 384, 768, 1024, 1536 and 2048, the switch
+between the two branches (max_offset = fft_size - 1, fft_size, fft_size + 1), the edges of the correlation kernel's 256-output tiles, the
+one-output window, the FOUND / FOUND_NOSPACE line, the CP stage alone, the CFO correction, the recorded captures, a transmit - impair -
+synchronise - decode-MIB chain, refusals and queued calls. 106 tests.
 
 Tolerances: T = max(1e-4, 4 fft_size 2^-24). A float output may differ from the restatement by max(T, 2 x the reference driver's own
 distance on the same item), relative to the output's scale (the figure itself for correlations and ratios, 1 subcarrier for CFOs). Discrete
@@ -10,7 +12,10 @@ outputs are compared on every item whose smallest deciding margin in the restate
 5 % of its items on that ground. One case is excused for peak_pos alone: where the correlation's runner-up within 10 T is a neighbour of the
 peak (at fft_size 1536 and 2048 it always is, the PSS being 12 and 16 times oversampled), the device's peak has to be within 10 T of the
 maximum, and all later stages are compared with the restatement continued from the device's position and with the driver where it chose the
-same position. The count of such rows is printed beside the count of rows left out."""
+same position. The maximum of the CP correlation has the same excuse (near_cp_index): where its runner-up within 10 T lies within 2
+positions, the device's index is the one within 10 T of the maximum at which the restatement's own estimate is within T of the device's
+cfo_cp - there has to be one - and every later stage is compared with the restatement continued from that index, and with the driver where
+its cfo is the one the restatement gives from there. The counts of both kinds of rows are printed beside the count of rows left out."""
 import ctypes as C
 import importlib
 import os
@@ -81,6 +86,21 @@ def _expand(items):
     return rows
 
 
+def near_cp_index(corr, cfo_cp_dev, T, key):
+    """The CP correlation's top two are within 10 T. Where they lie within 2 positions of each other (at oversampled sizes the maximum's
+    neighbours are that close, as the PSS peak's are) -> the index the device chose: the one among the positions within 10 T of the maximum
+    whose -arg(corr[i]) / 2 pi is within T of the device's cfo_cp, and there has to be one. The estimates at tied indices differ by far
+    more than T, so the later stages are compared with the restatement continued from that index. Far-apart ties (noise) -> None: the row
+    is left out like any other small margin."""
+    p2 = np.abs(corr) ** 2
+    i = int(np.argmax(p2))
+    if p2.size < 2 or abs(int(np.argmax(np.r_[p2[:i], -1.0, p2[i + 1:]])) - i) > 2:
+        return None
+    cand = [int(k) for k in np.flatnonzero(p2 >= (1 - 10 * T) * p2[i]) if abs(-np.angle(corr[k]) / 2 / np.pi - cfo_cp_dev) <= T]
+    assert cand, (key, "cfo_cp", cfo_cp_dev, "is the estimate at none of the positions within 10 T of the CP correlation's maximum", i)
+    return min(cand, key=lambda k: abs(-np.angle(corr[k]) / 2 / np.pi - cfo_cp_dev))
+
+
 def _parity(name, q, x, items, driver, max_left_out=0.05):
     """One device call on x [n][in_stride]; every row against the restatement and, where there is one, the reference driver."""
     c, N = q.cfg, q.cfg.fft_size
@@ -90,28 +110,36 @@ def _parity(name, q, x, items, driver, max_left_out=0.05):
     rows = _expand(items)
     assert len(got) == len(rows)
     ref_rows = driver(c, x, rows) if driver is not None and c.sss_threshold == 0 else None
-    cd, left_out, dist, near_ties, with_driver = _dict(c), 0, {}, 0, 0
+    cd, left_out, dist, near_ties, near_cps, with_driver = _dict(c), 0, {}, 0, 0, 0
+    off = N if c.max_offset < N else 0
     for r, (v, fo, id1, b) in enumerate(rows):
         w, g = sr.find_one(x[b], cd, v, fo, id1), got[r]
-        near_tie = False
+        near_tie, cp_i = False, None
+        if c.cfo_cp_enable and not w["margins"]["cp_argmax"] > 10 * T:
+            cp_i = near_cp_index(w["cp_corr"], g.cfo_cp, T, (name, r))
+            if cp_i is not None:
+                w = sr.find_one(x[b], cd, v, fo, id1, force_cp=cp_i)
+                near_cps += 1
         if not w["margins"]["peak"] > 10 * T:
             # the correlation's top two are within 10 T. Where they are neighbours (the PSS is 12 and 16 times oversampled at fft_size 1536 and
             # 2048: the peak's neighbours are always that close) only peak_pos is excused: the device's has to be within 10 T of the maximum, and
             # every later stage is compared with the restatement continued from there - and with the driver where it sits on the same position.
             # Far-apart ties (noise) are left out like any other small margin.
             a = w["avg"]
-            second = int(np.argmax(np.r_[a[:w["peak_pos"] - (N if c.max_offset < N else 0)], -1.0, a[w["peak_pos"] - (N if c.max_offset < N else 0) + 1:]]))
-            if abs(second - (w["peak_pos"] - (N if c.max_offset < N else 0))) <= 2:
+            second = int(np.argmax(np.r_[a[:w["peak_pos"] - off], -1.0, a[w["peak_pos"] - off + 1:]]))
+            if abs(second - (w["peak_pos"] - off)) <= 2:
                 near_tie = True
-                p_dev = int(g.peak_pos) - (N if c.max_offset < N else 0)
+                p_dev = int(g.peak_pos) - off
                 assert 0 <= p_dev < a.size and a[p_dev] >= (1 - 10 * T) * a.max(), (name, r, g.peak_pos, w["peak_pos"])
-                w = sr.find_one(x[b], cd, v, fo, id1, force_peak=p_dev)
+                w = sr.find_one(x[b], cd, v, fo, id1, force_peak=p_dev, force_cp=cp_i)
                 near_ties += 1
         margin = min(w["margins"].values()) if w["margins"] else 1.0
         if not margin > 10 * T:
             left_out += 1
             continue
-        with_ref = ref_rows is not None and (not near_tie or ref_rows[r].peak_pos == g.peak_pos)
+        # the driver follows where it sits on the device's peak and, beside a CP maximum, where its cfo is the one at the device's index
+        with_ref = ref_rows is not None and (not near_tie or ref_rows[r].peak_pos == g.peak_pos) and \
+            (cp_i is None or abs(ref_rows[r].cfo - w["cfo"]) <= T)
         with_driver += int(with_ref)
         for k in sr.DISCRETE:
             assert getattr(g, k) == w[k], (name, r, k, getattr(g, k), w[k], w["margins"])
@@ -129,9 +157,10 @@ def _parity(name, q, x, items, driver, max_left_out=0.05):
             else:
                 assert not np.isfinite(getattr(g, k)) or abs(getattr(g, k)) > 1e30, (name, r, k)
     LEFT_OUT[name] = (left_out, len(rows))
-    print("%s: %d of %d rows left out for a margin under 10 T, %d compared from the device's own position beside an oversampled peak, %d also "
-          "with the driver; reference driver's distances from the restatement: %s"
-          % (name, left_out, len(rows), near_ties, with_driver, {k: "%.2e" % v for k, v in dist.items()} if ref_rows is not None else "no driver"))
+    print("%s: %d of %d rows left out for a margin under 10 T, %d compared from the device's own position beside an oversampled peak, %d from the "
+          "device's own index beside a CP maximum, %d also with the driver; reference driver's distances from the restatement: %s"
+          % (name, left_out, len(rows), near_ties, near_cps, with_driver,
+             {k: "%.2e" % v for k, v in dist.items()} if ref_rows is not None else "no driver"))
     assert left_out <= max_left_out * len(rows), (name, left_out, len(rows))
     return got
 
@@ -146,16 +175,33 @@ def test_sync_test_matrix(cp_ext, driver):
     by the driver on those two items where it is built, says "normal" as well (the reference's sync_test runs cells 0-49 only, on one object
     whose averages carry over). Such a row has to give
     what the restatement decides; there may be no more than the two of cell 117, and every other row has to give the constructed CP."""
-    N, mo = 128, 9600
+    _matrix(128, range(504), (100, 400), cp_ext, driver, {117})
+
+
+# cells whose two CP metrics come out against the construction in the restatement at fft_size 384, on frames that hold only the SSS and the
+# PSS, as extended-CP cell 117's do at 128: none of the 72
+MATRIX_384_ODD = set()
+
+
+@pytest.mark.parametrize("cp_ext", [False, True])
+def test_sync_test_matrix_384(cp_ext, driver):
+    """The matrix at the 25-PRB symbol size: every seventh cell (72 cells) at offsets 300 and 1200, with the assertions of the 128-point
+    matrix. A cell whose CP metrics come out against the construction has to equal the restatement's decision and to stand in MATRIX_384_ODD."""
+    _matrix(384, range(0, 504, 7), (300, 1200), cp_ext, driver, MATRIX_384_ODD)
+
+
+def _matrix(N, cells, offsets, cp_ext, driver, odd_cells):
+    mo = 75 * N
     stride = mo + N
-    ids = [(cid, off) for cid in range(504) for off in (100, 400)]
+    ids = [(cid, off) for cid in cells for off in offsets]
     x = np.zeros((len(ids), stride), np.complex64)
     slots = {}
     for b, (cid, off) in enumerate(ids):
         sf = 5 if (cid + off) % 3 == 0 else 0
         if (cid, sf) not in slots:
             slots[cid, sf] = sr.sync_slot(cid, cp_ext, N, sf).astype(np.complex64)
-        x[b, off:off + 960] = slots[cid, sf]
+        x[b, off:off + slots[cid, sf].size] = slots[cid, sf]
+    end = slots[ids[0][0], 5 if sum(ids[0]) % 3 == 0 else 0].size  # the PSS is the slot's last symbol: 7.5 fft_size where no CP length rounds
     q = pkg.Sync(N, mo, mo, max_items=len(ids), cp_ext=cp_ext, threshold=1.0)
     rc, got = q.find(x, [pkg.SyncItem.make(3)] * len(ids))
     q.free()
@@ -166,25 +212,26 @@ def test_sync_test_matrix(cp_ext, driver):
         v = int(np.argmax([r.peak_value for r in rows]))
         r = rows[v]
         assert v == cid % 3, (cid, off, [r.peak_value for r in rows])
-        assert (r.ret, r.peak_pos, r.cell_id, r.sf_idx) == (1, off + 960, cid, 5 if (cid + off) % 3 == 0 else 0), (cid, off)
-        cp_ref, margin = sr.detect_cp(x[b].astype(complex), N, off + 960)
+        assert (r.ret, r.peak_pos, r.cell_id, r.sf_idx) == (1, off + end, cid, 5 if (cid + off) % 3 == 0 else 0), (cid, off)
+        cp_ref, margin = sr.detect_cp(x[b].astype(complex), N, off + end)
         assert margin > 10 * sr.tol(N)
         assert r.cp == cp_ref, (cid, off, r.cp, cp_ref, margin)
         if cp_ref != int(cp_ext):
             odd.append((cid, off))
-    assert set(c for c, _ in odd) <= {117} and len(odd) <= 2, odd
+    assert set(c for c, _ in odd) <= odd_cells and len(odd) <= 2 * len(odd_cells), odd
     if odd and driver is not None:  # the reference's own sync.c on those items says the same
         rows = [(cid % 3, 0, -1, ids.index((cid, off))) for cid, off in odd]
         for (cid, off), r in zip(odd, driver(q.cfg, x, rows)):
-            print("cell %d offset %d: the reference driver's cp %d, cell_id %d" % (cid, off, r.cp, r.cell_id))
-            assert (r.cp, r.cell_id, r.peak_pos) == (1 - int(cp_ext), cid, off + 960), (cid, off, r.cp)
+            print("fft_size %d cell %d offset %d: the reference driver's cp %d, cell_id %d" % (N, cid, off, r.cp, r.cell_id))
+            assert (r.cp, r.cell_id, r.peak_pos) == (1 - int(cp_ext), cid, off + end), (cid, off, r.cp)
 
 
 # ---------------------------------------------------------------- 2. parity
 def _drawn_items(rng, N, stride, n, known=False, special=True):
     """n items: cell, CP, delay, CFO in +-0.4 subcarriers; a quarter each noise-free, at 20 dB, at 5 dB and noise only. Of the last three (special)
-    the first two start inside slot 0, so that the peak lies before fft_size (100, then 64: no PSS CFO stage, FOUND_NOSPACE), and the third's peak
-    at 576 has room for the SSS but for one CP symbol only."""
+    the first two start inside slot 0, so that the peak lies before fft_size (100, then 64 at fft_size 128: no PSS CFO stage, FOUND_NOSPACE), and
+    the third's peak at 576 has room for the SSS but for one CP symbol only. Every length is in units of fft_size (a subframe is 15 fft_size; the
+    sizes whose CP lengths round up have a few samples more, which moves the special peaks by as many)."""
     x, items, truth = np.zeros((n, stride), np.complex64), [], []
     sf_len = 15 * N
     for b in range(n):
@@ -192,9 +239,9 @@ def _drawn_items(rng, N, stride, n, known=False, special=True):
         delay = int(rng.integers(0, 2 * sf_len))  # the capture starts this far into the transmission: the PSS lands anywhere in the window
         s = sr.ofdm_frame(cid, cp_ext, N, stride // sf_len + 4, rng, first)[delay:delay + stride].copy()
         if special and b >= n - 3:  # the capture starts inside slot 0 of a subframe 0 / 5 and ends before the next PSS
-            cut = (15 * N // 2 - 100, 7 * N, 3 * N)[b - (n - 3)]
+            cut, end = (15 * N // 2 - 25 * N // 32, 7 * N, 3 * N)[b - (n - 3)], 1125 * N // 16
             s[:] = 0
-            s[:9000 * N // 128 - cut] = sr.ofdm_frame(cid, cp_ext, N, stride // sf_len + 2, rng, 5 * (b % 2))[cut:9000 * N // 128]
+            s[:end - cut] = sr.ofdm_frame(cid, cp_ext, N, stride // sf_len + 2, rng, 5 * (b % 2))[cut:end]
         s *= np.exp(2j * np.pi * rng.uniform(-0.4, 0.4) / N * np.arange(stride))
         level = (None, 20.0, 5.0, "noise")[b % 4]
         if level == "noise":
@@ -246,38 +293,231 @@ def test_sss_threshold():
             assert (g.N_id_1, g.cell_id, g.sf_idx, g.sss_corr) == (-1, -1, 0, 0.0)
 
 
+# ---------------------------------------------------------------- 2b. full-window parity at the other sizes
+# (fft_size, configuration) -> seed of the 24 drawn items: the first of 400 + fft_size, + 1, + 2, ... that the restatement alone keeps inside
+# the 5 % cap (one row of 24) and whose rows take every ret
+SIZES_SEED = {(64, "find"): 464, (192, "find"): 592, (384, "find"): 784, (768, "find"): 1168, (384, "find_ext"): 784, (384, "known"): 784,
+              (384, "diff"): 784}
+
+
+def sizes_items(N, name, seed=None):
+    """-> (x, items, truth, max_offset = frame_size, in_stride) of test_parity_sizes: a window of 5 ms and fft_size samples behind it."""
+    mo, stride = 75 * N, 76 * N
+    x, items, truth = _drawn_items(np.random.default_rng(SIZES_SEED[N, name] if seed is None else seed), N, stride, 24, known=name == "known")
+    return x, items, truth, mo, stride
+
+
+@pytest.mark.parametrize("N,name", sorted(SIZES_SEED))
+def test_parity_sizes(N, name, driver):
+    """The 5 ms search of test_parity at the sizes under 128 and between the powers of two: 64 and 192, whose CP lengths round up (4.5 -> 5,
+    13.5 -> 14), 384 and 768, the symbol sizes of 25 and 50 PRB (at 384 the first symbol's CP is 30 samples, the others' 27). 24 drawn items,
+    the three special ones among them."""
+    x, items, truth, mo, stride = sizes_items(N, name)
+    q = pkg.Sync(N, mo, mo, max_items=24, **PARITY[name])
+    got = _parity("parity_%d_%s" % (N, name), q, x, items, driver)
+    q.free()
+    assert {g.ret for g in got} == {0, 1, 2}  # NOFOUND on noise, FOUND, and FOUND_NOSPACE on the early peaks
+    if name != "diff":
+        assert got[21].ret == 2 and got[21].peak_pos < N and got[21].cfo_pss == 0.0  # the PSS CFO stage is not entered before fft_size
+
+
+def _windowed_items(rng, N, n):
+    """n windows of 24 fft_size (and fft_size samples behind them) cut from four drawn subframes that start with subframe 4 or 9, so that the
+    PSS of subframe 5 or 0 ends between 1.5 and 22.5 fft_size into the window; CFO in +-0.4 subcarriers; noise-free, 20 dB, 5 dB, noise only."""
+    mo, stride = 24 * N, 25 * N
+    x, items = np.zeros((n, stride), np.complex64), []
+    for b in range(n):
+        cid, cp_ext, first = int(rng.integers(0, 504)), bool(rng.integers(0, 2)), int(rng.choice([4, 9]))
+        start = int(rng.integers(0, 21 * N))
+        s = sr.ofdm_frame(cid, cp_ext, N, 4, rng, first)[start:start + stride]
+        s = s * np.exp(2j * np.pi * rng.uniform(-0.4, 0.4) / N * np.arange(stride))
+        level = (None, 20.0, 5.0, "noise")[b % 4]
+        x[b] = (rng.normal(size=stride) + 1j * rng.normal(size=stride)) / np.sqrt(2) if level == "noise" else sr.awgn(s, level, rng)
+        items.append(pkg.SyncItem.make(cid % 3))
+    return x, items, mo, stride
+
+
+# fft_size -> seed: the first of 500 + fft_size, + 1, ... that the restatement alone (both neighbour rules applied at its own indices) keeps
+# inside the cap: none of 8 rows left out
+OVERSAMPLED_SEED = {1024: 1524, 1536: 2038, 2048: 2548}  # 2036 and 2037 leave one row of the 8 out at 1536
+
+
+@pytest.mark.parametrize("N", sorted(OVERSAMPLED_SEED))
+def test_parity_oversampled(N, driver):
+    """The full-window search where the PSS is 8, 12 and 16 times oversampled: a window of 24 fft_size (about a hundred tiles at 1024, two
+    hundred at 2048) with the PSS anywhere in it and room for the SSS and the CP stages. The peak's and the CP maximum's neighbours are within
+    10 T of them here, so both neighbour rules are in use."""
+    x, items, mo, stride = _windowed_items(np.random.default_rng(OVERSAMPLED_SEED[N]), N, 8)
+    q = pkg.Sync(N, mo, mo, max_items=8, **FIND)
+    got = _parity("parity_%d_find" % N, q, x, items, driver)
+    q.free()
+    assert {g.ret for g in got} >= {0, 1}
+
+
 # ---------------------------------------------------------------- 3. tracking
+TRACK_KW = dict(detect_cp=True, cfo_pss_enable=True, pss_filt_enable=True, sss_alg=pkg.SSS_PARTIAL_3, threshold=1.0, ema_alpha=1.0)
+
+
+def _guarded(name, N, frame, mo, x, items, driver, kw=TRACK_KW):
+    """Items [frame_size] in rows of x with NaN between and behind them: a read outside an item's frame poisons its row, which has to equal,
+    byte for byte, the row from a buffer with zeros there (that buffer is what the restatement and the driver see)."""
+    q = pkg.Sync(N, frame, mo, max_items=len(items), **kw)
+    rc, got_nan = q.find(x, items)
+    assert rc == 0
+    got = _parity(name, q, np.nan_to_num(x), items, driver)
+    for g, a in zip(got_nan, got):
+        assert bytes(g) == bytes(a)
+    q.free()
+    return got
+
+
+def _slot_row(rng, N, frame, d, cid, sf):
+    """A sync slot that starts d samples into a frame of zeros, a CFO in +-0.3 subcarriers, 20 dB on the two occupied symbols -> (samples,
+    the PSS symbol's end: peak_pos + find_offset)."""
+    s = np.zeros(frame, complex)
+    slot = sr.sync_slot(cid, False, N, sf)
+    s[d:d + slot.size] = slot
+    s *= np.exp(2j * np.pi * rng.uniform(-0.3, 0.3) / N * np.arange(frame))
+    return sr.awgn(s, 20.0 - 10 * np.log10(frame / (2.0 * N)), rng), d + slot.size
+
+
+def _tracking_branch(N, n, driver, seed):
+    mo = 32 if N > 64 else 24  # max_offset - 2 < fft_size / 2 for the drawn offsets
+    frame, stride = 15 * N, 15 * N + 37
+    rng = np.random.default_rng(seed)
+    x = np.full((n, stride), np.nan + 1j * np.nan, np.complex64)
+    items = []
+    for b in range(n):
+        cid, d = int(rng.integers(0, 504)), int(rng.integers(0, 225 * N // 32 - mo))
+        x[b, :frame], end = _slot_row(rng, N, frame, d, cid, 5 * (b % 2))
+        items.append(pkg.SyncItem.make(cid % 3, end - N - int(rng.integers(1, mo - 2))))
+    _guarded("tracking_%d_%d" % (N, n), N, frame, mo, x, items, driver)
+
+
 @pytest.mark.parametrize("N", [128, 256, 512, 1024, 1536, 2048])
 @pytest.mark.parametrize("n", [1, 5])
 def test_tracking_branch(N, n, driver):
     """max_offset 32 around the true PSS position; items [frame_size] in rows of in_stride = frame_size + 37 with NaN between them: a read
     outside an item's frame poisons its row."""
-    sc = N // 128
-    frame, stride, mo = 1920 * sc, 1920 * sc + 37, 32
-    rng = np.random.default_rng(N + n)
-    x = np.full((n, stride), np.nan + 1j * np.nan, np.complex64)
+    _tracking_branch(N, n, driver, N + n)
+
+
+# fft_size -> seed, where fft_size + 2 leaves a row out in the restatement alone (two rows: none may be left out)
+EVERY_SIZE_SEED = {1728: 1731}  # 1730 leaves one of its two rows out
+
+
+@pytest.mark.parametrize("N", range(64, 2049, 64))
+def test_tracking_branch_every_size(N, driver):
+    """The tracking branch at every transform size srslte_hip_sync_create accepts, two items each (max_offset 24 at 64). At 64, 192, 320 and 384
+    the CP lengths round up, or the first symbol's CP is more than a sample longer than the others'."""
+    _tracking_branch(N, 2, driver, EVERY_SIZE_SEED.get(N, N + 2))
+
+
+# ---------------------------------------------------------------- 3b. the switch between the two branches, tile edges, the smallest window
+def _placed(name, N, mo, outputs, driver, seed, kw=TRACK_KW, restated_at=None):
+    """One item per entry of outputs: the correlation output (index into the nout values of the call) on which the PSS is to peak. The slot is
+    drawn as in the tracking test; find_offset places the window. The restatement's peak has to be the one constructed (restated_at: the
+    rows to assert it on; all by default - beside an oversampled peak within 2 positions)."""
+    frame, stride, track = 15 * N, 15 * N + 37, mo < N
+    rng = np.random.default_rng(seed)
+    x = np.full((len(outputs), stride), np.nan + 1j * np.nan, np.complex64)
     items = []
-    for b in range(n):
-        cid, d = int(rng.integers(0, 504)), int(rng.integers(0, 900 * sc - mo))
-        s = np.zeros(frame, complex)
-        slot = sr.sync_slot(cid, False, N, 5 * (b % 2))
-        s[d:d + slot.size] = slot
-        s *= np.exp(2j * np.pi * rng.uniform(-0.3, 0.3) / N * np.arange(frame))
-        x[b, :frame] = sr.awgn(s, 20.0 - 10 * np.log10(frame / (2.0 * N)), rng)  # 20 dB on the two occupied symbols
-        items.append(pkg.SyncItem.make(cid % 3, d + slot.size - N - int(rng.integers(1, mo - 2))))
-    q = pkg.Sync(N, frame, mo, max_items=n, detect_cp=True, cfo_pss_enable=True, pss_filt_enable=True, sss_alg=pkg.SSS_PARTIAL_3, threshold=1.0,
-                 ema_alpha=1.0)
-    xs = np.nan_to_num(x)  # the restatement and the driver see zeros where the device must not look
-    rc, got_nan = q.find(x, items)
-    assert rc == 0
-    got = _parity("tracking_%d_%d" % (N, n), q, xs, items, driver)
-    for g, a in zip(got_nan, got):
-        assert bytes(g) == bytes(a)
+    slot_len = sr.cp_len(N, 160) + 6 * sr.cp_len(N, 144) + 7 * N
+    for b, m in enumerate(outputs):
+        # the slot starts at least 3 fft_size into the frame (room for the SSS and CP stages), and the window ends inside the frame
+        cid, d = int(rng.integers(0, 504)), int(rng.integers(3 * N, min(6 * N, frame - slot_len - (0 if track else mo - m)) + 1))
+        x[b, :frame], end = _slot_row(rng, N, frame, d, cid, 5 * (b % 2))
+        fo = end - (N if track else 0) - m  # peak_pos = m + fft_size in the tracking branch, m in the convolution branch
+        assert fo >= 0 and fo + mo <= frame and fo + mo + N - (0 if track else 2) <= stride
+        items.append(pkg.SyncItem.make(cid % 3, fo))
+    q = pkg.Sync(N, frame, mo, max_items=len(items), **kw)
+    cd, T = _dict(q.cfg), sr.tol(N)
     q.free()
+    for b, m in enumerate(outputs):
+        if restated_at is None or b in restated_at:
+            w = sr.find_one(np.nan_to_num(x[b]), cd, items[b].N_id_2, items[b].find_offset)
+            p = w["peak_pos"] - (N if track else 0)
+            assert p == m or (not w["margins"]["peak"] > 10 * T and abs(p - m) <= 2), (name, b, p, m)
+    return _guarded(name, N, frame, mo, x, items, driver, kw)
+
+
+@pytest.mark.parametrize("N", [64, 384, 768, 2048])
+@pytest.mark.parametrize("dmo", [-1, 0, 1])
+def test_branch_boundary(N, dmo, driver):
+    """max_offset = fft_size - 1 is the last window of the tracking branch (nout = fft_size - 2 starts, peak_pos = index + fft_size), fft_size and
+    fft_size + 1 the first two of the convolution branch (nout = 2 fft_size - 2 and one more). Six items each in guarded rows. In the tracking
+    branch the first two peak on output 0 and on the last output nout - 1. The convolution knows only the window's max_offset samples, so its
+    first and last outputs see one and two of the replica's taps and no window makes them the maximum (a window matched to those taps peaks
+    where more taps overlap); there the first two items put the PSS on the first and the last output that all fft_size taps reach, fft_size - 1
+    and max_offset - 1, and the others within fft_size / 8 of them."""
+    mo = N + dmo
+    rng = np.random.default_rng(7 * N + dmo)
+    if mo < N:
+        outputs = [0, mo - 2] + [int(v) for v in rng.integers(1, mo - 2, 4)]
+    else:
+        outputs = [N - 1, mo - 1] + [int(v) for v in rng.integers(N - N // 8, mo + N // 8, 4)]
+    # threshold 0.5: a peak on output 0 has no left side lobe but itself, so its peak_value can be 1.0 exactly; a threshold of 1.0 would sit on it
+    got = _placed("boundary_%d_%+d" % (N, dmo), N, mo, outputs, driver, N + mo, dict(TRACK_KW, threshold=0.5),
+                  restated_at=(0, 1))
+    assert all(g.ret == 1 for g in got)
+
+
+@pytest.mark.parametrize("N,mo,outputs", [(512, 256, (254, 100)), (512, 257, (255, 254)), (512, 258, (256, 255)), (512, 259, (257, 256, 255)),
+                                          (64, 194, (193, 63)), (64, 195, (194, 63)), (64, 320, (255, 256, 319))])
+def test_tile_edges(N, mo, outputs, driver):
+    """A tile of the correlation kernel holds 256 outputs. Tracking branch at 512 with nout 255 to 258: the peak on the last output, which is
+    the last of the first tile but one, the last of it, the first and the second of the next tile. Convolution branch at 64 with nout 256 and
+    257 (one full tile; a second tile of a single output): the peak on the last output that all taps reach (the outputs 255 and 256 there see
+    two taps and cannot hold the maximum, see test_branch_boundary), and with nout 382 on the last output of the first tile and the first of
+    the second."""
+    got = _placed("tile_%d_%d" % (N, mo), N, mo, outputs, driver, N + mo)
+    assert all(g.ret == 1 for g in got)
+
+
+@pytest.mark.parametrize("N", [64, 2048])
+def test_smallest_window(N, driver):
+    """max_offset 2: one output, so peak_pos == fft_size whatever the samples are, and with threshold 0 the row is FOUND."""
+    got = _placed("smallest_%d" % N, N, 2, (0, 0, 0), driver, N + 2, dict(TRACK_KW, threshold=0.0))
+    assert all((g.ret, g.peak_pos, g.peak_value) == (1, N, 0.0) for g in got)
+
+
+# ---------------------------------------------------------------- 3c. the FOUND / FOUND_NOSPACE line
+@pytest.mark.parametrize("N", [128, 384, 2048])
+def test_nospace_line(N, driver):
+    """Convolution branch, find_offset 0, extended CP configured and transmitted: three captures that start inside slot 0 so that the PSS ends
+    at 2 (fft_size + CP_EXT) - 1, on the line itself and one sample behind it: FOUND_NOSPACE, FOUND, FOUND. On the line the SSS symbol's CP
+    starts at the item's first sample."""
+    mo, line = 8 * N, 2 * (N + sr.cp_len(N, 512))
+    stride = mo + N
+    rng = np.random.default_rng(N + 40)
+    kw = dict(FIND, cp_ext=True, cfo_cp_enable=False)
+    x, items = np.zeros((3, stride), np.complex64), []
+    for b in range(3):
+        cid = int(rng.integers(0, 504))
+        f = sr.ofdm_frame(cid, True, N, 2, rng, 5 * (b % 2))
+        cut = 6 * (N + sr.cp_len(N, 512)) - (line - 1 + b)  # the PSS is the sixth symbol of slot 0
+        s = f[cut:cut + stride] * np.exp(2j * np.pi * rng.uniform(-0.3, 0.3) / N * np.arange(stride))
+        x[b] = sr.awgn(s, 20.0, rng)
+        items.append(pkg.SyncItem.make(cid % 3))
+    q = pkg.Sync(N, mo, mo, max_items=3, **kw)
+    cd, T = _dict(q.cfg), sr.tol(N)
+    for b in range(3):  # the three positions are the ones constructed, in the restatement
+        w = sr.find_one(x[b], cd, items[b].N_id_2)
+        if not w["margins"]["peak"] > 10 * T:  # beside an oversampled peak: the constructed position is within 10 T of the maximum
+            assert w["avg"][line - 1 + b] >= (1 - 10 * T) * w["avg"].max(), (N, b)
+            w = sr.find_one(x[b], cd, items[b].N_id_2, force_peak=line - 1 + b)
+        assert (w["peak_pos"], w["ret"]) == (line - 1 + b, 2 if b == 0 else 1), (N, b, w["peak_pos"], w["ret"])
+        if b == 1:
+            assert w["sss_available"] == 1
+    got = _parity("nospace_line_%d" % N, q, x, items, driver)
+    q.free()
+    if N < 1024:  # no oversampled peak at 128 and 384: the device's rows are on the constructed positions
+        assert [(g.ret, g.peak_pos) for g in got] == [(2, line - 1), (1, line), (1, line + 1)]
 
 
 # ---------------------------------------------------------------- 4. the CP stage alone
-@pytest.mark.parametrize("N,mo,ns", [(128, 9600, 14), (128, 32, 3), (512, 7680, 7), (2048, 30720, 8)])
+@pytest.mark.parametrize("N,mo,ns", [(128, 9600, 14), (128, 32, 3), (512, 7680, 7), (2048, 30720, 8), (64, 4800, 14), (192, 32, 3), (384, 28800, 14),
+                                     (768, 768, 7)])
 def test_cp_stage(N, mo, ns):
     rng = np.random.default_rng(N + ns)
     frame = max(mo, (ns + 1) * (N + sr.cp_len(N, 160)) + N)

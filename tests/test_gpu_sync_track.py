@@ -3,8 +3,10 @@ srslte_sync_t's state across calls, TDD cells and frame-type detection. Sequence
 tests/sync_track_ref.py and - where oracle/_ref/hip/libsrslte_upper.a exists - against the reference's own sync.c kept alive over the
 sequence (tests/sync_track_dropin_driver.c, compiled here).
 
-The tolerance T, the "2 x the driver's own distance" rule, the 10 T margin rule and the oversampled-peak excuse are those of
-tests/test_gpu_sync.py. Over a sequence a track is compared up to and excluding the first call whose smallest deciding margin in the
+The tolerance T, the "2 x the driver's own distance" rule, the 10 T margin rule, the oversampled-peak excuse and the one for the CP
+correlation's maximum are those of tests/test_gpu_sync.py. 26 tests: the sequences run at fft_size 128, one FDD sequence also at 384, the
+tracking branch with an average at 64, 128, 384, 512, 768 and 2048.
+Over a sequence a track is compared up to and excluding the first call whose smallest deciding margin in the
 restatement is not above 10 T; that call and the track's later calls count as left out, and a test fails when it leaves out more than 5 % of
 its rows. The two cases in which the reference reads uninitialised stack values (phy_hip.h defines them) are compared with the restatement
 only, as is every later call of such a track. The counts are printed, and recorded in profiles/sync_track/README.md."""
@@ -22,7 +24,7 @@ import pytest
 import sync_ref as sr
 import sync_track_ref as st
 from _libs import ROOT
-from test_gpu_sync import CSRC, FIND, HIP_REF, INVALID, PARITY, _dict, _drawn_items
+from test_gpu_sync import CSRC, FIND, HIP_REF, INVALID, PARITY, _dict, _drawn_items, near_cp_index
 
 pkg = importlib.import_module("srslte-emane_amd")
 pytestmark = pytest.mark.gpu
@@ -74,18 +76,21 @@ def driver():
 
 
 # ---------------------------------------------------------------- drawn sequences
-def _pss_end(tdd, cp_ext):
-    """Samples from the start of subframe 0 to the end of the first PSS symbol at N = 128."""
+def _pss_end(tdd, cp_ext, fft=N):
+    """Samples from the start of subframe 0 to the end of the first PSS symbol: the last symbol of slot 0, or the third of subframe 1 (TDD)."""
+    ext, first, norm = sr.cp_len(fft, 512), sr.cp_len(fft, 160), sr.cp_len(fft, 144)
+    slot = 6 * (fft + ext) if cp_ext else first + 6 * norm + 7 * fft
     if not tdd:
-        return 960
-    return 1920 + (3 * 160 if cp_ext else 138 + 2 * 137)
+        return slot
+    return 2 * slot + (3 * (fft + ext) if cp_ext else first + 2 * norm + 3 * fft)
 
 
-def draw_sequence(seed, n_tracks, n_calls, kind):
-    """n_calls consecutive 5 ms windows of n_tracks continuous transmissions. kind(t, rng) -> dict(tdd, cp_ext, snr (dB or None), and
+def draw_sequence(seed, n_tracks, n_calls, kind, fft=N):
+    """n_calls consecutive 5 ms windows (75 fft_size, and fft_size samples behind them) of n_tracks continuous transmissions. kind(t, rng) -> dict(tdd, cp_ext, snr (dB or None), and
     optionally noise_from (call index from which the windows hold noise only), cp_change (call index from which the cell uses the other
-    CP), peak (where the PSS peak is to lie in every window), cid). -> x [n_calls][n_tracks][STRIDE] complex64, the kinds with cid filled."""
+    CP), peak (where the PSS peak is to lie in every window), cid). -> x [n_calls][n_tracks][76 fft_size] complex64, the kinds with cid filled."""
     rng = np.random.default_rng(seed)
+    N, MO, STRIDE = fft, 75 * fft, 76 * fft
     x = np.zeros((n_calls, n_tracks, STRIDE), np.complex64)
     kinds = []
     total = n_calls * MO + (STRIDE - MO)
@@ -95,7 +100,7 @@ def draw_sequence(seed, n_tracks, n_calls, kind):
         k.setdefault("cid", int(rng.integers(0, 504)))
         delay = int(rng.integers(0, MO))
         if k["peak"] is not None:
-            delay = (_pss_end(k["tdd"], k["cp_ext"]) - k["peak"]) % MO
+            delay = (_pss_end(k["tdd"], k["cp_ext"], fft) - k["peak"]) % MO
         gen = st.ofdm_frame_tdd if k["tdd"] else sr.ofdm_frame
         cfo = rng.uniform(-0.4, 0.4)
         sig = []
@@ -141,20 +146,27 @@ def _compare(name, key, g, w, T, ref_row, dist, known=False):
 
 
 def _restate(trk, x, it, g, T, mo):
-    """The restatement's call on track trk -> (row, near_tie): beside an oversampled peak (test_gpu_sync._parity) it is continued from the
-    device's position, which has to be within 10 T of the maximum."""
+    """The restatement's call on track trk -> (track, row, near_tie, near_cp): beside an oversampled peak (test_gpu_sync._parity) it is
+    continued from the device's position, which has to be within 10 T of the maximum, and beside a maximum of the CP correlation from the
+    index at which the call's own estimate (cfo_cp_inst) is the device's (test_gpu_sync.near_cp_index)."""
     snap = copy.deepcopy(trk)
     w = trk.find(x, it.N_id_2, it.find_offset, it.N_id_1)
+    cp_i = None
+    if trk.cfg["cfo_cp_enable"] and not w["margins"]["cp_argmax"] > 10 * T:
+        cp_i = near_cp_index(w["cp_corr"], g.cfo_cp_inst, T, (it.track, g.nof_calls))
+        if cp_i is not None:
+            trk = copy.deepcopy(snap)
+            w = trk.find(x, it.N_id_2, it.find_offset, it.N_id_1, force_cp=cp_i)
     if w["margins"]["peak"] > 10 * T:
-        return trk, w, False
+        return trk, w, False, cp_i is not None
     off = N_OF[0] if mo < N_OF[0] else 0
     a, p = w["avg"], w["peak_pos"] - off
     second = int(np.argmax(np.r_[a[:p], -1.0, a[p + 1:]]))
     if abs(second - p) > 2:
-        return trk, w, False
+        return trk, w, False, cp_i is not None
     p_dev = int(g.peak_pos) - off
     assert 0 <= p_dev < a.size and a[p_dev] >= (1 - 10 * T) * a.max(), (g.peak_pos, w["peak_pos"])
-    return snap, snap.find(x, it.N_id_2, it.find_offset, it.N_id_1, force_peak=p_dev), True
+    return snap, snap.find(x, it.N_id_2, it.find_offset, it.N_id_1, force_peak=p_dev, force_cp=cp_i), True, cp_i is not None
 
 
 N_OF = [N]  # the fft_size _restate works at (the tracking test sets it)
@@ -184,7 +196,7 @@ def sequence_parity(name, q, tr, x, items, driver=None, ops=None, refs=None, max
     drv_flags = {0: 0, 1: OP_RESET, 2: OP_CFO_RST, 3: OP_RESET | OP_CFO_RST, 7: OP_NEW}
     if driver is not None and c.sss_threshold == 0 and all(f in drv_flags for call in ops for f, _ in call):
         ref_rows = driver(c, tc, x, items, [[(drv_flags[f] | (OP_COPY_CFO if s is not None else 0), s or 0) for f, s in call] for call in ops])
-    left_out, rows_total, near_ties, with_driver, dist = 0, 0, 0, 0, {}
+    left_out, rows_total, near_ties, near_cps, with_driver, dist = 0, 0, 0, 0, 0, {}
     alive, drv_ok = [True] * n_tracks, [ref_rows is not None] * n_tracks
     for k in range(n_calls):
         for t in range(n_tracks):  # resets first, then the copies, as on the device
@@ -202,19 +214,22 @@ def sequence_parity(name, q, tr, x, items, driver=None, ops=None, refs=None, max
                 left_out += 1
                 continue
             g = got[k][t]
-            refs[t], w, near = _restate(refs[t], x[k, t], it, g, T, c.max_offset)
+            refs[t], w, near, near_cp = _restate(refs[t], x[k, t], it, g, T, c.max_offset)
             near_ties += int(near)
+            near_cps += int(near_cp)
             if not min(w["margins"].values()) > 10 * T:
                 alive[t] = False
                 left_out += 1
                 continue
-            drv_ok[t] = drv_ok[t] and not w["undefined_in_reference"] and (not near or ref_rows[k][t].peak_pos == g.peak_pos)
+            drv_ok[t] = drv_ok[t] and not w["undefined_in_reference"] and (not near or ref_rows[k][t].peak_pos == g.peak_pos) and \
+                (not near_cp or abs(ref_rows[k][t].cfo - w["cfo"]) <= T)
             with_driver += int(drv_ok[t])
             _compare(name, (k, t), g, w, T, ref_rows[k][t] if drv_ok[t] else None, dist, it.N_id_1 >= 0)
     LEFT_OUT[name] = (left_out, rows_total)
     print("%s: %d of %d rows left out (a margin under 10 T in that call or an earlier one of the track), %d compared from the device's own "
-          "position beside an oversampled peak, %d also with the driver; reference driver's distances from the restatement: %s"
-          % (name, left_out, rows_total, near_ties, with_driver, {k: "%.2e" % v for k, v in dist.items()} if ref_rows is not None else "no driver"))
+          "position beside an oversampled peak, %d from the device's own index beside a CP maximum, %d also with the driver; reference driver's "
+          "distances from the restatement: %s" % (name, left_out, rows_total, near_ties, near_cps, with_driver,
+                                                  {k: "%.2e" % v for k, v in dist.items()} if ref_rows is not None else "no driver"))
     assert left_out <= max_left_out * rows_total, (name, left_out, rows_total)
     return got
 
@@ -290,6 +305,23 @@ def test_fdd_sequence(name, driver):
     q.free()
 
 
+# fft_size 384: 6 tracks x 4 windows, a quarter of test_fdd_sequence. The seed is the first of 1100, 1101, ... that the restatement alone keeps
+# inside the cap (one row of 24)
+FDD_384_SEED = 1100
+
+
+def test_fdd_sequence_384(driver):
+    """The tracked full-window search at the 25-PRB symbol size, with both averages."""
+    fft = 384
+    x, kinds = draw_sequence(FDD_384_SEED, 6, 4, lambda t, rng: dict(tdd=False, cp_ext=bool(rng.integers(0, 2)), snr=(None, 20.0, 10.0, 5.0)[t % 4]), fft)
+    q = pkg.Sync(fft, 76 * fft, 75 * fft, max_items=6, **dict(FIND, ema_alpha=0.3))
+    tr = pkg.SyncTracks(q, 6, 0.1, pkg.FRAME_FDD)
+    got = sequence_parity("fdd_384_a0.3_c0.1", q, tr, x, [_items(kinds)] * 4, driver)
+    assert all(got[3][t].nof_calls == 4 for t in range(6)) and any(got[3][t].ret == 1 and got[3][t].cell_id == kinds[t]["cid"] for t in range(6))
+    tr.free()
+    q.free()
+
+
 # ---------------------------------------------------------------- 3. TDD and detection
 def _mixed_kind(mode, cp_ext):
     def kind(t, rng):
@@ -353,18 +385,17 @@ def test_tdd_and_detection_sequence(name, driver):
 
 
 # ---------------------------------------------------------------- 4. the tracking branch
-TRACKING_SEED = {128: 135, 512: 519, 2048: 2056}  # 2055 leaves 5 of 48 rows out in the restatement alone
+TRACKING_SEED = {128: 135, 512: 519, 2048: 2056, 64: 71, 384: 391, 768: 775}  # 2055 leaves 5 of 48 rows out in the restatement alone
 
 
 def tracking_sequence(fft, n=8, calls=6, mo=32):
     """-> x [calls][n + 1][stride] with NaN guards (row 0 of every call is the leading guard), the items, the sync keywords."""
-    sc = fft // 128
-    frame, stride = 1920 * sc, 1920 * sc + 37
+    frame, stride = 15 * fft, 15 * fft + 37
     rng = np.random.default_rng(TRACKING_SEED[fft])
     x = np.full((calls, n + 1, stride), np.nan + 1j * np.nan, np.complex64)
     items = []
     for b in range(n):
-        cid, d = int(rng.integers(0, 504)), int(rng.integers(0, 900 * sc - mo - calls))
+        cid, d = int(rng.integers(0, 504)), int(rng.integers(0, 225 * fft // 32 - mo - calls))
         slot = sr.sync_slot(cid, False, fft, 5 * (b % 2))
         cfo = rng.uniform(-0.3, 0.3)
         for k in range(calls):
@@ -377,13 +408,13 @@ def tracking_sequence(fft, n=8, calls=6, mo=32):
     return x, items, kw
 
 
-@pytest.mark.parametrize("fft", [128, 512, 2048])
+@pytest.mark.parametrize("fft", [128, 512, 2048, 64, 384, 768])
 def test_tracking_branch_with_average(fft):
-    """max_offset 32 < fft_size with ema_alpha 0.2: 8 tracks x 6 calls, the peak drifting by a sample per call. Every item [frame_size] lies
+    """max_offset 32 < fft_size (24 at fft_size 64) with ema_alpha 0.2: 8 tracks x 6 calls, the peak drifting by a sample per call. Every item [frame_size] lies
     between guard samples (a row of them before the first item, 37 behind every item) that hold NaN: a read outside an item's frame poisons
     its row, which has to equal, byte for byte, the row from a buffer with zeros there; and the buffer is unchanged after every call."""
-    sc, mo, n, calls = fft // 128, 32, 8, 6
-    frame, stride = 1920 * sc, 1920 * sc + 37
+    mo, n, calls = 32 if fft > 64 else 24, 8, 6
+    frame, stride = 15 * fft, 15 * fft + 37
     x, items, kw = tracking_sequence(fft, n, calls, mo)
     q = pkg.Sync(fft, frame, mo, max_items=n, **kw)
     tr, tz = pkg.SyncTracks(q, n, 0.0, pkg.FRAME_FDD), pkg.SyncTracks(q, n, 0.0, pkg.FRAME_FDD)
