@@ -393,3 +393,122 @@ def run_state_script(cfg):
                 tracks[op[1]]["mean_cfo"] = float(np.float32(op[2]))
         rows.append([npss_find(x, cfg, tracks[t]) for t, x in items])
     return rows, tracks
+
+
+# ---------------------------------------------------------------- the edge cases the GPU edge test, the generator and the edge golden share
+EDGE_SEEDS = dict(short=20271, long=20272, planted=20273, big=20274, nsss=20275, walks=20276)
+EDGE_SHORT = (1, 2, 3, 127)
+EDGE_LONG = (128, 129, 255, 256, 257, 285, 286, 287)
+EDGE_PLANTED = (1507, 1508, 1509)
+EDGE_LAGS = (0, 1, 2, 3, 7, -3, -4, -700)
+EDGE_NSSS_IDS = (0, 63, 64, 127, 250, 252, 448, 503)
+EDGE_NSSS_LAGS = (0, 63, 64, 2332, 3000, -700, -36, -4, -3)
+
+
+def plant(h, n, lag, cfo_sc, snr_db, rng):
+    """n samples that hold the replica h - or the part of it that falls inside - with h[0] at index lag (negative: only the tail is inside, and
+    the circular correlation peaks at lag + n + 1508), rotated by cfo_sc subcarriers, plus noise snr_db below the replica's mean power
+    (None: noise-free, the samples outside the replica exact zeros)."""
+    sig = np.zeros(n, complex)
+    a, b = max(lag, 0), min(lag + LEN, n)
+    sig[a:b] = h[a - lag:b - lag]
+    return impair(sig, cfo_sc, snr_db, rng, ref_power=np.mean(np.abs(h) ** 2))
+
+
+def plant_npss(frame_size, lag, rng, cfo_sc=0.03, snr_db=15.0):
+    return plant(npss_replica(), frame_size, lag, cfo_sc, snr_db, rng).astype(np.complex64)
+
+
+def edge_noise(frame_size, count, stride=None):
+    """Seeded Gaussian items of the short and the tie-prone long frame sizes -> x [count][stride] complex64, all of the stride drawn."""
+    rng = np.random.default_rng([EDGE_SEEDS["short" if frame_size < N else "long"], frame_size])
+    stride = stride or frame_size
+    return (rng.normal(size=(count, stride)) + 1j * rng.normal(size=(count, stride))).astype(np.complex64)
+
+
+def edge_planted(frame_size, lags=EDGE_LAGS, key="planted"):
+    """One item per planted lag -> x [len(lags)][frame_size] complex64; SNR drawn in 10 .. 20 dB."""
+    rng = np.random.default_rng([EDGE_SEEDS[key], frame_size])
+    return np.stack([plant_npss(frame_size, lag, rng, snr_db=float(rng.uniform(10.0, 20.0))) for lag in lags])
+
+
+def edge_nsss():
+    """The nine planted NSSS captures at 20 dB -> (x [9][3840] complex64, ids, lags)."""
+    rng = np.random.default_rng(EDGE_SEEDS["nsss"])
+    ids = list(EDGE_NSSS_IDS) + [int(rng.integers(0, NUM_PCI))]
+    x = np.stack([plant(nsss_replica(c), NSSS_IN, lag, 0.0, 20.0, rng) for c, lag in zip(ids, EDGE_NSSS_LAGS)]).astype(np.complex64)
+    return x, ids, list(EDGE_NSSS_LAGS)
+
+
+EDGE_CFG = dict(PARITY_CFG, npss_ema_alpha=1.0)
+EDGE_GOLDEN_NOISE = (2, 3, 127, 128, 129, 286)
+
+
+def edge_golden_inputs():
+    """The NPSS cases of tests/golden/nbiot_sync_edges.npz, each item for find_offset 0 and a fresh track: name -> (frame_size, x [n][frame_size])."""
+    out = {}
+    for fs in EDGE_GOLDEN_NOISE:
+        out["noise_%d" % fs] = (fs, edge_noise(fs, 3 if fs < N else 4))
+    out["planted_1508"] = (1508, edge_planted(1508))
+    out["zero_3840"] = (3840, np.zeros((1, 3840), np.complex64))
+    return out
+
+
+EDGE_WALK_FRAME = 6
+# noise items at frame_size 6 (5 lags), picked by a search over seeds for the shape of their row a[0..4], every pair of values 20 T apart:
+#   53:  peak 3, a[1] above a[0], a[2] and a[4]: the left walk stops at 2 and the left range a[:2] holds the side lobe (peak > 2 taken as <= 2: a[0])
+#   412: peak 3, a[2] > a[1] > a[0] > a[4]: the left walk runs down to 1 and the left range is a[:1]
+#   144: peak 2, a[1] > a[0] > a[3], a[4]: pl_lb is 0, the empty left range answers a[0], not a[1]
+#   1:   peak 4, the last lag, a[3] < a[2]: the left walk stops at once and the right range is empty
+EDGE_WALK_SEEDS = (53, 412, 144, 1)
+
+
+def edge_walk_items():
+    """-> x [4][6 + 127] complex64 of EDGE_WALK_SEEDS."""
+    out = []
+    for seed in EDGE_WALK_SEEDS:
+        rng = np.random.default_rng([EDGE_SEEDS["walks"], seed])
+        n = EDGE_WALK_FRAME + N - 1
+        out.append((rng.normal(size=n) + 1j * rng.normal(size=n)).astype(np.complex64))
+    return np.stack(out)
+
+
+def conv_len(frame_size):
+    """conv_output_len of npss.c: nout + 1 in both branches."""
+    return frame_size + LEN - 1 if frame_size >= N else frame_size
+
+
+def tie_step(x, cfg, track, find_offset, dev_pos, Tm=None):
+    """The tie set: where the restatement's peak is within 10 Tm of a tie - at ANY distance, as below some 400 samples, where |c| repeats every
+    137 lags - a position p with avg[p] >= (1 - 10 Tm) max(avg) is accepted and the restatement is continued from it. dev_pos: the position to
+    test. -> (restatement row on `track` (updated), True when the row was continued from dev_pos). Raises AssertionError outside the set."""
+    Tm = T if Tm is None else Tm
+    before = {"avg": track["avg"].copy(), "mean_cfo": track["mean_cfo"]}
+    w = npss_find(x, cfg, track, find_offset)
+    if "peak" in w["margins"] and w["margins"]["peak"] <= 10 * Tm:
+        a, p = w["avg"], int(dev_pos)
+        assert 0 <= p < a.size and a[p] >= (1 - 10 * Tm) * a.max(), (p, w["peak_pos"])
+        track.clear()
+        track.update(before)
+        return npss_find(x, cfg, track, find_offset, force_peak=p), True
+    return w, False
+
+
+def self_consistent(row, res, frame_size, threshold):
+    """A device row against the device's own track row (npss_ema_alpha 1: the row is this call's |c|^2): the first maximum, the value there bit
+    for bit, the walk of psr() on that row within one float division, and the decision. res: (ret, peak_pos, peak_value, corr_peak).
+    Needs no margin, so it holds on every row. -> None or a description of what differs."""
+    ret, pos, val, peak = res
+    row = np.asarray(row, np.float32)
+    p = int(np.argmax(row)) if row.size else 0
+    if pos != p:
+        return "peak_pos %d, the row's first maximum is at %d" % (pos, p)
+    want = row[p] if row.size else np.float32(0)
+    if np.float32(peak).tobytes() != np.float32(want).tobytes():
+        return "corr_peak %r, the row holds %r" % (peak, want)
+    v = psr(row.astype(np.float64), p, conv_len(frame_size))
+    if np.isnan(v) != np.isnan(val) or (np.isinf(v) and val != v) or (np.isfinite(v) and not abs(val - v) <= 2.0 ** -23 * abs(v)):
+        return "peak_value %r, the walk on the row gives %r" % (val, v)
+    if ret != (1 if val >= threshold else 0):
+        return "ret %d with peak_value %r and threshold %r" % (ret, val, threshold)
+    return None

@@ -57,6 +57,49 @@ def test_nout_follows_the_reference_lengths():
     assert pkg.nbiot_npss_nout(64) == 63
 
 
+def test_nout_at_the_edges_of_both_branches():
+    """frame_size - 1 below 128 (0 at frame_size 1, and 0 for the refused frame_size 0, not a wrap to 2^32 - 1), frame_size + 1506 from 128 up
+    to the bound."""
+    for fs, want in ((1, 0), (2, 1), (127, 126), (128, 1634), (307200, 308706), (0, 0)):
+        assert pkg.nbiot_npss_nout(fs) == want, fs
+        if fs:
+            assert nr.nout(fs) == want and nr.conv_len(fs) == want + 1
+
+
+def test_check_stride_rule_on_either_side_of_the_branch_switch():
+    """The short branch's last dot product reads 127 samples past the frame: find_offset + frame_size + 127 <= in_stride at 127; at 128, the
+    long branch, find_offset + frame_size is enough."""
+    s = pkg.nbiot_sync_cfg(127, max_items=1)
+    assert pkg.nbiot_sync_check(s, 127 + 127, [It(0, 0)]) == 0
+    assert pkg.nbiot_sync_check(s, 127 + 126, [It(0, 0)]) == INVALID
+    assert pkg.nbiot_sync_check(s, 9 + 127 + 127, [It(0, 9)]) == 0
+    assert pkg.nbiot_sync_check(s, 9 + 127 + 126, [It(0, 9)]) == INVALID
+    c = pkg.nbiot_sync_cfg(128, max_items=1)
+    assert pkg.nbiot_sync_check(c, 128, [It(0, 0)]) == 0
+    assert pkg.nbiot_sync_check(c, 127, [It(0, 0)]) == INVALID
+    assert pkg.nbiot_sync_check(c, 9 + 128, [It(0, 9)]) == 0
+    assert pkg.nbiot_sync_check(c, 9 + 127, [It(0, 9)]) == INVALID
+    assert pkg.nbiot_sync_check(pkg.nbiot_sync_cfg(307200), 307200, [It(0, 0)]) == 0
+    assert pkg.nbiot_sync_check(pkg.nbiot_sync_cfg(307201), 307201, [It(0, 0)]) == INVALID
+
+
+def test_self_consistency_rule_has_teeth():
+    """nbiot_sync_ref.self_consistent, the rule the GPU edge tests hold every device row to, on a row of the restatement itself: it accepts the
+    row's own answers and names a later one of two equal maxima, a value one ulp off, a ratio 2^-22 off and a wrong decision."""
+    fs = 255
+    w = nr.npss_find(nr.edge_noise(fs, 1)[0], dict(nr.EDGE_CFG, frame_size=fs), nr.new_track(fs))
+    row = w["avg"].astype(np.float32)
+    row[40] = row[900] = 2 * row.max()  # two equal maxima: the first counts
+    val = np.float32(nr.psr(row.astype(np.float64), 40, nr.conv_len(fs)))
+    assert nr.self_consistent(row, (0, 40, val, row[40]), fs, 5.0) is None
+    assert "first maximum" in nr.self_consistent(row, (0, 900, val, row[900]), fs, 5.0)
+    assert "corr_peak" in nr.self_consistent(row, (0, 40, val, np.nextafter(row[40], np.float32(0))), fs, 5.0)
+    assert "peak_value" in nr.self_consistent(row, (0, 40, val * np.float32(1 + 2.0 ** -21), row[40]), fs, 5.0)
+    assert "ret" in nr.self_consistent(row, (1, 40, val, row[40]), fs, 5.0)
+    assert nr.self_consistent(np.zeros(0, np.float32), (0, 0, float("nan"), 0.0), 1, 5.0) is None
+    assert "peak_value" in nr.self_consistent(np.zeros(0, np.float32), (0, 0, 1.0, 0.0), 1, 5.0)
+
+
 @pytest.mark.parametrize("nof_prb", [1, 6, 25])
 def test_re_helpers_against_the_put_subframe_loops(nof_prb):
     for off in sorted({0, nof_prb // 2, nof_prb - 1}):
