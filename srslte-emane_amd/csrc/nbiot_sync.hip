@@ -5,8 +5,8 @@
 //                             frame with the class's 137 / 138 conjugated taps; input tile and taps in LDS, a lane per position
 //   nbiot_npss_comb_kernel    grid (tile of 256 lags, item): c[n] = sum_i sign_i W_cls(i)[n + s_i] (frame_size < 128: the 128-tap dot products),
 //                             |c|^2, the average into the track's row, the tile's (maximum, first index)
-//   nbiot_npss_decide_kernel  one workgroup per item: the peak over the tiles, the lobe walk (a parallel find-first over blocks of 256
-//                             positions), the side-lobe maxima, the CFO stage on the uncorrected item, the track's mean_cfo and the row
+//   nbiot_npss_decide_kernel  one workgroup per item: the peak over the tiles, the side lobe, the CFO stage on the uncorrected item, the track's
+//                             mean_cfo and the row
 //   nbiot_nsss_slide_kernel   grid (tile of 256 positions, CP class x subcarrier, item): Y_cls,sc[m]
 //   nbiot_nsss_prod_kernel    grid (tile of 64 lags, row of up to 64 cell ids): the [ids x 132] x [132 x lags] complex product in fp32 FMAs, the
 //                             table and Y through LDS a symbol (12 rows) at a time, 4 x 4 outputs per lane; writes each id's (maximum of |c|,
@@ -14,11 +14,12 @@
 //   nbiot_nsss_decide_kernel  one workgroup per item: every id's peak over the tiles, the first maximum over the ids, the row, and the |c| row
 //                             of the row's id for the debug entry
 //   nbiot_track_reset_kernel, nbiot_track_set_cfo_kernel
+// The rotated load, the workgroup reductions, the side lobe and the CP correlation are search_dev.hpp's, shared with sync.hip.
 // The tables come from nbiot_sync_host.cpp.
-#include "cf32_dev.hpp"
 #include "common.hpp"
 #include "dev_buf.hpp"
 #include "phy_hip_internal.hpp"
+#include "search_dev.hpp"
 #include <math.h>
 #include <string.h>
 
@@ -38,7 +39,6 @@ constexpr uint32_t NS_PT      = 64;                           // ids and lags of
 constexpr uint32_t NS_NT      = (NS_NOUT + NS_PT - 1) / NS_PT; // 84 lag tiles
 constexpr uint32_t NS_MY      = 27 * NB_TILE;                 // 6912 >= 84 x 64 + s_10: positions of Y a product tile may read
 constexpr uint32_t NS_IDROWS  = (NB_PCI + NS_PT - 1) / NS_PT; // 8 product rows of an exhaustive item
-constexpr uint32_t NO_INDEX   = 0xffffffffu;
 constexpr uint32_t CFO_OFFSET = 548, CFO_NSAMP = 823;         // SRSLTE_NPSS_CFO_OFFSET, SRSLTE_NPSS_CFO_NUM_SAMPS
 
 __device__ __forceinline__ uint32_t sym_start(uint32_t i) { return 137u * i + (i > 4u ? 1u : 0u); }
@@ -71,61 +71,6 @@ struct NsssParams {
   float*      peak_values; // [item][504]
   float*      abs_row;  // [item][NS_NOUT]
 };
-
-// x exp(j 2 pi f idx): the fractional part of f idx in double, so the phase is as exact at the end of a frame as at its start
-__device__ __forceinline__ cf32 rot(cf32 x, float f, uint32_t idx)
-{
-  double p = (double)f * (double)idx;
-  p -= rint(p);
-  float s, c;
-  sincospif(2.f * (float)p, &s, &c);
-  return cmul(x, make_float2(c, s));
-}
-__device__ __forceinline__ cf32 ld_rot(const cf32* x, uint32_t idx, float f) { return f != 0.f ? rot(x[idx], f, idx) : x[idx]; }
-
-// the first maximum over the workgroup (srslte_vec_max_fi: strict >, so the lowest index among equals); every thread gets the result
-__device__ void block_argmax(float& v, uint32_t& i, float* s_v, uint32_t* s_i)
-{
-  const int tid = threadIdx.x;
-  s_v[tid] = v, s_i[tid] = i;
-  __syncthreads();
-  for (int o = NB_THREADS / 2; o > 0; o >>= 1) {
-    if (tid < o) {
-      const float    v2 = s_v[tid + o];
-      const uint32_t i2 = s_i[tid + o];
-      if (v2 > s_v[tid] || (v2 == s_v[tid] && i2 < s_i[tid])) s_v[tid] = v2, s_i[tid] = i2;
-    }
-    __syncthreads();
-  }
-  v = s_v[0], i = s_i[0];
-  __syncthreads();
-}
-__device__ uint32_t block_min_u32(uint32_t v, uint32_t* s_i)
-{
-  const int tid = threadIdx.x;
-  s_i[tid]      = v;
-  __syncthreads();
-  for (int o = NB_THREADS / 2; o > 0; o >>= 1) {
-    if (tid < o && s_i[tid + o] < s_i[tid]) s_i[tid] = s_i[tid + o];
-    __syncthreads();
-  }
-  v = s_i[0];
-  __syncthreads();
-  return v;
-}
-__device__ float block_max_float(float v, float* s_v)
-{
-  const int tid = threadIdx.x;
-  s_v[tid]      = v;
-  __syncthreads();
-  for (int o = NB_THREADS / 2; o > 0; o >>= 1) {
-    if (tid < o && s_v[tid + o] > s_v[tid]) s_v[tid] = s_v[tid + o];
-    __syncthreads();
-  }
-  v = s_v[0];
-  __syncthreads();
-  return v;
-}
 
 // W_cls[m] = sum_t xe[m + t] taps[cls][t], xe the frame continued circularly over L with zeros from frame_size on, rotated by the track's mean
 __global__ __launch_bounds__(NB_THREADS) void nbiot_npss_slide_kernel(NpssParams p, const NpssRow* __restrict__ rows, const cf32* __restrict__ in)
@@ -176,7 +121,7 @@ __global__ __launch_bounds__(NB_THREADS) void nbiot_npss_comb_kernel(NpssParams 
     *a   = v;
     best = v, bi = n;
   }
-  block_argmax(best, bi, s_v, s_i);
+  block_argmax<NB_THREADS>(best, bi, s_v, s_i);
   if (tid == 0) p.tile_max[(size_t)item * p.ntiles + blockIdx.x] = make_float2(best, __uint_as_float(bi));
 }
 
@@ -200,50 +145,11 @@ __global__ __launch_bounds__(NB_THREADS) void nbiot_npss_decide_kernel(NpssParam
     const uint32_t i = __float_as_uint(m.y);
     if (i != NO_INDEX && (m.x > best || (m.x == best && i < pk))) best = m.x, pk = i;
   }
-  block_argmax(best, pk, s_v, s_i);
+  block_argmax<NB_THREADS>(best, pk, s_v, s_i);
   if (pk == NO_INDEX) pk = 0; // nothing compared greater than -inf: srslte_vec_max_fi answers index 0
   const float peak = av(pk);
 
-  // npss.c:305-308: pl_ub runs on while avg[pl_ub + 1] <= avg[pl_ub] and pl_ub < conv_output_len
-  uint32_t ub = pk + 1;
-  for (;;) {
-    const uint32_t j     = ub + tid;
-    const bool     go    = j < CL && av(j + 1) <= av(j);
-    const uint32_t first = block_min_u32(go ? NO_INDEX : j, s_i);
-    if (first != NO_INDEX) {
-      ub = first;
-      break;
-    }
-    ub += NB_THREADS;
-  }
-  // :310-318: pl_lb runs down while avg[pl_lb - 1] <= avg[pl_lb] and pl_lb > 1
-  uint32_t lb = 0;
-  if (pk > 2) {
-    lb = pk - 1;
-    for (;;) {
-      const bool     in_range = lb >= tid + 1; // j = lb - tid >= 1
-      const uint32_t j        = in_range ? lb - tid : 0u;
-      const bool     stop     = in_range && !(j > 1 && av(j - 1) <= av(j));
-      // the first stop going down is the largest such j: the minimum of lb - j
-      const uint32_t d = block_min_u32(stop ? lb - j : NO_INDEX, s_i);
-      if (d != NO_INDEX) {
-        lb -= d;
-        break;
-      }
-      lb -= NB_THREADS; // no stop among 256 positions that all lie above 1
-    }
-  }
-  // :320-328: the maxima right of pl_ub and left of pl_lb; an empty range answers its first index
-  const uint32_t dr    = CL - 1 > ub ? CL - 1 - ub : 0u;
-  float          right = -INFINITY, left = -INFINITY;
-  for (uint32_t j = tid; j < dr; j += NB_THREADS) right = fmaxf(right, av(ub + j));
-  for (uint32_t j = tid; j < lb; j += NB_THREADS) left = fmaxf(left, av(j));
-  right = block_max_float(right, s_v);
-  left  = block_max_float(left, s_v);
-  if (dr == 0) right = av(ub);
-  if (lb == 0) left = av(0);
-  const float side = right > left ? right : left;
-  const float psr  = peak / side;
+  const float psr = peak / side_lobe<NB_THREADS>(av, pk, CL, s_v, s_i); // npss.c:301-343
 
   // sync_nbiot.c:224-242
   const bool cfo_run = p.cfo_enable && (uint64_t)pk + CFO_OFFSET + CFO_NSAMP + 128 < p.frame_size;
@@ -254,19 +160,11 @@ __global__ __launch_bounds__(NB_THREADS) void nbiot_npss_decide_kernel(NpssParam
     float       bv  = -INFINITY;
     uint32_t    bi  = NO_INDEX;
     if (tid < p.cp_offsets) { // cp.c:61-77
-      cf32     acc = make_float2(0.f, 0.f);
-      uint32_t off = tid;
-      for (uint32_t n = 0; n < 6; n++) {
-        const uint32_t cpl = 9u + (n % 7 ? 0u : 1u);
-        cf32           d   = make_float2(0.f, 0.f);
-        for (uint32_t k = 0; k < cpl; k++) d = cadd(d, cmulconj(ld(off + k), ld(off + 128 + k)));
-        acc.x += d.x / 6.f, acc.y += d.y / 6.f;
-        off += 128 + cpl;
-      }
+      const cf32 acc = cp_synch_at(ld, 128, 9, 6, tid);
       s_corr[tid] = acc;
       bv = acc.x * acc.x + acc.y * acc.y, bi = tid;
     }
-    block_argmax(bv, bi, s_v, s_i);
+    block_argmax<NB_THREADS>(bv, bi, s_v, s_i);
     const cf32 c = s_corr[bi == NO_INDEX ? 0u : bi];
     cfo          = (float)(-atan2((double)c.y, (double)c.x) / M_PI / 2); // sync_nbiot.c:263
   }
@@ -404,7 +302,7 @@ __global__ __launch_bounds__(NB_THREADS) void nbiot_nsss_decide_kernel(NsssParam
     p.peak_values[(size_t)item * NB_PCI + id] = v;
     s_pos[id]                                 = pos;
   }
-  block_argmax(best, bid, s_v, s_i); // nsss.c:252: the first maximum of peak_values
+  block_argmax<NB_THREADS>(best, bid, s_v, s_i); // nsss.c:252: the first maximum of peak_values
   if (bid == NO_INDEX) bid = want < 0 ? 0u : (uint32_t)want;
   if (tid == 0) {
     const float v = p.peak_values[(size_t)item * NB_PCI + bid];

@@ -4,9 +4,8 @@
 //   sync_corr_kernel    grid (tile of 256 outputs, item x hypothesis): the replica and the tile's input samples - rotated by -cfo_cp / N as
 //                       they are loaded - in LDS, a lane per output with consecutive-address LDS reads; writes the averaged |c|^2 and the
 //                       tile's (maximum, first index)
-//   sync_decide_kernel  one workgroup per (item, hypothesis): the peak over the tiles, the lobe ends (a parallel find-first over blocks of 256
-//                       positions) and the side-lobe maxima, the 62-bin direct DFTs of the PSS and SSS symbols, the CFO from the replica's
-//                       halves, the m0 / m1 correlations, the CP metrics, and the result row
+//   sync_decide_kernel  one workgroup per (item, hypothesis): the peak over the tiles, the side lobe, the 62-bin direct DFTs of the PSS and SSS
+//                       symbols, the CFO from the replica's halves, the m0 / m1 correlations, the CP metrics, and the result row
 //   cfo_correct_kernel  a lane per sample, the phase reduced in double before sincospif
 // The tracked call (srslte_hip_sync_track_batch: a srslte_sync_t's state per track, kept on the device) runs the same three bodies, instantiated a
 // second time under kernel names of their own (track_cp_kernel, track_corr_kernel, track_decide_kernel): the stateless kernels take no state
@@ -16,12 +15,12 @@
 //   track_decide_kernel  the carried cp, the FDD / TDD SSS trials one after the other in the same LDS, the frame-type decision, the state
 //                        update and the 24-word row
 //   track_reset_kernel, track_copy_cfo_kernel   one workgroup per listed track
+// The rotated load, the workgroup reductions, the side lobe and the CP correlation are search_dev.hpp's, shared with nbiot_sync.hip.
 // The tables come from sync_host.cpp.
-#include "cf32_dev.hpp"
 #include "common.hpp"
 #include "dev_buf.hpp"
 #include "phy_hip_internal.hpp"
-#include <limits.h>
+#include "search_dev.hpp"
 #include <math.h>
 #include <string.h>
 #include <vector>
@@ -30,7 +29,6 @@ namespace {
 
 constexpr int      SYNC_THREADS = 256;
 constexpr uint32_t SYNC_TILE    = 256;
-constexpr uint32_t NO_INDEX     = 0xffffffffu;
 
 struct SyncRow {
   uint32_t item, N_id_2, find_offset;
@@ -63,60 +61,6 @@ struct SyncParams {
   cf32*          cp_corr;  // [item][min(max_offset, N)]
 };
 
-// x exp(j 2 pi f idx): the fractional part of f idx in double, so the phase is as exact at the end of a frame as at its start
-__device__ __forceinline__ cf32 rot(cf32 x, float f, uint32_t idx)
-{
-  double p = (double)f * (double)idx;
-  p -= rint(p);
-  float s, c;
-  sincospif(2.f * (float)p, &s, &c);
-  return cmul(x, make_float2(c, s));
-}
-__device__ __forceinline__ cf32 ld_rot(const cf32* x, uint32_t idx, float f) { return f != 0.f ? rot(x[idx], f, idx) : x[idx]; }
-
-// the first maximum over the workgroup (srslte_vec_max_fi: strict >, so the lowest index among equals); every thread gets the result
-__device__ void block_argmax(float& v, uint32_t& i, float* s_v, uint32_t* s_i)
-{
-  const int tid = threadIdx.x;
-  s_v[tid] = v, s_i[tid] = i;
-  __syncthreads();
-  for (int o = SYNC_THREADS / 2; o > 0; o >>= 1) {
-    if (tid < o) {
-      const float    v2 = s_v[tid + o];
-      const uint32_t i2 = s_i[tid + o];
-      if (v2 > s_v[tid] || (v2 == s_v[tid] && i2 < s_i[tid])) s_v[tid] = v2, s_i[tid] = i2;
-    }
-    __syncthreads();
-  }
-  v = s_v[0], i = s_i[0];
-  __syncthreads();
-}
-__device__ int block_max_int(int v, uint32_t* s_i)
-{
-  const int tid = threadIdx.x;
-  s_i[tid]      = (uint32_t)v;
-  __syncthreads();
-  for (int o = SYNC_THREADS / 2; o > 0; o >>= 1) {
-    if (tid < o && (int)s_i[tid + o] > (int)s_i[tid]) s_i[tid] = s_i[tid + o];
-    __syncthreads();
-  }
-  v = (int)s_i[0];
-  __syncthreads();
-  return v;
-}
-__device__ float block_max_float(float v, float* s_v)
-{
-  const int tid = threadIdx.x;
-  s_v[tid]      = v;
-  __syncthreads();
-  for (int o = SYNC_THREADS / 2; o > 0; o >>= 1) {
-    if (tid < o) s_v[tid] = fmaxf(s_v[tid], s_v[tid + o]);
-    __syncthreads();
-  }
-  v = s_v[0];
-  __syncthreads();
-  return v;
-}
 __device__ float block_sum(float v, float* s_red)
 {
   v = wave_sum(v);
@@ -135,24 +79,15 @@ __device__ __forceinline__ void cp_body(const SyncParams& p, const cf32* __restr
   const uint32_t item = blockIdx.x, M = p.max_offset < p.N ? p.max_offset : p.N;
   const cf32*    x    = in + (size_t)item * p.in_stride;
   cf32*          corr = p.cp_corr + (size_t)item * M;
-  const float    ns   = (float)p.cp_nsym;
   float          best = -INFINITY;
   uint32_t       bi   = NO_INDEX;
   for (uint32_t i = threadIdx.x; i < M; i += SYNC_THREADS) {
-    cf32     acc = make_float2(0.f, 0.f);
-    uint32_t off = i;
-    for (uint32_t n = 0; n < p.cp_nsym; n++) {
-      const uint32_t cpl = p.cpn + (n % 7 ? 0u : 1u);
-      cf32           d   = make_float2(0.f, 0.f);
-      for (uint32_t k = 0; k < cpl; k++) d = cadd(d, cmulconj(x[off + k], x[off + p.N + k]));
-      acc.x += d.x / ns, acc.y += d.y / ns;
-      off += p.N + cpl;
-    }
-    corr[i]       = acc;
-    const float v = acc.x * acc.x + acc.y * acc.y;
+    const cf32 acc = cp_synch_at([&](uint32_t j) { return x[j]; }, p.N, p.cpn, p.cp_nsym, i);
+    corr[i]        = acc;
+    const float v  = acc.x * acc.x + acc.y * acc.y;
     if (v > best) best = v, bi = i;
   }
-  block_argmax(best, bi, s_v, s_i);
+  block_argmax<SYNC_THREADS>(best, bi, s_v, s_i);
   if (threadIdx.x == 0) {
     const cf32  c   = corr[bi == NO_INDEX ? 0u : bi];
     const float est = (float)(-atan2((double)c.y, (double)c.x) / M_PI / 2); // cfo_cp_estimate (sync.c:572-579)
@@ -221,7 +156,7 @@ __device__ __forceinline__ void corr_body(const SyncParams& p, const SyncRow* __
     }
     best = v, bi = m;
   }
-  block_argmax(best, bi, s_v, s_i);
+  block_argmax<SYNC_THREADS>(best, bi, s_v, s_i);
   if (tid == 0) p.tile_max[(size_t)blockIdx.y * p.ntiles + blockIdx.x] = make_float2(best, __uint_as_float(bi));
 }
 __global__ __launch_bounds__(SYNC_THREADS) void sync_corr_kernel(SyncParams p, const SyncRow* __restrict__ rows, const cf32* __restrict__ in)
@@ -377,7 +312,7 @@ __device__ __forceinline__ void decide_body(const SyncParams& p, const SyncRow* 
   const cf32*    x   = in + (size_t)r.item * p.in_stride;
   const float*   A   = (TR && t.avg) ? t.avg + (size_t)r.track * p.nout : p.avg + (size_t)blockIdx.x * p.nout;
   const uint32_t tid = threadIdx.x, N = p.N, fo = r.find_offset;
-  const int      nout = (int)p.nout, len = nout + 1; // len: conv_output_len of pss.c
+  const int      nout = (int)p.nout;
   // The track's state: the stages read only what steers them - the CP-CFO mean (track_cp_kernel left it in p.cfo_cp), the PSS-CFO mean and
   // the carried cp. They note in wr what the call writes (WR_*), and thread 0 merges that into the state at the end: the row shows the
   // previous value of whatever the call left alone.
@@ -396,7 +331,7 @@ __device__ __forceinline__ void decide_body(const SyncParams& p, const SyncRow* 
     const uint32_t ti = __float_as_uint(tm.y);
     if (tm.x > pv || (tm.x == pv && ti < pi)) pv = tm.x, pi = ti;
   }
-  block_argmax(pv, pi, L.v, L.i);
+  block_argmax<SYNC_THREADS>(pv, pi, L.v, L.i);
   const int   peak = pi == NO_INDEX ? 0 : (int)pi;
   const float cpk  = Aat(peak);
 
@@ -404,34 +339,7 @@ __device__ __forceinline__ void decide_body(const SyncParams& p, const SyncRow* 
   float peak_value = 0.f;
   if (p.threshold > 0.f) {
     wr |= WR_PEAK;
-    int pl_ub = 0, pl_lb = 0;
-    for (int base = peak + 1;; base += SYNC_THREADS) { // the first c >= peak + 1 at which the walk to the right stops
-      const int  c    = base + (int)tid;
-      const bool stop = c >= len || !(Aat(c + 1) <= Aat(c));
-      const int  got  = block_max_int(stop ? -c : INT_MIN, L.i);
-      if (got != INT_MIN) {
-        pl_ub = -got;
-        break;
-      }
-    }
-    if (peak > 2) {
-      for (int base = peak - 1;; base -= SYNC_THREADS) { // the first c <= peak - 1 at which the walk to the left stops
-        const int  c    = base - (int)tid;
-        const bool stop = c <= 1 || !(Aat(c - 1) <= Aat(c));
-        const int  got  = block_max_int(stop ? c : INT_MIN, L.i);
-        if (got != INT_MIN) {
-          pl_lb = got;
-          break;
-        }
-      }
-    }
-    const int dist_right = len - 1 - pl_ub > 0 ? len - 1 - pl_ub : 0;
-    float     right = -INFINITY, left = -INFINITY;
-    for (int i = pl_ub + (int)tid; i < pl_ub + dist_right; i += SYNC_THREADS) right = fmaxf(right, Aat(i));
-    for (int i = (int)tid; i < pl_lb; i += SYNC_THREADS) left = fmaxf(left, Aat(i));
-    right = dist_right > 0 ? block_max_float(right, L.v) : Aat(pl_ub);
-    left  = pl_lb > 0 ? block_max_float(left, L.v) : Aat(0);
-    peak_value = cpk / (right > left ? right : left);
+    peak_value = cpk / side_lobe<SYNC_THREADS>(Aat, (uint32_t)peak, p.nout + 1, L.v, L.i); // conv_output_len of pss.c is nout + 1
   }
   const bool     found    = peak_value >= p.threshold || p.threshold == 0.f;
   const uint32_t peak_pos = (uint32_t)peak + (p.track ? N : 0u);

@@ -5,6 +5,7 @@ the CFO stage of sync_nbiot.c:189-265. Every decision comes with its relative ma
 import numpy as np
 
 import sync_ref as sr
+from sync_ref import psr  # npss.c:301-343 walks as compute_peak_sidelobe (pss.c:412-441) does
 
 N, LEN, SF = 128, 1508, 1920
 CORR_OFFSET = SF - LEN                      # 412
@@ -100,26 +101,6 @@ def nout(frame_size):
 def circ_corr(x, h, L):
     """c[n] = sum_k x[(n + k) mod L] conj(h[k]) (convolution.c:130-136 with its normalisations)."""
     return np.fft.ifft(np.fft.fft(np.r_[x, np.zeros(L - x.size)]) * np.conj(np.fft.fft(np.r_[h, np.zeros(L - h.size)])))
-
-
-def psr(avg, peak, conv_len):
-    """npss.c:301-343 as it walks; avg (conv_len - 1 values) is followed by zeros."""
-    A = np.r_[avg, np.zeros(4)]
-    ub = peak + 1
-    while A[ub + 1] <= A[ub] and ub < conv_len:
-        ub += 1
-    if peak > 2:
-        lb = peak - 1
-        while A[lb - 1] <= A[lb] and lb > 1:
-            lb -= 1
-    else:
-        lb = 0
-    dr = max(conv_len - 1 - ub, 0)
-    right = A[ub:ub + dr].max() if dr > 0 else A[ub]
-    left = A[:lb].max() if lb > 0 else A[0]
-    side = right if right > left else left
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return float(np.float64(A[peak]) / side)
 
 
 def cp_symbols():

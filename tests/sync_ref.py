@@ -121,21 +121,26 @@ def cp_corr(x, N, max_offset, nsym):
     return corr
 
 
-def _psr(avg, peak):
-    """compute_peak_sidelobe (pss.c:412-441); avg is followed by zeros, as conv_output_avg is."""
-    nout = avg.size
-    ln = nout + 1
-    A = np.r_[avg, np.zeros(3)]
+def lobe_ends(avg, peak, conv_len):
+    """The walks of compute_peak_sidelobe (pss.c:412-441) and npss.c:301-343 from the peak to the ends of its lobe -> (pl_lb, pl_ub); avg
+    (conv_len - 1 values) is followed by zeros, as conv_output_avg is."""
+    A = np.r_[avg, np.zeros(4)]
     ub = peak + 1
-    while A[ub + 1] <= A[ub] and ub < ln:
+    while A[ub + 1] <= A[ub] and ub < conv_len:
         ub += 1
+    lb = 0
     if peak > 2:
         lb = peak - 1
         while A[lb - 1] <= A[lb] and lb > 1:
             lb -= 1
-    else:
-        lb = 0
-    dr = max(ln - 1 - ub, 0)
+    return lb, ub
+
+
+def psr(avg, peak, conv_len):
+    """The peak over the larger of the maxima right of pl_ub and left of pl_lb; an empty range answers its first index."""
+    A = np.r_[avg, np.zeros(4)]
+    lb, ub = lobe_ends(avg, peak, conv_len)
+    dr = max(conv_len - 1 - ub, 0)
     right = A[ub:ub + dr].max() if dr > 0 else A[ub]
     left = A[:lb].max() if lb > 0 else A[0]
     side = right if right > left else left
@@ -228,7 +233,7 @@ def find_one(x, cfg, N_id_2, find_offset=0, N_id_1=-1, force_peak=None, force_cp
     o["corr_peak"] = float(avg[peak])
     thr = cfg["threshold"]
     if thr > 0:
-        o["peak_value"] = _psr(avg, peak)
+        o["peak_value"] = psr(avg, peak, avg.size + 1)
         mg["threshold"] = abs(o["peak_value"] - thr) / max(o["peak_value"], thr)
     peak_pos = peak + (N if mo < N else 0)
     o["peak_pos"] = peak_pos

@@ -123,7 +123,7 @@ class Track:
         o["corr_peak"] = float(avg[peak])
         thr = cfg["threshold"]
         if thr > 0:
-            self.peak_value = sr._psr(avg, peak)
+            self.peak_value = sr.psr(avg, peak, avg.size + 1)
             mg["threshold"] = abs(self.peak_value - thr) / max(self.peak_value, thr)
         peak_pos = peak + (N if mo < N else 0)
         o["peak_pos"] = peak_pos

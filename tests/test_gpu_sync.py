@@ -3,8 +3,8 @@ construction, parity with the float64 restatement of tests/sync_ref.py and - whe
 reference's own sync.c (tests/sync_dropin_driver.c, compiled here with gcc as tests/test_gpu_prach.py compiles its driver), the tracking
 branch at every accepted transform size in guarded buffers, the full-window search at 64, 192, 384, 768, 1024, 1536 and 2048, the switch
 between the two branches (max_offset = fft_size - 1, fft_size, fft_size + 1), the edges of the correlation kernel's 256-output tiles, the
-one-output window, the FOUND / FOUND_NOSPACE line, the CP stage alone, the CFO correction, the recorded captures, a transmit - impair -
-synchronise - decode-MIB chain, refusals and queued calls. 106 tests.
+one-output window, a lobe whose walks cross several 256-lag blocks, the FOUND / FOUND_NOSPACE line, the CP stage alone, the CFO correction,
+the recorded captures, a transmit - impair - synchronise - decode-MIB chain, refusals and queued calls. 108 tests.
 
 Tolerances: T = max(1e-4, 4 fft_size 2^-24). A float output may differ from the restatement by max(T, 2 x the reference driver's own
 distance on the same item), relative to the output's scale (the figure itself for correlations and ratios, 1 subcarrier for CFOs). Discrete
@@ -479,6 +479,44 @@ def test_smallest_window(N, driver):
     """max_offset 2: one output, so peak_pos == fft_size whatever the samples are, and with threshold 0 the row is FOUND."""
     got = _placed("smallest_%d" % N, N, 2, (0, 0, 0), driver, N + 2, dict(TRACK_KW, threshold=0.0))
     assert all((g.ret, g.peak_pos, g.peak_value) == (1, N, 0.0) for g in got)
+
+
+# ---------------------------------------------------------------- 3b'. a lobe of several 256-lag blocks on both sides of the peak
+# fft_size -> the occupied PSS bins whose tone, under the envelope below, gives N_id_2 0 a row that is monotone outside +- fft_size of its peak
+# (about a fifth of the (N_id_2, bin) pairs do: around the envelope's kink the row is the PSS's own and rises and falls as it likes)
+LONG_LOBE_BINS = {64: (-30, -27, -23, -22, -20, -17), 128: (-25, -20)}
+
+
+@pytest.mark.parametrize("N", sorted(LONG_LOBE_BINS))
+def test_lobe_walk_over_several_blocks(N, driver):
+    """The side-lobe walk of search_dev.hpp (sync.hip and nbiot_sync.hip share it) over more than three blocks of 256 lags to the right and to
+    the left. Sample n is e(n) exp(2 pi j f n / fft_size) with e(n) = 1.008^-|n - 1000|: wherever all fft_size taps see one geometric segment
+    the correlation is geometric too, so the averaged row rises by 1.6 % per lag (160 T) for about 950 lags up to the peak and falls the same
+    way behind it. Asserted on the restatement before the device runs: both walks are at least 768 lags long, every step along them outside
+    +- fft_size of the peak exceeds 10 T (the device's float32 row cannot turn one round), and walks that ended after one block of 256 would
+    answer a peak_value more than a factor of 2 off (they give 40 to 50 where the true one is about 3e6). The peak's runner-up is its
+    neighbour within 10 T on most rows, which _parity compares from the device's own position; no row may be left out."""
+    mo, bins = 2000, LONG_LOBE_BINS[N]
+    kw = dict(threshold=1.0, ema_alpha=1.0, detect_cp=False, sss_en=False, cfo_cp_enable=False, cfo_pss_enable=False)
+    n = np.arange(mo + N)
+    x = np.array([1.008 ** -np.abs(n - 1000.0) * np.exp(2j * np.pi * f * n / N) for f in bins]).astype(np.complex64)
+    items = [pkg.SyncItem.make(0) for _ in bins]
+    q = pkg.Sync(N, mo, mo, max_items=len(items), **kw)
+    cd, T, walks = _dict(q.cfg), sr.tol(N), []
+    for b, f in enumerate(bins):
+        w = sr.find_one(x[b], cd, 0)
+        a, pk = w["avg"], w["peak_pos"]
+        lb, ub = sr.lobe_ends(a, pk, a.size + 1)
+        walks.append((pk - lb, ub - pk))
+        assert min(walks[-1]) >= 768, (N, f, pk, lb, ub)
+        up, down = np.arange(lb, pk - N), np.arange(pk + N, ub)
+        assert ((a[up + 1] - a[up]) / a[up + 1]).min() > 10 * T and ((a[down] - a[down + 1]) / a[down]).min() > 10 * T, (N, f)
+        one_block = a[pk] / max(a[pk + 256:].max(), a[:pk - 256].max())
+        assert w["peak_value"] > 2 * one_block, (N, f, w["peak_value"], one_block)
+    print("lobe_walk_%d: %d rows, walks (left, right) in lags: %s" % (N, len(bins), walks))
+    got = _parity("lobe_walk_%d" % N, q, x, items, driver, max_left_out=0)
+    q.free()
+    assert all(g.ret == 1 for g in got)
 
 
 # ---------------------------------------------------------------- 3c. the FOUND / FOUND_NOSPACE line
