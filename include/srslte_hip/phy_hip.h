@@ -355,6 +355,17 @@ int srslte_hip_dl_rx_stage(srslte_hip_dl_rx_t* q, int stage, const void* d_iq, u
  * 10 the subframes' largest csi [nof_sf] */
 const void* srslte_hip_dl_rx_debug_buffer(const srslte_hip_dl_rx_t* q, int which);
 int         srslte_hip_dl_rx_keep_symbols(srslte_hip_dl_rx_t* q, int enable);
+/* At a high code rate the parity streams of a code block are mostly puncturing zeros: in the decoder's 16-window layout the transmitted
+ * values of rv 0 sit in every fourth 32-byte row. A fixed-grant call with rv 0 and new data (srslte_hip_dl_rx_batch, _stage, _batch_harq*)
+ * then keeps those rows alone in the soft buffer when the object has 16-bit LLRs, the 16-window decoder (K > 800), K a multiple of 64 and no
+ * code block of any subframe gets more than srslte_hip_rm_parity_compact_limit(K) LLRs; the rate de-matcher stores half the bytes and the
+ * decoder fetches a quarter of the parity rows. A retransmission into such a buffer expands it first; buffer 5 of the debug view is always the
+ * whole layout. Results are the same either way. Environment SRSLTE_HIP_PARITY_COMPACT=0, read when an object is created, keeps the whole
+ * layout (A/B, tests). srslte_hip_dl_rx_parity_compact: 1 if the object's last rate de-matcher run wrote the compact layout, else 0.
+ * srslte_hip_rm_parity_compact_limit: the first position of rv 0's circular buffer (36.212 5.1.4.1.2) that falls into a row the compact layout
+ * of block length K does not keep; 0 where K has no such layout (K not a multiple of 64, or no code-block length) */
+int      srslte_hip_dl_rx_parity_compact(const srslte_hip_dl_rx_t* q);
+uint32_t srslte_hip_rm_parity_compact_limit(uint32_t K);
 
 /* ------------------------------------------------------------------ PUSCH receive pipeline (eNB side): OFDM RX with the
  * -1/2 carrier shift (enb_ul.c:58-63) -> chest_ul -> RE extraction + one-tap MMSE -> inverse transform precoding -> soft demap +

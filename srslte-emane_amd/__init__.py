@@ -136,6 +136,9 @@ def lib():
         L.srslte_hip_dl_rx_debug_buffer.restype = vp
         L.srslte_hip_dl_rx_debug_buffer.argtypes = [vp, C.c_int]
         L.srslte_hip_dl_rx_keep_symbols.argtypes = [vp, C.c_int]
+        L.srslte_hip_dl_rx_parity_compact.argtypes = [vp]
+        L.srslte_hip_rm_parity_compact_limit.restype = C.c_uint32
+        L.srslte_hip_rm_parity_compact_limit.argtypes = [C.c_uint32]
         _bind_dl_ctrl(L)
         _bind_ul_ctrl(L)
         _bind_prach(L)
@@ -516,6 +519,10 @@ class DlRx:
     def keep_symbols(self, enable=True):
         """Also write the equalised symbols d (debug buffer 3); off by default: the fused kernel never stores them."""
         _check(lib().srslte_hip_dl_rx_keep_symbols(self.h, 1 if enable else 0), "dl_rx_keep_symbols")
+
+    def parity_compact(self):
+        """Whether the last rate de-matcher run wrote the soft buffer with its parity streams at a quarter of their rows."""
+        return bool(lib().srslte_hip_dl_rx_parity_compact(self.h))
 
     def run_device(self, d_iq_ptr, tti0, nof_sf, stream=None):
         return lib().srslte_hip_dl_rx_batch(self.h, d_iq_ptr, tti0, nof_sf, self.d_tb.ptr, self.tb_stride, self.d_ok.ptr, stream)

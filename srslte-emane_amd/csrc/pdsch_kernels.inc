@@ -419,6 +419,7 @@ struct RmGeom {
   int             combine; // HARQ: add to the soft buffer kept from earlier transmissions (rm_turbo.c:407-409 accumulates) instead of writing it
   const uint8_t*  skip;    // HARQ: [B*C] blocks whose CRC already passed are not touched (sch.c:317-318)
   int             e_off;   // LLRs in front of the shared channel's in every subframe (PUSCH: the CQI report's, sch.c:1058-1064)
+  int             w_len;   // slots of the table, where it covers less than the w_stride slots between two blocks (rm_parity_compact); 0: w_stride
 };
 
 // wrapping lane-wise add of packed int16 / int8 (the soft buffer accumulates with plain C '+=' on int16_t / int8_t)
@@ -491,7 +492,7 @@ __global__ __launch_bounds__(256) void rm_rx_kernel(const LLR* __restrict__ e, L
 {
   constexpr int PER = 4 / (int)sizeof(LLR); // slots per dword
   // the block: memory slot cbg = sf * g.C + cb; in grants mode its own (C, K, Qm, nof_re, table) come from the descriptor
-  int             cbg = blockIdx.y, sf = cbg / g.C, cb = cbg - sf * g.C, C = g.C, Qm = g.Qm, out_len = g.out_len, w_len = g.w_stride, combine = g.combine;
+  int             cbg = blockIdx.y, sf = cbg / g.C, cb = cbg - sf * g.C, C = g.C, Qm = g.Qm, out_len = g.out_len, w_len = g.w_len ? g.w_len : g.w_stride, combine = g.combine;
   int             nre = g.nof_re[sf_class((g.tti0 + sf) % 10)], Nl = g.Nl, e_off = g.e_off;
   const uint32_t* tbl = inv;
   if (g.cbd) {
@@ -543,7 +544,7 @@ __global__ __launch_bounds__(256) void rm_rx_lds_kernel(const LLR* __restrict__ 
   extern __shared__ __attribute__((aligned(16))) char seg_raw[];
   constexpr int PER = 16 / (int)sizeof(LLR), NV = PER / 8; // slots per 16 bytes; uint4 loads of 16-bit table entries per step
   LLR*          seg = reinterpret_cast<LLR*>(seg_raw);
-  int             cbg = blockIdx.x, sf = cbg / g.C, cb = cbg - sf * g.C, C = g.C, Qm = g.Qm, out_len = g.out_len, w_len = g.w_stride, combine = g.combine;
+  int             cbg = blockIdx.x, sf = cbg / g.C, cb = cbg - sf * g.C, C = g.C, Qm = g.Qm, out_len = g.out_len, w_len = g.w_len ? g.w_len : g.w_stride, combine = g.combine;
   int             nre = g.nof_re[sf_class((g.tti0 + sf) % 10)], Nl = g.Nl, e_off = g.e_off;
   const uint32_t* tbl = inv;
   if (g.cbd) {
@@ -1017,6 +1018,7 @@ std::vector<uint32_t> rm_slot_table(const std::vector<uint32_t>& t, uint32_t w_s
   std::vector<uint32_t> inv(w_stride + w_stride / 2, 0xffffffffu);
   uint16_t*             inv16 = reinterpret_cast<uint16_t*>(inv.data() + w_stride);
   for (uint32_t n = 0; n < t.size(); n++) {
+    if (t[n] == 0xffffffffu) continue; // a position without a slot (rm_parity_compact)
     inv[t[n]]   = n;
     inv16[t[n]] = (uint16_t)n; // n < 3 * 6144 + 12
   }
@@ -1082,6 +1084,77 @@ int rm_rx_table_upload(uint32_t K, uint32_t rv, uint32_t W, uint32_t w_stride, D
     for (auto& v : t) v = v < 3 * K ? (v % 3) * (K + 32) + ((v / 3) % (K / W)) * W + (v / 3) / (K / W) : (v - 3 * K) + 3 * (K + 32);
   }
   return upload(d_tbl, rm_slot_table(t, w_stride));
+}
+
+// Punctured parity at a quarter of its rows. At a high code rate the receiver gets the first few columns of the parity sub-block interleavers
+// only (36.212 5.1.4.1.1: columns 0, 16, 8, 24, 4, 20, 12, 28 come first, all = 0 mod 4), which in the 16-window layout of a block with
+// Lw = K / 16 = 0 mod 4 are the rows r = phase mod 4 of each parity stream - one 32-byte row of every 128-byte line. The compact layout of
+// rv 0 keeps those rows alone: the systematic stream as it is, row r of parity stream 1 + i (r % 4 == phase[i]) as row r / 4 of K / 4 slots at
+// K + 32 + i K / 4, the tails at K + 32 + K / 2; `len` slots (a multiple of 32) instead of 3 (K + 32) + 12. Nothing is hard-coded about the
+// interleaver: the phases are those of each stream's first position in the circular buffer, and e_lim is the first position whose slot the
+// layout does not hold - a block of at most e_lim LLRs loses nothing. The 16-window 16-bit decoder reads it (TdecOpts::pc).
+struct RmParityCompact {
+  uint32_t phase[2], len, e_lim;
+};
+// false: no such layout for this K (K % 64 != 0). t: lte_rm_rx_table's positions replaced by their slots, 0xffffffff where there is none
+bool rm_parity_compact(uint32_t K, RmParityCompact& c, std::vector<uint32_t>* t_out = nullptr)
+{
+  if (K % 64 || K / 16 < 4) return false;
+  std::vector<uint32_t> t;
+  lte_rm_rx_table(K, 0, t);
+  const uint32_t Lw = K / 16;
+  bool           seen[2] = {false, false};
+  c.phase[0] = c.phase[1] = 0;
+  c.len   = (K + 32 + K / 2 + 12 + 31) & ~31u;
+  c.e_lim = (uint32_t)t.size();
+  for (uint32_t n = 0; n < t.size(); n++) {
+    const uint32_t v = t[n], s = v % 3, i = v / 3;
+    if (v >= 3 * K) {
+      t[n] = (v - 3 * K) + K + 32 + K / 2;
+    } else if (s == 0) {
+      t[n] = (i % Lw) * 16 + i / Lw;
+    } else {
+      const uint32_t r = i % Lw;
+      if (!seen[s - 1]) {
+        seen[s - 1]    = true;
+        c.phase[s - 1] = r % 4;
+      }
+      if (r % 4 == c.phase[s - 1]) {
+        t[n] = K + 32 + (s - 1) * (K / 4) + (r / 4) * 16 + i / Lw;
+      } else {
+        if (c.e_lim == t.size()) c.e_lim = n;
+        t[n] = 0xffffffffu;
+      }
+    }
+  }
+  if (t_out) t_out->swap(t);
+  return true;
+}
+int rm_rx_table_upload_compact(uint32_t K, RmParityCompact& c, DevBuf<uint32_t>& d_tbl)
+{
+  std::vector<uint32_t> t;
+  if (!rm_parity_compact(K, c, &t)) return SRSLTE_ERROR_INVALID_INPUTS;
+  return upload(d_tbl, rm_slot_table(t, c.len));
+}
+
+// A block's soft buffer from the compact layout above to the whole one, in place: one workgroup per block takes the compact parity rows and
+// the tails through LDS, then writes both parity streams (zeros and the rows held), the tails and the padding up to the block's stride - slot for
+// slot what the rate de-matcher leaves with the whole table
+__global__ __launch_bounds__(256) void rm_parity_expand_kernel(int16_t* __restrict__ w, int w_stride, int K, int phase0, int phase1)
+{
+  __shared__ __attribute__((aligned(16))) int16_t cp[6144 / 2 + 16]; // the longest code block's two quarter streams and tails
+  int16_t*  p  = w + (size_t)blockIdx.x * w_stride;
+  const int nc = K / 2 + 12, base = K + 32;
+  for (int i = threadIdx.x; i < (nc + 7) / 8; i += 256) reinterpret_cast<uint4*>(cp)[i] = reinterpret_cast<const uint4*>(p + base)[i];
+  __syncthreads();
+  const int per = (K + 32) / 8; // 16-byte half rows of a whole stream, padding included
+  for (int j = threadIdx.x; j < 2 * per; j += 256) {
+    const int s = j >= per, h = j - s * per, r = h >> 1;
+    uint4     v = make_uint4(0, 0, 0, 0);
+    if (r < K / 16 && (r & 3) == (s ? phase1 : phase0)) v = *reinterpret_cast<const uint4*>(cp + s * (K / 4) + (r >> 2) * 16 + (h & 1) * 8);
+    *reinterpret_cast<uint4*>(p + (1 + s) * (K + 32) + h * 8) = v;
+  }
+  for (int i = 3 * (K + 32) + threadIdx.x; i < w_stride; i += 256) p[i] = i < 3 * (K + 32) + 12 ? cp[K / 2 + i - 3 * (K + 32)] : (int16_t)0;
 }
 
 // rate matching table of (K, rv) (rm_turbo.c:100-158): the coded bit of each circular-buffer position from k0(rv) on, addressed in the encoder's

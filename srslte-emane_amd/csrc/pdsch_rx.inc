@@ -33,6 +33,14 @@ struct srslte_hip_dl_rx {
   DevBuf<uint32_t>       d_rm_tbl_rv[4]; // [0] made with the object; 1..3 built on first use (srslte_hip_dl_rx_batch_harq)
   uint32_t               harq_rv      = 0;
   int                    harq_combine = 0;
+  // Punctured parity at a quarter of its rows (rm_parity_compact, pdsch_kernels.inc): whether this object's calls with rv 0 and new data take that
+  // layout, its table, the subframe slots [0, w_compact_n) of d_w that are in it now (every other slot holds the whole layout) and what
+  // the last rate de-matcher run (stage 3) chose
+  bool                   pc_ok = false;
+  RmParityCompact        pc    = {};
+  DevBuf<uint32_t>       d_rm_tbl_pc;
+  uint32_t               w_compact_n  = 0;
+  int                    last_compact = 0;
   DevBuf<uint32_t>       d_tbcrc;
   DevBuf<cf32>           d_grid, d_ce, d_d;
   const uint8_t*         direct_tb = nullptr; // where the last decoder run (stage 4) assembled the transport blocks itself, or null: stage 5 has nothing to do then,
@@ -185,6 +193,24 @@ static srslte_hip_dl_rx_t* dl_rx_create_impl(const srslte_hip_dl_rx_cfg_t* cfg, 
   // decodes every block); the memsets run on the null stream, which the callers' non-blocking streams do not order against: wait here
   ok = ok && hipMemset(q->d_cb_ok, 0, (size_t)B * C) == hipSuccess && hipMemset(q->d_w, 0, sizeof(int16_t) * (size_t)q->in_stride * B * C) == hipSuccess &&
        hipMemset(q->d_cb_bytes, 0, (size_t)(K / 8) * B * C) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+  // The compact parity layout serves the 16-window 16-bit decoder on a buffer it reads in place, when no block of any subframe class gets
+  // more LLRs than the layout holds (the code-block split of sch.c:331-334). Environment SRSLTE_HIP_PARITY_COMPACT=0, read here: never (A/B, tests)
+  if (ok && !cw && !cfg->llr_8bit && q->W == 16 && K % 64 == 0 && ((reinterpret_cast<uintptr_t>(q->d_w.get()) | (q->in_stride * sizeof(int16_t))) & 15) == 0) {
+    const char*     e = getenv("SRSLTE_HIP_PARITY_COMPACT");
+    RmParityCompact c;
+    if (!(e && atoi(e) == 0) && rm_parity_compact(K, c)) {
+      const uint32_t Nl = (npt > 1 && !mimo) ? 2 : 1;
+      uint32_t       mx = 0;
+      for (int i = 0; i < 3; i++) {
+        const uint32_t Gp = (uint32_t)q->rg.nof_re[i] / Nl, n_e = Qm * Nl * (Gp / C) + (Gp % C > 1 ? Qm * Nl : 0); // some cb > C - gamma
+        mx = n_e > mx ? n_e : mx;
+      }
+      if (mx <= c.e_lim) {
+        ok        = rm_rx_table_upload_compact(K, q->pc, q->d_rm_tbl_pc) == SRSLTE_SUCCESS;
+        q->pc_ok = ok;
+      }
+    }
+  }
   if (!ok) {
     hip_log("[srslte_hip] dl_rx: initialisation failed\n");
     return nullptr;
@@ -260,6 +286,25 @@ static const void* dl_rx_ce_full(srslte_hip_dl_rx_t* q)
   return hipDeviceSynchronize() == hipSuccess ? q->d_ce_full : nullptr;
 }
 
+// d_w's slots in the compact parity layout back to the whole one (HARQ combining, a call the compact layout does not serve, the debug view)
+static int dl_rx_w_whole(srslte_hip_dl_rx_t* q, hipStream_t st)
+{
+  if (!q->w_compact_n) return SRSLTE_SUCCESS;
+  hipLaunchKernelGGL(rm_parity_expand_kernel, dim3(q->w_compact_n * q->seg.C), dim3(256), 0, st, q->d_w.get(), (int)q->in_stride, (int)q->seg.K1,
+                     (int)q->pc.phase[0], (int)q->pc.phase[1]);
+  LAUNCH_CHECK();
+  q->w_compact_n = 0;
+  return SRSLTE_SUCCESS;
+}
+
+extern "C" int srslte_hip_dl_rx_parity_compact(const srslte_hip_dl_rx_t* q) { return q ? q->last_compact : 0; }
+
+extern "C" uint32_t srslte_hip_rm_parity_compact_limit(uint32_t K)
+{
+  RmParityCompact c;
+  return lte_cb_index(K) >= 0 && lte_qpp_table[lte_cb_index(K)].K == K && rm_parity_compact(K, c) ? c.e_lim : 0;
+}
+
 extern "C" const void* srslte_hip_dl_rx_debug_buffer(const srslte_hip_dl_rx_t* q, int which)
 {
   if (!q) return nullptr;
@@ -270,7 +315,11 @@ extern "C" const void* srslte_hip_dl_rx_debug_buffer(const srslte_hip_dl_rx_t* q
     case 2: return q->d_res;
     case 3: return q->d_d;
     case 4: return q->d_e;
-    case 5: return q->d_w;
+    case 5: { // the whole layout, whatever the last call left
+      srslte_hip_dl_rx_t* m = const_cast<srslte_hip_dl_rx_t*>(q);
+      if (hipDeviceSynchronize() != hipSuccess || dl_rx_w_whole(m, 0) || hipDeviceSynchronize() != hipSuccess) return nullptr;
+      return q->d_w;
+    }
     case 6: return q->d_cb_iters;
     case 7: return q->d_cb_ok;
     case 8: return q->d_cb_bytes;
@@ -376,6 +425,18 @@ extern "C" int srslte_hip_dl_rx_stage(srslte_hip_dl_rx_t* q, int stage, const vo
       g.combine = q->harq_combine;
       g.skip    = q->harq_combine ? q->d_cb_ok : nullptr;
       const uint32_t* tbl = q->d_rm_tbl_rv[q->harq_rv];
+      // New data at rv 0 goes to the compact parity layout where the object has it. Anything else works on the whole layout: slots a compact
+      // call left are expanded first if this call combines with them or does not overwrite all of them
+      q->last_compact = q->pc_ok && q->harq_rv == 0 && !q->harq_combine;
+      if (q->last_compact) {
+        tbl     = q->d_rm_tbl_pc;
+        g.w_len = (int)q->pc.len;
+        q->w_compact_n = nof_sf > q->w_compact_n ? nof_sf : q->w_compact_n;
+      } else if (q->harq_combine || nof_sf < q->w_compact_n) {
+        if (int r = dl_rx_w_whole(q, st)) return r;
+      } else {
+        q->w_compact_n = 0;
+      }
       if (q->cfg.llr_8bit) return rm_rx_launch<int8_t>(rm_lds_bytes(g, 1), nof_sf * C, q->d_e, q->d_w, tbl, g, st);
       return rm_rx_launch<int16_t>(rm_lds_bytes(g, 2), nof_sf * C, q->d_e, q->d_w, tbl, g, st);
     }
@@ -386,6 +447,12 @@ extern "C" int srslte_hip_dl_rx_stage(srslte_hip_dl_rx_t* q, int stage, const vo
       TdecOpts o;
       o.tb_rem = q->d_tb_rem; o.tb_C = C; o.tb_syn = q->d_cb_syn;
       o.skip   = q->harq_combine ? q->d_cb_ok.get() : nullptr;
+      if (q->w_compact_n && q->w_compact_n < nof_sf) { // a decoder run over more slots than the last compact call filled
+        if (int r = dl_rx_w_whole(q, st)) return r;
+      }
+      if (q->w_compact_n) {
+        o.pc = 1; o.pc_phase[0] = q->pc.phase[0]; o.pc_phase[1] = q->pc.phase[1];
+      }
       q->direct_tb = nullptr;
       if (dl_rx_tb_direct(q, d_tb, tb_stride, d_tb_ok)) {
         o.tb_out = d_tb; o.tb_out_stride = tb_stride; o.tb_rb = q->tg.rlen / 8; o.tb_ok_out = d_tb_ok;

@@ -76,6 +76,11 @@ struct TdecOpts {
   // tb_Cof[v] blocks and row v (v < tb_B) or tb_rows0 + v - tb_B of tb_out / tb_ok_out; tb_rb is not read
   const uint8_t* tb_Cof   = nullptr;
   uint32_t       tb_width = 0, tb_B = 0, tb_rows0 = 0;
+  // Punctured parity at a quarter of its rows (pdsch_kernels.inc, rm_parity_compact): the input keeps row r of parity stream i only where
+  // r % 4 == pc_phase[i], as row r / 4 of K / 4 elements at K + 32 + i K / 4 of the block; the rows it does not keep count as zeros, the
+  // tails sit at K + 32 + K / 2. tdec_run_batch_w with the 16-window 16-bit decoder on an SB-layout input it reads in place (16-byte aligned
+  // base and stride) and K % 64 == 0 - anything else is refused
+  uint32_t pc = 0, pc_phase[2] = {0, 0};
 };
 // The largest block count of a transport block that TdecOpts::tb_Cof may hold: block r of C multiplies its CRC24A share by factor C-1-r of
 // tdec_tbA_table (tdec.hip), which holds 16 factors. A grants call with a larger transport block has tb_crc_bytes_kernel assemble and judge them.

@@ -236,6 +236,10 @@ struct TdecArgs {
   uint32_t        tb_out_stride, tb_rb; // tb_rb: payload bytes per block (K / 8 - 3 with several blocks, K / 8 with one)
   uint8_t*        tb_ok_out;   // [nof_cb / tb_C]
   uint32_t*       tb_acc;      // [nof_cb / tb_C][4]: syndrome xor, flags, finished blocks, -; zero between launches (the last block clears them)
+  // tdec_pair_kernel, optional (TdecOpts::pc): bit 0 - the in-place SB-layout input keeps every fourth row of its parity streams only: row r of
+  // stream i, r % 4 == phase i (bits 2-3 / 4-5), is row r / 4 of a region of K / 4 elements at K + 32 + i K / 4; every other row counts as zeros;
+  // the tails sit at K + 32 + K / 2. One word: the kernel's copy of this struct lives in scalar registers, which it has none to spare of
+  uint32_t        pc;
   unsigned long long* prof;    // -DTDEC_PROF builds: [nof_cb][10] cycles per phase, else unused
   int            dbg;          // timing experiments only (SRSLTE_HIP_TDEC_DBG): 1 skips the SISO sweeps, 2 the element-wise subtractions,
                                // 4 replaces the interleaver scatters by in-order stores, 8 points every branch-metric load at the zero buffer
@@ -1978,6 +1982,12 @@ int tdec_run_batch_w(srslte_hip_tdec_t* q, const void* d_input_any, int llr8, ui
   a.cb_map = opts.cb_map;
   a.start_iter = start_iter;
   a.tb_out = opts.tb_out; a.tb_out_stride = opts.tb_out_stride; a.tb_rb = opts.tb_rb; a.tb_ok_out = opts.tb_ok_out; a.tb_acc = q->d_tb_acc;
+  a.pc = 0;
+  if (opts.pc) { // the pair kernel alone, on an input it reads in place (`inplace` in tdec_pair_body), with rows of every stream starting at multiples of 4
+    const bool inplace = sb_layout && ((reinterpret_cast<uintptr_t>(d_input) | (in_stride * sizeof(int16_t))) & 15) == 0;
+    if (llr8 || W != 16 || old_map || K % 64 || !inplace || opts.pc_phase[0] > 3 || opts.pc_phase[1] > 3) return SRSLTE_ERROR_INVALID_INPUTS;
+    a.pc = 1u | (opts.pc_phase[0] << 2) | (opts.pc_phase[1] << 4);
+  }
   a.prof = nullptr;
 #ifdef TDEC_PROF
   static unsigned long long* d_prof = nullptr;
@@ -2035,7 +2045,7 @@ int tdec_run_groups(srslte_hip_tdec_t* q, const void* d_input_any, int llr8, uin
                     uint32_t nof_iterations, uint8_t* d_output, uint32_t out_stride, uint32_t* d_iters, uint8_t* d_crc_ok, hipStream_t st,
                     const TdecOpts& opts)
 {
-  if (!q || !d_input_any || !d_output || !groups || nof_groups > (uint32_t)TDEC_MAX_GROUPS || nof_iterations == 0) return SRSLTE_ERROR_INVALID_INPUTS;
+  if (!q || !d_input_any || !d_output || !groups || nof_groups > (uint32_t)TDEC_MAX_GROUPS || nof_iterations == 0 || opts.pc) return SRSLTE_ERROR_INVALID_INPUTS;
   // opts.tb_out with opts.tb_Cof: the decoders assemble the transport blocks (one mixed launch, 16-bit kinds only)
   const bool ragged = opts.tb_out != nullptr;
   if ((ragged && (!opts.tb_Cof || llr8)) || opts.start_iter || opts.tb_rem) return SRSLTE_ERROR_INVALID_INPUTS; // modes of the one-length call

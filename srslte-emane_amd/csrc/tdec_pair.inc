@@ -257,26 +257,36 @@ struct PSrc { // x / y arrays of block slot 0 / 1 (packed window pairs, 8 per st
   // its arrays over and over (cache hits instead of HBM traffic) and stores nothing
   bool dead0, dead1;
   int  rs; // dwords between two steps' rows: 8 (a block of 16 windows per slot) or 16 (one block of 32 windows: x1 / y1 = x0 / y0 + 8)
+  // Punctured parity at a quarter of its rows (TdecArgs::pc): ysel = 3 | yph << 2 - the y arrays hold row r, r % 4 == yph, at row r >> 2 and
+  // every other row is zero. Every staged run of rows starts at a multiple of 4 (Lw % 4 == 0: the 12-step blocks, the 40-step warm-ups, their
+  // 4-step remainders, the last short segment), so a lane's row has the same residue every time. ysel = 0: whole arrays. (One word, as
+  // TdecArgs::pc: with two the kernel spills a fourth pointer around the sweeps, 36 bytes of scratch instead of 28.)
+  int  ysel = 0;
 };
 struct PRows { int4 x, y; };
 __device__ __forceinline__ PRows p_stage_load(const PSrc& S, const PLane& L, int k_lo, int n)
 {
   const int   t = L.lane < 48 ? L.lane : L.lane - 16, row = min(t >> 2, n - 1);
   const bool  b1 = (t >> 1) & 1;
-  const int   off = (((S.dbg & 32) || (b1 ? S.dead1 : S.dead0)) ? row : k_lo + row) * S.rs + (t & 1) * 4;
+  const int   kr = (((S.dbg & 32) || (b1 ? S.dead1 : S.dead0)) ? row : k_lo + row); // a dead slot reads its first rows over and over
+  const int   off = kr * S.rs + (t & 1) * 4, offy = (kr >> (S.ysel & 2)) * S.rs + (t & 1) * 4; // ysel = 3: k_lo % 4 == 0
   const pk_t *xs = b1 ? S.x1 : S.x0, *ys = b1 ? S.y1 : S.y0;
   PRows       r;
   r.x = *reinterpret_cast<const int4*>(xs + off);
-  r.y = *reinterpret_cast<const int4*>(ys + off);
+  r.y = *reinterpret_cast<const int4*>(ys + offy);
   return r;
 }
 // AR: the y rows come straight from the parity array (int8 values in int16 containers) and move to the high bytes here (tdec.hip stage_store)
 template <int AR = 0>
-__device__ __forceinline__ void p_stage_store(pk_t* __restrict__ lds, const PLane& L, int n, const PRows& r)
+__device__ __forceinline__ void p_stage_store(pk_t* __restrict__ lds, const PLane& L, const PSrc& S, int n, const PRows& r)
 {
   if (L.lane < 48 && (L.lane >> 2) < n) {
     pk_t*      d = lds + P_SEG + (L.lane >> 2) * 16 + ((L.lane >> 1) & 1) * 8 + (L.lane & 1) * 4;
-    const int4 y = AR ? make_int4((r.y.x & 0x00FF00FF) << 8, (r.y.y & 0x00FF00FF) << 8, (r.y.z & 0x00FF00FF) << 8, (r.y.w & 0x00FF00FF) << 8) : r.y;
+    // a row the y arrays do not hold (PSrc::ysel) was loaded from its group's row all the same - no branch around a load - and is zero from
+    // here on, where the rows are first used
+    const bool held = ((L.lane >> 2) & (S.ysel & 3)) == (S.ysel >> 2); // 0: every row
+    const int4 y = AR ? make_int4((r.y.x & 0x00FF00FF) << 8, (r.y.y & 0x00FF00FF) << 8, (r.y.z & 0x00FF00FF) << 8, (r.y.w & 0x00FF00FF) << 8)
+                      : make_int4(held ? r.y.x : 0, held ? r.y.y : 0, held ? r.y.z : 0, held ? r.y.w : 0);
     *reinterpret_cast<int4*>(d)             = r.x;
     *reinterpret_cast<int4*>(d + P_ARR)     = y;
     *reinterpret_cast<int4*>(d + 2 * P_ARR) = // turbodecoder_win.h:472-491; 8-bit: a 0x7fff here is harmless (tdec.hip, M8)
@@ -313,7 +323,7 @@ __device__ __forceinline__ void p_run(pk_t* __restrict__ lds, const PLane& L, co
   // Two blocks of rows in flight, in two register sets used alternately (the loop is unrolled by two): rotating one set into the other
   // is a VALU move that has to wait for the load that was just issued
   auto body = [&](PRows& r, int b) {
-    p_stage_store<AR>(lds, L, PB, r);
+    p_stage_store<AR>(lds, L, S, PB, r);
     r = p_stage_load(S, L, lo(b + 2), PB);
     const int k0 = k_first + DIR * PB * b, n0 = n_first + DIR * PB * b;
     constexpr int PHR0 = DIR > 0 ? PH0 : (PH0 + 1) % 3; // phase of the block's row 0 (its lowest step)
@@ -350,7 +360,7 @@ __device__ __forceinline__ void p_rem(pk_t* __restrict__ lds, const PLane& L, co
 {
   if (cnt <= 0) return;
   const int k_lo = DIR > 0 ? k_first : k_first - (cnt - 1);
-  p_stage_store<AR>(lds, L, cnt, p_stage_load(S, L, k_lo, cnt));
+  p_stage_store<AR>(lds, L, S, cnt, p_stage_load(S, L, k_lo, cnt));
   const PV none = {0, 0};
   for (int j = 0; j < cnt; j++) {
     const int k = k_first + DIR * j, n = n_first + DIR * j;
@@ -495,7 +505,7 @@ __device__ __forceinline__ void p_siso(const PLane& L, const PSrc& S, const int1
       const int k0 = PB * j;
       int2 cl = make_int2(0, 0);
       if constexpr (P_CK_LDS > 0) cl = p_ck_get_lds(lds, j + 1, L.lane);
-      p_stage_store<AR>(lds, L, PB, sr);
+      p_stage_store<AR>(lds, L, S, PB, sr);
       if (P_CK_LDS > 0 && j + 1 <= P_CK_LDS) cb = cl;
       const PV Btop = {cb.x, cb.y}; // beta[k0 + PB] as stored: before its normalisation
       sr = rows_of(j + 2);
@@ -571,7 +581,7 @@ __device__ __forceinline__ void p_siso(const PLane& L, const PSrc& S, const int1
     // the last, shorter segment [PB nf, Lw): run-time phases
     if (t > 0) {
       const int k0 = PB * nf;
-      p_stage_store<AR>(lds, L, t, p_stage_load(S, L, k0, t));
+      p_stage_store<AR>(lds, L, S, t, p_stage_load(S, L, k0, t));
       const int2 cbt  = p_ck_get(lds, ck, top, L.lane); // read before the segment area below is written (LDS runs in order)
       const PV   Btop = {cbt.x, cbt.y}, none = {0, 0};
       PV         vb   = Btop;
@@ -711,13 +721,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TDEC_PAIR_MI
   const int  cb0 = live_a ? cb_a : cb_b, lcb0 = live_a ? lcb_a : lcb_b, cb1 = two ? cb_b : cb0, lcb1 = two ? lcb_b : lcb0;
   PBlk       b0 = {(size_t)cb0 * a.in_stride, (size_t)lcb0 * 7 * a.Kp, false, a.start_iter};
   PBlk       b1 = {(size_t)cb1 * a.in_stride, (size_t)lcb1 * 7 * a.Kp, !two, a.start_iter};
-  const int  tb = a.sb_layout ? 3 * (K + 32) : 3 * K;
-  const bool inplace = a.sb_layout && ((reinterpret_cast<uintptr_t>(a.in) | (a.in_stride * sizeof(int16_t))) & 15) == 0;
+  const int  tb = a.pc ? K + 32 + K / 2 : (a.sb_layout ? 3 * (K + 32) : 3 * K);
+  const bool inplace = a.sb_layout && ((reinterpret_cast<uintptr_t>(a.in) | (a.in_stride * sizeof(int16_t))) & 15) == 0; // a.pc: the host has checked it
   const size_t Kp = a.Kp;
   // arrays of a block: work arrays 0 .. 6 = syst, par0, par1, app1, app2, ext1, ext2; systematic / parity LLRs in place when possible
   auto WK   = [&](const PBlk& b, int i) -> int16_t* { return a.work + b.wk_off + (size_t)i * Kp; };
   auto SYST = [&](const PBlk& b) -> const int16_t* { return inplace ? a.in + b.in_off : a.work + b.wk_off; };
-  auto PAR  = [&](const PBlk& b, int i) -> const int16_t* { return inplace ? a.in + b.in_off + (size_t)(1 + i) * (K + 32) : a.work + b.wk_off + (size_t)(1 + i) * Kp; };
+  auto PAR  = [&](const PBlk& b, int i) -> const int16_t* { return a.work + b.wk_off + (size_t)(1 + i) * Kp; }; // extracted; in place: see the sweeps
 
   // ---- input extraction (turbodecoder_win.h:727-769 / turbodecoder_iter.h:58-68,84-91); a 16-byte aligned SB-layout buffer is read in place
   auto extract = [&](const PBlk& b, int h) {
@@ -778,12 +788,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(TDEC_PAIR_MI
       S.dead0 = b0.ok;
       S.dead1 = b1.ok && two; // a shadow slot repeats slot 0's stores: same values to the same addresses
       S.rs    = 8;
+      S.ysel  = a.pc ? 3 | (int)((a.pc >> (odd ? 4 : 2)) & 3) << 2 : 0;
       if (!odd) {
         S.x0 = P(n_iter ? WK(b0, 6) : SYST(b0)); S.x1 = P(n_iter ? WK(b1, 6) : SYST(b1));
-        S.y0 = P(PAR(b0, 0)); S.y1 = P(PAR(b1, 0));
       } else {
         S.x0 = P(WK(b0, 4)); S.x1 = P(WK(b1, 4));
-        S.y0 = P(PAR(b0, 1)); S.y1 = P(PAR(b1, 1));
+      }
+      if (inplace) { // the parity rows sit behind the systematic ones of the same buffer: one uniform offset from there
+        uint32_t po = a.pc ? (uint32_t)(K + 32) + (odd ? K / 4 : 0) : (odd ? 2u : 1u) * (K + 32);
+        // formed per pass: hoisted out of the pass loop, the pointers of both parities wait in scratch (36 bytes instead of 28; the
+        // kernel-resources test allows 32)
+        asm volatile("" : "+s"(po));
+        S.y0 = P(a.in + b0.in_off + po); S.y1 = P(a.in + b1.in_off + po);
+      } else {
+        S.y0 = P(PAR(b0, odd)); S.y1 = P(PAR(b1, odd));
       }
 #if P_XCHG_INT
       // outputs: even pass -> ext1, odd -> ext2. A stopped slot's decision metrics are in ext1 (odd number of passes) or in ext2 (even):
