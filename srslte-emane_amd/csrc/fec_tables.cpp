@@ -1,7 +1,8 @@
 // Host-side 3GPP TS 36.212 tables and index maps used by the FEC kernels of libsrslte_phy_hip.so:
 // Table 5.1.3-3 (K, f1, f2), code-block segmentation (5.1.2; replaces cbsegm.c:53-150), the QPP interleaver in
 // natural and window-interleaved index space (5.1.3.2.3; replaces tc_interl_lte.c:65-114) and the turbo
-// rate-matching circular-buffer order (5.1.4.1; replaces rm_turbo.c:160-233).
+// rate-matching circular-buffer order (5.1.4.1; replaces rm_turbo.c:160-233); the fixed-grant pipelines' packed scrambling rows and
+// transport-block CRC tables.
 #include "phy_hip_internal.hpp"
 #include <math.h>
 #include <string.h>
@@ -155,4 +156,40 @@ void lte_gold_sequence(uint32_t c_init, uint32_t len, std::vector<uint8_t>& c)
   }
   c.resize(len);
   for (uint32_t n = 0; n < len; n++) c[n] = (x1[n + Nc] + x2[n + Nc]) & 1;
+}
+
+// The scrambling rows of a fixed grant: c(n) of c_init(sf), n < nbits, per subframe index, bit n at bit n % 32 of word n / 32 of a row of `words`
+void lte_scr_table(const std::function<uint32_t(uint32_t)>& c_init, uint32_t nbits, uint32_t words, std::vector<uint32_t>& scr)
+{
+  std::vector<uint8_t> c;
+  scr.assign((size_t)10 * words, 0);
+  for (uint32_t sf = 0; sf < 10; sf++) {
+    lte_gold_sequence(c_init(sf), nbits, c);
+    for (uint32_t i = 0; i < nbits; i++) scr[(size_t)sf * words + (i >> 5)] |= (uint32_t)c[i] << (i & 31);
+  }
+}
+
+// TB CRC24A remainders x^(tbs+24-1-j) mod g, j < tbs + 24
+void lte_tbcrc_rem_table(uint32_t tbs, std::vector<uint32_t>& rem)
+{
+  rem.resize(tbs + 24);
+  uint32_t v = 1;
+  for (int j = (int)tbs + 23; j >= 0; j--) {
+    rem[j] = v;
+    v <<= 1;
+    if (v & 0x1000000) v ^= 0x1864CFB;
+  }
+}
+
+// ... per code block of C blocks of K bits, in the W-window decoder's array order (window-interleaved); 0 on the CB CRC bits
+void lte_tbcrc_win_table(const std::vector<uint32_t>& rem, uint32_t C, uint32_t K, uint32_t W, std::vector<uint32_t>& t)
+{
+  const uint32_t rlen = C == 1 ? K : K - 24, Lw = K / W;
+  t.assign((size_t)C * K, 0);
+  for (uint32_t c = 0; c < C; c++) {
+    for (uint32_t n = 0; n < rlen; n++) {
+      const uint32_t pos = c * rlen + n;
+      if (pos < rem.size()) t[(size_t)c * K + (n % Lw) * W + n / Lw] = rem[pos];
+    }
+  }
 }

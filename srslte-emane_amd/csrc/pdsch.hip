@@ -31,6 +31,7 @@
 
 // One translation unit (the kernels share templates, descriptor structs and anonymous-namespace helpers), kept in fragments by pipeline:
 #include "pdsch_kernels.inc"
+#include "sch_fixed.inc" // the fixed-grant receivers' transport-block back end; the transmitters' encoder half is in pusch_tx.inc
 #include "pdsch_rx.inc"
 #include "pdsch_rx_grants.inc"
 #include "sch_host.inc"

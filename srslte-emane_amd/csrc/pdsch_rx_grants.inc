@@ -105,7 +105,7 @@ static int grants_init(srslte_hip_dl_rx_t* q)
 {
   const uint32_t P = q->cfg.nof_prb, B = q->cfg.max_batch;
   q->gs.reset(new GrantsState());
-  return grants_alloc(q->gs.get(), 14 * 12 * P, (q->pg.nof_ports == 2 && q->pg.nof_rx == 2) ? 2 * B : B, q->seg.C, B, q->cfg.csi_enable != 0, 0);
+  return grants_alloc(q->gs.get(), 14 * 12 * P, (q->pg.nof_ports == 2 && q->pg.nof_rx == 2) ? 2 * B : B, q->cw[0].sch.seg.C, B, q->cfg.csi_enable != 0, 0);
 }
 
 // slot table of (K, rv) in the input layout of the decoder AUTO selects for K, stride = that layout's length rounded up to 32
@@ -334,7 +334,7 @@ static int grants_back_end(GrantsState* g, const GrantsBuild& bd, const SfDesc* 
 }
 
 static int grants_run(srslte_hip_dl_rx_t* q, const void* d_iq, uint32_t tti0, uint32_t nof_sf, const srslte_hip_dl_grant2_t* grants, uint8_t* d_tb,
-                      uint32_t tb_stride, uint8_t* d_tb_ok, void* stream, bool second_rows);
+                      uint32_t tb_stride, uint8_t* d_tb_ok, void* stream, bool second_rows, const cf32* grid_in = nullptr);
 
 extern "C" int srslte_hip_dl_rx_batch_grants(srslte_hip_dl_rx_t* q, const void* d_iq, uint32_t tti0, uint32_t nof_sf, const srslte_hip_dl_grant_t* grants,
                                              uint8_t* d_tb, uint32_t tb_stride, uint8_t* d_tb_ok, void* stream)
@@ -363,15 +363,13 @@ extern "C" int srslte_hip_dl_rx_grid_batch_grants2(srslte_hip_dl_rx_t* q, const 
                                                    uint8_t* d_tb, uint32_t tb_stride, uint8_t* d_tb_ok, void* stream)
 {
   if (!q || !d_grid) return SRSLTE_ERROR_INVALID_INPUTS;
-  q->grid_in  = (const cf32*)d_grid;
-  const int r = grants_run(q, d_grid, tti0, nof_sf, grants, d_tb, tb_stride, d_tb_ok, stream, true);
-  q->grid_in  = nullptr;
-  return r;
+  return grants_run(q, d_grid, tti0, nof_sf, grants, d_tb, tb_stride, d_tb_ok, stream, true, (const cf32*)d_grid);
 }
 
-// second_rows: rows nof_sf .. 2 nof_sf - 1 of d_tb / d_tb_ok exist (srslte_hip_dl_rx_batch_grants2 on a cell where two-layer grants can occur)
+// second_rows: rows nof_sf .. 2 nof_sf - 1 of d_tb / d_tb_ok exist (srslte_hip_dl_rx_batch_grants2 on a cell where two-layer grants can occur);
+// grid_in: resource grids supplied by the caller instead of d_iq's
 static int grants_run(srslte_hip_dl_rx_t* q, const void* d_iq, uint32_t tti0, uint32_t nof_sf, const srslte_hip_dl_grant2_t* grants, uint8_t* d_tb,
-                      uint32_t tb_stride, uint8_t* d_tb_ok, void* stream, bool second_rows)
+                      uint32_t tb_stride, uint8_t* d_tb_ok, void* stream, bool second_rows, const cf32* grid_in)
 {
   if (!q || !d_iq || !grants || !d_tb || !d_tb_ok || nof_sf > q->cfg.max_batch || tb_stride < q->cfg.tbs / 8 + 6) return SRSLTE_ERROR_INVALID_INPUTS;
   if (q->cfg.tx_scheme) {
@@ -451,8 +449,9 @@ static int grants_run(srslte_hip_dl_rx_t* q, const void* d_iq, uint32_t tti0, ui
   // slots of subframes nof_sf .. B - 1 keep an earlier call's descriptors
   const uint8_t* d_cof = grants_direct_cof(g, h, d, V, l8, [&](uint32_t v) { return v % B < nof_sf; });
   // stages 0, 1: OFDM demodulation and channel estimation do not depend on the grants
-  int r = q->grid_in ? SRSLTE_SUCCESS : srslte_hip_dl_rx_stage(q, 0, d_iq, tti0, nof_sf, d_tb, tb_stride, d_tb_ok, stream); // grids from the caller: no OFDM stage
-  if (!r) r = srslte_hip_dl_rx_stage(q, 1, d_iq, tti0, nof_sf, d_tb, tb_stride, d_tb_ok, stream);
+  const DlRxCall call = {grid_in, {}};
+  int r = grid_in ? SRSLTE_SUCCESS : dl_rx_stage(q, 0, d_iq, tti0, nof_sf, d_tb, tb_stride, d_tb_ok, stream, call); // grids from the caller: no OFDM stage
+  if (!r) r = dl_rx_stage(q, 1, d_iq, tti0, nof_sf, d_tb, tb_stride, d_tb_ok, stream, call);
   if (r) return r;
   const uint32_t nrows = (second_rows && V > B) ? 2 * nof_sf : nof_sf; // transport-block rows of the call
   { // RE lists and scrambling sequences (with the second codewords' when a two-layer grant is among them) and the descriptors: one launch,
@@ -471,7 +470,7 @@ static int grants_run(srslte_hip_dl_rx_t* q, const void* d_iq, uint32_t tti0, ui
     PdschGeom pg = q->pg;
     pg.desc = d.sf; pg.tti0 = (int)tti0; pg.max_re = (int)g->max_re; pg.max_bits = (int)g->max_bits; pg.csi = g->d_csi; pg.csi_max = g->d_csi_max;
     if (g->d_csi_max) HIP_TRY(hipMemsetAsync(g->d_csi_max, 0, sizeof(uint32_t) * V, st));
-    const cf32* grid = q->grid_in ? q->grid_in : q->d_grid;
+    const cf32* grid = grid_in ? grid_in : q->d_grid;
     if (pg.nof_ports == 4) {
       if (l8) {
         hipLaunchKernelGGL(pdsch_demod_div4_kernel<int8_t>, dim3(ceil_div((int)g->max_re, 1024), nof_sf), dim3(256), 0, st, grid, (const cf32*)q->d_ce,

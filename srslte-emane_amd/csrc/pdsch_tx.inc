@@ -246,12 +246,10 @@ struct srslte_hip_dl_tx {
   srslte_hip_dl_tx_cfg_t cfg  = {};
   srslte_hip_ofdm_t*     ofdm = nullptr;
   srslte_hip_chest_dl_t* crs  = nullptr; // for its CRS table
-  srslte_hip_cbsegm_t    seg  = {};
-  PuschTxGeom            cg   = {}; // CRC attachment / segmentation geometry (shared kernels)
+  SchTxFixed             enc;
   PdschTxGeom            g    = {};
-  DevBuf<uint32_t>       d_scr, d_rm[4], d_tbcrc, d_idx[3];
+  DevBuf<uint32_t>       d_scr, d_idx[3];
   DevBuf<int32_t>        d_src[3][4];
-  DevBuf<uint8_t>        d_cb, d_parity, d_sys_tail;
   DevBuf<cf32>           d_y, d_grid;
   std::unique_ptr<TxGrantsState> gs; // srslte_hip_dl_tx_batch_grants / _grants2: created on first use
   float                  rho_a = 0.f; // pdsch.c:525: the precoders' `scaling`
@@ -272,11 +270,8 @@ extern "C" srslte_hip_dl_tx_t* srslte_hip_dl_tx_create(const srslte_hip_dl_tx_cf
   }
   std::unique_ptr<srslte_hip_dl_tx> q(new srslte_hip_dl_tx());
   q->cfg = *cfg;
-  if (srslte_hip_cbsegm(&q->seg, cfg->tbs) || q->seg.F || q->seg.C2 || (cfg->tbs % 8)) {
-    hip_log("[srslte_hip] dl_tx: TBS %u needs filler bits or two code-block sizes; not supported on device yet\n", cfg->tbs);
-    return nullptr;
-  }
-  const uint32_t P = cfg->nof_prb, nre = 12 * P, B = cfg->max_batch, C = q->seg.C, K = q->seg.K1, Qm = 2 * (uint32_t)cfg->mod;
+  if (fixed_grant_segmentation("dl_tx", cfg->tbs, &q->enc.seg)) return nullptr;
+  const uint32_t P = cfg->nof_prb, nre = 12 * P, B = cfg->max_batch, C = q->enc.seg.C, K = q->enc.seg.K1, Qm = 2 * (uint32_t)cfg->mod;
   const uint32_t nsl = (cfg->cp_ext || cfg->mbsfn) ? 6 : 7; // symbols per slot (an MBSFN subframe has 12 on any cell)
   const uint32_t lstart = cfg->cfi + (P < 10 ? 1 : 0), npt = cfg->nof_ports ? cfg->nof_ports : 1, glen = 2 * nsl * nre;
   if (cfg->mbsfn && (npt != 1 || cfg->tdd || cfg->mbsfn_area_id > 255 || cfg->non_mbsfn_region < 1 || cfg->non_mbsfn_region > 2 || cfg->p_a != 0.f)) {
@@ -318,20 +313,14 @@ extern "C" srslte_hip_dl_tx_t* srslte_hip_dl_tx_create(const srslte_hip_dl_tx_cf
     }
   }
   const uint32_t max_bits = max_re * Qm, scr_words = (max_bits + 31) / 32;
-  if (ok) { // srslte_sequence_pdsch (sequences.c:58-60), codeword 0
-    std::vector<uint32_t> scr((size_t)10 * scr_words, 0);
-    std::vector<uint8_t>  c;
-    for (uint32_t sf = 0; sf < 10; sf++) {
-      lte_gold_sequence(cfg->mbsfn ? (sf << 9) + cfg->mbsfn_area_id /* srslte_sequence_pmch, sequences.c:76-80 */
-                                   : ((uint32_t)cfg->rnti << 14) + (sf << 9) + cfg->cell_id, max_bits, c);
-      for (uint32_t i = 0; i < max_bits; i++) scr[(size_t)sf * scr_words + (i >> 5)] |= (uint32_t)c[i] << (i & 31);
-    }
+  if (ok) { // srslte_sequence_pdsch (sequences.c:58-60), codeword 0; srslte_sequence_pmch (sequences.c:76-80) for an MBSFN pipeline
+    std::vector<uint32_t> scr;
+    lte_scr_table([&](uint32_t sf) { return cfg->mbsfn ? (sf << 9) + cfg->mbsfn_area_id : ((uint32_t)cfg->rnti << 14) + (sf << 9) + cfg->cell_id; }, max_bits,
+                  scr_words, scr);
     ok = upload(q->d_scr, scr) == SRSLTE_SUCCESS;
   }
-  ok = ok && rm_tx_table_upload(K, 0, q->d_rm[0]) == SRSLTE_SUCCESS;
-  PuschTxGeom& cg = q->cg;
-  cg.C = (int)C; cg.K = (int)K; cg.tbs = (int)cfg->tbs; cg.rlenB = (int)((C == 1 ? K : K - 24) / 8); cg.cb_stride = (int)((K / 8 + 15) & ~15u);
-  cg.par_stride = (int)((K / 4 + 1 + 15) & ~15u);
+  ok = ok && q->enc.init(B) == SRSLTE_SUCCESS;
+  const PuschTxGeom& cg = q->enc.cg;
   g.mbsfn_pilots = cfg->mbsfn && ok ? (const cf32*)srslte_hip_chest_dl_mbsfn_pilots(q->crs, (uint16_t)cfg->mbsfn_area_id) : nullptr;
   g.mbsfn_nref   = 18 * (int)P;
   g.tdd_s6 = -1; // the fixed-grant calls are FDD (srslte_hip_dl_tx_batch refuses a TDD cell); the grants mode sets its own
@@ -341,8 +330,7 @@ extern "C" srslte_hip_dl_tx_t* srslte_hip_dl_tx_create(const srslte_hip_dl_tx_cf
   const float rho_a = powf(10.0f, cfg->p_a / 20.0f) * (npt == 1 ? 1.0f : sqrtf(2.0f)); // pdsch.c:525
   g.gain            = npt == 1 ? rho_a : rho_a / sqrtf(2.0f);                          // precoding.c:1859-1860
   q->rho_a          = rho_a;
-  ok = ok && !q->d_tbcrc.alloc(B) && !q->d_cb.alloc((size_t)cg.cb_stride * B * C) && !q->d_parity.alloc((size_t)cg.par_stride * B * C) &&
-       !q->d_sys_tail.alloc((size_t)B * C) && !q->d_y.alloc((size_t)max_re * B * npt) && !q->d_grid.alloc((size_t)glen * B * npt);
+  ok = ok && !q->d_y.alloc((size_t)max_re * B * npt) && !q->d_grid.alloc((size_t)glen * B * npt);
   if (!ok) {
     hip_log("[srslte_hip] dl_tx: initialisation failed\n");
     return nullptr;
@@ -354,8 +342,8 @@ extern "C" const void* srslte_hip_dl_tx_debug_buffer(const srslte_hip_dl_tx_t* q
 {
   if (!q) return nullptr;
   switch (which) {
-    case 0: return q->d_cb;
-    case 1: return q->d_parity;
+    case 0: return q->enc.d_cb;
+    case 1: return q->enc.d_parity;
     case 2: return q->d_y;
     case 3: return q->d_grid;
   }
@@ -371,23 +359,14 @@ extern "C" int srslte_hip_dl_tx_batch(srslte_hip_dl_tx_t* q, const uint8_t* d_tb
     hip_log("[srslte_hip] dl_tx: a TDD cell is served by srslte_hip_dl_tx_batch_grants (per-PDSCH grants)\n");
     return SRSLTE_ERROR;
   }
-  if (!q->d_rm[rv]) {
-    if (int r = rm_tx_table_upload(q->seg.K1, rv, q->d_rm[rv])) return r;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  PuschTxGeom cg = q->cg;
-  cg.tb_stride   = (int)tb_stride;
-  hipLaunchKernelGGL(pusch_tx_tbcrc_kernel, dim3(nof_sf), dim3(256), 0, st, d_tb, q->d_tbcrc, cg);
-  LAUNCH_CHECK();
-  hipLaunchKernelGGL(pusch_tx_seg_kernel, dim3(cg.C, nof_sf), dim3(256), 0, st, d_tb, (const uint32_t*)q->d_tbcrc, q->d_cb, cg);
-  LAUNCH_CHECK();
-  int r = srslte_hip_tcod_encode_bytes_batch(q->d_cb, (uint32_t)cg.cb_stride, q->d_parity, (uint32_t)cg.par_stride, q->d_sys_tail, (uint32_t)cg.K,
-                                             nof_sf * (uint32_t)cg.C, stream);
-  if (r) return r;
+  hipStream_t     st   = (hipStream_t)stream;
+  const uint32_t* d_rm = nullptr;
+  int             r    = q->enc.encode(d_tb, tb_stride, nof_sf, rv, stream, &d_rm);
+  if (r || !d_rm) return r ? r : SRSLTE_ERROR; // tbs = 0: create makes an object, this call fails, as ever (it used to fail at a launch of 0 blocks)
   PdschTxGeom g = q->g;
   g.tti0        = (int)tti0;
-  hipLaunchKernelGGL(pdsch_tx_mod_kernel, dim3(ceil_div(g.max_re / g.nof_ports, 256), nof_sf), dim3(256), 0, st, (const uint8_t*)q->d_cb,
-                     (const uint8_t*)q->d_parity, (const uint8_t*)q->d_sys_tail, (const uint32_t*)q->d_rm[rv], (const uint32_t*)q->d_scr, q->d_y, g);
+  hipLaunchKernelGGL(pdsch_tx_mod_kernel, dim3(ceil_div(g.max_re / g.nof_ports, 256), nof_sf), dim3(256), 0, st, (const uint8_t*)q->enc.d_cb,
+                     (const uint8_t*)q->enc.d_parity, (const uint8_t*)q->enc.d_sys_tail, d_rm, (const uint32_t*)q->d_scr, q->d_y, g);
   LAUNCH_CHECK();
   hipLaunchKernelGGL(pdsch_tx_map_kernel, dim3(ceil_div(g.grid_len, 256), nof_sf * g.nof_ports), dim3(256), 0, st, (const cf32*)q->d_y,
                      (const cf32*)srslte_hip_chest_dl_pilots(q->crs), q->d_grid, 8 * (int)q->cfg.nof_prb, g);
@@ -408,7 +387,7 @@ static int dl_tx_grants_init(srslte_hip_dl_tx_t* q, uint32_t V, uint32_t W)
   g->V      = V;
   g->W      = W;
   g->max_re = 14 * 12 * P;
-  if (g->enc_init(W, q->seg.C, (g->max_re * 8 + 31) / 32 + 2, (sizeof(GrantDev) + sizeof(TxDesc)) * W) || g->d_relist.alloc((size_t)g->max_re * V) ||
+  if (g->enc_init(W, q->enc.seg.C, (g->max_re * 8 + 31) / 32 + 2, (sizeof(GrantDev) + sizeof(TxDesc)) * W) || g->d_relist.alloc((size_t)g->max_re * V) ||
       g->d_y.alloc((size_t)g->max_re * V * npt))
     return SRSLTE_ERROR;
   for (int port = 0; port < npt; port++) { // the CRS as srslte_hip_dl_tx_create maps them
@@ -447,7 +426,7 @@ static int dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32
                               const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream, bool bcast = false)
 {
   if (!q || !d_tb || !d_iq || !grants || nof_sf > q->cfg.max_batch) return SRSLTE_ERROR_INVALID_INPUTS;
-  const uint32_t V = q->cfg.max_grants ? q->cfg.max_grants : q->cfg.max_batch, P = q->cfg.nof_prb, cell_id = q->cfg.cell_id, Cmax = q->seg.C;
+  const uint32_t V = q->cfg.max_grants ? q->cfg.max_grants : q->cfg.max_batch, P = q->cfg.nof_prb, cell_id = q->cfg.cell_id, Cmax = q->enc.seg.C;
   const int      npt = q->g.nof_ports;
   if (nof_grants > V) return SRSLTE_ERROR_INVALID_INPUTS;
   if (q->cfg.mbsfn) {

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.hpp"
 #include "srslte_hip/phy_hip.h"
+#include <functional>
 #include <vector>
 
 struct FftFactors {
@@ -27,6 +28,11 @@ extern const QppRow lte_qpp_table[188];
 int  lte_cb_index(uint32_t K);
 void lte_qpp_tables(uint32_t K, uint32_t W, std::vector<uint16_t>& fwd, std::vector<uint16_t>& rev);
 void lte_rm_rx_table(uint32_t K, uint32_t rv, std::vector<uint32_t>& d_index); // circular-buffer order -> 3*i+s
+// fec_tables.cpp: tables of the fixed-grant pipelines - the packed scrambling rows [10][words] of c_init(sf), nbits bits each; the TB CRC24A
+// remainders x^(tbs+23-j) mod g [tbs + 24]; the same per code block in the W-window decoder's array order [C][K]
+void lte_scr_table(const std::function<uint32_t(uint32_t)>& c_init, uint32_t nbits, uint32_t words, std::vector<uint32_t>& scr);
+void lte_tbcrc_rem_table(uint32_t tbs, std::vector<uint32_t>& rem);
+void lte_tbcrc_win_table(const std::vector<uint32_t>& rem, uint32_t C, uint32_t K, uint32_t W, std::vector<uint32_t>& t);
 
 // chest.hip: srslte_chest_ul_estimate_pusch for a list of PUSCHs of one (L_prb, n_dmrs): item i = {subframe of the batch, PRB offset of slot 0 / 1,
 // row of d_res}; d_items on the device

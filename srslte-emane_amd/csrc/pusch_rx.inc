@@ -384,18 +384,13 @@ struct srslte_hip_ul_rx {
   srslte_hip_ul_rx_cfg_t cfg   = {};
   srslte_hip_ofdm_t*     ofdm  = nullptr;
   srslte_hip_chest_ul_t* chest = nullptr;
-  srslte_hip_tdec_t*     tdec  = nullptr;
   srslte_hip_cbsegm_t    seg   = {};
   PuschGeom              pg    = {};
-  RmGeom                 rg    = {};
-  TbGeom                 tg    = {};
-  uint32_t               W = 0, in_stride = 0;
-  DevBuf<uint32_t>       d_scr, d_tbcrc, d_tb_rem, d_cb_syn, d_cb_iters;
-  DevBuf<uint32_t>       d_rm_tbl_rv[4]; // rate de-matching tables: [0] made with the object, 1-3 on first use
+  std::unique_ptr<SchRxFixed> sch; // from the LLR rows d_g to transport blocks; none (seg.C = 0) for a PUSCH that carries only a CQI report
+  DevBuf<uint32_t>       d_scr;
   DevBuf<cf32>           d_grid, d_ce, d_z, d_d;
   DevBuf<float>          d_res; // [B] x srslte_hip_chest_ul_res_t
-  DevBuf<int16_t>        d_g, d_w;
-  DevBuf<uint8_t>        d_cb_bytes, d_cb_ok;
+  DevBuf<int16_t>        d_g;   // [B][nbits] + 16; the CQI report's Qp_cqi Qm LLRs in front of the UL-SCH's in every row
   DevBuf<int>            d_ack_sum; // [B][4] ACK, then [B][4] RI
   DevBuf<uint8_t>        d_ack;     // [B][2] HARQ-ACK decisions of the last call, then [B][2] rank indications
   DevBuf<uint8_t>        d_cqi;     // [B][64] CQI report bits of the last call, then [B] CRC flags
@@ -405,7 +400,6 @@ struct srslte_hip_ul_rx {
   {
     srslte_hip_ofdm_destroy(ofdm);
     srslte_hip_chest_ul_destroy(chest);
-    srslte_hip_tdec_destroy(tdec);
   }
 };
 
@@ -431,10 +425,7 @@ extern "C" srslte_hip_ul_rx_t* srslte_hip_ul_rx_create(const srslte_hip_ul_rx_cf
   }
   std::unique_ptr<srslte_hip_ul_rx> q(new srslte_hip_ul_rx());
   q->cfg = *cfg;
-  if (srslte_hip_cbsegm(&q->seg, cfg->tbs) || q->seg.F || q->seg.C2 || (cfg->tbs % 8)) {
-    hip_log("[srslte_hip] ul_rx: TBS %u needs filler bits or two code-block sizes; not supported on device yet\n", cfg->tbs);
-    return nullptr;
-  }
+  if (fixed_grant_segmentation("ul_rx", cfg->tbs, &q->seg)) return nullptr;
   // tbs = 0: a PUSCH without UL-SCH data carries a CQI report and nothing to decode (srslte_ulsch_decode, sch.c:1031-1065)
   if (cfg->tbs == 0 && cfg->cqi_len == 0) {
     hip_log("[srslte_hip] ul_rx: neither a transport block nor a CQI report\n");
@@ -448,52 +439,28 @@ extern "C" srslte_hip_ul_rx_t* srslte_hip_ul_rx_create(const srslte_hip_ul_rx_cf
   const int      Qp_cqi = Qp_ri >= 0 ? pusch_cqi_qprime(cfg->cqi_len, cfg->I_offset_cqi, cfg->L_prb, nsymb, C * K, (uint32_t)Qp_ri) : -1;
   q->ofdm  = srslte_hip_ofdm_create((int)P, cfg->cp_ext ? 0 : 1, 1);
   q->chest = srslte_hip_chest_ul_create(cfg->cell_id, P, cfg->cp_ext ? 0 : 1, &cfg->dmrs_cfg);
-  q->tdec  = C ? srslte_hip_tdec_create(K, B * C) : nullptr;
-  bool ok  = q->ofdm && q->chest && (q->tdec || !C) && srslte_hip_ofdm_set_freq_shift(q->ofdm, -0.5f) == SRSLTE_SUCCESS; // enb_ul.c:62-63 (no normalisation)
+  bool ok  = q->ofdm && q->chest && srslte_hip_ofdm_set_freq_shift(q->ofdm, -0.5f) == SRSLTE_SUCCESS; // enb_ul.c:62-63 (no normalisation)
   if (ok) { // srslte_sequence_pusch (sequences.c:65-67), one sequence per subframe index
-    std::vector<uint32_t> scr((size_t)10 * scr_words, 0);
-    std::vector<uint8_t>  c;
-    for (uint32_t sf = 0; sf < 10; sf++) {
-      lte_gold_sequence(((uint32_t)cfg->rnti << 14) + (sf << 9) + cfg->cell_id, nbits, c);
-      for (uint32_t i = 0; i < nbits; i++) scr[(size_t)sf * scr_words + (i >> 5)] |= (uint32_t)c[i] << (i & 31);
-    }
+    std::vector<uint32_t> scr;
+    lte_scr_table([&](uint32_t sf) { return ((uint32_t)cfg->rnti << 14) + (sf << 9) + cfg->cell_id; }, nbits, scr_words, scr);
     ok = upload(q->d_scr, scr) == SRSLTE_SUCCESS;
-  }
-  q->W         = C ? srslte_hip_tdec_autoimp_get_subblocks(K) : 0;
-  q->in_stride = C ? (srslte_hip_tdec_input_len(K, q->W != 0) + 31) & ~31u : 0;
-  if (ok && C) ok = rm_rx_table_upload(K, 0, q->W, q->in_stride, q->d_rm_tbl_rv[0]) == SRSLTE_SUCCESS; // as for the PDSCH
-  if (ok && C) {
-    std::vector<uint32_t> rem(cfg->tbs + 24);
-    uint32_t              v = 1;
-    for (int j = (int)cfg->tbs + 23; j >= 0; j--) {
-      rem[j] = v;
-      v <<= 1;
-      if (v & 0x1000000) v ^= 0x1864CFB;
-    }
-    ok = upload(q->d_tbcrc, rem) == SRSLTE_SUCCESS;
-    if (ok && q->W) {
-      const uint32_t        rlen = C == 1 ? K : K - 24, Lw = K / q->W;
-      std::vector<uint32_t> t((size_t)C * K, 0);
-      for (uint32_t c = 0; c < C; c++) {
-        for (uint32_t n = 0; n < rlen; n++) {
-          const uint32_t pos = c * rlen + n;
-          if (pos < cfg->tbs + 24) t[(size_t)c * K + (n % Lw) * q->W + n / Lw] = rem[pos];
-        }
-      }
-      ok = upload(q->d_tb_rem, t) == SRSLTE_SUCCESS && !q->d_cb_syn.alloc((size_t)B * C);
-    }
   }
   const size_t glen = (size_t)2 * nsl * 12 * P;
   ok = ok && !q->d_grid.alloc(glen * B) && !q->d_ce.alloc(glen * B) && hipMemset(q->d_ce, 0, sizeof(cf32) * glen * B) == hipSuccess &&
        !q->d_z.alloc((size_t)nof_re * B) && !q->d_d.alloc((size_t)nof_re * B) && !q->d_res.alloc((size_t)5 * B) && !q->d_g.alloc((size_t)nbits * B + 16) &&
-       (!C || (!q->d_w.alloc((size_t)q->in_stride * B * C) && !q->d_cb_bytes.alloc((size_t)(K / 8) * B * C) && !q->d_cb_ok.alloc((size_t)B * C) &&
-               hipMemset(q->d_cb_ok, 0, (size_t)B * C) == hipSuccess &&
-               hipMemset(q->d_w, 0, sizeof(int16_t) * (size_t)q->in_stride * B * C) == hipSuccess && !q->d_cb_iters.alloc((size_t)B * C))) &&
        !q->d_ack_sum.alloc((size_t)8 * B) && !q->d_ack.alloc((size_t)4 * B) && hipMemset(q->d_ack, 0, (size_t)4 * B) == hipSuccess &&
        pusch_ack_qprime(cfg->ack_len, cfg->I_offset_ack, cfg->L_prb, nsymb, C * K, false, cfg->cqi_len, cfg->I_offset_cqi) >= 0 &&
        Qp_ri >= 0 && (uint32_t)Qp_ri < nof_re && Qp_cqi >= 0 && (C ? (uint32_t)(Qp_ri + Qp_cqi) + C < nof_re : (uint32_t)(Qp_ri + Qp_cqi) == nof_re) &&
        !q->d_cqi.alloc((size_t)65 * B) && hipMemset(q->d_cqi, 0, (size_t)65 * B) == hipSuccess;
   ok = ok && hipDeviceSynchronize() == hipSuccess; // the memsets above ran on the null stream
+  if (ok && C) { // as for the PDSCH, with the whole parity layout and the assembly kernel
+    // the UL-SCH is rate-matched to what the RI and the CQI report leave (sch.c:1157-1160) and follows the report in the stream
+    SchRxFixed::Cfg sc = {}; // 16-bit LLRs, no CSI weighting, neither permission
+    sc.tbs = cfg->tbs; sc.max_batch = B; sc.max_iterations = cfg->max_iterations; sc.Qm = Qm; sc.Nl = 1; sc.e_off = (uint32_t)Qp_cqi * Qm; sc.max_bits = nbits;
+    sc.nof_re[0] = sc.nof_re[1] = sc.nof_re[2] = nof_re - (uint32_t)Qp_ri - (uint32_t)Qp_cqi;
+    q->sch.reset(new SchRxFixed());
+    ok = q->sch->init(sc) == SRSLTE_SUCCESS;
+  }
   if (!ok) {
     hip_log("[srslte_hip] ul_rx: initialisation failed\n");
     return nullptr;
@@ -503,13 +470,7 @@ extern "C" srslte_hip_ul_rx_t* srslte_hip_ul_rx_create(const srslte_hip_ul_rx_cf
   q->pg.ack.O = (int)cfg->ack_len; q->pg.ack.Qprime = pusch_ack_qprime(cfg->ack_len, cfg->I_offset_ack, cfg->L_prb, nsymb, C * K, false, cfg->cqi_len, cfg->I_offset_cqi);
   q->pg.ack_sum = q->d_ack_sum;
   q->pg.ri.O = (int)cfg->ri_len; q->pg.ri.Qprime = Qp_ri; q->pg.ri_sum = q->d_ack_sum + 4 * B;
-  q->rg.C = (int)C; q->rg.K = (int)K; q->rg.Qm = (int)Qm; q->rg.max_bits = (int)nbits; q->rg.w_stride = (int)q->in_stride; q->rg.Nl = 1;
-  q->rg.out_len = (int)(3 * K + 12);
-  // the UL-SCH is rate-matched to what the RI and the CQI report leave (sch.c:1157-1160) and follows the report in the stream
-  q->rg.nof_re[0] = q->rg.nof_re[1] = q->rg.nof_re[2] = (int)nof_re - Qp_ri - Qp_cqi;
-  q->rg.e_off = Qp_cqi * (int)Qm;
   q->Qp_cqi   = Qp_cqi;
-  q->tg.C = (int)C; q->tg.K = (int)K; q->tg.tbs = (int)cfg->tbs; q->tg.rlen = (int)(C <= 1 ? K : K - 24); q->tg.cb_stride = (int)(K / 8);
   return q.release();
 }
 
@@ -522,10 +483,10 @@ extern "C" const void* srslte_hip_ul_rx_debug_buffer(const srslte_hip_ul_rx_t* q
     case 2: return q->d_res;
     case 3: return q->d_d;
     case 4: return q->d_g;
-    case 5: return q->d_w;
-    case 6: return q->d_cb_iters;
-    case 7: return q->d_cb_ok;
-    case 8: return q->d_cb_bytes;
+    case 5: return q->sch ? q->sch->d_w.get() : nullptr;
+    case 6: return q->sch ? q->sch->d_cb_iters.get() : nullptr;
+    case 7: return q->sch ? q->sch->d_cb_ok.get() : nullptr;
+    case 8: return q->sch ? q->sch->d_cb_bytes.get() : nullptr;
     case 9: return q->d_z;
     case 10: return q->d_ack;
     // per-PUSCH grants mode: estimator results, de-precoded symbols (at each PUSCH's offset), LLR rows, pass counts per block slot
@@ -554,12 +515,8 @@ extern "C" int srslte_hip_ul_rx_batch_harq(srslte_hip_ul_rx_t* q, const void* d_
   if (!q || !d_iq || !d_tb || !d_tb_ok || rv > 3 || nof_sf > q->cfg.max_batch || tb_stride < q->cfg.tbs / 8 + 6) return SRSLTE_ERROR_INVALID_INPUTS;
   if (nof_sf == 0) return SRSLTE_SUCCESS;
   hipStream_t    st = (hipStream_t)stream;
-  const uint32_t C = q->seg.C, K = q->seg.K1;
-  if (C && !q->d_rm_tbl_rv[rv]) {
-    if (int rc = rm_rx_table_upload(K, rv, q->W, q->in_stride, q->d_rm_tbl_rv[rv])) return rc;
-  }
-  const uint32_t* d_rm_tbl = q->d_rm_tbl_rv[rv];
-  const int combine = new_data ? 0 : 1;
+  const SchHarq  harq = {rv, new_data ? 0 : 1};
+  if (q->sch && q->sch->ensure_rv(rv)) return SRSLTE_ERROR; // made on first use, before anything is queued
   int            r = srslte_hip_ofdm_rx_sf_batch(q->ofdm, d_iq, q->d_grid, (int)nof_sf, stream);
   if (r) return r;
   r = srslte_hip_chest_ul_estimate_pusch_batch_hop(q->chest, tti0, q->cfg.L_prb, q->cfg.n_prb, (uint32_t)q->pg.n_prb1, q->cfg.n_dmrs, q->d_grid, q->d_ce, q->d_res, (int)nof_sf,
@@ -588,37 +545,17 @@ extern "C" int srslte_hip_ul_rx_batch_harq(srslte_hip_ul_rx_t* q, const void* d_
     LAUNCH_CHECK();
   }
   if (q->cfg.cqi_len) { // the report in front of the UL-SCH (sch.c:1031-1056)
-    hipLaunchKernelGGL(pusch_cqi_decode_kernel, dim3(nof_sf), dim3(256), 0, st, (const int16_t*)q->d_g, q->rg.max_bits, q->Qp_cqi * q->rg.Qm,
+    hipLaunchKernelGGL(pusch_cqi_decode_kernel, dim3(nof_sf), dim3(256), 0, st, (const int16_t*)q->d_g, g.nsymb * g.M_sc * g.Qm, q->Qp_cqi * g.Qm,
                        (int)q->cfg.cqi_len, q->d_cqi, q->d_cqi + 64 * q->cfg.max_batch, (const PuschDesc*)nullptr);
     LAUNCH_CHECK();
   }
-  if (C == 0) { // no UL-SCH data: nothing to de-match or decode, no transport block (sch.c:1062-1065)
+  if (!q->sch) { // no UL-SCH data: nothing to de-match or decode, no transport block (sch.c:1062-1065)
     HIP_TRY(hipMemsetAsync(d_tb_ok, 0, nof_sf, st));
     return SRSLTE_SUCCESS;
   }
-  RmGeom rg = q->rg;
-  rg.tti0   = (int)tti0;
-  rg.combine = combine;
-  rg.skip    = combine ? q->d_cb_ok : nullptr;
-  if (int rc = rm_rx_launch<int16_t>(rm_lds_bytes(rg, 2), nof_sf * C, q->d_g, q->d_w, d_rm_tbl, rg, st)) return rc;
-  TdecOpts o;
-  o.tb_rem = q->d_tb_rem; o.tb_C = C; o.tb_syn = q->d_cb_syn;
-  o.skip   = combine ? q->d_cb_ok.get() : nullptr;
-  r = tdec_run_batch_w(q->tdec, q->d_w, 0, q->in_stride, q->W != 0, K, -1, nof_sf * C, q->cfg.max_iterations, C > 1 ? 0x1800063u : 0x1864CFBu,
-                       C > 1 ? K : q->cfg.tbs + 24, q->d_cb_bytes, K / 8, q->d_cb_iters, q->d_cb_ok, st, o);
-  if (r) return r;
-  TbGeom tg    = q->tg;
-  tg.tb_stride = (int)tb_stride;
-  tg.iters     = q->d_cb_iters;
-  if (q->d_tb_rem) {
-    hipLaunchKernelGGL(tb_asm_kernel, dim3(nof_sf), dim3(256), 0, st, (const uint8_t*)q->d_cb_bytes, (const uint8_t*)q->d_cb_ok,
-                       (const uint32_t*)q->d_cb_syn, d_tb, d_tb_ok, tg);
-  } else {
-    hipLaunchKernelGGL(tb_crc_kernel, dim3(nof_sf), dim3(512), 0, st, (const uint8_t*)q->d_cb_bytes, (const uint8_t*)q->d_cb_ok,
-                       (const uint32_t*)q->d_tbcrc, d_tb, d_tb_ok, tg);
-  }
-  LAUNCH_CHECK();
-  return SRSLTE_SUCCESS;
+  if (int rc = q->sch->dematch(q->d_g, tti0, nof_sf, harq, st)) return rc;
+  if (int rc = q->sch->decode(nof_sf, harq, d_tb, tb_stride, d_tb_ok, st)) return rc;
+  return q->sch->assemble(nof_sf, d_tb, tb_stride, d_tb_ok, st);
 }
 
 static int ul_rx_grants_init(srslte_hip_ul_rx_t* q, uint32_t V, uint32_t max_re)

@@ -186,6 +186,47 @@ struct TxLevels { float v[5][16]; };   // constellation levels of one axis per s
 
 } // namespace
 
+// The encoder half of a fixed-grant transmitter, downlink or uplink: TB CRC24A, segmentation + CB CRC24B and the turbo encoder of a batch into
+// code-block slots of one block length, and the rate-matching tables the modulation kernels read them through
+struct SchTxFixed {
+  srslte_hip_cbsegm_t seg = {};
+  PuschTxGeom         cg  = {}; // CRC attachment / segmentation geometry: C, K, tbs, rlenB, cb_stride, par_stride
+  DevBuf<uint32_t>    d_tbcrc;
+  DevBuf<uint32_t>    d_rm_rv[4]; // rate-matching tables: [0] made by init, 1-3 on first use
+  DevBuf<uint8_t>     d_cb, d_parity, d_sys_tail;
+  // seg has passed fixed_grant_segmentation; seg.C = 0 (a PUSCH without UL-SCH data): no code-block slots, no table
+  int init(uint32_t B)
+  {
+    const uint32_t C = seg.C, K = seg.K1;
+    cg.C = (int)C; cg.K = (int)K; cg.tbs = (int)seg.tbs; cg.rlenB = (int)((C <= 1 ? K : K - 24) / 8); cg.cb_stride = (int)((K / 8 + 15) & ~15u);
+    cg.par_stride = (int)((K / 4 + 1 + 15) & ~15u);
+    if (d_tbcrc.alloc(B)) return SRSLTE_ERROR;
+    if (C == 0) return SRSLTE_SUCCESS;
+    const bool bad = rm_tx_table_upload(K, 0, d_rm_rv[0]) || d_cb.alloc((size_t)cg.cb_stride * B * C) || d_parity.alloc((size_t)cg.par_stride * B * C) ||
+                     d_sys_tail.alloc((size_t)B * C);
+    return bad ? SRSLTE_ERROR : SRSLTE_SUCCESS;
+  }
+  // rows of d_tb -> d_cb / d_parity / d_sys_tail of slots 0 .. nof_sf C - 1; *d_rm: the rate-matching table of rv (null and no launch for C = 0)
+  int encode(const uint8_t* d_tb, uint32_t tb_stride, uint32_t nof_sf, uint32_t rv, void* stream, const uint32_t** d_rm)
+  {
+    *d_rm = nullptr;
+    if (cg.C == 0) return SRSLTE_SUCCESS; // no UL-SCH data (tbs = 0): no CRC, no segmentation, no encoder (sch.c:1157)
+    if (!d_rm_rv[rv]) {
+      if (int r = rm_tx_table_upload(seg.K1, rv, d_rm_rv[rv])) return r;
+    }
+    *d_rm          = d_rm_rv[rv];
+    hipStream_t st = (hipStream_t)stream;
+    PuschTxGeom g  = cg;
+    g.tb_stride    = (int)tb_stride;
+    hipLaunchKernelGGL(pusch_tx_tbcrc_kernel, dim3(nof_sf), dim3(256), 0, st, d_tb, d_tbcrc, g);
+    LAUNCH_CHECK();
+    hipLaunchKernelGGL(pusch_tx_seg_kernel, dim3(g.C, nof_sf), dim3(256), 0, st, d_tb, (const uint32_t*)d_tbcrc, d_cb, g);
+    LAUNCH_CHECK();
+    return srslte_hip_tcod_encode_bytes_batch(d_cb, (uint32_t)g.cb_stride, d_parity, (uint32_t)g.par_stride, d_sys_tail, (uint32_t)g.K, nof_sf * (uint32_t)g.C,
+                                              stream);
+  }
+};
+
 // The encoder half of a transmit grants mode, downlink or uplink: ncw codewords of up to Cmax code blocks in slots spaced for the largest block
 // length, their scrambling rows and CRC words, the call's descriptor block and the rate-matching tables made on first use
 struct TxGrantsEnc {
@@ -230,11 +271,10 @@ struct srslte_hip_ul_tx {
   srslte_hip_ul_tx_cfg_t cfg  = {};
   srslte_hip_ofdm_t*     ofdm = nullptr;
   srslte_hip_chest_ul_t* dmrs = nullptr;
-  srslte_hip_cbsegm_t    seg  = {};
+  SchTxFixed             enc;
   PuschTxGeom            g    = {};
-  DevBuf<uint32_t>       d_scr, d_tbcrc;
-  DevBuf<uint32_t>       d_rm_rv[4]; // rate-matching tables: [0] made with the object, 1-3 on first use
-  DevBuf<uint8_t>        d_cb, d_parity, d_sys_tail, d_qcqi;
+  DevBuf<uint32_t>       d_scr;
+  DevBuf<uint8_t>        d_qcqi;
   DevBuf<uint16_t>       d_cqi_rm;
   DevBuf<cf32>           d_d, d_z, d_grid;
   std::unique_ptr<UlTxGrantsState> gs; // srslte_hip_ul_tx_batch_grants: created on first use
@@ -257,11 +297,8 @@ extern "C" srslte_hip_ul_tx_t* srslte_hip_ul_tx_create(const srslte_hip_ul_tx_cf
   }
   std::unique_ptr<srslte_hip_ul_tx> q(new srslte_hip_ul_tx());
   q->cfg = *cfg;
-  if (srslte_hip_cbsegm(&q->seg, cfg->tbs) || q->seg.F || q->seg.C2 || (cfg->tbs % 8)) {
-    hip_log("[srslte_hip] ul_tx: TBS %u needs filler bits or two code-block sizes; not supported on device yet\n", cfg->tbs);
-    return nullptr;
-  }
-  const uint32_t P = cfg->nof_prb, B = cfg->max_batch, C = q->seg.C, K = q->seg.K1, Qm = 2 * (uint32_t)cfg->mod, M_sc = 12 * cfg->L_prb;
+  if (fixed_grant_segmentation("ul_tx", cfg->tbs, &q->enc.seg)) return nullptr;
+  const uint32_t P = cfg->nof_prb, B = cfg->max_batch, C = q->enc.seg.C, K = q->enc.seg.K1, Qm = 2 * (uint32_t)cfg->mod, M_sc = 12 * cfg->L_prb;
   const uint32_t nsl = cfg->cp_ext ? 6 : 7, nsymb = 2 * (nsl - 1) - (cfg->shortened ? 1 : 0); // ra_ul.c:234 nof_symb
   const uint32_t nof_re = nsymb * M_sc, nbits = nof_re * Qm, scr_words = (nbits + 31) / 32;
   PuschTxGeom&   g = q->g;
@@ -277,8 +314,7 @@ extern "C" srslte_hip_ul_tx_t* srslte_hip_ul_tx_create(const srslte_hip_ul_tx_cf
     hip_log("[srslte_hip] ul_tx: invalid HARQ-ACK configuration\n");
     return nullptr;
   }
-  g.tbs = (int)cfg->tbs; g.rlenB = (int)((C <= 1 ? K : K - 24) / 8); g.cb_stride = (int)((K / 8 + 15) & ~15u);
-  g.par_stride = (int)((K / 4 + 1 + 15) & ~15u); g.rm_len = (int)(3 * K + 12);
+  g.tbs = (int)cfg->tbs; g.rm_len = (int)(3 * K + 12);
   g.ri.O = (int)cfg->ri_len; g.ri.Qprime = pusch_ack_qprime(cfg->ri_len, cfg->I_offset_ri, cfg->L_prb, nsymb, C * K, true, cfg->cqi_len, cfg->I_offset_cqi);
   if (g.ri.Qprime < 0 || (uint32_t)g.ri.Qprime >= nof_re) {
     hip_log("[srslte_hip] ul_tx: invalid rank-indication configuration\n");
@@ -298,15 +334,11 @@ extern "C" srslte_hip_ul_tx_t* srslte_hip_ul_tx_create(const srslte_hip_ul_tx_cf
   bool ok = q->ofdm && q->dmrs && srslte_hip_ofdm_set_normalize(q->ofdm, 1) == SRSLTE_SUCCESS &&
             srslte_hip_ofdm_set_freq_shift(q->ofdm, 0.5f) == SRSLTE_SUCCESS; // ue_ul.c:63-64
   if (ok) { // srslte_sequence_pusch (sequences.c:65-67)
-    std::vector<uint32_t> scr((size_t)10 * scr_words, 0);
-    std::vector<uint8_t>  c;
-    for (uint32_t sf = 0; sf < 10; sf++) {
-      lte_gold_sequence(((uint32_t)cfg->rnti << 14) + (sf << 9) + cfg->cell_id, nbits, c);
-      for (uint32_t i = 0; i < nbits; i++) scr[(size_t)sf * scr_words + (i >> 5)] |= (uint32_t)c[i] << (i & 31);
-    }
-    ok = upload(q->d_scr, scr) == SRSLTE_SUCCESS;
+    std::vector<uint32_t> scr;
+    lte_scr_table([&](uint32_t sf) { return ((uint32_t)cfg->rnti << 14) + (sf << 9) + cfg->cell_id; }, nbits, scr_words, scr);
+    ok = upload(q->d_scr, scr) == SRSLTE_SUCCESS && q->enc.init(B) == SRSLTE_SUCCESS;
   }
-  if (ok && C) ok = rm_tx_table_upload(K, 0, q->d_rm_rv[0]) == SRSLTE_SUCCESS; // rate matching, rv 0
+  g.rlenB = q->enc.cg.rlenB; g.cb_stride = q->enc.cg.cb_stride; g.par_stride = q->enc.cg.par_stride;
   if (ok && cfg->cqi_len > 11) { // the CQI report's rate matching: cqi_rm_conv_order read circularly up to Q
     const std::vector<uint16_t> w = cqi_rm_conv_order(cfg->cqi_len);
     const int                   Q = g.Qp_cqi * (int)Qm;
@@ -316,9 +348,7 @@ extern "C" srslte_hip_ul_tx_t* srslte_hip_ul_tx_create(const srslte_hip_ul_tx_cf
   }
   if (ok && cfg->cqi_len) ok = !q->d_qcqi.alloc((size_t)g.cqi_stride * B + 16);
   const size_t glen = (size_t)2 * nsl * 12 * P;
-  ok = ok && !q->d_tbcrc.alloc(B) &&
-       (!C || (!q->d_cb.alloc((size_t)g.cb_stride * B * C) && !q->d_parity.alloc((size_t)g.par_stride * B * C) && !q->d_sys_tail.alloc((size_t)B * C))) &&
-       !q->d_d.alloc((size_t)nof_re * B) && !q->d_z.alloc((size_t)nof_re * B) && !q->d_grid.alloc(glen * B);
+  ok = ok && !q->d_d.alloc((size_t)nof_re * B) && !q->d_z.alloc((size_t)nof_re * B) && !q->d_grid.alloc(glen * B);
   if (!ok) {
     hip_log("[srslte_hip] ul_tx: initialisation failed\n");
     return nullptr;
@@ -330,12 +360,12 @@ extern "C" const void* srslte_hip_ul_tx_debug_buffer(const srslte_hip_ul_tx_t* q
 {
   if (!q) return nullptr;
   switch (which) {
-    case 0: return q->d_cb;
-    case 1: return q->d_parity;
+    case 0: return q->enc.d_cb;
+    case 1: return q->enc.d_parity;
     case 2: return q->d_d;
     case 3: return q->d_z;
     case 4: return q->d_grid;
-    case 5: return q->d_tbcrc;
+    case 5: return q->enc.d_tbcrc;
   }
   return nullptr;
 }
@@ -377,10 +407,6 @@ extern "C" int srslte_hip_ul_tx_batch_rv(srslte_hip_ul_tx_t* q, const uint8_t* d
   hipStream_t st = (hipStream_t)stream;
   const void* d_r = nullptr;
   if (int r = chest_ul_dmrs_table(q->dmrs, q->cfg.L_prb, q->cfg.n_dmrs, &d_r)) return r;
-  if (q->seg.C && !q->d_rm_rv[rv]) {
-    if (int r = rm_tx_table_upload(q->seg.K1, rv, q->d_rm_rv[rv])) return r;
-  }
-  const uint32_t* d_rm = q->d_rm_rv[rv];
   PuschTxGeom g = q->g;
   g.tti0        = (int)tti0;
   g.tb_stride   = (int)tb_stride;
@@ -392,18 +418,11 @@ extern "C" int srslte_hip_ul_tx_batch_rv(srslte_hip_ul_tx_t* q, const uint8_t* d
                        (const uint16_t*)q->d_cqi_rm);
     LAUNCH_CHECK();
   }
-  int r = SRSLTE_SUCCESS;
-  if (g.C) { // no UL-SCH data (tbs = 0): no CRC, no segmentation, no encoder (sch.c:1157)
-    hipLaunchKernelGGL(pusch_tx_tbcrc_kernel, dim3(nof_sf), dim3(256), 0, st, d_tb, q->d_tbcrc, g);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(pusch_tx_seg_kernel, dim3(g.C, nof_sf), dim3(256), 0, st, d_tb, (const uint32_t*)q->d_tbcrc, q->d_cb, g);
-    LAUNCH_CHECK();
-    r = srslte_hip_tcod_encode_bytes_batch(q->d_cb, (uint32_t)g.cb_stride, q->d_parity, (uint32_t)g.par_stride, q->d_sys_tail, (uint32_t)g.K,
-                                           nof_sf * (uint32_t)g.C, stream);
-    if (r) return r;
-  }
-  hipLaunchKernelGGL(pusch_tx_mod_kernel, dim3(ceil_div(g.M_sc, 256), g.nsymb, nof_sf), dim3(256), 0, st, (const uint8_t*)q->d_cb,
-                     (const uint8_t*)q->d_parity, (const uint8_t*)q->d_sys_tail, d_rm, (const uint32_t*)q->d_scr, q->d_d, g);
+  const uint32_t* d_rm = nullptr;
+  int             r    = q->enc.encode(d_tb, tb_stride, nof_sf, rv, stream, &d_rm);
+  if (r) return r;
+  hipLaunchKernelGGL(pusch_tx_mod_kernel, dim3(ceil_div(g.M_sc, 256), g.nsymb, nof_sf), dim3(256), 0, st, (const uint8_t*)q->enc.d_cb,
+                     (const uint8_t*)q->enc.d_parity, (const uint8_t*)q->enc.d_sys_tail, d_rm, (const uint32_t*)q->d_scr, q->d_d, g);
   LAUNCH_CHECK();
   r = srslte_hip_dft_precoding_batch(q->d_d, q->d_z, q->cfg.L_prb, g.nsymb * nof_sf, 1, stream); // srslte_dft_precoding_init_tx: forward, 1/sqrt(N)
   if (r) return r;

@@ -98,7 +98,7 @@ static int ul_tx_grants_init(srslte_hip_ul_tx_t* q, uint32_t V)
   g->V          = V;
   g->max_sym    = nsymb * 12 * P;
   g->cqi_stride = (g->max_sym * 6 + 15) & ~15u; // a report may take the whole allocation (min(.., M_sc N_symb - Q'_ri), uci.c:264-281)
-  if (g->enc_init(V, q->seg.C, (g->max_sym * 6 + 31) / 32 + 2, (sizeof(GrantDev) + sizeof(TxDesc) + sizeof(PuschTxDesc)) * V) ||
+  if (g->enc_init(V, q->enc.seg.C, (g->max_sym * 6 + 31) / 32 + 2, (sizeof(GrantDev) + sizeof(TxDesc) + sizeof(PuschTxDesc)) * V) ||
       g->d_qcqi.alloc((size_t)g->cqi_stride * V) || g->d_d.alloc((size_t)g->max_sym * V) || g->d_z.alloc((size_t)g->max_sym * V))
     return SRSLTE_ERROR;
   return SRSLTE_SUCCESS;
@@ -113,7 +113,7 @@ extern "C" int srslte_hip_ul_tx_batch_grants(srslte_hip_ul_tx_t* q, const uint8_
 {
   if (!q || !d_tb || !d_iq || !grants || nof_sf > q->cfg.max_batch) return SRSLTE_ERROR_INVALID_INPUTS;
   const uint32_t V = q->cfg.max_grants ? q->cfg.max_grants : q->cfg.max_batch, P = q->cfg.nof_prb, nsymb = (uint32_t)q->g.nsymb;
-  if (nof_grants > V || q->seg.C == 0) return SRSLTE_ERROR_INVALID_INPUTS; // an object made without a transport-block size has no encoder buffers
+  if (nof_grants > V || q->enc.seg.C == 0) return SRSLTE_ERROR_INVALID_INPUTS; // an object made without a transport-block size has no encoder buffers
   if (nof_sf == 0) return SRSLTE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
   if (!q->gs && ul_tx_grants_init(q, V)) { // a failed start leaves no half-made state behind

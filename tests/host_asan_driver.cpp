@@ -1,6 +1,7 @@
 // TEST INFRASTRUCTURE: exercises the pure host side of libsrslte_phy_hip.so (fec_tables.cpp: segmentation, QPP interleaver tables, rate
-// de-matching tables) under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU (GPU sanitizers are not available on
-// the pool). Built and run by tests/test_host_sanitizers.py; prints a checksum so that the run cannot be optimised away.
+// de-matching tables, the fixed-grant pipelines' scrambling rows and TB CRC tables) under AddressSanitizer + UndefinedBehaviorSanitizer on
+// the CPU (GPU sanitizers are not available on the pool). Built and run by tests/test_host_sanitizers.py; prints a checksum so that the run
+// cannot be optimised away.
 #include "phy_hip_internal.hpp"
 #include "srslte_hip/srslte_compat.h"
 #include <stdarg.h>
@@ -75,6 +76,64 @@ static int refsignal_and_filters(unsigned long long* sum)
   return 0;
 }
 
+// the fixed-grant pipelines' host tables (fec_tables.cpp), each sized by the builder itself: an index past a row or a table is a heap overflow
+static int fixed_grant_tables(unsigned long long* sum)
+{
+  // scrambling rows: bit counts around a word boundary, one that fills the last word exactly, with and without the receivers' spare word
+  for (uint32_t nbits : {1u, 31u, 32u, 33u, 7 * 32u}) {
+    for (uint32_t spare = 0; spare < 2; spare++) {
+      const uint32_t        words = (nbits + 31) / 32 + spare;
+      std::vector<uint32_t> scr;
+      std::vector<uint8_t>  c;
+      lte_scr_table([](uint32_t sf) { return (0x1234u << 14) + (sf << 9) + 17; }, nbits, words, scr);
+      if (scr.size() != 10 * (size_t)words) return 20;
+      for (uint32_t sf = 0; sf < 10; sf++) {
+        lte_gold_sequence((0x1234u << 14) + (sf << 9) + 17, nbits, c);
+        for (uint32_t i = 0; i < 32 * words; i++) {
+          if (((scr[(size_t)sf * words + i / 32] >> (i % 32)) & 1) != (i < nbits ? c[i] : 0u)) return 21;
+        }
+        *sum += scr[(size_t)sf * words];
+      }
+    }
+  }
+  // the TB CRC tables of the smallest and the largest transport block the fixed-grant check admits (a multiple of 8 bits, no filler bits, one
+  // block size), found here by that rule; and the windowed table of one block (16 windows) and of two
+  uint32_t lo = 0, hi = 0, two = 0;
+  for (uint32_t tbs = 8; tbs <= 110000; tbs += 8) {
+    srslte_hip_cbsegm_t s;
+    if (srslte_hip_cbsegm(&s, tbs) || s.F || s.C2) continue;
+    lo = lo ? lo : tbs;
+    hi = tbs;
+    two = (!two && s.C == 2 && s.K1 % 16 == 0) ? tbs : two;
+  }
+  if (!lo || !two || hi <= two) return 22;
+  for (uint32_t tbs : {lo, two, hi}) {
+    srslte_hip_cbsegm_t s;
+    if (srslte_hip_cbsegm(&s, tbs)) return 23;
+    std::vector<uint32_t> rem, t;
+    lte_tbcrc_rem_table(tbs, rem);
+    if (rem.size() != tbs + 24 || rem[tbs + 23] != 1 || rem[tbs - 1] != 0x864CFB) return 24; // x^0, x^24 mod g
+    for (uint32_t W : {8u, 16u}) {
+      if (s.K1 % W) continue;
+      lte_tbcrc_win_table(rem, s.C, s.K1, W, t);
+      if (t.size() != (size_t)s.C * s.K1) return 25;
+      unsigned long long x = 0, y = 0; // every remainder once, the block CRC bits 0
+      for (uint32_t v : t) x += v;
+      for (uint32_t v : rem) y += v;
+      if (x != y) return 26;
+      *sum += x + t[0];
+    }
+  }
+  // C = 1 with 16 windows: position n of the block at (n % Lw) 16 + n / Lw
+  std::vector<uint32_t> rem, t;
+  lte_tbcrc_rem_table(808, rem);
+  lte_tbcrc_win_table(rem, 1, 832, 16, t);
+  for (uint32_t n = 0; n < 832; n++) {
+    if (t[(n % 52) * 16 + n / 52] != rem[n]) return 27;
+  }
+  return 0;
+}
+
 int main(void)
 {
   unsigned long long sum = 0;
@@ -109,6 +168,7 @@ int main(void)
     sum += fw[1];
   }
   if (int rc = refsignal_and_filters(&sum)) return rc;
+  if (int rc = fixed_grant_tables(&sum)) return rc;
   printf("host sanitizer run ok, checksum %llu\n", sum);
   return 0;
 }
