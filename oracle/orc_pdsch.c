@@ -197,10 +197,19 @@ void orc_predecoding_csi(const orc_cf_t* const* h, float* csi, int nof_rx, int n
   }
 }
 
+static int32_t csi_trunc(float v)
+{ /* the C casts (int16_t)(float) / (int8_t)(float) of pdsch.c:611,:681 as the x86 build compiles them: cvttss2si to 32 bits (0x80000000 for a
+     NaN and out of range, cvt_trunc of orc_modem.c), of which the cast keeps the low bits - written out, not left to this compiler's cast */
+  return (v > -2147483904.0f && v < 2147483648.0f) ? (int32_t)v : INT32_MIN;
+}
+
 static int16_t csi_weight(float csi, float scale)
-{ /* _mm_cvtps_pi16: round to nearest even, then saturate to int16 */
-  float v = nearbyintf(csi * scale);
-  return (int16_t)(v > 32767.0f ? 32767 : (v < -32768.0f ? -32768 : (int)v));
+{ /* _mm_cvtps_pi16 = cvtps2pi on both halves (round to nearest even; 0x80000000 for a NaN and for every value out of range, as cvt_rne of
+     orc_modem.c) + packssdw. A subframe of zeros has csi = csi_max = 0: 0 * (32767 / 0) is a NaN, the weight -32768, and -32768 x -32768
+     >> 16 makes 16384 of the demapper's -32768. */
+  float   v = csi * scale;
+  int32_t w = (v > -2147483904.0f && v < 2147483648.0f) ? (int32_t)nearbyintf(v) : INT32_MIN;
+  return (int16_t)(w > 32767 ? 32767 : (w < -32768 ? -32768 : w));
 }
 
 void orc_csi_correction_s(int16_t* e, const float* csi, int nsym, int mod)
@@ -254,7 +263,7 @@ void orc_csi_correction_s(int16_t* e, const float* csi, int nsym, int mod)
   const float inv = 1.0f / csi_max; /* the -Ofast build multiplies by the hoisted reciprocal */
   for (i /= qm; i < nsym; i++) {
     const float c = csi[i] * inv;
-    for (int k = 0; k < qm; k++) e[qm * i + k] = (int16_t)((float)e[qm * i + k] * c);
+    for (int k = 0; k < qm; k++) e[qm * i + k] = (int16_t)csi_trunc((float)e[qm * i + k] * c);
   }
 }
 
@@ -272,7 +281,7 @@ void orc_csi_correction_b(int8_t* e, const float* csi, int nsym, int mod)
   const float inv = 1.0f / csi_max; /* the -Ofast build multiplies by the hoisted reciprocal */
   for (int i = 0; i < nsym; i++) {
     const float c = csi[i] * inv;
-    for (int k = 0; k < qm; k++) e[qm * i + k] = (int8_t)((float)e[qm * i + k] * c);
+    for (int k = 0; k < qm; k++) e[qm * i + k] = (int8_t)csi_trunc((float)e[qm * i + k] * c);
   }
 }
 

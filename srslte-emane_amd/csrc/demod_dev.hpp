@@ -12,8 +12,14 @@ __device__ __forceinline__ int   sat16(int v) { return v > 32767 ? 32767 : (v < 
 __device__ __forceinline__ int   sat8(int v) { return v > 127 ? 127 : (v < -128 ? -128 : v); }
 __device__ __forceinline__ short abs16(short v) { return (short)(v < 0 ? -v : v); }          // _mm_abs_epi16: -32768 stays
 __device__ __forceinline__ signed char abs8(signed char v) { return (signed char)(v < 0 ? -v : v); }
-__device__ __forceinline__ int   rne(float v) { return __float2int_rn(v); }                    // _mm_cvtps_epi32
-__device__ __forceinline__ int   trunc_i(float v) { return (int)v; }                           // _mm_cvttps_epi32 / C cast
+// Float to int32 as the reference's x86 build converts: cvtps2dq / cvttps2dq, and the cvttss2si / cvttsd2si behind a C cast to a narrower
+// type, return 0x80000000 for a NaN and for every value outside int32; the saturating packs make -32768 / -128 of that, a cast keeps its
+// low bits (0). v_cvt_i32_f32 returns 0 for a NaN and saturates towards the sign of the value: the same for a negative overflow, not for a
+// NaN or a positive one - what a capture of exact zeros (0 / 0 in the equaliser) feeds every conversion behind it.
+__device__ __forceinline__ int   x86_i32(bool below_2_31, int converted) { return below_2_31 ? converted : (int)0x80000000; }
+__device__ __forceinline__ int   rne(float v) { return x86_i32(v < 2147483648.0f, __float2int_rn(v)); } // _mm_cvtps_epi32
+__device__ __forceinline__ int   trunc_i(float v) { return x86_i32(v < 2147483648.0f, (int)v); }        // _mm_cvttps_epi32 / C cast
+__device__ __forceinline__ int   trunc_i(double v) { return x86_i32(v < 2147483648.0, (int)v); }        // C cast of a double expression
 
 // ---- float ----------------------------------------------------------------
 __device__ __forceinline__ void demod_f(int mod, cf32 s, float* o)
@@ -55,7 +61,7 @@ __device__ __forceinline__ void demod_s(int mod, cf32 s, int i, int nsym, short*
 {
   const bool body = i < 4 * (nsym / 4); // SSE bodies of 16/64QAM take 4 symbols per step
   switch (mod) {
-    case MOD_BPSK: o[0] = (short)((double)(-100.0f * (s.x + s.y)) / 1.4142135623730951); break;
+    case MOD_BPSK: o[0] = (short)trunc_i((double)(-100.0f * (s.x + s.y)) / 1.4142135623730951); break;
     case MOD_QPSK: {
       const float g = (float)(-100 * 1.4142135623730951);
       // vector_simd.c:392-427: 16 floats per AVX2 step (cvtt + saturating pack), scalar C cast for the rest (wraps on x86)
@@ -95,10 +101,10 @@ __device__ __forceinline__ void demod_s(int mod, cf32 s, int i, int nsym, short*
     default: {
       float       re = -s.x, im = -s.y;
       const float o1 = 8.0f / 13.038404810405298f, o2 = 4.0f / 13.038404810405298f, o3 = 2.0f / 13.038404810405298f;
-      o[0] = (short)(1000 * re); o[1] = (short)(1000 * im);
-      re = fabsf(re) - o1; im = fabsf(im) - o1; o[2] = (short)(1000 * re); o[3] = (short)(1000 * im);
-      re = fabsf(re) - o2; im = fabsf(im) - o2; o[4] = (short)(1000 * re); o[5] = (short)(1000 * im);
-      re = fabsf(re) - o3; im = fabsf(im) - o3; o[6] = (short)(1000 * re); o[7] = (short)(1000 * im);
+      o[0] = (short)trunc_i(1000 * re); o[1] = (short)trunc_i(1000 * im);
+      re = fabsf(re) - o1; im = fabsf(im) - o1; o[2] = (short)trunc_i(1000 * re); o[3] = (short)trunc_i(1000 * im);
+      re = fabsf(re) - o2; im = fabsf(im) - o2; o[4] = (short)trunc_i(1000 * re); o[5] = (short)trunc_i(1000 * im);
+      re = fabsf(re) - o3; im = fabsf(im) - o3; o[6] = (short)trunc_i(1000 * re); o[7] = (short)trunc_i(1000 * im);
     }
   }
 }
@@ -108,7 +114,7 @@ __device__ __forceinline__ void demod_b(int mod, cf32 s, int i, int nsym, signed
 {
   const bool body = i < 8 * (nsym / 8); // SSE bodies take 8 symbols per step
   switch (mod) {
-    case MOD_BPSK: o[0] = (signed char)((double)(-20.0f * (s.x + s.y)) / 1.4142135623730951); break;
+    case MOD_BPSK: o[0] = (signed char)trunc_i((double)(-20.0f * (s.x + s.y)) / 1.4142135623730951); break;
     case MOD_QPSK: {
       const float g = (float)(-20 * 1.4142135623730951);
       // vector_simd.c:431-497: 16 floats per SSE step, scalar C cast for the rest
@@ -147,10 +153,10 @@ __device__ __forceinline__ void demod_b(int mod, cf32 s, int i, int nsym, signed
     default: {
       float       re = -s.x, im = -s.y;
       const float o1 = 8.0f / 13.038404810405298f, o2 = 4.0f / 13.038404810405298f, o3 = 2.0f / 13.038404810405298f;
-      o[0] = (signed char)(50 * re); o[1] = (signed char)(50 * im);
-      re = fabsf(re) - o1; im = fabsf(im) - o1; o[2] = (signed char)(50 * re); o[3] = (signed char)(50 * im);
-      re = fabsf(re) - o2; im = fabsf(im) - o2; o[4] = (signed char)(50 * re); o[5] = (signed char)(50 * im);
-      re = fabsf(re) - o3; im = fabsf(im) - o3; o[6] = (signed char)(50 * re); o[7] = (signed char)(50 * im);
+      o[0] = (signed char)trunc_i(50 * re); o[1] = (signed char)trunc_i(50 * im);
+      re = fabsf(re) - o1; im = fabsf(im) - o1; o[2] = (signed char)trunc_i(50 * re); o[3] = (signed char)trunc_i(50 * im);
+      re = fabsf(re) - o2; im = fabsf(im) - o2; o[4] = (signed char)trunc_i(50 * re); o[5] = (signed char)trunc_i(50 * im);
+      re = fabsf(re) - o3; im = fabsf(im) - o3; o[6] = (signed char)trunc_i(50 * re); o[7] = (signed char)trunc_i(50 * im);
     }
   }
 }

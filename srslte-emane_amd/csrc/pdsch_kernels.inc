@@ -437,7 +437,8 @@ __device__ __forceinline__ uint32_t add_wrap(uint32_t a, uint32_t b)
 // csi_correction (pdsch.c:574-690) applied to LLR number b of a subframe as it is read: 16-bit LLRs: (e * w) >> 16 with w = the gain of
 // "its" symbol scaled to 32767 at the subframe's maximum, rounded to nearest even and saturated, for the whole groups of 4 / 4 / 12 / 8
 // LLRs the SSE loops cover, (int16)(e * gain / max) for the symbols behind them; in the two-symbol groups (QPSK, 64QAM) the reference's
-// _mm_blend_ps takes the low lanes from the SECOND symbol: reproduced. 8-bit LLRs: (int8)(e * (gain / max)).
+// _mm_blend_ps takes the low lanes from the SECOND symbol: reproduced. 8-bit LLRs: (int8)(e * (gain / max)). The conversions are
+// demod_dev's, with the x86 rule for a NaN: a subframe of zeros has gain = max = 0, its weights are -32768 and its casts 0.
 struct CsiW {
   const float* csi; // the subframe's gains
   float        scale, inv;
@@ -460,11 +461,11 @@ __device__ __forceinline__ LLR csi_apply(const CsiW& c, LLR v, int b)
 {
   if constexpr (sizeof(LLR) == 1) {
     const int s = min(b / c.Qm, c.nsym - 1);
-    return (LLR)((float)v * (c.csi[s] * c.inv));
+    return (LLR)demod_dev::trunc_i((float)v * (c.csi[s] * c.inv));
   } else {
     if (b >= c.body_bits) {
       const int s = min(b / c.Qm, c.nsym - 1);
-      return (LLR)((float)v * (c.csi[s] * c.inv));
+      return (LLR)demod_dev::trunc_i((float)v * (c.csi[s] * c.inv));
     }
     int s;
     if (c.mod == 1) { // QPSK: LLRs 0,1 of a group of 4 take the second symbol's gain
@@ -475,8 +476,7 @@ __device__ __forceinline__ LLR csi_apply(const CsiW& c, LLR v, int b)
     } else {
       s = b / c.Qm;
     }
-    const float f = rintf(c.csi[s] * c.scale);
-    const int   w = f > 32767.0f ? 32767 : (int)f;
+    const int w = demod_dev::sat16(demod_dev::rne(c.csi[s] * c.scale)); // _mm_cvtps_pi16: cvtps2pi + packssdw
     return (LLR)(((int)v * w) >> 16);
   }
 }
