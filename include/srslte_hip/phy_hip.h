@@ -43,7 +43,7 @@ void  srslte_hip_event_destroy(void* event);
  * several threads at once). Returns the CALLING thread's stream, created on first use, and its hipStreamGetFlags value in *flags. */
 void* srslte_hip_compat_thread_stream(unsigned* flags);
 /* Counters of the compat layer since process start: [0] stream waits (one per synchronous call), [1] srslte_dlsch_decode2 calls served by the
- * device pipeline, [2] single-code-block decoder calls (srslte_tdec_run_all / _iteration), [3] reserved. With SRSLTE_HIP_STATS set in the
+ * device pipeline, [2] single-code-block decoder calls (srslte_tdec_run_all / _iteration), [3] srslte_dlsch_encode2 calls served by the device pipeline. With SRSLTE_HIP_STATS set in the
  * environment the library prints them to stderr at exit ("[srslte_hip] stats: ..."): how a caller's processes used the boundary. */
 void  srslte_hip_compat_stats(unsigned long long out[4]);
 
@@ -585,6 +585,27 @@ void              srslte_hip_sch_destroy(srslte_hip_sch_t* q);
  * call decoded; sum_passes: SISO passes over those blocks */
 int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, uint32_t nof_e_bits, uint32_t tbs, int mod, uint32_t Nl, uint32_t rv,
                           uint32_t max_iterations, int16_t** buffer_f, uint8_t* cb_crc, uint8_t* cb_bytes, uint32_t* sum_passes);
+
+/* ---- the transmit counterpart: encode_tb_off with w_offset = 0 behind srslte_dlsch_encode2 (sch.c:183-289,:549-575) in one device call with
+ * one stream wait per transport block: TB CRC24A, segmentation, CB CRC24B, turbo encoding, the circular buffer of every code block as
+ * srslte_rm_turbo_tx_lut leaves it (rm_turbo.c:328-372: packed bits without the NULLs, the interleaved systematic bits from bit 0, the
+ * interlaced parity bits from bit K + 4; 3K + 12 bits, the rest of the last byte undefined) and the bit selection of the rv. Upstream enters the
+ * library once per code block (srslte_tcod_encode_lut). include/srslte_hip/srslte_compat.h exports srslte_dlsch_encode2 on top of it. ---- */
+typedef struct srslte_hip_sch_enc srslte_hip_sch_enc_t;
+srslte_hip_sch_enc_t* srslte_hip_sch_enc_create(uint32_t max_tbs, uint32_t max_e_bits);
+void                  srslte_hip_sch_enc_destroy(srslte_hip_sch_enc_t* q);
+/* data (host): tbs / 8 bytes, or NULL for a retransmission (rv != 0); mod 1 QPSK .. 4 256QAM; Nl 1 or 2 (sch.c:552-556).
+ * buffer_b[c]: the C circular buffers of a srslte_softbuffer_tx_t (host): written for rv == 0; for rv 1-3 they are read and the result depends
+ * on them alone, whether data is given or not - buffers written by the reference's own encoder serve, and the other way round.
+ * e_bits (host): packed, MSB first, Qm Nl floor(nof_e_bits / (Qm Nl)) bits from bit 0: block i carries Qm Nl floor(G' / C) bits for
+ * i <= C - gamma - 1, else Qm Nl ceil(G' / C) (G' = nof_e_bits / (Qm Nl), gamma = G' mod C), and follows block i - 1 at bit granularity.
+ * Refused before anything is queued, e_bits and buffer_b untouched: a transport block with filler bits (SRSLTE_ERROR and upstream's message,
+ * sch.c:194-197); one with two code-block sizes (SRSLTE_ERROR_INVALID_INPUTS: no entry of this library takes them, as the grants modes and the
+ * fixed-grant pipelines); rv > 3, mod outside 1..4, Nl outside 1..2, tbs % 8, tbs > max_tbs, nof_e_bits of 0 or above max_e_bits, and data ==
+ * NULL with rv == 0, where upstream would rate-match what its scratch buffers held (all SRSLTE_ERROR_INVALID_INPUTS).
+ * tbs == 0: SRSLTE_SUCCESS and nothing written, as upstream's loop over C = 0 blocks. */
+int srslte_hip_sch_encode(srslte_hip_sch_enc_t* q, const uint8_t* data, uint32_t tbs, int mod, uint32_t Nl, uint32_t rv, uint32_t nof_e_bits,
+                          uint8_t** buffer_b, uint8_t* e_bits);
 
 /* ------------------------------------------------------------------ DL control region receive (UE side): the part of srslte_ue_dl_find_dl_dci
  * that precedes the DCI unpacking, for a batch of subframes (ue/ue_dl.c:334-367 estimate_pdcch_pcfich, :422-478 dci_blind_search, :534-646

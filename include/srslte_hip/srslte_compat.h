@@ -12,7 +12,8 @@
  * tests/test_abi_layout.py checks sizeof/offsetof of every struct below against the reference headers.
  *
  * Not provided (documented in DESIGN.md): interpolate_subframe on a 4-port cell or switched off in an MBSFN subframe; those calls
- * return SRSLTE_ERROR with a message.
+ * return SRSLTE_ERROR with a message. srslte_ulsch_encode is not exported: its transport-block half is sch.c's static encode_tb_off and the
+ * rest is UCI multiplexing, which stays the reference's (see srslte_dlsch_encode2 below, the DL-SCH's entry to the same encoder).
  */
 #ifndef SRSLTE_HIP_SRSLTE_COMPAT_H
 #define SRSLTE_HIP_SRSLTE_COMPAT_H
@@ -225,6 +226,19 @@ typedef struct { /* phch/sch.h:52-73 */
 } srslte_sch_t;
 int srslte_dlsch_decode(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, int16_t* e_bits, uint8_t* data);
 int srslte_dlsch_decode2(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, int16_t* e_bits, uint8_t* data, int codeword_idx, uint32_t nof_layers);
+/* DL-SCH encoding of one transport block (sch.c:544-575 -> encode_tb_off :183-289): srslte_dlsch_encode2 is what srslte_pdsch_encode calls once
+ * per codeword (pdsch.c:1032). Here CRC attachment, segmentation, turbo encoding and rate matching of all code blocks are ONE device call with one
+ * stream wait, instead of one srslte_tcod_encode_lut round trip per block. Byte for byte upstream's e_bits and softbuffers.tx[]->buffer_b[] (the
+ * HARQ state stays in the caller's srslte_softbuffer_tx_t: rv 0 writes it, rv 1-3 read it and nothing else), and upstream's return codes:
+ * SRSLTE_ERROR_INVALID_INPUTS for a NULL q / e_bits / soft buffer, SRSLTE_ERROR for a transport block with filler bits, -1 for more code blocks
+ * than softbuffer->max_cb. Beyond upstream: SRSLTE_ERROR_INVALID_INPUTS for a transport block with two code-block sizes (no entry of this
+ * library takes them), for data == NULL with rv == 0 and for rv > 3. This library reads grant.tb[] (mod, tbs, rv, nof_bits) / grant.nof_tb /
+ * softbuffers.tx[] of srslte_pdsch_cfg_t and the srslte_softbuffer_tx_t; of srslte_sch_t only that it is there. The encoder object belongs to the
+ * calling thread (srslte_tcod_t has no slot for a handle): made on first use, grown when a larger block comes, freed with the thread.
+ * Not served: srslte_ulsch_encode - its transport-block half is the static encode_tb_off, the rest is UCI multiplexing that stays the
+ * reference's; sch.c keeps it and reaches this library through srslte_tcod_encode_lut as before. */
+int srslte_dlsch_encode(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, uint8_t* data, uint8_t* e_bits);
+int srslte_dlsch_encode2(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, uint8_t* data, uint8_t* e_bits, int codeword_idx, uint32_t nof_layers);
 
 /* ------------------------------------------------------------------ DL channel estimator (chest_dl.h:49-156, refsignal_dl.h:49-54, interp.h:63-112) */
 typedef struct { cf_t* diff_vec; uint32_t vector_len; uint32_t max_vector_len; } srslte_interp_linsrslte_vec_t;

@@ -123,6 +123,10 @@ def lib():
         L.srslte_hip_tcod_encode_batch.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp]
         L.srslte_hip_tcod_encode_bytes_batch.argtypes = [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp]
         L.srslte_hip_cbsegm.argtypes = [C.POINTER(Cbsegm), C.c_uint32]
+        L.srslte_hip_sch_enc_create.restype = vp
+        L.srslte_hip_sch_enc_create.argtypes = [C.c_uint32, C.c_uint32]
+        L.srslte_hip_sch_enc_destroy.argtypes = [vp]
+        L.srslte_hip_sch_encode.argtypes = [vp, vp, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
         L.srslte_hip_tc_interl_LTE_gen_interl.argtypes = [vp, vp, C.c_uint32, C.c_uint32]
         L.srslte_hip_dl_rx_create.restype = vp
         L.srslte_hip_dl_rx_create.argtypes = [C.POINTER(DlRxCfg)]
@@ -432,6 +436,32 @@ def tc_interl(long_cb, win=1):
     f, r = np.zeros(long_cb, np.uint16), np.zeros(long_cb, np.uint16)
     rc = lib().srslte_hip_tc_interl_LTE_gen_interl(f.ctypes.data, r.ctypes.data, long_cb, win)
     return rc, f, r
+
+
+class SchEnc:
+    """srslte_hip_sch_enc_t: one transport block with host buffers in one device call, what encode_tb_off does behind srslte_dlsch_encode2
+    (sch.c:183-289,:549-575)."""
+
+    def __init__(self, max_tbs, max_e_bits):
+        self.h = lib().srslte_hip_sch_enc_create(max_tbs, max_e_bits)
+        if not self.h:
+            raise RuntimeError("srslte_hip_sch_enc_create failed")
+
+    def encode(self, data, tbs, mod, Nl, rv, nof_e_bits, buffer_b):
+        """data: tbs / 8 bytes or None (a retransmission); buffer_b: the code blocks' circular buffers, a list of C writable uint8 arrays of at
+        least ceil((3K + 12) / 8) bytes (written for rv 0, read for rv 1-3) -> (rc, the e bits, one per element; None where nothing was written)."""
+        d = None if data is None else np.ascontiguousarray(data, np.uint8)
+        ptrs = (C.c_void_p * max(1, len(buffer_b)))(*[b.ctypes.data for b in buffer_b])
+        e = np.zeros((nof_e_bits + 7) // 8 + 8, np.uint8)
+        rc = lib().srslte_hip_sch_encode(self.h, None if d is None else d.ctypes.data, tbs, mod, Nl, rv, nof_e_bits, ptrs, e.ctypes.data)
+        if rc != SRSLTE_SUCCESS or tbs == 0:
+            return rc, None
+        return rc, np.unpackbits(e)[:nof_e_bits // (2 * mod * Nl) * (2 * mod * Nl)]
+
+    def free(self):
+        if self.h:
+            lib().srslte_hip_sch_enc_destroy(self.h)
+            self.h = None
 
 
 class DmrsPuschCfg(C.Structure):

@@ -47,8 +47,8 @@ struct DevStage { // grow-only device staging buffer
 std::atomic<unsigned long long> g_stats[4];
 void stats_at_exit()
 {
-  fprintf(stderr, "[srslte_hip] stats: stream_waits=%llu dlsch_decode2=%llu tdec_single_block_calls=%llu\n", g_stats[0].load(), g_stats[1].load(),
-          g_stats[2].load());
+  fprintf(stderr, "[srslte_hip] stats: stream_waits=%llu dlsch_decode2=%llu tdec_single_block_calls=%llu dlsch_encode2=%llu\n", g_stats[0].load(),
+          g_stats[1].load(), g_stats[2].load(), g_stats[3].load());
 }
 struct StatsInit {
   StatsInit()
@@ -192,6 +192,15 @@ struct ChestState {
 // demod/tcod calls have no object to hang device staging on: one set per host thread, so that worker threads can call them
 // concurrently as they can upstream (SURVEY §8b "Threading")
 thread_local DevStage g_demod_in, g_demod_out, g_tcod_in, g_tcod_out;
+
+// srslte_dlsch_encode2: srslte_tcod_t has the reference's two fields and no slot for a handle, so the transport-block encoder is the calling
+// thread's, like its stream and arena: made on first use, again when a larger block comes, freed with the thread
+struct SchEncLink {
+  srslte_hip_sch_enc_t* h = nullptr;
+  uint32_t              tbs = 0, e = 0;
+  ~SchEncLink() { srslte_hip_sch_enc_destroy(h); }
+};
+thread_local SchEncLink g_sch_enc;
 
 int cp_nsymb(srslte_cp_t cp) { return cp == SRSLTE_CP_NORM ? 7 : 6; }
 
@@ -1040,6 +1049,50 @@ int srslte_dlsch_decode2(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, int16_t* e_bi
   return (par_rx == par_tx && par_rx) ? SRSLTE_SUCCESS : SRSLTE_ERROR;
 }
 int srslte_dlsch_decode(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, int16_t* e_bits, uint8_t* data) { return srslte_dlsch_decode2(q, cfg, e_bits, data, 0, 1); }
+
+// ---- srslte_dlsch_encode2 (sch.c:549-575) = encode_tb_off with w_offset 0 (sch.c:183-289) with all code blocks in one device call
+// (srslte_hip_sch_encode): upstream enters srslte_tcod_encode_lut once per block. The srslte_softbuffer_tx_t stays the HARQ state on the host
+int srslte_dlsch_encode2(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, uint8_t* data, uint8_t* e_bits, int tb_idx, uint32_t nof_layers)
+{
+  if (!cfg || tb_idx < 0 || tb_idx >= SRSLTE_MAX_CODEWORDS) return SRSLTE_ERROR_INVALID_INPUTS;
+  const uint32_t        Nl = nof_layers != cfg->grant.nof_tb ? 2 : 1; // :552-556
+  srslte_cbsegm_t       seg;
+  const srslte_ra_tb_t& tb = cfg->grant.tb[tb_idx];
+  if (srslte_cbsegm(&seg, (uint32_t)tb.tbs)) {
+    ERROR("Error computing Codeword (%d) segmentation for TBS=%d", tb_idx, tb.tbs);
+    return SRSLTE_ERROR;
+  }
+  srslte_softbuffer_tx_t* sb = cfg->softbuffers.tx[tb_idx];
+  if (!q || !e_bits || !sb) { // :192,:285-287
+    ERROR("Invalid parameters: e_bits=%d, cb_segm=%d, softbuffer=%d", e_bits != 0, 1, sb != 0);
+    return SRSLTE_ERROR_INVALID_INPUTS;
+  }
+  if (seg.F) {
+    hip_log("Error filler bits are not supported. Use standard TBS\n"); // :194-197
+    return SRSLTE_ERROR;
+  }
+  if (seg.C > sb->max_cb) {
+    hip_log("Error number of CB to encode (%d) exceeds soft buffer size (%d CBs)\n", seg.C, sb->max_cb); // :199-202
+    return -1;
+  }
+  if (seg.C == 0) return SRSLTE_SUCCESS; // the loop over no code blocks
+  if (tb.mod < SRSLTE_MOD_QPSK || tb.mod > SRSLTE_MOD_256QAM || tb.nof_bits == 0 || !sb->buffer_b) return SRSLTE_ERROR_INVALID_INPUTS;
+  SchEncLink& l = g_sch_enc;
+  if (!l.h || (uint32_t)tb.tbs > l.tbs || tb.nof_bits > l.e) {
+    srslte_hip_sch_enc_destroy(l.h);
+    l.tbs = (uint32_t)tb.tbs > l.tbs ? (uint32_t)tb.tbs : l.tbs;
+    l.e   = tb.nof_bits > l.e ? tb.nof_bits : l.e;
+    l.h   = srslte_hip_sch_enc_create(l.tbs, l.e);
+    if (!l.h) {
+      l.tbs = l.e = 0;
+      return SRSLTE_ERROR;
+    }
+  }
+  const int r = srslte_hip_sch_encode(l.h, data, (uint32_t)tb.tbs, (int)tb.mod, Nl, (uint32_t)tb.rv, tb.nof_bits, sb->buffer_b, e_bits);
+  if (r == SRSLTE_SUCCESS) g_stats[3]++;
+  return r;
+}
+int srslte_dlsch_encode(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, uint8_t* data, uint8_t* e_bits) { return srslte_dlsch_encode2(q, cfg, data, e_bits, 0, 1); }
 
 static int tdec_all(srslte_tdec_t* h, const void* input, bool api8, uint8_t* output, uint32_t nof_iterations, uint32_t long_cb)
 { // turbodecoder.c:547-562,:573-588

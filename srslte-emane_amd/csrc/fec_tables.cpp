@@ -120,11 +120,13 @@ extern "C" int srslte_hip_tc_interl_LTE_gen_interl(uint16_t* forward, uint16_t* 
   return SRSLTE_SUCCESS;
 }
 
-void lte_rm_rx_table(uint32_t K, uint32_t rv, std::vector<uint32_t>& d_index)
-{ // 36.212 5.1.4.1.1-2: sub-block interleavers, bit collection, k0; entry n = index 3*i+s of the n-th non-NULL bit read from k0
+// 36.212 5.1.4.1.1-2: sub-block interleavers and bit collection: w[k] = index 3*i+s of the coded bit at position k of the circular buffer, -1
+// for a NULL; returns k0 of rv
+static uint32_t rm_circular_buffer(uint32_t K, uint32_t rv, std::vector<int32_t>& w)
+{
   static const uint8_t P[32] = {0, 16, 8, 24, 4, 20, 12, 28, 2, 18, 10, 26, 6, 22, 14, 30, 1, 17, 9, 25, 5, 21, 13, 29, 3, 19, 11, 27, 7, 23, 15, 31};
   const uint32_t D = K + 4, R = (D - 1) / 32 + 1, Kp = 32 * R, ND = Kp - D, Ncb = 3 * Kp;
-  std::vector<int32_t> w(Ncb);
+  w.resize(Ncb);
   for (uint32_t j = 0; j < 32; j++) {
     for (uint32_t i = 0; i < R; i++) {
       const int32_t  y = (int32_t)(i * 32 + P[j]) - (int32_t)ND;
@@ -135,12 +137,30 @@ void lte_rm_rx_table(uint32_t K, uint32_t rv, std::vector<uint32_t>& d_index)
       w[Kp + 2 * k + 1] = y2 >= 0 ? 3 * y2 + 2 : -1;
     }
   }
-  const uint32_t k0 = R * (2 * (uint32_t)ceilf((float)Ncb / (float)(8 * R)) * rv + 2);
+  return R * (2 * (uint32_t)ceilf((float)Ncb / (float)(8 * R)) * rv + 2);
+}
+
+void lte_rm_rx_table(uint32_t K, uint32_t rv, std::vector<uint32_t>& d_index)
+{ // bit selection from k0: entry n = index 3*i+s of the n-th non-NULL bit read from k0
+  std::vector<int32_t> w;
+  const uint32_t       k0 = rm_circular_buffer(K, rv, w), Ncb = (uint32_t)w.size();
   d_index.clear();
   for (uint32_t j = 0; d_index.size() < 3 * K + 12; j++) {
     const int32_t d = w[(k0 + j) % Ncb];
     if (d >= 0) d_index.push_back((uint32_t)d);
   }
+}
+
+// The non-NULL positions of the circular buffer before k0 of rv: where the bits of rv begin in a circular buffer stored without its NULLs
+// (srslte_rm_turbo_tx_lut's w_buff and its k0_vec[cb_idx][rv][1], rm_turbo.c:91-158,:353-366). lte_rm_rx_table(K, rv)[n] is bit
+// (start + n) mod (3K + 12) of that buffer
+uint32_t lte_rm_tx_start(uint32_t K, uint32_t rv)
+{
+  std::vector<int32_t> w;
+  const uint32_t       k0 = rm_circular_buffer(K, rv, w);
+  uint32_t             n  = 0;
+  for (uint32_t k = 0; k < k0; k++) n += w[k] >= 0;
+  return n;
 }
 
 // Gold sequence c(n) of 36.211 7.2 (sequence.c:48-79): x1 from 1 0 0 ..., x2 from c_init, both advanced Nc = 1600 steps

@@ -37,5 +37,6 @@
 #include "sch_host.inc"
 #include "pusch_rx.inc"
 #include "pusch_tx.inc"
+#include "sch_enc_host.inc" // the transmit counterpart of sch_host.inc, on the encoder half pusch_tx.inc defines
 #include "pdsch_tx.inc"
 #include "pusch_tx_grants.inc"

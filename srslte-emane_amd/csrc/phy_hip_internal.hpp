@@ -28,6 +28,7 @@ extern const QppRow lte_qpp_table[188];
 int  lte_cb_index(uint32_t K);
 void lte_qpp_tables(uint32_t K, uint32_t W, std::vector<uint16_t>& fwd, std::vector<uint16_t>& rev);
 void lte_rm_rx_table(uint32_t K, uint32_t rv, std::vector<uint32_t>& d_index); // circular-buffer order -> 3*i+s
+uint32_t lte_rm_tx_start(uint32_t K, uint32_t rv); // bit of the NULL-free circular buffer that lte_rm_rx_table(K, rv) begins with
 // fec_tables.cpp: tables of the fixed-grant pipelines - the packed scrambling rows [10][words] of c_init(sf), nbits bits each; the TB CRC24A
 // remainders x^(tbs+23-j) mod g [tbs + 24]; the same per code block in the W-window decoder's array order [C][K]
 void lte_scr_table(const std::function<uint32_t(uint32_t)>& c_init, uint32_t nbits, uint32_t words, std::vector<uint32_t>& scr);
