@@ -585,6 +585,34 @@ void              srslte_hip_sch_destroy(srslte_hip_sch_t* q);
  * call decoded; sum_passes: SISO passes over those blocks */
 int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, uint32_t nof_e_bits, uint32_t tbs, int mod, uint32_t Nl, uint32_t rv,
                           uint32_t max_iterations, int16_t** buffer_f, uint8_t* cb_crc, uint8_t* cb_bytes, uint32_t* sum_passes);
+/* The same for one PUSCH: what srslte_ulsch_decode does (sch.c:991-1066) from the caller's descrambled LLRs q_bits (host, int16, nof_bits of
+ * them; 16-bit objects only) - HARQ-ACK and RI decisions with upstream's int32 sums, the UL channel de-interleaver with its ACK positions
+ * cleared, the CQI report in front of the UL-SCH, then the transport block as srslte_hip_sch_decode. One stream wait when every block passes
+ * (a second for the soft buffers of failed blocks; one more where the report's size depends on the rank decoded in the same call). tbs 0: a
+ * PUSCH without UL-SCH data, which carries a report (cqi_len > 0); buffer_f / cb_crc / cb_bytes are then not looked at. c_seq: the scrambling
+ * sequence, one bit per byte (read at the positions of a 1-bit ACK / RI). Refused with SRSLTE_ERROR_INVALID_INPUTS before anything is queued:
+ * mod outside 1..3, nof_symb outside 9..12, nof_bits no multiple of nof_symb Qm, ri_len > 2, a report longer than 64 bits, offsets above 15, a
+ * transport block with filler bits or two block sizes, Q' beyond the matrix; SRSLTE_ERROR for a reserved beta offset, as upstream. */
+typedef struct {
+  int      mod;                                   /* 1 QPSK, 2 16QAM, 3 64QAM */
+  uint32_t tbs, rv, nof_bits, L_prb, nof_symb, max_iterations;
+  uint32_t ack_len, ri_len, cqi_len;              /* total ACK bits (3 and more: positions cleared, nothing decided, as upstream); RI bits 0-2;
+                                                     srslte_cqi_size of the report with rank_is_not_one = false */
+  uint32_t I_offset_ack, I_offset_ri, I_offset_cqi;
+  uint32_t cqi_len_rank2, cqi_rank2;              /* a report whose size depends on the rank (sch.c:932-936,:982-986): its size for rank > 1, or 0;
+                                                     the rank decoded by this call decides, or cqi_rank2 when ri_len = 0 */
+} srslte_hip_ulsch_cfg_t;
+typedef struct {
+  uint8_t  ack[2], ri;                            /* decisions (sum > 0); ack[1] meaningful with ack_len = 2 */
+  uint8_t  cqi_bits[64], cqi_crc;                 /* the report, one bit per byte (zeros where its CRC8 failed); cqi_crc: srslte_cqi_value_t.data_crc */
+  uint32_t cqi_len;                               /* the size that was decoded */
+  uint32_t Q_prime_ack, Q_prime_ri, Q_prime_cqi;
+  uint32_t stream_waits;
+} srslte_hip_ulsch_res_t;
+int srslte_hip_ulsch_decode(srslte_hip_sch_t* q, const int16_t* q_bits, const uint8_t* c_seq, const srslte_hip_ulsch_cfg_t* cfg, int16_t** buffer_f,
+                            uint8_t* cb_crc, uint8_t* cb_bytes, uint32_t* sum_passes, srslte_hip_ulsch_res_t* res);
+/* debugging accessor: the first n LLRs of the last srslte_hip_ulsch_decode's de-interleaved stream g (n <= its nof_bits) to host memory */
+int srslte_hip_ulsch_debug_g(srslte_hip_sch_t* q, int16_t* out, uint32_t n);
 
 /* ---- the transmit counterpart: encode_tb_off with w_offset = 0 behind srslte_dlsch_encode2 (sch.c:183-289,:549-575) in one device call with
  * one stream wait per transport block: TB CRC24A, segmentation, CB CRC24B, turbo encoding, the circular buffer of every code block as

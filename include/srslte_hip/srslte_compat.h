@@ -12,8 +12,9 @@
  * tests/test_abi_layout.py checks sizeof/offsetof of every struct below against the reference headers.
  *
  * Not provided (documented in DESIGN.md): interpolate_subframe on a 4-port cell or switched off in an MBSFN subframe; those calls
- * return SRSLTE_ERROR with a message. srslte_ulsch_encode is not exported: its transport-block half is sch.c's static encode_tb_off and the
- * rest is UCI multiplexing, which stays the reference's (see srslte_dlsch_encode2 below, the DL-SCH's entry to the same encoder).
+ * return SRSLTE_ERROR with a message. Of sch.c the library serves the DL-SCH in both directions (srslte_dlsch_decode2, srslte_dlsch_encode2) and the
+ * UL-SCH receiver with its UCI (srslte_ulsch_decode); srslte_ulsch_encode is not exported: its transport-block half is sch.c's static
+ * encode_tb_off and the rest is UCI multiplexing, which stays the reference's.
  */
 #ifndef SRSLTE_HIP_SRSLTE_COMPAT_H
 #define SRSLTE_HIP_SRSLTE_COMPAT_H
@@ -239,6 +240,68 @@ int srslte_dlsch_decode2(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, int16_t* e_bi
  * reference's; sch.c keeps it and reaches this library through srslte_tcod_encode_lut as before. */
 int srslte_dlsch_encode(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, uint8_t* data, uint8_t* e_bits);
 int srslte_dlsch_encode2(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, uint8_t* data, uint8_t* e_bits, int codeword_idx, uint32_t nof_layers);
+
+/* UL-SCH decoding of one PUSCH (sch.h, sch.c:991-1066): srslte_ulsch_decode is what srslte_pusch_decode calls once per PUSCH (pusch.c:503) with
+ * the descrambled LLRs q_bits. Upstream decodes HARQ-ACK and RI on the host, builds the channel de-interleaver's table per call, scatters every
+ * LLR through it, decodes the CQI report and enters decode_tb_cb - one srslte_tdec_iteration round trip per code block and pass. Here all of it
+ * is ONE device call (srslte_hip_ulsch_decode, phy_hip.h) that waits for its stream once when every block passes. Upstream's values: the ACK /
+ * RI decisions from its int32 sums, the report through srslte_cqi_value_unpack, data with its three CRC bytes, the srslte_softbuffer_rx_t exactly
+ * as srslte_dlsch_decode2 leaves it, q->avg_iterations, cfg->K_segm, cfg->uci_cfg.cqi.rank_is_not_one, and its return codes - including that a
+ * call with tbs = 0 returns the last Q' it computed (Q'_cqi with a report, else Q'_ri), not 0. The device object is the one of srslte_dlsch_decode2,
+ * behind q->decoder.dec16_hdlr[0]; it grows on demand.
+ * Deliberate differences:
+ *  - q_bits, g_bits and q->ack_ri_bits are scratch for pusch.c, which reads none of them after the call: all three are left untouched (upstream
+ *    clears the ACK positions of q_bits, flips the p1 LLRs of 1-bit ACK / RI, and writes g_bits and the position list). g_bits may be NULL.
+ *  - ri_len = 2 sets uci_data->ri only; upstream writes a second byte behind it.
+ *  - refused with SRSLTE_ERROR_INVALID_INPUTS and a message, BEFORE anything is queued or written (cfg->K_segm excepted, which is written
+ *    first as upstream): objects with llr_is_8bit (upstream reads int8 LLRs through an int16_t* there); a modulation outside QPSK..64QAM; a
+ *    transport block with two code-block sizes or filler bits; nof_bits that is no multiple of nof_symb Qm; also NULL data or soft buffer with
+ *    tbs > 0 and more code blocks than the soft buffer holds (upstream decodes the UCI first and fails then), tbs = 0 without a report,
+ *    nof_symb outside 9..12, L_prb = 0, ri_len > 2, a report longer than 64 bits, offsets above 15, Q' beyond the matrix's rows.
+ *  - where the report's size depends on the rank decoded in the same call (a higher-layer subband report with PMI and ri_present, ri_len > 0)
+ *    the call waits for its stream a second time, between the RI decision and the report.
+ * Nothing falls back to a host path. srslte_ulsch_encode stays the reference's (above). */
+#define SRSLTE_MAX_CARRIERS 5          /* phy_common.h:48 */
+#define SRSLTE_UCI_MAX_ACK_BITS 10     /* uci_cfg.h:27-28 */
+#define SRSLTE_UCI_MAX_M 9
+#define SRSLTE_CQI_MAX_BITS 64         /* cqi.h:38 */
+typedef struct { uint8_t wideband_cqi_cw0; uint32_t subband_diff_cqi_cw0; uint8_t wideband_cqi_cw1; uint32_t subband_diff_cqi_cw1; uint32_t pmi; } srslte_cqi_hl_subband_t; /* cqi.h:74-80 */
+typedef struct { uint8_t wideband_cqi; uint8_t subband_diff_cqi; uint32_t position_subband; } srslte_cqi_ue_subband_t;                                                          /* :86-90 */
+typedef struct { uint8_t wideband_cqi; uint8_t spatial_diff_cqi; uint8_t pmi; } srslte_cqi_format2_wideband_t;                                                                  /* :103-107 */
+typedef struct { uint8_t subband_cqi; uint8_t subband_label; } srslte_cqi_format2_subband_t;                                                                                   /* :109-112 */
+typedef enum { SRSLTE_CQI_TYPE_WIDEBAND = 0, SRSLTE_CQI_TYPE_SUBBAND, SRSLTE_CQI_TYPE_SUBBAND_UE, SRSLTE_CQI_TYPE_SUBBAND_HL } srslte_cqi_type_t;                               /* :114-119 */
+typedef struct { /* cqi.h:121-132 */
+  bool data_enable; bool ri_present; bool pmi_present; bool four_antenna_ports; bool rank_is_not_one; bool subband_label_2_bits;
+  uint32_t L; uint32_t N; srslte_cqi_type_t type; uint32_t ri_len;
+} srslte_cqi_cfg_t;
+typedef struct { /* cqi.h:134-142 */
+  union { srslte_cqi_format2_wideband_t wideband; srslte_cqi_format2_subband_t subband; srslte_cqi_ue_subband_t subband_ue; srslte_cqi_hl_subband_t subband_hl; };
+  bool data_crc;
+} srslte_cqi_value_t;
+typedef struct { uint8_t ack_value[SRSLTE_UCI_MAX_ACK_BITS]; bool valid; } srslte_uci_value_ack_t; /* uci_cfg.h:30-33 */
+typedef struct { /* uci_cfg.h:35-45 */
+  bool pending_tb[SRSLTE_MAX_CODEWORDS]; uint32_t nof_acks; uint32_t ncce[SRSLTE_UCI_MAX_M]; uint32_t N_bundle; uint32_t tdd_ack_M; uint32_t tdd_ack_m;
+  bool tdd_is_multiplex; uint32_t tpc_for_pucch; uint32_t grant_cc_idx;
+} srslte_uci_cfg_ack_t;
+typedef struct { srslte_uci_cfg_ack_t ack[SRSLTE_MAX_CARRIERS]; srslte_cqi_cfg_t cqi; bool is_scheduling_request_tti; } srslte_uci_cfg_t;   /* :47-51 */
+typedef struct { bool scheduling_request; srslte_cqi_value_t cqi; srslte_uci_value_ack_t ack; uint8_t ri; } srslte_uci_value_t;             /* :53-58 */
+typedef struct { uint32_t I_offset_cqi; uint32_t I_offset_ri; uint32_t I_offset_ack; } srslte_uci_offset_cfg_t;                             /* pusch_cfg.h:29-33 */
+typedef struct { /* pusch_cfg.h:44-57 */
+  bool is_from_rar; uint32_t L_prb; uint32_t n_prb[2]; uint32_t n_prb_tilde[2]; uint32_t freq_hopping; uint32_t nof_re; uint32_t nof_symb;
+  srslte_ra_tb_t tb; srslte_ra_tb_t last_tb; uint32_t n_dmrs;
+} srslte_pusch_grant_t;
+typedef struct { /* pusch_cfg.h:59-82 */
+  uint16_t rnti; srslte_uci_cfg_t uci_cfg; srslte_uci_offset_cfg_t uci_offset; srslte_pusch_grant_t grant;
+  uint32_t max_nof_iterations; uint32_t last_O_cqi; uint32_t K_segm; uint32_t current_tx_nb; bool csi_enable; bool enable_64qam;
+  union { srslte_softbuffer_tx_t* tx; srslte_softbuffer_rx_t* rx; } softbuffers;
+  bool meas_time_en; uint32_t meas_time_value;
+} srslte_pusch_cfg_t;
+int srslte_ulsch_decode(srslte_sch_t* q, srslte_pusch_cfg_t* cfg, int16_t* q_bits, int16_t* g_bits, uint8_t* c_seq, uint8_t* data, srslte_uci_value_t* uci_data);
+/* {srslte_ulsch_decode calls served, stream waits inside them} (srslte_hip_compat_stats keeps its four entries) */
+void srslte_hip_compat_stats_ul(unsigned long long out[2]);
+/* the device object behind q->decoder.dec16_hdlr[0] (a srslte_hip_sch_t of phy_hip.h; NULL before the first served call): for
+ * srslte_hip_ulsch_debug_g, which copies the last call's de-interleaved stream to the host */
+struct srslte_hip_sch* srslte_hip_compat_sch_of(srslte_sch_t* q);
 
 /* ------------------------------------------------------------------ DL channel estimator (chest_dl.h:49-156, refsignal_dl.h:49-54, interp.h:63-112) */
 typedef struct { cf_t* diff_vec; uint32_t vector_len; uint32_t max_vector_len; } srslte_interp_linsrslte_vec_t;

@@ -19,5 +19,10 @@ __device__ __forceinline__ float wave_sum(float v)
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ int wave_sum(int v) // exact: the int32 sums of the UCI decisions (uci.c:627-654)
+{
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 
 } // namespace

@@ -45,10 +45,11 @@ struct DevStage { // grow-only device staging buffer
 // callers' pageable buffers costs ~50 us per call and serialises every host thread on the null stream; the reference's worker threads -
 // three sf_workers in srsue - call these functions concurrently on distinct objects, SURVEY 8b "Threading".)
 std::atomic<unsigned long long> g_stats[4];
+std::atomic<unsigned long long> g_stats_ul[2]; // srslte_ulsch_decode calls served, stream waits inside them (srslte_hip_compat_stats_ul)
 void stats_at_exit()
 {
-  fprintf(stderr, "[srslte_hip] stats: stream_waits=%llu dlsch_decode2=%llu tdec_single_block_calls=%llu dlsch_encode2=%llu\n", g_stats[0].load(),
-          g_stats[1].load(), g_stats[2].load(), g_stats[3].load());
+  fprintf(stderr, "[srslte_hip] stats: stream_waits=%llu dlsch_decode2=%llu tdec_single_block_calls=%llu dlsch_encode2=%llu ulsch_decode=%llu\n",
+          g_stats[0].load(), g_stats[1].load(), g_stats[2].load(), g_stats[3].load(), g_stats_ul[0].load());
 }
 struct StatsInit {
   StatsInit()
@@ -971,6 +972,10 @@ static void tdec_one_more(srslte_tdec_t* h, const void* input, bool api8, uint8_
 void srslte_tdec_iteration(srslte_tdec_t* h, int16_t* input, uint8_t* output) { tdec_one_more(h, input, false, output); }
 void srslte_tdec_iteration_8bit(srslte_tdec_t* h, int8_t* input, uint8_t* output) { tdec_one_more(h, input, true, output); }
 
+static srslte_hip_sch_t* sch_object(TdecState* st, uint32_t tbs, uint32_t nof_bits, bool l8);
+static void tb_begin(TdecState* st, const srslte_softbuffer_rx_t* sb, const srslte_cbsegm_t& seg, uint8_t* data);
+static int  tb_finish(srslte_sch_t* q, TdecState* st, srslte_softbuffer_rx_t* sb, const srslte_cbsegm_t& seg, uint8_t* data, uint32_t passes);
+
 // ---- srslte_dlsch_decode2 (sch.c:507-531) = decode_tb (sch.c:429-500) with all code blocks in one device call (srslte_hip_sch_decode)
 int srslte_dlsch_decode2(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, int16_t* e_bits, uint8_t* data, int tb_idx, uint32_t nof_layers)
 {
@@ -999,26 +1004,45 @@ int srslte_dlsch_decode2(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, int16_t* e_bi
   }
   auto* st = (TdecState*)q->decoder.dec16_hdlr[0];
   if (!st || tb.mod < SRSLTE_MOD_QPSK || tb.mod > SRSLTE_MOD_256QAM || tb.nof_bits == 0) return SRSLTE_ERROR_INVALID_INPUTS;
-  if (!st->sch || (uint32_t)tb.tbs > st->sch_tbs || tb.nof_bits > st->sch_e || st->sch_l8 != q->llr_is_8bit) {
-    srslte_hip_sch_destroy(st->sch);
-    st->sch_tbs = (uint32_t)tb.tbs > st->sch_tbs ? (uint32_t)tb.tbs : st->sch_tbs;
-    st->sch_e   = tb.nof_bits > st->sch_e ? tb.nof_bits : st->sch_e;
-    st->sch_l8  = q->llr_is_8bit;
-    st->sch     = srslte_hip_sch_create(st->sch_tbs, st->sch_e, st->sch_l8 ? 1 : 0);
-    if (!st->sch) {
-      st->sch_tbs = st->sch_e = 0;
-      return SRSLTE_ERROR;
-    }
-  }
-  const uint32_t C = seg.C, tbs8 = seg.tbs / 8;
-  data[tbs8 + 0] = data[tbs8 + 1] = data[tbs8 + 2] = 0; // :461-463
-  st->cb_bytes.resize((size_t)C * 768);
-  st->cb_crc.resize(C);
-  for (uint32_t i = 0; i < C; i++) st->cb_crc[i] = sb->cb_crc[i] ? 1 : 0;
+  if (!sch_object(st, (uint32_t)tb.tbs, tb.nof_bits, q->llr_is_8bit)) return SRSLTE_ERROR;
+  tb_begin(st, sb, seg, data);
   uint32_t passes = 0;
   const int r = srslte_hip_sch_decode(st->sch, e_bits, tb.nof_bits, (uint32_t)tb.tbs, (int)tb.mod, Nl, (uint32_t)tb.rv, q->max_iterations, sb->buffer_f,
                                       st->cb_crc.data(), st->cb_bytes.data(), &passes);
   if (r) return r == SRSLTE_ERROR_INVALID_INPUTS ? SRSLTE_ERROR_INVALID_INPUTS : SRSLTE_ERROR;
+  return tb_finish(q, st, sb, seg, data, passes);
+}
+int srslte_dlsch_decode(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, int16_t* e_bits, uint8_t* data) { return srslte_dlsch_decode2(q, cfg, e_bits, data, 0, 1); }
+
+// the transport-block decoder of the srslte_sch_t: made on first use and again when a larger block or the other LLR width comes
+static srslte_hip_sch_t* sch_object(TdecState* st, uint32_t tbs, uint32_t nof_bits, bool l8)
+{
+  if (!st->sch || tbs > st->sch_tbs || nof_bits > st->sch_e || st->sch_l8 != l8) {
+    srslte_hip_sch_destroy(st->sch);
+    st->sch_tbs = tbs > st->sch_tbs ? tbs : st->sch_tbs;
+    st->sch_e   = nof_bits > st->sch_e ? nof_bits : st->sch_e;
+    st->sch_l8  = l8;
+    st->sch     = srslte_hip_sch_create(st->sch_tbs, st->sch_e, st->sch_l8 ? 1 : 0);
+    if (!st->sch) st->sch_tbs = st->sch_e = 0;
+  }
+  return st->sch;
+}
+
+// decode_tb around the device call (sch.c:461-488, decode_tb_cb :312-412), for the DL-SCH and the UL-SCH alike. tb_begin: the three CRC bytes
+// cleared (data = null: the caller does that once nothing can be refused any more), the soft buffer's flags as the device call takes them
+static void tb_begin(TdecState* st, const srslte_softbuffer_rx_t* sb, const srslte_cbsegm_t& seg, uint8_t* data)
+{
+  const uint32_t C = seg.C, tbs8 = seg.tbs / 8;
+  if (data) data[tbs8 + 0] = data[tbs8 + 1] = data[tbs8 + 2] = 0; // :461-463
+  st->cb_bytes.resize((size_t)C * 768);
+  st->cb_crc.resize(C);
+  for (uint32_t i = 0; i < C; i++) st->cb_crc[i] = sb->cb_crc[i] ? 1 : 0;
+}
+
+// tb_finish: the transport block from the blocks' bytes, the soft buffer's flags and stored blocks, avg_iterations, the CRC24A verdict
+static int tb_finish(srslte_sch_t* q, TdecState* st, srslte_softbuffer_rx_t* sb, const srslte_cbsegm_t& seg, uint8_t* data, uint32_t passes)
+{
+  const uint32_t C = seg.C, tbs8 = seg.tbs / 8;
   // decode_tb_cb :312-412: bytes of every block in order (a decoded block's K / 8 bytes start where its rlen / 8 payload bytes go; the next
   // block overwrites its 24 CRC bits), blocks decoded in an earlier transmission from the soft buffer's copy
   for (uint32_t i = 0; i < C; i++) {
@@ -1048,7 +1072,134 @@ int srslte_dlsch_decode2(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, int16_t* e_bi
   const uint32_t par_tx = ((uint32_t)data[tbs8] << 16) | ((uint32_t)data[tbs8 + 1] << 8) | (uint32_t)data[tbs8 + 2];
   return (par_rx == par_tx && par_rx) ? SRSLTE_SUCCESS : SRSLTE_ERROR;
 }
-int srslte_dlsch_decode(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, int16_t* e_bits, uint8_t* data) { return srslte_dlsch_decode2(q, cfg, e_bits, data, 0, 1); }
+
+// ---- srslte_ulsch_decode (sch.c:991-1066): uci_decode_ri_ack, ulsch_deinterleave, srslte_uci_decode_cqi_pusch and decode_tb as ONE device call
+// (srslte_hip_ulsch_decode). The host keeps what is arithmetic on the configuration: segmentation, K_segm, the report's size and its unpacking
+static uint32_t ul_bits(const uint8_t* b, uint32_t* at, uint32_t n)
+{ // srslte_bit_pack on the 64-entry report buffer (zeros behind it)
+  uint32_t v = 0;
+  for (uint32_t i = 0; i < n; i++, ++*at) v = (v << 1) | (*at < SRSLTE_CQI_MAX_BITS ? (b[*at] & 1u) : 0u);
+  return v;
+}
+static void ul_cqi_unpack(const srslte_cqi_cfg_t* c, const uint8_t* b, srslte_cqi_value_t* v)
+{ // srslte_cqi_value_unpack (cqi.c:141-231)
+  uint32_t at = 0;
+  switch (c->type) {
+    case SRSLTE_CQI_TYPE_WIDEBAND:
+      v->wideband.wideband_cqi = (uint8_t)ul_bits(b, &at, 4);
+      if (c->pmi_present) {
+        if (c->rank_is_not_one) v->wideband.spatial_diff_cqi = (uint8_t)ul_bits(b, &at, 3);
+        v->wideband.pmi = (uint8_t)ul_bits(b, &at, c->four_antenna_ports ? 4 : (c->rank_is_not_one ? 1 : 2));
+      }
+      break;
+    case SRSLTE_CQI_TYPE_SUBBAND:
+      v->subband.subband_cqi   = (uint8_t)ul_bits(b, &at, 4);
+      v->subband.subband_label = (uint8_t)ul_bits(b, &at, c->subband_label_2_bits ? 2 : 1);
+      break;
+    case SRSLTE_CQI_TYPE_SUBBAND_UE: // the differential is read twice, the second time over L bits, as upstream
+      v->subband_ue.wideband_cqi     = (uint8_t)ul_bits(b, &at, 4);
+      v->subband_ue.subband_diff_cqi = (uint8_t)ul_bits(b, &at, 2);
+      v->subband_ue.subband_diff_cqi = (uint8_t)ul_bits(b, &at, c->L);
+      break;
+    case SRSLTE_CQI_TYPE_SUBBAND_HL:
+      v->subband_hl.wideband_cqi_cw0     = (uint8_t)ul_bits(b, &at, 4);
+      v->subband_hl.subband_diff_cqi_cw0 = ul_bits(b, &at, 2 * c->N);
+      if (c->rank_is_not_one) {
+        v->subband_hl.wideband_cqi_cw1     = (uint8_t)ul_bits(b, &at, 4);
+        v->subband_hl.subband_diff_cqi_cw1 = ul_bits(b, &at, 2 * c->N);
+      }
+      if (c->pmi_present) v->subband_hl.pmi = (uint8_t)ul_bits(b, &at, c->four_antenna_ports ? 4 : (c->rank_is_not_one ? 1 : 2));
+      break;
+  }
+}
+static int ul_cqi_size(const srslte_cqi_cfg_t* c, bool rank_is_not_one)
+{ // srslte_cqi_size (cqi.c:321-384)
+  srslte_hip_cqi_cfg_t h = {(int)c->type, c->data_enable, c->pmi_present, c->four_antenna_ports, rank_is_not_one, c->subband_label_2_bits, c->L, c->N};
+  return srslte_hip_cqi_size(&h);
+}
+
+int srslte_ulsch_decode(srslte_sch_t* q, srslte_pusch_cfg_t* cfg, int16_t* q_bits, int16_t* g_bits, uint8_t* c_seq, uint8_t* data, srslte_uci_value_t* uci_data)
+{
+  (void)g_bits; // pusch.c's scratch: never read after the call, not written here
+  if (!q || !cfg || !q_bits || !c_seq || !uci_data) return SRSLTE_ERROR_INVALID_INPUTS;
+  srslte_cbsegm_t       seg;
+  const srslte_ra_tb_t& tb = cfg->grant.tb;
+  if (srslte_cbsegm(&seg, (uint32_t)tb.tbs)) {
+    ERROR("Error computing segmentation for TBS=%d", tb.tbs);
+    return SRSLTE_ERROR;
+  }
+  cfg->K_segm = seg.C1 * seg.K1 + seg.C2 * seg.K2; // :1011
+  // ---- refusals, before anything is queued or written
+  srslte_softbuffer_rx_t* sb  = cfg->softbuffers.rx;
+  srslte_cqi_cfg_t*       cq  = &cfg->uci_cfg.cqi;
+  const uint32_t          Qm  = tb.mod == SRSLTE_MOD_QPSK ? 2 : tb.mod == SRSLTE_MOD_16QAM ? 4 : 6;
+  auto*                   st  = (TdecState*)q->decoder.dec16_hdlr[0];
+  auto refuse = [](const char* why) {
+    ERROR("srslte_ulsch_decode: %s", why);
+    return SRSLTE_ERROR_INVALID_INPUTS;
+  };
+  if (q->llr_is_8bit) return refuse("8-bit LLR objects are not served (upstream reads int8 LLRs through an int16_t* here)");
+  if (tb.mod < SRSLTE_MOD_QPSK || tb.mod > SRSLTE_MOD_64QAM) return refuse("modulation outside QPSK..64QAM");
+  if (seg.F || seg.C2) return refuse("transport block with filler bits or two code-block sizes");
+  if (cfg->grant.nof_symb < 9 || cfg->grant.nof_symb > 12 || cfg->grant.L_prb == 0 || tb.nof_bits == 0 || tb.nof_bits % (cfg->grant.nof_symb * Qm))
+    return refuse("nof_bits is no multiple of nof_symb x Qm (or nof_symb outside 9..12, L_prb 0)");
+  if (seg.tbs && (!data || !sb || !sb->buffer_f || !sb->data || !sb->cb_crc || seg.C > sb->max_cb)) return refuse("no data or soft buffer, or a soft buffer of too few blocks");
+  uint32_t total_ack = 0; // srslte_uci_cfg_total_ack
+  for (int i = 0; i < SRSLTE_MAX_CARRIERS; i++) total_ack += cfg->uci_cfg.ack[i].nof_acks;
+  const bool rank_dep = cq->data_enable && cq->type == SRSLTE_CQI_TYPE_SUBBAND_HL && cq->ri_present; // :932-936,:982-986
+  const int  len1 = ul_cqi_size(cq, rank_dep ? false : cq->rank_is_not_one), len2 = rank_dep ? ul_cqi_size(cq, true) : len1;
+  if (cq->ri_len > 2 || len1 < 0 || len1 > SRSLTE_CQI_MAX_BITS || len2 > SRSLTE_CQI_MAX_BITS || (cq->data_enable && len1 == 0) || (!seg.tbs && len1 == 0) ||
+      cfg->uci_offset.I_offset_ack > 15 || cfg->uci_offset.I_offset_ri > 15 || cfg->uci_offset.I_offset_cqi > 15)
+    return refuse("ri_len > 2, a report of 0 or more than 64 bits, no report on a PUSCH without data, or an offset index above 15");
+  if (!st) return refuse("the srslte_sch_t's decoder is not initialised");
+  if (!sch_object(st, seg.tbs ? seg.tbs : 40, tb.nof_bits, false)) return SRSLTE_ERROR;
+  srslte_hip_ulsch_cfg_t c;
+  memset(&c, 0, sizeof(c));
+  c.mod = (int)tb.mod; c.tbs = seg.tbs; c.rv = (uint32_t)tb.rv; c.nof_bits = tb.nof_bits; c.L_prb = cfg->grant.L_prb; c.nof_symb = cfg->grant.nof_symb;
+  c.max_iterations = q->max_iterations;
+  c.ack_len = total_ack; c.ri_len = cq->ri_len; c.cqi_len = (uint32_t)len1;
+  c.I_offset_ack = cfg->uci_offset.I_offset_ack; c.I_offset_ri = cfg->uci_offset.I_offset_ri; c.I_offset_cqi = cfg->uci_offset.I_offset_cqi;
+  c.cqi_len_rank2 = len2 != len1 ? (uint32_t)len2 : 0;
+  c.cqi_rank2     = uci_data->ri > 0; // ri_len = 0: the caller's value stands (:984)
+  srslte_hip_ulsch_res_t res;
+  uint32_t               passes = 0;
+  // what the device call itself refuses (a transport block beyond the object, Q' beyond the matrix, a reserved beta): nothing is written yet
+  if (seg.tbs) tb_begin(st, sb, seg, nullptr);
+  const int r = srslte_hip_ulsch_decode(st->sch, q_bits, c_seq, &c, seg.tbs ? sb->buffer_f : nullptr, seg.tbs ? st->cb_crc.data() : nullptr,
+                                        seg.tbs ? st->cb_bytes.data() : nullptr, &passes, &res);
+  if (r) {
+    if (r == SRSLTE_ERROR) ERROR("Error decoding RI/HARQ bits"); // :1015
+    return r == SRSLTE_ERROR_INVALID_INPUTS ? refuse("not served by the device call") : SRSLTE_ERROR;
+  }
+  g_stats_ul[0]++;
+  g_stats_ul[1] += res.stream_waits;
+  // ---- uci_decode_ri_ack's results (:932-986)
+  if (rank_dep) cq->rank_is_not_one = false;
+  if (total_ack > 0) {
+    uci_data->ack.ack_value[0] = res.ack[0]; // uci.c:782-785
+    if (total_ack == 2) uci_data->ack.ack_value[1] = res.ack[1];
+  }
+  if (cq->ri_len > 0) uci_data->ri = res.ri;
+  if (rank_dep) cq->rank_is_not_one = uci_data->ri > 0;
+  int ret = (int)res.Q_prime_ri;
+  if (cq->data_enable) { // :1039-1056
+    uci_data->cqi.data_crc = res.cqi_crc != 0;
+    ul_cqi_unpack(cq, res.cqi_bits, &uci_data->cqi);
+    ret = (int)res.Q_prime_cqi;
+  }
+  if (seg.tbs == 0) return ret; // :1061-1065: the last Q' computed, upstream's oddity
+  data[seg.tbs / 8 + 0] = data[seg.tbs / 8 + 1] = data[seg.tbs / 8 + 2] = 0;
+  return tb_finish(q, st, sb, seg, data, passes);
+}
+srslte_hip_sch_t* srslte_hip_compat_sch_of(srslte_sch_t* q)
+{
+  auto* st = q ? (TdecState*)q->decoder.dec16_hdlr[0] : nullptr;
+  return st ? st->sch : nullptr;
+}
+void srslte_hip_compat_stats_ul(unsigned long long out[2])
+{
+  for (int i = 0; i < 2; i++) out[i] = g_stats_ul[i].load();
+}
 
 // ---- srslte_dlsch_encode2 (sch.c:549-575) = encode_tb_off with w_offset 0 (sch.c:183-289) with all code blocks in one device call
 // (srslte_hip_sch_encode): upstream enters srslte_tcod_encode_lut once per block. The srslte_softbuffer_tx_t stays the HARQ state on the host

@@ -18,6 +18,7 @@
 // single-port csi variant multiplies by the 12-bit _mm256_rcp_ps approximation, precoding.c:262-275, whose value is CPU-vendor
 // dependent; LLRs may therefore differ from a given host's by an LSB, decoded blocks do not), demap, descramble and write the LLRs
 // through LDS with 16-byte stores: 16 B read and Qm * sizeof(LLR) B written per RE, no intermediate d/e round trips through HBM.
+#include "cf32_dev.hpp"
 #include "common.hpp"
 #include "demod_dev.hpp"
 #include "dev_buf.hpp"
@@ -36,6 +37,7 @@
 #include "pdsch_rx_grants.inc"
 #include "sch_host.inc"
 #include "pusch_rx.inc"
+#include "ulsch_host.inc" // srslte_ulsch_decode's device call: sch_host.inc's object behind pusch_rx.inc's UCI position arithmetic and CQI decoder
 #include "pusch_tx.inc"
 #include "sch_enc_host.inc" // the transmit counterpart of sch_host.inc, on the encoder half pusch_tx.inc defines
 #include "pdsch_tx.inc"

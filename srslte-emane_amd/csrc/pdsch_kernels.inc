@@ -286,11 +286,8 @@ __global__ __launch_bounds__(256) void pdsch_demod_div4_kernel(const cf32* __res
 // the demapper and descrambler of BOTH codewords (nof_layers == nof_tb in every case ra_dl.c:556-600 lets through: layer l is codeword l,
 // no layer de-mapping; srslte_pdsch_codeword_decode pdsch.c:729-790 with the codeword's own modulation and scrambling sequence).
 // One thread per PDSCH RE; ce is [sf][port][antenna][grid], grid [sf][antenna][grid]. grid = (ceil(max_re/256), nof_sf).
-__device__ __forceinline__ cf32 cmul(cf32 a, cf32 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+// cmul, cadd, csub, cmulj: cf32_dev.hpp
 __device__ __forceinline__ cf32 cmulc(cf32 a, cf32 b) { return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); } // a conj(b)
-__device__ __forceinline__ cf32 cadd(cf32 a, cf32 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ cf32 csub(cf32 a, cf32 b) { return make_float2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ cf32 cmulj(cf32 a) { return make_float2(-a.y, a.x); }
 
 template <typename LLR>
 __global__ __launch_bounds__(256) void pdsch_demod_mimo_kernel(const cf32* __restrict__ grid, const cf32* __restrict__ ce,

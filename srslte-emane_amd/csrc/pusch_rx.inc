@@ -237,8 +237,11 @@ __device__ __forceinline__ uint32_t cqi_crc8(const uint8_t* bits, int n)
 }
 
 __global__ __launch_bounds__(256) void pusch_cqi_decode_kernel(const int16_t* __restrict__ gl, int g_stride, int Q_all, int O_all, uint8_t* __restrict__ cqi_out,
-                                                               uint8_t* __restrict__ ok_out, const PuschDesc* __restrict__ desc)
+                                                               uint8_t* __restrict__ ok_out, const PuschDesc* __restrict__ desc, int as_host = 0)
 {
+  // as_host (srslte_hip_ulsch_decode): the two places where the reference's int16 arithmetic shows once a report is repeated until its sums
+  // are large - the block code's correlation in 16 int16 lanes (srslte_vec_dot_prod_sss_simd, vector_simd.c:62-98) and the Viterbi decoder's
+  // int16 quantiser (viterbi_dev::quant_sus). Without it: int32 correlation and the float quantiser, as before
   // per-PUSCH grants: the report's size comes from the row's descriptor (rows without a report are left alone)
   const int Q = desc ? desc[blockIdx.x].cqi_Q : Q_all, O = desc ? desc[blockIdx.x].cqi_O : O_all;
   if (O == 0) return;
@@ -261,12 +264,19 @@ __global__ __launch_bounds__(256) void pusch_cqi_decode_kernel(const int16_t* __
     const int n = Q < 32 ? Q : 32;
     long long key = INT64_MIN;
     for (uint32_t w = tid; w < (1u << O); w += 256) {
-      int corr = 0;
-      for (int i = 0; i < n; i++) {
+      int  corr = 0;
+      auto term = [&](int i) {
         uint32_t m = 0; // code bit i of word w: bit k of the report is bit O-1-k of w
         for (int k = 0; k < O; k++) m ^= ((w >> (O - 1 - k)) & 1u) & ((CQI_M32[i] >> k) & 1u);
-        corr += m ? acc[i] : -acc[i];
+        return m ? (int)acc[i] : -(int)acc[i];
+      };
+      const int nv = as_host ? (n & ~15) : 0; // whole 16-lane vectors: products and sums wrap per int16 lane
+      for (int k = 0; k < 16 && nv; k++) {
+        int lane = 0;
+        for (int i = k; i < nv; i += 16) lane += term(i);
+        corr += (int16_t)lane;
       }
+      for (int i = nv; i < n; i++) corr += term(i);
       const long long kk = ((long long)corr << 32) | (long long)(0xffffffffu - w); // highest correlation, then lowest word
       key = kk > key ? kk : key;
     }
@@ -312,7 +322,8 @@ __global__ __launch_bounds__(256) void pusch_cqi_decode_kernel(const int16_t* __
   }
   __syncthreads();
   if (tid >= 64) return;
-  viterbi_dev::quant_fus(dem, us, 3 * F, tid);
+  if (as_host) viterbi_dev::quant_sus(dem, us, 3 * F, tid);
+  else viterbi_dev::quant_fus(dem, us, 3 * F, tid);
   viterbi_dev::decode37_tb(us, dec, bits, F, tid);
   if (tid == 0) {
     const uint8_t* msg = bits + F; // the middle repetition
@@ -340,12 +351,12 @@ static int pusch_cqi_qprime(uint32_t O, uint32_t I_offset_cqi, uint32_t L_prb, u
 // Q' of the HARQ-ACK / rank indication (Q_prime_ri_ack, uci.c:547-571): min(ceil(O M_sc N_symb beta / sum K_r), 4 M_sc) in float arithmetic.
 // Without UL-SCH data (K_segm = 0: a CQI-only PUSCH, 36.212 5.2.4.1) the report's size O_cqi - plus its 8 CRC bits above 11 - stands for
 // sum K_r and the callers divide the offset by the report's (sch.c:943-946,:970-973,:1111-1114,:1171-1174).
+static const float pusch_beta_harq[16] = {2.0f, 2.5f, 3.125f, 4.0f, 5.0f, 6.250f, 8.0f, 10.0f, 12.625f, 15.875f, 20.0f, 31.0f, 50.0f, 80.0f, 126.0f, -1.0f}; // 36.213 Table 8.6.3-1
+static const float pusch_beta_ri[16] = {1.25f, 1.625f, 2.0f, 2.5f, 3.125f, 4.0f, 5.0f, 6.25f, 8.0f, 10.0f, 12.625f, 15.875f, 20.0f, -1.0f, -1.0f, -1.0f}; // Table 8.6.3-2 (sch.c:47-48)
 static int pusch_ack_qprime(uint32_t O, uint32_t I_offset_ack, uint32_t L_prb, uint32_t nsymb, uint32_t K_segm, bool is_ri = false, uint32_t O_cqi = 0,
                             uint32_t I_offset_cqi = 0)
 {
-  static const float beta_harq[16] = {2.0f, 2.5f, 3.125f, 4.0f, 5.0f, 6.250f, 8.0f, 10.0f, 12.625f, 15.875f, 20.0f, 31.0f, 50.0f, 80.0f, 126.0f, -1.0f}; // 36.213 Table 8.6.3-1
-  static const float beta_ri[16] = {1.25f, 1.625f, 2.0f, 2.5f, 3.125f, 4.0f, 5.0f, 6.25f, 8.0f, 10.0f, 12.625f, 15.875f, 20.0f, -1.0f, -1.0f, -1.0f}; // Table 8.6.3-2 (sch.c:47-48)
-  const float* tab = is_ri ? beta_ri : beta_harq;
+  const float* tab = is_ri ? pusch_beta_ri : pusch_beta_harq;
   if (O == 0) return 0;
   if (O > 2 || I_offset_ack > 15 || tab[I_offset_ack] < 0) return -1;
   float    beta = tab[I_offset_ack];

@@ -12,6 +12,12 @@ struct srslte_hip_sch {
   hipStream_t  st = nullptr;
   PinBuf       h_pin; // pinned: e_bits | soft buffers [Cmax][stride] | bytes [Cmax][768] | flags [Cmax] | passes [Cmax]
   size_t       o_w = 0, o_bytes = 0, o_ok = 0, o_it = 0, pin_bytes = 0;
+  // srslte_hip_ulsch_decode (ulsch_host.inc), made by its first call: the interleaved LLRs, the UCI sums, and pinned memory its kernels read
+  // (c_seq at the ACK / RI positions) and write (decisions, report)
+  DevBuf<int16_t> d_q;
+  DevBuf<int>     d_uci_sum;
+  PinBuf          h_ul;
+  uint32_t        g_len = 0; // LLRs of the last srslte_hip_ulsch_decode in d_e (srslte_hip_ulsch_debug_g)
   ~srslte_hip_sch()
   {
     if (st) (void)hipStreamSynchronize(st); // a decode that returned early may have left copies queued: they end before the buffers go
@@ -49,11 +55,12 @@ extern "C" srslte_hip_sch_t* srslte_hip_sch_create(uint32_t max_tbs, uint32_t ma
 // srslte_dlsch_decode2 derives it (2 where nof_layers != nof_tb). buffer_f[c] / cb_crc[c]: the srslte_softbuffer_rx_t's arrays of the C
 // code blocks (in / out). cb_bytes: [C][768] decoded bytes of the blocks decoded by THIS call (K / 8 each, block CRC included); blocks
 // with cb_crc set on entry are left alone. sum_passes: SISO passes over all decoded blocks (avg_iterations x C).
-extern "C" int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, uint32_t nof_e_bits, uint32_t tbs, int mod, uint32_t Nl, uint32_t rv,
-                                     uint32_t max_iterations, int16_t** buffer_f, uint8_t* cb_crc, uint8_t* cb_bytes, uint32_t* sum_passes)
+// e_bits = null (srslte_hip_ulsch_decode): the LLRs are what the stream has already been told to write to d_e, the transport block's from e_off
+// on, and the call waits for the stream even when no block is left to decode (the UCI results come down with it). waits: stream waits, added
+static int sch_decode_run(srslte_hip_sch_t* q, const void* e_bits, uint32_t nof_e_bits, uint32_t e_off, uint32_t tbs, int mod, uint32_t Nl, uint32_t rv,
+                          uint32_t max_iterations, int16_t** buffer_f, uint8_t* cb_crc, uint8_t* cb_bytes, uint32_t* sum_passes, uint32_t* waits)
 {
-  if (!q || !e_bits || !buffer_f || !cb_crc || !cb_bytes || nof_e_bits == 0 || nof_e_bits > q->max_e || max_iterations == 0 || Nl < 1 || Nl > 2 || mod < 1 ||
-      mod > 4)
+  if (!q || !buffer_f || !cb_crc || !cb_bytes || nof_e_bits == 0 || nof_e_bits > q->max_e || max_iterations == 0 || Nl < 1 || Nl > 2 || mod < 1 || mod > 4)
     return SRSLTE_ERROR_INVALID_INPUTS;
   GrantsState*   g    = &q->gs;
   const size_t   esz  = q->l8 ? 1 : 2;
@@ -67,7 +74,7 @@ extern "C" int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, ui
   GrantsBuild bd;
   bd.g = g; bd.h_sf = h_sf; bd.h_cb = h_cb; bd.l8 = q->l8; bd.max_tbs = q->max_tbs; bd.npt = 1; bd.max_mod = 4; bd.who = "sch";
   const uint32_t Qm = 2 * (uint32_t)mod;
-  if (int r = bd.add_tb(0, 0, mod, tbs, rv, 0, nof_e_bits / Qm, Nl)) return r;
+  if (int r = bd.add_tb(0, 0, mod, tbs, rv, 0, nof_e_bits / Qm, Nl, e_off)) return r;
   const uint32_t C = (uint32_t)h_sf[0].C, K = (uint32_t)h_sf[0].K;
   const uint32_t W = q->l8 ? srslte_hip_tdec_autoimp_get_subblocks_8bit(K) : srslte_hip_tdec_autoimp_get_subblocks(K);
   const uint32_t len = srslte_hip_tdec_input_len(K, W != 0); // meaningful soft-buffer elements of a block
@@ -95,10 +102,18 @@ extern "C" int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, ui
     HIP_TRY(hipMemcpyAsync((uint8_t*)g->d_w.get() + (size_t)c * g->stride * esz, stage, (size_t)len * esz, hipMemcpyHostToDevice, st));
   }
   if (sum_passes) *sum_passes = 0;
-  if (todo == 0) return SRSLTE_SUCCESS;
+  if (todo == 0) {
+    if (!e_bits) {
+      HIP_TRY(hipStreamSynchronize(st));
+      ++*waits;
+    }
+    return SRSLTE_SUCCESS;
+  }
   bd.fill_map(h.map);
-  memcpy(q->h_pin, e_bits, (size_t)nof_e_bits * esz);
-  HIP_TRY(hipMemcpyAsync(g->d_e, q->h_pin, (size_t)nof_e_bits * esz, hipMemcpyHostToDevice, st));
+  if (e_bits) {
+    memcpy(q->h_pin, e_bits, (size_t)nof_e_bits * esz);
+    HIP_TRY(hipMemcpyAsync(g->d_e, q->h_pin, (size_t)nof_e_bits * esz, hipMemcpyHostToDevice, st));
+  }
   HIP_TRY(hipMemcpyAsync(g->d_cb_ok, h_ok, C, hipMemcpyHostToDevice, st));
   if (int r = g->desc.commit(g->desc_bytes, st)) return r;
   // no transport-block assembly on the device: the caller (sch.c's decode_tb, compat) assembles from the blocks' bytes as upstream does
@@ -112,6 +127,7 @@ extern "C" int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, ui
   std::vector<uint8_t> was(cb_crc, cb_crc + C);
   HIP_TRY(hipMemcpyAsync(h_ok2, g->d_cb_ok, C, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
+  ++*waits;
   uint32_t failed = 0, passes = 0;
   for (uint32_t c = 0; c < C; c++) {
     if (was[c]) continue;
@@ -126,6 +142,7 @@ extern "C" int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, ui
   }
   if (failed) {
     HIP_TRY(hipStreamSynchronize(st));
+    ++*waits;
     for (uint32_t c = 0; c < C; c++) {
       if (was[c] || cb_crc[c]) continue;
       memcpy(buffer_f[c], q->h_pin + q->o_w + (size_t)c * g->stride * esz, (size_t)len * esz);
@@ -147,4 +164,12 @@ extern "C" int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, ui
   }
   if (sum_passes) *sum_passes = passes;
   return SRSLTE_SUCCESS;
+}
+
+extern "C" int srslte_hip_sch_decode(srslte_hip_sch_t* q, const void* e_bits, uint32_t nof_e_bits, uint32_t tbs, int mod, uint32_t Nl, uint32_t rv,
+                                     uint32_t max_iterations, int16_t** buffer_f, uint8_t* cb_crc, uint8_t* cb_bytes, uint32_t* sum_passes)
+{
+  uint32_t waits = 0;
+  if (!e_bits) return SRSLTE_ERROR_INVALID_INPUTS;
+  return sch_decode_run(q, e_bits, nof_e_bits, 0, tbs, mod, Nl, rv, max_iterations, buffer_f, cb_crc, cb_bytes, sum_passes, &waits);
 }

@@ -21,6 +21,17 @@ __device__ __forceinline__ void quant_fus(const T* in, uint16_t* us, int len, in
   }
 }
 
+// srslte_viterbi_decode_s's quantisation on an AVX2 host (viterbi.c:570-572, srslte_vec_quant_sus vector.c:443-453 with gain 1 and offset
+// 32767): the sum goes through an int16, so every positive soft bit wraps below zero and is clipped to 0; 0 gives 32767 and a negative one
+// 32767 + in. This, not the float form above, is what srslte_uci_decode_cqi_pusch's long report goes through (uci.c:403).
+__device__ __forceinline__ void quant_sus(const int16_t* in, uint16_t* us, int len, int lane)
+{
+  for (int i = lane; i < len; i += 64) {
+    const int v = in[i];
+    us[i]       = (uint16_t)(v > 0 || v == -32768 ? 0 : 32767 + v);
+  }
+}
+
 // The decoder on three repetitions of the F-bit frame (viterbi.c:144-150, TB_ITER = 3): predecessors by shuffle, decisions by ballot into
 // dec[0 .. 3F), traceback on lane 0 from the LAST state of smallest metric. dec[3F .. 3F + 6) must be zero on entry (the traceback reads
 // six words past the decisions, as the reference's does). Lane 0 leaves the decoded bits in bits[F .. 3F); the frame is bits[F .. 2F) (the
