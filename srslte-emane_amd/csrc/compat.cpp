@@ -2,49 +2,22 @@
 // kernels: copy in -> launch on the default stream -> copy out. One object per host thread, as upstream
 // (SURVEY §8b "Threading"); staging buffers are per object, so distinct objects may be used from distinct threads.
 #include "phy_hip_internal.hpp"
+#include "compat_link.hpp" // the thread's stream and pinned arena, DevStage, h2d / d2h / zc_in / zc_out, g_stats
 #include "srslte_hip/srslte_compat.h"
-#include <atomic>
 #include <math.h>
+#include <memory>
 #include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 #include <strings.h>
-#include <vector>
 
 #define ERROR(fmt, ...) hip_log("[srslte_hip] " fmt "\n", ##__VA_ARGS__)
 
+using namespace compat_link;
+
 namespace {
 
-struct DevStage { // grow-only device staging buffer
-  void*  ptr   = nullptr;
-  size_t bytes = 0;
-  void*  get(size_t n)
-  {
-    if (n > bytes) {
-      if (ptr) (void)hipFree(ptr);
-      ptr   = nullptr;
-      bytes = 0;
-      if (hipMalloc(&ptr, n) != hipSuccess) {
-        ERROR("hipMalloc(%zu) failed", n);
-        return nullptr;
-      }
-      bytes = n;
-    }
-    return ptr;
-  }
-  void release()
-  {
-    if (ptr) (void)hipFree(ptr);
-    ptr   = nullptr;
-    bytes = 0;
-  }
-};
+void* tl_stream() { return g_link.stream(); }
 
-// Host <-> device traffic of the single-call API. Every host thread owns a non-blocking stream and a pinned bounce arena: a call copies its
-// operands into the arena, queues the copies, the kernels and the copies back on that stream and waits once at the end. (hipMemcpy on the
-// callers' pageable buffers costs ~50 us per call and serialises every host thread on the null stream; the reference's worker threads -
-// three sf_workers in srsue - call these functions concurrently on distinct objects, SURVEY 8b "Threading".)
-std::atomic<unsigned long long> g_stats[4];
 std::atomic<unsigned long long> g_stats_ul[2]; // srslte_ulsch_decode calls served, stream waits inside them (srslte_hip_compat_stats_ul)
 void stats_at_exit()
 {
@@ -57,98 +30,6 @@ struct StatsInit {
     if (getenv("SRSLTE_HIP_STATS")) atexit(stats_at_exit);
   }
 } g_stats_init;
-
-struct HostLink {
-  hipStream_t st  = nullptr;
-  uint8_t*    pin = nullptr;
-  size_t      cap = 0, used = 0;
-  struct Back { void* host; const uint8_t* pinned; size_t n; };
-  std::vector<Back> back; // device -> host copies queued on the stream: their host-side half happens in flush()
-  bool ok = true;
-  hipStream_t stream()
-  {
-    if (!st && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) st = nullptr;
-    return st;
-  }
-  uint8_t* take(size_t n)
-  { // n bytes of the arena; growing it waits for what is queued (the old arena is still being read / written)
-    n = (n + 255) & ~(size_t)255;
-    if (used + n > cap) {
-      if (!flush()) return nullptr;
-      const size_t want = (cap * 2 > n ? cap * 2 : n) + (1u << 20);
-      if (pin) (void)hipHostFree(pin);
-      pin = nullptr;
-      cap = 0;
-      if (hipHostMalloc((void**)&pin, want) != hipSuccess) {
-        ERROR("hipHostMalloc(%zu) failed", want);
-        return nullptr;
-      }
-      cap = want;
-    }
-    uint8_t* p = pin + used;
-    used += n;
-    return p;
-  }
-  bool flush()
-  { // wait for the stream, hand the results to the caller's buffers, empty the arena
-    bool r = ok && (!st || hipStreamSynchronize(st) == hipSuccess);
-    g_stats[0]++;
-    for (const Back& b : back) {
-      if (r) memcpy(b.host, b.pinned, b.n);
-    }
-    back.clear();
-    used = 0;
-    ok   = true;
-    return r;
-  }
-  ~HostLink()
-  {
-    if (st) (void)hipStreamDestroy(st);
-    if (pin) (void)hipHostFree(pin);
-  }
-};
-thread_local HostLink g_link;
-void* tl_stream() { return g_link.stream(); }
-
-bool h2d(void* d, const void* h, size_t n)
-{
-  if (n == 0) return true;
-  uint8_t* p = g_link.take(n);
-  if (!p || !g_link.stream()) return false;
-  memcpy(p, h, n);
-  const bool r = hipMemcpyAsync(d, p, n, hipMemcpyHostToDevice, g_link.st) == hipSuccess;
-  g_link.ok    = g_link.ok && r;
-  return r;
-}
-// queues the copy back; the data is in `h` after the next flush (d2h() below does both)
-bool d2h_later(void* h, const void* d, size_t n)
-{
-  if (n == 0) return true;
-  uint8_t* p = g_link.take(n);
-  if (!p || !g_link.stream()) return false;
-  const bool r = hipMemcpyAsync(p, d, n, hipMemcpyDeviceToHost, g_link.st) == hipSuccess;
-  g_link.ok    = g_link.ok && r;
-  if (r) g_link.back.push_back({h, p, n});
-  return r;
-}
-bool d2h(void* h, const void* d, size_t n) { return d2h_later(h, d, n) && g_link.flush(); }
-// Small operands (a code block: under 1 KB in, 1.5 KB out): the kernel reads and writes the pinned arena itself - device-visible host memory -
-// instead of two DMA operations queued around it (each costs more than the kernel: rocprofv3 on phy_dl_test, profiles/r04/dropin_phy_dl_test_trace.txt).
-// zc_in: a device-readable copy of h[0, n); zc_out: n device-writable bytes that flush() hands to `h`.
-const uint8_t* zc_in(const void* h, size_t n)
-{
-  uint8_t* p = g_link.take(n);
-  if (!p || !g_link.stream()) return nullptr;
-  memcpy(p, h, n);
-  return p;
-}
-uint8_t* zc_out(void* h, size_t n)
-{
-  uint8_t* p = g_link.take(n);
-  if (!p || !g_link.stream()) return nullptr;
-  g_link.back.push_back({h, p, n});
-  return p;
-}
 
 void* host_alloc(size_t n)
 { // srslte_vec_malloc: posix_memalign to the SIMD width (vector.c:118-125)
@@ -172,6 +53,7 @@ struct OfdmState {
   bool               is_rx = true, norm = false, shift = false;
   float              shift_f = 0.f;
   int                mbsfn_region = 0; // 0 = regular layout on the device object
+  ~OfdmState() { srslte_hip_ofdm_destroy(h); }
 };
 
 struct TdecState {
@@ -183,15 +65,21 @@ struct TdecState {
   uint32_t           sch_tbs = 0, sch_e = 0;
   bool               sch_l8  = false;
   std::vector<uint8_t> cb_bytes, cb_crc;
+  ~TdecState()
+  {
+    srslte_hip_tdec_destroy(h);
+    srslte_hip_sch_destroy(sch);
+  }
 };
 
 struct ChestState {
   srslte_hip_chest_dl_t* h = nullptr;
   DevStage               grid, ce, res;
+  ~ChestState() { srslte_hip_chest_dl_destroy(h); }
 };
 
 // demod/tcod calls have no object to hang device staging on: one set per host thread, so that worker threads can call them
-// concurrently as they can upstream (SURVEY §8b "Threading")
+// concurrently as they can upstream (SURVEY §8b "Threading"); freed with the thread
 thread_local DevStage g_demod_in, g_demod_out, g_tcod_in, g_tcod_out;
 
 // srslte_dlsch_encode2: srslte_tcod_t has the reference's two fields and no slot for a handle, so the transport-block encoder is the calling
@@ -247,39 +135,31 @@ int srslte_symbol_sz(uint32_t nof_prb)
 void srslte_dft_load(void) {} // FFTW wisdom import/export (dft_fftw.c:44-57): nothing to persist
 void srslte_dft_exit(void) {}
 
-int srslte_dft_plan_c(srslte_dft_plan_t* plan, int dft_points, srslte_dft_dir_t dir)
-{ // dft_fftw.c:167-191
-  if (!plan) return SRSLTE_ERROR_INVALID_INPUTS;
+static size_t dft_elem(srslte_dft_mode_t mode) { return mode == SRSLTE_DFT_COMPLEX ? sizeof(cf_t) : sizeof(float); }
+static bool   dft_size_ok(int dft_points)
+{
   FftFactors  f;
   const cf32* tw;
-  if (fft_get_plan(dft_points, &f, &tw)) return SRSLTE_ERROR;
-  memset(plan, 0, sizeof(*plan));
-  plan->in  = host_alloc(sizeof(cf_t) * dft_points);
-  plan->out = host_alloc(sizeof(cf_t) * dft_points);
-  plan->p   = new DftState();
-  plan->size = plan->init_size = dft_points;
-  plan->mode    = SRSLTE_DFT_COMPLEX;
-  plan->dir     = dir;
-  plan->forward = dir == SRSLTE_DFT_FORWARD;
-  return SRSLTE_SUCCESS;
+  return fft_get_plan(dft_points, &f, &tw) == 0;
 }
 
-int srslte_dft_plan_r(srslte_dft_plan_t* plan, int dft_points, srslte_dft_dir_t dir)
-{ // dft_fftw.c:209-232: FFTW r2r plan, R2HC (forward) / HC2R (backward); served by the complex kernel
+static int dft_plan(srslte_dft_plan_t* plan, int dft_points, srslte_dft_dir_t dir, srslte_dft_mode_t mode)
+{
   if (!plan) return SRSLTE_ERROR_INVALID_INPUTS;
-  FftFactors  f;
-  const cf32* tw;
-  if (fft_get_plan(dft_points, &f, &tw)) return SRSLTE_ERROR;
+  if (!dft_size_ok(dft_points)) return SRSLTE_ERROR;
   memset(plan, 0, sizeof(*plan));
-  plan->in  = host_alloc(sizeof(float) * dft_points);
-  plan->out = host_alloc(sizeof(float) * dft_points);
+  plan->in  = host_alloc(dft_elem(mode) * dft_points);
+  plan->out = host_alloc(dft_elem(mode) * dft_points);
   plan->p   = new DftState();
   plan->size = plan->init_size = dft_points;
-  plan->mode    = SRSLTE_REAL;
+  plan->mode    = mode;
   plan->dir     = dir;
   plan->forward = dir == SRSLTE_DFT_FORWARD;
   return SRSLTE_SUCCESS;
 }
+// dft_fftw.c:167-191; :209-232: FFTW r2r plan, R2HC (forward) / HC2R (backward), served by the complex kernel
+int srslte_dft_plan_c(srslte_dft_plan_t* plan, int dft_points, srslte_dft_dir_t dir) { return dft_plan(plan, dft_points, dir, SRSLTE_DFT_COMPLEX); }
+int srslte_dft_plan_r(srslte_dft_plan_t* plan, int dft_points, srslte_dft_dir_t dir) { return dft_plan(plan, dft_points, dir, SRSLTE_REAL); }
 
 int srslte_dft_plan(srslte_dft_plan_t* plan, int dft_points, srslte_dft_dir_t dir, srslte_dft_mode_t mode)
 { // dft_fftw.c:80-85
@@ -291,9 +171,7 @@ int srslte_dft_plan_guru_c(srslte_dft_plan_t* plan, int dft_points, srslte_dft_d
 { // dft_fftw.c:137-165: batched strided transform bound to caller buffers
   if (!plan || !in_buffer || !out_buffer) return SRSLTE_ERROR_INVALID_INPUTS;
   if (istride < 1 || ostride < 1 || how_many < 1) return SRSLTE_ERROR_INVALID_INPUTS;
-  FftFactors  f;
-  const cf32* tw;
-  if (fft_get_plan(dft_points, &f, &tw)) return SRSLTE_ERROR;
+  if (!dft_size_ok(dft_points)) return SRSLTE_ERROR;
   memset(plan, 0, sizeof(*plan));
   auto* st     = new DftState();
   st->g_in     = in_buffer;
@@ -312,37 +190,21 @@ int srslte_dft_plan_guru_c(srslte_dft_plan_t* plan, int dft_points, srslte_dft_d
   return SRSLTE_SUCCESS;
 }
 
-int srslte_dft_replan_c(srslte_dft_plan_t* plan, int new_dft_points)
-{ // dft_fftw.c:120-135
-  FftFactors  f;
-  const cf32* tw;
-  if (!plan || fft_get_plan(new_dft_points, &f, &tw)) return SRSLTE_ERROR;
+static int dft_replan(srslte_dft_plan_t* plan, int new_dft_points, srslte_dft_mode_t mode)
+{ // the host buffers keep their init-time size upstream; grown here when needed
+  if (!plan || !dft_size_ok(new_dft_points)) return SRSLTE_ERROR;
   if (new_dft_points > plan->init_size) {
     free(plan->in);
     free(plan->out);
-    plan->in        = host_alloc(sizeof(cf_t) * new_dft_points);
-    plan->out       = host_alloc(sizeof(cf_t) * new_dft_points);
+    plan->in        = host_alloc(dft_elem(mode) * new_dft_points);
+    plan->out       = host_alloc(dft_elem(mode) * new_dft_points);
     plan->init_size = new_dft_points;
   }
   plan->size = new_dft_points;
   return SRSLTE_SUCCESS;
 }
-
-int srslte_dft_replan_r(srslte_dft_plan_t* plan, int new_dft_points)
-{ // dft_fftw.c:193-207 (the host buffers keep their init-time size upstream; grown here when needed)
-  FftFactors  f;
-  const cf32* tw;
-  if (!plan || fft_get_plan(new_dft_points, &f, &tw)) return SRSLTE_ERROR;
-  if (new_dft_points > plan->init_size) {
-    free(plan->in);
-    free(plan->out);
-    plan->in        = host_alloc(sizeof(float) * new_dft_points);
-    plan->out       = host_alloc(sizeof(float) * new_dft_points);
-    plan->init_size = new_dft_points;
-  }
-  plan->size = new_dft_points;
-  return SRSLTE_SUCCESS;
-}
+int srslte_dft_replan_c(srslte_dft_plan_t* plan, int new_dft_points) { return dft_replan(plan, new_dft_points, SRSLTE_DFT_COMPLEX); } // dft_fftw.c:120-135
+int srslte_dft_replan_r(srslte_dft_plan_t* plan, int new_dft_points) { return dft_replan(plan, new_dft_points, SRSLTE_REAL); }        // dft_fftw.c:193-207
 
 int srslte_dft_replan(srslte_dft_plan_t* plan, int new_dft_points)
 { // dft_fftw.c:66-78
@@ -377,12 +239,7 @@ void srslte_dft_plan_free(srslte_dft_plan_t* plan)
     free(plan->in);
     free(plan->out);
   }
-  if (plan->p) {
-    auto* st = (DftState*)plan->p;
-    st->in.release();
-    st->out.release();
-    delete st;
-  }
+  delete (DftState*)plan->p;
   memset(plan, 0, sizeof(*plan));
 }
 
@@ -400,10 +257,15 @@ static void dft_exec(srslte_dft_plan_t* plan, const cf_t* in, cf_t* out, int how
   }
 }
 
-void srslte_dft_run_c_zerocopy(srslte_dft_plan_t* plan, const cf_t* in, cf_t* out) { dft_exec(plan, in, out, 1, plan->size, plan->size); } // dft_fftw.c:277-279
+void srslte_dft_run_c_zerocopy(srslte_dft_plan_t* plan, const cf_t* in, cf_t* out)
+{ // dft_fftw.c:277-279
+  LinkScope scope;
+  dft_exec(plan, in, out, 1, plan->size, plan->size);
+}
 
 void srslte_dft_run_c(srslte_dft_plan_t* plan, const cf_t* in, cf_t* out)
 { // dft_fftw.c:281-305: copy_pre (mirror/dc for BACKWARD) -> transform -> norm -> dB -> copy_post (mirror for FORWARD)
+  LinkScope scope;
   const int N = plan->size, offset = plan->dc ? 1 : 0;
   cf_t *    pin = (cf_t*)plan->in, *pout = (cf_t*)plan->out;
   if (plan->mirror && !plan->forward) { // dft_fftw.c:249-260
@@ -437,6 +299,7 @@ void srslte_dft_run_c(srslte_dft_plan_t* plan, const cf_t* in, cf_t* out)
 
 void srslte_dft_run_r(srslte_dft_plan_t* plan, const float* in, float* out)
 { // dft_fftw.c:315-334. R2HC: out = r0 r1 .. r[N/2] i[(N+1)/2-1] .. i1 of the forward DFT; HC2R: its unnormalised inverse.
+  LinkScope         scope;
   const int         N = plan->size;
   std::vector<cf_t> a(N), b(N);
   if (plan->forward) {
@@ -482,7 +345,8 @@ void srslte_dft_run_guru_c(srslte_dft_plan_t* plan)
     ERROR("srslte_dft_run_guru_c: the selected plan is not guru!");
     return;
   }
-  auto* st = (DftState*)plan->p;
+  LinkScope scope;
+  auto*     st = (DftState*)plan->p;
   if (st->istride == 1 && st->ostride == 1) {
     dft_exec(plan, st->g_in, st->g_out, st->how_many, st->idist, st->odist);
     return;
@@ -524,14 +388,11 @@ static int ofdm_init(srslte_ofdm_t* q, srslte_cp_t cp, cf_t* in_buffer, cf_t* ou
   q->fft_plan.forward = rx;
   q->fft_plan.mirror  = true; // ofdm.c:110-111
   q->fft_plan.dc      = true;
-  auto* st            = new OfdmState();
+  auto st             = std::make_unique<OfdmState>();
   st->is_rx           = rx;
   st->h               = srslte_hip_ofdm_create_sz((int)nof_prb, N, cp == SRSLTE_CP_NORM, rx);
-  if (!st->h) {
-    delete st;
-    return SRSLTE_ERROR;
-  }
-  q->fft_plan.p = st;
+  if (!st->h) return SRSLTE_ERROR;
+  q->fft_plan.p = st.release();
   if (in_buffer) bzero(in_buffer, sizeof(cf_t) * (rx ? q->sf_sz : 2 * q->nof_symbols * q->nof_re)); // ofdm.c:80-84
   if (sf_type == SRSLTE_SF_MBSFN) { // ofdm.c:123-130
     q->mbsfn_subframe   = true;
@@ -563,13 +424,7 @@ void srslte_ofdm_set_non_mbsfn_region(srslte_ofdm_t* q, uint8_t non_mbsfn_region
 static void ofdm_free(srslte_ofdm_t* q)
 { // ofdm.c:214-233
   if (!q) return;
-  auto* st = (OfdmState*)q->fft_plan.p;
-  if (st) {
-    srslte_hip_ofdm_destroy(st->h);
-    st->in.release();
-    st->out.release();
-    delete st;
-  }
+  delete (OfdmState*)q->fft_plan.p;
   memset(q, 0, sizeof(*q));
 }
 void srslte_ofdm_rx_free(srslte_ofdm_t* q) { ofdm_free(q); }
@@ -666,10 +521,11 @@ static void ofdm_run(srslte_ofdm_t* q, const cf_t* host_in, cf_t* host_out, int 
   }
 }
 
-void srslte_ofdm_rx_sf(srslte_ofdm_t* q) { ofdm_run(q, q->in_buffer, q->out_buffer, 2, 0, q->mbsfn_subframe); } // ofdm.c:453-467
-void srslte_ofdm_tx_sf(srslte_ofdm_t* q) { ofdm_run(q, q->in_buffer, q->out_buffer, 2, 0, q->mbsfn_subframe); } // ofdm.c:580-594
+void srslte_ofdm_rx_sf(srslte_ofdm_t* q) { LinkScope scope; ofdm_run(q, q->in_buffer, q->out_buffer, 2, 0, q->mbsfn_subframe); } // ofdm.c:453-467
+void srslte_ofdm_tx_sf(srslte_ofdm_t* q) { LinkScope scope; ofdm_run(q, q->in_buffer, q->out_buffer, 2, 0, q->mbsfn_subframe); } // ofdm.c:580-594
 void srslte_ofdm_rx_sf_ng(srslte_ofdm_t* q, cf_t* input, cf_t* output)
 { // ofdm.c:469-483: the MBSFN branch upstream ignores the arguments and works on the bound buffers
+  LinkScope scope;
   if (q->mbsfn_subframe) {
     ofdm_run(q, q->in_buffer, q->out_buffer, 2, 0, true);
   } else {
@@ -678,13 +534,15 @@ void srslte_ofdm_rx_sf_ng(srslte_ofdm_t* q, cf_t* input, cf_t* output)
 }
 void srslte_ofdm_rx_slot(srslte_ofdm_t* q, int slot_in_sf)
 { // ofdm.c:398-422
+  LinkScope scope;
   ofdm_run(q, q->in_buffer + slot_in_sf * q->slot_sz, q->out_buffer + slot_in_sf * q->nof_re * q->nof_symbols, slot_in_sf ? 1 : 0, slot_in_sf ? 1 : 0, false);
 }
 void srslte_ofdm_tx_slot(srslte_ofdm_t* q, int slot_in_sf)
 { // ofdm.c:488-530
+  LinkScope scope;
   ofdm_run(q, q->in_buffer + slot_in_sf * q->nof_re * q->nof_symbols, q->out_buffer + slot_in_sf * q->slot_sz, slot_in_sf ? 1 : 0, slot_in_sf ? 1 : 0, false);
 }
-void srslte_ofdm_rx_slot_ng(srslte_ofdm_t* q, cf_t* input, cf_t* output) { ofdm_run(q, input, output, 0, 0, false); } // ofdm.c:384-393
+void srslte_ofdm_rx_slot_ng(srslte_ofdm_t* q, cf_t* input, cf_t* output) { LinkScope scope; ofdm_run(q, input, output, 0, 0, false); } // ofdm.c:384-393
 
 static bool mbsfn_ready(srslte_ofdm_t* q)
 {
@@ -694,10 +552,12 @@ static bool mbsfn_ready(srslte_ofdm_t* q)
 }
 void srslte_ofdm_rx_slot_mbsfn(srslte_ofdm_t* q, cf_t* input, cf_t* output)
 { // ofdm.c:424-437
+  LinkScope scope;
   if (mbsfn_ready(q)) ofdm_run(q, input, output, 0, 0, true);
 }
 void srslte_ofdm_tx_slot_mbsfn(srslte_ofdm_t* q, cf_t* input, cf_t* output)
 { // ofdm.c:558-574
+  LinkScope scope;
   if (mbsfn_ready(q)) ofdm_run(q, input, output, 0, 0, true);
 }
 
@@ -740,6 +600,7 @@ int srslte_dft_precoding(srslte_dft_precoding_t* q, cf_t* input, cf_t* output, u
     ERROR("Error invalid number of PRB (%u)", nof_prb);
     return SRSLTE_ERROR;
   }
+  LinkScope          scope;
   srslte_dft_plan_t* plan = &q->dft_plan[nof_prb];
   auto*              st   = (DftState*)plan->p;
   const int          N    = 12 * (int)nof_prb;
@@ -790,6 +651,7 @@ int srslte_tcod_encode(srslte_tcod_t* h, uint8_t* input, uint8_t* output, uint32
     ERROR("Turbo coder initiated for max_long_cb=%u", h->max_long_cb);
     return SRSLTE_ERROR;
   }
+  LinkScope scope;
   void *di = g_tcod_in.get(long_cb), *dout = g_tcod_out.get(3 * long_cb + 12);
   if (!di || !dout || !h2d(di, input, long_cb)) return SRSLTE_ERROR;
   if (srslte_hip_tcod_encode_batch((const uint8_t*)di, (uint8_t*)dout, long_cb, 1, tl_stream())) return SRSLTE_ERROR;
@@ -838,13 +700,13 @@ int srslte_tcod_encode_lut(srslte_tcod_t* h, srslte_crc_t* crc_tb, srslte_crc_t*
     if (last_cb) append(crc_tb, n, false);
   }
   const uint32_t npar = long_cb / 4 + 1;
+  LinkScope      scope;
+  // the three regions the kernel reads and writes come from one reservation: the arena does not move once the first is handed out
+  if (!g_link.reserve(HostLink::rounded(nbytes) + HostLink::rounded(npar) + HostLink::rounded(1))) return SRSLTE_ERROR;
   const uint8_t* di   = zc_in(input, nbytes);
   uint8_t *      dpar = zc_out(parity, npar), *dtail = zc_out(&input[nbytes], 1);
   if (!di || !dpar || !dtail) return SRSLTE_ERROR;
-  if (srslte_hip_tcod_encode_bytes_batch(di, nbytes, dpar, npar, dtail, long_cb, 1, tl_stream())) {
-    (void)g_link.flush();
-    return SRSLTE_ERROR;
-  }
+  if (srslte_hip_tcod_encode_bytes_batch(di, nbytes, dpar, npar, dtail, long_cb, 1, tl_stream())) return SRSLTE_ERROR;
   if (!g_link.flush()) return SRSLTE_ERROR;
   return (int)(3 * long_cb + 12);
 }
@@ -866,13 +728,10 @@ int srslte_tdec_init_manual(srslte_tdec_t* h, uint32_t max_long_cb, srslte_tdec_
     case SRSLTE_TDEC_AVX8_WINDOW: break;
     default: ERROR("Error decoder %d not supported", (int)dec_type); return SRSLTE_ERROR;
   }
-  auto* st = new TdecState();
-  st->h    = srslte_hip_tdec_create(max_long_cb, 1);
-  if (!st->h) {
-    delete st;
-    return SRSLTE_ERROR;
-  }
-  h->dec16_hdlr[0]    = st;
+  auto st = std::make_unique<TdecState>();
+  st->h   = srslte_hip_tdec_create(max_long_cb, 1);
+  if (!st->h) return SRSLTE_ERROR;
+  h->dec16_hdlr[0]    = st.release();
   h->max_long_cb      = max_long_cb;
   h->dec_type         = dec_type;
   h->current_llr_type = dec_type >= SRSLTE_TDEC_SSE8_WINDOW ? SRSLTE_TDEC_8 : SRSLTE_TDEC_16;
@@ -883,14 +742,7 @@ int srslte_tdec_init(srslte_tdec_t* h, uint32_t max_long_cb) { return srslte_tde
 
 void srslte_tdec_free(srslte_tdec_t* h)
 {
-  auto* st = (TdecState*)h->dec16_hdlr[0];
-  if (st) {
-    srslte_hip_tdec_destroy(st->h);
-    srslte_hip_sch_destroy(st->sch);
-    st->in.release();
-    st->out.release();
-    delete st;
-  }
+  delete (TdecState*)h->dec16_hdlr[0];
   memset(h, 0, sizeof(*h));
 }
 void srslte_tdec_force_not_sb(srslte_tdec_t* h) { h->force_not_sb = true; }
@@ -969,10 +821,22 @@ static void tdec_one_more(srslte_tdec_t* h, const void* input, bool api8, uint8_
     ERROR("Error CB index not set (call srslte_tdec_new_cb() first");
   }
 }
-void srslte_tdec_iteration(srslte_tdec_t* h, int16_t* input, uint8_t* output) { tdec_one_more(h, input, false, output); }
-void srslte_tdec_iteration_8bit(srslte_tdec_t* h, int8_t* input, uint8_t* output) { tdec_one_more(h, input, true, output); }
+void srslte_tdec_iteration(srslte_tdec_t* h, int16_t* input, uint8_t* output) { LinkScope scope; tdec_one_more(h, input, false, output); }
+void srslte_tdec_iteration_8bit(srslte_tdec_t* h, int8_t* input, uint8_t* output) { LinkScope scope; tdec_one_more(h, input, true, output); }
 
-static srslte_hip_sch_t* sch_object(TdecState* st, uint32_t tbs, uint32_t nof_bits, bool l8);
+// the transport-block decoder of the srslte_sch_t: made on first use and again when a larger block or the other LLR width comes
+static srslte_hip_sch_t* sch_object(TdecState* st, uint32_t tbs, uint32_t nof_bits, bool l8)
+{
+  if (!st->sch || tbs > st->sch_tbs || nof_bits > st->sch_e || st->sch_l8 != l8) {
+    srslte_hip_sch_destroy(st->sch);
+    st->sch_tbs = tbs > st->sch_tbs ? tbs : st->sch_tbs;
+    st->sch_e   = nof_bits > st->sch_e ? nof_bits : st->sch_e;
+    st->sch_l8  = l8;
+    st->sch     = srslte_hip_sch_create(st->sch_tbs, st->sch_e, st->sch_l8 ? 1 : 0);
+    if (!st->sch) st->sch_tbs = st->sch_e = 0;
+  }
+  return st->sch;
+}
 static void tb_begin(TdecState* st, const srslte_softbuffer_rx_t* sb, const srslte_cbsegm_t& seg, uint8_t* data);
 static int  tb_finish(srslte_sch_t* q, TdecState* st, srslte_softbuffer_rx_t* sb, const srslte_cbsegm_t& seg, uint8_t* data, uint32_t passes);
 
@@ -1013,20 +877,6 @@ int srslte_dlsch_decode2(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, int16_t* e_bi
   return tb_finish(q, st, sb, seg, data, passes);
 }
 int srslte_dlsch_decode(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, int16_t* e_bits, uint8_t* data) { return srslte_dlsch_decode2(q, cfg, e_bits, data, 0, 1); }
-
-// the transport-block decoder of the srslte_sch_t: made on first use and again when a larger block or the other LLR width comes
-static srslte_hip_sch_t* sch_object(TdecState* st, uint32_t tbs, uint32_t nof_bits, bool l8)
-{
-  if (!st->sch || tbs > st->sch_tbs || nof_bits > st->sch_e || st->sch_l8 != l8) {
-    srslte_hip_sch_destroy(st->sch);
-    st->sch_tbs = tbs > st->sch_tbs ? tbs : st->sch_tbs;
-    st->sch_e   = nof_bits > st->sch_e ? nof_bits : st->sch_e;
-    st->sch_l8  = l8;
-    st->sch     = srslte_hip_sch_create(st->sch_tbs, st->sch_e, st->sch_l8 ? 1 : 0);
-    if (!st->sch) st->sch_tbs = st->sch_e = 0;
-  }
-  return st->sch;
-}
 
 // decode_tb around the device call (sch.c:461-488, decode_tb_cb :312-412), for the DL-SCH and the UL-SCH alike. tb_begin: the three CRC bytes
 // cleared (data = null: the caller does that once nothing can be refused any more), the soft buffer's flags as the device call takes them
@@ -1255,10 +1105,12 @@ static int tdec_all(srslte_tdec_t* h, const void* input, bool api8, uint8_t* out
 }
 int srslte_tdec_run_all(srslte_tdec_t* h, int16_t* input, uint8_t* output, uint32_t nof_iterations, uint32_t long_cb)
 {
+  LinkScope scope;
   return tdec_all(h, input, false, output, nof_iterations, long_cb);
 }
 int srslte_tdec_run_all_8bit(srslte_tdec_t* h, int8_t* input, uint8_t* output, uint32_t nof_iterations, uint32_t long_cb)
 {
+  LinkScope scope;
   return tdec_all(h, input, true, output, nof_iterations, long_cb);
 }
 
@@ -1273,27 +1125,11 @@ int srslte_chest_dl_init(srslte_chest_dl_t* q, uint32_t max_prb, uint32_t nof_rx
   return SRSLTE_SUCCESS;
 }
 
-static void chest_drop_cell(srslte_chest_dl_t* q)
-{
-  auto* st = (ChestState*)q->tmp_noise;
-  if (st && st->h) {
-    srslte_hip_chest_dl_destroy(st->h);
-    st->h = nullptr;
-  }
-}
-
 void srslte_chest_dl_free(srslte_chest_dl_t* q)
 { // chest_dl.c:162-191
   if (!q) return;
-  chest_drop_cell(q);
   srslte_refsignal_free(&q->csr_refs);
-  auto* st = (ChestState*)q->tmp_noise;
-  if (st) {
-    st->grid.release();
-    st->ce.release();
-    st->res.release();
-    delete st;
-  }
+  delete (ChestState*)q->tmp_noise;
   memset(q, 0, sizeof(*q));
 }
 
@@ -1302,9 +1138,9 @@ int srslte_chest_dl_set_cell(srslte_chest_dl_t* q, srslte_cell_t cell)
   // srslte_cell_isvalid (phy_common.c:38-60): a cell of more than 100 PRB is refused before anything changes, as upstream
   if (!q || !q->tmp_noise || cell.nof_prb < 6 || cell.nof_prb > 100 || cell.id > 503 || cell.nof_ports > SRSLTE_MAX_PORTS) return SRSLTE_ERROR_INVALID_INPUTS;
   if (q->cell.id == cell.id && q->cell.nof_prb == cell.nof_prb && ((ChestState*)q->tmp_noise)->h) return SRSLTE_SUCCESS;
-  chest_drop_cell(q);
   auto* st = (ChestState*)q->tmp_noise;
-  st->h    = srslte_hip_chest_dl_create(cell.id, cell.nof_prb, cell.nof_ports, cell.cp == SRSLTE_CP_NORM);
+  srslte_hip_chest_dl_destroy(st->h);
+  st->h = srslte_hip_chest_dl_create(cell.id, cell.nof_prb, cell.nof_ports, cell.cp == SRSLTE_CP_NORM);
   if (!st->h) return SRSLTE_ERROR;
   q->cell = cell;
   // host copy of the CRS values for callers that use srslte_refsignal_cs_put_sf(&q->csr_refs, ...) (chest_test_dl.c:154); the device
@@ -1360,19 +1196,16 @@ void srslte_chest_dl_res_free(srslte_chest_dl_res_t* q)
 
 // MBSFN subframes (chest_dl.c:718-745,:892-896): estimates and, with the REFS algorithm, the noise come from the device; rsrp, rssi, cfo,
 // the sync error (and the noise with PSS / EMPTY) are what the last normal subframe left in q, and fill_res (:845-871) reads those
-static int chest_dl_estimate_mbsfn(srslte_chest_dl_t* q, ChestState* st, srslte_dl_sf_cfg_t* sf, srslte_chest_dl_cfg_t* cfg,
-                                   cf_t* input[SRSLTE_MAX_PORTS], srslte_chest_dl_res_t* res)
+static float chest_db(float a) { return (float)(10 * log10(a)); }
+static float chest_dbm(float a) { return (float)(10 * log10(a) + 30); }
+
+// srslte_chest_dl_estimate_cfg has sent the antennas' grids (n bytes each) to dg and filled the fields of hc that both subframe types read
+static int chest_dl_estimate_mbsfn(srslte_chest_dl_t* q, ChestState* st, srslte_dl_sf_cfg_t* sf, srslte_chest_dl_cfg_t* cfg, srslte_chest_dl_res_t* res,
+                                   srslte_hip_chest_dl_cfg_t& hc, size_t n, char* dg, char* dce, bool want_ce)
 {
   const uint32_t nrx = q->nof_rx_antennas, npt = q->cell.nof_ports;
-  const size_t   n   = sizeof(cf_t) * 2 * cp_nsymb(q->cell.cp) * 12 * q->cell.nof_prb; // SRSLTE_SF_LEN_RE
-  char *         dg = (char*)st->grid.get(n * nrx), *dce = (char*)st->ce.get(n * nrx * npt);
   float*         dnoise = (float*)st->res.get(sizeof(float) * 16);
-  if (!dg || !dce || !dnoise) return SRSLTE_ERROR;
-  bool want_ce = false;
-  for (uint32_t a = 0; a < nrx; a++) {
-    if (!input[a] || !h2d(dg + a * n, input[a], n)) return SRSLTE_ERROR_INVALID_INPUTS;
-    for (uint32_t pt = 0; pt < npt; pt++) want_ce = want_ce || res->ce[pt][a];
-  }
+  if (!dnoise) return SRSLTE_ERROR;
   if (want_ce) { // the caller's symbols 12, 13 (not part of the 12-symbol subframe) stay as they are
     for (uint32_t pt = 0; pt < npt; pt++) {
       for (uint32_t a = 0; a < nrx; a++) {
@@ -1380,11 +1213,7 @@ static int chest_dl_estimate_mbsfn(srslte_chest_dl_t* q, ChestState* st, srslte_
       }
     }
   }
-  srslte_hip_chest_dl_cfg_t hc;
-  memset(&hc, 0, sizeof(hc));
-  hc.noise_alg = cfg->noise_alg; hc.filter_type = cfg->filter_type; hc.filter_coef[0] = cfg->filter_coef[0]; hc.filter_coef[1] = cfg->filter_coef[1];
-  hc.interpolate_subframe = cfg->interpolate_subframe; hc.mbsfn_area_id = cfg->mbsfn_area_id;
-  srslte_hip_chest_dl_set_symbol_sz(st->h, srslte_symbol_sz(q->cell.nof_prb)); // chest_dl.c:575,:695: read at every call
+  hc.mbsfn_area_id = cfg->mbsfn_area_id;
   if (srslte_hip_chest_dl_estimate_mbsfn_batch(st->h, &hc, sf->tti % 10, dg, want_ce ? dce : nullptr, dnoise, 1, (int)nrx, tl_stream())) return SRSLTE_ERROR;
   if (cfg->noise_alg == SRSLTE_NOISE_ALG_REFS) {
     float nz[16];
@@ -1399,8 +1228,6 @@ static int chest_dl_estimate_mbsfn(srslte_chest_dl_t* q, ChestState* st, srslte_
     }
   }
   // fill_res (chest_dl.c:747-871) on the estimator's kept state
-  auto  dbm = [](float a) { return (float)(10 * log10(a) + 30); };
-  auto  db  = [](float a) { return (float)(10 * log10(a)); };
   float noise = 0.f, rssi = 0.f, rsrq = 0.f, rsrp = -1e9f, neigh = -1e9f;
   for (uint32_t a = 0; a < nrx; a++) {
     float s = 0.f, c = 0.f;
@@ -1418,18 +1245,18 @@ static int chest_dl_estimate_mbsfn(srslte_chest_dl_t* q, ChestState* st, srslte_
     neigh = c / npt > neigh ? c / npt : neigh;
   }
   noise /= nrx; rssi /= nrx; rsrq /= nrx;
-  res->noise_estimate = noise; res->noise_estimate_dbm = dbm(noise); res->cfo = q->cfo; res->rsrp = rsrp; res->rsrp_dbm = dbm(rsrp);
-  res->rsrp_neigh = neigh; res->rsrq = rsrq; res->rsrq_db = db(rsrq); res->snr_db = db(rsrp / noise); res->rssi_dbm = dbm(rssi);
+  res->noise_estimate = noise; res->noise_estimate_dbm = chest_dbm(noise); res->cfo = q->cfo; res->rsrp = rsrp; res->rsrp_dbm = chest_dbm(rsrp);
+  res->rsrp_neigh = neigh; res->rsrq = rsrq; res->rsrq_db = chest_db(rsrq); res->snr_db = chest_db(rsrp / noise); res->rssi_dbm = chest_dbm(rssi);
   res->sync_error = q->sync_err[0][0];
   for (uint32_t pt = 0; pt < npt; pt++) {
     float mean_rsrp = 0.f;
     for (uint32_t a = 0; a < nrx; a++) {
       mean_rsrp += q->rsrp[a][pt] / nrx;
-      res->snr_ant_port_db[a][pt]   = db(q->rsrp[a][pt] / q->noise_estimate[a][pt]);
-      res->rsrp_ant_port_dbm[a][pt] = dbm(q->rsrp[a][pt]);
-      res->rsrq_ant_port_db[a][pt]  = db(q->cell.nof_prb * q->rsrp[a][pt] / q->rssi[a][pt]);
+      res->snr_ant_port_db[a][pt]   = chest_db(q->rsrp[a][pt] / q->noise_estimate[a][pt]);
+      res->rsrp_ant_port_dbm[a][pt] = chest_dbm(q->rsrp[a][pt]);
+      res->rsrq_ant_port_db[a][pt]  = chest_db(q->cell.nof_prb * q->rsrp[a][pt] / q->rssi[a][pt]);
     }
-    res->rsrp_port_dbm[pt] = dbm(mean_rsrp);
+    res->rsrp_port_dbm[pt] = chest_dbm(mean_rsrp);
   }
   return SRSLTE_SUCCESS;
 }
@@ -1439,12 +1266,11 @@ int srslte_chest_dl_estimate_cfg(srslte_chest_dl_t* q, srslte_dl_sf_cfg_t* sf, s
 { // chest_dl.c:884-908
   auto* st = q ? (ChestState*)q->tmp_noise : nullptr;
   if (!st || !st->h || !sf || !cfg || !input || !res) return SRSLTE_ERROR_INVALID_INPUTS;
-  if (sf->sf_type == SRSLTE_SF_MBSFN) return chest_dl_estimate_mbsfn(q, st, sf, cfg, input, res);
+  LinkScope      scope;
   const uint32_t nrx = q->nof_rx_antennas, npt = q->cell.nof_ports;
   const size_t   n   = sizeof(cf_t) * 2 * cp_nsymb(q->cell.cp) * 12 * q->cell.nof_prb; // SRSLTE_SF_LEN_RE
   char *         dg = (char*)st->grid.get(n * nrx), *dce = (char*)st->ce.get(n * nrx * npt);
-  void*          dres = st->res.get(sizeof(srslte_hip_chest_dl_res_t));
-  if (!dg || !dce || !dres) return SRSLTE_ERROR;
+  if (!dg || !dce) return SRSLTE_ERROR;
   bool want_ce = false;
   for (uint32_t a = 0; a < nrx; a++) {
     if (!input[a] || !h2d(dg + a * n, input[a], n)) return SRSLTE_ERROR_INVALID_INPUTS;
@@ -1453,7 +1279,12 @@ int srslte_chest_dl_estimate_cfg(srslte_chest_dl_t* q, srslte_dl_sf_cfg_t* sf, s
   srslte_hip_chest_dl_cfg_t hc;
   memset(&hc, 0, sizeof(hc));
   hc.noise_alg = cfg->noise_alg; hc.filter_type = cfg->filter_type; hc.filter_coef[0] = cfg->filter_coef[0]; hc.filter_coef[1] = cfg->filter_coef[1];
-  hc.interpolate_subframe = cfg->interpolate_subframe; hc.rsrp_neighbour = cfg->rsrp_neighbour;
+  hc.interpolate_subframe = cfg->interpolate_subframe;
+  srslte_hip_chest_dl_set_symbol_sz(st->h, srslte_symbol_sz(q->cell.nof_prb)); // chest_dl.c:575,:695: read at every call
+  if (sf->sf_type == SRSLTE_SF_MBSFN) return chest_dl_estimate_mbsfn(q, st, sf, cfg, res, hc, n, dg, dce, want_ce);
+  void* dres = st->res.get(sizeof(srslte_hip_chest_dl_res_t));
+  if (!dres) return SRSLTE_ERROR;
+  hc.rsrp_neighbour       = cfg->rsrp_neighbour;
   hc.cfo_estimate_enable  = cfg->cfo_estimate_enable && ((1u << (sf->tti % 10)) & cfg->cfo_estimate_sf_mask);
   hc.cfo_estimate_sf_mask = cfg->cfo_estimate_sf_mask; hc.sync_error_enable = cfg->sync_error_enable;
   if (hc.noise_alg != SRSLTE_NOISE_ALG_REFS) { // PSS / EMPTY renew q->noise_estimate in subframes 0 and 5 only (chest_dl.c:657-672)
@@ -1472,7 +1303,6 @@ int srslte_chest_dl_estimate_cfg(srslte_chest_dl_t* q, srslte_dl_sf_cfg_t* sf, s
       }
     }
   }
-  srslte_hip_chest_dl_set_symbol_sz(st->h, srslte_symbol_sz(q->cell.nof_prb)); // chest_dl.c:575,:695: read at every call
   // TDD cell: a special subframe has only the CRS symbols of its DwPTS (srslte_refsignal_cs_nof_symbols reads sf->tdd_config at every call)
   const bool tdd = q->cell.frame_type == SRSLTE_TDD && sf->tdd_config.configured && sf->tdd_config.sf_config < 7 && sf->tdd_config.ss_config < 10;
   if (srslte_hip_chest_dl_set_tdd(st->h, tdd ? (int)sf->tdd_config.sf_config : -1, tdd ? (int)sf->tdd_config.ss_config : 0)) return SRSLTE_ERROR;
@@ -1522,11 +1352,11 @@ int srslte_chest_dl_estimate_cfg(srslte_chest_dl_t* q, srslte_dl_sf_cfg_t* sf, s
         q->rsrp[a][pt]           = v[1];
         q->rssi[a][pt]           = v[2];
         mean_rsrp += v[1] / nrx;
-        res->snr_ant_port_db[a][pt]   = (float)(10 * log10(v[1] / v[0]));
-        res->rsrp_ant_port_dbm[a][pt] = (float)(10 * log10(v[1]) + 30);
-        res->rsrq_ant_port_db[a][pt]  = (float)(10 * log10(q->cell.nof_prb * v[1] / v[2]));
+        res->snr_ant_port_db[a][pt]   = chest_db(v[1] / v[0]);
+        res->rsrp_ant_port_dbm[a][pt] = chest_dbm(v[1]);
+        res->rsrq_ant_port_db[a][pt]  = chest_db(q->cell.nof_prb * v[1] / v[2]);
       }
-      res->rsrp_port_dbm[pt] = (float)(10 * log10(mean_rsrp) + 30);
+      res->rsrp_port_dbm[pt] = chest_dbm(mean_rsrp);
     }
   }
   return SRSLTE_SUCCESS;
@@ -1554,8 +1384,8 @@ static int demod_host(int type, srslte_mod_t mod, const cf_t* symbols, void* llr
   if (demod_launch(type, (int)mod, di, dout, nsymbols, 1, nullptr, 0, 0, (hipStream_t)tl_stream())) return SRSLTE_ERROR;
   return d2h(llr, dout, nout) ? SRSLTE_SUCCESS : SRSLTE_ERROR;
 }
-int srslte_demod_soft_demodulate(srslte_mod_t m, const cf_t* s, float* llr, int n) { return demod_host(0, m, s, llr, n, sizeof(float)); }
-int srslte_demod_soft_demodulate_s(srslte_mod_t m, const cf_t* s, short* llr, int n) { return demod_host(1, m, s, llr, n, sizeof(short)); }
-int srslte_demod_soft_demodulate_b(srslte_mod_t m, const cf_t* s, int8_t* llr, int n) { return demod_host(2, m, s, llr, n, sizeof(int8_t)); }
+int srslte_demod_soft_demodulate(srslte_mod_t m, const cf_t* s, float* llr, int n) { LinkScope scope; return demod_host(0, m, s, llr, n, sizeof(float)); }
+int srslte_demod_soft_demodulate_s(srslte_mod_t m, const cf_t* s, short* llr, int n) { LinkScope scope; return demod_host(1, m, s, llr, n, sizeof(short)); }
+int srslte_demod_soft_demodulate_b(srslte_mod_t m, const cf_t* s, int8_t* llr, int n) { LinkScope scope; return demod_host(2, m, s, llr, n, sizeof(int8_t)); }
 
 } // extern "C"

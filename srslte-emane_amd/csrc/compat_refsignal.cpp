@@ -8,6 +8,7 @@
 //     copy out of the other single-call wrappers (compat.cpp); no host arithmetic path exists for them.
 // The batched pipeline uses none of this: its estimator kernels hold their own device tables (chest.hip).
 #include "phy_hip_internal.hpp"
+#include "compat_link.hpp"
 #include "srslte_hip/srslte_compat.h"
 #include <math.h>
 #include <stdlib.h>
@@ -65,26 +66,8 @@ int alloc_tables(srslte_refsignal_t* q, size_t n)
   return SRSLTE_SUCCESS;
 }
 
-// per-thread staging for the two device helpers (no object to hang it on, as for the demapper)
-struct Stage {
-  void*  p = nullptr;
-  size_t n = 0;
-  void*  get(size_t bytes)
-  {
-    if (bytes > n) {
-      if (p) (void)hipFree(p);
-      p = nullptr;
-      n = 0;
-      if (hipMalloc(&p, bytes) != hipSuccess) {
-        ERROR("hipMalloc(%zu) failed", bytes);
-        return nullptr;
-      }
-      n = bytes;
-    }
-    return p;
-  }
-};
-thread_local Stage g_a, g_b, g_c, g_f;
+// per-thread staging for the two device helpers (no object to hang it on, as for the demapper); freed with the thread
+thread_local compat_link::DevStage g_a, g_b, g_c, g_f;
 
 } // namespace
 
