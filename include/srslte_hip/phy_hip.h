@@ -634,6 +634,34 @@ void                  srslte_hip_sch_enc_destroy(srslte_hip_sch_enc_t* q);
  * tbs == 0: SRSLTE_SUCCESS and nothing written, as upstream's loop over C = 0 blocks. */
 int srslte_hip_sch_encode(srslte_hip_sch_enc_t* q, const uint8_t* data, uint32_t tbs, int mod, uint32_t Nl, uint32_t rv, uint32_t nof_e_bits,
                           uint8_t** buffer_b, uint8_t* e_bits);
+/* The same for one PUSCH: what srslte_ulsch_encode does (sch.c:1068-1210) into the caller's packed q_bits (host, nof_bits / 8 bytes, MSB first,
+ * every byte written) - the coded CQI report in bits [0, Q'_cqi Qm) of the stream g (srslte_uci_encode_cqi_pusch, uci.c:467-494), the UL-SCH's
+ * G Qm bits behind it at bit granularity (G = H' - Q'_ri - Q'_cqi; data / buffer_b / rv as srslte_hip_sch_encode), the channel interleaver
+ * that leaves the rank indication's symbols out of its read order (36.212 5.2.2.8) and the HARQ-ACK symbols over what it wrote: a coded bit of
+ * type 1 sets its position, every other type (0, repetition, placeholder) clears it, as upstream - pusch.c fills the placeholder and
+ * repetition bits after scrambling. One stream wait per call. g_bits: NULL, or (H' - Q'_ri) Qm bits of g from bit 0; the rest of the last
+ * byte keeps the caller's value. tbs 0: a PUSCH without UL-SCH data, which carries a report (cqi_len > 0); data / buffer_b are not looked at.
+ * Q' in upstream's float arithmetic (uci.c:266-281,:547-571). Refused before anything is queued or written, with
+ * SRSLTE_ERROR_INVALID_INPUTS: what srslte_hip_sch_encode refuses, with its codes (filler bits: SRSLTE_ERROR); mod outside 1..3, nof_symb
+ * outside 9..12, nof_bits != 12 L_prb nof_symb Qm, ri_len > 2, ack_len > 10, cqi_len > 64, offsets above 15, tbs 0 without a report,
+ * Q'_ri + Q'_cqi >= H' with tbs > 0; a reserved beta offset of a field in use: -1, as upstream. */
+typedef struct {
+  int      mod;                                   /* 1 QPSK, 2 16QAM, 3 64QAM */
+  uint32_t tbs, rv, nof_bits, L_prb, nof_symb;
+  uint32_t ack_len, ri_len, cqi_len;              /* HARQ-ACK bits 0-10 (3 and more: the (32, O) block code), RI bits 0-2, report bits 0-64 */
+  uint32_t I_offset_ack, I_offset_ri, I_offset_cqi;
+  uint8_t  ack[10], ri;                           /* srslte_uci_value_t.ack.ack_value / .ri (a 2-bit RI sends ri and a zero, sch.c:1115) */
+  uint8_t  cqi_bits[64];                          /* the packed report, one bit per byte (srslte_hip_cqi_value_pack's row) */
+} srslte_hip_ulsch_enc_cfg_t;
+typedef struct {
+  uint32_t Q_prime_ack, Q_prime_ri, Q_prime_cqi;
+  uint32_t stream_waits;
+} srslte_hip_ulsch_enc_res_t;
+int srslte_hip_ulsch_encode(srslte_hip_sch_enc_t* q, const uint8_t* data, const srslte_hip_ulsch_enc_cfg_t* cfg, uint8_t** buffer_b, uint8_t* g_bits,
+                            uint8_t* q_bits, srslte_hip_ulsch_enc_res_t* res);
+/* debugging accessor: the first n_words 32-bit words of the last srslte_hip_ulsch_encode's stream g from the device (n_words <= ceil of its
+ * (H' - Q'_ri) Qm bits / 32; byte order as g_bits) */
+int srslte_hip_ulsch_enc_debug(srslte_hip_sch_enc_t* q, uint32_t* out, uint32_t n_words);
 
 /* ------------------------------------------------------------------ DL control region receive (UE side): the part of srslte_ue_dl_find_dl_dci
  * that precedes the DCI unpacking, for a batch of subframes (ue/ue_dl.c:334-367 estimate_pdcch_pcfich, :422-478 dci_blind_search, :534-646

@@ -12,9 +12,9 @@
  * tests/test_abi_layout.py checks sizeof/offsetof of every struct below against the reference headers.
  *
  * Not provided (documented in DESIGN.md): interpolate_subframe on a 4-port cell or switched off in an MBSFN subframe; those calls
- * return SRSLTE_ERROR with a message. Of sch.c the library serves the DL-SCH in both directions (srslte_dlsch_decode2, srslte_dlsch_encode2) and the
- * UL-SCH receiver with its UCI (srslte_ulsch_decode); srslte_ulsch_encode is not exported: its transport-block half is sch.c's static
- * encode_tb_off and the rest is UCI multiplexing, which stays the reference's.
+ * return SRSLTE_ERROR with a message. Of sch.c the library serves all four shared-channel entries, each as one device call per transport
+ * block: the DL-SCH in both directions (srslte_dlsch_decode2, srslte_dlsch_encode2) and the UL-SCH with its UCI in both (srslte_ulsch_decode,
+ * srslte_ulsch_encode).
  */
 #ifndef SRSLTE_HIP_SRSLTE_COMPAT_H
 #define SRSLTE_HIP_SRSLTE_COMPAT_H
@@ -236,8 +236,7 @@ int srslte_dlsch_decode2(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, int16_t* e_bi
  * library takes them), for data == NULL with rv == 0 and for rv > 3. This library reads grant.tb[] (mod, tbs, rv, nof_bits) / grant.nof_tb /
  * softbuffers.tx[] of srslte_pdsch_cfg_t and the srslte_softbuffer_tx_t; of srslte_sch_t only that it is there. The encoder object belongs to the
  * calling thread (srslte_tcod_t has no slot for a handle): made on first use, grown when a larger block comes, freed with the thread.
- * Not served: srslte_ulsch_encode - its transport-block half is the static encode_tb_off, the rest is UCI multiplexing that stays the
- * reference's; sch.c keeps it and reaches this library through srslte_tcod_encode_lut as before. */
+ * srslte_ulsch_encode (below) runs on the same object. */
 int srslte_dlsch_encode(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, uint8_t* data, uint8_t* e_bits);
 int srslte_dlsch_encode2(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, uint8_t* data, uint8_t* e_bits, int codeword_idx, uint32_t nof_layers);
 
@@ -260,7 +259,7 @@ int srslte_dlsch_encode2(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, uint8_t* data
  *    nof_symb outside 9..12, L_prb = 0, ri_len > 2, a report longer than 64 bits, offsets above 15, Q' beyond the matrix's rows.
  *  - where the report's size depends on the rank decoded in the same call (a higher-layer subband report with PMI and ri_present, ri_len > 0)
  *    the call waits for its stream a second time, between the RI decision and the report.
- * Nothing falls back to a host path. srslte_ulsch_encode stays the reference's (above). */
+ * Nothing falls back to a host path. */
 #define SRSLTE_MAX_CARRIERS 5          /* phy_common.h:48 */
 #define SRSLTE_UCI_MAX_ACK_BITS 10     /* uci_cfg.h:27-28 */
 #define SRSLTE_UCI_MAX_M 9
@@ -302,6 +301,32 @@ void srslte_hip_compat_stats_ul(unsigned long long out[2]);
 /* the device object behind q->decoder.dec16_hdlr[0] (a srslte_hip_sch_t of phy_hip.h; NULL before the first served call): for
  * srslte_hip_ulsch_debug_g, which copies the last call's de-interleaved stream to the host */
 struct srslte_hip_sch* srslte_hip_compat_sch_of(srslte_sch_t* q);
+
+/* UL-SCH encoding of one PUSCH (sch.c:1068-1210): srslte_ulsch_encode is what srslte_pusch_encode calls once per PUSCH (pusch.c:367). Upstream
+ * packs and codes the CQI report on the host, enters encode_tb_off - one srslte_tcod_encode_lut round trip per code block -, runs the bit-serial
+ * channel interleaver and inserts the HARQ-ACK bits. Here all of it is ONE device call with one stream wait (srslte_hip_ulsch_encode, phy_hip.h)
+ * on the calling thread's encoder object, the one of srslte_dlsch_encode2. Written, byte for byte upstream's: q_bits (grant.tb.nof_bits / 8
+ * bytes), g_bits over its (H' - Q'_ri) Qm bits (NULL is accepted), cfg->K_segm, softbuffers.tx->buffer_b[] for rv 0 (rv 1-3 read them and
+ * nothing else; data may then be NULL), and q->ack_ri_bits[0 .. ret) as (position, type) pairs - the RI bits first, the ACK bits from
+ * Q'_ri Qm - which pusch.c:385-400 walks for the placeholder and repetition bits after scrambling. The report is packed from uci_data->cqi
+ * through srslte_hip_cqi_value_pack. Returns (Q'_ack + Q'_ri) Qm, and upstream's error codes: SRSLTE_ERROR_INVALID_INPUTS for a modulation of
+ * no bits or a NULL soft buffer with tbs > 0, SRSLTE_ERROR for a failed segmentation, a report that does not pack or a transport block with
+ * filler bits, -1 for more code blocks than softbuffer->max_cb or a reserved beta offset.
+ * Deliberate differences:
+ *  - q->temp_g_bits, q->cb_in and q->parity_bits (upstream's scratch) are not written.
+ *  - refused with SRSLTE_ERROR_INVALID_INPUTS and a message, BEFORE anything is queued or written (cfg->K_segm excepted, which is written first
+ *    as upstream): HARQ-ACK bits with uci_cfg.ack[0].N_bundle != 0 - the TDD bundling scrambling of uci.c:737-739 is not served (without ACK
+ *    bits upstream does not look at N_bundle either, and the call is served); a modulation outside QPSK..64QAM; a transport block with two
+ *    code-block sizes; data == NULL with rv == 0, rv > 3; nof_bits other than 12 L_prb nof_symb Qm, nof_symb outside 9..12; ri_len > 2, more
+ *    than 10 ACK bits, offsets above 15; tbs = 0 without a report (upstream would interleave stale scratch); Q'_ri + Q'_cqi that leave no
+ *    symbol to a transport block.
+ * Nothing falls back to a host path. */
+int srslte_ulsch_encode(srslte_sch_t* q, srslte_pusch_cfg_t* cfg, uint8_t* data, srslte_uci_value_t* uci_data, uint8_t* g_bits, uint8_t* q_bits);
+/* {srslte_ulsch_encode calls served, stream waits inside them} (srslte_hip_compat_stats and _stats_ul keep their shapes) */
+void srslte_hip_compat_stats_ul_tx(unsigned long long out[2]);
+/* the calling thread's encoder object (a srslte_hip_sch_enc_t of phy_hip.h; NULL before the first served srslte_dlsch_encode2 /
+ * srslte_ulsch_encode): for srslte_hip_ulsch_enc_debug, which copies the last call's stream g from the device */
+struct srslte_hip_sch_enc* srslte_hip_compat_sch_enc(void);
 
 /* ------------------------------------------------------------------ DL channel estimator (chest_dl.h:49-156, refsignal_dl.h:49-54, interp.h:63-112) */
 typedef struct { cf_t* diff_vec; uint32_t vector_len; uint32_t max_vector_len; } srslte_interp_linsrslte_vec_t;

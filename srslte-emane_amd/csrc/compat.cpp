@@ -19,10 +19,11 @@ namespace {
 void* tl_stream() { return g_link.stream(); }
 
 std::atomic<unsigned long long> g_stats_ul[2]; // srslte_ulsch_decode calls served, stream waits inside them (srslte_hip_compat_stats_ul)
+std::atomic<unsigned long long> g_stats_ul_tx[2]; // the same for srslte_ulsch_encode (srslte_hip_compat_stats_ul_tx)
 void stats_at_exit()
 {
-  fprintf(stderr, "[srslte_hip] stats: stream_waits=%llu dlsch_decode2=%llu tdec_single_block_calls=%llu dlsch_encode2=%llu ulsch_decode=%llu\n",
-          g_stats[0].load(), g_stats[1].load(), g_stats[2].load(), g_stats[3].load(), g_stats_ul[0].load());
+  fprintf(stderr, "[srslte_hip] stats: stream_waits=%llu dlsch_decode2=%llu tdec_single_block_calls=%llu dlsch_encode2=%llu ulsch_decode=%llu ulsch_encode=%llu\n",
+          g_stats[0].load(), g_stats[1].load(), g_stats[2].load(), g_stats[3].load(), g_stats_ul[0].load(), g_stats_ul_tx[0].load());
 }
 struct StatsInit {
   StatsInit()
@@ -90,6 +91,19 @@ struct SchEncLink {
   ~SchEncLink() { srslte_hip_sch_enc_destroy(h); }
 };
 thread_local SchEncLink g_sch_enc;
+// the thread's encoder for a transport block of tbs bits and nof_bits coded bits; null: it could not be made
+srslte_hip_sch_enc_t* sch_enc_object(uint32_t tbs, uint32_t nof_bits)
+{
+  SchEncLink& l = g_sch_enc;
+  if (!l.h || tbs > l.tbs || nof_bits > l.e) {
+    srslte_hip_sch_enc_destroy(l.h);
+    l.tbs = tbs > l.tbs ? tbs : l.tbs;
+    l.e   = nof_bits > l.e ? nof_bits : l.e;
+    l.h   = srslte_hip_sch_enc_create(l.tbs, l.e);
+    if (!l.h) l.tbs = l.e = 0;
+  }
+  return l.h;
+}
 
 int cp_nsymb(srslte_cp_t cp) { return cp == SRSLTE_CP_NORM ? 7 : 6; }
 
@@ -1078,22 +1092,126 @@ int srslte_dlsch_encode2(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, uint8_t* data
   }
   if (seg.C == 0) return SRSLTE_SUCCESS; // the loop over no code blocks
   if (tb.mod < SRSLTE_MOD_QPSK || tb.mod > SRSLTE_MOD_256QAM || tb.nof_bits == 0 || !sb->buffer_b) return SRSLTE_ERROR_INVALID_INPUTS;
-  SchEncLink& l = g_sch_enc;
-  if (!l.h || (uint32_t)tb.tbs > l.tbs || tb.nof_bits > l.e) {
-    srslte_hip_sch_enc_destroy(l.h);
-    l.tbs = (uint32_t)tb.tbs > l.tbs ? (uint32_t)tb.tbs : l.tbs;
-    l.e   = tb.nof_bits > l.e ? tb.nof_bits : l.e;
-    l.h   = srslte_hip_sch_enc_create(l.tbs, l.e);
-    if (!l.h) {
-      l.tbs = l.e = 0;
-      return SRSLTE_ERROR;
-    }
-  }
-  const int r = srslte_hip_sch_encode(l.h, data, (uint32_t)tb.tbs, (int)tb.mod, Nl, (uint32_t)tb.rv, tb.nof_bits, sb->buffer_b, e_bits);
+  srslte_hip_sch_enc_t* h = sch_enc_object((uint32_t)tb.tbs, tb.nof_bits);
+  if (!h) return SRSLTE_ERROR;
+  const int r = srslte_hip_sch_encode(h, data, (uint32_t)tb.tbs, (int)tb.mod, Nl, (uint32_t)tb.rv, tb.nof_bits, sb->buffer_b, e_bits);
   if (r == SRSLTE_SUCCESS) g_stats[3]++;
   return r;
 }
 int srslte_dlsch_encode(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, uint8_t* data, uint8_t* e_bits) { return srslte_dlsch_encode2(q, cfg, data, e_bits, 0, 1); }
+
+// ---- srslte_ulsch_encode (sch.c:1068-1210): the coded report, encode_tb_off behind it, ulsch_interleave and the ACK insertion as ONE device call
+// (srslte_hip_ulsch_encode) on the calling thread's encoder object. The host keeps what is arithmetic on the configuration: segmentation, K_segm,
+// the report's packing, and the (position, type) list q->ack_ri_bits that pusch.c:385-400 walks after scrambling
+static uint32_t ul_enc_fill_bits(srslte_uci_bit_t* bits, const uint8_t* d, uint32_t O, uint32_t Qprime, bool is_ri, uint32_t Qm, uint32_t rows, uint32_t nsymb)
+{ // srslte_uci_encode_ack_ri's output (uci.c:695-743) for Q' symbols: the coded types repeated, symbol n at row rows - 1 - n / 4 of its column set
+  static const uint32_t set_norm[2][4] = {{2, 3, 8, 9}, {1, 4, 7, 10}}, set_ext[2][4] = {{1, 2, 6, 7}, {0, 3, 5, 8}};
+  uint8_t        types[32];
+  const uint32_t period = lte_uci_ack_ri_types(d, O, Qm, types);
+  if (!period) return 0;
+  for (uint32_t n = 0; n < Qprime; n++) {
+    const uint32_t row = rows - 1 - n / 4, col = nsymb > 10 ? set_norm[is_ri][(3 * n) % 4] : set_ext[is_ri][(3 * n) % 4];
+    for (uint32_t k = 0; k < Qm; k++) {
+      bits[n * Qm + k].position = row * Qm + rows * col * Qm + k;
+      bits[n * Qm + k].type     = (srslte_uci_bit_type_t)types[(n * Qm + k) % period];
+    }
+  }
+  return Qprime * Qm;
+}
+
+int srslte_ulsch_encode(srslte_sch_t* q, srslte_pusch_cfg_t* cfg, uint8_t* data, srslte_uci_value_t* uci_data, uint8_t* g_bits, uint8_t* q_bits)
+{
+  if (!q || !cfg || !uci_data || !q_bits) return SRSLTE_ERROR_INVALID_INPUTS;
+  const srslte_ra_tb_t& tb = cfg->grant.tb;
+  const uint32_t Qm = tb.mod == SRSLTE_MOD_BPSK ? 1 : tb.mod == SRSLTE_MOD_QPSK ? 2 : tb.mod == SRSLTE_MOD_16QAM ? 4 : tb.mod == SRSLTE_MOD_64QAM ? 6 :
+                      tb.mod == SRSLTE_MOD_256QAM ? 8 : 0; // srslte_mod_bits_x_symbol
+  if (Qm == 0) return SRSLTE_ERROR_INVALID_INPUTS; // :1085-1087
+  srslte_cbsegm_t seg;
+  if (srslte_cbsegm(&seg, (uint32_t)tb.tbs)) {
+    ERROR("Error computing segmentation for TBS=%d", tb.tbs);
+    return SRSLTE_ERROR;
+  }
+  cfg->K_segm = seg.C1 * seg.K1 + seg.C2 * seg.K2; // :1096
+  // ---- refusals, before anything is queued or written
+  auto refuse = [](const char* why) {
+    ERROR("srslte_ulsch_encode: %s", why);
+    return SRSLTE_ERROR_INVALID_INPUTS;
+  };
+  srslte_cqi_cfg_t*          cq = &cfg->uci_cfg.cqi;
+  srslte_hip_ulsch_enc_cfg_t c;
+  memset(&c, 0, sizeof(c));
+  if (cq->data_enable) { // :1102-1108 through srslte_hip_cqi_value_pack, upstream's quirks included
+    const srslte_hip_cqi_cfg_t   hc = {(int)cq->type, cq->data_enable, cq->pmi_present, cq->four_antenna_ports, cq->rank_is_not_one, cq->subband_label_2_bits, cq->L, cq->N};
+    const srslte_cqi_value_t&    v  = uci_data->cqi;
+    srslte_hip_cqi_value_t       hv;
+    memset(&hv, 0, sizeof(hv));
+    switch (cq->type) {
+      case SRSLTE_CQI_TYPE_WIDEBAND: hv.wideband_cqi = v.wideband.wideband_cqi; hv.spatial_diff_cqi = v.wideband.spatial_diff_cqi; hv.pmi = v.wideband.pmi; break;
+      case SRSLTE_CQI_TYPE_SUBBAND: hv.subband_cqi = v.subband.subband_cqi; hv.subband_label = v.subband.subband_label; break;
+      case SRSLTE_CQI_TYPE_SUBBAND_UE: hv.wideband_cqi = v.subband_ue.wideband_cqi; hv.subband_diff_cqi = v.subband_ue.subband_diff_cqi; break;
+      case SRSLTE_CQI_TYPE_SUBBAND_HL:
+        hv.wideband_cqi = v.subband_hl.wideband_cqi_cw0; hv.subband_diff_cqi = v.subband_hl.subband_diff_cqi_cw0;
+        hv.wideband_cqi_cw1 = v.subband_hl.wideband_cqi_cw1; hv.subband_diff_cqi_cw1 = v.subband_hl.subband_diff_cqi_cw1; hv.pmi = v.subband_hl.pmi;
+        break;
+    }
+    const int len = srslte_hip_cqi_value_pack(&hc, &hv, c.cqi_bits);
+    if (len < 0) {
+      ERROR("Error encoding CQI bits"); // :1104-1107
+      return SRSLTE_ERROR;
+    }
+    c.cqi_len = (uint32_t)len;
+  }
+  uint32_t total_ack = 0; // srslte_uci_cfg_total_ack
+  for (int i = 0; i < SRSLTE_MAX_CARRIERS; i++) total_ack += cfg->uci_cfg.ack[i].nof_acks;
+  if (total_ack && cfg->uci_cfg.ack[0].N_bundle) return refuse("the TDD bundling scrambling of the HARQ-ACK (N_bundle != 0, uci.c:737-739) is not served");
+  if (tb.mod < SRSLTE_MOD_QPSK || tb.mod > SRSLTE_MOD_64QAM) return refuse("modulation outside QPSK..64QAM");
+  if (total_ack > SRSLTE_UCI_MAX_ACK_BITS) return refuse("more than 10 HARQ-ACK bits");
+  srslte_softbuffer_tx_t* sb = cfg->softbuffers.tx;
+  if (seg.tbs) {
+    if (!sb) { // encode_tb_off :192,:285-287
+      ERROR("Invalid parameters: e_bits=%d, cb_segm=%d, softbuffer=%d", g_bits != 0, 1, 0);
+      return SRSLTE_ERROR_INVALID_INPUTS;
+    }
+    if (seg.F) {
+      hip_log("Error filler bits are not supported. Use standard TBS\n"); // :194-197
+      return SRSLTE_ERROR;
+    }
+    if (seg.C > sb->max_cb) {
+      hip_log("Error number of CB to encode (%d) exceeds soft buffer size (%d CBs)\n", seg.C, sb->max_cb); // :199-202
+      return -1;
+    }
+    if (!sb->buffer_b) return refuse("a soft buffer without circular buffers");
+  }
+  c.mod = (int)tb.mod; c.tbs = seg.tbs; c.rv = (uint32_t)tb.rv; c.nof_bits = tb.nof_bits; c.L_prb = cfg->grant.L_prb; c.nof_symb = cfg->grant.nof_symb;
+  c.ack_len = total_ack; c.ri_len = cq->ri_len;
+  c.I_offset_ack = cfg->uci_offset.I_offset_ack; c.I_offset_ri = cfg->uci_offset.I_offset_ri; c.I_offset_cqi = cfg->uci_offset.I_offset_cqi;
+  memcpy(c.ack, uci_data->ack.ack_value, sizeof(c.ack));
+  c.ri = uci_data->ri;
+  // what the device call refuses (phy_hip.h), asked before an object is made or grown for the call
+  uint8_t** buffer_b = seg.tbs ? sb->buffer_b : nullptr;
+  if (const int r = ulsch_enc_check(&c, data, buffer_b)) return r == SRSLTE_ERROR_INVALID_INPUTS ? refuse("not served by the device call") : r;
+  srslte_hip_sch_enc_t* h = sch_enc_object(seg.tbs ? seg.tbs : 40, tb.nof_bits);
+  if (!h) return SRSLTE_ERROR;
+  srslte_hip_ulsch_enc_res_t res;
+  if (const int r = srslte_hip_ulsch_encode(h, data, &c, buffer_b, g_bits, q_bits, &res)) return r;
+  g_stats_ul_tx[0]++;
+  g_stats_ul_tx[1] += res.stream_waits;
+  // ---- what pusch.c reads after the call: (position, type) of the RI bits, then of the ACK bits from Q'_ri Qm (:1124,:1185)
+  const uint32_t rows = tb.nof_bits / Qm / cfg->grant.nof_symb, n_ri = res.Q_prime_ri * Qm, n_ack = res.Q_prime_ack * Qm;
+  if (n_ri + n_ack > sizeof(q->ack_ri_bits) / sizeof(q->ack_ri_bits[0])) {
+    ERROR("srslte_ulsch_encode: %u RI and ACK bits do not fit ack_ri_bits", n_ri + n_ack);
+    return SRSLTE_ERROR;
+  }
+  const uint8_t ri[2] = {uci_data->ri, 0}; // :1115
+  ul_enc_fill_bits(q->ack_ri_bits, ri, cq->ri_len, res.Q_prime_ri, true, Qm, rows, cfg->grant.nof_symb);
+  ul_enc_fill_bits(&q->ack_ri_bits[n_ri], uci_data->ack.ack_value, total_ack, res.Q_prime_ack, false, Qm, rows, cfg->grant.nof_symb);
+  return (int)(n_ri + n_ack);
+}
+srslte_hip_sch_enc_t* srslte_hip_compat_sch_enc(void) { return g_sch_enc.h; }
+void srslte_hip_compat_stats_ul_tx(unsigned long long out[2])
+{
+  for (int i = 0; i < 2; i++) out[i] = g_stats_ul_tx[i].load();
+}
 
 static int tdec_all(srslte_tdec_t* h, const void* input, bool api8, uint8_t* output, uint32_t nof_iterations, uint32_t long_cb)
 { // turbodecoder.c:547-562,:573-588

@@ -213,3 +213,30 @@ void lte_tbcrc_win_table(const std::vector<uint32_t>& rem, uint32_t C, uint32_t 
     }
   }
 }
+
+// The coded bit types of a HARQ-ACK or rank indication of O bits on the PUSCH (encode_ri_ack / encode_ack_long, uci.c:573-623): one period of the
+// sequence srslte_uci_encode_ack_ri repeats over Q' Qm bits - 0 / 1 a value, 2 a repetition of the bit before, 3 a placeholder. 1 bit: Qm
+// types; 2 bits: 3 Qm (o0 o1 | o2 o0 | o1 o2 with o2 = o0 ^ o1, placeholders behind each pair); 3-10 bits: the (32, O) block code of Table
+// 5.2.2.6.4-1, 32 types. Returns the period, 0 for O = 0 or above 10
+uint32_t lte_uci_ack_ri_types(const uint8_t* d, uint32_t O, uint32_t Qm, uint8_t types[32])
+{
+  static const uint16_t M32[32] = {0x403, 0x607, 0x749, 0x50D, 0x48F, 0x5D3, 0x755, 0x599, 0x69B, 0x65D, 0x6E5, 0x567, 0x7A9, 0x6AB, 0x4B1, 0x6F3,
+                                   0x277, 0x139, 0x0FB, 0x061, 0x445, 0x60B, 0x591, 0x717, 0x3DF, 0x4E3, 0x32D, 0x3AF, 0x175, 0x1FD, 0x7FF, 0x001};
+  if (O == 0 || O > 10 || Qm < 2 || Qm > 6) return 0;
+  if (O >= 3) {
+    for (uint32_t i = 0; i < 32; i++) {
+      uint32_t b = 0;
+      for (uint32_t n = 0; n < O; n++) b ^= d[n] & (M32[i] >> n) & 1u;
+      types[i] = (uint8_t)b;
+    }
+    return 32;
+  }
+  const uint8_t o[3] = {(uint8_t)(d[0] ? 1 : 0), (uint8_t)(O == 2 && d[1] ? 1 : 0), (uint8_t)(O == 2 && (d[0] ^ d[1]) ? 1 : 0)};
+  const uint32_t n = O == 1 ? Qm : 3 * Qm;
+  for (uint32_t i = 0; i < n; i++) {
+    const uint32_t b = i % Qm;
+    if (O == 1) types[i] = b == 0 ? o[0] : (b == 1 ? 2 : 3);
+    else types[i] = b >= 2 ? 3 : o[(2 * (i / Qm) + b) % 3];
+  }
+  return n;
+}

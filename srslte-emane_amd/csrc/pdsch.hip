@@ -40,5 +40,6 @@
 #include "ulsch_host.inc" // srslte_ulsch_decode's device call: sch_host.inc's object behind pusch_rx.inc's UCI position arithmetic and CQI decoder
 #include "pusch_tx.inc"
 #include "sch_enc_host.inc" // the transmit counterpart of sch_host.inc, on the encoder half pusch_tx.inc defines
+#include "ulsch_enc_host.inc" // srslte_ulsch_encode's device call: sch_enc_host.inc's object and chain, pusch_rx.inc's UCI position arithmetic
 #include "pdsch_tx.inc"
 #include "pusch_tx_grants.inc"

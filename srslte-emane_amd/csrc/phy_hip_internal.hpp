@@ -34,6 +34,11 @@ uint32_t lte_rm_tx_start(uint32_t K, uint32_t rv); // bit of the NULL-free circu
 void lte_scr_table(const std::function<uint32_t(uint32_t)>& c_init, uint32_t nbits, uint32_t words, std::vector<uint32_t>& scr);
 void lte_tbcrc_rem_table(uint32_t tbs, std::vector<uint32_t>& rem);
 void lte_tbcrc_win_table(const std::vector<uint32_t>& rem, uint32_t C, uint32_t K, uint32_t W, std::vector<uint32_t>& t);
+// fec_tables.cpp: one period of the coded bit types of a HARQ-ACK / rank indication of O bits on the PUSCH (encode_ri_ack / encode_ack_long,
+// uci.c:573-623): 0 / 1 a value, 2 a repetition, 3 a placeholder; returns the period (Qm, 3 Qm or 32; 0 for O = 0 or above 10)
+uint32_t lte_uci_ack_ri_types(const uint8_t* d, uint32_t O, uint32_t Qm, uint8_t types[32]);
+// pdsch.hip: the checks of srslte_hip_ulsch_encode on the configuration and the caller's buffers alone, with its codes (no object, nothing queued)
+int ulsch_enc_check(const srslte_hip_ulsch_enc_cfg_t* c, const uint8_t* data, uint8_t** buffer_b);
 
 // chest.hip: srslte_chest_ul_estimate_pusch for a list of PUSCHs of one (L_prb, n_dmrs): item i = {subframe of the batch, PRB offset of slot 0 / 1,
 // row of d_res}; d_items on the device

@@ -107,6 +107,13 @@ struct srslte_hip_sch_enc {
   DevBuf<uint32_t> d_tbcrc, d_w;
   DevBuf<uint8_t>  d_cb, d_parity, d_sys_tail;
   std::map<uint32_t, KTab> tab;
+  // srslte_hip_ulsch_encode (ulsch_enc_host.inc), made by its first call. Pinned: the report's bits [64] | the rate-matching order of its coded
+  // bits [max_e] uint16 | g words | q words. Device: the coded report, one bit per byte, and the copy of g the channel interleaver reads
+  PinBuf           h_ul;
+  size_t           o_ul_g = 0, o_ul_q = 0;
+  DevBuf<uint8_t>  d_qcqi;
+  DevBuf<uint32_t> d_g;
+  uint32_t         g_words = 0; // of the last call
   ~srslte_hip_sch_enc()
   {
     if (st) (void)hipStreamSynchronize(st); // a call that returned early may have left launches queued: they end before the buffers go
@@ -148,6 +155,86 @@ extern "C" srslte_hip_sch_enc_t* srslte_hip_sch_enc_create(uint32_t max_tbs, uin
   return q.release();
 }
 
+// The steps srslte_hip_sch_encode and srslte_hip_ulsch_encode (ulsch_enc_host.inc) share.
+// 1. The checks on a transport block of tbs > 0 bits and its buffers, with upstream's codes; seg: its segmentation.
+static int sch_enc_check(const uint8_t* data, uint32_t tbs, uint32_t rv, uint8_t** buffer_b, srslte_hip_cbsegm_t* seg)
+{
+  if (!buffer_b || (!data && rv == 0)) return SRSLTE_ERROR_INVALID_INPUTS; // upstream would rate-match what its scratch buffers held
+  if (srslte_hip_cbsegm(seg, tbs)) return SRSLTE_ERROR;
+  if (seg->F) {
+    hip_log("Error filler bits are not supported. Use standard TBS\n"); // sch.c:194-197
+    return SRSLTE_ERROR;
+  }
+  if (seg->C2) {
+    hip_log("[srslte_hip] sch_enc: TBS %u needs two code-block sizes; not supported on device yet\n", tbs);
+    return SRSLTE_ERROR_INVALID_INPUTS;
+  }
+  for (uint32_t c = 0; c < seg->C; c++) {
+    if (!buffer_b[c]) return SRSLTE_ERROR_INVALID_INPUTS;
+  }
+  return SRSLTE_SUCCESS;
+}
+
+// 2. The geometry of C blocks of K bits whose selection of the rv fills QN Gp bits (QN = Qm Nl)
+static SchEncGeom sch_enc_geom(const srslte_hip_sch_enc* q, const srslte_hip_sch_enc::KTab* kt, uint32_t C, uint32_t K, uint32_t QN, uint32_t Gp, uint32_t rv)
+{
+  const uint32_t gamma = Gp % C;
+  SchEncGeom     g;
+  g.C = (int)C; g.K = (int)K; g.L = (int)(3 * K + 12);
+  g.n0 = (int)((g.L - kt->start[0]) % g.L);
+  g.r = (int)kt->start[rv];
+  g.w_words = (int)q->W_WORDS;
+  g.C_lo = (int)(C - gamma); g.n_lo = (int)(QN * (Gp / C)); g.n_hi = g.n_lo + (int)QN; // sch.c:232-236
+  g.total = (int)(QN * Gp);
+  return g;
+}
+
+// 3. Queues what leaves the circular buffers where the selection reads them (*w_src): for rv 0 the chain from the transport block to
+// sch_enc_w_kernel, which also fills the pinned copy; for a retransmission the caller's buffers are staged in that pinned copy
+static int sch_enc_queue_w(srslte_hip_sch_enc* q, const srslte_hip_sch_enc::KTab* kt, const uint8_t* data, uint32_t tbs, uint32_t rv, uint8_t** buffer_b,
+                           const SchEncGeom& g, const uint8_t** w_src)
+{
+  const size_t   w_bytes = ((size_t)g.L + 7) / 8, w_stride = (size_t)q->W_WORDS * 4;
+  const uint32_t C = (uint32_t)g.C, K = (uint32_t)g.K;
+  uint8_t *      h_tb = q->h_pin, *h_w = q->h_pin + q->o_w;
+  hipStream_t    st   = q->st;
+  *w_src = h_w;
+  if (rv != 0) {
+    for (uint32_t c = 0; c < C; c++) memcpy(h_w + c * w_stride, buffer_b[c], w_bytes);
+    return SRSLTE_SUCCESS;
+  }
+  memcpy(h_tb, data, tbs / 8);
+  PuschTxGeom cg = {};
+  cg.C = (int)C; cg.K = (int)K; cg.tbs = (int)tbs; cg.rlenB = (int)((C <= 1 ? K : K - 24) / 8); cg.cb_stride = (int)q->CB_STRIDE;
+  cg.par_stride = (int)q->PAR_STRIDE; cg.tb_stride = 0;
+  hipLaunchKernelGGL(pusch_tx_tbcrc_kernel, dim3(1), dim3(256), 0, st, (const uint8_t*)h_tb, q->d_tbcrc.get(), cg);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(pusch_tx_seg_kernel, dim3(C, 1), dim3(256), 0, st, (const uint8_t*)h_tb, (const uint32_t*)q->d_tbcrc, q->d_cb.get(), cg);
+  LAUNCH_CHECK();
+  if (int r = srslte_hip_tcod_encode_bytes_batch(q->d_cb, q->CB_STRIDE, q->d_parity, q->PAR_STRIDE, q->d_sys_tail, K, C, st)) return r;
+  hipLaunchKernelGGL(sch_enc_w_kernel, dim3(C), dim3(256), 0, st, (const uint8_t*)q->d_cb, (int)q->CB_STRIDE, (const uint8_t*)q->d_parity, (int)q->PAR_STRIDE,
+                     (const uint8_t*)q->d_sys_tail, (const uint32_t*)kt->d_rm, q->d_w.get(), reinterpret_cast<uint32_t*>(h_w), g);
+  LAUNCH_CHECK();
+  *w_src = reinterpret_cast<const uint8_t*>(q->d_w.get());
+  return SRSLTE_SUCCESS;
+}
+
+// 4. After the stream wait: nbits packed bits from src; the bits of the last byte past them keep the caller's values ...
+static void sch_enc_copy_bits(uint8_t* dst, const uint8_t* src, size_t nbits)
+{
+  memcpy(dst, src, nbits / 8);
+  if (nbits % 8) {
+    const uint8_t m = (uint8_t)(0xff00u >> (nbits % 8));
+    dst[nbits / 8] = (uint8_t)((src[nbits / 8] & m) | (dst[nbits / 8] & ~m));
+  }
+}
+// ... and for rv 0 the circular buffers into the caller's soft buffer
+static void sch_enc_copy_w(const srslte_hip_sch_enc* q, const SchEncGeom& g, uint8_t** buffer_b)
+{
+  const uint8_t* h_w = q->h_pin + q->o_w;
+  for (int c = 0; c < g.C; c++) memcpy(buffer_b[c], h_w + (size_t)c * q->W_WORDS * 4, ((size_t)g.L + 7) / 8);
+}
+
 // data: tbs / 8 bytes of the transport block, or null for a retransmission. mod: 1 QPSK .. 4 256QAM; Nl as srslte_dlsch_encode2 derives it (2
 // where nof_layers != nof_tb). buffer_b[c]: the srslte_softbuffer_tx_t's circular buffers of the C code blocks, ceil((3K + 12) / 8) bytes each:
 // written for rv 0, read for rv 1-3 (whose result depends on them alone: data is not looked at, as upstream encodes it and then selects from
@@ -159,64 +246,21 @@ extern "C" int srslte_hip_sch_encode(srslte_hip_sch_enc_t* q, const uint8_t* dat
   if (!q || !e_bits || rv > 3 || mod < 1 || mod > 4 || Nl < 1 || Nl > 2 || (tbs % 8) || tbs > q->max_tbs || nof_e_bits == 0 || nof_e_bits > q->max_e)
     return SRSLTE_ERROR_INVALID_INPUTS;
   if (tbs == 0) return SRSLTE_SUCCESS; // upstream's loop over C = 0 code blocks
-  if (!buffer_b || (!data && rv == 0)) return SRSLTE_ERROR_INVALID_INPUTS; // upstream would rate-match what its scratch buffers held
   srslte_hip_cbsegm_t seg;
-  if (srslte_hip_cbsegm(&seg, tbs)) return SRSLTE_ERROR;
-  if (seg.F) {
-    hip_log("Error filler bits are not supported. Use standard TBS\n"); // sch.c:194-197
-    return SRSLTE_ERROR;
-  }
-  if (seg.C2) {
-    hip_log("[srslte_hip] sch_enc: TBS %u needs two code-block sizes; not supported on device yet\n", tbs);
-    return SRSLTE_ERROR_INVALID_INPUTS;
-  }
-  const uint32_t C = seg.C, K = seg.K1, QN = 2 * (uint32_t)mod * Nl, Gp = nof_e_bits / QN, gamma = Gp % C;
-  for (uint32_t c = 0; c < C; c++) {
-    if (!buffer_b[c]) return SRSLTE_ERROR_INVALID_INPUTS;
-  }
-  const srslte_hip_sch_enc::KTab* kt = q->table(K);
+  if (int r = sch_enc_check(data, tbs, rv, buffer_b, &seg)) return r;
+  const srslte_hip_sch_enc::KTab* kt = q->table(seg.K1);
   if (!kt) return SRSLTE_ERROR;
-  SchEncGeom g;
-  g.C = (int)C; g.K = (int)K; g.L = (int)(3 * K + 12);
-  g.n0 = (int)((g.L - kt->start[0]) % g.L);
-  g.r = (int)kt->start[rv];
-  g.w_words = (int)q->W_WORDS;
-  g.C_lo = (int)(C - gamma); g.n_lo = (int)(QN * (Gp / C)); g.n_hi = g.n_lo + (int)QN; // sch.c:232-236
-  g.total = (int)(QN * Gp);
-  const size_t   w_bytes = ((size_t)g.L + 7) / 8, w_stride = (size_t)q->W_WORDS * 4;
-  uint8_t *      h_tb = q->h_pin, *h_w = q->h_pin + q->o_w;
-  uint32_t*      h_e  = reinterpret_cast<uint32_t*>(q->h_pin + q->o_e);
-  hipStream_t    st   = q->st;
-  const uint8_t* w_src = h_w;
-  if (rv == 0) {
-    memcpy(h_tb, data, tbs / 8);
-    PuschTxGeom cg = {};
-    cg.C = (int)C; cg.K = (int)K; cg.tbs = (int)tbs; cg.rlenB = (int)((C <= 1 ? K : K - 24) / 8); cg.cb_stride = (int)q->CB_STRIDE;
-    cg.par_stride = (int)q->PAR_STRIDE; cg.tb_stride = 0;
-    hipLaunchKernelGGL(pusch_tx_tbcrc_kernel, dim3(1), dim3(256), 0, st, (const uint8_t*)h_tb, q->d_tbcrc.get(), cg);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(pusch_tx_seg_kernel, dim3(C, 1), dim3(256), 0, st, (const uint8_t*)h_tb, (const uint32_t*)q->d_tbcrc, q->d_cb.get(), cg);
-    LAUNCH_CHECK();
-    if (int r = srslte_hip_tcod_encode_bytes_batch(q->d_cb, q->CB_STRIDE, q->d_parity, q->PAR_STRIDE, q->d_sys_tail, K, C, st)) return r;
-    hipLaunchKernelGGL(sch_enc_w_kernel, dim3(C), dim3(256), 0, st, (const uint8_t*)q->d_cb, (int)q->CB_STRIDE, (const uint8_t*)q->d_parity, (int)q->PAR_STRIDE,
-                       (const uint8_t*)q->d_sys_tail, (const uint32_t*)kt->d_rm, q->d_w.get(), reinterpret_cast<uint32_t*>(h_w), g);
-    LAUNCH_CHECK();
-    w_src = reinterpret_cast<const uint8_t*>(q->d_w.get());
-  } else {
-    for (uint32_t c = 0; c < C; c++) memcpy(h_w + c * w_stride, buffer_b[c], w_bytes);
-  }
+  const uint32_t   QN = 2 * (uint32_t)mod * Nl;
+  const SchEncGeom g  = sch_enc_geom(q, kt, seg.C, seg.K1, QN, nof_e_bits / QN, rv);
+  uint32_t*        h_e = reinterpret_cast<uint32_t*>(q->h_pin + q->o_e);
+  const uint8_t*   w_src;
+  if (int r = sch_enc_queue_w(q, kt, data, tbs, rv, buffer_b, g, &w_src)) return r;
   if (g.total) {
-    hipLaunchKernelGGL(sch_enc_select_kernel, dim3(ceil_div(ceil_div(g.total, 32), 256)), dim3(256), 0, st, w_src, h_e, g);
+    hipLaunchKernelGGL(sch_enc_select_kernel, dim3(ceil_div(ceil_div(g.total, 32), 256)), dim3(256), 0, q->st, w_src, h_e, g);
     LAUNCH_CHECK();
   }
-  HIP_TRY(hipStreamSynchronize(st));
-  memcpy(e_bits, h_e, (size_t)g.total / 8);
-  if (g.total % 8) {
-    const uint8_t m = (uint8_t)(0xff00u >> (g.total % 8));
-    e_bits[g.total / 8] = (uint8_t)((reinterpret_cast<const uint8_t*>(h_e)[g.total / 8] & m) | (e_bits[g.total / 8] & ~m));
-  }
-  if (rv == 0) {
-    for (uint32_t c = 0; c < C; c++) memcpy(buffer_b[c], h_w + c * w_stride, w_bytes);
-  }
+  HIP_TRY(hipStreamSynchronize(q->st));
+  sch_enc_copy_bits(e_bits, reinterpret_cast<const uint8_t*>(h_e), (size_t)g.total);
+  if (rv == 0) sch_enc_copy_w(q, g, buffer_b);
   return SRSLTE_SUCCESS;
 }
