@@ -663,6 +663,34 @@ int srslte_hip_ulsch_encode(srslte_hip_sch_enc_t* q, const uint8_t* data, const 
  * (H' - Q'_ri) Qm bits / 32; byte order as g_bits) */
 int srslte_hip_ulsch_enc_debug(srslte_hip_sch_enc_t* q, uint32_t* out, uint32_t n_words);
 
+/* ---- PUSCH UCI plan: how the rows x nof_symb symbols of a PUSCH are divided between HARQ-ACK, rank indication, CQI report and UL-SCH
+ * (36.212 5.2.2.6, 5.2.4.1; Q_prime_ri_ack and Q_prime_cqi in upstream's float arithmetic, uci.c:264-281,:547-571) - what the PUSCH pipelines
+ * and the two UL-SCH calls above size themselves with, here for a check without a device. Returns one of the reasons below (the outputs
+ * computed up to that point stand, the rest are 0), or SRSLTE_ERROR_INVALID_INPUTS for a null pointer, a size of 0, or K_segm and C of which
+ * only one is 0. Limits beyond these - on the number of ACK / RI bits, on the report's length, on how many symbols the UL-SCH needs - are
+ * each caller's own. ---- */
+#define SRSLTE_HIP_PUSCH_UCI_OK 0
+#define SRSLTE_HIP_PUSCH_UCI_EMPTY 1   /* neither UL-SCH data nor a CQI report */
+#define SRSLTE_HIP_PUSCH_UCI_BETA 2    /* the offset index of a field in use is reserved or above 15 (the report's is in use without data, too) */
+#define SRSLTE_HIP_PUSCH_UCI_ROWS 3    /* Q'_ack or Q'_ri beyond the 4 rows symbols its columns hold */
+#define SRSLTE_HIP_PUSCH_UCI_NO_ROOM 4 /* Q'_ri + Q'_cqi beyond the matrix, or no symbol left for the UL-SCH data */
+typedef struct {
+  uint32_t L_prb, nof_symb, Qm;
+  uint32_t rows;                                  /* of the channel interleaver's matrix: 12 L_prb where nof_bits = 12 L_prb nof_symb Qm */
+  uint32_t K_segm, C;                             /* sum K_r and the number of code blocks; both 0 without UL-SCH data */
+  uint32_t ack_len, ri_len, cqi_len;
+  uint32_t I_offset_ack, I_offset_ri, I_offset_cqi;
+  uint32_t sym;                                   /* the ACK / RI symbol whose position is asked for */
+} srslte_hip_pusch_uci_cfg_t;
+typedef struct {
+  uint32_t Qp_ack, Qp_ri, Qp_cqi;
+  uint32_t Q_cqi;                                 /* Q'_cqi Qm: the coded report's bits in front of the UL-SCH's */
+  uint32_t G_prime;                               /* rows nof_symb - Q'_ri - Q'_cqi symbols for the UL-SCH */
+  uint32_t syms_lo, C_lo;                         /* the first C_lo code blocks carry syms_lo = floor(G' / C) symbols, the others one more */
+  uint32_t ack_pos[2], ri_pos[2];                 /* (row, column) of ACK / RI symbol cfg->sym (uci.c:497-545) */
+} srslte_hip_pusch_uci_res_t;
+int srslte_hip_pusch_uci_plan(const srslte_hip_pusch_uci_cfg_t* cfg, srslte_hip_pusch_uci_res_t* res);
+
 /* ------------------------------------------------------------------ DL control region receive (UE side): the part of srslte_ue_dl_find_dl_dci
  * that precedes the DCI unpacking, for a batch of subframes (ue/ue_dl.c:334-367 estimate_pdcch_pcfich, :422-478 dci_blind_search, :534-646
  * find_dl_dci_type_siprarnti / _crnti): PCFICH -> CFI -> PDCCH LLRs -> blind search -> one DL DCI message per subframe, all on the device and

@@ -976,9 +976,13 @@ static void ul_cqi_unpack(const srslte_cqi_cfg_t* c, const uint8_t* b, srslte_cq
       break;
   }
 }
+static srslte_hip_cqi_cfg_t ul_cqi_cfg(const srslte_cqi_cfg_t* c, bool rank_is_not_one)
+{
+  return {(int)c->type, c->data_enable, c->pmi_present, c->four_antenna_ports, rank_is_not_one, c->subband_label_2_bits, c->L, c->N};
+}
 static int ul_cqi_size(const srslte_cqi_cfg_t* c, bool rank_is_not_one)
 { // srslte_cqi_size (cqi.c:321-384)
-  srslte_hip_cqi_cfg_t h = {(int)c->type, c->data_enable, c->pmi_present, c->four_antenna_ports, rank_is_not_one, c->subband_label_2_bits, c->L, c->N};
+  const srslte_hip_cqi_cfg_t h = ul_cqi_cfg(c, rank_is_not_one);
   return srslte_hip_cqi_size(&h);
 }
 
@@ -1065,6 +1069,19 @@ void srslte_hip_compat_stats_ul(unsigned long long out[2])
   for (int i = 0; i < 2; i++) out[i] = g_stats_ul[i].load();
 }
 
+// encode_tb_off's refusals (sch.c:192-202,:285-287) with upstream's messages and codes, for the DL-SCH and the UL-SCH alike: a missing argument
+// (args_ok: the ones beside the soft buffer), filler bits, more code blocks than the soft buffer holds
+static int encode_tb_off_refusal(bool args_ok, const void* e_bits, const srslte_softbuffer_tx_t* sb, const srslte_cbsegm_t& seg)
+{
+  if (!args_ok || !sb) {
+    ERROR("Invalid parameters: e_bits=%d, cb_segm=%d, softbuffer=%d", e_bits != 0, 1, sb != 0);
+    return SRSLTE_ERROR_INVALID_INPUTS;
+  }
+  if (seg.F) hip_log("Error filler bits are not supported. Use standard TBS\n"); // :194-197
+  else if (seg.C > sb->max_cb) hip_log("Error number of CB to encode (%d) exceeds soft buffer size (%d CBs)\n", seg.C, sb->max_cb); // :199-202
+  return seg.F || seg.C > sb->max_cb ? SRSLTE_ERROR : SRSLTE_SUCCESS;
+}
+
 // ---- srslte_dlsch_encode2 (sch.c:549-575) = encode_tb_off with w_offset 0 (sch.c:183-289) with all code blocks in one device call
 // (srslte_hip_sch_encode): upstream enters srslte_tcod_encode_lut once per block. The srslte_softbuffer_tx_t stays the HARQ state on the host
 int srslte_dlsch_encode2(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, uint8_t* data, uint8_t* e_bits, int tb_idx, uint32_t nof_layers)
@@ -1078,18 +1095,7 @@ int srslte_dlsch_encode2(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, uint8_t* data
     return SRSLTE_ERROR;
   }
   srslte_softbuffer_tx_t* sb = cfg->softbuffers.tx[tb_idx];
-  if (!q || !e_bits || !sb) { // :192,:285-287
-    ERROR("Invalid parameters: e_bits=%d, cb_segm=%d, softbuffer=%d", e_bits != 0, 1, sb != 0);
-    return SRSLTE_ERROR_INVALID_INPUTS;
-  }
-  if (seg.F) {
-    hip_log("Error filler bits are not supported. Use standard TBS\n"); // :194-197
-    return SRSLTE_ERROR;
-  }
-  if (seg.C > sb->max_cb) {
-    hip_log("Error number of CB to encode (%d) exceeds soft buffer size (%d CBs)\n", seg.C, sb->max_cb); // :199-202
-    return -1;
-  }
+  if (const int r = encode_tb_off_refusal(q && e_bits, e_bits, sb, seg)) return r;
   if (seg.C == 0) return SRSLTE_SUCCESS; // the loop over no code blocks
   if (tb.mod < SRSLTE_MOD_QPSK || tb.mod > SRSLTE_MOD_256QAM || tb.nof_bits == 0 || !sb->buffer_b) return SRSLTE_ERROR_INVALID_INPUTS;
   srslte_hip_sch_enc_t* h = sch_enc_object((uint32_t)tb.tbs, tb.nof_bits);
@@ -1105,12 +1111,12 @@ int srslte_dlsch_encode(srslte_sch_t* q, srslte_pdsch_cfg_t* cfg, uint8_t* data,
 // the report's packing, and the (position, type) list q->ack_ri_bits that pusch.c:385-400 walks after scrambling
 static uint32_t ul_enc_fill_bits(srslte_uci_bit_t* bits, const uint8_t* d, uint32_t O, uint32_t Qprime, bool is_ri, uint32_t Qm, uint32_t rows, uint32_t nsymb)
 { // srslte_uci_encode_ack_ri's output (uci.c:695-743) for Q' symbols: the coded types repeated, symbol n at row rows - 1 - n / 4 of its column set
-  static const uint32_t set_norm[2][4] = {{2, 3, 8, 9}, {1, 4, 7, 10}}, set_ext[2][4] = {{1, 2, 6, 7}, {0, 3, 5, 8}};
   uint8_t        types[32];
   const uint32_t period = lte_uci_ack_ri_types(d, O, Qm, types);
   if (!period) return 0;
   for (uint32_t n = 0; n < Qprime; n++) {
-    const uint32_t row = rows - 1 - n / 4, col = nsymb > 10 ? set_norm[is_ri][(3 * n) % 4] : set_ext[is_ri][(3 * n) % 4];
+    uint32_t row, col;
+    pusch_uci_symbol_pos(is_ri, n, rows, nsymb, &row, &col);
     for (uint32_t k = 0; k < Qm; k++) {
       bits[n * Qm + k].position = row * Qm + rows * col * Qm + k;
       bits[n * Qm + k].type     = (srslte_uci_bit_type_t)types[(n * Qm + k) % period];
@@ -1141,7 +1147,7 @@ int srslte_ulsch_encode(srslte_sch_t* q, srslte_pusch_cfg_t* cfg, uint8_t* data,
   srslte_hip_ulsch_enc_cfg_t c;
   memset(&c, 0, sizeof(c));
   if (cq->data_enable) { // :1102-1108 through srslte_hip_cqi_value_pack, upstream's quirks included
-    const srslte_hip_cqi_cfg_t   hc = {(int)cq->type, cq->data_enable, cq->pmi_present, cq->four_antenna_ports, cq->rank_is_not_one, cq->subband_label_2_bits, cq->L, cq->N};
+    const srslte_hip_cqi_cfg_t   hc = ul_cqi_cfg(cq, cq->rank_is_not_one);
     const srslte_cqi_value_t&    v  = uci_data->cqi;
     srslte_hip_cqi_value_t       hv;
     memset(&hv, 0, sizeof(hv));
@@ -1168,18 +1174,7 @@ int srslte_ulsch_encode(srslte_sch_t* q, srslte_pusch_cfg_t* cfg, uint8_t* data,
   if (total_ack > SRSLTE_UCI_MAX_ACK_BITS) return refuse("more than 10 HARQ-ACK bits");
   srslte_softbuffer_tx_t* sb = cfg->softbuffers.tx;
   if (seg.tbs) {
-    if (!sb) { // encode_tb_off :192,:285-287
-      ERROR("Invalid parameters: e_bits=%d, cb_segm=%d, softbuffer=%d", g_bits != 0, 1, 0);
-      return SRSLTE_ERROR_INVALID_INPUTS;
-    }
-    if (seg.F) {
-      hip_log("Error filler bits are not supported. Use standard TBS\n"); // :194-197
-      return SRSLTE_ERROR;
-    }
-    if (seg.C > sb->max_cb) {
-      hip_log("Error number of CB to encode (%d) exceeds soft buffer size (%d CBs)\n", seg.C, sb->max_cb); // :199-202
-      return -1;
-    }
+    if (const int r = encode_tb_off_refusal(true, g_bits, sb, seg)) return r;
     if (!sb->buffer_b) return refuse("a soft buffer without circular buffers");
   }
   c.mod = (int)tb.mod; c.tbs = seg.tbs; c.rv = (uint32_t)tb.rv; c.nof_bits = tb.nof_bits; c.L_prb = cfg->grant.L_prb; c.nof_symb = cfg->grant.nof_symb;

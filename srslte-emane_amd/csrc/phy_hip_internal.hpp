@@ -39,6 +39,10 @@ void lte_tbcrc_win_table(const std::vector<uint32_t>& rem, uint32_t C, uint32_t 
 uint32_t lte_uci_ack_ri_types(const uint8_t* d, uint32_t O, uint32_t Qm, uint8_t types[32]);
 // pdsch.hip: the checks of srslte_hip_ulsch_encode on the configuration and the caller's buffers alone, with its codes (no object, nothing queued)
 int ulsch_enc_check(const srslte_hip_ulsch_enc_cfg_t* c, const uint8_t* data, uint8_t** buffer_b);
+// pusch_uci_host.cpp (beside srslte_hip_pusch_uci_plan): Q'_cqi of a report of O bits behind Q'_ri symbols, the offset index being the caller's to
+// check; (row, column) of ACK / RI symbol i in the channel interleaver's matrix of rows x nof_symb (uci.c:497-545)
+uint32_t pusch_uci_cqi_qprime(const srslte_hip_pusch_uci_cfg_t* c, uint32_t O, uint32_t Qp_ri);
+void     pusch_uci_symbol_pos(bool is_ri, uint32_t i, uint32_t rows, uint32_t nof_symb, uint32_t* row, uint32_t* col);
 
 // chest.hip: srslte_chest_ul_estimate_pusch for a list of PUSCHs of one (L_prb, n_dmrs): item i = {subframe of the batch, PRB offset of slot 0 / 1,
 // row of d_res}; d_items on the device

@@ -338,37 +338,17 @@ __global__ __launch_bounds__(256) void pusch_cqi_decode_kernel(const int16_t* __
 }
 } // namespace
 
-static const float pusch_beta_cqi[16] = {-1.0f, -1.0f, 1.125f, 1.25f, 1.375f, 1.625f, 1.750f, 2.0f, 2.25f, 2.5f, 2.875f, 3.125f, 3.5f, 4.0f, 5.0f, 6.25f}; // sch.c:51-52
-static int pusch_cqi_qprime(uint32_t O, uint32_t I_offset_cqi, uint32_t L_prb, uint32_t nsymb, uint32_t K_segm, uint32_t Qp_ri)
-{ // Q_prime_cqi (uci.c:264-281), float arithmetic; 0 without a report. K_segm = 0 (no UL-SCH data): everything the rank indication leaves
-  if (O == 0) return 0;
-  if (O > 64 || I_offset_cqi > 15 || pusch_beta_cqi[I_offset_cqi] < 0) return -1;
-  const uint32_t L = O < 11 ? 0 : 8, m = L_prb * 12 * nsymb - Qp_ri;
-  const uint32_t x = K_segm ? (uint32_t)ceilf((float)(O + L) * L_prb * 12 * nsymb * pusch_beta_cqi[I_offset_cqi] / K_segm) : 999999u;
-  return (int)(x < m ? x : m);
-}
-
-// Q' of the HARQ-ACK / rank indication (Q_prime_ri_ack, uci.c:547-571): min(ceil(O M_sc N_symb beta / sum K_r), 4 M_sc) in float arithmetic.
-// Without UL-SCH data (K_segm = 0: a CQI-only PUSCH, 36.212 5.2.4.1) the report's size O_cqi - plus its 8 CRC bits above 11 - stands for
-// sum K_r and the callers divide the offset by the report's (sch.c:943-946,:970-973,:1111-1114,:1171-1174).
-static const float pusch_beta_harq[16] = {2.0f, 2.5f, 3.125f, 4.0f, 5.0f, 6.250f, 8.0f, 10.0f, 12.625f, 15.875f, 20.0f, 31.0f, 50.0f, 80.0f, 126.0f, -1.0f}; // 36.213 Table 8.6.3-1
-static const float pusch_beta_ri[16] = {1.25f, 1.625f, 2.0f, 2.5f, 3.125f, 4.0f, 5.0f, 6.25f, 8.0f, 10.0f, 12.625f, 15.875f, 20.0f, -1.0f, -1.0f, -1.0f}; // Table 8.6.3-2 (sch.c:47-48)
-static int pusch_ack_qprime(uint32_t O, uint32_t I_offset_ack, uint32_t L_prb, uint32_t nsymb, uint32_t K_segm, bool is_ri = false, uint32_t O_cqi = 0,
-                            uint32_t I_offset_cqi = 0)
+// The UCI plan (pusch_uci_host.cpp) of a PUSCH of the four batched pipelines: u is a fixed grant's configuration or one grant of a grants call,
+// which name these fields alike, and the matrix has the allocation's 12 L_prb rows. On top of the plan, the limits these pipelines share: their
+// kernels code HARQ-ACK and RI of 1 or 2 bits and reports of up to 64, the UL-SCH keeps more symbols than it has code blocks, and the report of
+// a PUSCH without data leaves none. Returns the plan's reason, or -1 for one of these limits.
+template <class U>
+static int pusch_pipeline_uci(const U& u, uint32_t nsymb, const srslte_hip_cbsegm_t& seg, srslte_hip_pusch_uci_res_t* pl)
 {
-  const float* tab = is_ri ? pusch_beta_ri : pusch_beta_harq;
-  if (O == 0) return 0;
-  if (O > 2 || I_offset_ack > 15 || tab[I_offset_ack] < 0) return -1;
-  float    beta = tab[I_offset_ack];
-  uint32_t K    = K_segm;
-  if (K == 0) {
-    if (O_cqi == 0 || O_cqi > 64 || I_offset_cqi > 15 || pusch_beta_cqi[I_offset_cqi] < 0) return -1;
-    beta /= pusch_beta_cqi[I_offset_cqi];
-    K = O_cqi <= 11 ? O_cqi : O_cqi + 8;
-  }
-  const uint32_t x = (uint32_t)ceilf((float)O * L_prb * 12 * nsymb * beta / K), m = 4 * L_prb * 12;
-  const uint32_t Qp = x < m ? x : m;
-  return (Qp + 3) / 4 <= 12 * L_prb ? (int)Qp : -1; // the ACK rows must exist (uci.c:505)
+  const srslte_hip_pusch_uci_cfg_t c = {u.L_prb,   nsymb,    2 * (uint32_t)u.mod, 12 * u.L_prb,   seg.C * seg.K1, seg.C,
+                                        u.ack_len, u.ri_len, u.cqi_len,           u.I_offset_ack, u.I_offset_ri,  u.I_offset_cqi};
+  if (const int why = srslte_hip_pusch_uci_plan(&c, pl)) return why;
+  return u.ack_len > 2 || u.ri_len > 2 || u.cqi_len > 64 || (seg.C ? pl->G_prime <= seg.C : pl->G_prime != 0) ? -1 : 0;
 }
 
 namespace {
@@ -437,17 +417,16 @@ extern "C" srslte_hip_ul_rx_t* srslte_hip_ul_rx_create(const srslte_hip_ul_rx_cf
   std::unique_ptr<srslte_hip_ul_rx> q(new srslte_hip_ul_rx());
   q->cfg = *cfg;
   if (fixed_grant_segmentation("ul_rx", cfg->tbs, &q->seg)) return nullptr;
-  // tbs = 0: a PUSCH without UL-SCH data carries a CQI report and nothing to decode (srslte_ulsch_decode, sch.c:1031-1065)
-  if (cfg->tbs == 0 && cfg->cqi_len == 0) {
-    hip_log("[srslte_hip] ul_rx: neither a transport block nor a CQI report\n");
-    return nullptr;
-  }
-  const uint32_t P = cfg->nof_prb, B = cfg->max_batch, C = q->seg.C, K = q->seg.K1, Qm = 2 * (uint32_t)cfg->mod, M_sc = 12 * cfg->L_prb;
+  const uint32_t P = cfg->nof_prb, B = cfg->max_batch, C = q->seg.C, Qm = 2 * (uint32_t)cfg->mod, M_sc = 12 * cfg->L_prb;
   const uint32_t nsl   = cfg->cp_ext ? 6 : 7;                       // SRSLTE_CP_NSYMB
   const uint32_t nsymb = 2 * (nsl - 1) - (cfg->shortened ? 1 : 0); // 2 (N_symb - 1) - N_srs data symbols (ra_ul.c nof_symb, pusch.c:52-91)
   const uint32_t nof_re = nsymb * M_sc, nbits = nof_re * Qm, scr_words = (nbits + 31) / 32 + 1; // spare word: the demapper reads two per symbol
-  const int      Qp_ri = pusch_ack_qprime(cfg->ri_len, cfg->I_offset_ri, cfg->L_prb, nsymb, C * K, true, cfg->cqi_len, cfg->I_offset_cqi);
-  const int      Qp_cqi = Qp_ri >= 0 ? pusch_cqi_qprime(cfg->cqi_len, cfg->I_offset_cqi, cfg->L_prb, nsymb, C * K, (uint32_t)Qp_ri) : -1;
+  srslte_hip_pusch_uci_res_t uci;
+  if (const int why = pusch_pipeline_uci(*cfg, nsymb, q->seg, &uci)) {
+    // tbs = 0: a PUSCH without UL-SCH data carries a CQI report and nothing to decode (srslte_ulsch_decode, sch.c:1031-1065)
+    hip_log(why == SRSLTE_HIP_PUSCH_UCI_EMPTY ? "[srslte_hip] ul_rx: neither a transport block nor a CQI report\n" : "[srslte_hip] ul_rx: initialisation failed\n");
+    return nullptr;
+  }
   q->ofdm  = srslte_hip_ofdm_create((int)P, cfg->cp_ext ? 0 : 1, 1);
   q->chest = srslte_hip_chest_ul_create(cfg->cell_id, P, cfg->cp_ext ? 0 : 1, &cfg->dmrs_cfg);
   bool ok  = q->ofdm && q->chest && srslte_hip_ofdm_set_freq_shift(q->ofdm, -0.5f) == SRSLTE_SUCCESS; // enb_ul.c:62-63 (no normalisation)
@@ -460,15 +439,13 @@ extern "C" srslte_hip_ul_rx_t* srslte_hip_ul_rx_create(const srslte_hip_ul_rx_cf
   ok = ok && !q->d_grid.alloc(glen * B) && !q->d_ce.alloc(glen * B) && hipMemset(q->d_ce, 0, sizeof(cf32) * glen * B) == hipSuccess &&
        !q->d_z.alloc((size_t)nof_re * B) && !q->d_d.alloc((size_t)nof_re * B) && !q->d_res.alloc((size_t)5 * B) && !q->d_g.alloc((size_t)nbits * B + 16) &&
        !q->d_ack_sum.alloc((size_t)8 * B) && !q->d_ack.alloc((size_t)4 * B) && hipMemset(q->d_ack, 0, (size_t)4 * B) == hipSuccess &&
-       pusch_ack_qprime(cfg->ack_len, cfg->I_offset_ack, cfg->L_prb, nsymb, C * K, false, cfg->cqi_len, cfg->I_offset_cqi) >= 0 &&
-       Qp_ri >= 0 && (uint32_t)Qp_ri < nof_re && Qp_cqi >= 0 && (C ? (uint32_t)(Qp_ri + Qp_cqi) + C < nof_re : (uint32_t)(Qp_ri + Qp_cqi) == nof_re) &&
        !q->d_cqi.alloc((size_t)65 * B) && hipMemset(q->d_cqi, 0, (size_t)65 * B) == hipSuccess;
   ok = ok && hipDeviceSynchronize() == hipSuccess; // the memsets above ran on the null stream
   if (ok && C) { // as for the PDSCH, with the whole parity layout and the assembly kernel
     // the UL-SCH is rate-matched to what the RI and the CQI report leave (sch.c:1157-1160) and follows the report in the stream
     SchRxFixed::Cfg sc = {}; // 16-bit LLRs, no CSI weighting, neither permission
-    sc.tbs = cfg->tbs; sc.max_batch = B; sc.max_iterations = cfg->max_iterations; sc.Qm = Qm; sc.Nl = 1; sc.e_off = (uint32_t)Qp_cqi * Qm; sc.max_bits = nbits;
-    sc.nof_re[0] = sc.nof_re[1] = sc.nof_re[2] = nof_re - (uint32_t)Qp_ri - (uint32_t)Qp_cqi;
+    sc.tbs = cfg->tbs; sc.max_batch = B; sc.max_iterations = cfg->max_iterations; sc.Qm = Qm; sc.Nl = 1; sc.e_off = uci.Q_cqi; sc.max_bits = nbits;
+    sc.nof_re[0] = sc.nof_re[1] = sc.nof_re[2] = uci.G_prime;
     q->sch.reset(new SchRxFixed());
     ok = q->sch->init(sc) == SRSLTE_SUCCESS;
   }
@@ -478,10 +455,10 @@ extern "C" srslte_hip_ul_rx_t* srslte_hip_ul_rx_create(const srslte_hip_ul_rx_cf
   }
   q->pg.cell_nre = 12 * (int)P; q->pg.M_sc = (int)M_sc; q->pg.n_prb = (int)cfg->n_prb; q->pg.n_prb1 = (int)(cfg->hopping ? cfg->n_prb_slot1 : cfg->n_prb); q->pg.mod = cfg->mod; q->pg.Qm = (int)Qm;
   q->pg.scr_words = (int)scr_words; q->pg.mmse = cfg->mmse; q->pg.nsymb = (int)nsymb; q->pg.nsl = (int)nsl;
-  q->pg.ack.O = (int)cfg->ack_len; q->pg.ack.Qprime = pusch_ack_qprime(cfg->ack_len, cfg->I_offset_ack, cfg->L_prb, nsymb, C * K, false, cfg->cqi_len, cfg->I_offset_cqi);
+  q->pg.ack.O = (int)cfg->ack_len; q->pg.ack.Qprime = (int)uci.Qp_ack;
   q->pg.ack_sum = q->d_ack_sum;
-  q->pg.ri.O = (int)cfg->ri_len; q->pg.ri.Qprime = Qp_ri; q->pg.ri_sum = q->d_ack_sum + 4 * B;
-  q->Qp_cqi   = Qp_cqi;
+  q->pg.ri.O = (int)cfg->ri_len; q->pg.ri.Qprime = (int)uci.Qp_ri; q->pg.ri_sum = q->d_ack_sum + 4 * B;
+  q->Qp_cqi   = (int)uci.Qp_cqi;
   return q.release();
 }
 
@@ -675,24 +652,20 @@ static int ul_rx_grants(srslte_hip_ul_rx_t* q, const void* d_iq, uint32_t tti0, 
     // HARQ-ACK and rank indication of this PUSCH (srslte_uci_cfg_t of its srslte_pusch_cfg_t): Q' from the grant's own size and code blocks; the
     // UL-SCH is rate-matched to what the RI symbols leave (sch.c:1157-1160), the ACK symbols overwrite it
     srslte_hip_cbsegm_t seg;
-    const uint32_t      nof_re = nsymb * 12 * gr.L_prb;
     if (srslte_hip_cbsegm(&seg, gr.tbs)) return SRSLTE_ERROR_INVALID_INPUTS;
-    const int Qp_ack = pusch_ack_qprime(gr.ack_len, gr.I_offset_ack, gr.L_prb, nsymb, seg.C * seg.K1, false, gr.cqi_len, gr.I_offset_cqi);
-    const int Qp_ri  = pusch_ack_qprime(gr.ri_len, gr.I_offset_ri, gr.L_prb, nsymb, seg.C * seg.K1, true, gr.cqi_len, gr.I_offset_cqi);
-    const int Qp_cqi = Qp_ri >= 0 && gr.cqi_len <= 64 ? pusch_cqi_qprime(gr.cqi_len, gr.I_offset_cqi, gr.L_prb, nsymb, seg.C * seg.K1, (uint32_t)Qp_ri) : -1;
-    if (Qp_ack < 0 || Qp_ri < 0 || Qp_cqi < 0 || (seg.C ? (uint32_t)(Qp_ri + Qp_cqi) + seg.C >= nof_re : (uint32_t)(Qp_ri + Qp_cqi) != nof_re) || gr.mod < 1 ||
-        gr.mod > 3) {
+    srslte_hip_pusch_uci_res_t uci;
+    if (pusch_pipeline_uci(gr, nsymb, seg, &uci) || gr.mod < 1 || gr.mod > 3) {
       hip_log("[srslte_hip] ul_rx grants: entry %u: invalid UCI configuration (ack %u / %u, ri %u / %u, cqi %u / %u)\n", p, gr.ack_len, gr.I_offset_ack, gr.ri_len,
               gr.I_offset_ri, gr.cqi_len, gr.I_offset_cqi);
       return SRSLTE_ERROR_INVALID_INPUTS;
     }
-    pd.ack.O = (int)gr.ack_len; pd.ack.Qprime = Qp_ack; pd.ri.O = (int)gr.ri_len; pd.ri.Qprime = Qp_ri;
-    pd.cqi_O = (int)gr.cqi_len; pd.cqi_Q = Qp_cqi * 2 * gr.mod;
+    pd.ack.O = (int)gr.ack_len; pd.ack.Qprime = (int)uci.Qp_ack; pd.ri.O = (int)gr.ri_len; pd.ri.Qprime = (int)uci.Qp_ri;
+    pd.cqi_O = (int)gr.cqi_len; pd.cqi_Q = (int)uci.Q_cqi;
     any_uci = any_uci || gr.ack_len || gr.ri_len;
     any_cqi = any_cqi || gr.cqi_len;
     // the report's LLRs come first in the row; the UL-SCH is rate-matched to the rest (sch.c:1058-1064)
     if (gr.tbs == 0) continue; // no code blocks: row p of d_tb_ok becomes 0
-    if (int r = bd.add_tb(p, p, gr.mod, gr.tbs, gr.rv, gr.new_data, nof_re - (uint32_t)Qp_ri - (uint32_t)Qp_cqi, 1, (uint32_t)pd.cqi_Q)) return r;
+    if (int r = bd.add_tb(p, p, gr.mod, gr.tbs, gr.rv, gr.new_data, uci.G_prime, 1, uci.Q_cqi)) return r;
   }
   bd.fill_map(h.map);
   const uint8_t* d_cof = grants_direct_cof(g, h, d, nof_grants, false, [](uint32_t) { return true; });

@@ -305,29 +305,18 @@ extern "C" srslte_hip_ul_tx_t* srslte_hip_ul_tx_create(const srslte_hip_ul_tx_cf
   g.cell_nre = 12 * (int)P; g.M_sc = (int)M_sc; g.n_prb = (int)cfg->n_prb; g.n_prb1 = (int)(cfg->hopping ? cfg->n_prb_slot1 : cfg->n_prb); g.Qm = (int)Qm; g.scr_words = (int)scr_words; g.C = (int)C; g.K = (int)K;
   g.nsymb = (int)nsymb;
   g.nsl   = (int)nsl;
-  if (cfg->tbs == 0 && cfg->cqi_len == 0) { // a PUSCH without UL-SCH data carries a CQI report (srslte_ulsch_encode, sch.c:1133-1165)
-    hip_log("[srslte_hip] ul_tx: neither a transport block nor a CQI report\n");
-    return nullptr;
-  }
-  g.ack.O = (int)cfg->ack_len; g.ack.Qprime = pusch_ack_qprime(cfg->ack_len, cfg->I_offset_ack, cfg->L_prb, nsymb, C * K, false, cfg->cqi_len, cfg->I_offset_cqi);
-  if (g.ack.Qprime < 0) {
-    hip_log("[srslte_hip] ul_tx: invalid HARQ-ACK configuration\n");
+  srslte_hip_pusch_uci_res_t uci;
+  if (const int why = pusch_pipeline_uci(*cfg, nsymb, q->enc.seg, &uci)) {
+    // a PUSCH without UL-SCH data carries a CQI report (srslte_ulsch_encode, sch.c:1133-1165)
+    hip_log(why == SRSLTE_HIP_PUSCH_UCI_EMPTY ? "[srslte_hip] ul_tx: neither a transport block nor a CQI report\n"
+                                              : "[srslte_hip] ul_tx: invalid HARQ-ACK, rank-indication or CQI configuration\n");
     return nullptr;
   }
   g.tbs = (int)cfg->tbs; g.rm_len = (int)(3 * K + 12);
-  g.ri.O = (int)cfg->ri_len; g.ri.Qprime = pusch_ack_qprime(cfg->ri_len, cfg->I_offset_ri, cfg->L_prb, nsymb, C * K, true, cfg->cqi_len, cfg->I_offset_cqi);
-  if (g.ri.Qprime < 0 || (uint32_t)g.ri.Qprime >= nof_re) {
-    hip_log("[srslte_hip] ul_tx: invalid rank-indication configuration\n");
-    return nullptr;
-  }
-  g.Qp_cqi = pusch_cqi_qprime(cfg->cqi_len, cfg->I_offset_cqi, cfg->L_prb, nsymb, C * K, (uint32_t)g.ri.Qprime);
-  if (g.Qp_cqi < 0 || (C ? (uint32_t)(g.ri.Qprime + g.Qp_cqi) + C >= nof_re : (uint32_t)(g.ri.Qprime + g.Qp_cqi) != nof_re)) {
-    hip_log("[srslte_hip] ul_tx: invalid CQI configuration\n");
-    return nullptr;
-  }
-  g.cqi_stride = (g.Qp_cqi * (int)Qm + 15) & ~15;
-  const uint32_t g_re = nof_re - g.ri.Qprime - g.Qp_cqi; // UL-SCH symbols: what the RI and the CQI report leave (sch.c:1157-1160)
-  g.syms_lo = C ? (int)(g_re / C) : 0; g.C_lo = C ? (int)(C - g_re % C) : 0; // G' = the UL-SCH symbols, gamma = G' mod C (sch.c:205-207)
+  g.ack.O = (int)cfg->ack_len; g.ack.Qprime = (int)uci.Qp_ack;
+  g.ri.O = (int)cfg->ri_len; g.ri.Qprime = (int)uci.Qp_ri;
+  g.Qp_cqi = (int)uci.Qp_cqi; g.cqi_stride = ((int)uci.Q_cqi + 15) & ~15;
+  g.syms_lo = (int)uci.syms_lo; g.C_lo = (int)uci.C_lo; // of G', the symbols the RI and the report leave to the UL-SCH
   constellation_levels(cfg->mod, g.lvl); // one axis: bits b0 b2 b4 of the symbol
   q->ofdm = srslte_hip_ofdm_create((int)P, cfg->cp_ext ? 0 : 1, 0);
   q->dmrs = srslte_hip_chest_ul_create(cfg->cell_id, P, cfg->cp_ext ? 0 : 1, &cfg->dmrs_cfg);

@@ -163,11 +163,9 @@ extern "C" int srslte_hip_ul_tx_batch_grants(srslte_hip_ul_tx_t* q, const uint8_
     GrantDev&                    gd = h_gr[p];
     memset(&gd, 0, sizeof(gd));
     gd.sf_idx = (int)((tti0 + gr.sf) % 10); gd.rnti = gr.rnti;
-    // tbs = 0: a PUSCH without UL-SCH data (C = 0) - the Q' rules of 36.212 5.2.4.1 (pusch_ack_qprime / pusch_cqi_qprime), no code blocks
-    const int Qp_ack = pusch_ack_qprime(gr.ack_len, gr.I_offset_ack, gr.L_prb, nsymb, C * K, false, gr.cqi_len, gr.I_offset_cqi);
-    const int Qp_ri  = pusch_ack_qprime(gr.ri_len, gr.I_offset_ri, gr.L_prb, nsymb, C * K, true, gr.cqi_len, gr.I_offset_cqi);
-    const int Qp_cqi = Qp_ri >= 0 && gr.cqi_len <= 64 ? pusch_cqi_qprime(gr.cqi_len, gr.I_offset_cqi, gr.L_prb, nsymb, C * K, (uint32_t)Qp_ri) : -1;
-    if (Qp_ack < 0 || Qp_ri < 0 || Qp_cqi < 0 || (C ? (uint32_t)(Qp_ri + Qp_cqi) + C >= nof_re : (uint32_t)(Qp_ri + Qp_cqi) != nof_re)) {
+    // tbs = 0: a PUSCH without UL-SCH data (C = 0) - the Q' rules of 36.212 5.2.4.1 (pusch_uci_host.cpp), no code blocks
+    srslte_hip_pusch_uci_res_t uci;
+    if (pusch_pipeline_uci(gr, nsymb, segs[p], &uci)) {
       hip_log("[srslte_hip] ul_tx grants: entry %u: invalid UCI configuration\n", p);
       return SRSLTE_ERROR_INVALID_INPUTS;
     }
@@ -177,10 +175,9 @@ extern "C" int srslte_hip_ul_tx_batch_grants(srslte_hip_ul_tx_t* q, const uint8_
     td.row = (int)p; td.sf = (int)gr.sf; td.tbs = (int)gr.tbs; td.C = (int)C; td.K = (int)K; td.rlenB = (int)((C <= 1 ? K : K - 24) / 8);
     td.nre = (int)nof_re; td.mod = gr.mod; td.Qm = 2 * gr.mod;
     PuschTxDesc& pd = h_pd[p];
-    const uint32_t g_re = nof_re - (uint32_t)Qp_ri - (uint32_t)Qp_cqi; // UL-SCH symbols (sch.c:1157-1160)
-    pd.M_sc = 12 * (int)gr.L_prb; pd.n_prb = (int)gr.n_prb; pd.n_prb1 = (int)gr.n_prb_slot1; pd.syms_lo = C ? (int)(g_re / C) : 0; pd.C_lo = C ? (int)(C - g_re % C) : 0;
-    pd.Qp_cqi = Qp_cqi; pd.cqi_O = (int)gr.cqi_len; pd.cqi_w = nullptr; pd.cqi_wlen = 1; pd.sf_idx = gd.sf_idx;
-    pd.ack.O = (int)gr.ack_len; pd.ack.Qprime = Qp_ack; pd.ri.O = (int)gr.ri_len; pd.ri.Qprime = Qp_ri;
+    pd.M_sc = 12 * (int)gr.L_prb; pd.n_prb = (int)gr.n_prb; pd.n_prb1 = (int)gr.n_prb_slot1; pd.syms_lo = (int)uci.syms_lo; pd.C_lo = (int)uci.C_lo;
+    pd.Qp_cqi = (int)uci.Qp_cqi; pd.cqi_O = (int)gr.cqi_len; pd.cqi_w = nullptr; pd.cqi_wlen = 1; pd.sf_idx = gd.sf_idx;
+    pd.ack.O = (int)gr.ack_len; pd.ack.Qprime = (int)uci.Qp_ack; pd.ri.O = (int)gr.ri_len; pd.ri.Qprime = (int)uci.Qp_ri;
     if (gr.cqi_len > 11) { // the CQI report's rate matching (cqi_rm_conv_order), read circularly by the kernel
       auto cw = g->cqi_w.find(gr.cqi_len);
       if (cw == g->cqi_w.end()) {

@@ -139,8 +139,8 @@ uint32_t ulsch_enc_ones(const uint8_t* d, uint32_t O, uint32_t Qm, int* period)
 
 // what a call is made of, from its configuration alone
 struct UlschEncPlan {
-  srslte_hip_cbsegm_t seg;
-  uint32_t            Qm, H, rows, Qp_ack, Qp_ri, Qp_cqi;
+  srslte_hip_cbsegm_t        seg;
+  srslte_hip_pusch_uci_res_t uci;
 };
 
 } // namespace
@@ -156,32 +156,19 @@ static int ulsch_enc_plan(const srslte_hip_ulsch_enc_cfg_t* c, const uint8_t* da
     return SRSLTE_ERROR_INVALID_INPUTS;
   srslte_hip_cbsegm_t& seg = pl->seg;
   memset(&seg, 0, sizeof(seg));
-  if (c->tbs) {
-    if (int r = sch_enc_check(data, c->tbs, c->rv, buffer_b, &seg)) return r;
-  } else if (c->cqi_len == 0) {
-    hip_log("[srslte_hip] ulsch_enc: a PUSCH without UL-SCH data carries a CQI report (36.212 5.2.4)\n"); // upstream would interleave stale scratch
-    return SRSLTE_ERROR_INVALID_INPUTS;
-  }
-  const uint32_t K_segm = seg.C * seg.K1, H = c->nof_bits / Qm;
-  const float    b_cqi = pusch_beta_cqi[c->I_offset_cqi];
-  float          b_ack = pusch_beta_harq[c->I_offset_ack], b_ri = pusch_beta_ri[c->I_offset_ri];
-  if ((c->ack_len && b_ack < 0) || (c->ri_len && b_ri < 0) || ((c->cqi_len || !c->tbs) && b_cqi < 0)) {
+  if (int r = c->tbs ? sch_enc_check(data, c->tbs, c->rv, buffer_b, &seg) : 0) return r;
+  const srslte_hip_pusch_uci_cfg_t uc = {c->L_prb,   nsymb,     Qm,         12 * c->L_prb,   seg.C * seg.K1,   seg.C,
+                                         c->ack_len, c->ri_len, c->cqi_len, c->I_offset_ack, c->I_offset_ri, c->I_offset_cqi};
+  const int why = srslte_hip_pusch_uci_plan(&uc, &pl->uci);
+  if (why == SRSLTE_HIP_PUSCH_UCI_BETA) {
     hip_log("Error beta is reserved\n"); // uci.c:475-478,:705-708
     return -1;
   }
-  if (!c->tbs) b_ack /= b_cqi, b_ri /= b_cqi; // sch.c:1112-1114,:1174-1176
-  const uint32_t Kq = K_segm ? K_segm : (c->cqi_len <= 11 ? c->cqi_len : c->cqi_len + 8); // uci.c:555-564
-  pl->Qm = Qm; pl->H = H; pl->rows = H / nsymb;
-  pl->Qp_ri  = c->ri_len ? ulsch_qprime(c->ri_len, b_ri, c->L_prb, nsymb, Kq) : 0;
-  pl->Qp_ack = c->ack_len ? ulsch_qprime(c->ack_len, b_ack, c->L_prb, nsymb, Kq) : 0;
-  const int qc = pusch_cqi_qprime(c->cqi_len, c->I_offset_cqi, c->L_prb, nsymb, K_segm, pl->Qp_ri);
-  if (qc < 0) return SRSLTE_ERROR_INVALID_INPUTS;
-  pl->Qp_cqi = (uint32_t)qc;
-  if (c->tbs && pl->Qp_ri + pl->Qp_cqi >= H) {
-    hip_log("[srslte_hip] ulsch_enc: Q'_ri %u + Q'_cqi %u leave no symbol of %u to the UL-SCH\n", pl->Qp_ri, pl->Qp_cqi, H);
-    return SRSLTE_ERROR_INVALID_INPUTS;
-  }
-  return SRSLTE_SUCCESS;
+  if (why == SRSLTE_HIP_PUSCH_UCI_EMPTY) // upstream would interleave stale scratch
+    hip_log("[srslte_hip] ulsch_enc: a PUSCH without UL-SCH data carries a CQI report (36.212 5.2.4)\n");
+  if (why == SRSLTE_HIP_PUSCH_UCI_NO_ROOM)
+    hip_log("[srslte_hip] ulsch_enc: Q'_ri %u + Q'_cqi %u leave no symbol of %u to the UL-SCH\n", pl->uci.Qp_ri, pl->uci.Qp_cqi, uc.rows * nsymb);
+  return why ? SRSLTE_ERROR_INVALID_INPUTS : SRSLTE_SUCCESS;
 }
 int ulsch_enc_check(const srslte_hip_ulsch_enc_cfg_t* c, const uint8_t* data, uint8_t** buffer_b)
 {
@@ -200,7 +187,7 @@ extern "C" int srslte_hip_ulsch_encode(srslte_hip_sch_enc_t* q, const uint8_t* d
   if (int r = ulsch_enc_plan(c, data, buffer_b, &pl)) return r;
   if (c->nof_bits > q->max_e || c->tbs > q->max_tbs) return SRSLTE_ERROR_INVALID_INPUTS;
   const srslte_hip_cbsegm_t& seg = pl.seg;
-  const uint32_t Qm = pl.Qm, nsymb = c->nof_symb, H = pl.H, rows = pl.rows, Qp_ack = pl.Qp_ack, Qp_ri = pl.Qp_ri, Qp_cqi = pl.Qp_cqi;
+  const uint32_t Qm = 2 * (uint32_t)c->mod, nsymb = c->nof_symb, rows = 12 * c->L_prb, Qp_ack = pl.uci.Qp_ack, Qp_ri = pl.uci.Qp_ri, Qp_cqi = pl.uci.Qp_cqi;
   if (ulsch_enc_init(q)) return SRSLTE_ERROR;
   const srslte_hip_sch_enc::KTab* kt = c->tbs ? q->table(seg.K1) : nullptr;
   if (c->tbs && !kt) return SRSLTE_ERROR;
@@ -210,7 +197,7 @@ extern "C" int srslte_hip_ulsch_encode(srslte_hip_sch_enc_t* q, const uint8_t* d
   uint16_t*   h_rm  = reinterpret_cast<uint16_t*>(q->h_ul + UL_ENC_O_RM);
   uint32_t *  h_g = reinterpret_cast<uint32_t*>(q->h_ul + q->o_ul_g), *h_q = reinterpret_cast<uint32_t*>(q->h_ul + q->o_ul_q);
   // ---- the coded report: bits [0, Q'_cqi Qm) of g
-  const int off = (int)(Qp_cqi * Qm);
+  const int off = (int)pl.uci.Q_cqi;
   if (off) {
     memcpy(h_cqi, c->cqi_bits, 64);
     if (c->cqi_len > 11) { // the rate matching of the convolutional code: cqi_rm_conv_order read circularly
@@ -225,7 +212,7 @@ extern "C" int srslte_hip_ulsch_encode(srslte_hip_sch_enc_t* q, const uint8_t* d
   memset(&sg, 0, sizeof(sg));
   const uint8_t* w_src = nullptr;
   if (c->tbs) {
-    sg = sch_enc_geom(q, kt, seg.C, seg.K1, Qm, H - Qp_ri - Qp_cqi, c->rv);
+    sg = sch_enc_geom(q, kt, seg.C, seg.K1, Qm, pl.uci.G_prime, c->rv);
     if (int r = sch_enc_queue_w(q, kt, data, c->tbs, c->rv, buffer_b, sg, &w_src)) return r;
   }
   const int g_bits_n = off + sg.total, g_words = ceil_div(g_bits_n, 32);

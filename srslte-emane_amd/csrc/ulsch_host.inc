@@ -90,13 +90,6 @@ __global__ void ulsch_cqi_fold_kernel(int16_t* __restrict__ g, int Q)
   g[tid] = (int16_t)a;
 }
 
-// Q_prime_ri_ack (uci.c:547-571) in its float arithmetic, any number of bits O
-uint32_t ulsch_qprime(uint32_t O, float beta, uint32_t L_prb, uint32_t nsymb, uint32_t K)
-{
-  const uint32_t x = (uint32_t)ceilf((float)O * L_prb * 12 * nsymb * beta / K), m = 4 * L_prb * 12;
-  return x < m ? x : m;
-}
-
 // pinned block of the UL call: decisions [4] (ACK 0, 1, RI 0, 1) | report bits [64] at 64 | its CRC flag at 128 | c_seq bits from 256 on
 constexpr size_t UL_O_CQI = 64, UL_O_CRC = 128, UL_O_CS = 256;
 
@@ -130,40 +123,37 @@ extern "C" int srslte_hip_ulsch_decode(srslte_hip_sch_t* q, const int16_t* q_bit
     if (!buffer_f || !cb_crc || !cb_bytes || c->max_iterations == 0 || c->rv > 3 || c->tbs > q->max_tbs || srslte_hip_cbsegm(&seg, c->tbs) || seg.F || seg.C2 ||
         seg.C > q->Cmax)
       return SRSLTE_ERROR_INVALID_INPUTS;
-  } else if (c->cqi_len == 0) {
-    hip_log("[srslte_hip] ulsch: a PUSCH without UL-SCH data carries a CQI report (36.212 5.2.4)\n");
-    return SRSLTE_ERROR_INVALID_INPUTS;
   }
-  const uint32_t K_segm = seg.C * seg.K1, rows = c->nof_bits / Qm / nsymb, H = rows * nsymb;
+  const uint32_t rows = c->nof_bits / Qm / nsymb, H = rows * nsymb; // nof_bits is the caller's: the rows are not tied to 12 L_prb here
   const bool     cqi = c->cqi_len > 0;
-  const float    b_cqi = pusch_beta_cqi[c->I_offset_cqi];
-  float          b_ack = pusch_beta_harq[c->I_offset_ack], b_ri = pusch_beta_ri[c->I_offset_ri];
-  if ((c->ack_len && b_ack < 0) || (c->ri_len && b_ri < 0) || ((cqi || !c->tbs) && b_cqi < 0)) {
+  const srslte_hip_pusch_uci_cfg_t uc = {c->L_prb,   nsymb,     Qm,         rows,            seg.C * seg.K1,   seg.C,
+                                         c->ack_len, c->ri_len, c->cqi_len, c->I_offset_ack, c->I_offset_ri, c->I_offset_cqi};
+  srslte_hip_pusch_uci_res_t       pl;
+  const int                        why = srslte_hip_pusch_uci_plan(&uc, &pl); // any ack_len: 3 bits and more clear their positions and decide nothing
+  if (why == SRSLTE_HIP_PUSCH_UCI_BETA) {
     hip_log("Error beta is reserved\n"); // uci.c:432,:761
     return SRSLTE_ERROR;
   }
-  if (!c->tbs) b_ack /= b_cqi, b_ri /= b_cqi; // sch.c:943-945,:970-972
-  const uint32_t Kq = K_segm ? K_segm : (c->cqi_len <= 11 ? c->cqi_len : c->cqi_len + 8); // uci.c:555-564
-  const uint32_t Qp_ack = c->ack_len ? ulsch_qprime(c->ack_len, b_ack, c->L_prb, nsymb, Kq) : 0;
-  const uint32_t Qp_ri  = c->ri_len ? ulsch_qprime(c->ri_len, b_ri, c->L_prb, nsymb, Kq) : 0;
-  // the report's size may depend on the rank (cqi_len_rank2): both hypotheses are sized before anything runs
+  if (why == SRSLTE_HIP_PUSCH_UCI_EMPTY) hip_log("[srslte_hip] ulsch: a PUSCH without UL-SCH data carries a CQI report (36.212 5.2.4)\n");
+  if (why) return SRSLTE_ERROR_INVALID_INPUTS;
+  const uint32_t Qp_ack = pl.Qp_ack, Qp_ri = pl.Qp_ri;
+  // the report's size may depend on the rank (cqi_len_rank2): both hypotheses are sized before anything runs, each leaving every code block a symbol
   const uint32_t len2 = cqi && c->cqi_len_rank2 ? c->cqi_len_rank2 : c->cqi_len;
-  const int      Qc[2] = {pusch_cqi_qprime(c->cqi_len, c->I_offset_cqi, c->L_prb, nsymb, K_segm, Qp_ri),
-                          pusch_cqi_qprime(len2, c->I_offset_cqi, c->L_prb, nsymb, K_segm, Qp_ri)};
-  if (Qp_ack > 4 * rows || Qp_ri > 4 * rows || Qc[0] < 0 || Qc[1] < 0) return SRSLTE_ERROR_INVALID_INPUTS; // uci.c:504,:529: the rows must exist
+  const uint32_t Qc[2] = {pl.Qp_cqi, pusch_uci_cqi_qprime(&uc, len2, Qp_ri)};
   for (int k = 0; k < 2; k++) {
-    if (Qp_ri + (uint32_t)Qc[k] > H || (c->tbs && H - Qp_ri - (uint32_t)Qc[k] < seg.C)) return SRSLTE_ERROR_INVALID_INPUTS;
+    if (Qp_ri + Qc[k] > H || (c->tbs && H - Qp_ri - Qc[k] < seg.C)) return SRSLTE_ERROR_INVALID_INPUTS;
   }
   if (ulsch_init(q)) return SRSLTE_ERROR;
   hipStream_t st = q->st;
   uint8_t *   h_dec = q->h_ul, *h_cqi = q->h_ul + UL_O_CQI, *h_crc = q->h_ul + UL_O_CRC, *h_cs = q->h_ul + UL_O_CS;
   // ---- up: the LLRs, and c_seq where a 1-bit ACK / RI reads it (p0 and p1 of every symbol, uci.c:627-640)
-  const uint32_t set_norm[2][4] = {{2, 3, 8, 9}, {1, 4, 7, 10}}, set_ext[2][4] = {{1, 2, 6, 7}, {0, 3, 5, 8}};
   for (int w = 0; w < 2; w++) {
     const uint32_t Qp = w ? Qp_ri : Qp_ack, O = w ? c->ri_len : c->ack_len;
     uint8_t*       cs = h_cs + (w ? 2 * Qp_ack : 0);
     for (uint32_t i = 0; i < Qp; i++) {
-      const uint32_t row = rows - 1 - i / 4, col = nsymb > 10 ? set_norm[w][(3 * i) % 4] : set_ext[w][(3 * i) % 4], p0 = (col * rows + row) * Qm;
+      uint32_t row, col;
+      pusch_uci_symbol_pos(w != 0, i, rows, nsymb, &row, &col);
+      const uint32_t p0 = (col * rows + row) * Qm;
       cs[2 * i]     = O == 1 ? c_seq[p0] : 0;
       cs[2 * i + 1] = O == 1 ? c_seq[p0 + 1] : 0;
     }
