@@ -363,11 +363,10 @@ def test_invalid_configurations_are_refused():
     L, INV = pkg.lib(), pkg.SRSLTE_ERROR_INVALID_INPUTS
     assert L.srslte_hip_prach_create(C.byref(pkg.prach_cfg(6, 3, tdd=True))) is None
     assert L.srslte_hip_prach_create(C.byref(pkg.prach_cfg(5, 3))) is None
-    pkg._bind_ul_ctrl(L)
     for create in (L.srslte_hip_ul_ctrl_create, L.srslte_hip_ul_ctrl_tx_create):
         assert create(C.byref(pkg.ul_ctrl_cfg(6, 1, tdd=True, max_pucch=1))) is None
         assert create(C.byref(pkg.ul_ctrl_cfg(6, 1, max_pucch=0))) is None
-    assert pkg._bind_srs(L).srslte_hip_srs_create(C.byref(pkg.srs_cfg(6, 1, 0, max_srs=1))) is None  # a 36 PRB sounding band in a 6 PRB cell
+    assert L.srslte_hip_srs_create(C.byref(pkg.srs_cfg(6, 1, 0, max_srs=1))) is None  # a 36 PRB sounding band in a 6 PRB cell
     for bad in (dict(tdd=True), dict(nof_rx=5), dict(max_batch=0)):  # the last two refuse the BcastTables' owner before they are made
         with pytest.raises(RuntimeError):
             pkg.DlCtrl(6, 1, 1, **bad)

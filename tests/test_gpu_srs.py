@@ -398,7 +398,7 @@ def test_one_object_holds_many_tables():
 
 
 def test_refusals_and_calls_on_one_stream():
-    L = pkg._bind_srs(pkg.lib())
+    L = pkg.lib()
     for cfg in (pkg.srs_cfg(6, 1, 0, max_srs=2), pkg.srs_cfg(50, 1, 0, tdd=True, max_srs=2), pkg.srs_cfg(50, 1, 8, max_srs=2),
                 pkg.srs_cfg(50, 1, 0, subframe_config=15, max_srs=2), pkg.srs_cfg(5, 1, 7, max_srs=2), pkg.srs_cfg(111, 1, 7, max_srs=2)):
         assert L.srslte_hip_srs_create(C.byref(cfg)) is None

@@ -328,7 +328,6 @@ def test_grants_pipeline_and_round_trip():
 def test_refusals_and_calls_on_one_stream():
     spec = CELLS[3]
     P = spec[0]
-    pkg._bind_ul_ctrl(pkg.lib())  # lib() binds it too; a test run on its own must not depend on that
     assert pkg.lib().srslte_hip_ul_ctrl_create(C.byref(pkg.ul_ctrl_cfg(P, 5, tdd=True, max_pucch=4))) is None
     assert pkg.lib().srslte_hip_ul_ctrl_create(C.byref(pkg.ul_ctrl_cfg(P, 5, delta_pucch_shift=2, N_cs=3, max_pucch=4))) is None
     assert pkg.lib().srslte_hip_ul_ctrl_create(C.byref(pkg.ul_ctrl_cfg(P, 5, delta_pucch_shift=0, max_pucch=4))) is None

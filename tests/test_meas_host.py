@@ -45,7 +45,7 @@ def test_check_refuses_calls():
 
 
 def test_device_entry_points_refuse_null_objects_without_a_device():
-    L = pkg._bind_meas(pkg.lib())
+    L = pkg.lib()
     assert L.srslte_hip_meas_create(None) is None
     assert L.srslte_hip_meas_set_cells(None, None, 1, None) == INVALID
     assert L.srslte_hip_meas_run_batch(None, None, 0, 2, 1, None, None) == INVALID
