@@ -712,9 +712,30 @@ int srslte_hip_pusch_uci_plan(const srslte_hip_pusch_uci_cfg_t* cfg, srslte_hip_
  *   Search (cif disabled): SI / P / RA-RNTI: common space, 1A then 1C; C-RNTI: UE-specific space with ue_dci_formats[tm] (1A + 1 / 1 / 2A / 2
  *     for TM1-4, ue_dl.c:31-39), then 1A in the common space. The first candidate whose CRC remainder equals the RNTI and whose format is the
  *     one searched ends the search; a format-0 hit while searching 1A is not a DL DCI (ue_dl.c:452-470).
- * FDD cells, normal / extended CP, 6-110 PRB, 1 / 2 / 4 ports, 1-4 receive antennas, every PHICH configuration (phich_resources
- * srslte_phich_r_t 0-3 = 1/6, 1/2, 1, 2; phich_ext = SRSLTE_PHICH_EXT; the PHICH REGs of regs.c:245-367 with mi = 1). Refused: TDD cells
- * (srslte_hip_dl_ctrl_create returns NULL) and MBSFN subframes (SRSLTE_ERROR_INVALID_INPUTS).
+ * FDD and TDD cells, normal / extended CP, 6-110 PRB, 1 / 2 / 4 ports, 1-4 receive antennas, every PHICH configuration (phich_resources
+ * srslte_phich_r_t 0-3 = 1/6, 1/2, 1, 2; phich_ext = SRSLTE_PHICH_EXT; the PHICH REGs of regs.c:245-367, with mi = 1 on an FDD cell). Refused: cfg.tdd in
+ * srslte_hip_dl_ctrl_create (NULL; a TDD object comes from srslte_hip_dl_ctrl_create_tdd) and MBSFN subframes (SRSLTE_ERROR_INVALID_INPUTS).
+ * TDD cells (srslte_hip_dl_ctrl_create_tdd, uplink-downlink configuration 0-6; the special-subframe configuration is not needed: the control
+ * region lies inside every DwPTS). Per subframe, sf_idx = (tti0 + b) % 10:
+ *   REG lists: those of srslte_regs_init_opts(cell, mi, sf1_6) with mi of 36.213 Table 6.9-1 (mi_tdd_table, ue_dl.c:49-55) and sf1_6 set in
+ *     subframes 1 and 6 of an extended-PHICH cell - the regs[MI_IDX(sf_idx)] srslte_ue_dl's set_mi_value picks (ue_dl.c:57-62, :315-332).
+ *     With mi = 0 the PDCCH has every REG but the PCFICH's; the PCFICH REGs are the same everywhere. One list set per variant in use is
+ *     built when the object is made; the kernels pick the subframe's from a ten-entry table.
+ *   Sizes: the LLR row stride and the PDCCH scrambling length are those of the largest list, mi = 0 at CFI 3 (ue_dl.c:197-226).
+ *   Uplink subframes (36.211 Table 4.2-2): nothing of the grid is read; cfi 0, cfi_corr 0, nof_dci 0, nof_ul_dci 0, messages with nof_bits 0.
+ *   Subframes 1 and 6: a decoded CFI of 3 becomes 2 before the PDCCH is read (ue_dl.c:351-354), in every configuration; cfi_corr stays the
+ *     decoder's. A given cfi of 3 there is refused (36.211 Table 6.7-1; a deliberate narrowing). On a cell of at most 10 PRB a cfi of 2 is
+ *     three symbols and its REGs reach the PSS on symbol 2: it is served as the reference serves it, and the caller picks 1 there.
+ *   DCI sizes: srslte_dci_format_sizeof of a TDD cell (the DAI / UL index and the fourth HARQ process bit, dci.c:38-40, :142-143, :176-189);
+ *     formats 0 and 1A still share one size; search order and ue_dci_formats as in FDD.
+ *   PHICH: ngroup, nseq from srslte_phich_calc unchanged; a request whose ngroup is not below mi ngroups_m1 (x 2, extended CP) of its
+ *     subframe is refused - every request in an mi = 0 or uplink subframe, and I_phich = 1 outside the mi = 2 subframes of configuration 0.
+ *   A deliberate difference: where the cell is too small the reference lets two mapping units share a REG (6 PRB, Ng = 2, mi = 2: units 0
+ *     and 2). The device adds PHICHs in parallel, so srslte_hip_dl_ctrl_create_tdd / _tx_create_tdd return NULL for a cell and configuration
+ *     where any variant in use has such a REG; srslte_hip_dl_ctrl_phich_ngroups_tdd returns SRSLTE_ERROR for it.
+ *   A second refusal of both creators, with the same error return of that helper: a variant in use whose PHICH leaves fewer than nine REGs to a
+ *     CFI-1 region, so that it has no CCE (25 PRB, Ng = 2, configuration 0: mi = 2 takes 42 of the 46 REGs of symbol 0). The reference's
+ *     srslte_regs_pdcch_ncce answers -1 there.
  * The MIB: srslte_hip_dl_ctrl_mib_batch ("DL broadcast" below).
  * UL DCIs and the PHICH: srslte_hip_dl_ctrl_batch_ul / srslte_hip_dl_ctrl_phich_batch below.
  * Not here: carrier indicator / carrier
@@ -726,7 +747,7 @@ typedef struct {
   int      cp_ext;          /* srslte_cell_t.cp == SRSLTE_CP_EXT */
   int      phich_resources; /* srslte_phich_r_t */
   int      phich_ext;       /* srslte_cell_t.phich_length == SRSLTE_PHICH_EXT */
-  int      tdd;             /* srslte_cell_t.frame_type == SRSLTE_TDD: refused */
+  int      tdd;             /* srslte_cell_t.frame_type == SRSLTE_TDD: 0 for srslte_hip_dl_ctrl_create, 1 for srslte_hip_dl_ctrl_create_tdd */
   uint32_t nof_rx_antennas; /* 1-4 */
   uint32_t max_batch;       /* subframes per call */
 } srslte_hip_dl_ctrl_cfg_t;
@@ -757,6 +778,8 @@ typedef struct {            /* one searched candidate (srslte_hip_dl_ctrl_debug_
 } srslte_hip_dl_ctrl_cand_t;
 #define SRSLTE_HIP_DL_CTRL_MAX_CAND 38 /* 16 UE-specific x 2 formats + 6 common */
 srslte_hip_dl_ctrl_t* srslte_hip_dl_ctrl_create(const srslte_hip_dl_ctrl_cfg_t* cfg);
+/* a TDD cell: cfg->tdd must be 1, tdd_sf_config 0-6 (srslte_tdd_config_t.sf_config); every call below works on the object unchanged */
+srslte_hip_dl_ctrl_t* srslte_hip_dl_ctrl_create_tdd(const srslte_hip_dl_ctrl_cfg_t* cfg, uint32_t tdd_sf_config);
 void                  srslte_hip_dl_ctrl_destroy(srslte_hip_dl_ctrl_t* q);
 /* d_grid [nof_sf][nof_rx][nsym][12 nof_prb] (nsym 14 / 12), d_ce [nof_sf][nof_ports][nof_rx][nsym][12 nof_prb], d_res [nof_sf]
  * srslte_hip_chest_dl_res_t; subframe b is TTI tti0 + b and is searched with reqs[b]. d_out [nof_sf] and d_msg [nof_sf] (subframes without
@@ -777,6 +800,13 @@ uint32_t srslte_hip_pdcch_ue_locations_ncce(uint32_t nof_cce, uint32_t* loc, uin
 uint32_t srslte_hip_pdcch_common_locations_ncce(uint32_t nof_cce, uint32_t* loc, uint32_t max_candidates);
 /* srslte_dci_format_sizeof of an FDD cell with a zero srslte_dci_cfg_t, format srslte_dci_format_t 0-8 (0 1 1A 1C 1B 1D 2 2A 2B); 0 otherwise */
 uint32_t srslte_hip_dci_format_sizeof(uint32_t nof_prb, uint32_t nof_ports, int format);
+/* TDD twins. srslte_hip_dl_ctrl_tdd_mi: mi of 36.213 Table 6.9-1 for subframe sf_idx of configuration tdd_sf_config, < 0 for an uplink
+ * subframe or an invalid configuration / subframe. srslte_hip_dl_ctrl_pdcch_re_tdd: the PDCCH RE list of that subframe (cfg->tdd is not
+ * looked at); < 0 also for an uplink subframe. srslte_hip_dci_format_sizeof_tdd: the sizes of a TDD cell (only the frame type enters them) */
+int      srslte_hip_dl_ctrl_tdd_mi(uint32_t tdd_sf_config, uint32_t sf_idx);
+int      srslte_hip_dl_ctrl_pdcch_re_tdd(const srslte_hip_dl_ctrl_cfg_t* cfg, uint32_t tdd_sf_config, uint32_t sf_idx, uint32_t cfi, uint32_t* re,
+                                         uint32_t max);
+uint32_t srslte_hip_dci_format_sizeof_tdd(uint32_t nof_prb, uint32_t nof_ports, int format);
 
 /* ------------------------------------------------------------------ DL control region receive: UL DCIs and PHICH (UE side). What
  * srslte_ue_dl_find_ul_dci (ue_dl.c:480-531, with the pending-UL-DCI rule of dci_blind_search :448-470) and srslte_ue_dl_decode_phich
@@ -808,7 +838,9 @@ uint32_t srslte_hip_dci_format_sizeof(uint32_t nof_prb, uint32_t nof_ports, int 
  * beyond max_batch, MBSFN, tm > 3, cfi > 3), nof_phich beyond the capacity, a request's sf >= nof_sf, I_phich > 1, a resulting ngroup >=
  * srslte_regs_phich_ngroups (I_phich 1 names a group only on an extended-CP cell; phich.c:215-218. nseq is within the CP's sequence count by
  * srslte_phich_calc's own modulo, so the check of phich.c:204-214 has nothing to refuse).
- * Not here: TDD (mi factors, I_phich by UL / DL configuration), MBSFN subframes, carrier indicator / cross-carrier UL DCIs, TPC formats
+ * TDD objects (srslte_hip_dl_ctrl_create_tdd): see "TDD cells" above - the group check is the subframe's own, and requests naming an
+ * uplink subframe are refused; a cfi of 3 given for subframe 1 or 6 is refused.
+ * Not here: a manual mi (mi_manual of srslte_ue_dl), MBSFN subframes, carrier indicator / cross-carrier UL DCIs, TPC formats
  * 3 / 3A, the DCI -> grant unpacking (srslte_dci_msg_unpack_pusch + srslte_ra_ul_dci_to_grant stay with the caller), several UEs searching
  * one subframe's LLR row in one call, PHICH / UL DCIs in the fixed-grant srslte_hip_dl_rx_batch, and the single-subframe drop-in's phich.c,
  * which remains the reference's. */
@@ -862,14 +894,19 @@ const void* srslte_hip_dl_ctrl_phich_debug_buffer(const srslte_hip_dl_ctrl_t* q)
  * Refused with SRSLTE_ERROR_INVALID_INPUTS before anything is queued: a cfi outside 1-3, an entry's sf >= nof_sf, nof_sf > max_batch, L > 3,
  * ncce + 2^L > NOF_CCE(cfi), nof_bits 0 or >= SRSLTE_DCI_MAX_BITS - 16 (pdcch.c:572-573), two DCIs of one subframe on a common CCE (the
  * reference would silently overwrite: a deliberate difference), a PHICH group >= srslte_regs_phich_ngroups, ack > 1, more than max_dci DCIs or
- * max_phich PHICHs. TDD cells are refused by create (NULL).
- * Not here: control in the fixed-grant srslte_hip_dl_tx_batch, TDD (the PHICH mi factor, special
- * subframes) and MBSFN subframes, DCI packing (srslte_dci_msg_pack_pdsch / _pusch stay with the caller), carrier indicator, and the
+ * max_phich PHICHs. cfg.tdd is refused by srslte_hip_dl_ctrl_tx_create (NULL).
+ * TDD cells (srslte_hip_dl_ctrl_tx_create_tdd; "TDD cells" of the receive side above has the REG variants, the group check and the shared-REG
+ * refusal): each subframe is written over its own variant's lists, and every PHICH REG of that variant is set to zero first. An uplink
+ * subframe is not written at all and in->cfi[b] is not looked at there. Refused besides the above: a DCI or PHICH naming an uplink subframe,
+ * a PHICH group not below mi ngroups_m1 (x 2, extended CP) of its subframe, and cfi 3 in subframes 1 and 6 (36.211 Table 6.7-1; the
+ * reference's eNB has no TDD, so this is this library's narrowing). The grids are bit-identical to srslte_pcfich_encode +
+ * srslte_phich_encode + srslte_pdcch_encode over the subframe's own srslte_regs_t.
+ * Not here: control in the fixed-grant srslte_hip_dl_tx_batch, MBSFN subframes, DCI packing (srslte_dci_msg_pack_pdsch / _pusch stay with the caller), carrier indicator, and the
  * single-subframe drop-in's pcfich.c / pdcch.c / phich.c, which remain the reference's. */
 typedef struct srslte_hip_dl_ctrl_tx srslte_hip_dl_ctrl_tx_t;
 typedef struct {
   uint32_t nof_prb, nof_ports, cell_id;
-  int      cp_ext, phich_resources, phich_ext, tdd; /* as srslte_hip_dl_ctrl_cfg_t; tdd: refused */
+  int      cp_ext, phich_resources, phich_ext, tdd; /* as srslte_hip_dl_ctrl_cfg_t; tdd: 0 for _tx_create, 1 for _tx_create_tdd */
   uint32_t max_batch;       /* subframes per call */
   uint32_t max_dci;         /* DCIs per call */
   uint32_t max_phich;       /* PHICHs per call */
@@ -890,12 +927,15 @@ typedef struct {
   uint32_t                           nof_phich;
 } srslte_hip_dl_ctrl_tx_in_t;
 srslte_hip_dl_ctrl_tx_t* srslte_hip_dl_ctrl_tx_create(const srslte_hip_dl_ctrl_tx_cfg_t* cfg);
+/* a TDD cell: cfg->tdd must be 1, tdd_sf_config 0-6; every call below works on the object unchanged */
+srslte_hip_dl_ctrl_tx_t* srslte_hip_dl_ctrl_tx_create_tdd(const srslte_hip_dl_ctrl_tx_cfg_t* cfg, uint32_t tdd_sf_config);
 void                     srslte_hip_dl_ctrl_tx_destroy(srslte_hip_dl_ctrl_tx_t* q);
 int srslte_hip_dl_ctrl_tx_put(srslte_hip_dl_ctrl_tx_t* q, uint32_t tti0, uint32_t nof_sf, const srslte_hip_dl_ctrl_tx_in_t* in, void* d_grid, void* stream);
 /* srslte_hip_dl_tx_batch_grants with srslte_hip_dl_ctrl_tx_put on its grids between the PDSCH mapping and the OFDM modulation: one complete
  * subframe per TTI apart from PSS / SSS / PBCH (srslte_hip_dl_tx_batch_grants_full below adds them). Refused (SRSLTE_ERROR_INVALID_INPUTS) besides what either call refuses: a ctrl object of
- * another cell (nof_prb, ports - a pipeline's nof_ports 0 is 1 -, cell_id, cp_ext), a TDD or MBSFN pipeline, a grant whose cfi differs from
- * in->cfi[grant.sf]. */
+ * another cell (nof_prb, ports - a pipeline's nof_ports 0 is 1 -, cell_id, cp_ext), an MBSFN pipeline, a grant whose cfi differs from
+ * in->cfi[grant.sf] (not compared for a grant in an uplink subframe of a TDD object, where in->cfi is not looked at), and a pipeline and control object of different frame types or uplink-downlink configurations (a TDD pipeline takes a
+ * control object of srslte_hip_dl_ctrl_tx_create_tdd with its tdd_sf_config). */
 int srslte_hip_dl_tx_batch_grants_ctrl(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
                                        const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
                                        const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream);
@@ -906,11 +946,19 @@ int srslte_hip_dl_ctrl_phich_ngroups(const srslte_hip_dl_ctrl_tx_cfg_t* cfg);
 int srslte_hip_phich_calc(const srslte_hip_dl_ctrl_tx_cfg_t* cfg, uint32_t n_prb_lowest, uint32_t n_dmrs, uint32_t I_phich, uint32_t* ngroup,
                           uint32_t* nseq);
 int srslte_hip_dl_ctrl_phich_re(const srslte_hip_dl_ctrl_tx_cfg_t* cfg, uint32_t ngroup, uint32_t* re, uint32_t max);
+/* TDD twins for subframe sf_idx of configuration tdd_sf_config (cfg->tdd is not looked at): the groups are mi srslte_regs_phich_ngroups_m1
+ * (x 2, extended CP), 0 with mi = 0. < 0 for an uplink subframe; srslte_hip_dl_ctrl_phich_ngroups_tdd also returns SRSLTE_ERROR for a cell
+ * and configuration the creators refuse: two mapping units of a variant share a REG, or a variant has no CCE at CFI 1 */
+int srslte_hip_dl_ctrl_phich_ngroups_tdd(const srslte_hip_dl_ctrl_tx_cfg_t* cfg, uint32_t tdd_sf_config, uint32_t sf_idx);
+int srslte_hip_dl_ctrl_phich_re_tdd(const srslte_hip_dl_ctrl_tx_cfg_t* cfg, uint32_t tdd_sf_config, uint32_t sf_idx, uint32_t ngroup, uint32_t* re,
+                                    uint32_t max);
 
 /* ------------------------------------------------------------------ DL broadcast: PSS, SSS and PBCH of a batch of subframes (eNB side) and
  * the MIB of every subframe 0 of a batch (UE side), on the control objects above, one launch each on the caller's stream, no host
- * synchronisation and no per-call descriptors (the MIB depends only on the cell and the TTI). FDD only: TDD cells are refused when the
- * objects are made.
+ * synchronisation and no per-call descriptors (the MIB depends only on the cell and the TTI). On a TDD object (the _create_tdd calls) the
+ * PBCH and the MIB are where they are in FDD; the SSS goes on the last symbol of slot 1 of subframes 0 and 5 (signal0 / signal5) and the PSS
+ * on symbol 2 of subframes 1 and 6, each with its five zero guards - the positions the PDSCH pipelines skip (srslte_hip_dl_rx_cfg_t.tdd) and
+ * sync.c:732-809 searches.
  * srslte_hip_dl_ctrl_tx_put_bcast writes what put_sync and put_mib of srslte_enb_dl_put_base write (enb_dl.c:297-307, :324-335), on every port
  * of d_grid [nof_sf][nof_ports][nsym][12 nof_prb] cf32, subframe b being TTI t = tti0 + b, and touches nothing else:
  *   t % 10 in {0, 5}: the PSS (srslte_pss_generate of cell_id % 3, built on the host with the reference's expression) in the last symbol of
@@ -930,13 +978,12 @@ int srslte_hip_dl_ctrl_phich_re(const srslte_hip_dl_ctrl_tx_cfg_t* cfg, uint32_t
  * nant mask, which rejects an all-zero payload (pbch.c:373-391). The first hit in (nant, dst) order wins. Stateless: each subframe 0 of a
  * batch is decoded on its own. d_mib [nof_sf] may be device-visible pinned host memory. Buffers are allocated by srslte_hip_dl_ctrl_create.
  * Refused with SRSLTE_ERROR_INVALID_INPUTS: null pointers, nof_sf > max_batch.
- * Not here: soft combining across calls (the reference's frame_idx window and memmove), cell search (PSS / SSS detection: srslte_hip_sync_find_batch below), TDD positions of
- * PSS / SSS, broadcast in the fixed-grant srslte_hip_dl_tx_batch, and the single-subframe drop-in's pbch.c / pss.c / sss.c, which remain
+ * Not here: soft combining across calls (the reference's frame_idx window and memmove), cell search (PSS / SSS detection: srslte_hip_sync_find_batch below), broadcast in the fixed-grant srslte_hip_dl_tx_batch, and the single-subframe drop-in's pbch.c / pss.c / sss.c, which remain
  * the reference's. */
 int srslte_hip_dl_ctrl_tx_put_bcast(srslte_hip_dl_ctrl_tx_t* q, uint32_t tti0, uint32_t nof_sf, void* d_grid, void* stream);
 /* srslte_hip_dl_tx_batch_grants_ctrl with srslte_hip_dl_ctrl_tx_put_bcast on its grids after the CRS and before the PDSCHs, as the reference
  * writes sync and MIB before srslte_enb_dl_put_pdsch (a PDSCH RE wins where the two meet): srslte_enb_dl_put_base + _put_phich +
- * _put_pdcch_dl / _ul + _put_pdsch + srslte_enb_dl_gen_signal, a complete FDD subframe per TTI. Refused as srslte_hip_dl_tx_batch_grants_ctrl. */
+ * _put_pdcch_dl / _ul + _put_pdsch + srslte_enb_dl_gen_signal, a complete subframe per TTI, FDD or TDD. Refused as srslte_hip_dl_tx_batch_grants_ctrl. */
 int srslte_hip_dl_tx_batch_grants_full(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf,
                                        const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
                                        const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream);

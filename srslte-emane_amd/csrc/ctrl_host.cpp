@@ -19,9 +19,11 @@ bool ctrl_cell_ok(const srslte_hip_dl_ctrl_cfg_t* c)
          c->phich_resources >= 0 && c->phich_resources <= 3;
 }
 
-int ctrl_build_regs(const srslte_hip_dl_ctrl_cfg_t* c, CtrlRegs& out)
+int ctrl_build_regs(const srslte_hip_dl_ctrl_cfg_t* c, CtrlRegs& out) { return ctrl_build_regs_opts(c, 1, false, out); }
+
+int ctrl_build_regs_opts(const srslte_hip_dl_ctrl_cfg_t* c, uint32_t phich_mi, bool sf1_6, CtrlRegs& out)
 {
-  if (!ctrl_cell_ok(c)) return SRSLTE_ERROR_INVALID_INPUTS;
+  if (!ctrl_cell_ok(c) || phich_mi > 2) return SRSLTE_ERROR_INVALID_INPUTS;
   const uint32_t prb = c->nof_prb, id = c->cell_id, max_ctrl = prb <= 10 ? 4 : 3, vo = id % 3;
   uint32_t       n[4];
   for (uint32_t i = 0; i < max_ctrl; i++) n[i] = i == 0 ? 2 : i == 1 ? (c->nof_ports == 4 ? 2 : 3) : i == 2 ? 3 : (c->cp_ext ? 2 : 3);
@@ -64,18 +66,23 @@ int ctrl_build_regs(const srslte_hip_dl_ctrl_cfg_t* c, CtrlRegs& out)
     f->assigned = true;
     for (uint32_t t = 0; t < 4; t++) out.pcfich.push_back(re_of(*f, t));
   }
-  // PHICH: mapping unit mi takes REG q = 0, 1, 2 in this order (regs.c:320-340)
+  // PHICH: mapping unit mi takes REG q = 0, 1, 2 in this order (regs.c:320-340); with an extended PHICH in subframes 1 and 6 of a TDD cell
+  // the REGs alternate between symbols 0 and 1 and the cell offset is scaled by symbol 1's count (regs.c:325-335)
   const float    ng[4]   = {(float)1 / 6, (float)1 / 2, 1.0f, 2.0f};
   const uint32_t ngroups = (uint32_t)(int)ceilf(ng[c->phich_resources] * ((float)prb / 8));
   std::vector<Reg*> ph[3];
   for (auto& r : regs)
     if (r.l < 3 && !r.assigned) ph[r.l].push_back(&r);
+  const bool two_sym = c->phich_ext && sf1_6;
   out.ngroups_m1 = ngroups;
+  out.units      = phich_mi * ngroups;
+  out.shared     = false;
   out.phich.clear();
-  for (uint32_t mi = 0; mi < ngroups; mi++) {
+  for (uint32_t mi = 0; mi < out.units; mi++) {
     for (uint32_t q = 0; q < 3; q++) {
-      const uint32_t li = c->phich_ext ? q : 0, nl = (uint32_t)ph[li].size();
-      const uint32_t ni = ((id * nl / (uint32_t)ph[0].size()) + mi + q * nl / 3) % nl;
+      const uint32_t li = !c->phich_ext ? 0 : two_sym ? (mi / 2 + q + 1) % 2 : q, nl = (uint32_t)ph[li].size();
+      const uint32_t ni = ((id * nl / (uint32_t)ph[two_sym ? 1 : 0].size()) + mi + q * nl / 3) % nl;
+      if (ph[li][ni]->assigned) out.shared = true;
       ph[li][ni]->assigned = true;
       for (uint32_t t = 0; t < 4; t++) out.phich.push_back(re_of(*ph[li][ni], t));
     }
@@ -106,6 +113,57 @@ int ctrl_build_regs(const srslte_hip_dl_ctrl_cfg_t* c, CtrlRegs& out)
       for (uint32_t t = 0; t < 4; t++) out.pdcch[cfi].push_back(re_of(*perm[r], t));
   }
   return SRSLTE_SUCCESS;
+}
+
+int ctrl_tdd_mi(uint32_t tdd_sf_config, uint32_t sf_idx)
+{
+  // 36.213 Table 6.9-1 on the downlink and special subframes of 36.211 Table 4.2-2; -1: uplink
+  static const int8_t MI[7][10] = {{2, 1, -1, -1, -1, 2, 1, -1, -1, -1}, {0, 1, -1, -1, 1, 0, 1, -1, -1, 1}, {0, 0, -1, 1, 0, 0, 0, -1, 1, 0},
+                                   {1, 0, -1, -1, -1, 0, 0, 0, 1, 1},   {0, 0, -1, -1, 0, 0, 0, 0, 1, 1},   {0, 0, -1, 0, 0, 0, 0, 0, 1, 0},
+                                   {1, 1, -1, -1, -1, 1, 1, -1, -1, 1}};
+  return tdd_sf_config <= 6 && sf_idx < 10 ? MI[tdd_sf_config][sf_idx] : -1;
+}
+
+int ctrl_build_regs_set(const srslte_hip_dl_ctrl_cfg_t* c, int tdd_sf_config, CtrlRegsSet& s)
+{
+  if (!ctrl_cell_ok(c) || tdd_sf_config > 6) return SRSLTE_ERROR_INVALID_INPUTS;
+  s.v.clear();
+  if (tdd_sf_config < 0) {
+    s.v.resize(1);
+    memset(s.var, 0, sizeof(s.var));
+    const int r    = ctrl_build_regs(c, s.v[0]);
+    s.max_pdcch_re = (uint32_t)s.v[0].pdcch[2].size();
+    return r;
+  }
+  CtrlRegs mi0;
+  if (int r = ctrl_build_regs_opts(c, 0, false, mi0)) return r;
+  s.max_pdcch_re = (uint32_t)mi0.pdcch[2].size();
+  int key[CTRL_MAX_VAR];
+  for (uint32_t sf = 0; sf < 10; sf++) {
+    const int mi = ctrl_tdd_mi((uint32_t)tdd_sf_config, sf);
+    s.var[sf]    = CTRL_SF_UL;
+    if (mi < 0) continue;
+    // without PHICH REGs (mi = 0) or with a normal PHICH the rule of subframes 1 and 6 changes nothing: one variant serves both
+    const int k = mi | ((mi > 0 && c->phich_ext && (sf == 1 || sf == 6)) ? 4 : 0);
+    size_t    i = 0;
+    while (i < s.v.size() && key[i] != k) i++;
+    if (i == s.v.size()) {
+      if (i == (size_t)CTRL_MAX_VAR) return SRSLTE_ERROR;
+      key[i] = k;
+      s.v.emplace_back();
+      if (int r = ctrl_build_regs_opts(c, (uint32_t)mi, (k & 4) != 0, s.v.back())) return r;
+      if (s.v.back().shared || s.v.back().pdcch[0].size() < 36) return SRSLTE_ERROR;
+    }
+    s.var[sf] = (uint8_t)i;
+  }
+  return SRSLTE_SUCCESS;
+}
+
+uint32_t CtrlRegsSet::max_units() const
+{
+  uint32_t m = 0;
+  for (const CtrlRegs& r : v) m = r.units > m ? r.units : m;
+  return m;
 }
 
 void ctrl_scrambling(uint32_t cell_id, uint32_t pdcch_bits, std::vector<uint32_t>& scr, int* scr_words)

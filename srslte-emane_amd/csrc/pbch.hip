@@ -30,7 +30,10 @@ struct BcastGeom {
   const uint32_t* re;   // [nof_bits / 2] the PBCH REs of one port's subframe grid, srslte_pbch_put order
   const uint32_t* scr;  // srslte_sequence_pbch, 4 nof_bits bits
   const float*    sync; // [72][2] PSS with its guards, then [2][72] SSS of subframe 0 / 5 (real parts)
+  // first RE of the PSS / SSS with their guards. FDD: both in slot 0 of subframes 0 and 5. TDD: the PSS in symbol 2 of subframes 1 and 6, the
+  // SSS in the last symbol of subframes 0 and 5
   uint32_t        pss_k0, sss_k0;
+  int             tdd;
   int             nof_ports, grid_len, nof_bits;
   uint32_t        mib_head; // bandwidth, PHICH length and resources: the first 6 bits of the MIB
   float           s;        // srslte_precoding_diversity's 1/sqrtf(2) (scaling 1.0f)
@@ -45,14 +48,15 @@ __global__ __launch_bounds__(64) void dl_bcast_tx_kernel(uint32_t tti0, BcastGeo
   __shared__ uint8_t bits[MIB_F], coded[MIB_E], w[MIB_E];
   const int      b = blockIdx.x, lane = threadIdx.x, P = g.nof_ports;
   const uint32_t t = tti0 + (uint32_t)b, sf_idx = t % 10;
-  if (sf_idx != 0 && sf_idx != 5) return;
+  const bool     sss_sf = sf_idx == 0 || sf_idx == 5, pss_sf = g.tdd ? (sf_idx == 1 || sf_idx == 6) : sss_sf;
+  if (!sss_sf && !pss_sf) return;
   cf32* gb = grid + (size_t)b * P * g.grid_len;
   // srslte_pss_put_slot / srslte_sss_put_slot on every port (pss.c:380-386, sss.c:106-119)
   for (int i = lane; i < 72; i += 64) {
     const cf32 pss = make_float2(g.sync[2 * i], g.sync[2 * i + 1]), sss = make_float2(g.sync[144 + (sf_idx ? 72 : 0) + i], 0.f);
     for (int p = 0; p < P; p++) {
-      gb[(size_t)p * g.grid_len + g.pss_k0 + i] = pss;
-      gb[(size_t)p * g.grid_len + g.sss_k0 + i] = sss;
+      if (pss_sf) gb[(size_t)p * g.grid_len + g.pss_k0 + i] = pss;
+      if (sss_sf) gb[(size_t)p * g.grid_len + g.sss_k0 + i] = sss;
     }
   }
   if (sf_idx != 0) return;
@@ -291,6 +295,11 @@ BcastTables* bcast_tables_create(const srslte_hip_dl_ctrl_cfg_t* c, int phich_ex
   BcastGeom& g = t->g;
   g.re = t->tab.get(), g.scr = t->tab.get() + h.pbch_re.size(), g.sync = t->sync.get();
   g.pss_k0 = h.pss_k0, g.sss_k0 = h.sss_k0;
+  g.tdd = c->tdd ? 1 : 0;
+  if (g.tdd) { // the positions sync.c:732-809 searches: PSS on symbol 2 of subframes 1 and 6, SSS on the last symbol of subframes 0 and 5
+    const uint32_t w = 12 * c->nof_prb, nsym = c->cp_ext ? 6 : 7;
+    g.pss_k0 = 2 * w + w / 2 - 36, g.sss_k0 = (2 * nsym - 1) * w + w / 2 - 36;
+  }
   g.nof_ports = (int)c->nof_ports, g.grid_len = (c->cp_ext ? 12 : 14) * 12 * (int)c->nof_prb, g.nof_bits = (int)h.nof_bits;
   g.mib_head = mib_head(c->nof_prb, phich_ext, phich_resources);
   g.s        = 1.0f / sqrtf(2.0f);

@@ -72,7 +72,9 @@ struct CtrlGeom {
   const uint32_t* scr_pcfich; // [10] words: the 32 bits of srslte_sequence_pcfich of each subframe, bit i = bit i
   const uint32_t* scr_pdcch;  // [10][scr_words]
   int             scr_words;
-  int             off[3], n[3]; // PDCCH REs of CFI 1-3 (36 NOF_CCE)
+  int             off[CTRL_MAX_VAR][3], n[CTRL_MAX_VAR][3]; // PDCCH REs of CFI 1-3 (36 NOF_CCE) of each REG variant (ctrl_host.hpp)
+  uint8_t         var[10];      // the variant of subframe sf_idx; CTRL_SF_UL: an uplink subframe of a TDD cell. FDD: all 0
+  int             tdd;
   int             nof_ports, nof_rx, grid_len;
   int             llr_stride;
   uint32_t        dci_bits[NOF_FORMATS];
@@ -94,6 +96,13 @@ __global__ __launch_bounds__(256) void dl_ctrl_llr_kernel(const cf32* __restrict
   const cf32*    y = grid + (size_t)b * R * glen;
   const cf32*    h[4];
   for (int p = 0; p < 4; p++) h[p] = ce + ((size_t)b * P + (p < P ? p : 0)) * R * glen;
+  const int   v = g.var[sf_idx];
+  float*      row = llr + (size_t)b * g.llr_stride;
+  if (v == CTRL_SF_UL) { // nothing of the grid is read: no CFI, no candidates, an empty row
+    for (int i = tid; i < g.llr_stride; i += 256) row[i] = 0.f;
+    if (tid == 0) out[b].cfi = 0, out[b].cfi_corr = 0.f, ncand[b] = 0;
+    return;
+  }
   const float noise = res[(size_t)b * 10]; // srslte_hip_chest_dl_res_t.noise_estimate
   if (tid == 0) {
     // PCFICH: 16 REs, srslte_predecoding_single_multi / diversity_multi take their generic paths at 16 symbols (precoding.c:325-348,:665-683)
@@ -126,14 +135,14 @@ __global__ __launch_bounds__(256) void dl_ctrl_llr_kernel(const cf32* __restrict
     }
     const int cfi_req = (rq >> 20) & 3;
     cfi_s = cfi_req ? cfi_req : index + 1;
+    if (g.tdd && (sf_idx == 1 || sf_idx == 6) && cfi_s == 3) cfi_s = 2; // ue_dl.c:351-354
     out[b].cfi = cfi_s;
     out[b].cfi_corr = max_corr;
   }
   __syncthreads();
-  const int       cfi = cfi_s, n = g.n[cfi - 1], e_bits = 2 * n, ncce = n / 36;
-  const uint32_t* re  = g.re + g.off[cfi - 1];
+  const int       cfi = cfi_s, n = g.n[v][cfi - 1], e_bits = 2 * n, ncce = n / 36;
+  const uint32_t* re  = g.re + g.off[v][cfi - 1];
   const uint32_t* cs  = g.scr_pdcch + (size_t)sf_idx * g.scr_words;
-  float*          row = llr + (size_t)b * g.llr_stride;
   const int       G = P, n16 = 16 * (n / 16);
   for (int q = tid; q < n / G; q += 256) {
     cf32 x[4];
@@ -283,11 +292,13 @@ static bool     ambiguous(uint32_t n)
 }
 static uint32_t type0_P(uint32_t prb) { return prb <= 10 ? 1 : prb <= 26 ? 2 : prb <= 63 ? 3 : 4; } // ra.c:62-72
 
-// srslte_dci_format_sizeof (dci.c:114-360) for FDD, cif / multiple CSI request / SRS request / resource allocation type bit off
-static uint32_t dci_sizeof(uint32_t prb, uint32_t ports, int f)
+// srslte_dci_format_sizeof (dci.c:114-360), cif / multiple CSI request / SRS request / resource allocation type bit off. A TDD cell adds the
+// DAI / UL index (2 bits) and a fourth HARQ process bit (dci.c:38-40, :142-143, :176-189); the uplink-downlink configuration does not enter
+static uint32_t dci_sizeof(uint32_t prb, uint32_t ports, int f, bool tdd = false)
 {
-  const uint32_t f0_ = 1 + 1 + riv_nbits(prb) + 5 + 1 + 2 + 3 + 1;
-  uint32_t       f1a = 1 + 1 + riv_nbits(prb) + 5 + 3 + 1 + 2 + 2;
+  const uint32_t dai = tdd ? 2 : 0, pid = tdd ? 4 : 3;
+  const uint32_t f0_ = 1 + 1 + riv_nbits(prb) + 5 + 1 + 2 + 3 + dai + 1;
+  uint32_t       f1a = 1 + 1 + riv_nbits(prb) + 5 + pid + 1 + 2 + 2 + dai;
   while (f1a < f0_) f1a++;
   if (ambiguous(f1a)) f1a++;
   uint32_t f0 = f0_;
@@ -297,7 +308,7 @@ static uint32_t dci_sizeof(uint32_t prb, uint32_t ports, int f)
     case F0: return f0;
     case F1A: return f1a;
     case F1: {
-      uint32_t n = rbg + 5 + 3 + 1 + 2 + 2;
+      uint32_t n = rbg + 5 + pid + 1 + 2 + 2 + dai;
       while (n == f0 || n == f1a || ambiguous(n)) n++;
       return n;
     }
@@ -309,7 +320,7 @@ static uint32_t dci_sizeof(uint32_t prb, uint32_t ports, int f)
     }
     case F1B:
     case F1D: {
-      uint32_t n = f1a - 1 + (ports <= 2 ? 2 : 4) + 1;
+      uint32_t n = f1a - 1 + (ports <= 2 ? 2 : 4) + 1 + dai;
       while (ambiguous(n)) n++;
       return n;
     }
@@ -317,7 +328,7 @@ static uint32_t dci_sizeof(uint32_t prb, uint32_t ports, int f)
     case F2A:
     case F2B: {
       const uint32_t pre = f == F2 ? (ports <= 2 ? 3 : 6) : f == F2A ? (ports <= 2 ? 0 : 2) : 0;
-      uint32_t       n   = rbg + 2 + 3 + 1 + 2 * (5 + 1 + 2) + pre;
+      uint32_t       n   = rbg + 2 + pid + 1 + 2 * (5 + 1 + 2) + pre + dai;
       while (ambiguous(n)) n++;
       return n;
     }
@@ -333,21 +344,25 @@ struct srslte_hip_dl_ctrl {
   DevBuf<uint32_t>         re, scr, ncand;
   DevBuf<float>            llr;
   DevBuf<srslte_hip_dl_ctrl_cand_t> cand;
+  int                      tdd_sf_config = -1; // uplink-downlink configuration of a TDD object; -1: FDD
   BcastTables*             bc = nullptr; // the MIB decoder (pbch.hip)
   PhichRx*                 ph = nullptr; // the PHICH receiver (phich.hip), once srslte_hip_dl_ctrl_set_max_phich has made it
 };
 
 const BcastTables* dl_ctrl_bcast(const srslte_hip_dl_ctrl_t* q) { return q ? q->bc : nullptr; }
 
-DlCtrlView dl_ctrl_view(srslte_hip_dl_ctrl_t* q) { return DlCtrlView{&q->cfg, q->g.scr_pcfich, q->cand.get(), q->ncand.get()}; }
+DlCtrlView dl_ctrl_view(srslte_hip_dl_ctrl_t* q) { return DlCtrlView{&q->cfg, q->tdd_sf_config, q->g.scr_pcfich, q->cand.get(), q->ncand.get()}; }
 PhichRx*   dl_ctrl_phich(const srslte_hip_dl_ctrl_t* q) { return q->ph; }
 void       dl_ctrl_set_phich(srslte_hip_dl_ctrl_t* q, PhichRx* t) { q->ph = t; }
 
-int dl_ctrl_check(const srslte_hip_dl_ctrl_t* q, uint32_t nof_sf, const srslte_hip_dl_ctrl_req_t* reqs)
+int dl_ctrl_check(const srslte_hip_dl_ctrl_t* q, uint32_t tti0, uint32_t nof_sf, const srslte_hip_dl_ctrl_req_t* reqs)
 {
   if (!q || !reqs || nof_sf < 1 || nof_sf > q->cfg.max_batch) return SRSLTE_ERROR_INVALID_INPUTS;
   for (uint32_t b = 0; b < nof_sf; b++) {
     if (reqs[b].mbsfn || reqs[b].tm > 3 || reqs[b].cfi > 3) return SRSLTE_ERROR_INVALID_INPUTS;
+    // TDD: subframes 1 and 6 hold at most two control symbols (36.211 Table 6.7-1)
+    const uint32_t sf_idx = (tti0 + b) % 10;
+    if (q->cfg.tdd && reqs[b].cfi == 3 && (sf_idx == 1 || sf_idx == 6)) return SRSLTE_ERROR_INVALID_INPUTS;
   }
   return SRSLTE_SUCCESS;
 }
@@ -392,6 +407,27 @@ uint32_t srslte_hip_dci_format_sizeof(uint32_t nof_prb, uint32_t nof_ports, int 
   return dci_sizeof(nof_prb, nof_ports, format);
 }
 
+uint32_t srslte_hip_dci_format_sizeof_tdd(uint32_t nof_prb, uint32_t nof_ports, int format)
+{
+  if (nof_prb < 6 || nof_prb > 110) return 0;
+  return dci_sizeof(nof_prb, nof_ports, format, true);
+}
+
+int srslte_hip_dl_ctrl_tdd_mi(uint32_t tdd_sf_config, uint32_t sf_idx) { return ctrl_tdd_mi(tdd_sf_config, sf_idx); }
+
+int srslte_hip_dl_ctrl_pdcch_re_tdd(const srslte_hip_dl_ctrl_cfg_t* cfg, uint32_t tdd_sf_config, uint32_t sf_idx, uint32_t cfi, uint32_t* re, uint32_t max)
+{
+  const int mi = ctrl_tdd_mi(tdd_sf_config, sf_idx);
+  if (cfi < 1 || cfi > 3 || mi < 0 || !cfg) return SRSLTE_ERROR_INVALID_INPUTS;
+  CtrlRegs  r;
+  const int rc = ctrl_build_regs_opts(cfg, (uint32_t)mi, sf_idx == 1 || sf_idx == 6, r);
+  if (rc != SRSLTE_SUCCESS) return rc;
+  const std::vector<uint32_t>& v = r.pdcch[cfi - 1];
+  if (!re || max < v.size()) return SRSLTE_ERROR_INVALID_INPUTS;
+  memcpy(re, v.data(), v.size() * 4);
+  return (int)v.size();
+}
+
 void srslte_hip_dl_ctrl_destroy(srslte_hip_dl_ctrl_t* q)
 {
   if (!q) return;
@@ -400,32 +436,42 @@ void srslte_hip_dl_ctrl_destroy(srslte_hip_dl_ctrl_t* q)
   delete q;
 }
 
-srslte_hip_dl_ctrl_t* srslte_hip_dl_ctrl_create(const srslte_hip_dl_ctrl_cfg_t* cfg)
+// tdd_sf_config < 0: FDD
+static srslte_hip_dl_ctrl_t* dl_ctrl_make(const srslte_hip_dl_ctrl_cfg_t* cfg, int tdd_sf_config)
 {
-  if (!ctrl_cell_ok(cfg) || cfg->tdd || cfg->nof_rx_antennas < 1 || cfg->nof_rx_antennas > 4 || cfg->max_batch < 1) return nullptr;
-  CtrlRegs regs;
-  if (ctrl_build_regs(cfg, regs) != SRSLTE_SUCCESS) return nullptr;
-  const std::vector<uint32_t>&pc = regs.pcfich, *pd = regs.pdcch;
+  if (!ctrl_cell_ok(cfg) || cfg->nof_rx_antennas < 1 || cfg->nof_rx_antennas > 4 || cfg->max_batch < 1) return nullptr;
+  CtrlRegsSet set;
+  if (ctrl_build_regs_set(cfg, tdd_sf_config, set) != SRSLTE_SUCCESS) return nullptr;
   srslte_hip_dl_ctrl_t* q = new srslte_hip_dl_ctrl_t();
   q->cfg                  = *cfg;
+  q->tdd_sf_config        = tdd_sf_config;
   CtrlGeom& g             = q->g;
-  std::vector<uint32_t> re(pc);
-  for (int c = 0; c < 3; c++) {
-    g.off[c] = (int)re.size(), g.n[c] = (int)pd[c].size();
-    re.insert(re.end(), pd[c].begin(), pd[c].end());
+  memset(&g, 0, sizeof(g));
+  std::vector<uint32_t> re(set.v[0].pcfich); // the PCFICH REGs are the same in every variant
+  bool                  cce = true;
+  for (size_t v = 0; v < set.v.size(); v++) {
+    for (int c = 0; c < 3; c++) {
+      const std::vector<uint32_t>& pd = set.v[v].pdcch[c];
+      g.off[v][c] = (int)re.size(), g.n[v][c] = (int)pd.size();
+      re.insert(re.end(), pd.begin(), pd.end());
+    }
+    cce = cce && g.n[v][0] >= 36;
   }
+  memcpy(g.var, set.var, sizeof(g.var));
+  g.tdd        = tdd_sf_config >= 0 ? 1 : 0;
   g.nof_ports  = (int)cfg->nof_ports;
   g.nof_rx     = (int)cfg->nof_rx_antennas;
   g.grid_len   = (cfg->cp_ext ? 12 : 14) * 12 * (int)cfg->nof_prb;
-  g.llr_stride = (2 * g.n[2] + 3) & ~3; // 72 NOF_CCE(3)
-  for (int f = 0; f < NOF_FORMATS; f++) g.dci_bits[f] = dci_sizeof(cfg->nof_prb, cfg->nof_ports, f);
-  if (g.dci_bits[F2] + 16 > MAX_F || g.n[0] < 36) { // every cell of the range fits; a CFI-1 region without a CCE does not happen either
+  g.llr_stride = (2 * (int)set.max_pdcch_re + 3) & ~3; // 72 NOF_CCE(3) of the largest list
+  for (int f = 0; f < NOF_FORMATS; f++) g.dci_bits[f] = dci_sizeof(cfg->nof_prb, cfg->nof_ports, f, g.tdd != 0);
+  if (g.dci_bits[F2] + 16 > MAX_F || !cce) { // every cell of the range fits; an FDD CFI-1 region without a CCE does not happen, and
+                                               // ctrl_build_regs_set has refused the TDD cells where one does
     delete q;
     return nullptr;
   }
-  // scrambling: srslte_sequence_pcfich (32 bits) and srslte_sequence_pdcch sized 8 srslte_regs_pdcch_nregs(3) = 2 n[2] bits, slot 2 sf_idx
+  // scrambling: srslte_sequence_pcfich (32 bits) and srslte_sequence_pdcch sized 8 srslte_regs_pdcch_nregs(3) bits of the largest list, slot 2 sf_idx
   std::vector<uint32_t> scr;
-  ctrl_scrambling(cfg->cell_id, 2 * g.n[2], scr, &g.scr_words);
+  ctrl_scrambling(cfg->cell_id, 2 * set.max_pdcch_re, scr, &g.scr_words);
   const size_t B = cfg->max_batch;
   if (q->re.upload(re) || q->scr.upload(scr) || q->llr.alloc(B * g.llr_stride) || q->cand.alloc(B * MAX_CAND) || q->ncand.alloc(B) ||
       !(q->bc = bcast_tables_create(cfg, cfg->phich_ext, cfg->phich_resources, true))) {
@@ -437,11 +483,18 @@ srslte_hip_dl_ctrl_t* srslte_hip_dl_ctrl_create(const srslte_hip_dl_ctrl_cfg_t* 
   return q;
 }
 
+srslte_hip_dl_ctrl_t* srslte_hip_dl_ctrl_create(const srslte_hip_dl_ctrl_cfg_t* cfg) { return cfg && !cfg->tdd ? dl_ctrl_make(cfg, -1) : nullptr; }
+
+srslte_hip_dl_ctrl_t* srslte_hip_dl_ctrl_create_tdd(const srslte_hip_dl_ctrl_cfg_t* cfg, uint32_t tdd_sf_config)
+{
+  return cfg && cfg->tdd == 1 && tdd_sf_config <= 6 ? dl_ctrl_make(cfg, (int)tdd_sf_config) : nullptr;
+}
+
 int srslte_hip_dl_ctrl_batch(srslte_hip_dl_ctrl_t* q, const void* d_grid, const void* d_ce, const void* d_res, uint32_t tti0, uint32_t nof_sf,
                              const srslte_hip_dl_ctrl_req_t* reqs, srslte_hip_dl_ctrl_res_t* d_out, srslte_hip_dci_msg_t* d_msg, void* stream)
 {
   if (!d_grid || !d_ce || !d_res || !d_out || !d_msg) return SRSLTE_ERROR_INVALID_INPUTS;
-  if (int r = dl_ctrl_check(q, nof_sf, reqs)) return r;
+  if (int r = dl_ctrl_check(q, tti0, nof_sf, reqs)) return r;
   hipStream_t st = (hipStream_t)stream;
   for (uint32_t s0 = 0; s0 < nof_sf; s0 += REQ_CHUNK) {
     const uint32_t n = nof_sf - s0 < (uint32_t)REQ_CHUNK ? nof_sf - s0 : (uint32_t)REQ_CHUNK;

@@ -22,12 +22,14 @@ namespace {
 constexpr int MAX_F = 128; // nof_bits + 16 < SRSLTE_DCI_MAX_BITS (pdcch.c:572-573)
 
 struct CtrlTxGeom {
-  const uint32_t* re;         // [16 PCFICH][n[0]][n[1]][n[2]][units x 12 PHICH] RE indices into one port's [nsym][12 prb] grid
+  const uint32_t* re;         // [16 PCFICH], then per REG variant [n[0]][n[1]][n[2]][units x 12 PHICH] RE indices into one port's [nsym][12 prb] grid
   const uint32_t* scr_pcfich; // [10] words: srslte_sequence_pcfich of each subframe (its first 12 bits are srslte_sequence_phich's)
   const uint32_t* scr_pdcch;  // [10][scr_words]
   int             scr_words;
-  int             off[3];     // PDCCH REs of CFI 1-3
-  int             phich_off, units;
+  int             off[CTRL_MAX_VAR][3];                          // PDCCH REs of CFI 1-3 of each REG variant (ctrl_host.hpp)
+  int             phich_off[CTRL_MAX_VAR], units[CTRL_MAX_VAR]; // its PHICH mapping units
+  int             max_units;                                     // the descriptors' stride
+  uint8_t         var[10];    // the variant of subframe sf_idx; CTRL_SF_UL: an uplink subframe of a TDD cell. FDD: all 0
   int             nof_ports, grid_len, cp_ext;
   float           s;          // srslte_precoding_diversity's scaling / sqrtf(2) with scaling 1.0f (precoding.c:1859, :1863)
 };
@@ -69,7 +71,8 @@ __device__ __forceinline__ cf32 phich_d0(uint32_t ent, int m, uint32_t scr, int 
 __global__ __launch_bounds__(64) void dl_ctrl_tx_pcfich_phich_kernel(const uint32_t* __restrict__ desc, int ph_off, int ph_ent, uint32_t tti0,
                                                                      CtrlTxGeom g, cf32* __restrict__ grid)
 {
-  const int      b = blockIdx.x, tid = threadIdx.x, P = g.nof_ports, sf_idx = (tti0 + b) % 10;
+  const int      b = blockIdx.x, tid = threadIdx.x, P = g.nof_ports, sf_idx = (tti0 + b) % 10, v = g.var[sf_idx];
+  if (v == CTRL_SF_UL) return; // nothing is written
   const uint32_t cfi = desc[b], scr = g.scr_pcfich[sf_idx];
   cf32*          gb  = grid + (size_t)b * P * g.grid_len;
   if (tid < 16) {
@@ -88,8 +91,8 @@ __global__ __launch_bounds__(64) void dl_ctrl_tx_pcfich_phich_kernel(const uint3
     for (int p = 0; p < 4; p++)
       if (p < P) gb[(size_t)p * g.grid_len + re] = y[p];
   }
-  const uint32_t* off = desc + ph_off + (size_t)b * g.units;
-  for (int pos = tid; pos < 12 * g.units; pos += 64) {
+  const uint32_t* off = desc + ph_off + (size_t)b * g.max_units;
+  for (int pos = tid; pos < 12 * g.units[v]; pos += 64) {
     const int u = pos / 12, i = pos - 12 * u, k = i % P;
     float     ar[4] = {0.f, 0.f, 0.f, 0.f}, ai[4] = {0.f, 0.f, 0.f, 0.f}; // srslte_regs_phich_reset
     for (uint32_t e = off[u]; e < off[u + 1]; e++) {
@@ -101,7 +104,7 @@ __global__ __launch_bounds__(64) void dl_ctrl_tx_pcfich_phich_kernel(const uint3
 #pragma unroll
       for (int p = 0; p < 4; p++) ar[p] += y[p].x, ai[p] += y[p].y; // srslte_regs_phich_add, entry by entry
     }
-    const uint32_t re = g.re[g.phich_off + pos];
+    const uint32_t re = g.re[g.phich_off[v] + pos];
 #pragma unroll
     for (int p = 0; p < 4; p++)
       if (p < P) gb[(size_t)p * g.grid_len + re] = make_float2(ar[p], ai[p]);
@@ -150,7 +153,7 @@ __global__ __launch_bounds__(64) void dl_ctrl_tx_pdcch_kernel(const DciTxDesc* _
   __syncthreads();
   // scrambling from bit 72 ncce (pdcch.c:589), QPSK, precoding, srslte_regs_pdcch_put_offset on REs [36 ncce, 36 (ncce + 2^L)) of the CFI's list
   const uint32_t* cs  = g.scr_pdcch + (size_t)sf_idx * g.scr_words;
-  const uint32_t* re  = g.re + g.off[cfi - 1] + 36 * ncce;
+  const uint32_t* re  = g.re + g.off[g.var[sf_idx]][cfi - 1] + 36 * ncce; // the host refused DCIs in uplink subframes
   const int       e0  = 72 * (int)ncce, n3 = 3 * F;
   cf32*           gb  = grid + (size_t)b * P * g.grid_len;
   for (int q = lane; q < (E / 2) / P; q += 64) {
@@ -187,7 +190,9 @@ srslte_hip_dl_ctrl_cfg_t rx_cfg(const srslte_hip_dl_ctrl_tx_cfg_t* c)
 struct srslte_hip_dl_ctrl_tx {
   srslte_hip_dl_ctrl_tx_cfg_t cfg;
   CtrlTxGeom                  g;
-  int                         nof_cce[3];
+  int                         tdd_sf_config = -1; // uplink-downlink configuration of a TDD object; -1: FDD
+  int                         nof_cce[CTRL_MAX_VAR][3], max_cce = 0;
+  uint32_t                    ngroups_m1 = 0;
   DevBuf<uint32_t>            re, scr;
   DescStage                   desc;
   std::vector<uint32_t>       words;   // the descriptor block of a call, as it is built
@@ -201,17 +206,21 @@ namespace {
 // The checks of srslte_hip_dl_ctrl_tx_put, and the descriptor block in q->words: cfi [nof_sf] | DciTxDesc [nof_dci] | PHICH offsets
 // [nof_sf units + 1] (entries of subframe b, unit u: [off[b units + u], off[b units + u + 1])) | PHICH entries, nseq | ack << 3 | odd << 4,
 // stable-sorted by (subframe, unit)
-int ctrl_tx_prepare(srslte_hip_dl_ctrl_tx_t* q, uint32_t nof_sf, const srslte_hip_dl_ctrl_tx_in_t* in, int* ph_off, int* ph_ent)
+int ctrl_tx_prepare(srslte_hip_dl_ctrl_tx_t* q, uint32_t tti0, uint32_t nof_sf, const srslte_hip_dl_ctrl_tx_in_t* in, int* ph_off, int* ph_ent)
 {
   const srslte_hip_dl_ctrl_tx_cfg_t& c = q->cfg;
   if (!in || nof_sf > c.max_batch || (nof_sf && !in->cfi) || in->nof_dci > c.max_dci || in->nof_phich > c.max_phich || (in->nof_dci && !in->dci) ||
       (in->nof_phich && !in->phich))
     return SRSLTE_ERROR_INVALID_INPUTS;
-  const uint32_t U = (uint32_t)q->g.units, ngroups = U * (c.cp_ext ? 2 : 1), maxcce = (uint32_t)q->nof_cce[2];
+  const uint32_t U = (uint32_t)q->g.max_units, maxcce = (uint32_t)q->max_cce;
+  const bool     tdd = q->tdd_sf_config >= 0;
+  auto           var_of = [&](uint32_t sf) { return q->g.var[(tti0 + sf) % 10]; };
   std::vector<uint32_t>& w = q->words;
   w.assign(nof_sf + (size_t)in->nof_dci * (sizeof(DciTxDesc) / 4) + (size_t)nof_sf * U + 1 + in->nof_phich, 0u);
   for (uint32_t b = 0; b < nof_sf; b++) {
-    if (in->cfi[b] < 1 || in->cfi[b] > 3) return SRSLTE_ERROR_INVALID_INPUTS;
+    if (var_of(b) == CTRL_SF_UL) continue; // in->cfi[b] is not looked at
+    const uint32_t sf_idx = (tti0 + b) % 10;
+    if (in->cfi[b] < 1 || in->cfi[b] > 3 || (tdd && in->cfi[b] == 3 && (sf_idx == 1 || sf_idx == 6))) return SRSLTE_ERROR_INVALID_INPUTS;
     w[b] = in->cfi[b];
   }
   q->used.assign((size_t)nof_sf * maxcce, 0);
@@ -219,9 +228,9 @@ int ctrl_tx_prepare(srslte_hip_dl_ctrl_tx_t* q, uint32_t nof_sf, const srslte_hi
   for (uint32_t i = 0; i < in->nof_dci; i++) {
     const srslte_hip_dl_ctrl_tx_dci_t& d = in->dci[i];
     const srslte_hip_dci_msg_t&        m = d.msg;
-    if (d.sf >= nof_sf || m.L > 3 || m.nof_bits == 0 || m.nof_bits >= 128 - 16) return SRSLTE_ERROR_INVALID_INPUTS;
-    const uint32_t cfi = in->cfi[d.sf], n = 1u << m.L;
-    if (m.ncce > (uint32_t)q->nof_cce[cfi - 1] || m.ncce + n > (uint32_t)q->nof_cce[cfi - 1]) return SRSLTE_ERROR_INVALID_INPUTS;
+    if (d.sf >= nof_sf || m.L > 3 || m.nof_bits == 0 || m.nof_bits >= 128 - 16 || var_of(d.sf) == CTRL_SF_UL) return SRSLTE_ERROR_INVALID_INPUTS;
+    const uint32_t cfi = in->cfi[d.sf], n = 1u << m.L, cces = (uint32_t)q->nof_cce[var_of(d.sf)][cfi - 1];
+    if (m.ncce > cces || m.ncce + n > cces) return SRSLTE_ERROR_INVALID_INPUTS;
     uint8_t* u = q->used.data() + (size_t)d.sf * maxcce + m.ncce;
     for (uint32_t k = 0; k < n; k++) {
       if (u[k]) return SRSLTE_ERROR_INVALID_INPUTS; // two DCIs on one CCE: the reference would overwrite the first, here it is refused
@@ -237,8 +246,10 @@ int ctrl_tx_prepare(srslte_hip_dl_ctrl_tx_t* q, uint32_t nof_sf, const srslte_hi
     const srslte_hip_phich_tx_t& p = in->phich[i];
     uint32_t                     ngroup, nseq;
     if (p.sf >= nof_sf || p.ack > 1 || p.I_phich > 1) return SRSLTE_ERROR_INVALID_INPUTS;
-    phich_calc(U, c.cp_ext, p.n_prb_lowest, p.n_dmrs, p.I_phich, &ngroup, &nseq);
-    if (ngroup >= ngroups) return SRSLTE_ERROR_INVALID_INPUTS;
+    // TDD: the subframe's own group count, mi ngroups_m1 - none in an uplink subframe or with mi = 0, and I_phich = 1 only where mi = 2
+    if (var_of(p.sf) == CTRL_SF_UL) return SRSLTE_ERROR_INVALID_INPUTS;
+    phich_calc(q->ngroups_m1, c.cp_ext, p.n_prb_lowest, p.n_dmrs, p.I_phich, &ngroup, &nseq);
+    if (ngroup >= (uint32_t)q->g.units[var_of(p.sf)] * (c.cp_ext ? 2u : 1u)) return SRSLTE_ERROR_INVALID_INPUTS;
     const uint32_t unit = c.cp_ext ? ngroup / 2 : ngroup, key = p.sf * U + unit;
     q->ph_unit[i] = nseq | (uint32_t)p.ack << 3 | (c.cp_ext ? (ngroup & 1) << 4 : 0u) | key << 8;
     w[o_off + key + 1]++;
@@ -252,11 +263,15 @@ int ctrl_tx_prepare(srslte_hip_dl_ctrl_tx_t* q, uint32_t nof_sf, const srslte_hi
 
 } // namespace
 
-int dl_ctrl_tx_check(srslte_hip_dl_ctrl_tx_t* q, uint32_t nof_sf, const srslte_hip_dl_ctrl_tx_in_t* in)
+int dl_ctrl_tx_check(srslte_hip_dl_ctrl_tx_t* q, uint32_t tti0, uint32_t nof_sf, const srslte_hip_dl_ctrl_tx_in_t* in)
 {
   int a, b;
-  return q ? ctrl_tx_prepare(q, nof_sf, in, &a, &b) : SRSLTE_ERROR_INVALID_INPUTS;
+  return q ? ctrl_tx_prepare(q, tti0, nof_sf, in, &a, &b) : SRSLTE_ERROR_INVALID_INPUTS;
 }
+
+int dl_ctrl_tx_tdd_sf_config(const srslte_hip_dl_ctrl_tx_t* q) { return q ? q->tdd_sf_config : -1; }
+
+bool dl_ctrl_tx_is_uplink(const srslte_hip_dl_ctrl_tx_t* q, uint32_t tti) { return q && q->g.var[tti % 10] == CTRL_SF_UL; }
 
 const srslte_hip_dl_ctrl_tx_cfg_t* dl_ctrl_tx_cfg(const srslte_hip_dl_ctrl_tx_t* q) { return q ? &q->cfg : nullptr; }
 
@@ -271,29 +286,40 @@ void srslte_hip_dl_ctrl_tx_destroy(srslte_hip_dl_ctrl_tx_t* q)
   delete q;
 }
 
-srslte_hip_dl_ctrl_tx_t* srslte_hip_dl_ctrl_tx_create(const srslte_hip_dl_ctrl_tx_cfg_t* cfg)
+// tdd_sf_config < 0: FDD
+static srslte_hip_dl_ctrl_tx_t* dl_ctrl_tx_make(const srslte_hip_dl_ctrl_tx_cfg_t* cfg, int tdd_sf_config)
 {
-  if (!cfg || cfg->tdd || cfg->max_batch < 1) return nullptr;
+  if (!cfg || cfg->max_batch < 1) return nullptr;
   const srslte_hip_dl_ctrl_cfg_t rc = rx_cfg(cfg);
-  CtrlRegs                       regs;
-  if (!ctrl_cell_ok(&rc) || ctrl_build_regs(&rc, regs) != SRSLTE_SUCCESS) return nullptr;
+  CtrlRegsSet                    set;
+  if (!ctrl_cell_ok(&rc) || ctrl_build_regs_set(&rc, tdd_sf_config, set) != SRSLTE_SUCCESS) return nullptr;
   auto* q = new srslte_hip_dl_ctrl_tx_t();
-  q->cfg        = *cfg;
-  CtrlTxGeom& g = q->g;
-  std::vector<uint32_t> re(regs.pcfich);
-  for (int c = 0; c < 3; c++) {
-    g.off[c] = (int)re.size(), q->nof_cce[c] = (int)regs.pdcch[c].size() / 36;
-    re.insert(re.end(), regs.pdcch[c].begin(), regs.pdcch[c].end());
+  q->cfg           = *cfg;
+  q->tdd_sf_config = tdd_sf_config;
+  q->ngroups_m1    = set.v[0].ngroups_m1;
+  CtrlTxGeom& g    = q->g;
+  memset(&g, 0, sizeof(g));
+  memset(q->nof_cce, 0, sizeof(q->nof_cce));
+  std::vector<uint32_t> re(set.v[0].pcfich); // the PCFICH REGs are the same in every variant
+  for (size_t v = 0; v < set.v.size(); v++) {
+    const CtrlRegs& regs = set.v[v];
+    for (int c = 0; c < 3; c++) {
+      g.off[v][c] = (int)re.size(), q->nof_cce[v][c] = (int)regs.pdcch[c].size() / 36;
+      re.insert(re.end(), regs.pdcch[c].begin(), regs.pdcch[c].end());
+    }
+    g.phich_off[v] = (int)re.size(), g.units[v] = (int)regs.units;
+    re.insert(re.end(), regs.phich.begin(), regs.phich.end());
   }
-  g.phich_off = (int)re.size(), g.units = (int)regs.ngroups_m1;
-  re.insert(re.end(), regs.phich.begin(), regs.phich.end());
+  memcpy(g.var, set.var, sizeof(g.var));
+  g.max_units = (int)set.max_units();
+  q->max_cce  = (int)set.max_pdcch_re / 36;
   g.nof_ports = (int)cfg->nof_ports;
   g.grid_len  = (cfg->cp_ext ? 12 : 14) * 12 * (int)cfg->nof_prb;
   g.cp_ext    = cfg->cp_ext ? 1 : 0;
   g.s         = 1.0f / sqrtf(2.0f);
   std::vector<uint32_t> scr;
-  ctrl_scrambling(cfg->cell_id, 72 * (uint32_t)q->nof_cce[2], scr, &g.scr_words);
-  const size_t desc_bytes = 4 * ((size_t)cfg->max_batch + (size_t)cfg->max_dci * (sizeof(DciTxDesc) / 4) + (size_t)cfg->max_batch * g.units + 1 + cfg->max_phich);
+  ctrl_scrambling(cfg->cell_id, 72 * (uint32_t)q->max_cce, scr, &g.scr_words);
+  const size_t desc_bytes = 4 * ((size_t)cfg->max_batch + (size_t)cfg->max_dci * (sizeof(DciTxDesc) / 4) + (size_t)cfg->max_batch * g.max_units + 1 + cfg->max_phich);
   if (q->re.upload(re) || q->scr.upload(scr) || q->desc.init(desc_bytes) ||
       !(q->bc = bcast_tables_create(&rc, cfg->phich_ext, cfg->phich_resources, false))) {
     hip_log("[srslte_hip] srslte_hip_dl_ctrl_tx_create: device allocation failed\n");
@@ -304,11 +330,18 @@ srslte_hip_dl_ctrl_tx_t* srslte_hip_dl_ctrl_tx_create(const srslte_hip_dl_ctrl_t
   return q;
 }
 
+srslte_hip_dl_ctrl_tx_t* srslte_hip_dl_ctrl_tx_create(const srslte_hip_dl_ctrl_tx_cfg_t* cfg) { return cfg && !cfg->tdd ? dl_ctrl_tx_make(cfg, -1) : nullptr; }
+
+srslte_hip_dl_ctrl_tx_t* srslte_hip_dl_ctrl_tx_create_tdd(const srslte_hip_dl_ctrl_tx_cfg_t* cfg, uint32_t tdd_sf_config)
+{
+  return cfg && cfg->tdd == 1 && tdd_sf_config <= 6 ? dl_ctrl_tx_make(cfg, (int)tdd_sf_config) : nullptr;
+}
+
 int srslte_hip_dl_ctrl_tx_put(srslte_hip_dl_ctrl_tx_t* q, uint32_t tti0, uint32_t nof_sf, const srslte_hip_dl_ctrl_tx_in_t* in, void* d_grid, void* stream)
 {
   int ph_off = 0, ph_ent = 0;
   if (!q || !d_grid) return SRSLTE_ERROR_INVALID_INPUTS;
-  if (int r = ctrl_tx_prepare(q, nof_sf, in, &ph_off, &ph_ent)) return r;
+  if (int r = ctrl_tx_prepare(q, tti0, nof_sf, in, &ph_off, &ph_ent)) return r;
   if (nof_sf == 0) return SRSLTE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
   uint32_t*   h  = nullptr;
@@ -332,6 +365,36 @@ int srslte_hip_dl_ctrl_phich_ngroups(const srslte_hip_dl_ctrl_tx_cfg_t* cfg)
   CtrlRegs                       regs;
   if (int r = ctrl_build_regs(&rc, regs)) return r;
   return (int)regs.ngroups_m1 * (cfg->cp_ext ? 2 : 1);
+}
+
+// the REG lists of subframe sf_idx of a TDD cell; < 0 for an uplink subframe, an invalid configuration or cell
+static int tdd_regs(const srslte_hip_dl_ctrl_tx_cfg_t* cfg, uint32_t tdd_sf_config, uint32_t sf_idx, CtrlRegs& regs)
+{
+  const int mi = ctrl_tdd_mi(tdd_sf_config, sf_idx);
+  if (!cfg || mi < 0) return SRSLTE_ERROR_INVALID_INPUTS;
+  const srslte_hip_dl_ctrl_cfg_t rc = rx_cfg(cfg);
+  return ctrl_build_regs_opts(&rc, (uint32_t)mi, sf_idx == 1 || sf_idx == 6, regs);
+}
+
+int srslte_hip_dl_ctrl_phich_ngroups_tdd(const srslte_hip_dl_ctrl_tx_cfg_t* cfg, uint32_t tdd_sf_config, uint32_t sf_idx)
+{
+  if (!cfg) return SRSLTE_ERROR_INVALID_INPUTS;
+  const srslte_hip_dl_ctrl_cfg_t rc = rx_cfg(cfg);
+  CtrlRegsSet                    set;
+  CtrlRegs                       regs;
+  if (int r = tdd_regs(cfg, tdd_sf_config, sf_idx, regs)) return r;
+  if (int r = ctrl_build_regs_set(&rc, (int)tdd_sf_config, set)) return r; // SRSLTE_ERROR: the creators refuse the cell and configuration (ctrl_host.hpp)
+  return (int)regs.units * (cfg->cp_ext ? 2 : 1);
+}
+
+int srslte_hip_dl_ctrl_phich_re_tdd(const srslte_hip_dl_ctrl_tx_cfg_t* cfg, uint32_t tdd_sf_config, uint32_t sf_idx, uint32_t ngroup, uint32_t* re, uint32_t max)
+{
+  CtrlRegs regs;
+  if (int r = tdd_regs(cfg, tdd_sf_config, sf_idx, regs)) return r;
+  const uint32_t unit = cfg->cp_ext ? ngroup / 2 : ngroup;
+  if (unit >= regs.units || !re || max < 12) return SRSLTE_ERROR_INVALID_INPUTS;
+  memcpy(re, regs.phich.data() + 12 * unit, 12 * 4);
+  return 12;
 }
 
 int srslte_hip_phich_calc(const srslte_hip_dl_ctrl_tx_cfg_t* cfg, uint32_t n_prb_lowest, uint32_t n_dmrs, uint32_t I_phich, uint32_t* ngroup, uint32_t* nseq)

@@ -616,16 +616,20 @@ extern "C" int srslte_hip_dl_tx_batch_grants(srslte_hip_dl_tx_t* q, const uint8_
 static uint32_t dl_tx_grant_cfi(const srslte_hip_dl_tx_grant_t& g) { return g.grant.cfi; }
 static uint32_t dl_tx_grant_cfi(const srslte_hip_dl_tx_grant2_t& g) { return g.grant.tb0.cfi; }
 template <typename Grant>
-static int dl_tx_ctrl_check(srslte_hip_dl_tx_t* q, uint32_t nof_sf, const Grant* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
+static int dl_tx_ctrl_check(srslte_hip_dl_tx_t* q, uint32_t tti0, uint32_t nof_sf, const Grant* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
                             const srslte_hip_dl_ctrl_tx_in_t* in)
 {
   const srslte_hip_dl_ctrl_tx_cfg_t* cc = dl_ctrl_tx_cfg(ctrl);
-  if (!q || !cc || !in || !grants || q->cfg.tdd || q->cfg.mbsfn || cc->nof_prb != q->cfg.nof_prb || cc->nof_ports != (uint32_t)q->g.nof_ports ||
+  // a TDD pipeline takes a TDD control object of its uplink-downlink configuration, an FDD pipeline an FDD one
+  const int tdd_cfg = q && q->cfg.tdd ? (int)q->cfg.tdd_sf_config : -1;
+  if (!q || !cc || !in || !grants || tdd_cfg != dl_ctrl_tx_tdd_sf_config(ctrl) || q->cfg.mbsfn || cc->nof_prb != q->cfg.nof_prb || cc->nof_ports != (uint32_t)q->g.nof_ports ||
       cc->cell_id != q->cfg.cell_id || (cc->cp_ext != 0) != (q->cfg.cp_ext != 0))
     return SRSLTE_ERROR_INVALID_INPUTS;
-  if (int r = dl_ctrl_tx_check(ctrl, nof_sf, in)) return r;
+  if (int r = dl_ctrl_tx_check(ctrl, tti0, nof_sf, in)) return r;
   for (uint32_t p = 0; p < nof_grants; p++) {
-    if (grants[p].sf < nof_sf && dl_tx_grant_cfi(grants[p]) != in->cfi[grants[p].sf]) return SRSLTE_ERROR_INVALID_INPUTS;
+    // in->cfi[b] of an uplink subframe is not looked at, here as in srslte_hip_dl_ctrl_tx_put
+    if (grants[p].sf < nof_sf && !dl_ctrl_tx_is_uplink(ctrl, tti0 + grants[p].sf) && dl_tx_grant_cfi(grants[p]) != in->cfi[grants[p].sf])
+      return SRSLTE_ERROR_INVALID_INPUTS;
   }
   return SRSLTE_SUCCESS;
 }
@@ -637,7 +641,7 @@ extern "C" int srslte_hip_dl_tx_batch_grants_ctrl(srslte_hip_dl_tx_t* q, const u
                                                   const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
                                                   const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream)
 {
-  if (int r = dl_tx_ctrl_check(q, nof_sf, grants, nof_grants, ctrl, in)) return r;
+  if (int r = dl_tx_ctrl_check(q, tti0, nof_sf, grants, nof_grants, ctrl, in)) return r;
   return dl_tx_batch_grants(q, d_tb, tb_stride, tti0, nof_sf, grants, nof_grants, ctrl, in, d_iq, stream);
 }
 
@@ -647,7 +651,7 @@ extern "C" int srslte_hip_dl_tx_batch_grants_full(srslte_hip_dl_tx_t* q, const u
                                                   const srslte_hip_dl_tx_grant_t* grants, uint32_t nof_grants, srslte_hip_dl_ctrl_tx_t* ctrl,
                                                   const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream)
 {
-  if (int r = dl_tx_ctrl_check(q, nof_sf, grants, nof_grants, ctrl, in)) return r;
+  if (int r = dl_tx_ctrl_check(q, tti0, nof_sf, grants, nof_grants, ctrl, in)) return r;
   return dl_tx_batch_grants(q, d_tb, tb_stride, tti0, nof_sf, grants, nof_grants, ctrl, in, d_iq, stream, true);
 }
 
@@ -674,10 +678,10 @@ static int dl_tx_grants2_check(const srslte_hip_dl_tx_t* q, const uint8_t* d_tb,
 }
 
 // dl_tx_ctrl_check with the log line the two-codeword calls promise for every refusal
-static int dl_tx_grants2_ctrl_check(srslte_hip_dl_tx_t* q, uint32_t nof_sf, const srslte_hip_dl_tx_grant2_t* grants, uint32_t nof_grants,
+static int dl_tx_grants2_ctrl_check(srslte_hip_dl_tx_t* q, uint32_t tti0, uint32_t nof_sf, const srslte_hip_dl_tx_grant2_t* grants, uint32_t nof_grants,
                                     srslte_hip_dl_ctrl_tx_t* ctrl, const srslte_hip_dl_ctrl_tx_in_t* in)
 {
-  const int r = dl_tx_ctrl_check(q, nof_sf, grants, nof_grants, ctrl, in);
+  const int r = dl_tx_ctrl_check(q, tti0, nof_sf, grants, nof_grants, ctrl, in);
   if (r) hip_log("[srslte_hip] dl_tx grants2: the control region is refused (another cell, a grant's cfi that is not its subframe's, or its own inputs)\n");
   return r;
 }
@@ -694,7 +698,7 @@ extern "C" int srslte_hip_dl_tx_batch_grants2_ctrl(srslte_hip_dl_tx_t* q, const 
                                                    const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream)
 {
   if (int r = dl_tx_grants2_check(q, d_tb, nof_sf, grants, nof_grants, d_iq)) return r;
-  if (int r = dl_tx_grants2_ctrl_check(q, nof_sf, grants, nof_grants, ctrl, in)) return r;
+  if (int r = dl_tx_grants2_ctrl_check(q, tti0, nof_sf, grants, nof_grants, ctrl, in)) return r;
   return dl_tx_batch_grants(q, d_tb, tb_stride, tti0, nof_sf, grants, nof_grants, true, ctrl, in, d_iq, stream);
 }
 
@@ -703,6 +707,6 @@ extern "C" int srslte_hip_dl_tx_batch_grants2_full(srslte_hip_dl_tx_t* q, const 
                                                    const srslte_hip_dl_ctrl_tx_in_t* in, void* d_iq, void* stream)
 {
   if (int r = dl_tx_grants2_check(q, d_tb, nof_sf, grants, nof_grants, d_iq)) return r;
-  if (int r = dl_tx_grants2_ctrl_check(q, nof_sf, grants, nof_grants, ctrl, in)) return r;
+  if (int r = dl_tx_grants2_ctrl_check(q, tti0, nof_sf, grants, nof_grants, ctrl, in)) return r;
   return dl_tx_batch_grants(q, d_tb, tb_stride, tti0, nof_sf, grants, nof_grants, true, ctrl, in, d_iq, stream, true);
 }

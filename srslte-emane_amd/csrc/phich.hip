@@ -32,8 +32,10 @@ enum { F0 = 0, F1A = 2 };                                                       
 
 struct UlReqs { uint32_t rnti[REQ_CHUNK]; };
 struct PhichGeom {
-  const uint32_t* re;  // [units][12]: the REs of each PHICH mapping unit in srslte_regs_phich_get order
+  const uint32_t* re;  // per REG variant [units][12]: the REs of each PHICH mapping unit in srslte_regs_phich_get order
   const uint32_t* scr; // [10] words: srslte_sequence_pcfich of each subframe; its first 12 bits are srslte_sequence_phich
+  int             off[CTRL_MAX_VAR]; // where each variant's list starts in re
+  uint8_t         var[10];           // the variant of subframe sf_idx (ctrl_host.hpp); FDD: all 0
   int             nof_ports, nof_rx, grid_len, cp_ext;
 };
 
@@ -130,8 +132,8 @@ __global__ __launch_bounds__(256) void dl_ctrl_ul_phich_kernel(const srslte_hip_
     ngroup = w & 0xffffu, nseq = w >> 16;
     const int       P = g.nof_ports, R = g.nof_rx, glen = g.grid_len, ext = g.cp_ext;
     const uint32_t  unit = ext ? ngroup >> 1 : ngroup, odd = ext ? ngroup & 1u : 0u;
-    const uint32_t  scr = g.scr[(tti0 + b) % 10];
-    const uint32_t* re = g.re + 12 * unit + 4 * i;
+    const uint32_t  sf_idx = (tti0 + b) % 10, scr = g.scr[sf_idx];
+    const uint32_t* re = g.re + g.off[g.var[sf_idx]] + 12 * unit + 4 * i; // the host refused uplink subframes: var < CTRL_MAX_VAR
     const cf32*     y = grid + (size_t)b * R * glen;
     const cf32*     h[4];
     for (int p = 0; p < 4; p++) h[p] = ce + ((size_t)b * P + (p < P ? p : 0)) * R * glen;
@@ -197,7 +199,10 @@ __global__ __launch_bounds__(256) void dl_ctrl_ul_phich_kernel(const srslte_hip_
 
 // The PHICH receiver's tables and buffers of a srslte_hip_dl_ctrl_t, made by srslte_hip_dl_ctrl_set_max_phich
 struct PhichRx {
-  uint32_t                 units = 0, ngroups = 0, max_phich = 0;
+  uint32_t                 ngroups_m1 = 0, max_phich = 0;
+  uint32_t                 units[CTRL_MAX_VAR] = {}; // mapping units of each REG variant
+  int                      off[CTRL_MAX_VAR]   = {}; // its list in re
+  uint8_t                  var[10];
   DevBuf<uint32_t>         re;
   DescStage                req;
   DevBuf<srslte_hip_phich_soft_t> soft;
@@ -210,7 +215,7 @@ namespace {
 
 // phich_calc of ctrl_host.hpp and the group check of srslte_phich_decode (phich.c:215-218) for every request; fills t->words. The sequence
 // check of phich.c:204-214 has nothing to refuse: srslte_phich_calc reduces nseq modulo the CP's sequence count
-int phich_prepare(const srslte_hip_dl_ctrl_cfg_t& c, PhichRx* t, uint32_t nof_sf, const srslte_hip_phich_req_t* ph, uint32_t nof_phich)
+int phich_prepare(const srslte_hip_dl_ctrl_cfg_t& c, PhichRx* t, uint32_t tti0, uint32_t nof_sf, const srslte_hip_phich_req_t* ph, uint32_t nof_phich)
 {
   if (nof_phich == 0) return SRSLTE_SUCCESS;
   if (!t || !ph || nof_phich > t->max_phich) return SRSLTE_ERROR_INVALID_INPUTS;
@@ -219,8 +224,11 @@ int phich_prepare(const srslte_hip_dl_ctrl_cfg_t& c, PhichRx* t, uint32_t nof_sf
     const srslte_hip_phich_req_t& p = ph[i];
     uint32_t                      ngroup, nseq;
     if (p.sf >= nof_sf || p.I_phich > 1) return SRSLTE_ERROR_INVALID_INPUTS;
-    phich_calc(t->units, c.cp_ext, p.n_prb_lowest, p.n_dmrs, p.I_phich, &ngroup, &nseq);
-    if (ngroup >= t->ngroups) return SRSLTE_ERROR_INVALID_INPUTS;
+    // TDD: the subframe's own group count, mi ngroups_m1 - none in an uplink subframe or with mi = 0, and I_phich = 1 only where mi = 2
+    const uint8_t v = t->var[(tti0 + p.sf) % 10];
+    if (v == CTRL_SF_UL) return SRSLTE_ERROR_INVALID_INPUTS;
+    phich_calc(t->ngroups_m1, c.cp_ext, p.n_prb_lowest, p.n_dmrs, p.I_phich, &ngroup, &nseq);
+    if (ngroup >= t->units[v] * (c.cp_ext ? 2u : 1u)) return SRSLTE_ERROR_INVALID_INPUTS;
     t->words[2 * i] = p.sf, t->words[2 * i + 1] = ngroup | nseq << 16;
   }
   return SRSLTE_SUCCESS;
@@ -242,6 +250,8 @@ PhichGeom phich_geom(const DlCtrlView& v, const PhichRx* t)
   g.re = t ? t->re.get() : nullptr, g.scr = v.d_scr_pcfich;
   g.nof_ports = (int)v.cfg->nof_ports, g.nof_rx = (int)v.cfg->nof_rx_antennas;
   g.grid_len = (v.cfg->cp_ext ? 12 : 14) * 12 * (int)v.cfg->nof_prb, g.cp_ext = v.cfg->cp_ext ? 1 : 0;
+  memset(g.off, 0, sizeof(g.off)), memset(g.var, 0, sizeof(g.var));
+  if (t) memcpy(g.off, t->off, sizeof(g.off)), memcpy(g.var, t->var, sizeof(g.var));
   return g;
 }
 
@@ -256,13 +266,19 @@ int srslte_hip_dl_ctrl_set_max_phich(srslte_hip_dl_ctrl_t* q, uint32_t max_phich
   phich_rx_destroy(dl_ctrl_phich(q));
   dl_ctrl_set_phich(q, nullptr);
   if (max_phich == 0) return SRSLTE_SUCCESS;
-  CtrlRegs regs;
-  if (ctrl_build_regs(v.cfg, regs) != SRSLTE_SUCCESS || regs.ngroups_m1 == 0) return SRSLTE_ERROR;
-  PhichRx* t   = new PhichRx();
-  t->units     = regs.ngroups_m1;
-  t->ngroups   = regs.ngroups_m1 * (v.cfg->cp_ext ? 2 : 1);
-  t->max_phich = max_phich;
-  if (t->re.upload(regs.phich) || t->req.init(8 * (size_t)max_phich) || t->soft.alloc(max_phich)) {
+  CtrlRegsSet set;
+  if (ctrl_build_regs_set(v.cfg, v.tdd_sf_config, set) != SRSLTE_SUCCESS || set.v[0].ngroups_m1 == 0) return SRSLTE_ERROR;
+  PhichRx* t    = new PhichRx();
+  t->ngroups_m1 = set.v[0].ngroups_m1;
+  t->max_phich  = max_phich;
+  memcpy(t->var, set.var, sizeof(t->var));
+  std::vector<uint32_t> re;
+  for (size_t i = 0; i < set.v.size(); i++) {
+    t->units[i] = set.v[i].units, t->off[i] = (int)re.size();
+    re.insert(re.end(), set.v[i].phich.begin(), set.v[i].phich.end());
+  }
+  if (re.empty()) re.push_back(0u); // a TDD configuration whose downlink subframes all have mi = 0: every request is refused
+  if (t->re.upload(re) || t->req.init(8 * (size_t)max_phich) || t->soft.alloc(max_phich)) {
     hip_log("[srslte_hip] srslte_hip_dl_ctrl_set_max_phich: device allocation failed\n");
     phich_rx_destroy(t);
     return SRSLTE_ERROR;
@@ -278,7 +294,7 @@ int srslte_hip_dl_ctrl_phich_batch(srslte_hip_dl_ctrl_t* q, const void* d_grid, 
   const DlCtrlView v = dl_ctrl_view(q);
   if (nof_sf < 1 || nof_sf > v.cfg->max_batch || (nof_phich && !d_phich_res)) return SRSLTE_ERROR_INVALID_INPUTS;
   PhichRx* t = dl_ctrl_phich(q);
-  if (int r = phich_prepare(*v.cfg, t, nof_sf, phich, nof_phich)) return r;
+  if (int r = phich_prepare(*v.cfg, t, tti0, nof_sf, phich, nof_phich)) return r;
   if (nof_phich == 0) return SRSLTE_SUCCESS;
   hipStream_t st = (hipStream_t)stream;
   if (int r = phich_upload(t, nof_phich, st)) return r;
@@ -295,10 +311,10 @@ int srslte_hip_dl_ctrl_batch_ul(srslte_hip_dl_ctrl_t* q, const void* d_grid, con
                                 uint32_t nof_phich, srslte_hip_phich_res_t* d_phich_res, void* stream)
 {
   if (!d_grid || !d_ce || !d_res || !d_out || !d_msg || !d_ul_out || !d_ul_msg || (nof_phich && !d_phich_res)) return SRSLTE_ERROR_INVALID_INPUTS;
-  if (int r = dl_ctrl_check(q, nof_sf, reqs)) return r;
+  if (int r = dl_ctrl_check(q, tti0, nof_sf, reqs)) return r;
   const DlCtrlView v = dl_ctrl_view(q);
   PhichRx*         t = dl_ctrl_phich(q);
-  if (int r = phich_prepare(*v.cfg, t, nof_sf, phich, nof_phich)) return r;
+  if (int r = phich_prepare(*v.cfg, t, tti0, nof_sf, phich, nof_phich)) return r;
   hipStream_t st = (hipStream_t)stream;
   if (nof_phich)
     if (int r = phich_upload(t, nof_phich, st)) return r;

@@ -115,8 +115,10 @@ int tdec_run_batch_w(srslte_hip_tdec_t* q, const void* d_input, int llr8, uint32
                      uint32_t nof_cb, uint32_t nof_iterations, uint32_t crc_poly, uint32_t crc_nbits, uint8_t* d_output,
                      uint32_t out_stride, uint32_t* d_iters, uint8_t* d_crc_ok, hipStream_t st, const TdecOpts& opts);
 // pdcch_tx.hip: the checks of srslte_hip_dl_ctrl_tx_put alone (nothing is queued), and the cell an object was made for
-int                                dl_ctrl_tx_check(srslte_hip_dl_ctrl_tx_t* q, uint32_t nof_sf, const srslte_hip_dl_ctrl_tx_in_t* in);
+int                                dl_ctrl_tx_check(srslte_hip_dl_ctrl_tx_t* q, uint32_t tti0, uint32_t nof_sf, const srslte_hip_dl_ctrl_tx_in_t* in);
 const srslte_hip_dl_ctrl_tx_cfg_t* dl_ctrl_tx_cfg(const srslte_hip_dl_ctrl_tx_t* q);
+int                                dl_ctrl_tx_tdd_sf_config(const srslte_hip_dl_ctrl_tx_t* q); // -1: an FDD object
+bool                               dl_ctrl_tx_is_uplink(const srslte_hip_dl_ctrl_tx_t* q, uint32_t tti); // an uplink subframe of a TDD object
 // pbch.hip: the broadcast tables of a cell on the device (PBCH REs, PSS / SSS, srslte_sequence_pbch; rx: the MIB decoder's buffers for
 // c->max_batch subframes), owned by a srslte_hip_dl_ctrl_tx_t / srslte_hip_dl_ctrl_t; the broadcast put of a batch on the stream
 struct BcastTables;
@@ -133,11 +135,12 @@ const BcastTables* dl_ctrl_bcast(const srslte_hip_dl_ctrl_t* q);
 struct PhichRx;
 struct DlCtrlView {
   const srslte_hip_dl_ctrl_cfg_t*  cfg;
-  const uint32_t*                  d_scr_pcfich; // [10] words
+  int                              tdd_sf_config; // -1: FDD
+  const uint32_t*                  d_scr_pcfich;  // [10] words
   const srslte_hip_dl_ctrl_cand_t* d_cand;       // [max_batch][SRSLTE_HIP_DL_CTRL_MAX_CAND]
   const uint32_t*                  d_ncand;      // [max_batch]
 };
-int        dl_ctrl_check(const srslte_hip_dl_ctrl_t* q, uint32_t nof_sf, const srslte_hip_dl_ctrl_req_t* reqs);
+int        dl_ctrl_check(const srslte_hip_dl_ctrl_t* q, uint32_t tti0, uint32_t nof_sf, const srslte_hip_dl_ctrl_req_t* reqs);
 DlCtrlView dl_ctrl_view(srslte_hip_dl_ctrl_t* q);
 PhichRx*   dl_ctrl_phich(const srslte_hip_dl_ctrl_t* q);
 void       dl_ctrl_set_phich(srslte_hip_dl_ctrl_t* q, PhichRx* t);

@@ -112,6 +112,7 @@ _TX_GRANTS_CTRL = [vp, vp, u32, u32, u32, vp, u32, vp, P(DlCtrlTxIn), vp, vp]
 SIGNATURES = {
     # DL control region receive
     "srslte_hip_dl_ctrl_create": (vp, [P(DlCtrlCfg)]),
+    "srslte_hip_dl_ctrl_create_tdd": (vp, [P(DlCtrlCfg), u32]),
     "srslte_hip_dl_ctrl_destroy": (void, [vp]),
     "srslte_hip_dl_ctrl_batch": (None, [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp]),
     "srslte_hip_dl_ctrl_debug_buffer": (vp, [vp, cint]),
@@ -121,6 +122,9 @@ SIGNATURES = {
     "srslte_hip_pdcch_ue_locations_ncce": (u32, [u32, vp, u32, u32, u16]),
     "srslte_hip_pdcch_common_locations_ncce": (u32, [u32, vp, u32]),
     "srslte_hip_dci_format_sizeof": (u32, [u32, u32, cint]),
+    "srslte_hip_dl_ctrl_tdd_mi": (cint, [u32, u32]),
+    "srslte_hip_dl_ctrl_pdcch_re_tdd": (None, [P(DlCtrlCfg), u32, u32, u32, vp, u32]),
+    "srslte_hip_dci_format_sizeof_tdd": (u32, [u32, u32, cint]),
     # DL control region receive: UL DCIs and PHICH
     "srslte_hip_dl_ctrl_set_max_phich": (None, [vp, u32]),
     "srslte_hip_dl_ctrl_batch_ul": (None, [vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp, u32, vp, vp]),
@@ -128,12 +132,15 @@ SIGNATURES = {
     "srslte_hip_dl_ctrl_phich_debug_buffer": (vp, [vp]),
     # DL control region transmit
     "srslte_hip_dl_ctrl_tx_create": (vp, [P(DlCtrlTxCfg)]),
+    "srslte_hip_dl_ctrl_tx_create_tdd": (vp, [P(DlCtrlTxCfg), u32]),
     "srslte_hip_dl_ctrl_tx_destroy": (void, [vp]),
     "srslte_hip_dl_ctrl_tx_put": (None, [vp, u32, u32, P(DlCtrlTxIn), vp, vp]),
     "srslte_hip_dl_tx_batch_grants_ctrl": (None, _TX_GRANTS_CTRL),
     "srslte_hip_dl_ctrl_phich_ngroups": (None, [P(DlCtrlTxCfg)]),
     "srslte_hip_phich_calc": (None, [P(DlCtrlTxCfg), u32, u32, u32, P(u32), P(u32)]),
     "srslte_hip_dl_ctrl_phich_re": (None, [P(DlCtrlTxCfg), u32, vp, u32]),
+    "srslte_hip_dl_ctrl_phich_ngroups_tdd": (None, [P(DlCtrlTxCfg), u32, u32]),
+    "srslte_hip_dl_ctrl_phich_re_tdd": (None, [P(DlCtrlTxCfg), u32, u32, u32, vp, u32]),
     # DL broadcast
     "srslte_hip_dl_ctrl_tx_put_bcast": (None, [vp, u32, u32, vp, vp]),
     "srslte_hip_dl_tx_batch_grants_full": (None, _TX_GRANTS_CTRL),
@@ -191,6 +198,24 @@ def dci_format_sizeof(nof_prb, nof_ports, fmt):
     return lib().srslte_hip_dci_format_sizeof(nof_prb, nof_ports, fmt)
 
 
+def tdd_mi(tdd_sf_config, sf_idx):
+    """mi of 36.213 Table 6.9-1 for subframe sf_idx of uplink-downlink configuration tdd_sf_config; < 0: uplink subframe or invalid (host)."""
+    return lib().srslte_hip_dl_ctrl_tdd_mi(tdd_sf_config, sf_idx)
+
+
+def pdcch_re_tdd(nof_prb, nof_ports, cell_id, tdd_sf_config, sf_idx, cfi, cp_ext=False, phich_resources=0, phich_ext=False):
+    """pdcch_re for subframe sf_idx of a TDD cell: the list of srslte_regs_init_opts(cell, mi, sf1_6) (host; no GPU)."""
+    out = np.zeros(14 * 12 * 110, np.uint32)
+    cfg = _ctrl_cfg(nof_prb, nof_ports, cell_id, cp_ext, phich_resources, phich_ext, tdd=True)
+    n = lib().srslte_hip_dl_ctrl_pdcch_re_tdd(C.byref(cfg), tdd_sf_config, sf_idx, cfi, out.ctypes.data, out.size)
+    return _re_list("srslte_hip_dl_ctrl_pdcch_re_tdd", n, out)
+
+
+def dci_format_sizeof_tdd(nof_prb, nof_ports, fmt):
+    """srslte_dci_format_sizeof for a TDD cell with a zero srslte_dci_cfg_t (host)."""
+    return lib().srslte_hip_dci_format_sizeof_tdd(nof_prb, nof_ports, fmt)
+
+
 def pbch_re(nof_prb, nof_ports, cell_id, cp_ext=False):
     """The PBCH REs of one port's subframe grid in srslte_pbch_put's order (host; no GPU)."""
     out = np.zeros(240, np.uint32)
@@ -225,9 +250,14 @@ class DlCtrl(Handle):
     with batch_ul / phich also srslte_ue_dl_find_ul_dci and srslte_ue_dl_decode_phich (max_phich: PHICH requests per call)."""
     DESTROY = "srslte_hip_dl_ctrl_destroy"
 
-    def __init__(self, nof_prb, nof_ports, cell_id, cp_ext=False, phich_resources=0, phich_ext=False, nof_rx=1, max_batch=1, tdd=False, max_phich=0):
-        self.cfg = _ctrl_cfg(nof_prb, nof_ports, cell_id, cp_ext, phich_resources, phich_ext, nof_rx, max_batch, tdd)
-        self._create("srslte_hip_dl_ctrl_create", C.byref(self.cfg))
+    def __init__(self, nof_prb, nof_ports, cell_id, cp_ext=False, phich_resources=0, phich_ext=False, nof_rx=1, max_batch=1, tdd=False, max_phich=0,
+                 tdd_sf_config=None):
+        """tdd_sf_config 0-6: a TDD cell of that uplink-downlink configuration (srslte_hip_dl_ctrl_create_tdd); tdd alone is refused."""
+        self.cfg = _ctrl_cfg(nof_prb, nof_ports, cell_id, cp_ext, phich_resources, phich_ext, nof_rx, max_batch, tdd or tdd_sf_config is not None)
+        if tdd_sf_config is None:
+            self._create("srslte_hip_dl_ctrl_create", C.byref(self.cfg))
+        else:
+            self._create("srslte_hip_dl_ctrl_create_tdd", C.byref(self.cfg), tdd_sf_config)
         self.grid_len = (12 if cp_ext else 14) * 12 * nof_prb
         self.nof_ports, self.nof_rx, self.max_batch = nof_ports, nof_rx, max_batch
         self.llr_stride = lib().srslte_hip_dl_ctrl_llr_stride(self.h)
@@ -365,13 +395,37 @@ def phich_re(nof_prb, nof_ports, cell_id, ngroup, cp_ext=False, phich_resources=
     return _re_list("srslte_hip_dl_ctrl_phich_re", lib().srslte_hip_dl_ctrl_phich_re(C.byref(cfg), ngroup, out.ctypes.data, 12), out)
 
 
+def phich_ngroups_tdd(nof_prb, nof_ports, cell_id, tdd_sf_config, sf_idx, cp_ext=False, phich_resources=0, phich_ext=False):
+    """PHICH groups of subframe sf_idx of a TDD cell: mi srslte_regs_phich_ngroups_m1 (x 2 on an extended-CP cell). ValueError for an uplink
+    subframe, and for a cell and configuration the device refuses because two mapping units share a REG (host; no GPU)."""
+    cfg = _ctrl_tx_cfg(nof_prb, nof_ports, cell_id, cp_ext, phich_resources, phich_ext, tdd=True)
+    n = lib().srslte_hip_dl_ctrl_phich_ngroups_tdd(C.byref(cfg), tdd_sf_config, sf_idx)
+    if n < 0:
+        raise ValueError("srslte_hip_dl_ctrl_phich_ngroups_tdd: %d" % n)
+    return n
+
+
+def phich_re_tdd(nof_prb, nof_ports, cell_id, tdd_sf_config, sf_idx, ngroup, cp_ext=False, phich_resources=0, phich_ext=False):
+    """phich_re for subframe sf_idx of a TDD cell (host)."""
+    out = np.zeros(12, np.uint32)
+    cfg = _ctrl_tx_cfg(nof_prb, nof_ports, cell_id, cp_ext, phich_resources, phich_ext, tdd=True)
+    n = lib().srslte_hip_dl_ctrl_phich_re_tdd(C.byref(cfg), tdd_sf_config, sf_idx, ngroup, out.ctypes.data, 12)
+    return _re_list("srslte_hip_dl_ctrl_phich_re_tdd", n, out)
+
+
 class DlCtrlTx(Handle):
     """Batched control-region transmit: the PCFICH of srslte_enb_dl_put_base, srslte_enb_dl_put_phich and srslte_enb_dl_put_pdcch_dl / _ul."""
     DESTROY = "srslte_hip_dl_ctrl_tx_destroy"
 
-    def __init__(self, nof_prb, nof_ports, cell_id, cp_ext=False, phich_resources=0, phich_ext=False, max_batch=1, max_dci=16, max_phich=16, tdd=False):
-        self.cfg = _ctrl_tx_cfg(nof_prb, nof_ports, cell_id, cp_ext, phich_resources, phich_ext, max_batch, max_dci, max_phich, tdd)
-        self._create("srslte_hip_dl_ctrl_tx_create", C.byref(self.cfg))
+    def __init__(self, nof_prb, nof_ports, cell_id, cp_ext=False, phich_resources=0, phich_ext=False, max_batch=1, max_dci=16, max_phich=16, tdd=False,
+                 tdd_sf_config=None):
+        """tdd_sf_config 0-6: a TDD cell of that uplink-downlink configuration (srslte_hip_dl_ctrl_tx_create_tdd); tdd alone is refused."""
+        self.cfg = _ctrl_tx_cfg(nof_prb, nof_ports, cell_id, cp_ext, phich_resources, phich_ext, max_batch, max_dci, max_phich,
+                                tdd or tdd_sf_config is not None)
+        if tdd_sf_config is None:
+            self._create("srslte_hip_dl_ctrl_tx_create", C.byref(self.cfg))
+        else:
+            self._create("srslte_hip_dl_ctrl_tx_create_tdd", C.byref(self.cfg), tdd_sf_config)
         self.grid_len = (12 if cp_ext else 14) * 12 * nof_prb
         self.nof_ports, self.max_batch = nof_ports, max_batch
 
