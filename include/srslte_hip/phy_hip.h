@@ -69,6 +69,31 @@ int srslte_hip_ofdm_set_mbsfn(srslte_hip_ofdm_t* q, int enable, int non_mbsfn_re
  * rx or tx according to the object; d_in/d_out are subframe bases as in the _sf_batch calls */
 int srslte_hip_ofdm_slot_batch(srslte_hip_ofdm_t* q, const void* d_in, void* d_out, int nof_sf, int slot_in_sf, int mbsfn_layout, void* stream);
 
+/* ------------------------------------------------------------------ Sample formats
+ * The radios the reference drives deliver and accept int16 pairs; its bladeRF path runs srslte_vec_convert_if(rx_buffer, 2048, data, 2 * nsamples)
+ * after every receive and srslte_vec_convert_fi(data, 2048, tx_buffer, 2 * nsamples) before every send (lib/src/phy/rf/rf_blade_imp.c:443,:485;
+ * bodies in lib/src/phy/utils/vector_simd.c:362-427). An OFDM object does either conversion inside its kernel, so that a caller moves 4 bytes per
+ * sample over the link instead of 8 and touches no sample on the CPU. The format belongs to the object and concerns its TIME-DOMAIN side only:
+ * d_in_time of srslte_hip_ofdm_rx_sf_batch / d_in of srslte_hip_ofdm_slot_batch on a receive object, d_out_time / d_out on a transmit object.
+ *   SRSLTE_HIP_IQ_CF32  interleaved float re, im: 8 bytes per sample (the default; scale is not used)
+ *   SRSLTE_HIP_IQ_SC16  interleaved int16 I, Q: 4 bytes per sample, same layouts counted in samples ([nof_sf][15 N])
+ * Receive, sc16: each component is (float)x * gain with gain = 1.0f / scale computed once on the host, the product rounded to fp32 before the
+ * half-carrier shift or the transform sees it: srslte_vec_convert_if (vector_simd.c:362-390) in the load. The grid is bit for bit that of the
+ * cf32 call on the converted samples.
+ * Transmit, sc16: each component of the cf32 value the object would store (after 1/sqrt(N) and the half-carrier shift), cyclic prefix
+ * included, goes through the vector body of srslte_vec_convert_fi (vector_simd.c:395-422, srslte_simd_convert_2f_s simd.h:1681-1686 in the
+ * reference's AVX2 build: mul, cvttps_epi32, packs_epi32): multiplied by scale and rounded to fp32, truncated towards zero, saturated to
+ * [-32768, 32767]; a product that is not finite or whose magnitude is 2^31 or more gives -32768 (the conversion's "integer indefinite", packed).
+ * The reference's scalar tail, (int16_t)(x * scale) at vector_simd.c:424-426, does not saturate; it only touches the last
+ * len % SRSLTE_SIMD_S_SIZE values, and a subframe (2 * 15 N floats, N >= 128) has none. Guard samples of an MBSFN layout stay unwritten.
+ * format outside the two, or a scale that is not finite and > 0: SRSLTE_ERROR_INVALID_INPUTS, object unchanged. The format may be switched
+ * between calls (a call uses the format set when it is made). The pipelines forward it: srslte_hip_{dl,ul}_{rx,tx}_set_iq_format and
+ * srslte_hip_dl_rx_pool_set_iq_format below. cf32 only: the single-call API of srslte_compat.h (srslte_ofdm_rx_sf and friends), synchronisation
+ * (srslte_hip_sync_*, srslte_hip_nbiot_sync_*), neighbour-cell measurement, PRACH and the channel emulator. */
+#define SRSLTE_HIP_IQ_CF32 0
+#define SRSLTE_HIP_IQ_SC16 1 /* int16 I, int16 Q interleaved, 4 bytes per sample */
+int srslte_hip_ofdm_set_sample_format(srslte_hip_ofdm_t* q, int format, float scale);
+
 /* generic batched c2c DFT (replaces srslte_dft_run_guru_c, dft.h:137-152, dft_fftw.c:137-165,307-313) */
 int srslte_hip_dft_batch(const void* d_in, void* d_out, int N, int howmany, int idist, int odist, int forward, float scale, void* stream);
 /* SC-FDMA transform precoding (replaces srslte_dft_precoding, dft_precoding.h:39-64, dft_precoding.c:88-113) */
@@ -265,6 +290,10 @@ typedef struct {
 } srslte_hip_dl_rx_cfg_t;
 srslte_hip_dl_rx_t* srslte_hip_dl_rx_create(const srslte_hip_dl_rx_cfg_t* cfg);
 void                srslte_hip_dl_rx_destroy(srslte_hip_dl_rx_t* q);
+/* "Sample formats" above: forwards to the object's OFDM object. After the call d_iq of EVERY entry point of the object that takes time samples is
+ * in that format, layout [nof_sf][nof_rx][15 N] samples as before: the fixed grant, _harq / _harq2, _grants / _grants2 and stage 0 of
+ * srslte_hip_dl_rx_stage. The *_grid_batch calls take grids and are not concerned. */
+int                 srslte_hip_dl_rx_set_iq_format(srslte_hip_dl_rx_t* q, int format, float scale);
 uint32_t            srslte_hip_dl_rx_nof_re(const srslte_hip_dl_rx_t* q, uint32_t sf_idx);
 /* d_iq: [nof_sf][15*N]; outputs: d_tb [nof_sf][tb_stride] bytes (tbs/8 + 3 CRC bytes used), d_tb_ok [nof_sf]. The two output pointers may be
  * device-visible HOST memory (hipHostMalloc / a pinned allocation): the pipeline's last phase then stores the results where the MAC reads them and no
@@ -337,13 +366,25 @@ int srslte_hip_dl_rx_grid_batch_grants2(srslte_hip_dl_rx_t* q, const void* d_gri
  * n % depth (waiting first, on the host, for the batch that used that object `depth` submissions ago) and returns a ticket; wait(ticket) blocks
  * until that batch's d_tb / d_tb_ok are final (their device buffers are the caller's; copy them on any stream after wait, or pass a pinned host
  * record to have the pool copy [nof_sf][tb_stride] bytes + [nof_sf] flags there on the batch's stream before the event). grants may be NULL (the
- * object's fixed grant). All calls from one host thread. */
+ * object's fixed grant). All calls from one host thread.
+ * Precondition of submit(), as it has always been: the pool's streams are non-blocking and order against NOTHING of the caller's, so d_iq must be
+ * complete (whatever filled it has finished, not merely been queued) and d_tb / d_tb_ok must not be in use by earlier work when submit() is called.
+ * submit_host() is the call without such a precondition on device work: it first copies nof_sf * nof_rx * 15 N samples of the pool's format from
+ * h_iq (host memory; pinned, or the copy is not asynchronous) into a device staging buffer of the chosen object, ON THAT OBJECT'S STREAM, and runs
+ * the batch from there - after waiting, as submit() does, for the batch that used the object before. h_iq must stay valid and unchanged until
+ * wait(ticket). The staging buffers (one per object, max_batch subframes) are allocated by the first submit_host(); a pool that never calls it
+ * allocates nothing for it. The same refusals as submit(), made before anything is queued: NULL pointers, nof_sf > max_batch. The d_tb / d_tb_ok
+ * part of the precondition remains. set_iq_format() sets the format of all the pool's objects ("Sample formats" above) and is refused once a
+ * batch has been submitted. */
 typedef struct srslte_hip_dl_rx_pool srslte_hip_dl_rx_pool_t;
 srslte_hip_dl_rx_pool_t* srslte_hip_dl_rx_pool_create(const srslte_hip_dl_rx_cfg_t* cfg, uint32_t depth);
 void                     srslte_hip_dl_rx_pool_destroy(srslte_hip_dl_rx_pool_t* p);
 int64_t srslte_hip_dl_rx_pool_submit(srslte_hip_dl_rx_pool_t* p, const void* d_iq, uint32_t tti0, uint32_t nof_sf, const srslte_hip_dl_grant_t* grants,
                                      uint8_t* d_tb, uint32_t tb_stride, uint8_t* d_tb_ok, void* h_record /* pinned, or NULL */);
 int     srslte_hip_dl_rx_pool_wait(srslte_hip_dl_rx_pool_t* p, int64_t ticket);
+int     srslte_hip_dl_rx_pool_set_iq_format(srslte_hip_dl_rx_pool_t* p, int format, float scale);
+int64_t srslte_hip_dl_rx_pool_submit_host(srslte_hip_dl_rx_pool_t* p, const void* h_iq, uint32_t tti0, uint32_t nof_sf, const srslte_hip_dl_grant_t* grants,
+                                          uint8_t* d_tb, uint32_t tb_stride, uint8_t* d_tb_ok, void* h_record /* pinned, or NULL */);
 
 /* one stage of the chain (0 OFDM RX, 1 chest_dl, 2 extract+equalise+demap+descramble, 3 rate de-matching, 4 turbo decode, 5 TB CRC):
  * what srslte_hip_dl_rx_batch runs in order; exposed so that each kernel can be timed on its own */
@@ -404,6 +445,8 @@ typedef struct {
 } srslte_hip_ul_rx_cfg_t;
 srslte_hip_ul_rx_t* srslte_hip_ul_rx_create(const srslte_hip_ul_rx_cfg_t* cfg);
 void                srslte_hip_ul_rx_destroy(srslte_hip_ul_rx_t* q);
+/* "Sample formats": d_iq of every receive call of the object (fixed grant, _harq, _grants, _grants_pucch, _grants_pucch_srs) */
+int                 srslte_hip_ul_rx_set_iq_format(srslte_hip_ul_rx_t* q, int format, float scale);
 /* d_iq: [nof_sf][15*N]; d_tb [nof_sf][tb_stride] (tbs/8 + 3 CRC bytes used), d_tb_ok [nof_sf]; subframe b is TTI tti0 + b */
 int srslte_hip_ul_rx_batch(srslte_hip_ul_rx_t* q, const void* d_iq, uint32_t tti0, uint32_t nof_sf, uint8_t* d_tb, uint32_t tb_stride,
                            uint8_t* d_tb_ok, void* stream);
@@ -474,6 +517,8 @@ typedef struct {
 } srslte_hip_ul_tx_cfg_t;
 srslte_hip_ul_tx_t* srslte_hip_ul_tx_create(const srslte_hip_ul_tx_cfg_t* cfg);
 void                srslte_hip_ul_tx_destroy(srslte_hip_ul_tx_t* q);
+/* "Sample formats": d_iq of every transmit call of the object, after 1/sqrt(N) and the half-carrier shift */
+int                 srslte_hip_ul_tx_set_iq_format(srslte_hip_ul_tx_t* q, int format, float scale);
 /* d_tb: [nof_sf][tb_stride] payload bytes (tbs/8 used); d_iq: [nof_sf][15*N] cf32 time samples; subframe b is TTI tti0 + b */
 int srslte_hip_ul_tx_batch(srslte_hip_ul_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf, void* d_iq,
                            void* stream);
@@ -529,6 +574,9 @@ typedef struct {
 } srslte_hip_dl_tx_cfg_t;
 srslte_hip_dl_tx_t* srslte_hip_dl_tx_create(const srslte_hip_dl_tx_cfg_t* cfg);
 void                srslte_hip_dl_tx_destroy(srslte_hip_dl_tx_t* q);
+/* "Sample formats": d_iq [nof_sf][nof_ports][15 N] of every transmit call of the object (fixed grant, _grants / _grants2, their _ctrl and _full
+ * forms); the guard samples of an MBSFN subframe are zero in either format */
+int                 srslte_hip_dl_tx_set_iq_format(srslte_hip_dl_tx_t* q, int format, float scale);
 /* d_tb: [nof_sf][tb_stride] payload bytes; d_iq: [nof_sf][nof_ports][15*N] cf32, one time-domain signal per antenna port; rv: the
  * redundancy version of the whole batch (the circular buffer is re-encoded, not kept) */
 int srslte_hip_dl_tx_batch(srslte_hip_dl_tx_t* q, const uint8_t* d_tb, uint32_t tb_stride, uint32_t tti0, uint32_t nof_sf, uint32_t rv, void* d_iq,

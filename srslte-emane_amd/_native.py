@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libsrslte_phy_hip.so")
 SRSLTE_SUCCESS, SRSLTE_ERROR, SRSLTE_ERROR_INVALID_INPUTS = 0, -1, -2
 MOD_BPSK, MOD_QPSK, MOD_16QAM, MOD_64QAM, MOD_256QAM = range(5)
 CRC24A, CRC24B = 0x1864CFB, 0x1800063
+IQ_CF32, IQ_SC16 = 0, 1  # SRSLTE_HIP_IQ_*: the sample format of an object's time-domain side (phy_hip.h, "Sample formats")
 
 # the spellings the SIGNATURES rows use
 vp, cint, sz, P = C.c_void_p, C.c_int, C.c_size_t, C.POINTER

@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._native import (MOD_BPSK, SRSLTE_SUCCESS, DevBuf, Handle, P, _check, cint, f32, host_copy, lib, sync, u16, u32, void, vp)
+from ._native import (IQ_CF32, IQ_SC16, MOD_BPSK, SRSLTE_SUCCESS, DevBuf, Handle, P, _check, cint, f32, host_copy, lib, sync, u16, u32, void, vp)
 
 
 class ChestDlCfg(C.Structure):
@@ -49,6 +49,7 @@ SIGNATURES = {
     "srslte_hip_ofdm_tx_sf_batch": (None, [vp, vp, vp, cint, vp]),
     "srslte_hip_ofdm_set_mbsfn": (None, [vp, cint, cint]),
     "srslte_hip_ofdm_slot_batch": (None, [vp, vp, vp, cint, cint, cint, vp]),
+    "srslte_hip_ofdm_set_sample_format": (None, [vp, cint, f32]),
     "srslte_hip_dft_batch": (None, [vp, vp, cint, cint, cint, cint, cint, f32, vp]),
     "srslte_hip_dft_precoding_valid_prb": (None, [u32]),
     "srslte_hip_dft_precoding_batch": (None, [vp, vp, u32, u32, cint, vp]),
@@ -120,6 +121,15 @@ class Ofdm(Handle):
         self.nsym = 14 if cp_norm else 12
         self.sf_len = lib().srslte_hip_ofdm_sf_len(self.h)
         self.grid_len = self.nsym * 12 * nof_prb
+        self.iq_format = IQ_CF32
+
+    def set_sample_format(self, fmt, scale=1.0):
+        """IQ_SC16: time samples are int16 pairs [nof_sf][sf_len][2] (phy_hip.h, "Sample formats"). Returns the status code; a refused call
+        leaves the object as it was."""
+        rc = lib().srslte_hip_ofdm_set_sample_format(self.h, fmt, scale)
+        if rc == SRSLTE_SUCCESS:
+            self.iq_format = fmt
+        return rc
 
     def set_normalize(self, en):
         _check(lib().srslte_hip_ofdm_set_normalize(self.h, 1 if en else 0), "set_normalize")
@@ -128,7 +138,10 @@ class Ofdm(Handle):
         _check(lib().srslte_hip_ofdm_set_freq_shift(self.h, f), "set_freq_shift")
 
     def rx_sf(self, time_samples):
-        x = np.ascontiguousarray(time_samples, np.complex64).reshape(-1, self.sf_len)
+        if self.iq_format == IQ_SC16:
+            x = np.ascontiguousarray(time_samples, np.int16).reshape(-1, 2 * self.sf_len)
+        else:
+            x = np.ascontiguousarray(time_samples, np.complex64).reshape(-1, self.sf_len)
         din, dout = DevBuf.from_host(x), DevBuf(x.shape[0] * self.grid_len * 8)
         _check(lib().srslte_hip_ofdm_rx_sf_batch(self.h, din.ptr, dout.ptr, x.shape[0], None), "ofdm_rx_sf_batch")
         sync()
@@ -139,6 +152,8 @@ class Ofdm(Handle):
         din, dout = DevBuf.from_host(x), DevBuf(x.shape[0] * self.sf_len * 8)
         _check(lib().srslte_hip_ofdm_tx_sf_batch(self.h, din.ptr, dout.ptr, x.shape[0], None), "ofdm_tx_sf_batch")
         sync()
+        if self.iq_format == IQ_SC16:
+            return dout.to_host(np.int16, 2 * x.shape[0] * self.sf_len).reshape(x.shape[0], self.sf_len, 2)
         return dout.to_host(np.complex64).reshape(x.shape[0], self.sf_len)
 
 

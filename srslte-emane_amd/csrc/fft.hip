@@ -240,43 +240,101 @@ struct OfdmGeom {
 constexpr int FFT_THREADS = 128;
 #define FFT_BOUNDS __launch_bounds__(FFT_THREADS)
 
+// Sample format of the time-domain side (phy_hip.h, "Sample formats"). A cf32 object launches the kernels with the arguments they always had;
+// the sc16 instances take the geometry with one float behind it: 1 / scale on a receive object, scale on a transmit object.
+struct OfdmGeomSc16 : OfdmGeom {
+  float iq;
+};
+template <int FMT>
+struct IqFmt {
+  using sample = cf32;
+  using geom   = OfdmGeom;
+};
+template <>
+struct IqFmt<SRSLTE_HIP_IQ_SC16> {
+  using sample = short2;
+  using geom   = OfdmGeomSc16;
+};
+
+// srslte_vec_convert_if (vector_simd.c:362-393) on one sample: the product is rounded to fp32 before the shift or the first butterfly sees it
+__device__ __forceinline__ cf32 iq_load(const short2* p, int n, const OfdmGeomSc16& g)
+{
+  const int w = reinterpret_cast<const int*>(p)[n]; // I in the low half, Q in the high half
+  return make_float2(__fmul_rn((float)(short)w, g.iq), __fmul_rn((float)(w >> 16), g.iq));
+}
+
+// The vector body of srslte_vec_convert_fi (vector_simd.c:395-422 with srslte_simd_convert_2f_s, simd.h:1681-1686: _mm256_mul_ps,
+// _mm256_cvttps_epi32, _mm256_packs_epi32) on one value: product rounded to fp32, truncated towards zero, saturated; a product that is no
+// int32 (NaN, +-inf, magnitude >= 2^31) converts to INT32_MIN there and packs to -32768. Every negative product below -32768 gives -32768 as
+// well, so only the positive side needs the test.
+__device__ __forceinline__ short iq_quant(float v, float scale)
+{
+  const float r = truncf(__fmul_rn(v, scale));
+  if (!(r < 2147483648.0f)) return (short)-32768;
+  return (short)(int)fminf(fmaxf(r, -32768.0f), 32767.0f);
+}
+__device__ __forceinline__ void iq_store(short2* p, int n, cf32 v, const OfdmGeomSc16& g)
+{
+  short2 o;
+  o.x  = iq_quant(v.x, g.iq);
+  o.y  = iq_quant(v.y, g.iq);
+  p[n] = o;
+}
+
 // grid = (nsym, nof_sf). in: [nof_sf][sf_len] time samples; out: [nof_sf][nsym][nof_re] resource grid.
 // CP strip and the half-carrier shift ride on the first pass's global loads; guard/DC strip, half swap and 1/sqrt(N) on
 // the last pass's global stores (ofdm.c:410-416): every sample is read once and every used bin written once.
-template <int R0, int R1, int R2>
-__global__ FFT_BOUNDS void ofdm_rx_kernel(const cf32* __restrict__ in, cf32* __restrict__ out, OfdmGeom g,
-                                                              const cf32* __restrict__ tw, const cf32* __restrict__ shift)
+template <int R0, int R1, int R2, int FMT = SRSLTE_HIP_IQ_CF32, bool SC16_SHIFT = false>
+__global__ FFT_BOUNDS void ofdm_rx_kernel(const typename IqFmt<FMT>::sample* __restrict__ in, cf32* __restrict__ out, typename IqFmt<FMT>::geom g,
+                                          const cf32* __restrict__ tw, const cf32* __restrict__ shift)
 {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   const int   s = blockIdx.x + g.sym0, sf = blockIdx.y, N = g.f.N, half = g.nof_re / 2;
-  const cf32* src = in + (size_t)sf * g.sf_len + g.sym_off[s] + g.cp_len[s];
+  const auto* src = in + (size_t)sf * g.sf_len + g.sym_off[s] + g.cp_len[s];
   cf32*       dst = out + ((size_t)sf * g.nsym + s) * g.nof_re;
-  fft_any<R0, R1, R2>(
-      g.f, tw, -1.0f, reinterpret_cast<cf32*>(lds_raw),
-      [&](int n) {
-        cf32 v = src[n];
-        if (shift) v = cmul(v, shift[g.cp_max + n]); // ofdm.c:369-371 with t - cplen = n
-        return v;
-      },
-      [&](int n, cf32 v) { // ofdm.c:411-412
-        v = make_float2(v.x * g.norm, v.y * g.norm);
-        if (n >= N - half) {
-          dst[n - (N - half)] = v;
-        } else if (n >= g.dc && n < g.dc + half) {
-          dst[half + n - g.dc] = v;
-        }
-      });
+  auto gst = [&](int n, cf32 v) { // ofdm.c:411-412
+    v = make_float2(v.x * g.norm, v.y * g.norm);
+    if (n >= N - half) {
+      dst[n - (N - half)] = v;
+    } else if (n >= g.dc && n < g.dc + half) {
+      dst[half + n - g.dc] = v;
+    }
+  };
+  if constexpr (FMT == SRSLTE_HIP_IQ_CF32) {
+    fft_any<R0, R1, R2>(
+        g.f, tw, -1.0f, reinterpret_cast<cf32*>(lds_raw),
+        [&](int n) {
+          cf32 v = src[n];
+          if (shift) v = cmul(v, shift[g.cp_max + n]); // ofdm.c:369-371 with t - cplen = n
+          return v;
+        },
+        gst);
+  } else {
+    // The conversion needs the sample before anything can be tested, so the half-carrier shift is an instance of its own (SC16_SHIFT, chosen by
+    // the host) and not a test per element. Without it a butterfly's 16 loads are in flight together, as in the cf32 kernel. With it the elements
+    // come one after the other, which is the order the cf32 kernel's per-element test gives them: 16 samples and 16 shift factors in flight at
+    // once cost every plan a wave of occupancy or more. The empty asm is that ordering point; it emits nothing.
+    fft_any<R0, R1, R2>(
+        g.f, tw, -1.0f, reinterpret_cast<cf32*>(lds_raw),
+        [&](int n) {
+          cf32 v = iq_load(src, n, g);
+          if constexpr (SC16_SHIFT) v = cmul(v, shift[g.cp_max + n]);
+          if constexpr (SC16_SHIFT) asm volatile("" : "+v"(v.x), "+v"(v.y) : : "memory");
+          return v;
+        },
+        gst);
+  }
 }
 
 // in: [nof_sf][nsym][nof_re] grid; out: [nof_sf][sf_len] time samples with CP.
-template <int R0, int R1, int R2>
-__global__ FFT_BOUNDS void ofdm_tx_kernel(const cf32* __restrict__ in, cf32* __restrict__ out, OfdmGeom g,
-                                                              const cf32* __restrict__ tw, const cf32* __restrict__ shift)
+template <int R0, int R1, int R2, int FMT = SRSLTE_HIP_IQ_CF32>
+__global__ FFT_BOUNDS void ofdm_tx_kernel(const cf32* __restrict__ in, typename IqFmt<FMT>::sample* __restrict__ out, typename IqFmt<FMT>::geom g,
+                                          const cf32* __restrict__ tw, const cf32* __restrict__ shift)
 {
   extern __shared__ __align__(16) unsigned char lds_raw[];
   const int   s = blockIdx.x + g.sym0, sf = blockIdx.y, N = g.f.N, half = g.nof_re / 2, cp = g.cp_len[s];
   const cf32* src = in + ((size_t)sf * g.nsym + s) * g.nof_re;
-  cf32*       dst = out + (size_t)sf * g.sf_len + g.sym_off[s];
+  auto*       dst = out + (size_t)sf * g.sf_len + g.sym_off[s];
   fft_any<R0, R1, R2>(
       g.f, tw, 1.0f, reinterpret_cast<cf32*>(lds_raw),
       [&](int n) { // ofdm.c:509-515 (guards and DC stay zero)
@@ -286,10 +344,18 @@ __global__ FFT_BOUNDS void ofdm_tx_kernel(const cf32* __restrict__ in, cf32* __r
       },
       [&](int n, cf32 v) { // ofdm.c:519-529: body, and the tail again as cyclic prefix
         v = make_float2(v.x * g.norm, v.y * g.norm);
-        dst[cp + n] = shift ? cmul(v, shift[g.cp_max + n]) : v;
-        if (n >= N - cp) {
-          const int t = n - (N - cp);
-          dst[t]      = shift ? cmul(v, shift[g.cp_max + t - cp]) : v;
+        if constexpr (FMT == SRSLTE_HIP_IQ_CF32) {
+          dst[cp + n] = shift ? cmul(v, shift[g.cp_max + n]) : v;
+          if (n >= N - cp) {
+            const int t = n - (N - cp);
+            dst[t]      = shift ? cmul(v, shift[g.cp_max + t - cp]) : v;
+          }
+        } else { // the same two values, each through srslte_vec_convert_fi
+          iq_store(dst, cp + n, shift ? cmul(v, shift[g.cp_max + n]) : v, g);
+          if (n >= N - cp) {
+            const int t = n - (N - cp);
+            iq_store(dst, t, shift ? cmul(v, shift[g.cp_max + t - cp]) : v, g);
+          }
         }
       });
 }
@@ -396,17 +462,29 @@ int factorize(int N, FftFactors* f)
 static size_t fft_lds_bytes(const FftFactors& f) { return (f.inplace ? 1 : 2) * sizeof(cf32) * (size_t)(f.N + f.N / 16 + 2); }
 
 // launches KERNEL<plan> for the transform size: fixed plans for the OFDM sizes, <0,0,0> = generic otherwise
+#define FFT_CASES(KERNEL, TAIL, GRID, BLOCK, LDS, STREAM, ...)                                                        \
+  case 128: hipLaunchKernelGGL((KERNEL<16, 8, 1 TAIL()>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;              \
+  case 256: hipLaunchKernelGGL((KERNEL<16, 16, 1 TAIL()>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;             \
+  case 384: hipLaunchKernelGGL((KERNEL<16, 8, 3 TAIL()>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;              \
+  case 512: hipLaunchKernelGGL((KERNEL<16, 16, 2 TAIL()>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;             \
+  case 768: hipLaunchKernelGGL((KERNEL<16, 16, 3 TAIL()>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;             \
+  case 1024: hipLaunchKernelGGL((KERNEL<16, 16, 4 TAIL()>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;            \
+  case 1536: hipLaunchKernelGGL((KERNEL<16, 16, 6 TAIL()>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;            \
+  case 2048: hipLaunchKernelGGL((KERNEL<16, 16, 8 TAIL()>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;
+#define FFT_TAIL_NONE()
 #define FFT_DISPATCH(KERNEL, N, GRID, BLOCK, LDS, STREAM, ...)                                                        \
   switch (N) {                                                                                                        \
-    case 128: hipLaunchKernelGGL((KERNEL<16, 8, 1>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;                   \
-    case 256: hipLaunchKernelGGL((KERNEL<16, 16, 1>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;                  \
-    case 384: hipLaunchKernelGGL((KERNEL<16, 8, 3>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;                   \
-    case 512: hipLaunchKernelGGL((KERNEL<16, 16, 2>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;                  \
-    case 768: hipLaunchKernelGGL((KERNEL<16, 16, 3>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;                  \
-    case 1024: hipLaunchKernelGGL((KERNEL<16, 16, 4>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;                 \
-    case 1536: hipLaunchKernelGGL((KERNEL<16, 16, 6>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;                 \
-    case 2048: hipLaunchKernelGGL((KERNEL<16, 16, 8>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;                 \
+    FFT_CASES(KERNEL, FFT_TAIL_NONE, GRID, BLOCK, LDS, STREAM, __VA_ARGS__)                                           \
     default: hipLaunchKernelGGL((KERNEL<0, 0, 0>), GRID, BLOCK, LDS, STREAM, __VA_ARGS__); break;                     \
+  }
+// the fixed plans only, with further template arguments behind the plan (TAIL: a macro that gives them with their leading comma): the sc16
+// instances of the OFDM kernels. An OFDM object has one of the eight sizes (srslte_hip_ofdm_create_sz), so there is no generic sc16 instance.
+#define FFT_TAIL_SC16() , SRSLTE_HIP_IQ_SC16
+#define FFT_TAIL_SC16_SHIFT() , SRSLTE_HIP_IQ_SC16, true
+#define FFT_DISPATCH_FIXED(KERNEL, TAIL, N, GRID, BLOCK, LDS, STREAM, ...)                                            \
+  switch (N) {                                                                                                        \
+    FFT_CASES(KERNEL, TAIL, GRID, BLOCK, LDS, STREAM, __VA_ARGS__)                                                    \
+    default: return SRSLTE_ERROR;                                                                                     \
   }
 
 } // namespace
@@ -445,6 +523,8 @@ struct srslte_hip_ofdm {
   bool         is_rx = false, normalize = false;
   float        freq_shift_f = 0.f;
   int          nof_prb      = 0;
+  int          iq_format    = SRSLTE_HIP_IQ_CF32; // of d_in_time (receive) / d_out_time (transmit)
+  float        iq_scale     = 1.0f;
 };
 
 extern "C" srslte_hip_ofdm_t* srslte_hip_ofdm_create(int nof_prb, int cp_is_norm, int is_rx)
@@ -553,6 +633,15 @@ extern "C" int srslte_hip_ofdm_set_freq_shift(srslte_hip_ofdm_t* q, float freq_s
   return SRSLTE_SUCCESS;
 }
 
+extern "C" int srslte_hip_ofdm_set_sample_format(srslte_hip_ofdm_t* q, int format, float scale)
+{
+  if (!q || (format != SRSLTE_HIP_IQ_CF32 && format != SRSLTE_HIP_IQ_SC16) || !std::isfinite(scale) || !(scale > 0.0f))
+    return SRSLTE_ERROR_INVALID_INPUTS;
+  q->iq_format = format;
+  q->iq_scale  = scale;
+  return SRSLTE_SUCCESS;
+}
+
 extern "C" void srslte_hip_ofdm_destroy(srslte_hip_ofdm_t* q) { delete q; }
 
 static int ofdm_launch(srslte_hip_ofdm_t* q, const void* d_in, void* d_out, int nof_sf, int sym0, int nsym, bool mbsfn_layout, void* stream)
@@ -561,7 +650,21 @@ static int ofdm_launch(srslte_hip_ofdm_t* q, const void* d_in, void* d_out, int 
   OfdmGeom g = mbsfn_layout ? q->gm : q->g;
   g.sym0     = sym0;
   dim3 grid(nsym, nof_sf);
-  if (q->is_rx) {
+  if (q->iq_format == SRSLTE_HIP_IQ_SC16) {
+    OfdmGeomSc16 gs;
+    static_cast<OfdmGeom&>(gs) = g;
+    gs.iq                      = q->is_rx ? 1.0f / q->iq_scale : q->iq_scale; // the gain of srslte_vec_convert_if, computed once
+    if (q->is_rx && q->d_shift) {
+      FFT_DISPATCH_FIXED(ofdm_rx_kernel, FFT_TAIL_SC16_SHIFT, g.f.N, grid, dim3(fft_threads(g.f.N)), fft_lds_bytes(g.f), (hipStream_t)stream,
+                     (const short2*)d_in, (cf32*)d_out, gs, q->d_tw, (const cf32*)q->d_shift.get());
+    } else if (q->is_rx) {
+      FFT_DISPATCH_FIXED(ofdm_rx_kernel, FFT_TAIL_SC16, g.f.N, grid, dim3(fft_threads(g.f.N)), fft_lds_bytes(g.f), (hipStream_t)stream,
+                     (const short2*)d_in, (cf32*)d_out, gs, q->d_tw, (const cf32*)nullptr);
+    } else {
+      FFT_DISPATCH_FIXED(ofdm_tx_kernel, FFT_TAIL_SC16, g.f.N, grid, dim3(fft_threads(g.f.N)), fft_lds_bytes(g.f), (hipStream_t)stream,
+                     (const cf32*)d_in, (short2*)d_out, gs, q->d_tw, (const cf32*)q->d_shift.get());
+    }
+  } else if (q->is_rx) {
     FFT_DISPATCH(ofdm_rx_kernel, g.f.N, grid, dim3(fft_threads(g.f.N)), fft_lds_bytes(g.f), (hipStream_t)stream, (const cf32*)d_in,
                  (cf32*)d_out, g, q->d_tw, (const cf32*)q->d_shift.get());
   } else {
@@ -593,6 +696,7 @@ extern "C" int srslte_hip_ofdm_slot_batch(srslte_hip_ofdm_t* q, const void* d_in
 
 extern "C" int srslte_hip_ofdm_symbol_sz(const srslte_hip_ofdm_t* q) { return q ? q->g.f.N : -1; }
 extern "C" int srslte_hip_ofdm_sf_len(const srslte_hip_ofdm_t* q) { return q ? q->g.sf_len : -1; }
+size_t ofdm_sample_bytes(const srslte_hip_ofdm_t* q) { return q->iq_format == SRSLTE_HIP_IQ_SC16 ? 2 * sizeof(int16_t) : sizeof(cf32); }
 
 // ---------------------------------------------------------------- generic DFT + transform precoding
 extern "C" int srslte_hip_dft_batch(const void* d_in, void* d_out, int N, int howmany, int idist, int odist, int forward, float scale,

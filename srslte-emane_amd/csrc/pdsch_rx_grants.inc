@@ -519,6 +519,7 @@ struct srslte_hip_dl_rx_pool {
   std::vector<hipStream_t>         st;
   std::vector<hipEvent_t>          ev;
   std::vector<int64_t>             last; // ticket of the batch each object works on, -1: none
+  std::vector<DevBuf<uint8_t>>     iq;   // submit_host: one batch of time samples per object, allocated by the first such call
   int64_t                          next = 0;
   ~srslte_hip_dl_rx_pool()
   {
@@ -541,6 +542,7 @@ extern "C" srslte_hip_dl_rx_pool_t* srslte_hip_dl_rx_pool_create(const srslte_hi
   p->st.assign(depth, nullptr);
   p->ev.assign(depth, nullptr);
   p->last.assign(depth, -1);
+  p->iq.resize(depth);
   for (uint32_t i = 0; i < depth; i++) {
     p->rx[i] = srslte_hip_dl_rx_create(cfg);
     if (!p->rx[i] || hipStreamCreateWithFlags(&p->st[i], hipStreamNonBlocking) != hipSuccess ||
@@ -567,6 +569,35 @@ extern "C" int64_t srslte_hip_dl_rx_pool_submit(srslte_hip_dl_rx_pool_t* p, cons
   if (hipEventRecord(p->ev[i], p->st[i]) != hipSuccess) return SRSLTE_ERROR;
   p->last[i] = p->next;
   return p->next++;
+}
+
+extern "C" int srslte_hip_dl_rx_pool_set_iq_format(srslte_hip_dl_rx_pool_t* p, int format, float scale)
+{
+  if (!p || p->next != 0) return SRSLTE_ERROR_INVALID_INPUTS; // before the first submit: no batch is in flight in the other format
+  for (auto* rx : p->rx)
+    if (int r = srslte_hip_dl_rx_set_iq_format(rx, format, scale)) return r; // the first object refuses what any would: none is changed
+  return SRSLTE_SUCCESS;
+}
+
+extern "C" int64_t srslte_hip_dl_rx_pool_submit_host(srslte_hip_dl_rx_pool_t* p, const void* h_iq, uint32_t tti0, uint32_t nof_sf, const srslte_hip_dl_grant_t* grants,
+                                                     uint8_t* d_tb, uint32_t tb_stride, uint8_t* d_tb_ok, void* h_record)
+{
+  if (!p || !h_iq || !d_tb || !d_tb_ok || nof_sf > p->rx[0]->cfg.max_batch) return SRSLTE_ERROR_INVALID_INPUTS;
+  const size_t          i  = (size_t)(p->next % (int64_t)p->rx.size());
+  srslte_hip_dl_rx_t*   rx = p->rx[i];
+  const size_t          sf_bytes = ofdm_sample_bytes(rx->ofdm) * (size_t)rx->pg.nof_rx * (size_t)srslte_hip_ofdm_sf_len(rx->ofdm);
+  if (!p->iq[0]) { // sized for either format, so that the buffers never move
+    for (auto& b : p->iq)
+      if (b.alloc(sizeof(cf32) * (size_t)rx->pg.nof_rx * (size_t)srslte_hip_ofdm_sf_len(rx->ofdm) * rx->cfg.max_batch)) {
+        for (auto& c : p->iq) c = DevBuf<uint8_t>();
+        hip_log("[srslte_hip] dl_rx_pool: device allocation failed\n");
+        return SRSLTE_ERROR;
+      }
+  }
+  // the staging buffer is the object's: its previous batch has to be through before the copy overwrites it. submit() waits for the same event.
+  if (p->last[i] >= 0 && hipEventSynchronize(p->ev[i]) != hipSuccess) return SRSLTE_ERROR;
+  if (nof_sf && hipMemcpyAsync(p->iq[i], h_iq, sf_bytes * nof_sf, hipMemcpyHostToDevice, p->st[i]) != hipSuccess) return SRSLTE_ERROR;
+  return srslte_hip_dl_rx_pool_submit(p, p->iq[i], tti0, nof_sf, grants, d_tb, tb_stride, d_tb_ok, h_record);
 }
 
 extern "C" int srslte_hip_dl_rx_pool_wait(srslte_hip_dl_rx_pool_t* p, int64_t ticket)

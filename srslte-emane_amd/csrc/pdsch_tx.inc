@@ -262,6 +262,12 @@ struct srslte_hip_dl_tx {
 
 extern "C" void srslte_hip_dl_tx_destroy(srslte_hip_dl_tx_t* q) { delete q; }
 
+// phy_hip.h, "Sample formats": d_iq of every entry point of the object is in the OFDM object's format from here on
+extern "C" int srslte_hip_dl_tx_set_iq_format(srslte_hip_dl_tx_t* q, int format, float scale)
+{
+  return q ? srslte_hip_ofdm_set_sample_format(q->ofdm, format, scale) : SRSLTE_ERROR_INVALID_INPUTS;
+}
+
 extern "C" srslte_hip_dl_tx_t* srslte_hip_dl_tx_create(const srslte_hip_dl_tx_cfg_t* cfg)
 {
   if (!cfg || cfg->max_batch == 0 || cfg->mod < 1 || cfg->mod > 4 || cfg->nof_ports > 4 || cfg->nof_ports == 3 || cfg->nof_prb < 6 || cfg->nof_prb > 110) {
@@ -372,7 +378,7 @@ extern "C" int srslte_hip_dl_tx_batch(srslte_hip_dl_tx_t* q, const uint8_t* d_tb
                      (const cf32*)srslte_hip_chest_dl_pilots(q->crs), q->d_grid, 8 * (int)q->cfg.nof_prb, g);
   LAUNCH_CHECK();
   if (q->cfg.mbsfn) { // srslte_ofdm_tx_slot_mbsfn skips the guard between the two regions (ofdm.c:558-574): those samples are zero here, not left-overs
-    HIP_TRY(hipMemsetAsync(d_iq, 0, sizeof(cf32) * (size_t)srslte_hip_ofdm_sf_len(q->ofdm) * nof_sf, st));
+    HIP_TRY(hipMemsetAsync(d_iq, 0, ofdm_sample_bytes(q->ofdm) * (size_t)srslte_hip_ofdm_sf_len(q->ofdm) * nof_sf, st));
   }
   return srslte_hip_ofdm_tx_sf_batch(q->ofdm, q->d_grid, d_iq, (int)nof_sf * g.nof_ports, stream);
 }

@@ -13,6 +13,7 @@ struct FftFactors {
 
 // Returns (creating on first use, per device) the factorisation and the device twiddle table exp(-j2*pi*k/N).
 int fft_get_plan(int N, FftFactors* f, const cf32** d_tw);
+size_t ofdm_sample_bytes(const srslte_hip_ofdm_t* q); // of one time-domain sample in the object's format (phy_hip.h, "Sample formats")
 
 
 // Gold sequence c(n) of 36.211 7.2 (sequence.c:48-79), host side, for init-time tables.

@@ -406,6 +406,12 @@ extern "C" const uint8_t* srslte_hip_ul_rx_grants_ri(const srslte_hip_ul_rx_t* q
 
 extern "C" void srslte_hip_ul_rx_destroy(srslte_hip_ul_rx_t* q) { delete q; }
 
+// phy_hip.h, "Sample formats": d_iq of every entry point of the object is in the OFDM object's format from here on
+extern "C" int srslte_hip_ul_rx_set_iq_format(srslte_hip_ul_rx_t* q, int format, float scale)
+{
+  return q ? srslte_hip_ofdm_set_sample_format(q->ofdm, format, scale) : SRSLTE_ERROR_INVALID_INPUTS;
+}
+
 extern "C" srslte_hip_ul_rx_t* srslte_hip_ul_rx_create(const srslte_hip_ul_rx_cfg_t* cfg)
 {
   if (!cfg || cfg->max_batch == 0 || cfg->mod < 1 || cfg->mod > 3 || cfg->max_iterations == 0 || cfg->L_prb < 1 ||

@@ -287,6 +287,12 @@ struct srslte_hip_ul_tx {
 
 extern "C" void srslte_hip_ul_tx_destroy(srslte_hip_ul_tx_t* q) { delete q; }
 
+// phy_hip.h, "Sample formats": d_iq of every entry point of the object is in the OFDM object's format from here on
+extern "C" int srslte_hip_ul_tx_set_iq_format(srslte_hip_ul_tx_t* q, int format, float scale)
+{
+  return q ? srslte_hip_ofdm_set_sample_format(q->ofdm, format, scale) : SRSLTE_ERROR_INVALID_INPUTS;
+}
+
 extern "C" srslte_hip_ul_tx_t* srslte_hip_ul_tx_create(const srslte_hip_ul_tx_cfg_t* cfg)
 {
   if (!cfg || cfg->max_batch == 0 || cfg->mod < 1 || cfg->mod > 3 || cfg->L_prb < 1 || cfg->n_prb + cfg->L_prb > cfg->nof_prb ||

@@ -4,8 +4,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._native import (SRSLTE_SUCCESS, DevBuf, DevView, Handle, P, _check, cint, host_copy, i64, lib, read_structs, result_structs, struct_array,
-                      symbol_sz, sync, u32, void, vp)
+from ._native import (IQ_CF32, IQ_SC16, SRSLTE_SUCCESS, DevBuf, DevView, Handle, P, _check, cint, f32, host_copy, i64, lib, read_structs,
+                      result_structs, struct_array, symbol_sz, sync, u32, void, vp)
 from .core import ChestDlCfg, DmrsPuschCfg
 from .csi import CsiRes
 from .dl_ctrl import _ctrl_tx_in
@@ -107,6 +107,7 @@ SIGNATURES = {
     # PDSCH receive pipeline
     "srslte_hip_dl_rx_create": (vp, [P(DlRxCfg)]),
     "srslte_hip_dl_rx_destroy": (void, [vp]),
+    "srslte_hip_dl_rx_set_iq_format": (None, [vp, cint, f32]),
     "srslte_hip_dl_rx_nof_re": (u32, [vp, u32]),
     "srslte_hip_dl_rx_batch": (None, _RX_BATCH),
     "srslte_hip_dl_rx_batch_harq": (None, _RX_HARQ),
@@ -119,6 +120,8 @@ SIGNATURES = {
     "srslte_hip_dl_rx_pool_destroy": (void, [vp]),
     "srslte_hip_dl_rx_pool_submit": (i64, [vp, vp, u32, u32, vp, vp, u32, vp, vp]),
     "srslte_hip_dl_rx_pool_wait": (None, [vp, i64]),
+    "srslte_hip_dl_rx_pool_set_iq_format": (None, [vp, cint, f32]),
+    "srslte_hip_dl_rx_pool_submit_host": (i64, [vp, vp, u32, u32, vp, vp, u32, vp, vp]),
     "srslte_hip_dl_rx_stage": (None, [vp, cint, vp, u32, u32, vp, u32, vp, vp]),
     "srslte_hip_dl_rx_debug_buffer": (vp, [vp, cint]),
     "srslte_hip_dl_rx_keep_symbols": (None, [vp, cint]),
@@ -127,6 +130,7 @@ SIGNATURES = {
     # PUSCH receive pipeline
     "srslte_hip_ul_rx_create": (vp, [P(UlRxCfg)]),
     "srslte_hip_ul_rx_destroy": (void, [vp]),
+    "srslte_hip_ul_rx_set_iq_format": (None, [vp, cint, f32]),
     "srslte_hip_ul_rx_batch": (None, _RX_BATCH),
     "srslte_hip_ul_rx_batch_harq": (None, _RX_HARQ),
     "srslte_hip_ul_rx_batch_grants": (None, [vp, vp, u32, u32, vp, u32, vp, u32, vp, vp]),
@@ -140,6 +144,7 @@ SIGNATURES = {
     # PUSCH transmit pipeline
     "srslte_hip_ul_tx_create": (vp, [P(UlTxCfg)]),
     "srslte_hip_ul_tx_destroy": (void, [vp]),
+    "srslte_hip_ul_tx_set_iq_format": (None, [vp, cint, f32]),
     "srslte_hip_ul_tx_batch": (None, [vp, vp, u32, u32, u32, vp, vp]),
     "srslte_hip_ul_tx_batch_ack": (None, [vp, vp, u32, vp, u32, u32, vp, vp]),
     "srslte_hip_ul_tx_batch_uci": (None, [vp, vp, u32, vp, vp, u32, u32, vp, vp]),
@@ -150,6 +155,7 @@ SIGNATURES = {
     # PDSCH transmit pipeline
     "srslte_hip_dl_tx_create": (vp, [P(DlTxCfg)]),
     "srslte_hip_dl_tx_destroy": (void, [vp]),
+    "srslte_hip_dl_tx_set_iq_format": (None, [vp, cint, f32]),
     "srslte_hip_dl_tx_batch": (None, [vp, vp, u32, u32, u32, u32, vp, vp]),
     "srslte_hip_dl_tx_batch_grants": (None, _DL_TX_GRANTS),
     "srslte_hip_dl_tx_batch_grants2": (None, _DL_TX_GRANTS),
@@ -158,12 +164,34 @@ SIGNATURES = {
 
 
 class Pipeline(Handle):
-    """A pipeline object: a handle with debug buffers, read through the C function DEBUG names."""
+    """A pipeline object: a handle with debug buffers, read through the C function DEBUG names, and the sample format of its time-domain side
+    (phy_hip.h, "Sample formats"), set through the C function IQ_FORMAT names."""
 
-    DEBUG = None
+    DEBUG = IQ_FORMAT = None
+    iq_format = IQ_CF32
 
     def debug(self, which, dtype, count):
         return host_copy(getattr(lib(), self.DEBUG)(self.h, which), dtype, count)
+
+    def set_iq_format(self, fmt, scale=1.0):
+        """IQ_SC16: the object's time samples are int16 pairs, arrays [...][sf_len][2] (I, Q) where they were complex [...][sf_len]; scale as
+        srslte_vec_convert_if / _fi take it. Returns the status code; a refused call leaves the object as it was."""
+        rc = getattr(lib(), self.IQ_FORMAT)(self.h, fmt, scale)
+        if rc == SRSLTE_SUCCESS:
+            self.iq_format = fmt
+        return rc
+
+    def _iq_in(self, iq, width):
+        """The caller's time samples as [nof_sf][width] rows of the object's format (int16: 2 * width values per row)."""
+        if self.iq_format == IQ_SC16:
+            return np.ascontiguousarray(iq, np.int16).reshape(-1, 2 * width)
+        return np.ascontiguousarray(iq, np.complex64).reshape(-1, width)
+
+    def _iq_out(self, *shape):
+        """self.d_iq as an array of that shape in the object's format (int16: a last axis of 2)."""
+        if self.iq_format == IQ_SC16:
+            return self.d_iq.to_host(np.int16, 2 * int(np.prod(shape))).reshape(shape + (2,))
+        return self.d_iq.to_host(np.complex64).reshape(shape)
 
 
 def _tb_rows(d_tb, d_ok, stride, n, nbytes=None):
@@ -179,7 +207,7 @@ def _tb_rows2(d_tb, d_ok, stride, n, nbytes=(None, None)):
 
 class DlRx(Pipeline):
     """Batched PDSCH receive chain (ue_dl.c:369-384 + pdsch.c:833-997 + sch.c:507-532 for one codeword)."""
-    DESTROY, DEBUG = "srslte_hip_dl_rx_destroy", "srslte_hip_dl_rx_debug_buffer"
+    DESTROY, DEBUG, IQ_FORMAT = "srslte_hip_dl_rx_destroy", "srslte_hip_dl_rx_debug_buffer", "srslte_hip_dl_rx_set_iq_format"
 
     def __init__(self, cell_id, nof_prb, cfi, rnti, mod, tbs, max_iterations, max_batch, mmse=True, chest_cfg=None, llr_8bit=False, nof_rx=1,
                  nof_ports=1, csi=False, power_scale=False, p_a=0.0, out_ptrs=None, tx_scheme=0, pmi=0, mod2=0, tbs2=0, cp_ext=False, tdd=None,
@@ -226,7 +254,7 @@ class DlRx(Pipeline):
         return _tb_rows2(self.d_tb, self.d_ok, self.tb_stride, n, (self.tbs // 8 + 3, self.tbs2 // 8 + 3))
 
     def decode(self, iq, tti0=0):
-        x = np.ascontiguousarray(iq, np.complex64).reshape(-1, self.nof_rx * self.sf_len)  # [nsf][nof_rx][sf_len]
+        x = self._iq_in(iq, self.nof_rx * self.sf_len)  # [nsf][nof_rx][sf_len]
         din = DevBuf.from_host(x)
         _check(self.run_device(din.ptr, tti0, x.shape[0]), "dl_rx_batch")
         sync()
@@ -234,7 +262,7 @@ class DlRx(Pipeline):
 
     def decode_harq2(self, iq, tti0, rv, new_data):
         """srslte_hip_dl_rx_batch_harq2: rv / new_data per transport block (two-layer modes)."""
-        x = np.ascontiguousarray(iq, np.complex64).reshape(-1, self.nof_rx * self.sf_len)
+        x = self._iq_in(iq, self.nof_rx * self.sf_len)
         din = DevBuf.from_host(x)
         n = x.shape[0]
         _check(lib().srslte_hip_dl_rx_batch_harq2(self.h, din.ptr, tti0, n, (C.c_uint32 * 2)(*rv), (C.c_int * 2)(*[1 if v else 0 for v in new_data]),
@@ -244,7 +272,7 @@ class DlRx(Pipeline):
 
     def decode_grants(self, iq, tti0, grants):
         """srslte_hip_dl_rx_batch_grants: subframe b with grants[b] (DlGrant). Returns (rc, tb [nsf][tbs_max/8+3], ok [nsf])."""
-        x = np.ascontiguousarray(iq, np.complex64).reshape(-1, self.nof_rx * self.sf_len)
+        x = self._iq_in(iq, self.nof_rx * self.sf_len)
         assert len(grants) == x.shape[0]
         arr = (DlGrant * len(grants))(*grants)
         din = DevBuf.from_host(x)
@@ -258,7 +286,10 @@ class DlRx(Pipeline):
         """srslte_hip_dl_rx_batch_grants2: subframe b with grants[b] (DlGrant2: scheme, pmi and a second transport block per subframe).
         Returns (rc, [tb0 rows, tb1 rows], [ok0, ok1]); on a cell without two-layer grants the second entries are None.
         from_grid: iq holds frequency-domain grids [nsf][nof_rx][14 * 12 * nof_prb] (srslte_hip_dl_rx_grid_batch_grants2)."""
-        x = np.ascontiguousarray(iq, np.complex64).reshape(-1, self.nof_rx * (14 * 12 * self.cfg.nof_prb if from_grid else self.sf_len))
+        if from_grid:
+            x = np.ascontiguousarray(iq, np.complex64).reshape(-1, self.nof_rx * 14 * 12 * self.cfg.nof_prb)
+        else:
+            x = self._iq_in(iq, self.nof_rx * self.sf_len)
         n = x.shape[0]
         assert len(grants) == n
         arr = (DlGrant2 * n)(*grants)
@@ -275,7 +306,7 @@ class DlRx(Pipeline):
 
     def decode_harq(self, iq, tti0, rv, new_data):
         """srslte_hip_dl_rx_batch_harq: slot b keeps its soft buffers / CRC flags / bytes between calls."""
-        x = np.ascontiguousarray(iq, np.complex64).reshape(-1, self.nof_rx * self.sf_len)
+        x = self._iq_in(iq, self.nof_rx * self.sf_len)
         din = DevBuf.from_host(x)
         _check(lib().srslte_hip_dl_rx_batch_harq(self.h, din.ptr, tti0, x.shape[0], rv, 1 if new_data else 0, self.d_tb.ptr, self.tb_stride,
                                                  self.d_ok.ptr, None), "dl_rx_batch_harq")
@@ -299,9 +330,32 @@ class DlRx(Pipeline):
         return result_structs(lib().srslte_hip_dl_rx_csi_batch(self.h, nof_sf, dout.ptr, None), dout.ptr, CsiRes, nof_sf)
 
 
+class DlRxPool(Handle):
+    """srslte_hip_dl_rx_pool_*: `depth` receive pipelines behind one submission call; cfg: a DlRxCfg (e.g. DlRx(...).cfg). Pointers are the
+    caller's: device d_iq / d_tb / d_tb_ok, pinned host h_iq / h_record. submit calls return the ticket, or the negative status code."""
+    DESTROY = "srslte_hip_dl_rx_pool_destroy"
+
+    def __init__(self, cfg, depth):
+        self._create("srslte_hip_dl_rx_pool_create", C.byref(cfg), depth)
+
+    def set_iq_format(self, fmt, scale=1.0):
+        return lib().srslte_hip_dl_rx_pool_set_iq_format(self.h, fmt, scale)
+
+    def submit(self, d_iq, tti0, nof_sf, d_tb, tb_stride, d_tb_ok, grants=None, h_record=None):
+        arr = (DlGrant * len(grants))(*grants) if grants else None
+        return lib().srslte_hip_dl_rx_pool_submit(self.h, d_iq, tti0, nof_sf, arr, d_tb, tb_stride, d_tb_ok, h_record)
+
+    def submit_host(self, h_iq, tti0, nof_sf, d_tb, tb_stride, d_tb_ok, grants=None, h_record=None):
+        arr = (DlGrant * len(grants))(*grants) if grants else None
+        return lib().srslte_hip_dl_rx_pool_submit_host(self.h, h_iq, tti0, nof_sf, arr, d_tb, tb_stride, d_tb_ok, h_record)
+
+    def wait(self, ticket):
+        return lib().srslte_hip_dl_rx_pool_wait(self.h, ticket)
+
+
 class UlRx(Pipeline):
     """Batched PUSCH receive chain (enb_ul.c + pusch.c:423-520 + the UL-SCH part of sch.c:991-1066)."""
-    DESTROY, DEBUG = "srslte_hip_ul_rx_destroy", "srslte_hip_ul_rx_debug_buffer"
+    DESTROY, DEBUG, IQ_FORMAT = "srslte_hip_ul_rx_destroy", "srslte_hip_ul_rx_debug_buffer", "srslte_hip_ul_rx_set_iq_format"
 
     def __init__(self, cell_id, nof_prb, rnti, mod, tbs, L_prb, n_prb, n_dmrs, max_iterations, max_batch, cyclic_shift=0, delta_ss=0,
                  group_hopping=False, sequence_hopping=False, mmse=True, shortened=False, ack_len=0, I_offset_ack=0, ri_len=0, I_offset_ri=0,
@@ -323,7 +377,7 @@ class UlRx(Pipeline):
 
     def decode_grants(self, iq, tti0, grants):
         """srslte_hip_ul_rx_batch_grants: grants = list of UlGrant; row p of the result belongs to grants[p]."""
-        x = np.ascontiguousarray(iq, np.complex64).reshape(-1, self.sf_len)
+        x = self._iq_in(iq, self.sf_len)
         din = DevBuf.from_host(x)
         arr = (UlGrant * len(grants))(*grants)
         _check(lib().srslte_hip_ul_rx_batch_grants(self.h, din.ptr, tti0, x.shape[0], arr, len(grants), self.d_tb.ptr, self.tb_stride, self.d_ok.ptr, None),
@@ -334,7 +388,7 @@ class UlRx(Pipeline):
 
     def decode_grants_pucch(self, iq, tti0, grants, ctrl, reqs):
         """srslte_hip_ul_rx_batch_grants_pucch: (rc, tb, tb_ok, [PucchRes]); grants may be empty."""
-        x = np.ascontiguousarray(iq, np.complex64).reshape(-1, self.sf_len)
+        x = self._iq_in(iq, self.sf_len)
         din = DevBuf.from_host(x)
         dres = DevBuf(C.sizeof(PucchRes) * max(1, len(reqs)))
         rc = lib().srslte_hip_ul_rx_batch_grants_pucch(self.h, din.ptr, tti0, x.shape[0], struct_array(UlGrant, grants), len(grants), self.d_tb.ptr,
@@ -347,7 +401,7 @@ class UlRx(Pipeline):
 
     def decode_grants_pucch_srs(self, iq, tti0, grants, ctrl, reqs, srs, ues):
         """srslte_hip_ul_rx_batch_grants_pucch_srs: (rc, tb, tb_ok, [PucchRes], [SrsRes], ce); ctrl and srs may each be None."""
-        x = np.ascontiguousarray(iq, np.complex64).reshape(-1, self.sf_len)
+        x = self._iq_in(iq, self.sf_len)
         din = DevBuf.from_host(x)
         dres = DevBuf(C.sizeof(PucchRes) * max(1, len(reqs)))
         dsr, dsc = DevBuf(C.sizeof(SrsRes) * max(1, len(ues))), DevBuf(8 * SRS_MAX_CE * max(1, len(ues)))
@@ -373,7 +427,7 @@ class UlRx(Pipeline):
         return out[:64 * self.rows_grants].reshape(-1, 64)[:n], out[64 * self.rows_grants:][:n]
 
     def decode(self, iq, tti0=0):
-        x = np.ascontiguousarray(iq, np.complex64).reshape(-1, self.sf_len)
+        x = self._iq_in(iq, self.sf_len)
         din = DevBuf.from_host(x)
         _check(lib().srslte_hip_ul_rx_batch(self.h, din.ptr, tti0, x.shape[0], self.d_tb.ptr, self.tb_stride, self.d_ok.ptr, None), "ul_rx_batch")
         sync()
@@ -382,7 +436,7 @@ class UlRx(Pipeline):
 
     def decode_harq(self, iq, tti0, rv, new_data):
         """srslte_hip_ul_rx_batch_harq: slot b keeps its soft buffers between calls; new_data starts new transport blocks."""
-        x = np.ascontiguousarray(iq, np.complex64).reshape(-1, self.sf_len)
+        x = self._iq_in(iq, self.sf_len)
         din = DevBuf.from_host(x)
         _check(lib().srslte_hip_ul_rx_batch_harq(self.h, din.ptr, tti0, x.shape[0], rv, 1 if new_data else 0, self.d_tb.ptr, self.tb_stride,
                                                  self.d_ok.ptr, None), "ul_rx_batch_harq")
@@ -435,7 +489,7 @@ def _tb_upload(tbs_bytes, n, stride):
 class UlTx(Pipeline):
     """Batched PUSCH transmit chain (srslte_ue_ul_encode ue_ul.c:300-340: srslte_pusch_encode pusch.c:314-421 with the UL-SCH part of
     srslte_ulsch_encode sch.c:1068-1160, DMRS, srslte_ofdm_tx_sf with ue_ul.c:59-64 settings)."""
-    DESTROY, DEBUG = "srslte_hip_ul_tx_destroy", "srslte_hip_ul_tx_debug_buffer"
+    DESTROY, DEBUG, IQ_FORMAT = "srslte_hip_ul_tx_destroy", "srslte_hip_ul_tx_debug_buffer", "srslte_hip_ul_tx_set_iq_format"
 
     def __init__(self, cell_id, nof_prb, rnti, mod, tbs, L_prb, n_prb, n_dmrs, max_batch, cyclic_shift=0, delta_ss=0, group_hopping=False,
                  sequence_hopping=False, shortened=False, ack_len=0, I_offset_ack=0, ri_len=0, I_offset_ri=0, cqi_len=0, I_offset_cqi=0,
@@ -459,7 +513,7 @@ class UlTx(Pipeline):
         _check(lib().srslte_hip_ul_tx_batch_grants(self.h, din.ptr, stride, *[_ptr(b) for b in bufs], tti0, nof_sf, struct_array(UlGrant, grants), n,
                                                    self.d_iq.ptr, None), "ul_tx_batch_grants")
         sync()
-        return self.d_iq.to_host(np.complex64).reshape(self.max_batch, self.sf_len)[:nof_sf]
+        return self._iq_out(self.max_batch, self.sf_len)[:nof_sf]
 
     def encode(self, tb, tti0=0, ack=None, ri=None, cqi=None, rv=None):
         """tb: [nof_sf][tbs/8] payload bytes (ack: [nof_sf][ack_len] HARQ-ACK values, ri: [nof_sf][ri_len] rank-indication bits,
@@ -483,12 +537,12 @@ class UlTx(Pipeline):
         else:
             _check(L.srslte_hip_ul_tx_batch(*head, *tail), "ul_tx_batch")
         sync()
-        return self.d_iq.to_host(np.complex64).reshape(self.max_batch, self.sf_len)[:n]
+        return self._iq_out(self.max_batch, self.sf_len)[:n]
 
 
 class DlTx(Pipeline):
     """Batched PDSCH transmit chain (srslte_pdsch_encode pdsch.c:1059-1185 + CRS + srslte_ofdm_tx_sf, enb_dl.c)."""
-    DESTROY, DEBUG = "srslte_hip_dl_tx_destroy", "srslte_hip_dl_tx_debug_buffer"
+    DESTROY, DEBUG, IQ_FORMAT = "srslte_hip_dl_tx_destroy", "srslte_hip_dl_tx_debug_buffer", "srslte_hip_dl_tx_set_iq_format"
 
     def __init__(self, cell_id, nof_prb, cfi, rnti, mod, tbs, max_batch, nof_ports=1, p_a=0.0, max_grants=0, cp_ext=False, tdd=None, mbsfn=None):
         self.cfg = DlTxCfg(cell_id, nof_prb, cfi, rnti, mod, tbs, max_batch, nof_ports, p_a, max_grants, 1 if cp_ext else 0,
@@ -499,7 +553,7 @@ class DlTx(Pipeline):
         self.d_iq = DevBuf(8 * self.sf_len * max_batch * self.nof_ports)
 
     def _iq(self, nof_sf):
-        return self.d_iq.to_host(np.complex64).reshape(self.max_batch, self.nof_ports, self.sf_len)[:nof_sf]
+        return self._iq_out(self.max_batch, self.nof_ports, self.sf_len)[:nof_sf]
 
     def _result(self, rc, nof_sf):
         if rc != SRSLTE_SUCCESS:
