@@ -661,6 +661,32 @@ int srslte_hip_ulsch_decode(srslte_hip_sch_t* q, const int16_t* q_bits, const ui
                             uint8_t* cb_crc, uint8_t* cb_bytes, uint32_t* sum_passes, srslte_hip_ulsch_res_t* res);
 /* debugging accessor: the first n LLRs of the last srslte_hip_ulsch_decode's de-interleaved stream g (n <= its nof_bits) to host memory */
 int srslte_hip_ulsch_debug_g(srslte_hip_sch_t* q, int16_t* out, uint32_t n);
+/* One level up: what srslte_pusch_decode does (pusch.c:427-522) from the subframe's grid and channel estimates in HOST memory, in one visit of
+ * the device - the allocation's rows as pusch_cp takes them (pusch.c:53-91), the one-tap MMSE equaliser with noise_estimate as given
+ * (srslte_predecoding_single), the inverse transform precoding over nof_symb symbols of 12 L_prb points, the int16 soft demapper and the
+ * descrambling with the sequence of c_init = (rnti << 14) + (sf_idx << 9) + cell_id made on the device (sequences.c:65-67), then everything
+ * srslte_hip_ulsch_decode does, from the LLRs where the chain left them. sf_symbols / ce: [2 nsl][12 nof_prb] cf32 (nsl 7, or 6 with cp_ext).
+ * Only the allocation's rows cross the link, 2 x nof_re x 8 bytes; bytes, decisions, report and flags come back; nothing else goes up or
+ * down between the steps. Stream waits as srslte_hip_ulsch_decode: one when every block passes. The bits of the sequence that a 1-bit ACK /
+ * RI reads come from the device's own sequence. Refused with SRSLTE_ERROR_INVALID_INPUTS before anything is queued or written: everything
+ * srslte_hip_ulsch_decode refuses for cfg->sch; an L_prb that srslte_hip_dft_precoding_valid_prb rejects; n_prb_tilde[s] + L_prb > nof_prb;
+ * nof_re != 12 L_prb nof_symb; nof_symb != 2 nsl - 2 - shortened; sch.nof_bits != nof_re Qm; 8-bit objects. One receive antenna. */
+typedef struct {
+  srslte_hip_ulsch_cfg_t sch;                     /* everything srslte_hip_ulsch_decode takes (nof_bits = nof_re Qm) */
+  uint32_t nof_prb, cell_id, cp_ext;              /* the cell */
+  uint32_t rnti, sf_idx;                          /* srslte_pusch_cfg_t.rnti, srslte_ul_sf_cfg_t.tti % 10 */
+  uint32_t n_prb_tilde[2];                        /* the PRB offset of each slot (intra-subframe hopping where they differ) */
+  uint32_t shortened;                             /* srslte_ul_sf_cfg_t.shortened: the last symbol is left to the SRS */
+  uint32_t nof_re;                                /* srslte_pusch_grant_t.nof_re */
+} srslte_hip_pusch_cfg_t;
+int srslte_hip_pusch_decode(srslte_hip_sch_t* q, const void* sf_symbols, const void* ce, float noise_estimate, const srslte_hip_pusch_cfg_t* cfg,
+                            int16_t** buffer_f, uint8_t* cb_crc, uint8_t* cb_bytes, uint32_t* sum_passes, srslte_hip_ulsch_res_t* res);
+/* The geometry of that call alone, without a device: the refusals that concern the allocation, and the rows the call stages, in pusch_cp's order.
+ * rows: NULL, or [nof_symb][2] = (symbol of the subframe, first sub-carrier) of each row of 12 L_prb REs. Returns nof_symb, or
+ * SRSLTE_ERROR_INVALID_INPUTS. */
+int srslte_hip_pusch_rows(const srslte_hip_pusch_cfg_t* cfg, uint32_t* rows);
+/* debugging accessor: the first n descrambled LLRs of the last srslte_hip_pusch_decode, in received order (pusch.c:499's q; n <= its nof_bits) */
+int srslte_hip_pusch_debug_q(srslte_hip_sch_t* q, int16_t* out, uint32_t n);
 
 /* ---- the transmit counterpart: encode_tb_off with w_offset = 0 behind srslte_dlsch_encode2 (sch.c:183-289,:549-575) in one device call with
  * one stream wait per transport block: TB CRC24A, segmentation, CB CRC24B, turbo encoding, the circular buffer of every code block as

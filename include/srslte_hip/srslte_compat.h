@@ -14,7 +14,7 @@
  * Not provided (documented in DESIGN.md): interpolate_subframe on a 4-port cell or switched off in an MBSFN subframe; those calls
  * return SRSLTE_ERROR with a message. Of sch.c the library serves all four shared-channel entries, each as one device call per transport
  * block: the DL-SCH in both directions (srslte_dlsch_decode2, srslte_dlsch_encode2) and the UL-SCH with its UCI in both (srslte_ulsch_decode,
- * srslte_ulsch_encode).
+ * srslte_ulsch_encode). One level up, srslte_pusch_decode as one device call per PUSCH: srslte_compat_pusch.h, a header of its own.
  */
 #ifndef SRSLTE_HIP_SRSLTE_COMPAT_H
 #define SRSLTE_HIP_SRSLTE_COMPAT_H

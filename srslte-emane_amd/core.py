@@ -98,6 +98,9 @@ SIGNATURES = {
     "srslte_hip_sch_decode": (None, [vp, vp, u32, u32, cint, u32, u32, u32, vp, vp, vp, vp]),
     "srslte_hip_ulsch_decode": (None, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "srslte_hip_ulsch_debug_g": (None, [vp, vp, u32]),
+    "srslte_hip_pusch_decode": (None, [vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]),
+    "srslte_hip_pusch_rows": (None, [vp, vp]),
+    "srslte_hip_pusch_debug_q": (None, [vp, vp, u32]),
     "srslte_hip_sch_enc_create": (vp, [u32, u32]),
     "srslte_hip_sch_enc_destroy": (void, [vp]),
     "srslte_hip_sch_encode": (None, [vp, vp, u32, cint, u32, u32, u32, vp, vp]),

@@ -4,11 +4,13 @@
 #include "phy_hip_internal.hpp"
 #include "compat_link.hpp" // the thread's stream and pinned arena, DevStage, h2d / d2h / zc_in / zc_out, g_stats
 #include "srslte_hip/srslte_compat.h"
+#include "srslte_hip/srslte_compat_pusch.h"
 #include <math.h>
 #include <memory>
 #include <stdio.h>
 #include <stdlib.h>
 #include <strings.h>
+#include <sys/time.h>
 
 #define ERROR(fmt, ...) hip_log("[srslte_hip] " fmt "\n", ##__VA_ARGS__)
 
@@ -20,6 +22,7 @@ void* tl_stream() { return g_link.stream(); }
 
 std::atomic<unsigned long long> g_stats_ul[2]; // srslte_ulsch_decode calls served, stream waits inside them (srslte_hip_compat_stats_ul)
 std::atomic<unsigned long long> g_stats_ul_tx[2]; // the same for srslte_ulsch_encode (srslte_hip_compat_stats_ul_tx)
+std::atomic<unsigned long long> g_stats_pusch[2]; // the same for srslte_pusch_decode (srslte_hip_compat_stats_pusch)
 void stats_at_exit()
 {
   fprintf(stderr, "[srslte_hip] stats: stream_waits=%llu dlsch_decode2=%llu tdec_single_block_calls=%llu dlsch_encode2=%llu ulsch_decode=%llu ulsch_encode=%llu\n",
@@ -986,6 +989,68 @@ static int ul_cqi_size(const srslte_cqi_cfg_t* c, bool rank_is_not_one)
   return srslte_hip_cqi_size(&h);
 }
 
+// What srslte_ulsch_decode and srslte_pusch_decode share around their device calls. ulsch_prepare: every refusal that is arithmetic on the
+// configuration, and the device call's configuration; nothing is written. tb: the grant's transport block as the call will use it.
+struct UlschCall {
+  srslte_hip_ulsch_cfg_t c;
+  uint32_t               total_ack;
+  bool                   rank_dep;
+  int                    len1;
+};
+static const char* ulsch_prepare(const srslte_sch_t* q, const srslte_pusch_cfg_t* cfg, const srslte_ra_tb_t& tb, const srslte_cbsegm_t& seg, const uint8_t* data,
+                                 const srslte_uci_value_t* uci_data, UlschCall* u)
+{
+  const srslte_softbuffer_rx_t* sb = cfg->softbuffers.rx;
+  const srslte_cqi_cfg_t*       cq = &cfg->uci_cfg.cqi;
+  const uint32_t                Qm = tb.mod == SRSLTE_MOD_QPSK ? 2 : tb.mod == SRSLTE_MOD_16QAM ? 4 : 6;
+  if (q->llr_is_8bit) return "8-bit LLR objects are not served (upstream reads int8 LLRs through an int16_t* here)";
+  if (tb.mod < SRSLTE_MOD_QPSK || tb.mod > SRSLTE_MOD_64QAM) return "modulation outside QPSK..64QAM";
+  if (seg.F || seg.C2) return "transport block with filler bits or two code-block sizes";
+  if (cfg->grant.nof_symb < 9 || cfg->grant.nof_symb > 12 || cfg->grant.L_prb == 0 || tb.nof_bits == 0 || tb.nof_bits % (cfg->grant.nof_symb * Qm))
+    return "nof_bits is no multiple of nof_symb x Qm (or nof_symb outside 9..12, L_prb 0)";
+  if (seg.tbs && (!data || !sb || !sb->buffer_f || !sb->data || !sb->cb_crc || seg.C > sb->max_cb)) return "no data or soft buffer, or a soft buffer of too few blocks";
+  uint32_t total_ack = 0; // srslte_uci_cfg_total_ack
+  for (int i = 0; i < SRSLTE_MAX_CARRIERS; i++) total_ack += cfg->uci_cfg.ack[i].nof_acks;
+  const bool rank_dep = cq->data_enable && cq->type == SRSLTE_CQI_TYPE_SUBBAND_HL && cq->ri_present; // :932-936,:982-986
+  const int  len1 = ul_cqi_size(cq, rank_dep ? false : cq->rank_is_not_one), len2 = rank_dep ? ul_cqi_size(cq, true) : len1;
+  if (cq->ri_len > 2 || len1 < 0 || len1 > SRSLTE_CQI_MAX_BITS || len2 > SRSLTE_CQI_MAX_BITS || (cq->data_enable && len1 == 0) || (!seg.tbs && len1 == 0) ||
+      cfg->uci_offset.I_offset_ack > 15 || cfg->uci_offset.I_offset_ri > 15 || cfg->uci_offset.I_offset_cqi > 15)
+    return "ri_len > 2, a report of 0 or more than 64 bits, no report on a PUSCH without data, or an offset index above 15";
+  if (!q->decoder.dec16_hdlr[0]) return "the srslte_sch_t's decoder is not initialised";
+  srslte_hip_ulsch_cfg_t& c = u->c;
+  memset(&c, 0, sizeof(c));
+  c.mod = (int)tb.mod; c.tbs = seg.tbs; c.rv = (uint32_t)tb.rv; c.nof_bits = tb.nof_bits; c.L_prb = cfg->grant.L_prb; c.nof_symb = cfg->grant.nof_symb;
+  c.max_iterations = q->max_iterations;
+  c.ack_len = total_ack; c.ri_len = cq->ri_len; c.cqi_len = (uint32_t)len1;
+  c.I_offset_ack = cfg->uci_offset.I_offset_ack; c.I_offset_ri = cfg->uci_offset.I_offset_ri; c.I_offset_cqi = cfg->uci_offset.I_offset_cqi;
+  c.cqi_len_rank2 = len2 != len1 ? (uint32_t)len2 : 0;
+  c.cqi_rank2     = uci_data->ri > 0; // ri_len = 0: the caller's value stands (:984)
+  u->total_ack = total_ack; u->rank_dep = rank_dep; u->len1 = len1;
+  return nullptr;
+}
+// ulsch_finish: uci_decode_ri_ack's results (:932-986), the report (:1039-1056), the transport block -> srslte_ulsch_decode's return value
+static int ulsch_finish(srslte_sch_t* q, srslte_pusch_cfg_t* cfg, TdecState* st, const UlschCall& u, const srslte_cbsegm_t& seg, const srslte_hip_ulsch_res_t& res,
+                        uint32_t passes, uint8_t* data, srslte_uci_value_t* uci_data)
+{
+  srslte_cqi_cfg_t* cq = &cfg->uci_cfg.cqi;
+  if (u.rank_dep) cq->rank_is_not_one = false;
+  if (u.total_ack > 0) {
+    uci_data->ack.ack_value[0] = res.ack[0]; // uci.c:782-785
+    if (u.total_ack == 2) uci_data->ack.ack_value[1] = res.ack[1];
+  }
+  if (cq->ri_len > 0) uci_data->ri = res.ri;
+  if (u.rank_dep) cq->rank_is_not_one = uci_data->ri > 0;
+  int ret = (int)res.Q_prime_ri;
+  if (cq->data_enable) { // :1039-1056
+    uci_data->cqi.data_crc = res.cqi_crc != 0;
+    ul_cqi_unpack(cq, res.cqi_bits, &uci_data->cqi);
+    ret = (int)res.Q_prime_cqi;
+  }
+  if (seg.tbs == 0) return ret; // :1061-1065: the last Q' computed, upstream's oddity
+  data[seg.tbs / 8 + 0] = data[seg.tbs / 8 + 1] = data[seg.tbs / 8 + 2] = 0;
+  return tb_finish(q, st, cfg->softbuffers.rx, seg, data, passes);
+}
+
 int srslte_ulsch_decode(srslte_sch_t* q, srslte_pusch_cfg_t* cfg, int16_t* q_bits, int16_t* g_bits, uint8_t* c_seq, uint8_t* data, srslte_uci_value_t* uci_data)
 {
   (void)g_bits; // pusch.c's scratch: never read after the call, not written here
@@ -998,42 +1063,20 @@ int srslte_ulsch_decode(srslte_sch_t* q, srslte_pusch_cfg_t* cfg, int16_t* q_bit
   }
   cfg->K_segm = seg.C1 * seg.K1 + seg.C2 * seg.K2; // :1011
   // ---- refusals, before anything is queued or written
-  srslte_softbuffer_rx_t* sb  = cfg->softbuffers.rx;
-  srslte_cqi_cfg_t*       cq  = &cfg->uci_cfg.cqi;
-  const uint32_t          Qm  = tb.mod == SRSLTE_MOD_QPSK ? 2 : tb.mod == SRSLTE_MOD_16QAM ? 4 : 6;
-  auto*                   st  = (TdecState*)q->decoder.dec16_hdlr[0];
   auto refuse = [](const char* why) {
     ERROR("srslte_ulsch_decode: %s", why);
     return SRSLTE_ERROR_INVALID_INPUTS;
   };
-  if (q->llr_is_8bit) return refuse("8-bit LLR objects are not served (upstream reads int8 LLRs through an int16_t* here)");
-  if (tb.mod < SRSLTE_MOD_QPSK || tb.mod > SRSLTE_MOD_64QAM) return refuse("modulation outside QPSK..64QAM");
-  if (seg.F || seg.C2) return refuse("transport block with filler bits or two code-block sizes");
-  if (cfg->grant.nof_symb < 9 || cfg->grant.nof_symb > 12 || cfg->grant.L_prb == 0 || tb.nof_bits == 0 || tb.nof_bits % (cfg->grant.nof_symb * Qm))
-    return refuse("nof_bits is no multiple of nof_symb x Qm (or nof_symb outside 9..12, L_prb 0)");
-  if (seg.tbs && (!data || !sb || !sb->buffer_f || !sb->data || !sb->cb_crc || seg.C > sb->max_cb)) return refuse("no data or soft buffer, or a soft buffer of too few blocks");
-  uint32_t total_ack = 0; // srslte_uci_cfg_total_ack
-  for (int i = 0; i < SRSLTE_MAX_CARRIERS; i++) total_ack += cfg->uci_cfg.ack[i].nof_acks;
-  const bool rank_dep = cq->data_enable && cq->type == SRSLTE_CQI_TYPE_SUBBAND_HL && cq->ri_present; // :932-936,:982-986
-  const int  len1 = ul_cqi_size(cq, rank_dep ? false : cq->rank_is_not_one), len2 = rank_dep ? ul_cqi_size(cq, true) : len1;
-  if (cq->ri_len > 2 || len1 < 0 || len1 > SRSLTE_CQI_MAX_BITS || len2 > SRSLTE_CQI_MAX_BITS || (cq->data_enable && len1 == 0) || (!seg.tbs && len1 == 0) ||
-      cfg->uci_offset.I_offset_ack > 15 || cfg->uci_offset.I_offset_ri > 15 || cfg->uci_offset.I_offset_cqi > 15)
-    return refuse("ri_len > 2, a report of 0 or more than 64 bits, no report on a PUSCH without data, or an offset index above 15");
-  if (!st) return refuse("the srslte_sch_t's decoder is not initialised");
+  UlschCall u;
+  if (const char* why = ulsch_prepare(q, cfg, tb, seg, data, uci_data, &u)) return refuse(why);
+  auto* st = (TdecState*)q->decoder.dec16_hdlr[0];
   if (!sch_object(st, seg.tbs ? seg.tbs : 40, tb.nof_bits, false)) return SRSLTE_ERROR;
-  srslte_hip_ulsch_cfg_t c;
-  memset(&c, 0, sizeof(c));
-  c.mod = (int)tb.mod; c.tbs = seg.tbs; c.rv = (uint32_t)tb.rv; c.nof_bits = tb.nof_bits; c.L_prb = cfg->grant.L_prb; c.nof_symb = cfg->grant.nof_symb;
-  c.max_iterations = q->max_iterations;
-  c.ack_len = total_ack; c.ri_len = cq->ri_len; c.cqi_len = (uint32_t)len1;
-  c.I_offset_ack = cfg->uci_offset.I_offset_ack; c.I_offset_ri = cfg->uci_offset.I_offset_ri; c.I_offset_cqi = cfg->uci_offset.I_offset_cqi;
-  c.cqi_len_rank2 = len2 != len1 ? (uint32_t)len2 : 0;
-  c.cqi_rank2     = uci_data->ri > 0; // ri_len = 0: the caller's value stands (:984)
-  srslte_hip_ulsch_res_t res;
-  uint32_t               passes = 0;
+  srslte_softbuffer_rx_t* sb = cfg->softbuffers.rx;
+  srslte_hip_ulsch_res_t  res;
+  uint32_t                passes = 0;
   // what the device call itself refuses (a transport block beyond the object, Q' beyond the matrix, a reserved beta): nothing is written yet
   if (seg.tbs) tb_begin(st, sb, seg, nullptr);
-  const int r = srslte_hip_ulsch_decode(st->sch, q_bits, c_seq, &c, seg.tbs ? sb->buffer_f : nullptr, seg.tbs ? st->cb_crc.data() : nullptr,
+  const int r = srslte_hip_ulsch_decode(st->sch, q_bits, c_seq, &u.c, seg.tbs ? sb->buffer_f : nullptr, seg.tbs ? st->cb_crc.data() : nullptr,
                                         seg.tbs ? st->cb_bytes.data() : nullptr, &passes, &res);
   if (r) {
     if (r == SRSLTE_ERROR) ERROR("Error decoding RI/HARQ bits"); // :1015
@@ -1041,23 +1084,77 @@ int srslte_ulsch_decode(srslte_sch_t* q, srslte_pusch_cfg_t* cfg, int16_t* q_bit
   }
   g_stats_ul[0]++;
   g_stats_ul[1] += res.stream_waits;
-  // ---- uci_decode_ri_ack's results (:932-986)
-  if (rank_dep) cq->rank_is_not_one = false;
-  if (total_ack > 0) {
-    uci_data->ack.ack_value[0] = res.ack[0]; // uci.c:782-785
-    if (total_ack == 2) uci_data->ack.ack_value[1] = res.ack[1];
+  return ulsch_finish(q, cfg, st, u, seg, res, passes, data, uci_data);
+}
+
+// ---- srslte_pusch_decode (pusch.c:427-522) as ONE device call (srslte_hip_pusch_decode): the allocation's rows of sf_symbols and channel->ce go up,
+// and what came back from srslte_ulsch_decode's call comes back from this one. Everything a refusal depends on is decided before anything is
+// queued or written - the rewrite of a 64QAM grant (:445-450) and cfg->K_segm included, which are written once the device call has returned.
+int srslte_pusch_decode(srslte_pusch_t* q, srslte_ul_sf_cfg_t* sf, srslte_pusch_cfg_t* cfg, srslte_chest_ul_res_t* channel, cf_t* sf_symbols, srslte_pusch_res_t* out)
+{
+  if (!q || !sf_symbols || !out || !cfg) return SRSLTE_ERROR_INVALID_INPUTS; // :434-437
+  struct timeval t0, t1;
+  if (cfg->meas_time_en) gettimeofday(&t0, nullptr);
+  auto refuse = [](const char* why) {
+    ERROR("srslte_pusch_decode: %s", why);
+    return SRSLTE_ERROR_INVALID_INPUTS;
+  };
+  if (!sf || !channel || !channel->ce) return refuse("no subframe configuration or channel estimates");
+  if (q->llr_is_8bit) return refuse("8-bit LLR objects are not served");
+  srslte_ra_tb_t tb = cfg->grant.tb;
+  if (!cfg->enable_64qam && tb.mod >= SRSLTE_MOD_64QAM) { // :445-450
+    tb.mod      = SRSLTE_MOD_16QAM;
+    tb.nof_bits = cfg->grant.nof_re * 4;
   }
-  if (cq->ri_len > 0) uci_data->ri = res.ri;
-  if (rank_dep) cq->rank_is_not_one = uci_data->ri > 0;
-  int ret = (int)res.Q_prime_ri;
-  if (cq->data_enable) { // :1039-1056
-    uci_data->cqi.data_crc = res.cqi_crc != 0;
-    ul_cqi_unpack(cq, res.cqi_bits, &uci_data->cqi);
-    ret = (int)res.Q_prime_cqi;
+  srslte_cbsegm_t seg;
+  if (srslte_cbsegm(&seg, (uint32_t)tb.tbs)) return refuse("the transport block size has no segmentation");
+  srslte_sch_t* sch = &q->ul_sch;
+  UlschCall     u;
+  if (const char* why = ulsch_prepare(sch, cfg, tb, seg, out->data, &out->uci, &u)) return refuse(why);
+  srslte_hip_pusch_cfg_t pc;
+  memset(&pc, 0, sizeof(pc));
+  pc.sch = u.c;
+  pc.nof_prb = q->cell.nof_prb; pc.cell_id = q->cell.id; pc.cp_ext = q->cell.cp == SRSLTE_CP_EXT;
+  pc.rnti = cfg->rnti; pc.sf_idx = sf->tti % 10;
+  pc.n_prb_tilde[0] = cfg->grant.n_prb_tilde[0]; pc.n_prb_tilde[1] = cfg->grant.n_prb_tilde[1];
+  pc.shortened = sf->shortened; pc.nof_re = cfg->grant.nof_re;
+  if (srslte_hip_pusch_rows(&pc, nullptr) < 0)
+    return refuse("the allocation does not fit: L_prb no product of 2, 3 and 5, n_prb_tilde + L_prb beyond the cell, or nof_re / nof_symb / nof_bits not those of L_prb and the subframe");
+  auto* st = (TdecState*)sch->decoder.dec16_hdlr[0];
+  if (!sch_object(st, seg.tbs ? seg.tbs : 40, tb.nof_bits, false)) return SRSLTE_ERROR;
+  srslte_softbuffer_rx_t* sb = cfg->softbuffers.rx;
+  srslte_hip_ulsch_res_t  res;
+  uint32_t                passes = 0;
+  if (seg.tbs) tb_begin(st, sb, seg, nullptr);
+  const int r = srslte_hip_pusch_decode(st->sch, sf_symbols, channel->ce, channel->noise_estimate, &pc, seg.tbs ? sb->buffer_f : nullptr,
+                                        seg.tbs ? st->cb_crc.data() : nullptr, seg.tbs ? st->cb_bytes.data() : nullptr, &passes, &res);
+  if (r == SRSLTE_ERROR_INVALID_INPUTS) return refuse("not served by the device call");
+  g_stats_pusch[0]++;
+  cfg->grant.tb.mod      = tb.mod;
+  cfg->grant.tb.nof_bits = tb.nof_bits;
+  cfg->K_segm            = seg.C1 * seg.K1 + seg.C2 * seg.K2; // sch.c:1011
+  int ret = SRSLTE_ERROR;
+  if (r) {
+    ERROR("Error decoding RI/HARQ bits"); // sch.c:1015
+  } else {
+    g_stats_pusch[1] += res.stream_waits;
+    ret = ulsch_finish(sch, cfg, st, u, seg, res, passes, out->data, &out->uci);
   }
-  if (seg.tbs == 0) return ret; // :1061-1065: the last Q' computed, upstream's oddity
-  data[seg.tbs / 8 + 0] = data[seg.tbs / 8 + 1] = data[seg.tbs / 8 + 2] = 0;
-  return tb_finish(q, st, sb, seg, data, passes);
+  out->crc                  = ret == 0;                  // :504
+  out->uci.ack.valid        = channel->snr_db > -1.0;    // ACK_SNR_TH, :44,:507
+  out->avg_iterations_block = sch->avg_iterations;
+  cfg->last_O_cqi           = (uint32_t)ul_cqi_size(&cfg->uci_cfg.cqi, cfg->uci_cfg.cqi.rank_is_not_one); // :511
+  if (cfg->meas_time_en) { // :514-518, get_time_interval
+    gettimeofday(&t1, nullptr);
+    long us = t1.tv_usec - t0.tv_usec;
+    if (us < 0) us += 1000000;
+    cfg->meas_time_value = (uint32_t)us;
+  }
+  return SRSLTE_SUCCESS;
+}
+void srslte_hip_compat_stats_pusch(unsigned long long out[2])
+{
+  for (int i = 0; i < 2; i++) out[i] = g_stats_pusch[i].load();
 }
 srslte_hip_sch_t* srslte_hip_compat_sch_of(srslte_sch_t* q)
 {

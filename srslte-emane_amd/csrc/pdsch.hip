@@ -38,6 +38,7 @@
 #include "sch_host.inc"
 #include "pusch_rx.inc"
 #include "ulsch_host.inc" // srslte_ulsch_decode's device call: sch_host.inc's object behind pusch_rx.inc's UCI position arithmetic and CQI decoder
+#include "pusch_host.inc" // srslte_pusch_decode's device call: the allocation's rows through equaliser, transform and demapper into ulsch_host.inc's chain
 #include "pusch_tx.inc"
 #include "sch_enc_host.inc" // the transmit counterpart of sch_host.inc, on the encoder half pusch_tx.inc defines
 #include "ulsch_enc_host.inc" // srslte_ulsch_encode's device call: sch_enc_host.inc's object and chain, pusch_rx.inc's UCI position arithmetic

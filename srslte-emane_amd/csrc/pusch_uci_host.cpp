@@ -63,3 +63,24 @@ extern "C" int srslte_hip_pusch_uci_plan(const srslte_hip_pusch_uci_cfg_t* c, sr
   if (data) r->syms_lo = r->G_prime / c->C, r->C_lo = c->C - r->G_prime % c->C; // gamma = G' mod C (sch.c:205-207)
   return SRSLTE_HIP_PUSCH_UCI_OK;
 }
+
+// The allocation of one PUSCH as pusch_cp walks it (pusch.c:53-91): slot by slot, every symbol but the DMRS (l = 3, or 2 with the extended CP) and,
+// in a shortened subframe, the last one of slot 1; 12 L_prb REs from sub-carrier 12 n_prb_tilde[slot]. What srslte_hip_pusch_decode stages.
+extern "C" int srslte_hip_pusch_rows(const srslte_hip_pusch_cfg_t* c, uint32_t* rows)
+{
+  if (!c || c->sch.mod < 1 || c->sch.mod > 3 || c->shortened > 1 || c->cp_ext > 1 || c->sf_idx > 9 || c->rnti > 0xffff || c->cell_id > 503)
+    return SRSLTE_ERROR_INVALID_INPUTS;
+  const uint32_t nsl = c->cp_ext ? 6 : 7, L = c->sch.L_prb, nsymb = 2 * nsl - 2 - c->shortened;
+  if (!srslte_hip_dft_precoding_valid_prb(L) || c->nof_prb == 0 || c->nof_prb > 110 || c->n_prb_tilde[0] + L > c->nof_prb || c->n_prb_tilde[1] + L > c->nof_prb ||
+      c->sch.nof_symb != nsymb || c->nof_re != 12 * L * nsymb || c->sch.nof_bits != c->nof_re * 2 * (uint32_t)c->sch.mod)
+    return SRSLTE_ERROR_INVALID_INPUTS;
+  uint32_t n = 0;
+  for (uint32_t slot = 0; slot < 2; slot++) {
+    for (uint32_t l = 0; l < nsl - (slot ? c->shortened : 0); l++) {
+      if (l == nsl - 4) continue;
+      if (rows) rows[2 * n] = l + slot * nsl, rows[2 * n + 1] = 12 * c->n_prb_tilde[slot];
+      n++;
+    }
+  }
+  return (int)n;
+}

@@ -18,6 +18,12 @@ struct srslte_hip_sch {
   DevBuf<int>     d_uci_sum;
   PinBuf          h_ul;
   uint32_t        g_len = 0; // LLRs of the last srslte_hip_ulsch_decode in d_e (srslte_hip_ulsch_debug_g)
+  // srslte_hip_pusch_decode (pusch_host.inc), made by its first call: the allocation's rows of grid and estimates (pinned, then device), the
+  // equalised and the de-precoded symbols, and c_seq at the ACK / RI positions from the device's own sequence
+  PinBuf          h_re;
+  DevBuf<cf32>    d_re, d_z, d_d;
+  DevBuf<uint8_t> d_cs;
+  uint32_t        q_len = 0; // LLRs of the last srslte_hip_pusch_decode in d_q (srslte_hip_pusch_debug_q)
   ~srslte_hip_sch()
   {
     if (st) (void)hipStreamSynchronize(st); // a decode that returned early may have left copies queued: they end before the buffers go

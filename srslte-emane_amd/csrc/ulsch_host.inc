@@ -106,18 +106,23 @@ int ulsch_init(srslte_hip_sch* q)
 
 } // namespace
 
-// q_bits: cfg->nof_bits descrambled LLRs as pusch.c:499 leaves them; c_seq: the scrambling sequence, one bit per byte (read at the ACK / RI
-// positions of a 1-bit ACK / RI only). buffer_f / cb_crc / cb_bytes / sum_passes as srslte_hip_sch_decode takes them (unused with tbs = 0).
-// Everything is checked before anything is queued.
-extern "C" int srslte_hip_ulsch_decode(srslte_hip_sch_t* q, const int16_t* q_bits, const uint8_t* c_seq, const srslte_hip_ulsch_cfg_t* c, int16_t** buffer_f,
-                                       uint8_t* cb_crc, uint8_t* cb_bytes, uint32_t* sum_passes, srslte_hip_ulsch_res_t* res)
+// What both UL entries - srslte_hip_ulsch_decode here, srslte_hip_pusch_decode in pusch_host.inc - share: the plan (every check, nothing queued) and
+// everything behind the upload of the LLRs (ulsch_run).
+struct UlschPlan {
+  uint32_t            Qm, nsymb, rows, H; // the channel interleaver's matrix: rows x nsymb entries of Qm LLRs
+  uint32_t            Qp_ack, Qp_ri, Qc[2], len2; // Q'_cqi and the report's size for rank 1 / above (equal where the size does not depend on it)
+  srslte_hip_cbsegm_t seg;
+};
+
+// Everything is checked before anything is queued. SRSLTE_ERROR for a reserved beta offset (with upstream's message), else SRSLTE_ERROR_INVALID_INPUTS.
+static int ulsch_plan(srslte_hip_sch_t* q, const srslte_hip_ulsch_cfg_t* c, int16_t** buffer_f, const uint8_t* cb_crc, const uint8_t* cb_bytes, UlschPlan* p)
 {
-  if (!q || !q_bits || !c_seq || !c || !res || q->l8 || c->mod < 1 || c->mod > 3) return SRSLTE_ERROR_INVALID_INPUTS;
+  if (!q || !c || q->l8 || c->mod < 1 || c->mod > 3) return SRSLTE_ERROR_INVALID_INPUTS;
   const uint32_t Qm = 2 * (uint32_t)c->mod, nsymb = c->nof_symb;
   if (nsymb < 9 || nsymb > 12 || c->L_prb == 0 || c->nof_bits == 0 || c->nof_bits > q->max_e || c->nof_bits % (nsymb * Qm) || c->ri_len > 2 || c->cqi_len > 64 ||
       c->cqi_len_rank2 > 64 || c->I_offset_ack > 15 || c->I_offset_ri > 15 || c->I_offset_cqi > 15)
     return SRSLTE_ERROR_INVALID_INPUTS;
-  srslte_hip_cbsegm_t seg;
+  srslte_hip_cbsegm_t& seg = p->seg;
   memset(&seg, 0, sizeof(seg));
   if (c->tbs) {
     if (!buffer_f || !cb_crc || !cb_bytes || c->max_iterations == 0 || c->rv > 3 || c->tbs > q->max_tbs || srslte_hip_cbsegm(&seg, c->tbs) || seg.F || seg.C2 ||
@@ -136,41 +141,37 @@ extern "C" int srslte_hip_ulsch_decode(srslte_hip_sch_t* q, const int16_t* q_bit
   }
   if (why == SRSLTE_HIP_PUSCH_UCI_EMPTY) hip_log("[srslte_hip] ulsch: a PUSCH without UL-SCH data carries a CQI report (36.212 5.2.4)\n");
   if (why) return SRSLTE_ERROR_INVALID_INPUTS;
-  const uint32_t Qp_ack = pl.Qp_ack, Qp_ri = pl.Qp_ri;
   // the report's size may depend on the rank (cqi_len_rank2): both hypotheses are sized before anything runs, each leaving every code block a symbol
-  const uint32_t len2 = cqi && c->cqi_len_rank2 ? c->cqi_len_rank2 : c->cqi_len;
-  const uint32_t Qc[2] = {pl.Qp_cqi, pusch_uci_cqi_qprime(&uc, len2, Qp_ri)};
+  p->len2  = cqi && c->cqi_len_rank2 ? c->cqi_len_rank2 : c->cqi_len;
+  p->Qc[0] = pl.Qp_cqi;
+  p->Qc[1] = pusch_uci_cqi_qprime(&uc, p->len2, pl.Qp_ri);
   for (int k = 0; k < 2; k++) {
-    if (Qp_ri + Qc[k] > H || (c->tbs && H - Qp_ri - Qc[k] < seg.C)) return SRSLTE_ERROR_INVALID_INPUTS;
+    if (pl.Qp_ri + p->Qc[k] > H || (c->tbs && H - pl.Qp_ri - p->Qc[k] < seg.C)) return SRSLTE_ERROR_INVALID_INPUTS;
   }
-  if (ulsch_init(q)) return SRSLTE_ERROR;
-  hipStream_t st = q->st;
-  uint8_t *   h_dec = q->h_ul, *h_cqi = q->h_ul + UL_O_CQI, *h_crc = q->h_ul + UL_O_CRC, *h_cs = q->h_ul + UL_O_CS;
-  // ---- up: the LLRs, and c_seq where a 1-bit ACK / RI reads it (p0 and p1 of every symbol, uci.c:627-640)
-  for (int w = 0; w < 2; w++) {
-    const uint32_t Qp = w ? Qp_ri : Qp_ack, O = w ? c->ri_len : c->ack_len;
-    uint8_t*       cs = h_cs + (w ? 2 * Qp_ack : 0);
-    for (uint32_t i = 0; i < Qp; i++) {
-      uint32_t row, col;
-      pusch_uci_symbol_pos(w != 0, i, rows, nsymb, &row, &col);
-      const uint32_t p0 = (col * rows + row) * Qm;
-      cs[2 * i]     = O == 1 ? c_seq[p0] : 0;
-      cs[2 * i + 1] = O == 1 ? c_seq[p0 + 1] : 0;
-    }
-  }
+  p->Qm = Qm; p->nsymb = nsymb; p->rows = rows; p->H = H; p->Qp_ack = pl.Qp_ack; p->Qp_ri = pl.Qp_ri;
+  return SRSLTE_SUCCESS;
+}
+
+// From the LLRs the stream has been told to leave in q->d_q: decisions, de-interleaver, report, transport block, results down.
+// cs: [Q'_ack][2] then [Q'_ri][2] bits of c_seq at p0 / p1 of each ACK / RI symbol, where the kernels can read them (1-bit cases only)
+static int ulsch_run(srslte_hip_sch_t* q, const srslte_hip_ulsch_cfg_t* c, const UlschPlan& p, const uint8_t* cs, int16_t** buffer_f, uint8_t* cb_crc,
+                     uint8_t* cb_bytes, uint32_t* sum_passes, srslte_hip_ulsch_res_t* res)
+{
+  const uint32_t Qm = p.Qm, H = p.H, Qp_ack = p.Qp_ack, Qp_ri = p.Qp_ri, len2 = p.len2;
+  const bool     cqi = c->cqi_len > 0;
+  hipStream_t    st = q->st;
+  uint8_t *      h_dec = q->h_ul, *h_cqi = q->h_ul + UL_O_CQI, *h_crc = q->h_ul + UL_O_CRC;
   memset(h_dec, 0, 4);
   memset(h_cqi, 0, 64); // uci.c / sch.c:1042: the report starts as zeros and a failed CRC leaves it so
   *h_crc = 0;
-  memcpy(q->h_pin, q_bits, (size_t)c->nof_bits * 2);
-  HIP_TRY(hipMemcpyAsync(q->d_q.get(), q->h_pin, (size_t)c->nof_bits * 2, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemsetAsync(q->d_uci_sum.get(), 0, sizeof(int) * 8, st));
   UlschGeom u;
-  u.rows = (int)rows; u.cols = (int)nsymb; u.Qm = (int)Qm;
+  u.rows = (int)p.rows; u.cols = (int)p.nsymb; u.Qm = (int)Qm;
   u.ack = AckGeom{(int)c->ack_len, (int)Qp_ack};
   u.ri  = AckGeom{(int)c->ri_len, (int)Qp_ri};
   u.ri_imax = Qp_ri >= 2 ? 1 : 0;
   int16_t* d_g = q->gs.d_e;
-  hipLaunchKernelGGL(ulsch_deint_kernel, dim3(ceil_div((int)H, 256)), dim3(256), 0, st, (const int16_t*)q->d_q, (const uint8_t*)h_cs, d_g, q->d_uci_sum.get(), u);
+  hipLaunchKernelGGL(ulsch_deint_kernel, dim3(ceil_div((int)H, 256)), dim3(256), 0, st, (const int16_t*)q->d_q, cs, d_g, q->d_uci_sum.get(), u);
   LAUNCH_CHECK();
   q->g_len = c->nof_bits;
   uint32_t waits = 0;
@@ -180,7 +181,7 @@ extern "C" int srslte_hip_ulsch_decode(srslte_hip_sch_t* q, const int16_t* q_bit
   }
   // ---- the report in front of the UL-SCH (sch.c:1036-1056)
   uint32_t cqi_len = c->cqi_len;
-  int      Qp_cqi  = Qc[0];
+  int      Qp_cqi  = p.Qc[0];
   if (len2 != c->cqi_len) {
     bool rank2 = c->cqi_rank2 != 0;
     if (c->ri_len) { // sch.c:982-986: the rank just decoded sizes the report; the one case in which the call waits for its own first half
@@ -188,7 +189,7 @@ extern "C" int srslte_hip_ulsch_decode(srslte_hip_sch_t* q, const int16_t* q_bit
       waits++;
       rank2 = h_dec[2] > 0;
     }
-    if (rank2) cqi_len = len2, Qp_cqi = Qc[1];
+    if (rank2) cqi_len = len2, Qp_cqi = p.Qc[1];
   }
   if (cqi) {
     hipLaunchKernelGGL(pusch_cqi_decode_kernel, dim3(1), dim3(256), 0, st, (const int16_t*)d_g, 0, Qp_cqi * (int)Qm, (int)cqi_len, h_cqi, h_crc,
@@ -216,6 +217,33 @@ extern "C" int srslte_hip_ulsch_decode(srslte_hip_sch_t* q, const int16_t* q_bit
   res->Q_prime_ack = Qp_ack; res->Q_prime_ri = Qp_ri; res->Q_prime_cqi = cqi ? (uint32_t)Qp_cqi : 0;
   res->stream_waits = waits;
   return SRSLTE_SUCCESS;
+}
+
+// q_bits: cfg->nof_bits descrambled LLRs as pusch.c:499 leaves them; c_seq: the scrambling sequence, one bit per byte (read at the ACK / RI
+// positions of a 1-bit ACK / RI only). buffer_f / cb_crc / cb_bytes / sum_passes as srslte_hip_sch_decode takes them (unused with tbs = 0).
+extern "C" int srslte_hip_ulsch_decode(srslte_hip_sch_t* q, const int16_t* q_bits, const uint8_t* c_seq, const srslte_hip_ulsch_cfg_t* c, int16_t** buffer_f,
+                                       uint8_t* cb_crc, uint8_t* cb_bytes, uint32_t* sum_passes, srslte_hip_ulsch_res_t* res)
+{
+  if (!q_bits || !c_seq || !res) return SRSLTE_ERROR_INVALID_INPUTS;
+  UlschPlan p;
+  if (int r = ulsch_plan(q, c, buffer_f, cb_crc, cb_bytes, &p)) return r;
+  if (ulsch_init(q)) return SRSLTE_ERROR;
+  uint8_t* h_cs = q->h_ul + UL_O_CS;
+  // ---- up: the LLRs, and c_seq where a 1-bit ACK / RI reads it (p0 and p1 of every symbol, uci.c:627-640)
+  for (int w = 0; w < 2; w++) {
+    const uint32_t Qp = w ? p.Qp_ri : p.Qp_ack, O = w ? c->ri_len : c->ack_len;
+    uint8_t*       cs = h_cs + (w ? 2 * p.Qp_ack : 0);
+    for (uint32_t i = 0; i < Qp; i++) {
+      uint32_t row, col;
+      pusch_uci_symbol_pos(w != 0, i, p.rows, p.nsymb, &row, &col);
+      const uint32_t p0 = (col * p.rows + row) * p.Qm;
+      cs[2 * i]     = O == 1 ? c_seq[p0] : 0;
+      cs[2 * i + 1] = O == 1 ? c_seq[p0 + 1] : 0;
+    }
+  }
+  memcpy(q->h_pin, q_bits, (size_t)c->nof_bits * 2);
+  HIP_TRY(hipMemcpyAsync(q->d_q.get(), q->h_pin, (size_t)c->nof_bits * 2, hipMemcpyHostToDevice, q->st));
+  return ulsch_run(q, c, p, h_cs, buffer_f, cb_crc, cb_bytes, sum_passes, res);
 }
 
 extern "C" int srslte_hip_ulsch_debug_g(srslte_hip_sch_t* q, int16_t* out, uint32_t n)
