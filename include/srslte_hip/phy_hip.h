@@ -1193,7 +1193,8 @@ int srslte_hip_ul_ctrl_tx_put_pucch(srslte_hip_ul_ctrl_tx_t* q, uint32_t tti0, u
 /* host helpers (no device needed), for a configuration given as srslte_hip_ul_ctrl_cfg_t (max_pucch not looked at):
  * srslte_pucch_n_cs_cell into n_cs_cell [20][7]; the resource selection of a request (uci: NULL = the receiver's zero value, else the
  * transmitter's values) into res = {format, n_pucch, n_prb slot 0, n_prb slot 1}; the DMRS of srslte_refsignal_dmrs_pucch_gen for (format,
- * n_pucch, TTI, 2a / 2b bits) into r [2][N_rs][12] cf32, returning 12 N_rs per slot. < 0: invalid input. */
+ * n_pucch, TTI, 2a / 2b bits) into r [2][N_rs][12] cf32, returning 12 N_rs per slot. < 0: invalid input; for the resource selection also a
+ * request no format fits, or whose n_pucch puts a slot outside the band (what put_pucch and pucch_batch refuse). */
 int srslte_hip_pucch_n_cs_cell(const srslte_hip_ul_ctrl_cfg_t* cfg, uint32_t* n_cs_cell);
 int srslte_hip_pucch_resource(const srslte_hip_ul_ctrl_cfg_t* cfg, const srslte_hip_pucch_tx_t* uci, const srslte_hip_pucch_req_t* req, uint32_t* res);
 int srslte_hip_pucch_dmrs(const srslte_hip_ul_ctrl_cfg_t* cfg, uint32_t format, uint32_t n_pucch, uint32_t tti, const uint8_t* drs_bits, void* r);

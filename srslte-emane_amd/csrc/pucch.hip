@@ -725,7 +725,8 @@ int srslte_hip_pucch_resource(const srslte_hip_ul_ctrl_cfg_t* cfg, const srslte_
   if (!cfg_ok(cfg) || !req || !res || !req_ok(*req, 0xffffffffu)) return SRSLTE_ERROR_INVALID_INPUTS;
   int      f;
   uint32_t n;
-  if (!select_res(cfg, *req, uci, req->sr_tti, &f, &n)) return SRSLTE_ERROR_INVALID_INPUTS;
+  // a resource outside the band is refused as put_pucch and pucch_batch refuse it, not answered with a wrapped nof_prb - 1 - m / 2
+  if (!select_res(cfg, *req, uci, req->sr_tti, &f, &n) || !in_band(cfg, f, n)) return SRSLTE_ERROR_INVALID_INPUTS;
   res[0] = (uint32_t)f, res[1] = n;
   for (uint32_t s = 0; s < 2; s++) res[2 + s] = pucch_n_prb(f, n, s, cfg->nof_prb, cfg->delta_pucch_shift, cfg->N_cs, cfg->n_rb_2, cfg->cp_ext);
   return SRSLTE_SUCCESS;

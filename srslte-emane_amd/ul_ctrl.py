@@ -168,7 +168,8 @@ def pucch_n_cs_cell(cfg):
 
 
 def pucch_resource(cfg, req, uci=None):
-    """srslte_ue_ul_pucch_resource_selection -> (format, n_pucch, n_prb slot 0, n_prb slot 1), or None where no format fits (host).
+    """srslte_ue_ul_pucch_resource_selection -> (format, n_pucch, n_prb slot 0, n_prb slot 1), or None where no format fits or the
+    resource lies outside the band (host).
     uci: None for the receiver's zero value, else a PucchTx whose UCI values count."""
     out = np.zeros(4, np.uint32)
     rc = lib().srslte_hip_pucch_resource(C.byref(cfg), C.byref(uci) if uci is not None else None, C.byref(req), out.ctypes.data)

@@ -1,4 +1,5 @@
-"""Reference side of the PUCCH tests (tests/test_ul_ctrl_host.py, tests/test_gpu_ul_ctrl.py) and of scripts/bench_ul_ctrl.py.
+"""Reference side of the PUCCH tests (tests/test_ul_ctrl_host.py, tests/test_gpu_ul_ctrl.py, tests/test_pucch_golden.py,
+tests/test_gpu_pucch_sweep.py) and of scripts/bench_ul_ctrl.py.
 
 srslte_pucch_* / srslte_ue_ul_* / srslte_enb_ul_* and srslte_refsignal_dmrs_pucch_* are not exported from oracle/_ref/libsrslte_ref.so, so the
 chain of srslte_enb_ul_get_pucch (enb_ul.c:175-228) is assembled from what is: srslte_refsignal_ul_set_cell (n_cs_cell and f_gh read through a
@@ -6,7 +7,9 @@ mirror of srslte_refsignal_ul_t), srslte_refsignal_r_uv_arg_1prb, srslte_chest_u
 srslte_refsignal_dmrs_pucch_gen / _get, srslte_pucch_alpha_format1 / 2, srslte_pucch_n_prb and the 2a / 2b hypotheses), srslte_predecoding_single,
 srslte_vec_corr_ccc, srslte_demod_soft_demodulate_s, srslte_sequence_pucch, srslte_scrambling_s_offset, srslte_uci_encode_cqi_pucch and
 srslte_uci_decode_cqi_pucch. Restated in numpy, each with its lines: encode_signal_format12 (pucch.c:429-492), pucch_cp (:380-417), the DMRS of
-srslte_refsignal_dmrs_pucch_gen / _put (refsignal_ul.c:558-680), get_format (ue_ul.c:482-531) and get_npucch (:823-900). Test infrastructure only."""
+srslte_refsignal_dmrs_pucch_gen / _put (refsignal_ul.c:558-680), get_format (ue_ul.c:482-531) and get_npucch (:823-900). encode_z and the
+format-2 means of _attempt follow the float operations of the reference's release build, and tests/test_pucch_golden.py holds all of it to
+tests/golden/pucch.npz, recorded from the reference's own srslte_pucch_encode / srslte_pucch_decode. Test infrastructure only."""
 import ctypes as C
 
 import numpy as np
@@ -33,6 +36,25 @@ W_DMRS1E = np.array([[0, 0], [0, np.pi], [0, 0]], np.float32)  # :50-52
 Z2AB = {(0, 0): 1, (0, 1): -1j, (1, 0): 1j, (1, 1): -1}  # srslte_pucch_format2ab_mod_bits (pucch.c:1061-1088) for 2b; 2a: bit 0 -> +-1
 
 
+def _fma32(a, b, c):
+    """float fma(a, b, c) element-wise: the product of two floats is exact in float64; its sum with c is rounded there once before the
+    rounding to float, which moves the result only where that sum lies within 2^-29 ulp of a tie."""
+    return (np.asarray(a, np.float32).astype(np.float64) * np.float64(np.float32(b)) + np.asarray(c, np.float32).astype(np.float64)).astype(np.float32)
+
+
+_libm = C.CDLL("libm.so.6")
+_libm.sincosf.restype, _libm.sincosf.argtypes = None, [C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+
+
+def _sincosf(x):
+    """(cos, sin) float32 of glibc's sincosf, which the reference's cexpf(I x) is compiled to."""
+    out, s, c = np.empty((2, x.size), np.float32), C.c_float(), C.c_float()
+    for i, v in enumerate(np.asarray(x, np.float32).tolist()):
+        _libm.sincosf(v, C.byref(s), C.byref(c))
+        out[0, i], out[1, i] = c.value, s.value
+    return out[0], out[1]
+
+
 def n_rs(fmt, ext):  # srslte_refsignal_dmrs_N_rs (refsignal_ul.c:489-514)
     return (2 if ext else 3) if fmt < F2 else ((1 if ext else 2) if fmt == F2 else 2)
 
@@ -53,6 +75,7 @@ def _R():
     R.srslte_chest_ul_estimate_pucch.argtypes = [vp, vp, vp, vp, vp]
     R.srslte_vec_corr_ccc.restype = C.c_float
     R.srslte_vec_corr_ccc.argtypes = [vp, vp, C.c_uint32]
+    R.srslte_vec_prod_conj_ccc.argtypes = [vp, vp, vp, C.c_int]
     R.srslte_demod_soft_demodulate_s.argtypes = [C.c_int, vp, vp, C.c_int]
     R.srslte_sequence_pucch.argtypes = [vp, C.c_uint16, C.c_uint32, C.c_uint32]
     R.srslte_scrambling_s_offset.argtypes = [vp, vp, C.c_int, C.c_int]
@@ -208,7 +231,10 @@ class RefUlCtrl:
         return np.array(out, np.int64)
 
     def encode_z(self, fmt, n_pucch, tti, shortened, d):
-        """encode_signal_format12 (pucch.c:429-492): d = d(0) for 1/1a/1b, the 10 QPSK symbols (or ones) for 2/2a/2b -> z complex64."""
+        """encode_signal_format12 (pucch.c:429-492): d = d(0) for 1/1a/1b, the 10 QPSK symbols (or ones) for 2/2a/2b -> z complex64. In the
+        order of the reference's release build (-Ofast -mfma), read from its object code: the phase is fma(n, alpha, tmp_arg[n]) for formats
+        2-2b and (w + tmp_arg[n]) + fma(n, alpha, S_ns) for 1-1b, cexpf is glibc's sincosf, and d (c + j s) is
+        (fma(-s, Im d, Re d c), fma(c, Im d, Re d s)), which is exact for the unit values of d(0)."""
         c, sf_idx, n = self.cfg, tti % 10, np.arange(12, dtype=np.float32)
         d = np.atleast_1d(np.asarray(d, np.complex64))
         z = []
@@ -218,12 +244,14 @@ class RefUlCtrl:
             for m in range(Nsf):
                 l = data_sym(fmt, m, self.ext)
                 if fmt >= F2:
-                    ph = self.arg[ns] + ALPHA[alpha2(self.n_cs_cell, c.N_cs, c.n_rb_2, n_pucch, ns, l)] * n
-                    z.append(d[s * 5 + m] * np.exp(1j * ph.astype(np.float64)).astype(np.complex64))
+                    co, si = _sincosf(_fma32(n, ALPHA[alpha2(self.n_cs_cell, c.N_cs, c.n_rb_2, n_pucch, ns, l)], self.arg[ns]))
+                    a, b = d[s * 5 + m].real, d[s * 5 + m].imag
+                    z.append((_fma32(-si, b, a * co) + 1j * _fma32(co, b, a * si)).astype(np.complex64))
                 else:
                     n_cs, n_oc, npr = alpha1(self.n_cs_cell, self.ext, c.delta_pucch_shift, c.N_cs, n_pucch, ns, l)
-                    ph = ((W_N_OC[1 if Nsf == 3 else 0][n_oc % 3][m] + self.arg[ns]) + ALPHA[n_cs] * n) + (S_NS if npr % 2 else np.float32(0))
-                    z.append(d[0] * np.exp(1j * ph.astype(np.float64)).astype(np.complex64))
+                    ph = (W_N_OC[1 if Nsf == 3 else 0][n_oc % 3][m] + self.arg[ns]) + _fma32(n, ALPHA[n_cs], S_NS if npr % 2 else np.float32(0))
+                    co, si = _sincosf(ph)
+                    z.append(d[0] * (co + 1j * si).astype(np.complex64))
         return np.concatenate(z).astype(np.complex64)
 
     def coded_bits(self, bits, length):
@@ -309,23 +337,31 @@ class RefUlCtrl:
         if fmt < F2:
             hyps = [((0, 0), 1)] if fmt == F1 else ([((b, 0), [1, -1][b]) for b in range(2)] if fmt == F1A else
                                                    [((b, b2), {(0, 0): 1, (0, 1): -1j, (1, 0): 1j, (1, 1): -1}[(b, b2)]) for b in range(2) for b2 in range(2)])
-            corrs = []
+            corrs, base = [], self.encode_z(fmt, n_pucch, tti, q.shortened, 1)
             for bits, d in hyps:
                 e = aligned(nre, np.complex64)
-                e[:] = self.encode_z(fmt, n_pucch, tti, q.shortened, d)
+                e[:] = np.complex64(d) * base  # exact for the unit values of d(0)
                 corrs.append(R.srslte_vec_corr_ccc(z.ctypes.data, e.ctypes.data, nre))
             k = int(np.argmax(corrs))  # the first maximum (decode_signal's >)
             out["corr"], out["bits"], out["hyp"] = np.float32(corrs[k]), hyps[k][0], corrs
             out["detected"] = corrs[0] >= c.threshold_format1 if fmt == F1 else corrs[k] > c.threshold_format1
             return out
-        ref = self.encode_z(fmt, n_pucch, tti, q.shortened, np.ones(10, np.complex64))
-        zz = (z * np.conj(ref)).astype(np.complex64)
+        # decode_signal (pucch.c:683-690) as the reference's release build runs it: srslte_vec_prod_conj_ccc over the 128 symbols, then each
+        # 12-RE mean as z[0] r, fma(z[j], r, acc) for j = 1..11 with r = float(1 / 12) (-Ofast turns the division by SRSLTE_NRE into a
+        # product with the reciprocal and contracts it with the sum). A noise-free QPSK symbol sits on a step of the int16 LLR (100), so
+        # the order decides 99 or 100. The fma is taken in float64, where the product is exact.
+        ref, zin, zz = aligned(128, np.complex64), aligned(128, np.complex64), aligned(128, np.complex64)
+        ref[:nre], zin[:nre] = self.encode_z(fmt, n_pucch, tti, q.shortened, np.ones(10, np.complex64)), z
+        R.srslte_vec_prod_conj_ccc(zin.ctypes.data, ref.ctypes.data, zz.ctypes.data, 128)
+        r12 = np.float64(np.float32(1) / np.float32(12))
+        zf = zz.view(np.float32).reshape(128, 2)
         z2 = aligned(10, np.complex64)
+        z2f = z2.view(np.float32).reshape(10, 2)
         for i in range(10):
-            acc = np.complex64(0)
-            for j in range(12):
-                acc = np.complex64(acc + zz[12 * i + j] / np.float32(12))
-            z2[i] = acc
+            acc = zf[12 * i] * np.float32(r12)
+            for j in range(1, 12):
+                acc = (zf[12 * i + j].astype(np.float64) * r12 + acc.astype(np.float64)).astype(np.float32)
+            z2f[i] = acc
         llr = aligned(20, np.int16)
         R.srslte_demod_soft_demodulate_s(QPSK, z2.ctypes.data, llr.ctypes.data, 10)
         assert R.srslte_sequence_pucch(self.seq, q.rnti, 2 * (tti % 10), self.cell_id) == 0
